@@ -26,6 +26,12 @@ value     = frames/s over all ranks (weak scaling: every rank runs its own batch
 roofline  = FAST+NMS kernel (the dominant HBM consumer named by north_star): algorithmic bytes P per image
              / kernel time from HIP events on the library's stream.
 cpu_baseline = the ORACLE restatement of the SAME composite (oracle/chain.py + oracle LocalBA, C, 1 core) on a bounded sample.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, ms_per_step, dtype, config).  Everything else -- the parity check of the last timed step against the oracle (`parity_checked`),
+`cpu_baseline`, `stage_ms`, `roofline*`, `exchange` and the `extra` rows, which take runs of their own -- comes with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed sample of the rows of
+the larger outputs), so that two builds can be compared output for output on the same generated inputs.
 """
 import argparse
 import json
@@ -41,6 +47,65 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+DUMP_ROWS = 64             # --dump-outputs keeps at most this many rows (frames, keyframe pairs, LocalBA windows) of an output
+DUMP_LIMIT = 64 << 20      # bytes of all the files of one --dump-outputs
+
+
+def dump_rows(n):
+    """the rows --dump-outputs keeps of an output with n rows: all of them, or a fixed seeded sample of DUMP_ROWS"""
+    if n <= DUMP_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(n).choice(n, DUMP_ROWS, replace=False))
+
+
+def keypoint_table(kps, n, KP_DTYPE):
+    """[B][cap][7] float32 keypoint records (octave / class_id are int32 bit patterns) -> [B][cap][7] float64, zero past n[b]"""
+    B, cap = kps.shape[:2]
+    rec = np.ascontiguousarray(kps).view(np.uint8).reshape(B, cap, KP_DTYPE.itemsize).copy().view(KP_DTYPE).reshape(B, cap)
+    out = np.stack([rec[f].astype(np.float64) for f in KP_DTYPE.names], axis=-1)
+    return per_keypoint(out, n)
+
+
+def per_keypoint(a, n):
+    """a [B][cap]... with the entries past n[b] (not written by the step) set to 0"""
+    a = np.array(a)
+    a[np.arange(a.shape[1])[None, :] >= np.asarray(n).reshape(-1, 1)] = 0
+    return a
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 when that holds it exactly (float32, 8- / 16-bit integers), else float64"""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = a.dtype == np.float32 or (a.dtype.kind in "iub" and a.dtype.itemsize <= 2)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def synth_lba_windows(mix):
+    """synth.synth_lba_problems(mix), the job of main()'s helper process"""
+    import __graft_entry__ as g
+    return g.load_package().synth.synth_lba_problems(mix)
+
+
+def chain_outputs(pkg, p):
+    """what TrackingChain.step() left for its batch: the Frame members a caller reads (keypoints, descriptors, mvuRight / mvDepth,
+    mvpMapPoints, mvbOutlier of a fixed sample of frames; N, mTcw and the match / inlier counts of every frame)"""
+    F = pkg.capi.Frames
+    n = p.d_n.cpu().numpy()
+    fr = dump_rows(p.B)
+    return {"frame_n": n, "frame_Tcw": p.cur.get(F.TCW), "frame_match_counts": p.d_nm.cpu().numpy(), "frame_sample": fr,
+            "frame_keypoints": keypoint_table(p.d_kps.cpu().numpy()[fr], n[fr], pkg.capi.KP_DTYPE),
+            "frame_descriptors": per_keypoint(p.d_desc.cpu().numpy()[fr], n[fr]),
+            "frame_u_right": per_keypoint(p.cur.get(F.U_RIGHT)[fr], n[fr]), "frame_depth": per_keypoint(p.cur.get(F.DEPTH)[fr], n[fr]),
+            "frame_map_points": per_keypoint(p.cur.get(F.MAP_POINTS)[fr], n[fr]), "frame_outlier": per_keypoint(p.cur.get(F.OUTLIER)[fr], n[fr])}
 
 
 def run_euroc8(args, pkg, torch, dist, rank, world, local_rank, dev, cdev, backend, dist_on):
@@ -117,10 +182,16 @@ def run_euroc8(args, pkg, torch, dist, rank, world, local_rank, dev, cdev, backe
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:   # rank 0's frames of the last timed step: both eyes' keypoints / descriptors, mvuRight / mvDepth
+        hl, hr = ln.cpu().numpy(), rn.cpu().numpy()
+        dump_outputs(args.dump_outputs, {
+            "left_n": hl, "left_keypoints": keypoint_table(lk.cpu().numpy(), hl, pkg.capi.KP_DTYPE), "left_descriptors": per_keypoint(ld.cpu().numpy(), hl),
+            "right_n": hr, "right_keypoints": keypoint_table(rk.cpu().numpy(), hr, pkg.capi.KP_DTYPE), "right_descriptors": per_keypoint(rd.cpu().numpy(), hr),
+            "u_right": per_keypoint(ur.cpu().numpy(), hl), "depth": per_keypoint(dp.cpu().numpy(), hl)})
     # ---- parity of the LAST timed step (oracle imported only here): every rank checks its own frames' left keypoints /
     # descriptors and mvuRight / mvDepth, rank 0 also the slots it gathered from every rank, all against the oracle
     parity_checked = None
-    if args.verify is None or args.verify:
+    if args.verify:
         import __graft_entry__ as g
         g.load_oracle()
         import parity
@@ -152,7 +223,7 @@ def run_euroc8(args, pkg, torch, dist, rank, world, local_rank, dev, cdev, backe
                           "against": "oracle (C restatement; parity unpinned by the reference)", "mismatches_rank0": bad[:10]}
     if rank == 0:
         ok = None
-        if dist_on:
+        if dist_on and args.full:
             hdr = torch.stack([b_[:, :4].contiguous().cpu().view(torch.int32).reshape(-1) for b_ in bufs[(args.steps - 1) % 2]])
             ok = bool(((hdr > 0) & (hdr <= cap)).all())
         print(json.dumps({"parity_checked": parity_checked, 
@@ -194,10 +265,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the untimed `extra` rows (matcher / BA / stereo / vocabulary): used for the rocprofv3 summaries, whose per-kernel averages should cover the timed workload only")
     ap.add_argument("--verify", dest="verify", action="store_true", default=None,
-                    help="after the timed region, check results of the LAST timed step against the oracle and report them as "
-                         "`parity_checked` (default: on, rank 0, at every N")
+                    help="with --full: after the timed region, check results of the LAST timed step against the oracle and report them as "
+                         "`parity_checked` (default with --full: on, rank 0, at every N")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the parity check against the oracle, cpu_baseline, stage_ms, roofline, exchange and the "
+                         "extra rows (other forms of the step, other calls and sizes); without it the run prints the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.verify and not args.full:
+        ap.error("--verify checks the last timed step as part of --full")
+    args.verify = args.full and args.verify is not False
 
     # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, torch.distributed.run on
     # 127.0.0.1); under a launcher (WORLD_SIZE set) the two must agree -- an 8-GPU line is never printed by one rank
@@ -214,6 +293,14 @@ def main():
     elif int(os.environ["WORLD_SIZE"]) != args.gpus:
         raise SystemExit("bench.py: --gpus %d but the launcher started WORLD_SIZE=%s ranks" % (args.gpus, os.environ["WORLD_SIZE"]))
 
+    # One helper process, forked here while this process has no thread and no HIP runtime yet: it generates the step's LocalBA windows
+    # (seconds of numpy on worker processes of its own) while this process builds the tracking pipelines, which is one core's work.
+    helper = None
+    if args.workload != "euroc8":
+        import multiprocessing
+        from concurrent.futures import ProcessPoolExecutor
+        helper = ProcessPoolExecutor(1, mp_context=multiprocessing.get_context("fork"))
+        helper.submit(os.getpid).result()   # (the worker is forked now, not at the first real job)
     import torch  # first: the library then binds to the same HIP runtime as torch
     import torch.distributed as dist
     import __graft_entry__ as g
@@ -287,6 +374,29 @@ def main():
         scens = [pkg.scenario.tracking_scenario(100 + rank + 1000 * j, B, cfg=cfg_name, n_unique=n_unique, stereo=KITTI) for j in range(NPIPE)]
         scen = scens[0]
     base = scen["cur"]
+    fpk = max(1, args.frames_per_keyframe)
+    # ---- LocalBA windows of the step: one per frames_per_keyframe frames, every one a DIFFERENT problem drawn over the sizes
+    # LocalMapping meets (synth.lba_window_mix: 10-40 local keyframes, 2-6 k points, 4-8 observations per point, 5-20 % gross
+    # outliers; src/Optimizer.cc:457-505).  --lba-mix homogeneous = round 3's step: SURVEY 8(d)-size windows, 4 distinct, tiled
+    n_win = max(1, B // fpk)
+    # AOS2_BENCH_LBA_STEPS_PER_CALL=k: one LocalBA CALL solves the windows of k consecutive steps (all different problems; every step's
+    # windows are solved inside the timed region, a step count that is no multiple gets a last call for the rest).  The batch program's cost
+    # grows less than linearly with its windows ALONE (64 windows 4.12 ms, 128 7.16, 192 10.5) -- in the composite k = 2 / 3 / 4 gave
+    # 70.0, 70.4 / 76.4 / 67.9 k frames/s beside 71.6, 72.6 k for k = 1 in one session (profiles/r06_composite_decomposition.txt): no
+    # gain that survives the run-to-run spread, at two to four times the latency of a window's result.  Default 1.
+    LBA_SPC = max(1, int(os.environ.get("AOS2_BENCH_LBA_STEPS_PER_CALL", "1")))
+    n_win_call = n_win * LBA_SPC
+    if KITTI:   # BASELINE configs[3]: the 20-keyframe window of SURVEY 8(d) (20 local + 30 fixed keyframes, ~24 k stereo edges), every one a different problem
+        lba_mix = [dict(seed=200000 + 1000 * rank + i, n_local=20, n_fixed=30, n_points=8000) for i in range(n_win_call)]
+    elif args.lba_mix == "heterogeneous":
+        # One window of the timed, parity-checked step (the last of the batch; AOS2_BENCH_LBA_HARD_EVERY=k: every k-th, 0: none) starts far
+        # from the optimum: rejected steps, a continuation round for it alone.  Its end point is gated like every other window's, at the
+        # resolution the oracle itself has on it (parity.lba_resolution: the oracle against its own re-associated runs, times parity.LBA_RESOLUTION_FACTOR = 4, never
+        # below 1e-5; profiles/r06_lba_sensitivity.txt).  A whole batch with every 8th window like that: extra.local_ba_batch_with_rejected_steps
+        lba_mix = pkg.synth.lba_window_mix(rank, n_win_call, hard_every=int(os.environ.get("AOS2_BENCH_LBA_HARD_EVERY", str(n_win))))
+    else:
+        lba_mix = None
+    lba_job = None if lba_mix is None else helper.submit(synth_lba_windows, lba_mix)
     N_LOCAL = 1500
     Chain = pkg.chain.StereoTrackingChain if KITTI else pkg.chain.TrackingChain   # kitti: the stereo Frame constructor (src/Frame.cc:57-113)
     pipes = [Chain(scens[j], device=local_rank, n_local=N_LOCAL) for j in range(NPIPE)]
@@ -311,7 +421,6 @@ def main():
     # ---- per keyframe (every `frames_per_keyframe` frames) the front part of Tracking::TrackReferenceKeyFrame (Tracking.cc:858-866):
     # Frame::ComputeBoW (ORBVocabulary::transform, a vocabulary of the ORBvoc shape k = 10, L = 6) + SearchByBoW(reference
     # keyframe, frame), device-resident (chain.ReferenceKeyFrameBoW), on a thread of its own beside the chain
-    fpk = max(1, args.frames_per_keyframe)
     n_bow = max(1, B // fpk)
     NO_BOW = os.environ.get("AOS2_BENCH_NO_BOW") == "1"   # diagnostics only
     voc_nodes = None if NO_BOW else pkg.synth.synth_vocabulary(400, 10, int(os.environ.get("AOS2_BENCH_VOC_LEVELS", "6")))
@@ -339,33 +448,17 @@ def main():
             kfws[j].run()
         kf_walls.append(time.perf_counter() - t_)
     d_img, d_kps, d_desc, d_n = pipes[0].d_cur, pipes[0].d_kps, pipes[0].d_desc, pipes[0].d_n
-    # ---- LocalBA windows of the step: one per frames_per_keyframe frames, every one a DIFFERENT problem drawn over the sizes
-    # LocalMapping meets (synth.lba_window_mix: 10-40 local keyframes, 2-6 k points, 4-8 observations per point, 5-20 % gross
-    # outliers; src/Optimizer.cc:457-505).  --lba-mix homogeneous = round 3's step: SURVEY 8(d)-size windows, 4 distinct, tiled
-    n_win = max(1, B // fpk)
-    # AOS2_BENCH_LBA_STEPS_PER_CALL=k: one LocalBA CALL solves the windows of k consecutive steps (all different problems; every step's
-    # windows are solved inside the timed region, a step count that is no multiple gets a last call for the rest).  The batch program's cost
-    # grows less than linearly with its windows ALONE (64 windows 4.12 ms, 128 7.16, 192 10.5) -- in the composite k = 2 / 3 / 4 gave
-    # 70.0, 70.4 / 76.4 / 67.9 k frames/s beside 71.6, 72.6 k for k = 1 in one session (profiles/r06_composite_decomposition.txt): no
-    # gain that survives the run-to-run spread, at two to four times the latency of a window's result.  Default 1.
-    LBA_SPC = max(1, int(os.environ.get("AOS2_BENCH_LBA_STEPS_PER_CALL", "1")))
-    n_win_call = n_win * LBA_SPC
-    lba_hom_unique = [pkg.synth.synth_lba_problem(10 * rank + i, n_points=8000) for i in range(min(4, n_win))]
-    lba_hom = [lba_hom_unique[i % len(lba_hom_unique)] for i in range(n_win_call)]
-    if KITTI:   # BASELINE configs[3]: the 20-keyframe window of SURVEY 8(d) (20 local + 30 fixed keyframes, ~24 k stereo edges), every one a different problem
-        lba_mix = [dict(seed=200000 + 1000 * rank + i, n_local=20, n_fixed=30, n_points=8000) for i in range(n_win_call)]
-        lba_unique = pkg.synth.synth_lba_problems(lba_mix)
-        lba_probs = lba_unique
-    elif args.lba_mix == "heterogeneous":
-        # One window of the timed, parity-checked step (the last of the batch; AOS2_BENCH_LBA_HARD_EVERY=k: every k-th, 0: none) starts far
-        # from the optimum: rejected steps, a continuation round for it alone.  Its end point is gated like every other window's, at the
-        # resolution the oracle itself has on it (parity.lba_resolution: the oracle against its own re-associated runs, times parity.LBA_RESOLUTION_FACTOR = 4, never
-        # below 1e-5; profiles/r06_lba_sensitivity.txt).  A whole batch with every 8th window like that: extra.local_ba_batch_with_rejected_steps
-        lba_mix = pkg.synth.lba_window_mix(rank, n_win_call, hard_every=int(os.environ.get("AOS2_BENCH_LBA_HARD_EVERY", str(n_win))))
-        lba_unique = pkg.synth.synth_lba_problems(lba_mix)
+    # round 3's windows: the step's LocalBA batch with --lba-mix homogeneous, an extra row of --full (~3 s of generation per window)
+    lba_hom_unique, lba_hom = [], []
+    if args.full or args.lba_mix == "homogeneous":
+        lba_hom_unique = [pkg.synth.synth_lba_problem(10 * rank + i, n_points=8000) for i in range(min(4, n_win))]
+        lba_hom = [lba_hom_unique[i % len(lba_hom_unique)] for i in range(n_win_call)]
+    if lba_mix is not None:
+        lba_unique = lba_job.result()
         lba_probs = lba_unique
     else:
-        lba_mix, lba_unique, lba_probs = None, lba_hom_unique, lba_hom
+        lba_unique, lba_probs = lba_hom_unique, lba_hom
+    helper.shutdown()
     # LocalBA batches in flight (own handle + host thread each): one more than steps in flight -- a call is ~4 ms of host work (structure
     # build, staging) and ~8 ms of device program beside everything else, i.e. two steps long; with two handles the stepping thread
     # waited 6-7 ms of every 8 ms step for it (62.7 k frames/s; three handles 66.7-69.7 k, four 65.9 k, one 51.8 k in one session)
@@ -593,6 +686,96 @@ def main():
         dt_ranks = [float(x.item()) for x in tl]   # every rank's own clock around its K steps (the line reports the maximum)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    def headline():
+        """the result line's figures of the timed steps (rank 0)"""
+        _ne = [int(q_["n_edges"]) for q_ in lba_probs]
+        if lba_mix is not None:
+            lba_desc = ("%d of them starting far from the optimum (rejected steps); " % sum(1 for m_ in lba_mix if "hard" in m_) if any("hard" in m_ for m_ in lba_mix) else "") + \
+                       ("%d windows per step, the %d different windows of %d steps solved per call: %d-%d keyframes (%d-%d of them local), %d-%d points, %d-%d edges, mean %.0f edges -- SURVEY 8(d)'s "
+                        "window has 24 066" % (n_win, n_win_call, LBA_SPC, min(q_["n_poses"] for q_ in lba_probs), max(q_["n_poses"] for q_ in lba_probs),
+                                              min(m_["n_local"] for m_ in lba_mix), max(m_["n_local"] for m_ in lba_mix),
+                                              min(q_["n_points"] for q_ in lba_probs), max(q_["n_points"] for q_ in lba_probs), min(_ne), max(_ne), float(np.mean(_ne))))
+        else:
+            lba_desc = "%d keyframes, %d points, %d edges: SURVEY 8(d); 4 distinct problems tiled" % (lba_probs[0]["n_poses"], lba_probs[0]["n_points"], lba_probs[0]["n_edges"])
+        n_kp, nm_host, lba_res = pipes[0].d_n.cpu().numpy(), pipes[0].d_nm.cpu().numpy(), lba_prep[0]["R"]
+        return {
+            "metric": "stereo frames/sec (extract x2 + stereo match + track + BoW + localBA) KITTI 1241x376" if KITTI else "frames/sec (extract+match+localBA) TUM 640x480",
+            "value": world * B * args.steps / dt,
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8 (extract, match) + f64 (PoseOptimization, LocalBA)",
+            "data": "real (TUM fr1_desk frames from $TUM_FR1_DESK; LocalBA windows synthetic)" if real else "synthetic",
+            "config": {"workload": ("BASELINE configs[2] + [3]: KITTI 00 stereo 1241x376, 2000 features, 8 levels, scale 1.2, FAST 20/7 (Examples/Stereo/KITTI00-02.yaml): "
+                                    "per stereo frame both eyes' ORBextractor::operator() on two handles + Frame::ComputeStereoMatches + " if KITTI else
+                                    "TUM 640x480 RGB-D, 1000 features, 8 levels, scale 1.2, FAST 20/7: per frame ORBextractor::operator() + ") +
+                                   "Frame::Frame + SearchByProjection(Current, Last) + PoseOptimization + SearchLocalPoints(%d local map "
+                                   "points) + PoseOptimization; per %d frames one keyframe: Frame::ComputeBoW (vocabulary k = 10, L = 6) + "
+                                   "SearchByBoW(reference keyframe, frame), %s"
+                                   "and one LocalBundleAdjustment window (%s)" % (N_LOCAL, fpk, ("SearchForTriangulation against %d neighbour keyframes + Fuse (search) into them and %d second-order neighbours + Fuse of the local map points into the keyframe " % (N_NB, N_NB * N_SECOND)) if kfws else "",
+                                                            lba_desc),
+                       "baseline_metric": "frames/sec (extract+match+localBA) TUM 640\u00d7480, 1/2/4/8 GPU + %HBM roofline",
+                       "frames_per_gpu_per_step": B, "frames_per_keyframe": fpk, "local_ba_windows_per_step": n_win,
+                       "local_ba_steps_per_call": LBA_SPC, "local_ba_windows_per_call": n_win_call,
+                       "local_ba_mix": args.lba_mix, "distinct_frame_pairs_per_step": n_unique, "pipelines": NPIPE,
+                       "local_ba_handles_in_flight": NLBA, "step_runner": "native threads (csrc/host_runner.cpp)" if NATIVE else "python threads",
+                       "images": ("page-locked host memory every step%s, results to page-locked host arrays (--host-images)" % (", uploaded one step ahead" if HB_PREFETCH else "")) if args.host_images
+                                 else "resident in HBM (the host-boundary form: extra.composite_host_boundary)",
+                       "hip_hardware_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "local_ba_window_groups_per_handle": LBA_GROUPS,
+                       "host_cpus_bound_to_the_gpus_numa_node": numa_cpus,
+                       "frames_per_s_per_rank": [B * args.steps / d_ for d_ in dt_ranks],
+                       "host_threads_per_rank": {"enqueue": 1, "local_ba_handles": NLBA, "local_ba_workers_per_handle": lba_threads,
+                                                 "keyframe_legs": NPIPE, "host_cores": os.cpu_count()},
+                       "keyframe_legs_per_step": {"reference_keyframe_bow_searches": n_bow if bows else 0,
+                                                  "triangulation_pairs": len(kfws[0].tri_pairs) if kfws else 0,
+                                                  "fuse_pairs": len(kfws[0].kf1) if kfws else 0,
+                                                  "reverse_fuse_problems": n_bow if kfws else 0,
+                                                  "note": None if kfws or not real else "the neighbour keyframes are views of the generator's scenes: with recorded "
+                                                          "frames the triangulation / fuse leg is left out"},
+                       "host_threads": "the GPU path is driven by 1 enqueueing thread + %d LocalMapping-side threads (one per LocalBA handle), each handle "
+                                       "building its windows' index structures on up to %d worker threads, + %d threads for the keyframe legs (BoW, triangulation / fuse searches); "
+                                       "cpu_baseline is ONE core (the reference's threading per stage)" % (NLBA, lba_threads, NPIPE),
+                       "independent_frame_pairs": "the B frames of a step are B independent (LastFrame, CurrentFrame) pairs (%d distinct per pipeline, "
+                                                  "another set per pipeline and rank); the chain of ONE sequence is sequential in time and is reported as "
+                                                  "extra.tracking_frame_chain_wall_ms" % n_unique,
+                       "octree": os.environ.get("AOS2_OCTREE", "device"),
+                       "keypoints_per_frame_mean": float(n_kp.mean()),
+                       "matches_per_frame_mean": {"search_by_projection_last": float(nm_host[0].mean()), "inliers_1": float(nm_host[1].mean()),
+                                                  "search_local_points": float(nm_host[2].mean()), "inliers_2": float(nm_host[3].mean())},
+                       "local_ba_iterations": [int(lba_res[0].iters_done_first), int(lba_res[0].iters_done_second)]},
+        }
+
+    jv = (args.steps - 1) % NPIPE   # the pipeline of the last timed step: the one the oracle checks (and the cpu_baseline sample runs)
+    if args.dump_outputs and rank == 0:   # the last timed step: pipeline jv's frames, its keyframe legs, the windows of the last LocalBA call
+        outs = chain_outputs(pkg, pipes[jv])
+        if bows:
+            kr = dump_rows(n_bow)
+            outs.update(keyframe_bow_matches=bows[jv].match[kr], keyframe_bow_nmatches=bows[jv].nmatches)
+        if kfws:
+            kw = kfws[jv]
+            tr, fr, rr = dump_rows(len(kw.match12)), dump_rows(len(kw.best_idx)), dump_rows(len(kw.rev_idx))
+            outs.update(triangulation_matches=kw.match12[tr], triangulation_nmatches=kw.nm, fuse_best_idx=kw.best_idx[fr],
+                        fuse_best_dist=kw.best_dist[fr], reverse_fuse_best_idx=kw.rev_idx[rr], reverse_fuse_best_dist=kw.rev_dist[rr])
+        if not NO_LBA:
+            ll = lba_prep[max(0, runner.last_lba() if NATIVE else lba_sched["last"])]
+            wr = dump_rows(n_win_call)
+            outs.update({"local_ba_" + k_: np.concatenate([ll["arrs"][w][i_].reshape(-1) for w in wr]) for i_, k_ in enumerate(("pose_Tcw", "point_xyz", "edge_outlier"))})
+            outs.update(local_ba_final_chi2=[ll["R"][w].final_chi2 for w in wr],
+                        local_ba_iterations=[(ll["R"][w].iters_done_first, ll["R"][w].iters_done_second) for w in wr],
+                        local_ba_trials=[(ll["R"][w].trials_first, ll["R"][w].trials_second) for w in wr])
+        dump_outputs(args.dump_outputs, outs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()))
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- the LocalBA device program of the last batch: Levenberg-Marquardt trial slots enqueued for every window against the trials
     # the windows needed (a heterogeneous batch runs in lock step: a window that needs fewer trials leaves its slots empty)
     lock_step = None
@@ -612,11 +795,10 @@ def main():
                              "compacted, sized for what it still needs.  slots_over_trials = trial slots summed over the windows each round "
                              "covered / trials the windows needed (1.0 = no launch covered a window with nothing left to do; a window whose "
                              "optimisation ends early leaves its remaining slots of the round empty)"}
-    jv = (args.steps - 1) % NPIPE   # the pipeline of the last timed step: the one the oracle checks (and the cpu_baseline sample runs)
     scen_v = scens[jv]
     # ---- what the LAST timed step left behind, copied before anything else reuses the buffers: checked against the oracle
     # below (`parity_checked`).  The oracle is only imported here, after the timed region.
-    do_verify = True if args.verify is None else args.verify   # rank 0, at every N
+    do_verify = args.verify   # rank 0, at every N
     snap = None
     if rank == 0 and do_verify:
         g.load_oracle()
@@ -705,8 +887,6 @@ def main():
                              "trials_needed_min_mean_max": [min(hneed), float(np.mean(hneed)), max(hneed)],
                              "windows_not_needing_15_trials": int(sum(1 for n_ in hneed if n_ != 15)),
                              "slots_over_trials": lbas[0].last_window_slots() / max(1, sum(hneed))})
-    nm_host = pipes[0].d_nm.cpu().numpy()
-    lba_res = lba_prep[0]["R"]
     # ---- stage times of one synchronous pass (every stage waited for: wall clock incl. launch latency)
     def timed(fn):
         torch.cuda.synchronize()
@@ -1063,69 +1243,12 @@ def main():
         except Exception as exc:  # secondary numbers must never break the contract line
             extra["error"] = repr(exc)
 
-    _ne = [int(q_["n_edges"]) for q_ in lba_probs]
-    if lba_mix is not None:
-        lba_desc = ("%d of them starting far from the optimum (rejected steps); " % sum(1 for m_ in lba_mix if "hard" in m_) if any("hard" in m_ for m_ in lba_mix) else "") + \
-                   ("%d windows per step, the %d different windows of %d steps solved per call: %d-%d keyframes (%d-%d of them local), %d-%d points, %d-%d edges, mean %.0f edges -- SURVEY 8(d)'s "
-                    "window has 24 066" % (n_win, n_win_call, LBA_SPC, min(q_["n_poses"] for q_ in lba_probs), max(q_["n_poses"] for q_ in lba_probs),
-                                          min(m_["n_local"] for m_ in lba_mix), max(m_["n_local"] for m_ in lba_mix),
-                                          min(q_["n_points"] for q_ in lba_probs), max(q_["n_points"] for q_ in lba_probs), min(_ne), max(_ne), float(np.mean(_ne))))
-    else:
-        lba_desc = "%d keyframes, %d points, %d edges: SURVEY 8(d); 4 distinct problems tiled" % (lba_probs[0]["n_poses"], lba_probs[0]["n_points"], lba_probs[0]["n_edges"])
     if rank == 0:
         P = 1_444_097 if KITTI else 950_532  # sum of level pixels for 1241x376 / 640x480
         fast_bytes = P * B
         achieved = fast_bytes / (fast_ms * 1e-3) / 1e9
-        out = {
-            "metric": "stereo frames/sec (extract x2 + stereo match + track + BoW + localBA) KITTI 1241x376" if KITTI else "frames/sec (extract+match+localBA) TUM 640x480",
-            "value": world * B * args.steps / dt,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8 (extract, match) + f64 (PoseOptimization, LocalBA)",
-            "data": "real (TUM fr1_desk frames from $TUM_FR1_DESK; LocalBA windows synthetic)" if real else "synthetic",
-            "config": {"workload": ("BASELINE configs[2] + [3]: KITTI 00 stereo 1241x376, 2000 features, 8 levels, scale 1.2, FAST 20/7 (Examples/Stereo/KITTI00-02.yaml): "
-                                    "per stereo frame both eyes' ORBextractor::operator() on two handles + Frame::ComputeStereoMatches + " if KITTI else
-                                    "TUM 640x480 RGB-D, 1000 features, 8 levels, scale 1.2, FAST 20/7: per frame ORBextractor::operator() + ") +
-                                   "Frame::Frame + SearchByProjection(Current, Last) + PoseOptimization + SearchLocalPoints(%d local map "
-                                   "points) + PoseOptimization; per %d frames one keyframe: Frame::ComputeBoW (vocabulary k = 10, L = 6) + "
-                                   "SearchByBoW(reference keyframe, frame), %s"
-                                   "and one LocalBundleAdjustment window (%s)" % (N_LOCAL, fpk, ("SearchForTriangulation against %d neighbour keyframes + Fuse (search) into them and %d second-order neighbours + Fuse of the local map points into the keyframe " % (N_NB, N_NB * N_SECOND)) if kfws else "",
-                                                            lba_desc),
-                       "baseline_metric": "frames/sec (extract+match+localBA) TUM 640\u00d7480, 1/2/4/8 GPU + %HBM roofline",
-                       "frames_per_gpu_per_step": B, "frames_per_keyframe": fpk, "local_ba_windows_per_step": n_win,
-                       "local_ba_steps_per_call": LBA_SPC, "local_ba_windows_per_call": n_win_call,
-                       "local_ba_mix": args.lba_mix, "distinct_frame_pairs_per_step": n_unique, "pipelines": NPIPE,
-                       "local_ba_handles_in_flight": NLBA, "step_runner": "native threads (csrc/host_runner.cpp)" if NATIVE else "python threads",
-                       "images": ("page-locked host memory every step%s, results to page-locked host arrays (--host-images)" % (", uploaded one step ahead" if HB_PREFETCH else "")) if args.host_images
-                                 else "resident in HBM (the host-boundary form: extra.composite_host_boundary)",
-                       "hip_hardware_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "local_ba_window_groups_per_handle": LBA_GROUPS,
-                       "host_cpus_bound_to_the_gpus_numa_node": numa_cpus,
-                       "frames_per_s_per_rank": [B * args.steps / d_ for d_ in dt_ranks],
-                       "host_threads_per_rank": {"enqueue": 1, "local_ba_handles": NLBA, "local_ba_workers_per_handle": lba_threads,
-                                                 "keyframe_legs": NPIPE, "host_cores": os.cpu_count()},
-                       "keyframe_legs_per_step": {"reference_keyframe_bow_searches": n_bow if bows else 0,
-                                                  "triangulation_pairs": len(kfws[0].tri_pairs) if kfws else 0,
-                                                  "fuse_pairs": len(kfws[0].kf1) if kfws else 0,
-                                                  "reverse_fuse_problems": n_bow if kfws else 0,
-                                                  "note": None if kfws or not real else "the neighbour keyframes are views of the generator's scenes: with recorded "
-                                                          "frames the triangulation / fuse leg is left out"},
-                       "host_threads": "the GPU path is driven by 1 enqueueing thread + %d LocalMapping-side threads (one per LocalBA handle), each handle "
-                                       "building its windows' index structures on up to %d worker threads, + %d threads for the keyframe legs (BoW, triangulation / fuse searches); "
-                                       "cpu_baseline is ONE core (the reference's threading per stage)" % (NLBA, lba_threads, NPIPE),
-                       "independent_frame_pairs": "the B frames of a step are B independent (LastFrame, CurrentFrame) pairs (%d distinct per pipeline, "
-                                                  "another set per pipeline and rank); the chain of ONE sequence is sequential in time and is reported as "
-                                                  "extra.tracking_frame_chain_wall_ms" % n_unique,
-                       "octree": os.environ.get("AOS2_OCTREE", "device"),
-                       "keypoints_per_frame_mean": float(n_kp.mean()),
-                       "matches_per_frame_mean": {"search_by_projection_last": float(nm_host[0].mean()), "inliers_1": float(nm_host[1].mean()),
-                                                  "search_local_points": float(nm_host[2].mean()), "inliers_2": float(nm_host[3].mean())},
-                       "local_ba_iterations": [int(lba_res[0].iters_done_first), int(lba_res[0].iters_done_second)]},
+        out = headline()
+        out.update({
             "stage_ms": composite_stage,
             "extractor_stage_ms": stage,
             "roofline": {"bound": "hbm", "kernel": "fast_cells_kernel", "achieved": achieved, "peak": 8000.0,
@@ -1138,7 +1261,7 @@ def main():
                                  "812 per cell-wave in round 1, -> 712 in round 2; round 3: the tile is staged by LDS-DMA, 0.109 -> 0.123 at "
                                  "B = 512)"},
             "extra": extra,
-        }
+        })
         # the other two streaming kernels of the step, from the un-chunked stage times (HIP events of the library)
         pyr_bytes = 2.0 * P - W * H - round(W / 3.583181) * round(H / 3.583181)   # every level but the last read once, every level but the first written once (tum: 1.57e6)
         out["roofline_other"] = [

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def _run(cmd, env_extra=None, timeout=600):
 
 
 def test_bench_contract_single_gpu(gpu):
-    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--cpu-frames", "8", "--no-extra"])
+    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--cpu-frames", "8", "--no-extra", "--full"])
     assert d["metric"] == "frames/sec (extract+match+localBA) TUM 640x480" and d["unit"] == "frames/s"
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["value"] > 0 and abs(d["value"] - 32 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
@@ -62,11 +63,38 @@ def test_bench_contract_single_gpu(gpu):
     assert {"search_for_triangulation", "fuse", "search_by_bow"} <= set(d["cpu_baseline"]["ms_per_frame"])
 
 
+
+@pytest.mark.parametrize("workload", ["tum", "euroc8"])
+def test_bench_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(gpu, tmp_path, workload):
+    """without --full the line holds the headline figures only (no oracle, no runs beside the timed steps); --dump-outputs writes
+    what the last timed step computed as float32 / float64 within 64 MB, and a second run with the same arguments writes the same arrays"""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--workload", workload,
+                  "--dump-outputs", str(out)])
+        assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["parity_checked"] is None if workload == "euroc8" else not {"parity_checked", "cpu_baseline", "extra", "roofline", "stage_ms", "exchange"} & set(d)
+        files = sorted(out.glob("*.npy"))
+        assert files and sum(f.stat().st_size for f in files) <= 64 << 20
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        dumps.append(arrs)
+    a, b = dumps
+    if workload == "tum":
+        assert d["metric"] == "frames/sec (extract+match+localBA) TUM 640x480" and abs(d["value"] - 32 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert {"frame_keypoints", "frame_descriptors", "frame_Tcw", "frame_map_points", "keyframe_bow_matches", "fuse_best_idx",
+                "local_ba_pose_Tcw", "local_ba_point_xyz"} <= set(a)
+        assert a["frame_n"].shape == (32,) and (a["frame_n"] > 0).all() and a["local_ba_final_chi2"].shape == (4,)
+    else:
+        assert {"left_keypoints", "left_descriptors", "right_keypoints", "u_right", "depth"} <= set(a) and (a["left_n"] > 0).all()
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+
 def test_bench_kitti_slice(gpu):
     """BASELINE configs[2] + [3] as a bench line (--workload kitti): a 2-step slice -- both eyes' extraction on two handles,
     ComputeStereoMatches and the stereo Frame members on the device, the tracking chain, the keyframe's BoW search and the 20-keyframe
     LocalBA windows; the last timed step equals the oracle (mvuRight / mvDepth from the oracle's ComputeStereoMatches, bit for bit)"""
-    d = _run([sys.executable, "bench.py", "--workload", "kitti", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "8"])
+    d = _run([sys.executable, "bench.py", "--workload", "kitti", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "8", "--full"])
     assert d["metric"].startswith("stereo frames/sec") and "KITTI" in d["config"]["workload"] and d["n_gpus"] == 1
     assert abs(d["value"] - 16 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     pc = d["parity_checked"]
@@ -80,7 +108,7 @@ def test_bench_kitti_slice(gpu):
 def test_bench_with_the_large_batch_pose_optimization_form(gpu):
     """batches of more than 256 frames run PoseOptimization with 128 threads per frame (all frames resident at once); forced here on a
     small batch: the last timed step still equals the oracle (inlier counts, outlier flags bit-identical, poses 1e-5)"""
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-extra"],
+    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-extra", "--full"],
              {"AOS2_PO_THREADS": "128"})
     assert d["parity_checked"]["ok"] is True and d["parity_checked"]["frames"] >= 8
 
@@ -88,7 +116,7 @@ def test_bench_with_the_large_batch_pose_optimization_form(gpu):
 def test_bench_local_ba_windows_of_two_steps_per_call(gpu):
     """AOS2_BENCH_LBA_STEPS_PER_CALL=2: a LocalBA call every second step with both steps' windows (8 different problems here), an odd step
     count gets a last call for the rest; every window of the last call equals the oracle"""
-    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu-baseline", "--no-extra"],
+    d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu-baseline", "--no-extra", "--full"],
              {"AOS2_BENCH_LBA_STEPS_PER_CALL": "2"})
     pc = d["parity_checked"]
     assert pc["ok"] is True and pc["local_ba_windows"] == 8 and pc["distinct_local_ba_problems"] == 8
@@ -100,7 +128,7 @@ def test_bench_detects_a_wrong_result(gpu):
     (AOS2_BENCH_FAULT, a test hook) the line reports the mismatch and the process fails"""
     env = dict(os.environ)
     env["AOS2_BENCH_FAULT"] = "1"
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-extra"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-extra", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 3 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
@@ -113,7 +141,7 @@ def test_bench_two_ranks_share_the_gpu(gpu, workload, launcher):
     """N = 2 both ways: under torch.distributed.run (the driver's form) and as plain `python bench.py --gpus 2`, which starts
     its own ranks"""
     tail = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--no-extra", "--no-cpu-baseline",
-            "--workload", workload, "--verify"]
+            "--workload", workload, "--full", "--verify"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + tail
@@ -148,7 +176,7 @@ def test_bench_rccl_path_on_one_gpu(gpu, workload):
     gathered as DEVICE tensors on the step's own stream, the all-reduce of the timing, the barriers -- and rank 0 checks the
     gathered slots (AOS2_BENCH_FORCE_DIST is a test hook; with N GPUs the driver's torchrun launch takes the same path)."""
     d = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "16", "--no-extra", "--no-cpu-baseline",
-              "--workload", workload, "--verify"], {"AOS2_BENCH_FORCE_DIST": "1", "MASTER_PORT": str(_free_port())})
+              "--workload", workload, "--full", "--verify"], {"AOS2_BENCH_FORCE_DIST": "1", "MASTER_PORT": str(_free_port())})
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["parity_checked"]["ok"] is True
     if workload == "tum":
         assert d["exchange"]["backend"] == "nccl" and d["exchange"]["headers_ok"] is True
@@ -163,7 +191,7 @@ def test_bench_on_a_recorded_sequence(gpu, tmp_path):
     import __graft_entry__ as g
     from test_datasets_cpu import _mini_tum
     _mini_tum(g.load_package(), tmp_path, n=12)
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "8", "--no-extra"],
+    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "8", "--no-extra", "--full"],
              {"TUM_FR1_DESK": str(tmp_path)})
     assert d["data"].startswith("real") and d["parity_checked"]["ok"] is True and d["parity_checked"]["frames"] >= 8
     assert d["config"]["matches_per_frame_mean"]["search_by_projection_last"] > 50

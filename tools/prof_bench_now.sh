@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_bench_now
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python $R/bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extra > $O/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python $R/bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-extra > $O/log.txt 2>&1
 tail -1 $O/log.txt | cut -c1-200
 f=$(find $O -name "*kernel_stats.csv" | head -1)
 python - <<PY

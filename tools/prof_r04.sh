@@ -10,21 +10,21 @@ O=$R/gpurun_out/prof_r04
 rm -rf $O; mkdir -p $O
 cd $R && timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
-python bench.py --lba-mix homogeneous --no-extra > $O/bench_homogeneous.json 2> $O/bench_homogeneous.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
+python bench.py --full --lba-mix homogeneous --no-extra > $O/bench_homogeneous.json 2> $O/bench_homogeneous.err
 # round 3's step exactly (32 distinct frame pairs tiled, 4 LocalBA problems of one size tiled, first-order Fuse targets only): like for like
-AOS2_BENCH_SECOND_NEIGHBOURS=0 AOS2_BENCH_UNIQUE=32 python bench.py --lba-mix homogeneous --no-extra --no-cpu-baseline > $O/bench_r03_form.json 2> $O/bench_r03_form.err
-python bench.py --workload kitti > $O/bench_kitti.json 2> $O/bench_kitti.err; tail -c 300 $O/bench_kitti.json
+AOS2_BENCH_SECOND_NEIGHBOURS=0 AOS2_BENCH_UNIQUE=32 python bench.py --full --lba-mix homogeneous --no-extra --no-cpu-baseline > $O/bench_r03_form.json 2> $O/bench_r03_form.err
+python bench.py --full --workload kitti > $O/bench_kitti.json 2> $O/bench_kitti.err; tail -c 300 $O/bench_kitti.json
 cd /tmp
 # ---- one profiled run: stats + trace + the run's own line
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python $R/bench.py --no-cpu-baseline --no-extra > $O/bench_profiled.json 2> $O/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python $R/bench.py --full --no-cpu-baseline --no-extra > $O/bench_profiled.json 2> $O/bench_profiled.err
 cd $R
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 python tools/fast_kernel_from_trace.py $(find $O/prof -name "*kernel_trace.csv" | head -1) > $O/bench_fast_kernel_trace.txt
 tail -1 $O/bench_profiled.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench.py line of this SAME profiled run: roofline.kernel_ms %.4f (frac %.4f), value %.0f frames/s, parity_checked.ok %s' % (d['roofline']['kernel_ms'], d['roofline']['frac'], d['value'], d['parity_checked']['ok']))" >> $O/bench_fast_kernel_trace.txt
 cat $O/bench_fast_kernel_trace.txt
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kitti -- python $R/bench.py --workload kitti --no-cpu-baseline --steps 20 > $O/kitti_profiled.json 2> $O/kitti_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kitti -- python $R/bench.py --full --workload kitti --no-cpu-baseline --steps 20 > $O/kitti_profiled.json 2> $O/kitti_profiled.err
 cp $(find $O/kitti -name "*kernel_stats.csv" | head -1) $O/kitti_kernel_stats.csv
 # ---- LocalBA
 cd $R

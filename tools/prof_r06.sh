@@ -13,15 +13,15 @@ if has suite; then
 fi
 if has bench; then
   # the default line ten times in a row (the spread), the median run is the committed line; then the other forms once each
-  for i in 01 02 03 04 05; do python bench.py > $O/bench_default_$i.json 2> $O/bench_default_$i.err; tail -c 200 $O/bench_default_$i.json; done
-  python bench.py --host-images --no-extra > $O/bench_host_images.json 2> $O/bench_host_images.err
-  python bench.py --lba-mix homogeneous --no-extra > $O/bench_homogeneous.json 2> $O/bench_homogeneous.err
-  AOS2_BENCH_RUNNER=python AOS2_BENCH_LBA_HANDLES=2 python bench.py --no-extra --no-cpu-baseline > $O/bench_python_threads.json 2> $O/bench_python_threads.err
+  for i in 01 02 03 04 05; do python bench.py --full > $O/bench_default_$i.json 2> $O/bench_default_$i.err; tail -c 200 $O/bench_default_$i.json; done
+  python bench.py --full --host-images --no-extra > $O/bench_host_images.json 2> $O/bench_host_images.err
+  python bench.py --full --lba-mix homogeneous --no-extra > $O/bench_homogeneous.json 2> $O/bench_homogeneous.err
+  AOS2_BENCH_RUNNER=python AOS2_BENCH_LBA_HANDLES=2 python bench.py --full --no-extra --no-cpu-baseline > $O/bench_python_threads.json 2> $O/bench_python_threads.err
 fi
 cd /tmp
 if has prof; then
   # ---- one profiled run: stats + trace + the run's own line
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python $R/bench.py --no-cpu-baseline --no-extra > $O/bench_profiled.json 2> $O/bench_profiled.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python $R/bench.py --full --no-cpu-baseline --no-extra > $O/bench_profiled.json 2> $O/bench_profiled.err
   cd $R
   cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
   python tools/fast_kernel_from_trace.py $(find $O/prof -name "*kernel_trace.csv" | head -1) > $O/bench_fast_kernel_trace.txt
@@ -30,8 +30,8 @@ if has prof; then
   cd /tmp
 fi
 if has kitti; then
-  python $R/bench.py --workload kitti > $O/bench_kitti.json 2> $O/bench_kitti.err; tail -c 200 $O/bench_kitti.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kitti -- python $R/bench.py --workload kitti --no-cpu-baseline --steps 20 > $O/kitti_profiled.json 2> $O/kitti_profiled.err
+  python $R/bench.py --full --workload kitti > $O/bench_kitti.json 2> $O/bench_kitti.err; tail -c 200 $O/bench_kitti.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kitti -- python $R/bench.py --full --workload kitti --no-cpu-baseline --steps 20 > $O/kitti_profiled.json 2> $O/kitti_profiled.err
   cp $(find $O/kitti -name "*kernel_stats.csv" | head -1) $O/kitti_kernel_stats.csv
 fi
 if has pmc_extract; then

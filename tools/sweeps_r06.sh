@@ -5,7 +5,7 @@
 sec_a() {
 # composite decomposition: which part of the step is the device busy with (each run ~40 s)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sweep_r06a; mkdir -p $O
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
@@ -25,7 +25,7 @@ run default_again X=1
 sec_b() {
 # wave priority of the LocalBA kernels: the composite and the batch alone, per library variant
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sweep_r06b; mkdir -p $O; L=$PWD/active-orb-slam2_amd/lib
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
@@ -40,7 +40,7 @@ done
 }
 sec_c() {
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sweep_r06c; mkdir -p $O
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
@@ -68,7 +68,7 @@ echo "32:"; LBA_N=32 AOS2_LBA_DEAL_BY_UNITS=1 python tools/gpu_lba_mix_prof.py 2
 sec_e() {
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sweep_r06e; mkdir -p $O
 python -m pytest tests/test_bench_gpu.py tests/test_frames_gpu.py -m gpu -x -q 2>&1 | tail -5
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
@@ -87,7 +87,7 @@ sec_f() {
 cd $GRAFT_REPO_ROOT; O=gpurun_out/sweep_r06f; mkdir -p $O
 for v in 0 1 0 1; do echo "AOS2_OCT_IMAGE=$v:"; AOS2_OCT_IMAGE=$v python tools/prof_extract.py 512 2>&1 | tail -1; done
 for v in 0 1; do echo "kitti AOS2_OCT_IMAGE=$v:"; AOS2_OCT_IMAGE=$v python tools/prof_extract.py 256 kitti 2>&1 | tail -1; done
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --no-verify --steps 60 --warmup 6 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
@@ -105,7 +105,7 @@ python -m pytest tests/test_extractor_gpu.py tests/test_stereo_gpu.py tests/test
 for v in 0 1 0 1; do echo "tum AOS2_OCT_PAIR=$v:"; AOS2_OCT_PAIR=$v python tools/prof_extract.py 512 2>&1 | tail -1 | cut -c1-330; done
 for v in 0 1 0 1; do echo "kitti AOS2_OCT_PAIR=$v:"; AOS2_OCT_PAIR=$v python tools/prof_extract.py 256 kitti 2>&1 | tail -1 | cut -c1-330; done
 python tools/gpu_fuzz_extractor.py 100000 100 2>&1 | tail -1
-run() { name=$1; shift; env "$@" python bench.py --no-extra --no-cpu-baseline --steps 60 --warmup 6 $BA 2>$O/$name.err | tail -1 > $O/$name.json
+run() { name=$1; shift; env "$@" python bench.py --full --no-extra --no-cpu-baseline --steps 60 --warmup 6 $BA 2>$O/$name.err | tail -1 > $O/$name.json
   python - <<PY
 import json
 d = json.loads(open("$O/$name.json").read()); t = d["extra"]["timed_steps"]
