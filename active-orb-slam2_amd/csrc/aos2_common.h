@@ -20,12 +20,6 @@ int bind_device(int device);
 
 // Every stream of the library is created here (csrc/replay.hip): non-blocking, of the highest priority class when asked for.
 int stream_create(hipStream_t *q, bool high_priority);
-// (measurement switch: AOS2_PRIO_MATCHER / _VOCABULARY / _FRAMES = 1 puts that handle kind's stream into the high priority class)
-inline bool stream_priority_env(const char *name)
-{
-    const char *e = getenv(name);
-    return e && e[0] == '1';
-}
 
 #define AOS2_HIP_CHECK(expr)                                                              \
     do {                                                                                  \

@@ -2,7 +2,6 @@
 // device buffers, stage orchestration on one HIP stream, and the C ABI of include/aos2.h.
 // Reference: src/ORBextractor.cc (ctor :410-470, operator() :1043-1105, ComputePyramid :1107-1132,
 // ComputeKeyPointsOctTree :765-853).
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cctype>
@@ -10,7 +9,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "aos2_common.h"
@@ -104,17 +102,13 @@ struct aos2_extractor {
     int gauss7[7];
     int cap_level = 0, max_kp = 0;
     unsigned long long umax_nibbles = 0;
-    bool host_octree = false;
     int oct_lds = 0;                     // LDS bytes per octree job (0 = global-scratch path only)
-    OctImageLayout oct_image = {};       // total > 0: one workgroup per image with per-level LDS slices
     OctImageLayout oct_pair = {};        // total > 0: two levels per workgroup for batches of >= 8 images (extractor_kernels.h)
-    int host_threads = 8;
 
     bool dev_ready = false;
     hipStream_t stream = nullptr;       // = streams[0]
     hipStream_t streams[kMaxStreams] = {};
     int chunks = 0;                      // 0 = automatic
-    int n_streams = 0;
     hipEvent_t ev[8] = {};
     hipEvent_t order_ev[kMaxStreams] = {};   // aos2_extractor_stream_wait
     // ComputeStereoMatches reads BOTH extractors' pyramid blocks on the left one's first stream: each extractor keeps an event behind
@@ -138,15 +132,10 @@ struct aos2_extractor {
     DevBuf<int32_t> d_status;   // sticky [lowest octree failure code, largest n_out] of the batches in flight
     const uint8_t *img0 = nullptr;  // level 0 of the last batch = the caller's (device) images
     size_t img0_stride = 0;
-    // AOS2_DESC_BLUR=level: the reference's whole-level GaussianBlur as a streaming pass, describe on the blurred planes
-    bool blur_level = false;
-    BlurPlanHost blur_plan_h = {};
-    size_t blur_bytes = 0;           // per image
-    DevBuf<uint8_t> d_blur;
     int pitch0 = 0;
     DevBuf<uint8_t> d_pyr, d_in, d_desc;
     DevBuf<uint32_t> d_slots, d_dense, d_sel;
-    DevBuf<int32_t> d_cell_cnt, d_level_off, d_level_cnt, d_sel_cnt, d_nout;
+    DevBuf<int32_t> d_cell_cnt, d_level_cnt, d_sel_cnt, d_nout;
     DevBuf<aos2_keypoint_t> d_kps;
     int out_cap = 0;
     // ComputeStereoMatches scratch (this handle = the left eye)
@@ -160,8 +149,7 @@ struct aos2_extractor {
     DevBuf<int32_t> o_perm, o_tmp, o_pairs, o_idx;
     DevBuf<OctNode> o_nodes;
     // host mirrors
-    PinnedBuf<int32_t> h_level_off, h_sel_cnt, h_nout, h_status;
-    PinnedBuf<uint32_t> h_dense, h_sel;
+    PinnedBuf<int32_t> h_sel_cnt, h_nout, h_status;
     float timing[8] = {};
 };
 
@@ -494,26 +482,13 @@ static int init_device(aos2_extractor *e)
     int st = bind_device(e->device);
     if (st) return st;
     if (e->dev_ready) return AOS2_OK;
-    {
-        const char *v = getenv("AOS2_NSTREAMS");
-        const int ns = v ? std::max(1, std::min(kMaxStreams, atoi(v))) : kMaxStreams;
-        for (int i = 0; i < kMaxStreams; ++i) {
-            if (i < ns) {
-                if ((st = stream_create(&e->streams[i], false))) return st;
-            } else
-                e->streams[i] = e->streams[i % ns];
-        }
-        e->n_streams = ns;
-    }
+    for (auto &q : e->streams)
+        if ((st = stream_create(&q, false))) return st;
     e->stream = e->streams[0];
     for (auto &ev : e->ev) AOS2_HIP_CHECK(hipEventCreate(&ev));
-    if (e->oct_image.total > 0 && prepare_octree_image_kernel(e->oct_image.total) != 0) {
-        (void)hipGetLastError();
-        e->oct_image.total = 0;  // the runtime refuses that much LDS: keep the per-job kernel
-    }
     if (e->oct_pair.total > 0 && prepare_octree_pair_kernel(e->oct_pair.total) != 0) {
         (void)hipGetLastError();
-        e->oct_pair.total = 0;
+        e->oct_pair.total = 0;  // the runtime refuses that much LDS: keep the per-job kernel
     }
     int r = upload_constants(k_pattern, e->umax, e->gauss7, e->stream);
     if (r != 0) {
@@ -539,30 +514,20 @@ static int ensure_batch(aos2_extractor *e, int batch)
     if ((st = e->d_slots.alloc(P.slot_total * batch))) return st;
     if ((st = e->d_dense.alloc(P.slot_total * batch))) return st;
     if ((st = e->d_cell_cnt.alloc(nc * batch))) return st;
-    if ((st = e->d_level_off.alloc((size_t)(L + 1) * batch))) return st;
     if ((st = e->d_level_cnt.alloc((size_t)L * batch))) return st;
     if ((st = e->d_sel.alloc((size_t)L * e->cap_level * batch))) return st;
     if ((st = e->d_sel_cnt.alloc((size_t)L * batch))) return st;
-    if ((st = e->h_level_off.alloc((size_t)(L + 1) * batch))) return st;
     if ((st = e->h_sel_cnt.alloc((size_t)L * batch))) return st;
     if ((st = e->h_nout.alloc(batch))) return st;
-    if (!e->host_octree) {
-        const size_t jobs = (size_t)L * batch;
-        if ((st = e->o_xs.alloc(P.oct_cand_total * batch))) return st;
-        if ((st = e->o_ys.alloc(P.oct_cand_total * batch))) return st;
-        if ((st = e->o_sc.alloc(P.oct_cand_total * batch))) return st;
-        if ((st = e->o_perm.alloc(P.oct_cand_total * batch))) return st;
-        if ((st = e->o_tmp.alloc(P.oct_cand_total * batch))) return st;
-        if ((st = e->o_pairs.alloc(P.oct_node_total * 4 * batch))) return st;
-        if ((st = e->o_idx.alloc(jobs * e->cap_level))) return st;
-        if ((st = e->o_nodes.alloc(P.oct_node_total * batch))) return st;
-    } else {
-        if ((st = e->h_sel.alloc((size_t)L * e->cap_level * batch))) return st;
-    }
-    if (e->blur_level) {
-        e->blur_bytes = blur_plan(P.levels.data(), L, P.pyr_bytes, &e->blur_plan_h);
-        if ((st = e->d_blur.alloc(e->blur_bytes * batch + 256))) return st;
-    }
+    const size_t jobs = (size_t)L * batch;
+    if ((st = e->o_xs.alloc(P.oct_cand_total * batch))) return st;
+    if ((st = e->o_ys.alloc(P.oct_cand_total * batch))) return st;
+    if ((st = e->o_sc.alloc(P.oct_cand_total * batch))) return st;
+    if ((st = e->o_perm.alloc(P.oct_cand_total * batch))) return st;
+    if ((st = e->o_tmp.alloc(P.oct_cand_total * batch))) return st;
+    if ((st = e->o_pairs.alloc(P.oct_node_total * 4 * batch))) return st;
+    if ((st = e->o_idx.alloc(jobs * e->cap_level))) return st;
+    if ((st = e->o_nodes.alloc(P.oct_node_total * batch))) return st;
     // row h of every plane (1 guard row) and pitch padding are read by 32-bit tile loads: keep
     // them defined
     AOS2_HIP_CHECK(hipMemsetAsync(e->d_pyr.p, 0, P.pyr_bytes * batch + 256, e->stream));
@@ -580,72 +545,6 @@ static int ensure_out(aos2_extractor *e, int batch, int cap)
     if ((st = e->d_kps.alloc((size_t)batch * cap))) return st;
     if ((st = e->d_desc.alloc((size_t)batch * cap * 32))) return st;
     if ((st = e->d_nout.alloc(batch))) return st;
-    return AOS2_OK;
-}
-
-// host octree stage (optional): D2H candidates, std::thread pool, H2D selection
-static int octree_on_host(aos2_extractor *e, int batch)
-{
-    Plan &P = e->plan;
-    const int L = e->nlevels;
-    AOS2_HIP_CHECK(hipMemcpyAsync(e->h_level_off.p, e->d_level_off.p, sizeof(int32_t) * (L + 1) * batch,
-                                  hipMemcpyDeviceToHost, e->stream));
-    AOS2_HIP_CHECK(hipStreamSynchronize(e->stream));
-    int maxn = 0;
-    for (int b = 0; b < batch; ++b) maxn = std::max(maxn, e->h_level_off.p[(size_t)b * (L + 1) + L]);
-    if (maxn == 0) maxn = 1;
-    int st;
-    if ((st = e->h_dense.alloc((size_t)maxn * batch))) return st;
-    AOS2_HIP_CHECK(hipMemcpy2DAsync(e->h_dense.p, (size_t)maxn * 4, e->d_dense.p, P.slot_total * 4, (size_t)maxn * 4,
-                                    batch, hipMemcpyDeviceToHost, e->stream));
-    AOS2_HIP_CHECK(hipStreamSynchronize(e->stream));
-    std::atomic<int> next{0}, fail{0};
-    const int jobs = batch * L;
-    auto worker = [&]() {
-        std::vector<int16_t> xs, ys;
-        std::vector<uint8_t> sc;
-        std::vector<int32_t> perm, tmp, pairs, idx(e->cap_level);
-        std::vector<OctNode> nodes;
-        for (;;) {
-            const int job = next.fetch_add(1);
-            if (job >= jobs) break;
-            const int b = job / L, l = job % L;
-            const int32_t *lo = e->h_level_off.p + (size_t)b * (L + 1);
-            const int beg = lo[l], n = lo[l + 1] - lo[l];
-            const uint32_t *cand = e->h_dense.p + (size_t)b * maxn + beg;
-            int nk = 0;
-            if (n > 0) {
-                xs.resize(n); ys.resize(n); sc.resize(n); perm.resize(n); tmp.resize(n);
-                for (int i = 0; i < n; ++i) {
-                    xs[i] = (int16_t)(cand[i] & 0xfff);
-                    ys[i] = (int16_t)((cand[i] >> 12) & 0xfff);
-                    sc[i] = (uint8_t)(cand[i] >> 24);
-                }
-                const int mn = oct_max_nodes(n, P.levels[l].nfeat);
-                nodes.resize(mn);
-                pairs.resize((size_t)4 * mn);
-                OctScratch S{nodes.data(), perm.data(), tmp.data(), pairs.data(), pairs.data() + 2 * mn, mn, mn};
-                nk = distribute_octree(xs.data(), ys.data(), sc.data(), n, 16, P.levels[l].w - 16, 16,
-                                       P.levels[l].h - 16, P.levels[l].nfeat, S, idx.data(), e->cap_level);
-                if (nk < 0) fail.store(nk);
-                uint32_t *out = e->h_sel.p + ((size_t)b * L + l) * e->cap_level;
-                for (int k = 0; k < nk; ++k) out[k] = cand[idx[k]];
-            }
-            e->h_sel_cnt.p[(size_t)b * L + l] = nk;
-        }
-    };
-    const int nt = std::max(1, std::min(e->host_threads, jobs));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(worker);
-    worker();
-    for (auto &t : th) t.join();
-    if (fail.load() < 0) {
-        set_error("host octree scratch exhausted (%d)", fail.load());
-        return AOS2_ERR_CAPACITY;
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(e->d_sel.p, e->h_sel.p, sizeof(uint32_t) * L * e->cap_level * batch,
-                                  hipMemcpyHostToDevice, e->stream));
-    AOS2_HIP_CHECK(hipMemcpyAsync(e->d_sel_cnt.p, e->h_sel_cnt.p, sizeof(int32_t) * L * batch, hipMemcpyHostToDevice, e->stream));
     return AOS2_OK;
 }
 
@@ -706,7 +605,6 @@ static int enqueue_device(aos2_extractor *e, const uint8_t *d_imgs, int batch, i
     // (smaller chunks lose to kernel tails and queue sharing; replaying each chunk as one hipGraph changed nothing).
     int chunks = e->chunks > 0 ? e->chunks : (batch >= 96 ? 3 : batch >= 64 ? 2 : 1);
     if (io && e->chunks <= 0 && batch >= 32) chunks = 4;   // copy / compute pipeline of the host-pointer call
-    if (e->host_octree) chunks = 1;
     chunks = std::min(chunks, std::min(batch, kMaxStreams));
     e->streams_used = std::max(e->streams_used, chunks);
     if (e->input_waited > 0 && chunks > e->input_waited) {   // (aos2_extractor_wait_for_stream: stream 0 waits for the inputs already)
@@ -733,7 +631,7 @@ static int enqueue_device(aos2_extractor *e, const uint8_t *d_imgs, int batch, i
         const uint8_t *img = d_imgs + (size_t)b0 * image_stride;
         uint8_t *pyr = e->d_pyr.p + (size_t)b0 * P.pyr_bytes;
         uint32_t *slots = e->d_slots.p + (size_t)b0 * P.slot_total, *dense = e->d_dense.p + (size_t)b0 * P.slot_total;
-        int32_t *cell_cnt = e->d_cell_cnt.p + (size_t)b0 * NC, *level_off = e->d_level_off.p + (size_t)b0 * (L + 1);
+        int32_t *cell_cnt = e->d_cell_cnt.p + (size_t)b0 * NC;
         uint32_t *sel = e->d_sel.p + (size_t)b0 * L * e->cap_level;
         int32_t *sel_cnt = e->d_sel_cnt.p + (size_t)b0 * L;
         if (io) {
@@ -763,41 +661,21 @@ static int enqueue_device(aos2_extractor *e, const uint8_t *d_imgs, int batch, i
         launch_fast(img, image_stride, stride, pyr, P.pyr_bytes, P.d_levels.p, P.d_cells.p, NC, e->iniTh, e->minTh, P.TP,
                     P.TH, P.SP, P.fast_lds, P.list_cap, P.keep_cap, slots, P.slot_total, cell_cnt, nb, s);
         if (timed) AOS2_HIP_CHECK(hipEventRecord(e->ev[2], s));
-        // device octree: every (image, level) job gathers its own candidates from the cell slots; the separate
-        // compaction kernel (one latency-bound workgroup per image on the critical path of the chunk, 31 us at
-        // B=256) only feeds the host octree path
-        if (e->host_octree)
-            launch_compact(P.d_cells.p, NC, L, P.d_level_cell_begin.p, slots, P.slot_total, cell_cnt, dense, P.slot_total,
-                           level_off, nb, s);
+        // (timing slot [2], once a candidate compaction kernel: every octree job now gathers its own candidates from the cell slots)
         if (timed) AOS2_HIP_CHECK(hipEventRecord(e->ev[3], s));
-        if (e->host_octree) {
-            int st2 = octree_on_host(e, nb);
-            if (st2) return st2;
-        } else {
-            const size_t j0 = (size_t)b0 * L, c0 = (size_t)b0 * P.oct_cand_total, n0 = (size_t)b0 * P.oct_node_total;
-            OctDevScratch scr{e->o_xs.p + c0, e->o_ys.p + c0, e->o_sc.p + c0, e->o_perm.p + c0, e->o_tmp.p + c0,
-                              e->o_pairs.p + 4 * n0, e->o_idx.p + j0 * e->cap_level, e->o_nodes.p + n0,
-                              P.oct_cand_total, P.oct_node_total};
-            const OctGather gather{P.d_cells.p, P.d_level_cell_begin.p, slots, P.slot_total, cell_cnt, NC,
-                                   e->d_level_cnt.p + (size_t)b0 * L};
-            if (e->oct_image.total > 0)
-                launch_octree_image(dense, P.slot_total, gather, P.d_levels.p, L, nb, scr, sel, (size_t)L * e->cap_level,
-                                    sel_cnt, e->cap_level, e->oct_image, s);
-            else if (e->oct_pair.total > 0 && nb >= 8)   // (fewer images: the helper-wave form of the per-job kernel)
-                launch_octree_pairs(dense, P.slot_total, gather, P.d_levels.p, L, nb, scr, sel, (size_t)L * e->cap_level,
-                                    sel_cnt, e->cap_level, e->oct_pair, s);
-            else
-                launch_octree(dense, P.slot_total, gather, P.d_levels.p, L, nb, scr, sel, (size_t)L * e->cap_level, sel_cnt,
-                              e->cap_level, e->oct_lds, s);
-        }
+        const size_t j0 = (size_t)b0 * L, c0 = (size_t)b0 * P.oct_cand_total, n0 = (size_t)b0 * P.oct_node_total;
+        OctDevScratch scr{e->o_xs.p + c0, e->o_ys.p + c0, e->o_sc.p + c0, e->o_perm.p + c0, e->o_tmp.p + c0,
+                          e->o_pairs.p + 4 * n0, e->o_idx.p + j0 * e->cap_level, e->o_nodes.p + n0,
+                          P.oct_cand_total, P.oct_node_total};
+        const OctGather gather{P.d_cells.p, P.d_level_cell_begin.p, slots, P.slot_total, cell_cnt, NC,
+                               e->d_level_cnt.p + (size_t)b0 * L};
+        if (e->oct_pair.total > 0 && nb >= 8)   // (fewer images: the helper-wave form of the per-job kernel)
+            launch_octree_pairs(dense, P.slot_total, gather, P.d_levels.p, L, nb, scr, sel, (size_t)L * e->cap_level,
+                                sel_cnt, e->cap_level, e->oct_pair, s);
+        else
+            launch_octree(dense, P.slot_total, gather, P.d_levels.p, L, nb, scr, sel, (size_t)L * e->cap_level, sel_cnt,
+                          e->cap_level, e->oct_lds, s);
         if (timed) AOS2_HIP_CHECK(hipEventRecord(e->ev[4], s));
-        if (e->blur_level) {   // (inside the describe stage's events: the A/B compares the stage as a whole)
-            uint8_t *bl = e->d_blur.p + (size_t)b0 * e->blur_bytes;
-            launch_blur_levels(img, image_stride, stride, pyr, P.pyr_bytes, P.d_levels.p, L, e->blur_plan_h, bl, e->blur_bytes, nb, s);
-            launch_describe_blur(img, image_stride, stride, pyr, P.pyr_bytes, bl, e->blur_bytes, e->blur_plan_h, P.d_levels.p, L, sel,
-                                 (size_t)L * e->cap_level, e->cap_level, sel_cnt, d_kps + (size_t)b0 * cap, d_desc + (size_t)b0 * cap * 32, cap,
-                                 d_nout + b0, nb, e->d_status.p, s);
-        } else
         launch_describe(img, image_stride, stride, pyr, P.pyr_bytes, P.d_levels.p, L, sel, (size_t)L * e->cap_level,
                         e->cap_level, sel_cnt, d_kps + (size_t)b0 * cap, d_desc + (size_t)b0 * cap * 32, cap, d_nout + b0, nb,
                         e->umax_nibbles, e->d_status.p, s);
@@ -838,8 +716,7 @@ static int finish_device(aos2_extractor *e)
     for (int c = 1; c < kMaxStreams; ++c) AOS2_HIP_CHECK(hipStreamSynchronize(e->streams[c]));
     // status words + the counts of the last batch: three small copies behind the last chunk of stream 0, one wait
     AOS2_HIP_CHECK(hipMemcpyAsync(e->h_status.p, e->d_status.p, sizeof(status), hipMemcpyDeviceToHost, e->streams[0]));
-    if (!e->host_octree)
-        AOS2_HIP_CHECK(hipMemcpyAsync(e->h_sel_cnt.p, e->d_sel_cnt.p, sizeof(int32_t) * (size_t)L * batch, hipMemcpyDeviceToHost, e->streams[0]));
+    AOS2_HIP_CHECK(hipMemcpyAsync(e->h_sel_cnt.p, e->d_sel_cnt.p, sizeof(int32_t) * (size_t)L * batch, hipMemcpyDeviceToHost, e->streams[0]));
     AOS2_HIP_CHECK(hipMemcpyAsync(e->h_nout.p, e->flight_nout, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost, e->streams[0]));
     AOS2_HIP_CHECK(hipStreamSynchronize(e->streams[0]));
     status[0] = e->h_status.p[0];
@@ -957,7 +834,6 @@ int aos2_extractor_create(int nfeatures, float scale_factor, int nlevels, int in
     e->scaleFactor = scale_factor;
     e->device = device;
     build_host_tables(e);
-    if (const char *v = getenv("AOS2_OCTREE")) e->host_octree = (strcmp(v, "host") == 0);
     {
         // LDS budget of an octree job: sized for ~8 candidates per requested feature on level 0 (the
         // busiest level), capped at the 64 KB a workgroup may take without opt-in; jobs that need more
@@ -967,22 +843,6 @@ int aos2_extractor_create(int nfeatures, float scale_factor, int nlevels, int in
         if (want > 65536) want = 65536;
         e->oct_lds = (int)want;
         if (const char *v = getenv("AOS2_OCT_LDS")) e->oct_lds = std::max(0, std::min(65536, atoi(v)));
-        // Optional (AOS2_OCT_IMAGE=1): if the working sets of all levels of one image fit the 160 KB of a CU together,
-        // the octree runs as one workgroup per image (one wave per level, per-level LDS slices), so that every job of
-        // the batch is resident at once.  Measured: 0.161 vs 0.166 ms un-chunked, but 1.166 vs 1.151 ms per step with
-        // the default two-stream chunking (a 137 KB workgroup starves the other chunk's kernels) -- hence opt-in.
-        const char *vi = getenv("AOS2_OCT_IMAGE");
-        if (e->oct_lds > 0 && nlevels <= 16 && vi && atoi(vi) != 0) {
-            int off = 0;
-            for (int l = 0; l < nlevels; ++l) {
-                const int nl = e->mnFeaturesPerLevel[l];
-                const int bytes = (int)((oct_lds_bytes(8 * nl + 128, nl) + 255) & ~(size_t)255);
-                e->oct_image.off[l] = off;
-                e->oct_image.bytes[l] = bytes;
-                off += bytes;
-            }
-            e->oct_image.total = off <= 160 * 1024 ? off : 0;
-        }
         // Default for batches: level g paired with level nlevels - 1 - g in one workgroup, each job in a slice of its own size
         // (AOS2_OCT_PAIR=0: one job per workgroup with the level-0 reservation, the form of rounds 1-5 and of calls of < 8 images).
         const char *vp = getenv("AOS2_OCT_PAIR");
@@ -1006,10 +866,6 @@ int aos2_extractor_create(int nfeatures, float scale_factor, int nlevels, int in
             e->oct_pair.total = total <= 160 * 1024 ? total : 0;
         }
     }
-    const unsigned hc = std::thread::hardware_concurrency();
-    e->host_threads = (int)std::min(32u, std::max(1u, hc));
-    if (const char *v = getenv("AOS2_HOST_THREADS")) e->host_threads = std::max(1, atoi(v));
-    if (const char *v = getenv("AOS2_DESC_BLUR")) e->blur_level = strcmp(v, "level") == 0 && e->nlevels <= 8;   // (the blur plan holds 8 levels; beyond, the per-keypoint form)
     if (const char *v = getenv("AOS2_CHUNKS")) e->chunks = std::max(0, std::min(kMaxStreams, atoi(v)));
     *out = e;
     return AOS2_OK;
@@ -1023,22 +879,22 @@ void aos2_extractor_destroy(aos2_extractor_t *e)
         for (auto &sx : e->streams) (void)hipStreamSynchronize(sx);
         if (aos2_extractor *peer = e->stereo_peer) {   // the other eye's guard may name a stream of this handle: drained above, so the
             if (peer->stereo_peer == e) peer->stereo_peer = nullptr;   // guard has nothing left to order -- forget it before the stream dies
-            for (int i = 0; i < e->n_streams; ++i)
-                if (peer->stereo_guard_stream == e->streams[i]) {
+            for (hipStream_t q : e->streams)
+                if (peer->stereo_guard_stream == q) {
                     peer->stereo_guard_armed = peer->stereo_guard_captured = false;
                     peer->stereo_guard_stream = nullptr;
                 }
         }
         e->plan.release_device();
-        e->d_pyr.release(); e->d_blur.release(); e->d_in.release(); e->d_desc.release(); e->d_slots.release(); e->d_dense.release();
-        e->d_sel.release(); e->d_cell_cnt.release(); e->d_level_off.release(); e->d_level_cnt.release(); e->d_sel_cnt.release();
+        e->d_pyr.release(); e->d_in.release(); e->d_desc.release(); e->d_slots.release(); e->d_dense.release();
+        e->d_sel.release(); e->d_cell_cnt.release(); e->d_level_cnt.release(); e->d_sel_cnt.release();
         e->d_nout.release(); e->d_kps.release();
         e->st_sad.release(); e->st_rows.release(); e->st_io.release(); e->st_host.release();
         e->o_xs.release(); e->o_ys.release(); e->o_sc.release(); e->o_perm.release(); e->o_tmp.release();
         e->o_pairs.release(); e->o_idx.release(); e->o_nodes.release();
-        e->h_level_off.release(); e->h_sel_cnt.release(); e->h_nout.release(); e->h_status.release(); e->h_dense.release(); e->h_sel.release();
+        e->h_sel_cnt.release(); e->h_nout.release(); e->h_status.release();
         for (auto &ev : e->ev) (void)hipEventDestroy(ev);
-        for (int i = 0; i < e->n_streams; ++i) (void)hipStreamDestroy(e->streams[i]);
+        for (hipStream_t q : e->streams) (void)hipStreamDestroy(q);
         for (auto &oe : e->order_ev)
             if (oe) (void)hipEventDestroy(oe);
         for (hipEvent_t x : {e->stereo_guard, e->stereo_t0, e->stereo_t1, e->input_ev, e->input_fan_ev})
@@ -1082,9 +938,6 @@ int aos2_extractor_extract_batch_device_async(aos2_extractor_t *e, const uint8_t
     if (!e || !d_imgs || !d_kps || !d_desc || !d_n_out || batch <= 0 || w <= 0 || h <= 0 || stride < w || cap <= 0) {
         set_error("bad argument");
         return AOS2_ERR_ARG;
-    }
-    if (e->host_octree) {   // the host octree path synchronises inside the batch: run it synchronously
-        return run_device(e, d_imgs, batch, w, h, stride, image_stride, d_kps, d_desc, cap, d_n_out);
     }
     return enqueue_device(e, d_imgs, batch, w, h, stride, image_stride, d_kps, d_desc, cap, d_n_out);
 }
@@ -1147,7 +1000,7 @@ int aos2_extractor_wait_for_stream(aos2_extractor_t *e, void *hip_stream)
     // streams that never return to it.
     // While `src` is being recorded only stream 0 joins: the batch behind this call may be cut into fewer chunks than the last one,
     // and a stream that joined a recording without getting work never returns to it (hipStreamEndCapture would fail).
-    const int k = stream_is_capturing(src) ? 1 : std::max(1, std::min(e->n_streams, e->last_chunks));
+    const int k = stream_is_capturing(src) ? 1 : std::max(1, std::min(kMaxStreams, e->last_chunks));
     for (int i = 0; i < k; ++i) AOS2_HIP_CHECK(hipStreamWaitEvent(e->streams[i], e->input_ev, 0));
     e->input_waited = std::max(e->input_waited, k);
     return AOS2_OK;
@@ -1163,7 +1016,7 @@ int aos2_extractor_stream_wait(aos2_extractor_t *e, void *hip_stream)
     int st = bind_device(e->device);
     if (st) return st;
     hipStream_t waiter = static_cast<hipStream_t>(hip_stream);
-    const int used = std::max(1, std::min(e->n_streams, e->streams_used));
+    const int used = std::max(1, std::min(kMaxStreams, e->streams_used));
     for (int i = 0; i < used; ++i) {
         if (!e->order_ev[i]) AOS2_HIP_CHECK(hipEventCreateWithFlags(&e->order_ev[i], hipEventDisableTiming));
         if (e->streams[i] == waiter) continue;   // (in order behind its own work already)
@@ -1472,22 +1325,16 @@ int aos2_extractor_debug_candidates(aos2_extractor_t *e, int image, int level, i
     if ((st = bind_device(e->device))) return st;
     if ((st = finish_device(e))) return st;   // batches enqueued asynchronously
     const int L = e->nlevels;
-    int32_t lo[2];
-    if (e->host_octree) {   // dense list of the whole image, written by the compaction kernel
-        AOS2_HIP_CHECK(hipMemcpy(lo, e->d_level_off.p + (size_t)image * (L + 1) + level, sizeof(lo), hipMemcpyDeviceToHost));
-    } else {                // per-level lists, written by the octree jobs at the level's first slot
-        int32_t n_l = 0;
-        AOS2_HIP_CHECK(hipMemcpy(&n_l, e->d_level_cnt.p + (size_t)image * L + level, sizeof(n_l), hipMemcpyDeviceToHost));
-        lo[0] = e->plan.cells[e->plan.level_cell_begin[level]].slot_off;
-        lo[1] = lo[0] + n_l;
-    }
-    const int cnt = lo[1] - lo[0];
+    // per-level lists, written by the octree jobs at the level's first slot
+    int32_t cnt = 0;
+    AOS2_HIP_CHECK(hipMemcpy(&cnt, e->d_level_cnt.p + (size_t)image * L + level, sizeof(cnt), hipMemcpyDeviceToHost));
+    const int first = e->plan.cells[e->plan.level_cell_begin[level]].slot_off;
     *n = cnt;
     if (!xs || !ys || !score) return AOS2_OK;
     if (cnt > cap) return AOS2_ERR_CAPACITY;
     std::vector<uint32_t> tmp(cnt > 0 ? cnt : 1);
     if (cnt > 0)
-        AOS2_HIP_CHECK(hipMemcpy(tmp.data(), e->d_dense.p + (size_t)image * e->plan.slot_total + lo[0],
+        AOS2_HIP_CHECK(hipMemcpy(tmp.data(), e->d_dense.p + (size_t)image * e->plan.slot_total + first,
                                  sizeof(uint32_t) * cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < cnt; ++i) {
         xs[i] = (int16_t)(tmp[i] & 0xfff);

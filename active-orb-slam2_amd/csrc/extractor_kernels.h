@@ -67,9 +67,6 @@ void launch_fast(const uint8_t *img0, size_t img0_stride, int pitch0, const uint
                  const LevelDev *levels, const CellDev *cells, int n_cells,
                  int ini_th, int min_th, int TP, int TH, int SP, size_t lds_bytes, int list_cap, int keep_cap,
                  uint32_t *slots, size_t slot_stride, int32_t *cell_cnt, int batch, hipStream_t st);
-void launch_compact(const CellDev *cells, int n_cells, int n_levels, const int *level_cell_begin,
-                    const uint32_t *slots, size_t slot_stride, const int32_t *cell_cnt, uint32_t *dense,
-                    size_t dense_stride, int32_t *level_off, int batch, hipStream_t st);
 // LDS working set of one octree job with n candidates and target N (OctCompact layout in
 // octree_kernel: packed candidates | perm | tmp | 16-byte node arena | two pairs arrays)
 __host__ __device__ inline int oct_lds_nodes(int N) { return 2 * N + 96; }   // ~1.4 N nodes are created in practice
@@ -80,20 +77,16 @@ __host__ __device__ inline size_t oct_lds_bytes(int n, int N)
     return ncand * 8 + (size_t)oct_lds_nodes(N) * 16 + (size_t)oct_lds_pairs(N) * 16;
 }
 
-// LDS slices of the one-workgroup-per-image octree kernel (one wave per level)
+// LDS slices of the pair octree kernel (one wave per level)
 struct OctImageLayout {
     int off[16], bytes[16];
     int total;
 };
-int prepare_octree_image_kernel(int total_lds);
 // Two levels per workgroup (level g and level n_levels - 1 - g: the largest with the smallest), a wave and an LDS slice of its own size
 // each: OctImageLayout::off[l] is level l's offset INSIDE its workgroup, total the largest pair.  The per-job kernel reserves the
 // level-0 size for every level; the pairs hold 1.3-1.6 x as many jobs per compute unit in workgroups no larger than two level-0 jobs.
 int prepare_octree_pair_kernel(int total_lds);
 void launch_octree_pairs(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                         int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                         int32_t *sel_level_cnt, int cap_level, const OctImageLayout &lay, hipStream_t st);
-void launch_octree_image(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
                          int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
                          int32_t *sel_level_cnt, int cap_level, const OctImageLayout &lay, hipStream_t st);
 void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
@@ -104,22 +97,5 @@ void launch_describe(const uint8_t *img0, size_t img0_stride, int pitch0, const 
                      const uint32_t *sel, size_t sel_stride, int cap_level, const int32_t *sel_level_cnt,
                      aos2_keypoint_t *kps, uint8_t *desc, int cap, int32_t *n_out, int batch,
                      unsigned long long umax_nibbles, int32_t *status, hipStream_t st);
-
-// whole-level blur (AOS2_DESC_BLUR=level): plan of the blurred planes, the streaming blur, describe on blurred levels
-struct BlurPlanHost {
-    int first[9];
-    int nq[8];
-    int nq_in[8];
-    uint32_t dst_off[8];
-    int dst_pitch[8];
-};
-size_t blur_plan(const LevelDev *h_levels, int n_levels, size_t pyr_bytes, BlurPlanHost *out);   // returns bytes per image
-void launch_blur_levels(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                        const LevelDev *levels, int n_levels, const BlurPlanHost &plan, uint8_t *blur, size_t blur_stride, int batch,
-                        hipStream_t st);
-void launch_describe_blur(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                          const uint8_t *blur, size_t blur_stride, const BlurPlanHost &plan, const LevelDev *levels, int n_levels,
-                          const uint32_t *sel, size_t sel_stride, int cap_level, const int32_t *sel_level_cnt,
-                          aos2_keypoint_t *kps, uint8_t *desc, int cap, int32_t *n_out, int batch, int32_t *status, hipStream_t st);
 
 }  // namespace aos2

@@ -281,29 +281,16 @@ typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ us2_t as_us2(uint32_t x) { return __builtin_bit_cast(us2_t, x); }
 __device__ __forceinline__ uint32_t as_u32(us2_t x) { return __builtin_bit_cast(uint32_t, x); }
 
-// compass pre-test on two pixels at once (packed u16 lanes): non-zero lane <=> one pixel of EACH antipodal compass pair -- (a, b) =
+// compass pre-test on two pixels at once (packed u16 lanes): a pixel survives <=> one pixel of EACH antipodal compass pair -- (a, b) =
 // ring pixels 0 / 8, (c, d) = ring pixels 4 / 12 -- is brighter than v+t, or one of each pair is darker than v-t.  A contiguous arc of 9 of
 // the 16 ring pixels holds ring pixel i or i + 8 for every i, so every FAST-9 corner passes; pixels with two bright compass pixels of
-// the SAME pair (no 9-arc can hold both without one of the other pair) do not -- tighter than "two of the four" and two instructions
-// shorter (round 3; the survivors are scored exactly either way, so the result is the same).
-__device__ __forceinline__ uint32_t compass2(us2_t v, us2_t a, us2_t b, us2_t c, us2_t d, us2_t T)
-{
-    const us2_t h1 = __builtin_elementwise_max(a, b), l1 = __builtin_elementwise_min(a, b);
-    const us2_t h2 = __builtin_elementwise_max(c, d), l2 = __builtin_elementwise_min(c, d);
-    const us2_t hi = __builtin_elementwise_min(h1, h2);   // the smaller of the pairs' maxima: both pairs have a pixel above it or equal
-    const us2_t lo = __builtin_elementwise_max(l1, l2);
-    // hi > v + T  <=>  (hi -sat T) > v: no sum that could leave 16 bits, so the same code serves operands that are
-    // scaled by 256 (the odd bytes of a dword taken with one AND instead of shift + AND; T scaled alike)
-    const us2_t bright = __builtin_elementwise_sub_sat(__builtin_elementwise_sub_sat(hi, T), v);
-    const us2_t dark = __builtin_elementwise_sub_sat(__builtin_elementwise_sub_sat(v, T), lo);
-    return as_u32(bright) | as_u32(dark);
-}
-
-// The same test as a MARGIN: max(hi -sat v, v -sat lo) per 16-bit lane -- three packed operations (two saturating differences and their
-// maximum) instead of four saturating subtractions and an OR; a lane of the result is > T exactly where compass2's lane is non-zero
-// (hi - T > v <=> hi - v > T in integers; a difference that saturates to 0 is false on both sides), also for operands scaled by 256
-// with a fraction below them (T scaled alike).  Round 6: 0.489 -> 0.478 ms per 512 frames of the profiling batch with the even pixels
-// alone in this form, same candidates; -DAOS2_FAST_NO_MARGIN keeps compass2.
+// the SAME pair (no 9-arc can hold both without one of the other pair) do not -- tighter than "two of the four" (round 3; the
+// survivors are scored exactly either way, so the result is the same).
+// The test is taken as a MARGIN: max(hi -sat v, v -sat lo) per 16-bit lane, with hi / lo the smaller of the pairs' maxima / the larger
+// of their minima -- three packed operations (two saturating differences and their maximum); a lane of the result is > t exactly where
+// the pixel survives (hi - t > v <=> hi - v > t in integers; a difference that saturates to 0 is false on both sides), also for operands
+// scaled by 256 with a fraction below them (t scaled alike).  Round 6: 0.489 -> 0.478 ms per 512 frames of the profiling batch with the
+// even pixels alone in this form, same candidates.
 __device__ __forceinline__ uint32_t compass2_margin(us2_t v, us2_t a, us2_t b, us2_t c, us2_t d)
 {
     const us2_t h1 = __builtin_elementwise_max(a, b), l1 = __builtin_elementwise_min(a, b);
@@ -312,8 +299,6 @@ __device__ __forceinline__ uint32_t compass2_margin(us2_t v, us2_t a, us2_t b, u
     return as_u32(__builtin_elementwise_max(__builtin_elementwise_sub_sat(hi, v), __builtin_elementwise_sub_sat(v, lo)));
 }
 
-// (AOS2_FAST_ABL = 1..4, AOS2_DESC_ABL = 1..4: timing-only ablation builds of tools/build_abl_libs.sh -- the kernel stops after /
-// skips one phase, results are wrong by construction; DESIGN.md section 0, item 6 has the phase shares they gave.)
 // Phases per wave (one grid cell of one image, 64-thread workgroup = one wave, so list counters are
 // wave-uniform registers and no LDS atomics or multi-wave barriers are needed):
 //   0. stage the cell + ring halo in LDS (32-bit loads), evaluated column 0 on a dword boundary
@@ -383,7 +368,6 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
     // then owns LDS dword rs * ndw + c = its lane number, which is the one layout gfx950's LDS-DMA can write
     // (global_load_lds_dword: per-lane global address, LDS destination = M0 base + 4 * lane) -- the tile goes from HBM / L2
     // to LDS without passing through VGPRs and without a ds_write per row step.
-#if !defined(AOS2_FAST_STAGE_DWORD) && !defined(AOS2_FAST_STAGE_VGPR)
     // (round 3, second step) 16 bytes per lane: global_load_lds_dwordx4 -- a row is n16 = ceil(ndw / 4) lanes, the pitch 16 * n16, a
     // 41-row tile two instructions instead of eight; the bytes past the right halo come from the same image row (the 16-pixel border)
     const int n16 = (ndw + 3) >> 2;
@@ -405,46 +389,7 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
                                                      (__attribute__((address_space(3))) void *)(tile + dbase), 16, 0, 0);
         }
     }
-#else
-    const int tp = 4 * ndw;
-    {
-        const int nrs = max(1, (int)((64u * cell.inv_ndw) >> 16));      // rows per step = 64 / ndw (cells are < 64 px wide: ndw <= 18)
-        const int rs = (int)(__umul24((uint32_t)lane, cell.inv_ndw) >> 16), c = lane - (int)__umul24((uint32_t)rs, (uint32_t)ndw);
-        const int nrows = ch + 6;
-        if (rs < nrs) {
-            const uint8_t *sbase = plane + (size_t)(cell.vy0 - 3) * lv.pitch + (cell.vx0 - 4);   // uniform
-            const uint32_t soff = __umul24((uint32_t)rs, (uint32_t)lv.pitch) + 4u * (uint32_t)c;
-            const uint32_t sstep = (uint32_t)(nrs * lv.pitch);
-#if !defined(AOS2_FAST_STAGE_VGPR)
-            const uint32_t dstep = (uint32_t)(nrs * tp);   // = 4 * nrs * ndw: the dwords one step's lanes cover
-            uint32_t dbase = 0;
-            for (int r0 = 0; r0 < nrows; r0 += nrs, sbase += sstep, dbase += dstep)
-                if (rs < nrows - r0)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(sbase + soff),
-                                                     (__attribute__((address_space(3))) void *)(tile + dbase), 4, 0, 0);
-#else
-            // (the round-2 form: up to 8 row steps requested together into registers, then written to LDS)
-            uint32_t doff = __umul24((uint32_t)rs, (uint32_t)tp) + 4u * (uint32_t)c;
-            const uint32_t dstep = (uint32_t)(nrs * tp);
-            for (int r0 = 0; r0 < nrows; r0 += 8 * nrs, sbase += 8 * (size_t)sstep, doff += 8 * dstep) {
-                uint32_t t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (rs < nrows - r0 - u * nrs) t[u] = load_u32_unaligned(sbase + (size_t)u * sstep + soff);
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (rs < nrows - r0 - u * nrs) *reinterpret_cast<uint32_t *>(tile + doff + (uint32_t)u * dstep) = t[u];
-            }
-#endif
-        }
-    }
-#endif
     const int SH = ch + 2;
-#if defined(AOS2_FAST_ABL) && AOS2_FAST_ABL == 1
-    __syncthreads();
-    if (lane == 0) cell_cnt[(size_t)b * n_cells + cell_id] = tile[5] == 0x7ffffff;
-    return;
-#endif
     uint32_t *my_slots = slots + (size_t)b * slot_stride + cell.slot_off;
     int th = ini_th;
     int nkept = 0;
@@ -478,10 +423,6 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
         // ---- 1. compass pre-test (a 9-arc contains one pixel of each antipodal compass pair)
         int n1 = 0;
         bool overflowed = false;   // the survivor list was emptied at least once: NMS walks the score map instead
-        const us2_t T = {(unsigned short)th, (unsigned short)th};
-        (void)T; (void)TH;   // (the margin form compares with th directly)
-        const us2_t TH = {(unsigned short)(th << 8), (unsigned short)(th << 8)};   // for operands scaled by 256 (th <= 255)
-        (void)T; (void)TH;   // (the margin form compares with th / th << 8 directly)
         const int nitems = nq * ch;
         for (int g0 = 0; g0 < nitems; g0 += 64) {
             if (n1 > 0 && n1 + 256 > list_cap) {  // one iteration appends <= 256 entries (wave-uniform test)
@@ -506,34 +447,21 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
                 const uint32_t Wq = __builtin_amdgcn_alignbyte(C, Wd, 1);               // columns x-3
                 const uint32_t Eq = __builtin_amdgcn_alignbyte(Ed, C, 3);               // columns x+3
                 const uint32_t M = 0x00ff00ffu, MH = 0xff00ff00u;
-#ifndef AOS2_FAST_NO_MARGIN
                 f_lo = compass2_margin(as_us2(C & M), as_us2(S & M), as_us2(N & M), as_us2(Eq & M), as_us2(Wq & M));
-#else
-                f_lo = compass2(as_us2(C & M), as_us2(S & M), as_us2(N & M), as_us2(Eq & M), as_us2(Wq & M), T);
-#endif
                 // the odd pixels in the high byte of each 16-bit lane, the even pixels' bytes left below them as "fraction": a maximum / minimum of
                 // such lanes has the exact high byte, and with H, L, V the high bytes and t the threshold `(H - t) * 256 + g > V * 256 + g'` can
                 // differ from `H - t > V` only for H - t == V (the fractions g, g' < 256): a pixel exactly AT the threshold may survive to the
                 // exact score, none above it is lost -- five mask instructions less
                 (void)MH;
-#ifndef AOS2_FAST_NO_MARGIN
                 f_hi = compass2_margin(as_us2(C), as_us2(S), as_us2(N), as_us2(Eq), as_us2(Wq));
-#else
-                f_hi = compass2(as_us2(C), as_us2(S), as_us2(N), as_us2(Eq), as_us2(Wq), TH);
-#endif
             }
             // (columns >= cw of the last quad are dropped in phase 2)
             const int x0 = 4 * qd;
-#ifndef AOS2_FAST_NO_MARGIN
             // (a lane of the margin is > t -- t << 8 for the odd pixels, whose operands are scaled by 256 -- where the pixel survives; a lane
             // without an item holds 0.  High lane: m.hi > t <=> m > (t << 16 | 0xffff) as unsigned 32-bit numbers)
             const uint32_t th8 = (uint32_t)th << 8;
             const bool p0 = (f_lo & 0xffffu) > (uint32_t)th, p2 = f_lo > (((uint32_t)th << 16) | 0xffffu);
             const bool p1 = (f_hi & 0xffffu) > th8, p3 = f_hi > ((th8 << 16) | 0xffffu);
-#else
-            const bool p0 = (f_lo & 0xffffu) != 0, p1 = (f_hi & 0xffffu) != 0;
-            const bool p2 = (f_lo >> 16) != 0, p3 = (f_hi >> 16) != 0;
-#endif
             const unsigned long long b0 = __ballot(p0), b1 = __ballot(p1), b2 = __ballot(p2), b3 = __ballot(p3);
             if ((b0 | b1 | b2 | b3) == 0ull) continue;
             // row-major list order (= cv::FAST's emission order, kept through scoring and NMS, so nothing is sorted
@@ -555,16 +483,8 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
             n1 += __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
         }
         __syncthreads();
-#if defined(AOS2_FAST_ABL) && AOS2_FAST_ABL == 2
-        if (lane == 0) cell_cnt[(size_t)b * n_cells + cell_id] = (n1 + list1[n1 >> 1]) == 0x7ffffff;
-        return;
-#endif
         score_survivors(n1);
         __syncthreads();
-#if defined(AOS2_FAST_ABL) && AOS2_FAST_ABL == 3
-        if (lane == 0) cell_cnt[(size_t)b * n_cells + cell_id] = (n1 + smap[SP + 5]) == 0x7ffffff;
-        return;
-#endif
         // ---- 3. NMS (strictly greater than the 8 neighbours inside the cell) over the corners, in row-major order: the
         // kept ones go straight to the cell's slots (a pass that keeps nothing writes nothing)
         nkept = 0;
@@ -594,9 +514,6 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
             }
             nkept += __popcll(bk);
         }
-#if defined(AOS2_FAST_ABL) && AOS2_FAST_ABL == 4
-        break;
-#endif
         if (nkept > 0 || th == min_th) break;
         th = min_th;  // vKeysCell.empty() -> retry with minThFAST (:812-816)
         __syncthreads();
@@ -605,77 +522,10 @@ __global__ __launch_bounds__(64) void fast_cells_kernel(const uint8_t *__restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// Per image: exclusive scan of the cell counts in the reference's emission order (levels, then
-// cells row-major) and gather of the per-cell slots into one dense list per image.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void compact_candidates_kernel(const CellDev *__restrict__ cells,
-                                                                 int n_cells, int n_levels,
-                                                                 const int *__restrict__ level_cell_begin,
-                                                                 const uint32_t *__restrict__ slots,
-                                                                 size_t slot_stride,
-                                                                 const int32_t *__restrict__ cell_cnt,
-                                                                 uint32_t *__restrict__ dense,
-                                                                 size_t dense_stride,
-                                                                 int32_t *__restrict__ level_off)
-{
-    __shared__ int wsum[4];
-    __shared__ int carry;
-    __shared__ int cell_off_sh[256];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t *cnt = cell_cnt + (size_t)b * n_cells;
-    const uint32_t *sl = slots + (size_t)b * slot_stride;
-    uint32_t *out = dense + (size_t)b * dense_stride;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n_cells; c0 += 256) {
-        const int c = c0 + tid;
-        const int v = c < n_cells ? cnt[c] : 0;
-        // wave inclusive scan
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        const int excl = carry + woff + x - v;
-        cell_off_sh[tid] = excl;
-        // level boundaries
-        if (c < n_cells) {
-            for (int l = 0; l < n_levels; ++l)
-                if (level_cell_begin[l] == c) level_off[(size_t)b * (n_levels + 1) + l] = excl;
-            const uint32_t *src = sl + cells[c].slot_off;
-            for (int i = 0; i < v; ++i) out[excl + i] = src[i];
-        }
-        __syncthreads();
-        if (tid == 255) carry = excl + v;
-        __syncthreads();
-    }
-    if (tid == 0) level_off[(size_t)b * (n_levels + 1) + n_levels] = carry;
-}
-
-// ---------------------------------------------------------------------------------------------
 // DistributeOctTree on the device: one lane per (image, level) running the shared serial
 // routine of octree.h over global scratch.  Latency-bound by construction (pointer-chasing
 // control flow of src/ORBextractor.cc:539-763); it exists to keep the candidates on the device.
 // ---------------------------------------------------------------------------------------------
-#if defined(AOS2_OCT_PROF)
-}  // namespace aos2
-__device__ long long g_oct_prof[16];
-extern "C" int aos2_debug_oct_prof(long long *out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_oct_prof), sizeof(long long) * 16) != hipSuccess) return -4;
-    if (reset) {
-        long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_oct_prof), z, sizeof(z)) != hipSuccess) return -4;
-    }
-    return 0;
-}
-namespace aos2 {
-#endif
 static_assert(sizeof(OctNode16) == 16, "oct_lds_bytes() assumes 16-byte compact nodes");
 
 // one (image, level) job, executed by ONE wave (lane = threadIdx.x & 63) over the LDS slice [lds, lds + lds_bytes)
@@ -825,22 +675,6 @@ __global__ __launch_bounds__(256) void octree_kernel(uint32_t *__restrict__ dens
         octdetail::group_helper_loop<OctCompact>(wave);
 }
 
-// one workgroup per image, one wave per level, each with its own LDS slice sized for that level: the LDS
-// reservation matches the jobs (the per-job kernel reserves the level-0 size for every level, which halves the
-// number of resident jobs), so all (image, level) jobs of a 256-image batch are resident at once.  The waves are
-// independent (wave-local fences only).
-__global__ __launch_bounds__(1024) void octree_image_kernel(uint32_t *__restrict__ dense, size_t dense_stride,
-                              OctGather gather, const LevelDev *__restrict__ levels,
-                              int n_levels, OctDevScratch scr, uint32_t *__restrict__ sel, size_t sel_stride,
-                              int32_t *__restrict__ sel_level_cnt, int cap_level, OctImageLayout lay)
-{
-    extern __shared__ uint32_t oct_lds[];
-    const int l = threadIdx.x >> 6;
-    if (l >= n_levels) return;
-    octree_job<false>(blockIdx.x, l, dense, dense_stride, gather, levels, n_levels, scr, sel, sel_stride, sel_level_cnt, cap_level,
-                      oct_lds + (lay.off[l] >> 2), lay.bytes[l]);
-}
-
 // two levels per workgroup: wave 0 = level g, wave 1 = level n_levels - 1 - g (extractor_kernels.h); jobs stay independent
 __global__ __launch_bounds__(128) void octree_pair_kernel(uint32_t *__restrict__ dense, size_t dense_stride,
                               OctGather gather, const LevelDev *__restrict__ levels,
@@ -911,12 +745,8 @@ constexpr int HTP = 23;           // row-PAIR pitch (dwords) of the transposed h
 constexpr int HTC = 40;           // columns of the h-blur tile (10 quads, 37 used)
 constexpr int VBP = 44;           // byte pitch of the blurred tile, stored transposed ([x][y]); 11 dwords (odd)
 
-#ifndef AOS2_DESC_KPW
-#define AOS2_DESC_KPW 8
-#endif
-constexpr int DK_BATCH = AOS2_DESC_KPW;   // keypoints per wave of describe_kernel: large batches (the per-wave work is shared by 8)
+constexpr int DK_BATCH = 8;               // keypoints per wave of describe_kernel: large batches (the per-wave work is shared by 8)
 constexpr int DK_FEW = 2;                 // ... a few images (the launch is as long as one wave: short waves)
-constexpr int DKB = 4;              // keypoints per wave (describe_blur_kernel)
 
 // LDS traffic of ONE wave is processed in issue order, so a write by one lane is visible to a later read by
 // another lane of the same wave; this only stops the compiler from moving LDS accesses across the phase boundary
@@ -926,13 +756,8 @@ __device__ __forceinline__ void wave_lds_phase() { asm volatile("" ::: "memory")
 // One wave (= one 64-thread workgroup) per DK consecutive output slots of one image.  The 43x43 patch of slot
 // i+1 is fetched into registers while slot i is processed out of LDS, so the L2/HBM latency of the staging
 // phase is covered by the wave's own arithmetic instead of by occupancy.
-#ifdef AOS2_DESC_WPE
-#define DESC_ATTR __attribute__((amdgpu_waves_per_eu(AOS2_DESC_WPE, 8)))
-#else
-#define DESC_ATTR
-#endif
 template <int DK>
-__global__ __launch_bounds__(64) DESC_ATTR void describe_kernel(const uint8_t *__restrict__ img0,
+__global__ __launch_bounds__(64) void describe_kernel(const uint8_t *__restrict__ img0,
                                                       size_t img0_stride, int pitch0,
                                                       const uint8_t *__restrict__ pyr,
                                                       size_t pyr_stride,
@@ -1285,265 +1110,6 @@ __global__ __launch_bounds__(64) DESC_ATTR void describe_kernel(const uint8_t *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// The reference's own form of the blur (src/ORBextractor.cc:1085-1086: GaussianBlur(workingMat, 7x7, sigma 2, BORDER_REFLECT_101)
-// of every whole level before its descriptors) as a streaming pass: AOS2_DESC_BLUR=level.  A/B against the per-keypoint blur
-// of describe_kernel above (profiles/README.md, round 4): the whole pyramid is blurred once (0.95 M pixels per 640x480 frame
-// instead of ~1.5 M pixel-blurs over the overlapping 43x37 patches of 1000 keypoints) but goes to HBM and back.
-//
-// blur_levels_kernel: one launch for all levels.  A lane owns 4 adjacent output pixels x BL_ROWS rows: per source row one
-// horizontal pass (the three dwords around the quad, 10 v_dot4 with the taps shifted in the weights -- describe_kernel's h-pass),
-// the last 7 rows' sums stay in registers, per output row the symmetric vertical pass (3 adds + 4 multiply-adds per pixel),
-// (sum + 2^15) >> 16 saturated, one aligned 32-bit store.  Same integer arithmetic as the per-keypoint form: same bytes.
-// ---------------------------------------------------------------------------------------------
-constexpr int BL_ROWS = 16;
-struct BlurPlan {
-    int first[9];            // first item of each level (item = (band, quad)); first[n_levels] = total
-    int nq[8];               // quads per row
-    int nq_in[8];            // ... of which interior (quads 1 .. nq_in: the 12 bytes around them lie inside the row); a level's interior
-                             // items come first, the edge quads (0 and the last two or three of a row, REFLECT_101 byte by byte) behind
-                             // them in waves of their own: mixed into every wave they doubled the kernel's time
-    uint32_t dst_off[8];     // byte offset of the level's blurred plane inside one image's block
-    int dst_pitch[8];
-};
-
-__global__ __launch_bounds__(256) void blur_levels_kernel(const uint8_t *__restrict__ img0, size_t img0_stride, int pitch0,
-                                                          const uint8_t *__restrict__ pyr, size_t pyr_stride,
-                                                          const LevelDev *__restrict__ levels, int n_levels, BlurPlan plan,
-                                                          uint8_t *__restrict__ blur, size_t blur_stride)
-{
-    const int b = blockIdx.y;
-    const int it = blockIdx.x * 256 + threadIdx.x;
-    if (it >= plan.first[n_levels]) return;
-    int l = 0;
-    while (l + 1 < n_levels && it >= plan.first[l + 1]) ++l;
-    const LevelDev &L = levels[l];
-    const int w = L.w, h = L.h, pitch = l == 0 ? pitch0 : L.pitch;
-    const uint8_t *plane = l == 0 ? img0 + (size_t)b * img0_stride : pyr + (size_t)b * pyr_stride + L.off;
-    uint8_t *dst = blur + (size_t)b * blur_stride + plan.dst_off[l];
-    const int dpitch = plan.dst_pitch[l];
-    const int id = it - plan.first[l], nq = plan.nq[l], nqi = plan.nq_in[l], nbands = (h + BL_ROWS - 1) / BL_ROWS;
-    int band, q;
-    if (id < nbands * nqi) {
-        band = id / nqi;
-        q = 1 + (id - band * nqi);
-    } else {
-        const int ne = nq - nqi, ie = id - nbands * nqi;
-        band = ie / ne;
-        q = ie - band * ne;
-        q = q == 0 ? 0 : nqi + q;   // quad 0, then the quads behind the interior ones
-    }
-    const int x0 = 4 * q, y0 = band * BL_ROWS;
-    const uint32_t g0 = c_gauss[0], g1 = c_gauss[1], g2 = c_gauss[2], g3 = c_gauss[3];
-    const uint32_t g[7] = {g0, g1, g2, g3, g2, g1, g0};
-    auto wq = [&](int first) {   // weights of taps first .. first+3 (taps outside 0..6 are 0)
-        uint32_t wv = 0;
-        for (int k = 0; k < 4; ++k)
-            if (first + k >= 0 && first + k < 7) wv |= g[first + k] << (8 * k);
-        return wv;
-    };
-    const uint32_t WA0 = wq(0), WA1 = wq(4), WB0 = wq(-1), WB1 = wq(3), WC0 = wq(-2), WC1 = wq(2), WC2 = wq(6);
-    const uint32_t WD0 = wq(-3), WD1 = wq(1), WD2 = wq(5);
-    const bool inner = x0 >= 3 && x0 + 8 < w;   // the 12 bytes x0 - 3 .. x0 + 8 lie inside the row
-    uint32_t hs[7][4];
-#pragma unroll
-    for (int r = 0; r < BL_ROWS + 6; ++r) {
-        // source row y0 + r - 3 (REFLECT_101 at the level's edges); rows past the band's last needed one are skipped
-        const int ys = y0 + r - 3;
-        uint32_t D0, D1, D2;
-        if (ys - 3 < h) {   // (row ys feeds output rows ys - 3 .. ys + 3: needed iff ys - 3 < h)
-            const uint8_t *row = plane + (size_t)reflect101(ys, h) * pitch;
-            if (inner) {
-                D0 = load_u32_unaligned(row + x0 - 3);
-                D1 = load_u32_unaligned(row + x0 + 1);
-                D2 = load_u32_unaligned(row + x0 + 5);
-            } else {
-                uint32_t d[3] = {0, 0, 0};
-#pragma unroll
-                for (int k = 0; k < 10; ++k) d[k >> 2] |= (uint32_t)row[reflect101(x0 - 3 + k, w)] << (8 * (k & 3));
-                D0 = d[0]; D1 = d[1]; D2 = d[2];
-            }
-        } else
-            D0 = D1 = D2 = 0;
-        uint32_t *o = hs[r % 7];
-        o[0] = __builtin_amdgcn_udot4(D0, WA0, __builtin_amdgcn_udot4(D1, WA1, 0u, false), false);
-        o[1] = __builtin_amdgcn_udot4(D0, WB0, __builtin_amdgcn_udot4(D1, WB1, 0u, false), false);
-        o[2] = __builtin_amdgcn_udot4(D0, WC0, __builtin_amdgcn_udot4(D1, WC1, __builtin_amdgcn_udot4(D2, WC2, 0u, false), false), false);
-        o[3] = __builtin_amdgcn_udot4(D0, WD0, __builtin_amdgcn_udot4(D1, WD1, __builtin_amdgcn_udot4(D2, WD2, 0u, false), false), false);
-        if (r >= 6) {
-            const int y = y0 + r - 6;
-            if (y < h) {
-                uint32_t out = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t a0 = hs[(r - 6) % 7][k] + hs[r % 7][k], a1 = hs[(r - 5) % 7][k] + hs[(r - 1) % 7][k];
-                    const uint32_t a2 = hs[(r - 4) % 7][k] + hs[(r - 2) % 7][k], a3 = hs[(r - 3) % 7][k];
-                    uint32_t v = __umul24(a0, g0) + (1u << 15);
-                    v += __umul24(a1, g1);
-                    v += __umul24(a2, g2);
-                    v += __umul24(a3, g3);
-                    out |= min(v >> 16, 255u) << (8 * k);
-                }
-                *reinterpret_cast<uint32_t *>(dst + (size_t)y * dpitch + x0) = out;
-            }
-        }
-    }
-}
-
-// describe_kernel on a blurred pyramid: per keypoint the raw 31-row disc for IC_Angle and the 37x37 blurred tile are staged (no
-// reflection: a keypoint lies >= 19 pixels inside its level, the pattern reaches 18), then the steered comparisons.
-constexpr int RP = 9;      // dwords per raw row staged (36 bytes: columns -17 .. +18; IC_Angle reads -15 .. +15)
-constexpr int BP = 40;     // byte pitch of the blurred tile in LDS ([y][x], 37 used)
-__global__ __launch_bounds__(64) void describe_blur_kernel(const uint8_t *__restrict__ img0, size_t img0_stride, int pitch0,
-                                                           const uint8_t *__restrict__ pyr, size_t pyr_stride,
-                                                           const uint8_t *__restrict__ blur, size_t blur_stride, BlurPlan plan,
-                                                           const LevelDev *__restrict__ levels, int n_levels,
-                                                           const uint32_t *__restrict__ sel, size_t sel_stride, int cap_level,
-                                                           const int32_t *__restrict__ sel_level_cnt,
-                                                           aos2_keypoint_t *__restrict__ kps, uint8_t *__restrict__ desc, int cap,
-                                                           int32_t *__restrict__ n_out, int32_t *__restrict__ status, int batch)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t raw32[31 * RP + 1];
-    __shared__ __attribute__((aligned(16))) uint32_t bl32[BW * (BP / 4)];
-    const int b = blockIdx.x;
-    if (b >= batch) return;
-    const int lane = threadIdx.x;
-    const int k0 = blockIdx.y * DKB;
-    int lv_pitch = 0, lv_sp = 0, lv_bpitch = 0;
-    uint32_t lv_off = 0, lv_boff = 0;
-    float lv_scale = 0.f;
-    if (lane < n_levels) {
-        const LevelDev &L = levels[lane];
-        lv_pitch = lane == 0 ? pitch0 : L.pitch; lv_off = (uint32_t)L.off;
-        lv_sp = L.scaled_patch; lv_scale = L.scale;
-        lv_boff = plan.dst_off[lane]; lv_bpitch = plan.dst_pitch[lane];
-    }
-    const int32_t *cnt = sel_level_cnt + (size_t)b * n_levels;
-    int my_level = -1, my_kin = k0 + lane, total = 0, worst = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        const int c = cnt[l] > 0 ? cnt[l] : 0;
-        worst = min(worst, cnt[l]);
-        if (my_level < 0 && my_kin < c) my_level = l;
-        if (my_level < 0) my_kin -= c;
-        total += c;
-    }
-    if (k0 == 0 && lane == 0) {
-        n_out[b] = total;
-        if (worst < 0) atomicMin(status, worst);
-        if (total > cap) atomicMax(status + 1, total);
-    }
-    const int nk = min(DKB, min(total, cap) - k0);
-    if (nk <= 0) return;
-    uint32_t my_sel = 0;
-    if (lane < nk) my_sel = sel[(size_t)b * sel_stride + (size_t)my_level * cap_level + my_kin];
-    const uint8_t *img_pyr = pyr + (size_t)b * pyr_stride, *img_l0 = img0 + (size_t)b * img0_stride;
-    const uint8_t *img_bl = blur + (size_t)b * blur_stride;
-    const uint8_t *bl8 = reinterpret_cast<const uint8_t *>(bl32);
-    uint32_t pats[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) pats[r] = *reinterpret_cast<const uint32_t *>(&c_pattern[4 * (r * 64 + lane)]);
-    const int ic_rs = (lane * 57) >> 9, ic_dj = lane - 9 * ic_rs + 1;   // IC_Angle: 7 rows x 9 dwords
-    // staging grids: raw 31 rows x 9 dwords = 279 items (5 rounds), blurred 37 rows x 10 dwords = 370 items (6 rounds); the loads
-    // of keypoint i + 1 are in flight while keypoint i is processed out of LDS (like describe_kernel's prefetch)
-    struct Slot {
-        int level, kx, ky, score;
-    };
-    auto locate = [&](int i) {
-        Slot sl;
-        sl.level = __builtin_amdgcn_readlane(my_level, i);
-        const uint32_t csel = (uint32_t)__builtin_amdgcn_readlane((int)my_sel, i);
-        sl.kx = (int)(csel & 0xfff) + 16;
-        sl.ky = (int)((csel >> 12) & 0xfff) + 16;
-        sl.score = (int)(csel >> 24);
-        return sl;
-    };
-    uint32_t rw[5], bw[6];
-    auto prefetch = [&](const Slot &sl) {
-        const int pitch = __builtin_amdgcn_readlane(lv_pitch, sl.level), bpitch = __builtin_amdgcn_readlane(lv_bpitch, sl.level);
-        const uint8_t *plane = sl.level == 0 ? img_l0 : img_pyr + (uint32_t)__builtin_amdgcn_readlane((int)lv_off, sl.level);
-        const uint8_t *bplane = img_bl + (uint32_t)__builtin_amdgcn_readlane((int)lv_boff, sl.level);
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            const int id = lane + 64 * t, rr = id / RP, cc = id - rr * RP;
-            rw[t] = id < 31 * RP ? load_u32_unaligned(plane + (size_t)(sl.ky - 15 + rr) * pitch + (sl.kx - 17 + 4 * cc)) : 0u;
-        }
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            const int id = lane + 64 * t, rr = id / 10, cc = id - rr * 10;
-            bw[t] = id < BW * 10 ? load_u32_unaligned(bplane + (size_t)(sl.ky - HR + rr) * bpitch + (sl.kx - HR + 4 * cc)) : 0u;
-        }
-    };
-    Slot cur = locate(0);
-    prefetch(cur);
-    for (int i = 0; i < nk; ++i) {
-        const int k = k0 + i;
-        const int level = cur.level, kx = cur.kx, ky = cur.ky, score = cur.score;
-        wave_lds_phase();   // (the previous keypoint's reads are done)
-#pragma unroll
-        for (int t = 0; t < 5; ++t)
-            if (lane + 64 * t < 31 * RP) raw32[lane + 64 * t] = rw[t];
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-            if (lane + 64 * t < BW * 10) bl32[lane + 64 * t] = bw[t];
-        if (i + 1 < nk) {
-            cur = locate(i + 1);
-            prefetch(cur);
-        }
-        wave_lds_phase();
-        // ---- IC_Angle: integer moments over the circular patch, 4 pixels per LDS dword.  Raw dword (row vr, dj - 1) holds the
-        // columns u = 4 dj - 21 .. 4 dj - 18 -- the alignment of describe_kernel's patch dwords 1..9, so its byte masks apply
-        int m10 = 0, m01 = 0;
-        if (ic_rs < 7) {
-            const int c0 = 4 * ic_dj - PR;
-            for (int vr = ic_rs; vr < 31; vr += 7) {
-                const uint32_t d = raw32[vr * RP + ic_dj - 1] & c_icmask[vr * 9 + ic_dj - 1];
-                const int S = (int)__builtin_amdgcn_udot4(d, 0x01010101u, 0u, false);
-                const int T = (int)__builtin_amdgcn_udot4(d, 0x03020100u, 0u, false);
-                m10 += c0 * S + T;
-                m01 += (vr - 15) * S;
-            }
-        }
-        m10 = wave_sum_i32(m10);
-        m01 = wave_sum_i32(m01);
-        const float angle = fast_atan2_deg((float)m01, (float)m10);
-        const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
-        const float ang = __fmul_rn(angle, factorPI);
-        float a, bb;
-        sincos_exact(ang, &bb, &a);
-        unsigned long long words[4];
-        const float MAGIC = 12582912.f;
-        const uint32_t K = 0x400000u * (uint32_t)BP + 0x4B400000u - (uint32_t)(HR * BP + HR);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t pat = pats[r];
-            int val[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float px = (float)(int8_t)(pat >> (16 * q)), py = (float)(int8_t)(pat >> (16 * q + 8));
-                const float fy = __fadd_rn(__fadd_rn(__fmul_rn(px, bb), __fmul_rn(py, a)), MAGIC);
-                const float fx = __fadd_rn(__fsub_rn(__fmul_rn(px, a), __fmul_rn(py, bb)), MAGIC);
-                const uint32_t off = (uint32_t)(__mul24(__builtin_bit_cast(int, fy), BP) + __builtin_bit_cast(int, fx)) - K;
-                val[q] = bl8[off];
-            }
-            words[r] = __ballot(val[0] < val[1]);
-        }
-        if (lane == 0) {
-            unsigned long long *d = reinterpret_cast<unsigned long long *>(desc + ((size_t)b * cap + k) * 32);
-            d[0] = words[0]; d[1] = words[1]; d[2] = words[2]; d[3] = words[3];
-            aos2_keypoint_t kp;
-            const float scale = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lv_scale), level));
-            kp.x = level != 0 ? __fmul_rn((float)kx, scale) : (float)kx;
-            kp.y = level != 0 ? __fmul_rn((float)ky, scale) : (float)ky;
-            kp.size = (float)__builtin_amdgcn_readlane(lv_sp, level);
-            kp.angle = angle;
-            kp.response = (float)score;
-            kp.octave = level;
-            kp.class_id = -1;
-            kps[(size_t)b * cap + k] = kp;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // The whole pyramid of an image in ONE launch (ComputePyramid, src/ORBextractor.cc:1107-1132: level k is cv::resize of
 // level k - 1).  A workgroup owns one tile of every level (the tiles of a workgroup sit on top of each other) and walks
 // the levels through two LDS buffers: level k - 1's region -> level k's region, of which it stores the part it owns.
@@ -1663,14 +1229,6 @@ void launch_fast(const uint8_t *img0, size_t img0_stride, int pitch0, const uint
                        min_th, TP, TH, SP, slots, slot_stride, cell_cnt, list_cap, keep_cap, batch);
 }
 
-void launch_compact(const CellDev *cells, int n_cells, int n_levels, const int *level_cell_begin,
-                    const uint32_t *slots, size_t slot_stride, const int32_t *cell_cnt, uint32_t *dense,
-                    size_t dense_stride, int32_t *level_off, int batch, hipStream_t st)
-{
-    hipLaunchKernelGGL(compact_candidates_kernel, dim3(batch), dim3(256), 0, st, cells, n_cells, n_levels,
-                       level_cell_begin, slots, slot_stride, cell_cnt, dense, dense_stride, level_off);
-}
-
 void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
                    int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
                    int32_t *sel_level_cnt, int cap_level, int lds_bytes, hipStream_t st)
@@ -1687,19 +1245,6 @@ void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather
                        levels, n_levels, batch, scr, sel, sel_stride, sel_level_cnt, cap_level, lds_bytes, group_levels);
 }
 
-int prepare_octree_image_kernel(int total_lds)
-{
-    return (int)hipFuncSetAttribute((const void *)octree_image_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, total_lds);
-}
-
-void launch_octree_image(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                         int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                         int32_t *sel_level_cnt, int cap_level, const OctImageLayout &lay, hipStream_t st)
-{
-    hipLaunchKernelGGL(octree_image_kernel, dim3(batch), dim3(64 * n_levels), (size_t)lay.total, st, dense, dense_stride,
-                       gather, levels, n_levels, scr, sel, sel_stride, sel_level_cnt, cap_level, lay);
-}
-
 int prepare_octree_pair_kernel(int total_lds)
 {
     return (int)hipFuncSetAttribute((const void *)octree_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, total_lds);
@@ -1711,53 +1256,6 @@ void launch_octree_pairs(uint32_t *dense, size_t dense_stride, const OctGather &
 {
     hipLaunchKernelGGL(octree_pair_kernel, dim3(batch * ((n_levels + 1) / 2)), dim3(128), (size_t)lay.total, st, dense, dense_stride,
                        gather, levels, n_levels, batch, scr, sel, sel_stride, sel_level_cnt, cap_level, lay);
-}
-
-// blurred planes of one image: level 0 first (pitch = width rounded up to 16), then the levels >= 1 at their pyramid offsets
-size_t blur_plan(const LevelDev *h_levels, int n_levels, size_t pyr_bytes, BlurPlanHost *out)
-{
-    const size_t l0 = (size_t)((h_levels[0].w + 15) & ~15) * h_levels[0].h;
-    const size_t l0_bytes = (l0 + 255) & ~(size_t)255;
-    int first = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        out->first[l] = first;
-        out->nq[l] = (h_levels[l].w + 3) / 4;
-        out->nq_in[l] = std::max(0, std::min(out->nq[l] - 1, (h_levels[l].w - 9) / 4));   // quads q >= 1 with 4 q + 8 < w
-        first += out->nq[l] * ((h_levels[l].h + BL_ROWS - 1) / BL_ROWS);
-        out->dst_off[l] = l == 0 ? 0u : (uint32_t)(l0_bytes + h_levels[l].off);
-        out->dst_pitch[l] = l == 0 ? (h_levels[0].w + 15) & ~15 : h_levels[l].pitch;
-    }
-    out->first[n_levels] = first;
-    return l0_bytes + pyr_bytes;
-}
-
-static BlurPlan to_dev(const BlurPlanHost &h)
-{
-    BlurPlan p;
-    for (int i = 0; i < 9; ++i) p.first[i] = h.first[i];
-    for (int i = 0; i < 8; ++i) {
-        p.nq[i] = h.nq[i]; p.nq_in[i] = h.nq_in[i]; p.dst_off[i] = h.dst_off[i]; p.dst_pitch[i] = h.dst_pitch[i];
-    }
-    return p;
-}
-
-void launch_blur_levels(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                        const LevelDev *levels, int n_levels, const BlurPlanHost &plan, uint8_t *blur, size_t blur_stride, int batch,
-                        hipStream_t st)
-{
-    dim3 grd((plan.first[n_levels] + 255) / 256, batch);
-    hipLaunchKernelGGL(blur_levels_kernel, grd, dim3(256), 0, st, img0, img0_stride, pitch0, pyr, pyr_stride, levels, n_levels, to_dev(plan),
-                       blur, blur_stride);
-}
-
-void launch_describe_blur(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                          const uint8_t *blur, size_t blur_stride, const BlurPlanHost &plan, const LevelDev *levels, int n_levels,
-                          const uint32_t *sel, size_t sel_stride, int cap_level, const int32_t *sel_level_cnt,
-                          aos2_keypoint_t *kps, uint8_t *desc, int cap, int32_t *n_out, int batch, int32_t *status, hipStream_t st)
-{
-    dim3 blk(64), grd((batch + 7) & ~7, (cap + DKB - 1) / DKB);
-    hipLaunchKernelGGL(describe_blur_kernel, grd, blk, 0, st, img0, img0_stride, pitch0, pyr, pyr_stride, blur, blur_stride, to_dev(plan),
-                       levels, n_levels, sel, sel_stride, cap_level, sel_level_cnt, kps, desc, cap, n_out, status, batch);
 }
 
 void launch_describe(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,

@@ -132,10 +132,7 @@ __device__ __forceinline__ ProjLastDev last_of(const FramesDev &cur, const Frame
 // a wave per query (4 waves per workgroup measured slower: 0.48 vs 0.43 ms for 256 frames)
 // (a wave per query, one query per workgroup: four waves per workgroup were measured for the 540 k / 768 k workgroup grids of a
 // 512-frame batch -- slower: 0.265 -> 0.286 and 0.204 -> 0.235 ms for the two fill kernels)
-#ifndef AOS2_ENTRY_WAVES
-#define AOS2_ENTRY_WAVES 1
-#endif
-constexpr int kEntryWaves = AOS2_ENTRY_WAVES;
+constexpr int kEntryWaves = 1;
 __global__ __launch_bounds__(64 * kEntryWaves) void frames_last_entries_kernel(FramesDev cur, FramesDev last, MapPointsDev M, float th, int mono,
                                                                  QuerySlot *slots, Entry *pool, int32_t *overflow, int phase, QueryRec *rec)
 {
@@ -398,7 +395,7 @@ static int frames_init(aos2_frames *f)
     int st = bind_device(f->device);
     if (st) return st;
     if (f->dev_ready) return AOS2_OK;
-    if (int st_ = stream_create(&f->stream, stream_priority_env("AOS2_PRIO_FRAMES"))) return st_;
+    if (int st_ = stream_create(&f->stream, false)) return st_;
     for (auto &e : f->ev) AOS2_HIP_CHECK(hipEventCreate(&e));
     // member arrays
     const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap, n = B * cap;

@@ -72,7 +72,6 @@ struct LmState {
     int32_t err_at;
     int32_t pad_;
     double tr_rho[48], tr_temp[48], tr_cur[48], tr_lambda[48];
-    long long dbg[16];      // cycle counters of the last reduced-system kernel (AOS2_LBA_TRACE=1)
 };
 
 // device-side view of one window
@@ -135,20 +134,6 @@ struct SchurTask {
 // bool SparseOptimizer::terminate(): counts the evaluation, latches the flag
 // `seen` >= 0: the value of the flag read by the caller shortly before (the word lives in host memory: a read is a PCIe
 // round trip, which the decision starts ahead of its other loads)
-// (measurement switch, off: a raised wave priority for LocalBA's kernels -- chains of dependent memory and f64 operations at low
-// occupancy -- so that they issue ahead of another stream's VALU-bound waves on the same SIMD, like octree_kernel's.  The composite
-// did not move: 72.5 / 72.5 k frames/s without, 70.8 / 72.2 k with priority 2, 71.9 k with 3; the batch alone 4.10 ms either way
-// (profiles/r06_composite_decomposition.txt).  What LocalBA costs the step is not issue order.)
-#ifndef AOS2_LBA_WAVE_PRIO
-#define AOS2_LBA_WAVE_PRIO 0
-#endif
-__device__ __forceinline__ void lba_wave_prio()
-{
-#if AOS2_LBA_WAVE_PRIO > 0
-    __builtin_amdgcn_s_setprio(AOS2_LBA_WAVE_PRIO);
-#endif
-}
-
 __device__ inline bool lm_poll(LmState *st, const int32_t *abort_word, int seen = -1)
 {
     st->polls++;
@@ -201,7 +186,6 @@ __device__ __forceinline__ void workgroup_sum2(double v0, double v1, double *out
 // Converter::toSE3Quat / toVector3d and the float -> double copies of Optimizer.cc:523-525, 552-553, 597-606
 __global__ __launch_bounds__(256) void k_prepare(const LbaWin *__restrict__ wins, int stop_at_poll)
 {
-    lba_wave_prio();
     const LbaWin &W = wins[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < W.n_poses) pose_from_Tcw(W.in_Tcw + 16 * (size_t)i, W.pose + 7 * (size_t)i);
@@ -333,13 +317,7 @@ __device__ __forceinline__ void lm_decide(const LbaWin &W)
     // pbStopFlag lives in host memory: its read (a PCIe round trip) travels together with the loads of the sums
     const int flag_seen = threadIdx.x == 0 && W.abort_word ? __hip_atomic_load(W.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0;
     double tempChi, scale;
-#if defined(AOS2_TAIL_TIMING)
-    const long long tt0 = wall_clock64();
-#endif
     canonical_sums(W, true, tempChi, scale);
-#if defined(AOS2_TAIL_TIMING)
-    const long long tt1 = wall_clock64();
-#endif
     if (threadIdx.x == 0) {
         const int pass = st->phase == 0 ? 0 : 1;
         const bool ok2 = W.np == 0 || W.scal[3] != 0.0;
@@ -405,11 +383,6 @@ __device__ __forceinline__ void lm_decide(const LbaWin &W)
             }
         }
         st->lin = lin;
-#if defined(AOS2_TAIL_TIMING)
-        st->dbg[12] += tt1 - tt0;
-        st->dbg[13] += wall_clock64() - tt1 + (flag_seen & 0);
-        st->dbg[14] += 1;
-#endif
     }
     __syncthreads();
     // pop() after a rejected step (SparseOptimizer::push / pop, sparse_optimizer.cpp:600-610).  The backup holds the
@@ -584,19 +557,10 @@ __device__ __forceinline__ void lrec_backsub(const Cam &cam, const dbl4_t rec, c
 // thread adds the per-edge terms in edge order, so the sums are the ones a thread walking the edges one after the other
 // would form (the order g2o adds them in), while the chain of dependent gathers per thread is one edge long instead of
 // the whole observation list (a single window has only ~2000 landmarks: the walk was pure latency).
-// Timing-only ablation builds (tools/build_lba_abl_libs.sh; results are wrong by construction): one phase switched off at a
-// time under rocprofv3 -- 1: k_points_walk without the deciding tail, 2: without the residual loop, 3: without the
-// back-substitution loop, 5: k_lin landmark blocks only, 6: k_lin keyframe blocks only.  (DESIGN.md 5.3's table)
-#ifndef AOS2_LBA_ABL
-#define AOS2_LBA_ABL 0
-#endif
 constexpr int kLmBlock = 32, kLmSlots = 8;
 // edges of a landmark fetched together by the one-thread-per-landmark kernels (measured on 32 windows of 24 k edges, 6
 // observations per landmark: k_points_walk 43.4 us with 4 / 4, 38.6 with 6 / 6; the linearisation spills beyond 4)
-#ifndef AOS2_WALK_CHUNK
-#define AOS2_WALK_CHUNK 4
-#endif
-constexpr int kWalkChunk = AOS2_WALK_CHUNK;   // free-keyframe edges (back-substitution)
+constexpr int kWalkChunk = 4;     // free-keyframe edges (back-substitution)
 constexpr int kWalkChunkE = 6;     // all edges (residuals)
 constexpr int kWalkChunkLin = 4;   // all edges (linearisation)
 
@@ -609,7 +573,6 @@ constexpr int kWalkChunkLin = 4;   // all edges (linearisation)
 // Landmark l leaves its chi2 terms in part[l] and its scale terms in part[nl + l] (canonical_sums adds them).
 __global__ __launch_bounds__(256) void k_points(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks, int solve)
 {
-    lba_wave_prio();
     __shared__ double s_v[kLmBlock][kLmSlots][3];
     __shared__ double s_X[kLmBlock][3];
     const SchurTask tk = tasks[blockIdx.x];
@@ -715,7 +678,6 @@ __global__ __launch_bounds__(256) void k_points(const LbaWin *__restrict__ wins,
 // leave the same bits.
 __global__ __launch_bounds__(128) void k_points_walk(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks, int solve)
 {
-    lba_wave_prio();
     const SchurTask tk = tasks[blockIdx.x];
     const LbaWin &W = wins[tk.w];
     if (!(solve ? W.st->run : W.st->initp)) return;
@@ -730,11 +692,7 @@ __global__ __launch_bounds__(128) void k_points_walk(const LbaWin *__restrict__ 
             double cl[3] = {W.b[n6 + 3 * l], W.b[n6 + 3 * l + 1], W.b[n6 + 3 * l + 2]};
             // The walk is a chain of dependent gathers (edge list -> edge -> keyframe); kWalkChunk edges are fetched level by
             // level together, then their terms are added in edge order (the same sums, a quarter of the round trips).
-#if AOS2_LBA_ABL == 3
-            const int a0 = 0, a1 = 0;
-#else
             const int a0 = W.pl_off[l], a1 = W.pl_off[l + 1];
-#endif
             for (int a = a0; a < a1; a += kWalkChunk) {
                 int ka[kWalkChunk], i1[kWalkChunk];   // (positions in the list = the indices of the dense Hpl array)
 #pragma unroll
@@ -774,11 +732,7 @@ __global__ __launch_bounds__(128) void k_points_walk(const LbaWin *__restrict__ 
                 sc += xl * (lambda * xl + W.b[n6 + 3 * l + r]);
             }
         }
-#if AOS2_LBA_ABL == 2
-        const int e0 = 0, e1 = 0;
-#else
         const int e0 = W.pt_off[l], e1 = W.pt_off[l + 1];
-#endif
         for (int a = e0; a < e1; a += kWalkChunkE) {
             int e[kWalkChunkE], ep[kWalkChunkE];
             uint8_t lv1[kWalkChunkE], ste[kWalkChunkE], rob[kWalkChunkE];
@@ -819,9 +773,7 @@ __global__ __launch_bounds__(128) void k_points_walk(const LbaWin *__restrict__ 
         store_dev(W.part + l, chi);
         store_dev(W.part + W.nl + l, sc);
     }
-#if AOS2_LBA_ABL != 1
     if (solve) points_tail<128>(W);
-#endif
 }
 
 // robustified information of an edge (BaseBinaryEdge::constructQuadraticForm, base_binary_edge.hpp:55-120):
@@ -1074,17 +1026,11 @@ __device__ __forceinline__ void lin_poses_body(const LbaWin &W, int ph, int init
 template <bool kWalk>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_lin(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks, int init)
 {
-    lba_wave_prio();
     const SchurTask tk = tasks[blockIdx.x];
     const LbaWin &W = wins[tk.w];
     if (!(init ? W.st->initp : W.st->lin)) return;
     const int blk = tk.code & 0x0fffffff;
     const bool keyframe = (tk.code >> 28) != 0;
-#if AOS2_LBA_ABL == 5
-    if (keyframe) return;
-#elif AOS2_LBA_ABL == 6
-    if (!keyframe) return;
-#endif
     if (keyframe)
         lin_poses_body(W, blk, init);
     else if (kWalk)
@@ -1097,7 +1043,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // (computeLambdaInit :166-180), ni = 2; the first trial's push() (the backup of the estimates)
 __global__ __launch_bounds__(1024) void k_lm_init(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     __shared__ double sh[1024];
     const LbaWin &W = wins[blockIdx.x];
     LmState *st = W.st;
@@ -1164,17 +1109,7 @@ constexpr int kSchurDiag = 0, kSchurBig = 1, kSchurPack = 2;
 // and the products with E = [ [a b 1]x | -iz I ] are cross products: the two 144-byte blocks are neither stored nor fetched --
 // each side is its 32-byte record (LbaWin::lrec) and the keyframe's rotation (uniform over the block: a broadcast load) --
 // and an item takes ~360 operations instead of the ~350 of the stored-block form plus 23 divergent 16-byte requests (9 now).
-#ifndef AOS2_SCHUR_FMA
-#define AOS2_SCHUR_FMA 0
-#endif
-__device__ __forceinline__ double sf(double a, double b, double c)
-{
-#if AOS2_SCHUR_FMA
-    return __builtin_fma(a, b, c);
-#else
-    return a * b + c;
-#endif
-}
+__device__ __forceinline__ double sf(double a, double b, double c) { return a * b + c; }
 template <bool kDiag>
 __device__ __forceinline__ void schur_item(const LbaWin &W, int j, double lambda, int n6, const double *__restrict__ Ra_g,
                                            const double *__restrict__ Rb_g, double (&acc)[42])
@@ -1285,13 +1220,10 @@ __device__ __forceinline__ void schur_store(const LbaWin &W, int i1, int i2, int
     // (bschur of a diagonal unit: k_schur, after its b_p pass)
 }
 
-#ifndef AOS2_SCHUR_WPE
-#define AOS2_SCHUR_WPE 3   // workgroups per compute unit (one wave of a workgroup per SIMD)
-#endif
-__global__ __launch_bounds__(kSchurThreads) __attribute__((amdgpu_waves_per_eu(AOS2_SCHUR_WPE, AOS2_SCHUR_WPE)))
+// three workgroups per compute unit (one wave of a workgroup per SIMD)
+__global__ __launch_bounds__(kSchurThreads) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_schur(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks)
 {
-    lba_wave_prio();
     constexpr int NT = kSchurThreads;
     __shared__ double red[(NT / 16) * 43];
     __shared__ int32_t s_info[16], s_ij[16];
@@ -1411,13 +1343,6 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 // with the same look-ahead (x_k = T_k^T s_k, one barrier per panel); finally the first np threads apply the update to
 // the poses.  (The former version -- 4 waves, panel by per-row substitution with 16 divisions per row, predicated
 // pivot updates, separate forward / backward passes by one wave -- took 76 us at 20 free keyframes.)
-// cycle counters of the phases (s_memtime) for tools: compile with -DAOS2_LDLT_TIMING; off by default (every timestamp waits
-// for the wave's outstanding LDS traffic)
-#ifdef AOS2_LDLT_TIMING
-#define LDLT_T(...) __VA_ARGS__
-#else
-#define LDLT_T(...)
-#endif
 // kGlob: the same algorithm for a reduced system beyond LDS (more than 21 free keyframes: npad > 128) -- the matrix lives in the
 // device memory (in place in Wn.Hs, which k_schur wrote with leading dimension npad: 240 x 240 doubles at 40 free keyframes,
 // L2-resident), everything else (the panel's L D,
@@ -1426,10 +1351,7 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 // wave_sync() = completion of the wave's outstanding stores.  The pivot chain of the diagonal blocks never touches memory, so
 // what the variant pays is one device-memory round trip per phase instead of an LDS one (measured: DESIGN.md 5.3).
 typedef double __attribute__((address_space(1))) gdouble_t;
-#ifndef AOS2_LDLT_TILE_BATCH
-#define AOS2_LDLT_TILE_BATCH 4
-#endif
-constexpr int kTileBatch = AOS2_LDLT_TILE_BATCH;
+constexpr int kTileBatch = 4;
 template <bool kGlob>
 __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 {
@@ -1451,7 +1373,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
     double *xs = rv + npad;                      // npad: solution
     double *Tb = xs + npad;                      // 2 x 16 x 17: T_k^T of the current / next panel
     double *Dst = Tb + 2 * 16 * 17;              // kGlob: 16 x 17, the next diagonal block on its way from the trailing update to wave 0's rows
-    LDLT_T(long long tD = 0, tP = 0, tU = 0, t_a = 0; const long long t_begin = __builtin_amdgcn_s_memtime();)
     if (tid == 0) s_fail = 0;
     // load (identity-padded), lower BLOCK triangle only -- row r needs its columns up to the end of its diagonal block,
     // nothing reads the blocks above the diagonal -- as element pairs (n is even, rows are 16-byte aligned): block row R
@@ -1494,7 +1415,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
     }
     for (int i = tid; i < npad; i += NT) rv[i] = i < n ? Wn.bs[i] : 0.0;
     __syncthreads();
-    LDLT_T(const long long t_loaded = __builtin_amdgcn_s_memtime();)
     auto wave_sync = [] {   // LDS writes of this wave visible to its other lanes (one wave: LDS operations execute in order)
         if (kGlob) {   // ... and its stores to the device scratch complete before its other lanes load them
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1513,7 +1433,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
     // while the reciprocal is refined (30 v_readlane would cost 200 cycles of issue), and nothing is predicated: the
     // upper halves of the rows are scratch.  T = L_kk^-1 is built on the way -- lane c owns column c,
     // T <- (I - l_j e_j^T) T needs only column j of L, which every lane has just read -- and so is y_k = L_kk^-1 r_k.
-    LDLT_T(long long dt1 = 0, dt2 = 0, dt3 = 0, dt4 = 0;)
     auto rcp_newton = [](double d) {   // 1 / d within 1 ulp: v_rcp_f64 + two Newton steps (34 cycles; the IEEE division takes 67)
         double rd = __builtin_amdgcn_rcp(d);
         double e = __builtin_fma(-d, rd, 1.0);
@@ -1522,7 +1441,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
         return __builtin_fma(rd, e, rd);
     };
     auto diag_block = [&](int k0, bool staged) {
-        LDLT_T(const long long q0 = __builtin_amdgcn_s_memtime();)
         const int li = lane & 15;
         double *colbuf = xs;   // 16 doubles of scratch (xs is unused until the backward pass)
         double *Tk = Tb + ((k0 >> 4) & 1) * (16 * 17);
@@ -1548,7 +1466,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 #pragma unroll
         for (int c = 0; c < 16; ++c) t[c] = c == li ? 1.0 : 0.0;
         __builtin_amdgcn_sched_barrier(0);
-        LDLT_T(const long long q1 = __builtin_amdgcn_s_memtime(); dt1 += q1 - q0;)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const double ci = row[j];
@@ -1578,7 +1495,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             cur = li > j ? __builtin_fma(-lij, yj, cur) : cur;   // forward substitution inside the block
             __builtin_amdgcn_sched_barrier(0);   // keep the pivots apart (hoisting the later pivots' reads only costs spills)
         }
-        LDLT_T(const long long q2 = __builtin_amdgcn_s_memtime(); dt2 += q2 - q1;)
         if (bad) {
             if (lane == 0) s_fail = 1;
             return;
@@ -1590,18 +1506,14 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             dvec[k0 + li] = d;
             rdv[k0 + li] = rcp_newton(d);   // (the same operations as in the loop: the same bits)
         }
-        LDLT_T(const long long q3 = __builtin_amdgcn_s_memtime(); dt3 += q3 - q2;)
-        LDLT_T(dt4 += __builtin_amdgcn_s_memtime() - q3;)
     };
     if (wave == 0) diag_block(0, false);
     __syncthreads();
-    LDLT_T(const long long t_d0 = __builtin_amdgcn_s_memtime();)
     const int nb = npad >> 4;
     const int col = lane & 15, rq = lane >> 4;
     for (int kb = 0; kb < nb && !s_fail; ++kb) {
         const int k0 = kb << 4;
         const int m = nb - kb - 1;
-        LDLT_T(t_a = __builtin_amdgcn_s_memtime();)
         // ---- P_k: W_I = A_Ik T^T (one 16-row tile per wave turn), L_Ik = W_I D^-1
         // (kGlob: wave 0 requests the entries of the NEXT diagonal block -- tile 0 of the trailing update, final since the last
         // panel's update -- before the panel: its round trip to device memory is off the critical path of the look-ahead)
@@ -1640,7 +1552,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             for (int c = 0; c < 16; ++c) ri -= l[c] * rv[k0 + c];
             rv[i] = ri;
         }
-        LDLT_T(tP += __builtin_amdgcn_s_memtime() - t_a; t_a = __builtin_amdgcn_s_memtime();)
         // ---- U_k: trailing update with f64 MFMA on the lower-triangle tiles (I >= J > kb); tile 0 = (kb+1, kb+1) goes
         // to wave 0, which then factorises that block while the other waves finish the update
         const int ntiles = m * (m + 1) / 2;
@@ -1732,9 +1643,7 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
                 wave_sync();
                 tile(0);
                 wave_sync();
-                LDLT_T(const long long t_d = __builtin_amdgcn_s_memtime();)
                 diag_block(k0 + 16, true);
-                LDLT_T(tD += __builtin_amdgcn_s_memtime() - t_d;)
                 if (kGlob) run_tiles();
             }
         } else if (kGlob) {
@@ -1743,9 +1652,7 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             for (int t = wave; t < ntiles; t += NW - 1) tile(t);
         }
         __syncthreads();
-        LDLT_T(tU += __builtin_amdgcn_s_memtime() - t_a;)
     }
-    LDLT_T(const long long t_fact = __builtin_amdgcn_s_memtime();)
     if (s_fail) {
         if (tid == 0) Wn.scal[3] = 0.0;
         if (tid < Wn.np) {   // the trial is rejected (lm_decide): its pop() must find the estimates it started from
@@ -1803,11 +1710,7 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
         __syncthreads();
     }
     for (int i = tid; i < n; i += NT) Wn.x[i] = xs[i];
-    if (tid == 0) {
-        Wn.scal[3] = 1.0;
-        LDLT_T(long long *g = Wn.st->dbg; g[0] = t_loaded - t_begin; g[1] = t_d0 - t_loaded; g[2] = tP; g[3] = tU; g[4] = tD;
-               g[5] = t_fact - t_d0; g[6] = __builtin_amdgcn_s_memtime() - t_fact; g[8] = dt1; g[9] = dt2; g[10] = dt3; g[11] = dt4;)
-    }
+    if (tid == 0) Wn.scal[3] = 1.0;
     if (tid < Wn.np) {   // VertexSE3Expmap::oplusImpl + the poses' scale terms
         double upd[6];
         for (int i = 0; i < 6; ++i) {
@@ -1822,7 +1725,6 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 
 __global__ __launch_bounds__(512) void k_ldlt_lds(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LbaWin &Wn = wins[blockIdx.x];
     if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 1) return;
@@ -1831,7 +1733,6 @@ __global__ __launch_bounds__(512) void k_ldlt_lds(const LbaWin *__restrict__ win
 // (a kernel of its own: both forms in one kernel cost the LDS form 25 spilled registers)
 __global__ __launch_bounds__(512) void k_ldlt_dev(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LbaWin &Wn = wins[blockIdx.x];
     if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 0) return;
@@ -1843,18 +1744,13 @@ __global__ __launch_bounds__(512) void k_ldlt_dev(const LbaWin *__restrict__ win
 // epilogue is ldlt_body's (solution, pose update with the push() backup, the poses' scale terms).
 __global__ __launch_bounds__(kLrThreads) void k_ldlt_reg(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LbaWin &Wn = wins[blockIdx.x];
     if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 2) return;
     const int tid = threadIdx.x, n = 6 * Wn.np;
     const double lambda = Wn.st->lambda;
     double *xs = nullptr;
-#ifdef AOS2_LDLT_TIMING
-    const bool ok = ldlt_reg_solve<true>(Wn.Hs, n, Wn.npad, Wn.bs, sm, xs, Wn.st->dbg);
-#else
     const bool ok = ldlt_reg_solve<false>(Wn.Hs, n, Wn.npad, Wn.bs, sm, xs, nullptr);
-#endif
     if (!ok) {
         if (tid == 0) Wn.scal[3] = 0.0;
         if (tid < Wn.np) {   // the trial is rejected (lm_decide): its pop() must find the estimates it started from
@@ -1903,7 +1799,6 @@ __device__ __forceinline__ void edge_last_error(const LbaWin &W, int e, int at, 
 
 __global__ __launch_bounds__(256) void k_transition(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     __shared__ int s_last;
     const LbaWin &W = wins[blockIdx.y];
     LmState *st = W.st;
@@ -1951,7 +1846,6 @@ __global__ __launch_bounds__(256) void k_transition(const LbaWin *__restrict__ w
 // final inlier check (:712-744) and the write-back conversions (:763-778)
 __global__ __launch_bounds__(256) void k_final(const LbaWin *__restrict__ wins)
 {
-    lba_wave_prio();
     const LbaWin &W = wins[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < W.n_edges) {
@@ -1977,11 +1871,8 @@ int lba_handle_init(aos2_lba *s)
     if (s->dev_ready) return AOS2_OK;
     // The optimiser's kernels are few workgroups on a latency-bound chain; the tracking kernels that share the device in a
     // running system (extraction, searches) are wide and throughput-bound.  On a high-priority stream the optimiser's
-    // workgroups are dispatched ahead of the waiting ones of those kernels (AOS2_LBA_STREAM_PRIORITY=normal switches it off).
-    {
-        const char *e = getenv("AOS2_LBA_STREAM_PRIORITY");
-        if ((st = stream_create(&s->stream, !e || strcmp(e, "normal")))) return st;
-    }
+    // workgroups are dispatched ahead of the waiting ones of those kernels.
+    if ((st = stream_create(&s->stream, true))) return st;
     for (auto &e : s->ev) AOS2_HIP_CHECK(hipEventCreate(&e));
     {
         if ((st = stream_create(&s->stream2, true))) return st;
@@ -2003,10 +1894,8 @@ int lba_handle_init(aos2_lba *s)
 static int lba_group_streams(aos2_lba *s)
 {
     if (s->stream_b) return AOS2_OK;
-    const char *e = getenv("AOS2_LBA_STREAM_PRIORITY");
-    const bool prio = !e || strcmp(e, "normal");
-    if (int st_ = stream_create(&s->stream_b, prio)) return st_;
-    if (int st_ = stream_create(&s->stream2_b, prio)) return st_;
+    if (int st_ = stream_create(&s->stream_b, true)) return st_;
+    if (int st_ = stream_create(&s->stream2_b, true)) return st_;
     for (hipEvent_t *ev : {&s->ev_fork_b, &s->ev_join_b, &s->ev_up, &s->ev_stag, &s->ev_done_b}) AOS2_HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     return AOS2_OK;
 }
@@ -2527,9 +2416,8 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     // idles).  A batch of many windows runs as TWO groups with the same program each, on their own streams, the second started
     // behind the first group's first Schur launch: one group's reduced systems are factorised while the other group's landmark
     // kernels fill the device.  Windows are dealt to the groups by size (edges), largest first, so both get the same mix; the
-    // windows of a group are neighbours in the descriptor array.  (aos2_lba_set_window_groups; AOS2_LBA_GROUPS overrides.)
+    // windows of a group are neighbours in the descriptor array.  (aos2_lba_set_window_groups overrides.)
     int G = s->window_groups ? s->window_groups : nw >= 16 ? 2 : 1;
-    if (const char *e = getenv("AOS2_LBA_GROUPS")) G = std::max(1, std::min(2, atoi(e)));
     if (G > nw) G = 1;
     if (G == 2 && (st = lba_group_streams(s))) return st;
     int goff[3] = {0, nw, nw};
@@ -2552,7 +2440,6 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     if (const char *e = getenv("AOS2_LBA_LAYOUT")) walk = !strcmp(e, "walk");
     const int lm_per_block = walk ? 128 : kLmBlock;
     const bool prof = getenv("AOS2_LBA_PROF") != nullptr;
-    const bool ldlt_old = getenv("AOS2_LDLT") && !strcmp(getenv("AOS2_LDLT"), "old");
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (!prof) return;
@@ -2725,9 +2612,8 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
         {
             const size_t ldlt_bytes = ((size_t)l.npad * (l.npad + 1) + (size_t)l.npad * 17 + 4 * (size_t)l.npad + 2 * 16 * 17 + 16) * 8;
             l.ldlt_lds = ldlt_bytes <= 159 * 1024 ? 1 : 0;
-            // the register-resident form (k_ldlt_reg) serves every window of up to 40 free keyframes; AOS2_LDLT=old keeps the two
-            // earlier forms (LDS-resident up to 21 free keyframes, in place in device memory beyond) for comparison
-            if (l.npad <= 16 * kLrMaxNb && !ldlt_old) l.ldlt_lds = 2;
+            // the register-resident form (k_ldlt_reg) serves every window of up to 40 free keyframes
+            if (l.npad <= 16 * kLrMaxNb) l.ldlt_lds = 2;
         }
         // (beyond LDS the reduced system is factorised in place: k_schur writes it with leading dimension npad)
         l.Hs = B.take(l.ldlt_lds == 1 ? 8 * n6 * n6 + 8 : 8 * (size_t)l.npad * l.npad + 8, 256); l.bs = B.take(8 * n6 + 8);
@@ -2876,7 +2762,6 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     const LbaWin *dw = (const LbaWin *)(base + o_wins);
     auto blocks = [](size_t n, int t) { return (unsigned)((n + t - 1) / t); };
     hipStream_t gq[2] = {s->stream, s->stream_b}, gq2[2] = {s->stream2, s->stream2_b};
-    if (getenv("AOS2_LBA_GROUPS_SERIAL")) gq[1] = gq[0], gq2[1] = gq2[0];   // (debugging: the groups one after the other)
     hipEvent_t gfork[2] = {s->ev_fork, s->ev_fork_b}, gjoin[2] = {s->ev_join, s->ev_join_b};
     if (G == 2) {   // the second group's stream starts behind the upload
         AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
@@ -2912,7 +2797,7 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
         hipLaunchKernelGGL(k_lm_init, dim3(P.nw), dim3(1024), 0, P.q, P.blk);
     };
     // one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of two kinds)
-    bool stagger_pending = G == 2 && !getenv("AOS2_LBA_NO_STAGGER");
+    bool stagger_pending = G == 2;
     auto enqueue_trial = [&](const Prog &P, bool first_group) {
         const GroupDims &D = P.D;
         if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
@@ -2922,7 +2807,6 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
             stagger_pending = false;
         }
         // the forms of the reduced-system kernel work on different windows: side by side (one of them on a stream of its own)
-        // (k_ldlt_reg and k_ldlt_lds never meet in one call: AOS2_LDLT chooses for the whole call)
         const bool both = D.any_glob && (D.any_lds || D.any_reg);
         if (both) {
             (void)hipEventRecord(P.fork, P.q);
@@ -3089,14 +2973,6 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     if (getenv("AOS2_LBA_TRACE"))
         for (int i = 0; i < nw; ++i) {
             const LmState *ls = state_of(i);
-#ifdef AOS2_TAIL_TIMING
-            fprintf(stderr, "[lba]   lm_decide (AOS2_TAIL_TIMING builds): sums %lld, decision %lld ticks of 10 ns over %lld calls\n", ls->dbg[12], ls->dbg[13], ls->dbg[14]);
-#endif
-#ifdef AOS2_LDLT_TIMING
-            fprintf(stderr, "[lba] win %d reduced-system kernel cycles: load %lld, D0 %lld, P %lld, U(+lookahead D) %lld, D inside U %lld, factor %lld, backward %lld\n", i,
-                    ls->dbg[0], ls->dbg[1], ls->dbg[2], ls->dbg[3], ls->dbg[4], ls->dbg[5], ls->dbg[6]);
-            fprintf(stderr, "[lba]   diagonal blocks (8 of them): load %lld, pivots %lld, store %lld, T %lld\n", ls->dbg[8], ls->dbg[9], ls->dbg[10], ls->dbg[11]);
-#endif
             for (int t = 0; t < ls->ntr; ++t)
                 fprintf(stderr, "[lba] win %d trial %2d lambda %.6e chi %.9e -> %.9e rho %.6e\n", i, t, ls->tr_lambda[t], ls->tr_cur[t], ls->tr_temp[t], ls->tr_rho[t]);
         }

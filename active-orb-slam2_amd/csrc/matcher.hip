@@ -327,18 +327,7 @@ __device__ __forceinline__ void resolve_fixpoint_impl(int n_f, int n_q, int32_t 
         for (int q = tid; q < n_q; q += NT) choice[q] = -2;
     }
     __syncthreads();
-#ifdef AOS2_FIX_DEBUG
-    __shared__ int dbg_ovf, dbg_ent;
-    if (tid == 0) dbg_ovf = dbg_ent = 0;
-    __syncthreads();
-    if (CACHED) for (int j = 0; j < QPT; ++j) { if (covf[j]) atomicAdd(&dbg_ovf, 1); atomicAdd(&dbg_ent, ccnt[j]); }
-    int dbg_pass = 0;
-    const long long dbg_t0 = __builtin_amdgcn_s_memtime();
-#endif
     for (;;) {
-#ifdef AOS2_FIX_DEBUG
-        ++dbg_pass;
-#endif
         if (tid == 0) changed = 0;
         for (int i = tid; i < n_f; i += NT) Bn[i] = initB(i);
         __syncthreads();
@@ -401,9 +390,6 @@ __device__ __forceinline__ void resolve_fixpoint_impl(int n_f, int n_q, int32_t 
         int32_t *t = Bc; Bc = Bn; Bn = t;
         __syncthreads();
     }
-#ifdef AOS2_FIX_DEBUG
-    if (tid == 0 && blockIdx.x == 0) printf("FIX n_f %d n_q %d cached %d passes %d overflow queries %d entries %d cycles %lld\n", n_f, n_q, (int)CACHED, dbg_pass, dbg_ovf, dbg_ent, __builtin_amdgcn_s_memtime() - dbg_t0);
-#endif
     if (CACHED) {
 #pragma unroll
         for (int j = 0; j < QPT; ++j) {
@@ -2154,7 +2140,7 @@ static int matcher_init(aos2_matcher *m)
     int st = bind_device(m->device);
     if (st) return st;
     if (m->dev_ready) return AOS2_OK;
-    if (int st_ = stream_create(&m->stream, stream_priority_env("AOS2_PRIO_MATCHER"))) return st_;
+    if (int st_ = stream_create(&m->stream, false)) return st_;
     for (auto &e : m->ev) AOS2_HIP_CHECK(hipEventCreate(&e));
     {
         const char *v = getenv("AOS2_SERIAL_RESOLVE");

@@ -23,33 +23,6 @@
 #define AOS2_OCT_HD inline
 #endif
 
-#if defined(AOS2_OCT_PROF) && defined(__HIP_DEVICE_COMPILE__)
-extern __device__ long long g_oct_prof[16];
-// phase counters accumulate in registers and reach memory once, when the job ends (atomics per tick perturbed the
-// very latencies they were measuring)
-#define OCT_T0()                          \
-    long long t_prof = wall_clock64();    \
-    long long prof_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define OCT_TICK(i)                                \
-    do {                                           \
-        const long long t_now = wall_clock64();    \
-        prof_acc[i] += t_now - t_prof;             \
-        t_prof = t_now;                            \
-    } while (0)
-#define OCT_COUNT(i, v) prof_acc[i] += (long long)(v)
-#define OCT_FLUSH()                                                                                              \
-    do {                                                                                                         \
-        if (prof_on && (threadIdx.x & 63) == 0)                                                                  \
-            for (int i_ = 0; i_ < 16; ++i_)                                                                      \
-                if (prof_acc[i_]) atomicAdd((unsigned long long *)&g_oct_prof[i_], (unsigned long long)prof_acc[i_]); \
-    } while (0)
-#else
-#define OCT_T0()
-#define OCT_TICK(i)
-#define OCT_COUNT(i, v)
-#define OCT_FLUSH()
-#endif
-
 namespace aos2 {
 
 // bNoMore of the reference (:1012-1019, :573) is exactly "holds one key", so it is not stored.
@@ -545,10 +518,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
     using Node = typename Tr::Node;
     using Idx = typename Tr::Idx;
     if (n <= 0) return 0;
-#if defined(AOS2_OCT_PROF) && defined(__HIP_DEVICE_COMPILE__)
-    const bool prof_on = N > 200;  // level 0 only
-#endif
-    OCT_T0();
     List<Node> L;
     L.nodes = S.nodes;
     L.n_alloc = 0;
@@ -624,7 +593,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
             lit = nd.next;
     }
 
-    OCT_TICK(0);  // roots + bucketing
     bool finish = false;
     int32_t *cur = S.pairs_a, *prv = S.pairs_b;
     int ncur = 0;
@@ -650,10 +618,7 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                 }
             }
             lit = nxt;
-            OCT_COUNT(8, 1);
         }
-        OCT_TICK(1);  // main passes
-        OCT_COUNT(9, 1);
         if (L.size >= N || L.size == prevSize) {
             finish = true;
         } else if (L.size + nToExpand * 3 > N) {
@@ -663,8 +628,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                 const int nprev = ncur;
                 ncur = 0;
                 pair_sort_to<Coop>(cur, nprev, prv);
-                OCT_TICK(2);  // sort
-                OCT_COUNT(10, nprev);
                 int j_start = nprev - 1;
                 if (Coop::kWave) {
                     // Device: the divides of this round are independent except for the stop test "size >= N after a
@@ -700,7 +663,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                                 }
                             }
                             --j_start;
-                            OCT_COUNT(11, 1);
                             continue;
                         }
                         const int hx = (p.x1 - p.x0 + 1) / 2, hy = (p.y1 - p.y0 + 1) / 2;
@@ -812,7 +774,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                         L.size += coop_sum(act ? npush - 1 : 0);
                         L.n_alloc += 4 * K;
                         j_start -= K;
-                        OCT_COUNT(11, K);
                         coop_sync();
                     }
                 }
@@ -830,10 +791,8 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                             ncur++;
                         }
                     }
-                    OCT_COUNT(11, 1);
                     if (L.size >= N) break;
                 }
-                OCT_TICK(3);  // final-phase divides
                 if (L.size >= N || L.size == prevSize2) finish = true;
             }
         }
@@ -926,7 +885,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
                 lit = nx;
             }
         }
-        OCT_TICK(5);  // list walk
         coop_sync();
         for (int j = coop_lane(); j < nout; j += 64) {
             const Node nd = L.nodes[order[j]];
@@ -943,10 +901,6 @@ AOS2_OCT_HD int distribute_octree(const typename Tr::Cands &C, int n, int minX, 
         }
         coop_sync();
     }
-    OCT_TICK(4);  // best response
-    OCT_COUNT(12, 1);
-    OCT_COUNT(13, L.n_alloc);
-    OCT_FLUSH();
     return nout;
 }
 

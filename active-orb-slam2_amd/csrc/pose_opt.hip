@@ -118,13 +118,6 @@ __device__ __forceinline__ bool solve6(const double *Hb, double lambda, double (
     return pos;
 }
 
-// cycle counters of the phases (s_memtime), printed by workgroup 0: compile with -DAOS2_PO_TIMING (tools only)
-#ifdef AOS2_PO_TIMING
-#define PO_T(...) __VA_ARGS__
-#else
-#define PO_T(...)
-#endif
-
 constexpr int kPoSum = 28;   // 21 (H, upper triangle) + 6 (b) + 1 (robust chi2)
 constexpr size_t kPoLds = (4 * kPoSum + 2 * kPoSum) * sizeof(double);   // 4 wave sums, two result buffers (256 threads)
 constexpr size_t po_lds_bytes(int nt) { return ((size_t)(nt / 64) * kPoSum + 2 * kPoSum) * sizeof(double); }
@@ -273,7 +266,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
     const double delta_m = (double)(float)sqrt(5.991), delta_s = (double)(float)sqrt(7.815);
     // one pass over the active edges at pose q: residuals (stored), robust chi2, H (upper triangle) and b
     // (computeActiveErrors + activeRobustChi2 + buildSystem; types_six_dof_expmap.cpp:266-364, base_unary_edge.hpp)
-    PO_T(long long t_edges = 0, t_sum = 0, t_solve = 0, t_dec = 0, t_all = __builtin_amdgcn_s_memtime(); int n_pass = 0, n_trial = 0;)
     // kReg: the edges of a wave's threads are processed K at a time as ONE straight-line block (no branch: the mono / stereo forms,
     // the Huber case and "edge is at level 1 / slot is empty" are selects; an inactive slot is the point (0, 0, 1) with weight 0, whose
     // terms are exact zeros), so that the K dependent chains -- ~200 f64 instructions of 9 cycles latency each -- interleave.  K is
@@ -375,7 +367,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
         }
     };
     auto pass = [&](const double (&q)[7], double *fin) {
-        PO_T(const long long p0 = __builtin_amdgcn_s_memtime();)
         double acc[kPoSum];
 #pragma unroll
         for (int k = 0; k < kPoSum; ++k) acc[k] = 0;
@@ -497,9 +488,7 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
             }
         }
         }
-        PO_T(const long long p1 = __builtin_amdgcn_s_memtime();)
         block_sum28<NT>(acc, sh, fin);
-        PO_T(const long long p2 = __builtin_amdgcn_s_memtime(); t_edges += p1 - p0; t_sum += p2 - p1; ++n_pass;)
     };
     int nBad = 0, cur = 0;
     double *fin0 = sh + (NT / 64) * kPoSum;   // two result buffers of the sums
@@ -538,7 +527,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
                 double bk[7];
                 do {
                     double *dst = fin0 + cur * kPoSum;
-                    PO_T(const long long s0 = __builtin_amdgcn_s_memtime();)
                     if (!init) {
 #pragma unroll
                         for (int k = 0; k < 7; ++k) bk[k] = qt[k];
@@ -550,9 +538,7 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
                         for (int j = 0; j < 6; ++j) scale += xs[j] * (lambda * xs[j] + Hb[21 + j]);
                         scale += 1e-3;
                         dst = fin0 + (cur ^ 1) * kPoSum;   // the trial's sums go to the other buffer: accepting = switching
-                        PO_T(++n_trial;)
                     }
-                    PO_T(const long long s1 = __builtin_amdgcn_s_memtime(); t_solve += s1 - s0;)
                     pass(qt, dst);
                     if (init) {
                         currentChi = dst[27];
@@ -561,7 +547,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
                         rho = -1;   // (stay in the loop: the first trial follows)
                         continue;
                     }
-                    PO_T(const long long s2 = __builtin_amdgcn_s_memtime();)
                     const double tempChi = pos ? dst[27] : 1.7976931348623157e308;
                     double r = currentChi - tempChi;
                     r /= scale;
@@ -584,7 +569,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
                     }
                     rho = r;
                     qmax++;
-                    PO_T(t_dec += __builtin_amdgcn_s_memtime() - s2;)
                 } while (rho < 0 && qmax < 10);
                 if (qmax == 10 || rho == 0) {
                     ok = false;
@@ -627,7 +611,6 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
 #pragma unroll EPT
         PO_FOR_EDGES(j, e) P.outlier[e] = Outr[j];
     }
-    PO_T(if (tid == 0 && blockIdx.x == 0) printf("PO n %d passes %d trials %d cycles: edges %lld sum %lld solve+oplus %lld decide %lld total %lld\n", n, n_pass, n_trial, t_edges, t_sum, t_solve, t_dec, __builtin_amdgcn_s_memtime() - t_all);)
     if (tid == 0) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) P.pose_out[k] = qt[k];

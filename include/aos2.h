@@ -203,8 +203,8 @@ int aos2_extractor_debug_candidates(aos2_extractor_t *e, int image, int level, i
 int aos2_extractor_set_chunks(aos2_extractor_t *e, int chunks);
 
 /* Timing of the last batch, milliseconds, measured with HIP events on the handle's stream:
- * [0] pyramid kernels, [1] FAST+NMS kernel, [2] candidate compaction, [3] octree stage
- * (device kernel, or D2H + host + H2D when the host octree is selected), [4] orientation +
+ * [0] pyramid kernels, [1] FAST+NMS kernel, [2] empty (two back-to-back events: the slot of a
+ * former candidate compaction stage, kept so the layout stays), [3] octree kernel, [4] orientation +
  * blur + rBRIEF kernel, [5] whole call (host wall clock).  n <= 8 values are written. */
 int aos2_extractor_last_timing(const aos2_extractor_t *e, float *ms, int n);
 

@@ -98,12 +98,11 @@ def test_batch_equals_single_and_idempotent(pkg, oracle, gpu):
     assert t["fast"] > 0 and t["describe"] > 0
 
 
-def test_host_octree_path_equals_device_octree(pkg, gpu, monkeypatch):
+def test_device_octree_batch_equals_the_oracle(pkg, oracle, gpu):
     imgs = pkg.synth.synth_batch(60, 6)
     dev = pkg.Extractor().extract_batch(imgs)
-    monkeypatch.setenv("AOS2_OCTREE", "host")
-    host = pkg.Extractor().extract_batch(imgs)
-    assert all(same(a, b) for a, b in zip(dev, host))
+    oe = oracle.Extractor()
+    assert all(same(a, oe.extract(im)) for a, im in zip(dev, imgs))
 
 
 def test_fallback_paths_equal_the_fast_paths(pkg, oracle, gpu, monkeypatch):
@@ -118,10 +117,9 @@ def test_fallback_paths_equal_the_fast_paths(pkg, oracle, gpu, monkeypatch):
     monkeypatch.setenv("AOS2_OCT_LDS", "0")
     alt = [pkg.Extractor(nfeatures=2000)(im) for im in imgs]
     assert all(same(a, b) for a, b in zip(ref, alt))
-    # the one-workgroup-per-image octree kernel (opt-in) gives the same bits as the one-wave-per-job kernel
+    # a batch gives the same bits as single calls
     monkeypatch.delenv("AOS2_FAST_LIST")
     monkeypatch.delenv("AOS2_OCT_LDS")
-    monkeypatch.setenv("AOS2_OCT_IMAGE", "1")
     ex = pkg.Extractor(nfeatures=1000)
     batch = pkg.synth.synth_batch(80, 6)
     assert all(same(a, b) for a, b in zip(ex.extract_batch(batch), [pkg.Extractor(nfeatures=1000)(im) for im in batch]))
@@ -387,11 +385,10 @@ def test_very_wide_image_exceeds_twice_the_feature_budget(pkg, oracle, gpu):
     assert ex.max_keypoints_for(1171, 131) >= 268
 
 
-def test_whole_level_blur_form_equals_the_per_keypoint_form(pkg, oracle, gpu, monkeypatch):
-    """AOS2_DESC_BLUR=level (the reference's own order: GaussianBlur of every whole level, then the descriptors on the blurred
-    planes -- measured slower, kept for the A/B of profiles/r04_desc_blur_ab.txt) gives the same keypoints and descriptors, also
-    at the level borders (keypoints 19 pixels from an edge: the blur's REFLECT_101 columns / rows are sampled)."""
-    monkeypatch.setenv("AOS2_DESC_BLUR", "level")
+def test_per_keypoint_blur_equals_the_whole_level_blur_at_borders(pkg, oracle, gpu):
+    """The per-keypoint blur of the descriptors gives the keypoints and descriptors of the reference's own order (GaussianBlur of
+    every whole level, then the descriptors on the blurred planes), also at the level borders (keypoints 19 pixels from an edge:
+    the blur's REFLECT_101 columns / rows are sampled)."""
     for cfg, seed in (("tum", 11), ("kitti", 12)):
         c = pkg.synth.CONFIGS[cfg]
         img = pkg.synth.synth_image(seed, c["w"], c["h"])
