@@ -34,7 +34,6 @@
 #include <functional>
 #include <mutex>
 #include <thread>
-#include <type_traits>
 
 #include "lba_math.h"
 #include "ldlt_reg.h"
@@ -73,6 +72,10 @@ struct LmState {
     int32_t pad_;
     double tr_rho[48], tr_temp[48], tr_cur[48], tr_lambda[48];
 };
+
+// The kernel that factorises a window's reduced system: k_ldlt_reg (the matrix in registers, up to 40 free keyframes) or
+// k_ldlt_dev (in place in device memory, any size)
+enum LdltForm : int { kLdltDev = 0, kLdltReg = 2 };
 
 // device-side view of one window
 struct LbaWin {
@@ -113,15 +116,19 @@ struct LbaWin {
     double *scal;                    // [3] solve ok
     double *part;                    // per-landmark sums of k_points: chi2 terms [0, nl), scale terms [nl, 2 nl)
     int n_part;                      // workgroups of a k_points launch for this window
-    double *ldlt;                    // factorisation scratch of the global-memory variant
-    int npad, ldlt_lds;
-    int hs_ld;                       // leading dimension of Hs: 6 np, or npad when the reduced system is factorised in place (beyond LDS)
+    double *ldlt;                    // (unused: 8 bytes of the arena per window)
+    int npad;                        // 6 np rounded up to a multiple of 16
+    LdltForm ldlt_form;
+    int hs_ld;                       // leading dimension of Hs: always npad now (both forms take the padded matrix)
     LmState *st;
     const int32_t *abort_word;       // mapped host memory: the forwarded pbStopFlag
     float *out_Tcw, *out_xyz;        // Converter::toCvMat / toCvMat(Vector3d) write-back (Optimizer.cc:763-778)
     double *out_chi2;
     uint8_t *out_outlier;
 };
+
+// (the kernels' code depends on the members' offsets: a change here is a change of every kernel, to be measured as one)
+static_assert(sizeof(LbaWin) == 520 && offsetof(LbaWin, st) == 472, "LbaWin's layout is fixed");
 
 // One workgroup's share of a launch: (window, what).  The host lays the work of ALL windows of a call out as task lists (one per
 // kernel family) instead of grids padded to the largest window -- the windows of a batch differ (10-40 keyframes, 2-6 k points),
@@ -1317,23 +1324,15 @@ void k_schur(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ task
     }
 }
 
-// Dense LDL^T (no pivoting; fails on a zero pivot like Eigen::SimplicialLDLT) + solve of the reduced
-// camera system, one workgroup per window.  Blocked right-looking factorisation, block 16:
-//   (1) 16x16 diagonal block: unblocked LDL^T by wave 0 (wave-synchronous, no workgroup barrier)
-//   (2) panel: one thread per row below the block, 16-column forward substitution, W = L * D kept
-//   (3) trailing update A[I][J] -= W[I] * L[J]^T on 16x16 tiles with v_mfma_f64_16x16x4_f64
-//       (the only GEMM-shaped piece of the path; tiles round-robin over the waves)
-// then forward / diagonal / backward substitution.
-// The matrix is padded to a multiple of 16 with an identity tail.  kLds: it lives in LDS (npad <= 128, i.e. <= 21 free
-// keyframes; 4 waves; substitution by wave 0 with the vector in registers, which then applies the update to the
-// poses).  Otherwise (any size): in a global scratch, 16 waves, the vector in LDS, k_update_poses follows.
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// ---- LDS variant (npad <= 128): 8 waves, per 16-column panel k
+// Dense LDL^T (no pivoting; fails on a zero pivot like Eigen::SimplicialLDLT) + solve of the reduced camera system of a window
+// of more than 40 free keyframes (up to 40: k_ldlt_reg), one workgroup of 8 waves per window.  The matrix is padded to a multiple
+// of 16 with an identity tail and lives in device memory: in place in Wn.Hs, which k_schur wrote with leading dimension npad
+// (L2-resident; the identity tail is set once by k_prepare and stays an identity under the factorisation).  Everything else --
+// the panel's L D, the vectors, T -- stays in LDS.  Blocked right-looking factorisation, block 16; per 16-column panel k
 //   D_k  the 16x16 diagonal block by wave 0: unblocked LDL^T with row i of the block in the registers of lane i (pivot
 //        and column entries travel through v_readlane; no predication: the upper halves of the rows are scratch), the
-//        reciprocal pivots, then T_k = L_kk^-1 (lane c owns column c), stored in the unused UPPER triangle of the
-//        block, and the block's part of the forward substitution y_k = T_k r_k
+//        reciprocal pivots, then T_k = L_kk^-1 (lane c owns column c) and the block's part of the forward substitution
+//        y_k = T_k r_k
 //   P_k  panel below the block as a GEMM: W_I = A_Ik T_k^T on 16x16 tiles with v_mfma_f64_16x16x4_f64, L_Ik = W_I D^-1;
 //        the rows' share of the forward substitution r_i -= L_ik y_k (so L y = b is solved while the matrix is
 //        factorised)
@@ -1341,18 +1340,13 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 //        straight on to D_{k+1} (look-ahead) while the other seven waves update the rest
 // Two workgroup barriers per panel.  The backward substitution x = L^-T D^-1 y walks the panels the other way round
 // with the same look-ahead (x_k = T_k^T s_k, one barrier per panel); finally the first np threads apply the update to
-// the poses.  (The former version -- 4 waves, panel by per-row substitution with 16 divisions per row, predicated
-// pivot updates, separate forward / backward passes by one wave -- took 76 us at 20 free keyframes.)
-// kGlob: the same algorithm for a reduced system beyond LDS (more than 21 free keyframes: npad > 128) -- the matrix lives in the
-// device memory (in place in Wn.Hs, which k_schur wrote with leading dimension npad: 240 x 240 doubles at 40 free keyframes,
-// L2-resident), everything else (the panel's L D,
-// the vectors, T) stays in LDS.  What one wave stores and another wave of the workgroup loads afterwards is ordered by
+// the poses.  What one wave stores to the matrix and another wave of the workgroup loads afterwards is ordered by
 // __syncthreads() (the compute unit's vector cache is write-through and shared by the workgroup's waves); inside wave 0 by
 // wave_sync() = completion of the wave's outstanding stores.  The pivot chain of the diagonal blocks never touches memory, so
-// what the variant pays is one device-memory round trip per phase instead of an LDS one (measured: DESIGN.md 5.3).
+// what the matrix in device memory costs is one round trip per phase (measured: DESIGN.md 5.3).
+typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double __attribute__((address_space(1))) gdouble_t;
 constexpr int kTileBatch = 4;
-template <bool kGlob>
 __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 {
     constexpr int NT = 512, NW = 8;
@@ -1360,71 +1354,26 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
     const int n = 6 * Wn.np, npad = Wn.npad;
     const double lambda = Wn.st->lambda;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // odd leading dimensions: column-direction accesses (MFMA operands, substitution) fall on distinct banks
-    const int ld = kGlob ? npad : npad + 1, lw = 17;   // (device scratch: rows on 128-byte boundaries)
-    using mptr_t = std::conditional_t<kGlob, gdouble_t *, double *>;
-    // npad x ld: lower triangle = the matrix, then L.  kGlob: k_schur wrote the matrix straight into this layout (Wn.hs_ld = npad,
-    // identity tail set once by k_prepare; the tail stays an identity under the factorisation) -- factorised in place
-    mptr_t M = kGlob ? (mptr_t)Wn.Hs : (mptr_t)sm;
-    double *W = kGlob ? sm : sm + (size_t)npad * ld;   // npad x lw: L * D of the current panel
+    // the matrix's rows lie on 128-byte boundaries; the LDS arrays have odd leading dimensions: column-direction accesses (MFMA
+    // operands, substitution) fall on distinct banks
+    const int ld = npad, lw = 17;
+    gdouble_t *M = (gdouble_t *)Wn.Hs;           // npad x ld: lower triangle = the matrix, then L (factorised in place)
+    double *W = sm;                              // npad x lw: L * D of the current panel
     double *dvec = W + (size_t)npad * lw;        // npad: D
     double *rdv = dvec + npad;                   // npad: 1 / D
     double *rv = rdv + npad;                     // npad: residual of the forward substitution, then y, then D^-1 y, then s
     double *xs = rv + npad;                      // npad: solution
     double *Tb = xs + npad;                      // 2 x 16 x 17: T_k^T of the current / next panel
-    double *Dst = Tb + 2 * 16 * 17;              // kGlob: 16 x 17, the next diagonal block on its way from the trailing update to wave 0's rows
+    double *Dst = Tb + 2 * 16 * 17;              // 16 x 17: the next diagonal block on its way from the trailing update to wave 0's rows
     if (tid == 0) s_fail = 0;
-    // load (identity-padded), lower BLOCK triangle only -- row r needs its columns up to the end of its diagonal block,
-    // nothing reads the blocks above the diagonal -- as element pairs (n is even, rows are 16-byte aligned): block row R
-    // holds 16 x 8 (R + 1) pairs, 64 R (R + 1) pairs lie before it.  9 independent 16-byte global loads in flight per
-    // thread before the stores: a 128 x 128 system is one round.
-    if (!kGlob) {
-        const int nbr = npad >> 4, npairs = 64 * nbr * (nbr + 1);
-        auto where = [&](int q, int &r, int &c) {
-            int R = (int)((__fsqrt_rn(1.0f + (float)q * 0.0625f) - 1.0f) * 0.5f);
-            while (64 * (R + 1) * (R + 2) <= q) ++R;   // (the float estimate can be one short)
-            while (64 * R * (R + 1) > q) --R;
-            const int q1 = q - 64 * R * (R + 1), w = 8 * (R + 1);
-            const int rr = q1 / w;
-            r = 16 * R + rr;
-            c = (q1 - rr * w) << 1;
-        };
-        for (int p0 = tid; p0 < npairs; p0 += 9 * NT) {
-            double2 v[9];
-            int rr[9], cc[9];
-#pragma unroll
-            for (int u = 0; u < 9; ++u) {
-                const int q = p0 + u * NT;
-                rr[u] = cc[u] = 0;
-                if (q < npairs) where(q, rr[u], cc[u]);
-                const int r = rr[u], c = cc[u];
-                if (q < npairs && r < n && c < n)
-                    v[u] = *reinterpret_cast<const double2 *>(Wn.Hs + (size_t)r * n + c);
-                else
-                    v[u] = double2{r == c ? 1.0 : 0.0, r == c + 1 ? 1.0 : 0.0};
-            }
-#pragma unroll
-            for (int u = 0; u < 9; ++u) {
-                const int q = p0 + u * NT;
-                if (q < npairs) {
-                    M[(size_t)rr[u] * ld + cc[u]] = v[u].x;
-                    M[(size_t)rr[u] * ld + cc[u] + 1] = v[u].y;
-                }
-            }
-        }
-    }
     for (int i = tid; i < npad; i += NT) rv[i] = i < n ? Wn.bs[i] : 0.0;
     __syncthreads();
-    auto wave_sync = [] {   // LDS writes of this wave visible to its other lanes (one wave: LDS operations execute in order)
-        if (kGlob) {   // ... and its stores to the device scratch complete before its other lanes load them
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        } else {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
+    // LDS writes of this wave visible to its other lanes (one wave: LDS operations execute in order), and its stores to the
+    // matrix complete before its other lanes load them
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     // D_k (wave 0 only; lanes >= 16 mirror lanes 0..15, their results are not stored).  Measured single-wave latencies
     // (tools/microbench/f64_latency.hip): dependent f64 FMA 9 cycles, IEEE division 67, v_rcp_f64 + 2 Newton steps 34,
@@ -1445,7 +1394,7 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
         double *colbuf = xs;   // 16 doubles of scratch (xs is unused until the backward pass)
         double *Tk = Tb + ((k0 >> 4) & 1) * (16 * 17);
         double row[16];
-        if (kGlob && staged) {
+        if (staged) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) row[c] = Dst[li * 17 + c];
         } else {
@@ -1469,7 +1418,7 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const double ci = row[j];
-            if (kGlob) dsave = li == j ? ci : dsave;   // the pivot of this lane's row (what is stored at M[k0 + li][k0 + li] below)
+            dsave = li == j ? ci : dsave;   // the pivot of this lane's row (what is stored at M[k0 + li][k0 + li] below)
             if (j < 15) colbuf[li] = ci;
             const double dj = readlane_f64(ci, j);
             if (dj == 0.0 || dj != dj) bad = true;
@@ -1501,11 +1450,8 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
         }
         rv[k0 + li] = cur;   // y of this block
         wave_sync();
-        {
-            const double d = kGlob ? dsave : (double)M[(size_t)(k0 + li) * ld + k0 + li];
-            dvec[k0 + li] = d;
-            rdv[k0 + li] = rcp_newton(d);   // (the same operations as in the loop: the same bits)
-        }
+        dvec[k0 + li] = dsave;
+        rdv[k0 + li] = rcp_newton(dsave);   // (the same operations as in the loop: the same bits)
     };
     if (wave == 0) diag_block(0, false);
     __syncthreads();
@@ -1515,10 +1461,10 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
         const int k0 = kb << 4;
         const int m = nb - kb - 1;
         // ---- P_k: W_I = A_Ik T^T (one 16-row tile per wave turn), L_Ik = W_I D^-1
-        // (kGlob: wave 0 requests the entries of the NEXT diagonal block -- tile 0 of the trailing update, final since the last
+        // (wave 0 requests the entries of the NEXT diagonal block -- tile 0 of the trailing update, final since the last
         // panel's update -- before the panel: its round trip to device memory is off the critical path of the look-ahead)
         double4_t acc0 = {0, 0, 0, 0};
-        if (kGlob && wave == 0 && m > 0) {
+        if (wave == 0 && m > 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc0[r] = M[(size_t)(k0 + 16 + rq + 4 * r) * ld + k0 + 16 + col];
         }
@@ -1540,13 +1486,13 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
                 M[(size_t)(I0 + rq + 4 * r) * ld + k0 + col] = acc[r] * rd;
             }
         }
-        if (kGlob && tid == 0) s_tile = 1;   // (tile 0 is wave 0's)
+        if (tid == 0) s_tile = 1;   // (tile 0 is wave 0's)
         __syncthreads();
         // forward substitution of the rows below: r_i -= sum_c L[i][k0 + c] y_c (c ascending)
         for (int i = k0 + 16 + tid; i < npad; i += NT) {
             double l[16];
 #pragma unroll
-            for (int c = 0; c < 16; ++c) l[c] = kGlob ? W[(size_t)i * lw + c] * rdv[k0 + c] : (double)M[(size_t)i * ld + k0 + c];   // (L = W D^-1: the product the panel stored, the same bits)
+            for (int c = 0; c < 16; ++c) l[c] = W[(size_t)i * lw + c] * rdv[k0 + c];   // (L = W D^-1: the product the panel stored, the same bits)
             double ri = rv[i];
 #pragma unroll
             for (int c = 0; c < 16; ++c) ri -= l[c] * rv[k0 + c];
@@ -1564,34 +1510,22 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             I0 = (kb + 1 + ii) << 4;
             J0 = (kb + 1 + rem) << 4;
         };
-        // B[k][j] = L[J0 + j][k0 + k]: from the matrix, or (kGlob) as the product W D^-1 the panel stored there -- the same bits, from LDS
-        auto lval = [&](int J0, int kk) -> double {
-            return kGlob ? W[(size_t)(J0 + col) * lw + 4 * kk + rq] * rdv[k0 + 4 * kk + rq] : (double)M[(size_t)(J0 + col) * ld + k0 + 4 * kk + rq];
-        };
-        auto tile = [&](int t) {
-            int I0, J0;
-            tile_at(t, I0, J0);
-            double4_t acc;
-            if (kGlob && t == 0)
-                acc = acc0;
-            else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = M[(size_t)(I0 + rq + 4 * r) * ld + J0 + col];
-            }
+        // B[k][j] = L[J0 + j][k0 + k]: as the product W D^-1 the panel stored in the matrix -- the same bits, from LDS
+        auto lval = [&](int J0, int kk) -> double { return W[(size_t)(J0 + col) * lw + 4 * kk + rq] * rdv[k0 + 4 * kk + rq]; };
+        // tile 0, started from the entries wave 0 requested before the panel; the result is the next diagonal block and goes to
+        // wave 0's rows through LDS, not through the matrix
+        auto tile0 = [&]() {
+            const int I0 = (kb + 1) << 4;
+            double4_t acc = acc0;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const double av = -W[(size_t)(I0 + col) * lw + 4 * kk + rq];          // A[i = lane&15][k = lane>>4]
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, lval(J0, kk), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, lval(I0, kk), acc, 0, 0, 0);
             }
-            if (kGlob && t == 0) {   // the next diagonal block: to wave 0's rows through LDS, not through the device scratch
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Dst[(rq + 4 * r) * 17 + col] = acc[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) M[(size_t)(I0 + rq + 4 * r) * ld + J0 + col] = acc[r];
-            }
+            for (int r = 0; r < 4; ++r) Dst[(rq + 4 * r) * 17 + col] = acc[r];
         };
-        // kGlob: the tiles are handed out kTileBatch at a time from a counter in LDS (a tile's result does not depend on the wave
+        // The tiles are handed out kTileBatch at a time from a counter in LDS (a tile's result does not depend on the wave
         // that forms it), the next batch's entries are requested before the current batch's products are formed (a batch is a
         // round trip to device memory), and wave 0 joins when its diagonal block is done: at 30-40 free keyframes the trailing
         // update, not the pivot chain, was the longer side of the look-ahead (measured: DESIGN.md 5.3)
@@ -1641,15 +1575,13 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
             if (ntiles > 0) {
                 // (the rows k0+16 .. k0+31 of the forward substitution above belong to threads 0..15 = this wave)
                 wave_sync();
-                tile(0);
+                tile0();
                 wave_sync();
                 diag_block(k0 + 16, true);
-                if (kGlob) run_tiles();
+                run_tiles();
             }
-        } else if (kGlob) {
-            run_tiles();
         } else {
-            for (int t = wave; t < ntiles; t += NW - 1) tile(t);
+            run_tiles();
         }
         __syncthreads();
     }
@@ -1723,20 +1655,12 @@ __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
     }
 }
 
-__global__ __launch_bounds__(512) void k_ldlt_lds(const LbaWin *__restrict__ wins)
-{
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const LbaWin &Wn = wins[blockIdx.x];
-    if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 1) return;
-    ldlt_body<false>(Wn, sm);
-}
-// (a kernel of its own: both forms in one kernel cost the LDS form 25 spilled registers)
 __global__ __launch_bounds__(512) void k_ldlt_dev(const LbaWin *__restrict__ wins)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LbaWin &Wn = wins[blockIdx.x];
-    if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 0) return;
-    ldlt_body<true>(Wn, sm);
+    if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_form != kLdltDev) return;
+    ldlt_body(Wn, sm);
 }
 
 // The form every window of <= 40 free keyframes takes (ldlt_reg.h): the trailing matrix as MFMA accumulator tiles in the registers of
@@ -1746,7 +1670,7 @@ __global__ __launch_bounds__(kLrThreads) void k_ldlt_reg(const LbaWin *__restric
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LbaWin &Wn = wins[blockIdx.x];
-    if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_lds != 2) return;
+    if (!Wn.st->run || Wn.np == 0 || Wn.ldlt_form != kLdltReg) return;
     const int tid = threadIdx.x, n = 6 * Wn.np;
     const double lambda = Wn.st->lambda;
     double *xs = nullptr;
@@ -1879,8 +1803,7 @@ int lba_handle_init(aos2_lba *s)
         AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
         AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
     }
-    // the reduced-system factorisation keeps up to 128x128 doubles + panel in LDS (<= 150 KB)
-    AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
+    // the reduced-system kernels take their LDS dynamically: the panel and the vectors of the largest window of a launch
     AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_dev, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLrMaxDynLds));
     s->dev_ready = true;
@@ -2162,16 +2085,16 @@ struct WinLayout {
     size_t est, bk, robust, level1, err, lrec, lomr, Rl, Hpp, Hll, b, x, Hs, bs, tmp, scal, part, ldlt;
     // results (downloaded)
     size_t out_Tcw, out_xyz, out_outlier, out_chi2, st;
-    int n_part, npad, ldlt_lds;
+    int n_part, npad;
+    LdltForm ldlt_form;
     size_t n_items;
 };
-
 
 // ROCTx ranges around the host-side phases of a solve (AOS2_ROCTX=1; rocprofv3 --marker-trace shows them next to the
 // kernels).  The library is looked up at run time: no link dependency.  g2o's statistics buckets
 // (Thirdparty/g2o/g2o/core/batch_stats.h, filled in block_solver.hpp:441-453 and sparse_optimizer.cpp:376-414) map to
 // the kernels of the device program: timeResiduals -> k_points, timeLinearize + timeQuadraticForm -> k_lin,
-// timeSchurComplement -> k_schur, timeLinearSolver -> k_ldlt_lds / k_ldlt_solve, timeUpdate -> the pose
+// timeSchurComplement -> k_schur, timeLinearSolver -> k_ldlt_reg / k_ldlt_dev, timeUpdate -> the pose
 // update inside the LDL^T kernel and the landmark update inside k_points.
 struct RoctxRange {
     typedef int (*push_t)(const char *);
@@ -2218,6 +2141,622 @@ struct Bump {
         return off;
     }
 };
+
+// ---- the per-window host work: index structures, arena regions, staging
+
+// The index structures of n windows -- window i is problems[ids ? ids[i] : i] -- into passes[0 .. n), a pool thread per window,
+// after the range check of the edges' vertex indices
+static int build_structures(WindowPool &pool, const aos2_lba_problem_t *problems, const int *ids, int n, std::vector<Pass> &passes)
+{
+    std::vector<uint8_t> pass_ok(n, 1);
+    std::vector<int> bad_edge(n, -1);
+    pool.run(n, [&](int i) {
+        const aos2_lba_problem_t *p = problems + (ids ? ids[i] : i);
+        for (int e = 0; e < p->n_edges; ++e)
+            if (p->edge_pose[e] < 0 || p->edge_pose[e] >= p->n_poses || p->edge_point[e] < 0 || p->edge_point[e] >= p->n_points) {
+                bad_edge[i] = e;
+                return;
+            }
+        pass_ok[i] = build_pass(p, passes[i]) ? 1 : 0;
+        if (pass_ok[i] && passes[i].np > 0) {
+            build_schur_items(passes[i]);
+            build_schur_units(passes[i]);
+        } else
+            passes[i].units.clear();
+    });
+    for (int i = 0; i < n; ++i)
+        if (bad_edge[i] >= 0) {
+            set_error("problem %d: edge %d references a vertex out of range", ids ? ids[i] : i, bad_edge[i]);
+            return AOS2_ERR_ARG;
+        }
+    for (int i = 0; i < n; ++i)
+        if (!pass_ok[i]) {   // (cannot come from the reference: KeyFrame observations are a map MapPoint -> index)
+            set_error("problem %d: two edges connect the same keyframe and map point", ids ? ids[i] : i);
+            return AOS2_ERR_ARG;
+        }
+    return AOS2_OK;
+}
+
+// The landmark kernels' layout of a call (see aos2_lba_solve_batch) and the block sizes that follow from it
+struct LmLayout {
+    bool walk;
+    int lm_per_block, lin_block;
+    int points_blocks(const Pass &S) const { return std::max(1, (S.nl + lm_per_block - 1) / lm_per_block); }   // workgroups of a k_points launch
+    int lin_blocks(const Pass &S) const { return (S.nl + lin_block - 1) / lin_block; }                         // landmark workgroups of a k_lin launch
+};
+
+// The staged regions of a window, in arena order: fn(its WinLayout member, the host array it is filled from, the array's bytes,
+// bytes of tail).  A region is array + tail long.  The layout and the staging copy both go through this one list.
+template <class Layout, class Fn>
+static inline void for_each_staged(const aos2_lba_problem_t &p, const Pass &S, Layout &l, Fn &&fn)
+{
+    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
+    fn(l.in_Tcw, p.pose_Tcw, 64 * NP, 0); fn(l.in_xyz, p.point_xyz, 12 * NL, 0); fn(l.in_obs, p.edge_obs, 12 * E, 0); fn(l.in_w, p.edge_inv_sigma2, 4 * E, 0);
+    fn(l.e_pose, p.edge_pose, 4 * E, 0); fn(l.e_point, p.edge_point, 4 * E, 0); fn(l.e_stereo, p.edge_stereo, E, 0);
+    auto list = [&](auto &off, const std::vector<int32_t> &v, size_t tail) { fn(off, v.data(), 4 * v.size(), tail); };
+    list(l.pl_pos, S.pl_pos, 0);   // (one per edge)
+    list(l.hpose, S.hpose, 4); list(l.hpoint, S.hpoint, 4);
+    list(l.pt_off, S.pt_off, 0); list(l.pt_k, S.pt_k, 4);   // (the offset lists hold nl + 1 or np + 1 entries: never empty)
+    list(l.ps_off, S.ps_off, 0); list(l.ps_k, S.ps_k, 4);
+    list(l.pl_off, S.pl_off, 0); list(l.pl_k, S.pl_ph, 4);
+    list(l.it_ka, S.it_ka, 4); list(l.it_kb, S.it_kb, 4); list(l.it_l, S.it_l, 4);
+    list(l.blk_off, S.blk_off, 4);
+    list(l.sr_o0, S.sr_o0, 4); list(l.sr_info, S.sr_info, 4); list(l.sr_ij, S.sr_ij, 4);
+}
+
+static void layout_staged(const aos2_lba_problem_t &p, const Pass &S, Bump &B, WinLayout &l)
+{
+    for_each_staged(p, S, l, [&](size_t &off, const void *, size_t bytes, size_t tail) { off = B.take(bytes + tail); });
+    l.n_items = S.it_ka.size();
+}
+
+// the window's staged regions into the staging buffer `dst` (which mirrors the arena)
+static void stage_window(uint8_t *dst, const WinLayout &l, const aos2_lba_problem_t &p, const Pass &S)
+{
+    for_each_staged(p, S, l, [&](size_t off, const void *src, size_t bytes, size_t) {
+        if (bytes) memcpy(dst + off, src, bytes);
+    });
+}
+
+// the device-only regions, and which reduced-system kernel the window takes
+static void layout_scratch(const aos2_lba_problem_t &p, const Pass &S, const LmLayout &lay, Bump &B, WinLayout &l)
+{
+    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
+    const size_t n6 = 6 * (size_t)S.np, dim = n6 + 3 * (size_t)S.nl;
+    l.est = B.take(8 * (7 * NP + 3 * NL)); l.bk = B.take(8 * (7 * NP + 3 * NL));
+    l.robust = B.take(E); l.level1 = B.take(E);
+    l.err = B.take(24 * E);
+    l.lrec = B.take(32 * (S.pl_k.size() + 1)); l.lomr = B.take(24 * (S.pl_k.size() + 1)); l.Rl = B.take(72 * (size_t)S.np + 8);
+    l.Hpp = B.take(288 * (size_t)S.np + 8); l.Hll = B.take(72 * (size_t)S.nl + 8);
+    l.b = B.take(8 * dim + 8); l.x = B.take(8 * dim + 8);
+    l.npad = (int)((n6 + 15) & ~(size_t)15);
+    // the register-resident form serves every window of up to 40 free keyframes
+    l.ldlt_form = l.npad <= 16 * kLrMaxNb ? kLdltReg : kLdltDev;
+    // (both forms take the reduced system padded: k_schur writes it with leading dimension npad, k_ldlt_dev factorises it in place)
+    l.Hs = B.take(8 * (size_t)l.npad * l.npad + 8); l.bs = B.take(8 * n6 + 8);
+    l.tmp = B.take(8 * n6 + 8);
+    l.n_part = lay.points_blocks(S);
+    l.scal = B.take(64); l.part = B.take(16 * (size_t)std::max(S.nl, 1) + 8);
+    l.ldlt = B.take(8);
+}
+
+// the regions that come back in one copy: the window's state, then its results
+static void layout_results(const aos2_lba_problem_t &p, bool want_chi2, Bump &B, WinLayout &l)
+{
+    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
+    l.st = B.take(sizeof(LmState), 64);
+    l.out_Tcw = B.take(64 * NP, 64); l.out_xyz = B.take(12 * NL, 64); l.out_outlier = B.take(E, 64);
+    l.out_chi2 = want_chi2 ? B.take(8 * E, 64) : 0;
+}
+
+// the device-side view of a window whose regions lie at `base` + l
+static void describe_window(LbaWin &W, uint8_t *base, const aos2_lba_problem_t &p, const Pass &S, const WinLayout &l, const int32_t *abort_word, bool want_chi2)
+{
+    memset(&W, 0, sizeof(W));
+    W.n_poses = p.n_poses; W.n_points = p.n_points; W.n_edges = p.n_edges;
+    W.np = S.np; W.nl = S.nl; W.n_items = (int)l.n_items;
+    W.iters1 = p.iters_first; W.iters2 = p.iters_second;
+    W.in_Tcw = (const float *)(base + l.in_Tcw); W.in_xyz = (const float *)(base + l.in_xyz);
+    W.in_obs = (const float *)(base + l.in_obs); W.in_w = (const float *)(base + l.in_w);
+    W.pose = (double *)(base + l.est); W.point = W.pose + 7 * (size_t)p.n_poses;
+    W.bk = (double *)(base + l.bk);
+    W.est_n = 7 * p.n_poses + 3 * p.n_points;
+    W.e_pose = (const int32_t *)(base + l.e_pose); W.e_point = (const int32_t *)(base + l.e_point);
+    W.e_stereo = base + l.e_stereo; W.e_robust = base + l.robust; W.e_level1 = base + l.level1;
+    W.err = (double *)(base + l.err);
+    W.cam.fx = (double)p.fx; W.cam.fy = (double)p.fy; W.cam.cx = (double)p.cx; W.cam.cy = (double)p.cy;
+    W.cam.bf = (double)p.bf; W.cam.bf_f = p.bf;
+    W.cam.delta_mono = (double)(float)std::sqrt(5.991);
+    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    W.pl_pos = (const int32_t *)(base + l.pl_pos);
+    W.hpose = (const int32_t *)(base + l.hpose); W.hpoint = (const int32_t *)(base + l.hpoint);
+    W.pt_off = (const int32_t *)(base + l.pt_off); W.pt_k = (const int32_t *)(base + l.pt_k);
+    W.ps_off = (const int32_t *)(base + l.ps_off); W.ps_k = (const int32_t *)(base + l.ps_k);
+    W.pl_off = (const int32_t *)(base + l.pl_off); W.pl_ph = (const int32_t *)(base + l.pl_k);
+    W.it_ka = (const int32_t *)(base + l.it_ka); W.it_kb = (const int32_t *)(base + l.it_kb);
+    W.it_l = (const int32_t *)(base + l.it_l); W.blk_off = (const int32_t *)(base + l.blk_off);
+    W.sr_o0 = (const int32_t *)(base + l.sr_o0); W.sr_info = (const int32_t *)(base + l.sr_info); W.sr_ij = (const int32_t *)(base + l.sr_ij);
+    W.n_srows = (int)S.sr_o0.size();
+    W.lrec = (double *)(base + l.lrec); W.lomr = (double *)(base + l.lomr); W.Rl = (double *)(base + l.Rl); W.Hpp = (double *)(base + l.Hpp);
+    W.Hll = (double *)(base + l.Hll); W.b = (double *)(base + l.b); W.x = (double *)(base + l.x);
+    W.Hs = (double *)(base + l.Hs); W.bs = (double *)(base + l.bs);
+    W.tmp = (double *)(base + l.tmp); W.scal = (double *)(base + l.scal); W.part = (double *)(base + l.part);
+    W.n_part = l.n_part;
+    W.ldlt = (double *)(base + l.ldlt); W.npad = l.npad; W.ldlt_form = l.ldlt_form;
+    W.hs_ld = l.npad;
+    W.st = (LmState *)(base + l.st);
+    W.abort_word = abort_word;
+    W.out_Tcw = (float *)(base + l.out_Tcw); W.out_xyz = (float *)(base + l.out_xyz);
+    W.out_outlier = base + l.out_outlier;
+    W.out_chi2 = want_chi2 ? (double *)(base + l.out_chi2) : nullptr;
+}
+
+// ---- what a launch sequence runs on
+
+// the largest dimensions of a set of windows, and which reduced-system kernels it needs
+struct GroupDims {
+    bool any_glob = false, any_reg = false;
+    int mx_E = 0, mx_pts = 0, mx_npad_glob = 0, mx_npad_reg = 0;
+    void add(const aos2_lba_problem_t &p, const Pass &S, const WinLayout &l)
+    {
+        if (S.np > 0) {
+            if (l.ldlt_form == kLdltReg) {
+                any_reg = true;
+                mx_npad_reg = std::max(mx_npad_reg, l.npad);
+            } else {
+                any_glob = true;
+                mx_npad_glob = std::max(mx_npad_glob, l.npad);
+            }
+        }
+        mx_E = std::max(mx_E, p.n_edges);
+        mx_pts = std::max(mx_pts, std::max(p.n_points, p.n_poses));
+    }
+};
+
+struct TaskLists {
+    std::vector<SchurTask> schur, pts, lin;
+    size_t size() const { return schur.size() + pts.size() + lin.size(); }
+};
+
+// The task lists of a set of windows `ids` (indices into passes), addressed by their position in `ids` (by_position: a compacted
+// descriptor array) or by ids[position].
+// k_schur's list: the units of all windows, window w on XCD w' (workgroups go round-robin to the 8 XCDs in linear-id order,
+// each with an L2 of its own -- 4 MB, about one window's working set: the Hpl blocks a window's items share are then served by
+// one L2), the windows dealt to the XCDs largest first (every XCD gets about the same number of units), two windows of an XCD
+// at a time, unit by unit -- their DIAG units first.  Padding entries (w = -1) keep the 8 queues in step.
+// The landmark kernels' lists: block b of every window before block b + 1 of any (the windows advance side by side); k_lin: every
+// landmark block first (the long dependent chains of the launch), then one task per free keyframe
+static void build_tasks(const std::vector<Pass> &passes, const std::vector<int> &ids, bool by_position, const LmLayout &lay, TaskLists &T, bool one_queue = false)
+{
+    auto wmap = [&](int k) { return by_position ? k : ids[k]; };
+    std::vector<SchurTask> &tasks = T.schur;
+    const int nwg = (int)ids.size();
+    std::vector<int> order(nwg);
+    std::iota(order.begin(), order.end(), 0);
+    // (dealt by unit count.  By estimated cost instead -- a DIAG / BIG unit = 2 + ceil(items / 256) workgroup rounds, a PACK unit one --
+    // the mixed 64-window batch took 4.15 / 4.17 / 4.14 ms against 4.14 / 4.13 / 4.12: the XCD queues are not what k_schur's tail waits for)
+    auto weight = [&](int k) { return passes[ids[k]].units.size(); };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return weight(a) > weight(b); });
+    const int NX = nwg >= 8 && !one_queue ? 8 : 1;
+    std::vector<std::vector<int>> xw(NX);
+    std::vector<size_t> load(NX, 0);
+    for (int k : order) {
+        const int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        xw[x].push_back(k);
+        load[x] += weight(k);
+    }
+    std::vector<std::vector<SchurTask>> qx(NX);
+    for (int x = 0; x < NX; ++x)
+        for (size_t k = 0; k < xw[x].size(); k += 2) {
+            const int a = xw[x][k], b = k + 1 < xw[x].size() ? xw[x][k + 1] : -1;
+            const std::vector<int32_t> &ua = passes[ids[a]].units;
+            static const std::vector<int32_t> none;
+            const std::vector<int32_t> &ub = b >= 0 ? passes[ids[b]].units : none;
+            for (size_t u = 0; u < std::max(ua.size(), ub.size()); ++u) {
+                if (u < ua.size()) qx[x].push_back(SchurTask{wmap(a), ua[u]});
+                if (u < ub.size()) qx[x].push_back(SchurTask{wmap(b), ub[u]});
+            }
+        }
+    size_t mxq = 0;
+    for (auto &q_ : qx) mxq = std::max(mxq, q_.size());
+    tasks.assign(mxq * NX, SchurTask{-1, 0});
+    for (int x = 0; x < NX; ++x)
+        for (size_t k = 0; k < qx[x].size(); ++k) tasks[k * NX + x] = qx[x][k];
+    int mx_pb = 0, mx_lb = 0, mx_k = 0;
+    std::vector<int> npb(nwg), nlb(nwg);
+    for (int k = 0; k < nwg; ++k) {
+        const Pass &S = passes[ids[k]];
+        npb[k] = lay.points_blocks(S);   // = WinLayout::n_part
+        nlb[k] = lay.lin_blocks(S);
+        mx_pb = std::max(mx_pb, npb[k]); mx_lb = std::max(mx_lb, nlb[k]); mx_k = std::max(mx_k, S.np);
+    }
+    T.pts.clear();
+    T.lin.clear();
+    for (int b = 0; b < mx_pb; ++b)
+        for (int k = 0; k < nwg; ++k)
+            if (b < npb[k]) T.pts.push_back(SchurTask{wmap(k), b});
+    for (int b = 0; b < mx_lb; ++b)
+        for (int k = 0; k < nwg; ++k)
+            if (b < nlb[k]) T.lin.push_back(SchurTask{wmap(k), b});
+    for (int kf = 0; kf < mx_k; ++kf)
+        for (int k = 0; k < nwg; ++k)
+            if (kf < passes[ids[k]].np) T.lin.push_back(SchurTask{wmap(k), (1 << 28) | kf});
+}
+
+// the device addresses of a TaskLists
+struct DevTasks {
+    const SchurTask *schur, *pts, *lin;
+};
+// Writes the three lists of T behind each other at byte offset `o` of the staging buffer `host`, which mirrors the device memory
+// at `dev`; `o` moves on to the end of what was written
+static DevTasks put_tasks(const TaskLists &T, uint8_t *host, const uint8_t *dev, size_t &o)
+{
+    DevTasks d;
+    const std::vector<SchurTask> *lists[3] = {&T.schur, &T.pts, &T.lin};
+    const SchurTask **where[3] = {&d.schur, &d.pts, &d.lin};
+    for (int k = 0; k < 3; ++k) {
+        *where[k] = (const SchurTask *)(dev + o);
+        if (!lists[k]->empty()) memcpy(host + o, lists[k]->data(), sizeof(SchurTask) * lists[k]->size());
+        o += sizeof(SchurTask) * lists[k]->size();
+    }
+    return d;
+}
+
+// the streams a launch sequence is enqueued on: its own, and the one the second reduced-system kernel runs on, forked and joined
+struct StreamSet {
+    hipStream_t q, q2;
+    hipEvent_t fork, join;
+};
+static StreamSet group_streams(const aos2_lba *s, int g)
+{
+    return g == 0 ? StreamSet{s->stream, s->stream2, s->ev_fork, s->ev_join} : StreamSet{s->stream_b, s->stream2_b, s->ev_fork_b, s->ev_join_b};
+}
+
+// What a launch sequence runs on: the descriptor array its task lists index (`wins`), the first descriptor and the number of
+// windows of the kernels that take one workgroup row per window (`blk`, nw), the lists, the largest dimensions, the streams
+struct Prog : StreamSet {
+    const LbaWin *wins, *blk;
+    int nw;
+    const SchurTask *schur, *pts, *lin;
+    size_t n_schur, n_pts, n_lin;
+    GroupDims D;
+};
+static Prog make_prog(const LbaWin *wins, const LbaWin *blk, int nw, const TaskLists &T, const DevTasks &d, const GroupDims &D, const StreamSet &Q)
+{
+    return Prog{Q, wins, blk, nw, d.schur, d.pts, d.lin, T.schur.size(), T.pts.size(), T.lin.size(), D};
+}
+
+// ---- enqueueing.  What the launches of a call share besides their Prog:
+struct LaunchCtx {
+    aos2_lba *s;
+    bool walk;              // the landmark kernels' layout (LmLayout::walk)
+    bool stagger_pending;   // two groups: the second group's stream has not been released yet (enqueue_trial)
+};
+
+static unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+static void enqueue_points(const LaunchCtx &C, const Prog &P, int solve)
+{
+    if (C.walk)
+        hipLaunchKernelGGL(k_points_walk, dim3((unsigned)P.n_pts), dim3(128), 0, P.q, P.wins, P.pts, solve);
+    else
+        hipLaunchKernelGGL(k_points, dim3((unsigned)P.n_pts), dim3(256), 0, P.q, P.wins, P.pts, solve);
+}
+static void enqueue_lin(const LaunchCtx &C, const Prog &P, int init)
+{
+    if (!P.n_lin) return;
+    if (C.walk)
+        hipLaunchKernelGGL(k_lin<true>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
+    else
+        hipLaunchKernelGGL(k_lin<false>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
+}
+static void enqueue_init(const LaunchCtx &C, const Prog &P)
+{
+    enqueue_points(C, P, 0);
+    enqueue_lin(C, P, 1);
+    hipLaunchKernelGGL(k_lm_init, dim3(P.nw), dim3(1024), 0, P.q, P.blk);
+}
+// one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of both kinds)
+static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
+{
+    const GroupDims &D = P.D;
+    if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
+    if (first_group && C.stagger_pending) {   // the other group starts here: half a trial behind
+        (void)hipEventRecord(C.s->ev_stag, C.s->stream);
+        (void)hipStreamWaitEvent(C.s->stream_b, C.s->ev_stag, 0);
+        C.stagger_pending = false;
+    }
+    // the two forms of the reduced-system kernel work on different windows: side by side (the register form on a stream of its own)
+    const bool both = D.any_glob && D.any_reg;
+    if (both) {
+        (void)hipEventRecord(P.fork, P.q);
+        (void)hipStreamWaitEvent(P.q2, P.fork, 0);
+    }
+    if (D.any_reg)
+        hipLaunchKernelGGL(k_ldlt_reg, dim3(P.nw), dim3(kLrThreads), ldlt_reg_lds_doubles(D.mx_npad_reg) * sizeof(double), both ? P.q2 : P.q, P.blk);
+    if (D.any_glob)
+        hipLaunchKernelGGL(k_ldlt_dev, dim3(P.nw), dim3(512), ((size_t)D.mx_npad_glob * 17 + 4 * (size_t)D.mx_npad_glob + 3 * 16 * 17 + 16) * sizeof(double), P.q,
+                           P.blk);
+    if (both) {
+        (void)hipEventRecord(P.join, P.q2);
+        (void)hipStreamWaitEvent(P.q, P.join, 0);
+    }
+    enqueue_points(C, P, 1);   // + the LM decision in its last workgroup
+    enqueue_lin(C, P, 0);
+}
+static void enqueue_transition(const Prog &P)
+{
+    hipLaunchKernelGGL(k_transition, dim3(blocks(P.D.mx_E, 256), P.nw), dim3(256), 0, P.q, P.blk);
+}
+
+// ---- the steps of aos2_lba_solve_batch
+
+// Validates the call and settles the windows whose stop flag is set on entry (Optimizer.cc:656-658: return before optimising when
+// the flag is already set; nothing is written back); `act` lists the others
+static int settle_entry(const aos2_lba *s, const aos2_lba_problem_t *problems, aos2_lba_result_t *results, int n_problems, std::vector<int> &act, bool &want_chi2)
+{
+    want_chi2 = false;
+    for (int w = 0; w < n_problems; ++w) {
+        const aos2_lba_problem_t *p = problems + w;
+        aos2_lba_result_t *r = results + w;
+        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id ||
+            !p->point_xyz || !p->point_id || !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo ||
+            !p->edge_inv_sigma2 || !r->pose_Tcw || !r->point_xyz) {
+            set_error("bad LocalBA problem %d", w);
+            return AOS2_ERR_ARG;
+        }
+        want_chi2 |= r->edge_chi2 != nullptr;   // (the edges' vertex indices are checked with the structure build, a thread per window)
+    }
+    for (int w = 0; w < n_problems; ++w) {
+        const aos2_lba_problem_t *p = problems + w;
+        aos2_lba_result_t *r = results + w;
+        r->iters_done_first = r->iters_done_second = 0;
+        r->trials_first = r->trials_second = 0;
+        r->final_chi2 = r->final_lambda = 0;
+        r->ms_device = 0;
+        r->polls = 1;
+        r->stop_poll = 0;
+        r->status = AOS2_OK;
+        if (stop_requested(p) || s->debug_stop_at_poll == 1) {
+            memcpy(r->pose_Tcw, p->pose_Tcw, sizeof(float) * 16 * p->n_poses);
+            memcpy(r->point_xyz, p->point_xyz, sizeof(float) * 3 * p->n_points);
+            if (r->edge_outlier) memset(r->edge_outlier, 0, p->n_edges);
+            r->status = AOS2_ERR_STOPPED;
+            r->stop_poll = 1;
+        } else
+            act.push_back(w);
+    }
+    return AOS2_OK;
+}
+
+// Window groups.  A trial is three wide launches (Schur, back-substitution, linearisation: every window's landmarks) and one
+// narrow one (the reduced systems: ONE workgroup per window, the longest launch of the mixed batch, during which most of the device
+// idles).  A batch of many windows runs as TWO groups with the same program each, on their own streams, the second started
+// behind the first group's first Schur launch: one group's reduced systems are factorised while the other group's landmark
+// kernels fill the device.  Windows are dealt to the groups by size (edges), largest first, so both get the same mix; the
+// windows of a group are neighbours in the descriptor array.  (aos2_lba_set_window_groups overrides.)
+// Returns the number of groups; group g is act[goff[g] .. goff[g + 1]), `act` reordered accordingly.
+static int deal_groups(const aos2_lba *s, const aos2_lba_problem_t *problems, std::vector<int> &act, int (&goff)[3])
+{
+    const int nw = (int)act.size();
+    int G = s->window_groups ? s->window_groups : nw >= 16 ? 2 : 1;
+    if (G > nw) G = 1;
+    goff[0] = 0;
+    goff[1] = goff[2] = nw;
+    if (G == 2) {
+        std::vector<int> order(act);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return problems[a].n_edges > problems[b].n_edges; });
+        std::vector<int> g0, g1;
+        for (size_t k = 0; k < order.size(); ++k) (((k & 3) == 0 || (k & 3) == 3) ? g0 : g1).push_back(order[k]);   // a b b a | a b b a ...
+        act = g0;
+        act.insert(act.end(), g1.begin(), g1.end());
+        goff[1] = (int)g0.size();
+    }
+    return G;
+}
+
+// The arena of a call: [staged regions of all windows | task lists of the groups | descriptors] (the part that is uploaded)
+// [continuation region][device-only regions of all windows][states and results of all windows] (the part that comes back)
+struct ArenaPlan {
+    std::vector<WinLayout> L;
+    size_t o_tasks, o_wins, staged_bytes, o_cont, cont_bytes, o_res, res_bytes, bytes;
+};
+static void plan_arena(const aos2_lba_problem_t *problems, const std::vector<int> &act, const std::vector<Pass> &passes, const LmLayout &lay, size_t n_all_tasks,
+                       bool want_chi2, ArenaPlan &A)
+{
+    const int nw = (int)act.size();
+    A.L.resize(nw);
+    Bump B;
+    for (int i = 0; i < nw; ++i) layout_staged(problems[act[i]], passes[i], B, A.L[i]);
+    A.o_tasks = B.take(sizeof(SchurTask) * n_all_tasks + 8);
+    A.o_wins = B.take(sizeof(LbaWin) * (size_t)nw);
+    A.staged_bytes = B.size;
+    // (a continuation round runs on the windows that are not finished, compacted: their descriptors and task lists go here)
+    // Sized for ANY subset of the windows, not for the first round's lists: a subset is dealt to the 8 queues anew (largest first; with
+    // queues of about equal length the padded list holds about sum + 8 x max units -- a first round of fewer than 8 windows per group
+    // is not padded at all, and the dealing is not monotone on subsets); the landmark / linearisation lists of a subset are parts of
+    // the full ones.  A subset whose padded list is longer still falls back to one unpadded queue (continuation_round), which always fits.
+    size_t cont_tasks = 0, cont_max_units = 0;
+    for (int i = 0; i < nw; ++i) {
+        const Pass &S = passes[i];
+        cont_max_units = std::max(cont_max_units, S.units.size());
+        cont_tasks += S.units.size() + (size_t)lay.points_blocks(S) + (size_t)lay.lin_blocks(S) + (size_t)S.np;
+    }
+    cont_tasks += 8 * cont_max_units;
+    A.cont_bytes = sizeof(LbaWin) * (size_t)nw + sizeof(SchurTask) * std::max(cont_tasks, n_all_tasks) + 64;
+    A.o_cont = B.take(A.cont_bytes);
+    for (int i = 0; i < nw; ++i) layout_scratch(problems[act[i]], passes[i], lay, B, A.L[i]);
+    A.o_res = B.take(0);
+    for (int i = 0; i < nw; ++i) layout_results(problems[act[i]], want_chi2, B, A.L[i]);
+    A.res_bytes = B.size - A.o_res;
+    A.bytes = B.size;
+}
+
+// Staging, a pool thread per window.  A window's staged region goes to the device as soon as it is assembled: its upload overlaps
+// the staging of the other windows (one copy of everything after the staging cost 0.4 ms more per 32-window call)
+static int stage_and_upload(aos2_lba *s, WindowPool &pool, const aos2_lba_problem_t *problems, const std::vector<int> &act, const std::vector<Pass> &passes,
+                            const ArenaPlan &A)
+{
+    const int nw = (int)act.size();
+    uint8_t *base = s->arena.p, *hin = s->h_in.p;
+    std::vector<uint8_t> up_fail(nw, 0);
+    pool.run(nw, [&](int i) {
+        stage_window(hin, A.L[i], problems[act[i]], passes[i]);
+        const size_t r0 = A.L[i].in_Tcw, r1 = i + 1 < nw ? A.L[i + 1].in_Tcw : A.o_tasks;
+        if (hipSetDevice(s->device) != hipSuccess || hipMemcpyAsync(base + r0, hin + r0, r1 - r0, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+            up_fail[i] = 1;
+    });
+    for (int i = 0; i < nw; ++i)
+        if (up_fail[i]) {
+            set_error("LocalBA: upload of window %d failed", act[i]);
+            return AOS2_ERR_HIP;
+        }
+    return AOS2_OK;
+}
+
+// The whole procedure of a group's windows: optimisation k gets slots[k] trials and runs if any window of the call asks for
+// iterations (iters[k] > 0)
+static void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const int (&iters)[2], const int (&slots)[2])
+{
+    hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, C.s->debug_stop_at_poll);
+    for (int k = 0; k < 2; ++k) {
+        if (k == 1) enqueue_transition(P);
+        if (iters[k] > 0) {
+            enqueue_init(C, P);
+            for (int t = 0; t < slots[k]; ++t) enqueue_trial(C, P, first_group);
+        }
+    }
+}
+
+// what the steps after the upload work on
+struct Batch {
+    const aos2_lba_problem_t *problems;
+    const std::vector<int> &act;        // the windows that run, in descriptor order
+    const std::vector<Pass> &passes;    // their structures ...
+    const ArenaPlan &A;                 // ... and regions
+    LmLayout lay;
+    const LbaWin *hw;                   // the host's copy of their descriptors
+    bool any_flag;                      // a window has a stop flag: forwarded to the abort words while the device runs
+    const LmState *state_of(const aos2_lba *s, int i) const { return reinterpret_cast<const LmState *>(s->h_stage.p + (A.L[i].st - A.o_res)); }
+};
+
+// Ends the programs with the final check; the results (and states) come back as one copy; the host forwards pbStopFlag into the
+// mapped abort words meanwhile
+static int finish(aos2_lba *s, const Prog *progs, int n_progs, const Batch &Bt)
+{
+    hipStream_t q = s->stream;
+    for (int g = 0; g < n_progs; ++g) {
+        const Prog &P = progs[g];
+        hipLaunchKernelGGL(k_final, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk);
+    }
+    if (n_progs == 2) {
+        AOS2_HIP_CHECK(hipEventRecord(s->ev_done_b, s->stream_b));
+        AOS2_HIP_CHECK(hipStreamWaitEvent(q, s->ev_done_b, 0));
+    }
+    AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, s->arena.p + Bt.A.o_res, Bt.A.res_bytes, hipMemcpyDeviceToHost, q));
+    if (Bt.any_flag) {
+        AOS2_HIP_CHECK(hipEventRecord(s->ev[2], q));
+        while (hipEventQuery(s->ev[2]) == hipErrorNotReady)
+            for (size_t i = 0; i < Bt.act.size(); ++i)
+                if (stop_requested(Bt.problems + Bt.act[i])) __atomic_store_n(&s->h_abort.p[i], 1, __ATOMIC_RELAXED);
+    }
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    return AOS2_OK;
+}
+
+// One continuation round: the windows that are not finished when a program has run (steps rejected by the gain ratio) get another,
+// sized for what they still need at most if no further step is rejected, compacted: their descriptors and task lists, which address
+// them by position, go to the continuation region.  *done: there was no such window.
+static int continuation_round(LaunchCtx &C, const Batch &Bt, int max_i2, int round, bool *done)
+{
+    aos2_lba *s = C.s;
+    const ArenaPlan &A = Bt.A;
+    std::vector<int> todo;
+    int need1 = 0, need2 = 0;
+    bool before_second = false;
+    for (int i = 0; i < (int)Bt.act.size(); ++i) {
+        const LmState *ls = Bt.state_of(s, i);
+        if (ls->phase == 3) continue;
+        todo.push_back(i);
+        if (ls->phase == 0) need1 = std::max(need1, std::max(1, ls->iters_max[0] - ls->it));
+        if (ls->phase <= 1) before_second = true;
+        if (ls->phase == 2) need2 = std::max(need2, std::max(1, ls->iters_max[1] - ls->it));
+    }
+    *done = todo.empty();
+    if (*done) return AOS2_OK;
+    if (round > 64) {   // 2 x 10 iterations x 10 trials at most: cannot happen
+        set_error("internal: LocalBA program did not finish");
+        return AOS2_ERR_ARG;
+    }
+    if (before_second) need2 = std::max(need2, max_i2);
+    TaskLists TC;
+    build_tasks(Bt.passes, todo, true, Bt.lay, TC);
+    static const bool force_one_queue = getenv("AOS2_LBA_CONT_ONE_QUEUE") != nullptr;   // (test hook: the fallback below on every continuation)
+    // (the dealing is not monotone on subsets: should one pad past the bound, one unpadded queue always fits -- its length is the subset's sum)
+    if (force_one_queue || sizeof(LbaWin) * todo.size() + sizeof(SchurTask) * TC.size() > A.cont_bytes) build_tasks(Bt.passes, todo, true, Bt.lay, TC, true);
+    if (sizeof(LbaWin) * todo.size() + sizeof(SchurTask) * TC.size() > A.cont_bytes) {
+        set_error("internal: continuation region");
+        return AOS2_ERR_ARG;
+    }
+    uint8_t *hc = s->h_in.p + A.o_cont;
+    const uint8_t *dc = s->arena.p + A.o_cont;
+    GroupDims D;
+    for (size_t k = 0; k < todo.size(); ++k) {
+        const int i = todo[k];
+        reinterpret_cast<LbaWin *>(hc)[k] = Bt.hw[i];
+        D.add(Bt.problems[Bt.act[i]], Bt.passes[i], A.L[i]);
+    }
+    size_t o = sizeof(LbaWin) * todo.size();
+    const DevTasks dt = put_tasks(TC, hc, dc, o);
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p + A.o_cont, hc, o, hipMemcpyHostToDevice, s->stream));
+    const Prog PC = make_prog((const LbaWin *)dc, (const LbaWin *)dc, (int)todo.size(), TC, dt, D, group_streams(s, 0));
+    for (int t = 0; t < need1; ++t) enqueue_trial(C, PC, false);
+    if (before_second) {
+        enqueue_transition(PC);
+        enqueue_init(C, PC);
+    }
+    for (int t = 0; t < need2; ++t) enqueue_trial(C, PC, false);
+    s->last_trial_slots += need1 + need2;
+    s->last_window_slots += (long long)(need1 + need2) * (long long)todo.size();
+    s->last_host_rounds++;
+    return finish(s, &PC, 1, Bt);
+}
+
+static void write_back(const aos2_lba *s, const Batch &Bt, aos2_lba_result_t *results)
+{
+    const ArenaPlan &A = Bt.A;
+    const int nw = (int)Bt.act.size();
+    if (getenv("AOS2_LBA_TRACE"))
+        for (int i = 0; i < nw; ++i) {
+            const LmState *ls = Bt.state_of(s, i);
+            for (int t = 0; t < ls->ntr; ++t)
+                fprintf(stderr, "[lba] win %d trial %2d lambda %.6e chi %.9e -> %.9e rho %.6e\n", i, t, ls->tr_lambda[t], ls->tr_cur[t], ls->tr_temp[t], ls->tr_rho[t]);
+        }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+    for (int i = 0; i < nw; ++i) {
+        const aos2_lba_problem_t *p = Bt.problems + Bt.act[i];
+        aos2_lba_result_t *r = results + Bt.act[i];
+        const WinLayout &l = A.L[i];
+        const uint8_t *hb = s->h_stage.p;
+        const LmState *ls = Bt.state_of(s, i);
+        memcpy(r->pose_Tcw, hb + (l.out_Tcw - A.o_res), 64 * (size_t)p->n_poses);
+        memcpy(r->point_xyz, hb + (l.out_xyz - A.o_res), 12 * (size_t)p->n_points);
+        if (r->edge_outlier) memcpy(r->edge_outlier, hb + (l.out_outlier - A.o_res), (size_t)p->n_edges);
+        if (r->edge_chi2) memcpy(r->edge_chi2, hb + (l.out_chi2 - A.o_res), 8 * (size_t)p->n_edges);
+        r->iters_done_first = ls->iters_done[0];
+        r->iters_done_second = ls->iters_done[1];
+        r->trials_first = ls->trials[0];
+        r->trials_second = ls->trials[1];
+        r->final_chi2 = ls->final_chi2;
+        r->final_lambda = ls->final_lambda;
+        r->polls = ls->polls;
+        r->stop_poll = ls->stop_poll;
+        r->ms_device = ms;
+    }
+}
 
 }  // namespace aos2
 
@@ -2303,47 +2842,16 @@ int aos2_lba_debug_host_phase(const aos2_lba_problem_t *problems, int n_problems
     std::vector<Pass> passes(n_problems);
     WindowPool pool;
     if (n_problems > 1 && threads > 1) pool.start(std::min(threads, n_problems));
-    std::vector<uint8_t> ok(n_problems, 1);
     const auto t0 = std::chrono::steady_clock::now();
-    pool.run(n_problems, [&](int i) {
-        const aos2_lba_problem_t *p = problems + i;
-        for (int e = 0; e < p->n_edges; ++e)
-            if (p->edge_pose[e] < 0 || p->edge_pose[e] >= p->n_poses || p->edge_point[e] < 0 || p->edge_point[e] >= p->n_points) {
-                ok[i] = 0;
-                return;
-            }
-        ok[i] = build_pass(p, passes[i]) ? 1 : 0;
-        if (ok[i] && passes[i].np > 0) {
-            build_schur_items(passes[i]);
-            build_schur_units(passes[i]);
-        }
-    });
+    if (int st = build_structures(pool, problems, nullptr, n_problems, passes)) return st;
     const auto t1 = std::chrono::steady_clock::now();
-    for (int i = 0; i < n_problems; ++i)
-        if (!ok[i]) {
-            set_error("problem %d: bad edge", i);
-            return AOS2_ERR_ARG;
-        }
     std::vector<std::vector<uint8_t>> stage(n_problems);
     pool.run(n_problems, [&](int i) {
-        const aos2_lba_problem_t *p = problems + i;
-        const Pass &S = passes[i];
-        const size_t NP = p->n_poses, NL = p->n_points, E = p->n_edges;
-        const std::vector<int32_t> *lists[] = {&S.pl_pos, &S.hpose, &S.hpoint, &S.pt_off, &S.pt_k, &S.ps_off, &S.ps_k, &S.pl_off, &S.pl_ph,
-                                               &S.it_ka, &S.it_kb, &S.it_l, &S.blk_off, &S.sr_o0, &S.sr_info, &S.sr_ij};
-        size_t bytes = 64 * NP + 12 * NL + 12 * E + 4 * E + 4 * E + 4 * E + E;
-        for (auto *v : lists) bytes += 4 * v->size();
-        std::vector<uint8_t> &buf = stage[i];
-        buf.resize(bytes);
-        uint8_t *d = buf.data();
-        auto put = [&](const void *src, size_t n) {
-            memcpy(d, src, n);
-            d += n;
-        };
-        put(p->pose_Tcw, 64 * NP); put(p->point_xyz, 12 * NL); put(p->edge_obs, 12 * E); put(p->edge_inv_sigma2, 4 * E);
-        put(p->edge_pose, 4 * E); put(p->edge_point, 4 * E); put(p->edge_stereo, E);
-        for (auto *v : lists)
-            if (!v->empty()) put(v->data(), 4 * v->size());
+        WinLayout l{};
+        Bump B;
+        layout_staged(problems[i], passes[i], B, l);
+        stage[i].resize(B.size);
+        stage_window(stage[i].data(), l, problems[i], passes[i]);
     });
     const auto t2 = std::chrono::steady_clock::now();
     if (build_ms) *build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -2374,63 +2882,17 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
         set_error("bad LocalBA batch");
         return AOS2_ERR_ARG;
     }
-    bool want_chi2 = false;
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        aos2_lba_result_t *r = results + w;
-        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id ||
-            !p->point_xyz || !p->point_id || !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo ||
-            !p->edge_inv_sigma2 || !r->pose_Tcw || !r->point_xyz) {
-            set_error("bad LocalBA problem %d", w);
-            return AOS2_ERR_ARG;
-        }
-        want_chi2 |= r->edge_chi2 != nullptr;   // (the edges' vertex indices are checked with the structure build, a thread per window)
-    }
-    // Optimizer.cc:656-658: return before optimising when the flag is already set; nothing is written back
+    // ---- the windows that run, dealt to one or two groups
     std::vector<int> act;
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        aos2_lba_result_t *r = results + w;
-        r->iters_done_first = r->iters_done_second = 0;
-        r->trials_first = r->trials_second = 0;
-        r->final_chi2 = r->final_lambda = 0;
-        r->ms_device = 0;
-        r->polls = 1;
-        r->stop_poll = 0;
-        r->status = AOS2_OK;
-        if (stop_requested(p) || s->debug_stop_at_poll == 1) {
-            memcpy(r->pose_Tcw, p->pose_Tcw, sizeof(float) * 16 * p->n_poses);
-            memcpy(r->point_xyz, p->point_xyz, sizeof(float) * 3 * p->n_points);
-            if (r->edge_outlier) memset(r->edge_outlier, 0, p->n_edges);
-            r->status = AOS2_ERR_STOPPED;
-            r->stop_poll = 1;
-        } else
-            act.push_back(w);
-    }
+    bool want_chi2;
+    int st = settle_entry(s, problems, results, n_problems, act, want_chi2);
+    if (st) return st;
     const int nw = (int)act.size();
     if (nw == 0) return AOS2_OK;
-    int st = lba_handle_init(s);
-    if (st) return st;
-    // Window groups.  A trial is three wide launches (Schur, back-substitution, linearisation: every window's landmarks) and one
-    // narrow one (the reduced systems: ONE workgroup per window, the longest launch of the mixed batch, during which most of the device
-    // idles).  A batch of many windows runs as TWO groups with the same program each, on their own streams, the second started
-    // behind the first group's first Schur launch: one group's reduced systems are factorised while the other group's landmark
-    // kernels fill the device.  Windows are dealt to the groups by size (edges), largest first, so both get the same mix; the
-    // windows of a group are neighbours in the descriptor array.  (aos2_lba_set_window_groups overrides.)
-    int G = s->window_groups ? s->window_groups : nw >= 16 ? 2 : 1;
-    if (G > nw) G = 1;
+    if ((st = lba_handle_init(s))) return st;
+    int goff[3];
+    const int G = deal_groups(s, problems, act, goff);
     if (G == 2 && (st = lba_group_streams(s))) return st;
-    int goff[3] = {0, nw, nw};
-    if (G == 2) {
-        std::vector<int> order(act);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return problems[a].n_edges > problems[b].n_edges; });
-        std::vector<int> g0, g1;
-        for (size_t k = 0; k < order.size(); ++k) (((k & 3) == 0 || (k & 3) == 3) ? g0 : g1).push_back(order[k]);   // a b b a | a b b a ...
-        act = g0;
-        act.insert(act.end(), g1.begin(), g1.end());
-        goff[1] = (int)g0.size();
-    }
-    s->last_groups = G;
     // layout of the landmark kernels: kLmSlots threads per landmark while the landmarks of the call cannot fill the device
     // (one or a few windows: latency), one thread per landmark beyond (throughput); same results either way.
     // AOS2_LBA_LAYOUT=slots|walk forces one (tests).
@@ -2438,203 +2900,32 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     for (int i = 0; i < nw; ++i) total_points += (size_t)problems[act[i]].n_points;
     bool walk = total_points > 16000;
     if (const char *e = getenv("AOS2_LBA_LAYOUT")) walk = !strcmp(e, "walk");
-    const int lm_per_block = walk ? 128 : kLmBlock;
-    const bool prof = getenv("AOS2_LBA_PROF") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!prof) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[lba] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - t_prev).count());
-        t_prev = t;
-    };
+    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
 
-    // ---- per-window structure (host; windows in parallel when there are several)
+    // ---- per-window structure (host; windows in parallel when there are several), the groups' task lists
     auto rg = std::make_unique<RoctxRange>("LocalBA::buildStructure (index mapping, edge lists, Schur items)");
     if (!s->lba_cache) s->lba_cache = new LbaCache();
     std::vector<Pass> &passes = static_cast<LbaCache *>(s->lba_cache)->passes;
     if ((int)passes.size() < nw) passes.resize(nw);
     WindowPool &pool = static_cast<LbaCache *>(s->lba_cache)->pool;
     if (nw > 1) pool.start(lba_host_threads(s, nw));
-    auto for_windows = [&](auto &&fn) { pool.run(nw, fn); };
-    std::vector<uint8_t> pass_ok(nw, 1);
-    std::vector<int> bad_edge(nw, -1);
-    for_windows([&](int i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        for (int e = 0; e < p->n_edges; ++e)
-            if (p->edge_pose[e] < 0 || p->edge_pose[e] >= p->n_poses || p->edge_point[e] < 0 || p->edge_point[e] >= p->n_points) {
-                bad_edge[i] = e;
-                return;
-            }
-        pass_ok[i] = build_pass(p, passes[i]) ? 1 : 0;
-        if (pass_ok[i] && passes[i].np > 0) {
-            build_schur_items(passes[i]);
-            build_schur_units(passes[i]);
-        } else
-            passes[i].units.clear();
-    });
-    for (int i = 0; i < nw; ++i)
-        if (bad_edge[i] >= 0) {
-            set_error("problem %d: edge %d references a vertex out of range", act[i], bad_edge[i]);
-            return AOS2_ERR_ARG;
-        }
-    for (int i = 0; i < nw; ++i)
-        if (!pass_ok[i]) {   // (cannot come from the reference: KeyFrame observations are a map MapPoint -> index)
-            set_error("problem %d: two edges connect the same keyframe and map point", act[i]);
-            return AOS2_ERR_ARG;
-        }
-    lap("build_pass + items");
+    if ((st = build_structures(pool, problems, act.data(), nw, passes))) return st;
     rg = std::make_unique<RoctxRange>("LocalBA::stage + upload");
-
-    // ---- arena layout: [staged inputs of all windows | descriptors][device-only scratch][results of all windows]
-    std::vector<WinLayout> L(nw);
-    Bump B;
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        const Pass &S = passes[i];
-        WinLayout &l = L[i];
-        const size_t NP = p->n_poses, NL = p->n_points, E = p->n_edges;
-        l.in_Tcw = B.take(64 * NP); l.in_xyz = B.take(12 * NL); l.in_obs = B.take(12 * E); l.in_w = B.take(4 * E);
-        l.e_pose = B.take(4 * E); l.e_point = B.take(4 * E); l.e_stereo = B.take(E);
-        l.pl_pos = B.take(4 * E);
-        l.hpose = B.take(4 * (size_t)S.np + 4); l.hpoint = B.take(4 * (size_t)S.nl + 4);
-        l.pt_off = B.take(4 * ((size_t)S.nl + 1)); l.pt_k = B.take(4 * S.pt_k.size() + 4);
-        l.ps_off = B.take(4 * ((size_t)S.np + 1)); l.ps_k = B.take(4 * S.ps_k.size() + 4);
-        l.pl_off = B.take(4 * ((size_t)S.nl + 1)); l.pl_k = B.take(4 * S.pl_k.size() + 4);
-        l.n_items = S.it_ka.size();
-        l.it_ka = B.take(4 * l.n_items + 4); l.it_kb = B.take(4 * l.n_items + 4); l.it_l = B.take(4 * l.n_items + 4);
-        l.blk_off = B.take(4 * S.blk_off.size() + 4);
-        l.sr_o0 = B.take(4 * S.sr_o0.size() + 4); l.sr_info = B.take(4 * S.sr_o0.size() + 4); l.sr_ij = B.take(4 * S.sr_o0.size() + 4);
-    }
-    // k_schur's task list: the units of all windows, window w on XCD w' (workgroups go round-robin to the 8 XCDs in linear-id order,
-    // each with an L2 of its own -- 4 MB, about one window's working set: the Hpl blocks a window's items share are then served by
-    // one L2), the windows dealt to the XCDs largest first (every XCD gets about the same number of units), two windows of an XCD
-    // at a time, unit by unit -- their DIAG units first.  Padding entries (w = -1) keep the 8 queues in step.
-    // The task lists of a set of windows `ids` (indices into passes / L), the windows addressed as wmap(position): the Schur units
-    // (see above), then the landmark kernels' lists: block b of every window before block b + 1 of any (the windows advance side by
-    // side); k_lin: every landmark block first (the long dependent chains of the launch), then one task per free keyframe
-    struct TaskLists {
-        std::vector<SchurTask> schur, pts, lin;
-    };
-    const int lin_block = walk ? 256 : kLmBlock;
-    auto build_tasks = [&](const std::vector<int> &ids, auto &&wmap, TaskLists &T, bool one_queue = false) {
-        std::vector<SchurTask> &tasks = T.schur;
-        const int nwg = (int)ids.size();
-        std::vector<int> order(nwg);
-        std::iota(order.begin(), order.end(), 0);
-        // (dealt by unit count.  By estimated cost instead -- a DIAG / BIG unit = 2 + ceil(items / 256) workgroup rounds, a PACK unit one --
-        // the mixed 64-window batch took 4.15 / 4.17 / 4.14 ms against 4.14 / 4.13 / 4.12: the XCD queues are not what k_schur's tail waits for)
-        auto weight = [&](int k) { return passes[ids[k]].units.size(); };
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return weight(a) > weight(b); });
-        const int NX = nwg >= 8 && !one_queue ? 8 : 1;
-        std::vector<std::vector<int>> xw(NX);
-        std::vector<size_t> load(NX, 0);
-        for (int k : order) {
-            const int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            xw[x].push_back(k);
-            load[x] += weight(k);
-        }
-        std::vector<std::vector<SchurTask>> qx(NX);
-        for (int x = 0; x < NX; ++x)
-            for (size_t k = 0; k < xw[x].size(); k += 2) {
-                const int a = xw[x][k], b = k + 1 < xw[x].size() ? xw[x][k + 1] : -1;
-                const std::vector<int32_t> &ua = passes[ids[a]].units;
-                static const std::vector<int32_t> none;
-                const std::vector<int32_t> &ub = b >= 0 ? passes[ids[b]].units : none;
-                for (size_t u = 0; u < std::max(ua.size(), ub.size()); ++u) {
-                    if (u < ua.size()) qx[x].push_back(SchurTask{wmap(a), ua[u]});
-                    if (u < ub.size()) qx[x].push_back(SchurTask{wmap(b), ub[u]});
-                }
-            }
-        size_t mxq = 0;
-        for (auto &q_ : qx) mxq = std::max(mxq, q_.size());
-        tasks.assign(mxq * NX, SchurTask{-1, 0});
-        for (int x = 0; x < NX; ++x)
-            for (size_t k = 0; k < qx[x].size(); ++k) tasks[k * NX + x] = qx[x][k];
-        int mx_pb = 0, mx_lb = 0, mx_k = 0;
-        std::vector<int> npb(nwg), nlb(nwg);
-        for (int k = 0; k < nwg; ++k) {
-            const Pass &S = passes[ids[k]];
-            npb[k] = std::max(1, (S.nl + lm_per_block - 1) / lm_per_block);   // = WinLayout::n_part
-            nlb[k] = (S.nl + lin_block - 1) / lin_block;
-            mx_pb = std::max(mx_pb, npb[k]); mx_lb = std::max(mx_lb, nlb[k]); mx_k = std::max(mx_k, S.np);
-        }
-        T.pts.clear();
-        T.lin.clear();
-        for (int b = 0; b < mx_pb; ++b)
-            for (int k = 0; k < nwg; ++k)
-                if (b < npb[k]) T.pts.push_back(SchurTask{wmap(k), b});
-        for (int b = 0; b < mx_lb; ++b)
-            for (int k = 0; k < nwg; ++k)
-                if (b < nlb[k]) T.lin.push_back(SchurTask{wmap(k), b});
-        for (int kf = 0; kf < mx_k; ++kf)
-            for (int k = 0; k < nwg; ++k)
-                if (kf < passes[ids[k]].np) T.lin.push_back(SchurTask{wmap(k), (1 << 28) | kf});
-    };
     TaskLists TL[2];
-    std::vector<SchurTask> *tasks_g[2] = {&TL[0].schur, &TL[1].schur}, *pts_tasks_g[2] = {&TL[0].pts, &TL[1].pts}, *lin_tasks_g[2] = {&TL[0].lin, &TL[1].lin};
     size_t n_all_tasks = 0;
     for (int g = 0; g < G; ++g) {
         std::vector<int> ids(goff[g + 1] - goff[g]);
         std::iota(ids.begin(), ids.end(), goff[g]);
-        build_tasks(ids, [&](int k) { return ids[k]; }, TL[g]);   // (the groups' kernels index the whole descriptor array)
-        n_all_tasks += TL[g].schur.size() + TL[g].pts.size() + TL[g].lin.size();
+        build_tasks(passes, ids, false, lay, TL[g]);   // (the groups' kernels index the whole descriptor array)
+        n_all_tasks += TL[g].size();
     }
-    const size_t o_tasks = B.take(sizeof(SchurTask) * n_all_tasks + 8);
-    const size_t o_wins = B.take(sizeof(LbaWin) * (size_t)nw);
-    const size_t staged_bytes = B.size;
-    // (a continuation round runs on the windows that are not finished, compacted: their descriptors and task lists go here)
-    // Sized for ANY subset of the windows, not for the first round's lists: a subset is dealt to the 8 queues anew (largest first; with
-    // queues of about equal length the padded list holds about sum + 8 x max units -- a first round of fewer than 8 windows per group
-    // is not padded at all, and the dealing is not monotone on subsets); the landmark / linearisation lists of a subset are parts of
-    // the full ones.  A subset whose padded list is longer still falls back to one unpadded queue (below), which always fits.
-    size_t cont_tasks = 0, cont_max_units = 0;
-    for (int i = 0; i < nw; ++i) {
-        const Pass &S = passes[i];
-        cont_max_units = std::max(cont_max_units, S.units.size());
-        cont_tasks += S.units.size() + (size_t)std::max(1, (S.nl + lm_per_block - 1) / lm_per_block) + (size_t)(S.nl + lin_block - 1) / lin_block + (size_t)S.np;
-    }
-    cont_tasks += 8 * cont_max_units;
-    const size_t cont_bytes = sizeof(LbaWin) * (size_t)nw + sizeof(SchurTask) * std::max(cont_tasks, n_all_tasks) + 64;
-    const size_t o_cont = B.take(cont_bytes);
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        const Pass &S = passes[i];
-        WinLayout &l = L[i];
-        const size_t NP = p->n_poses, NL = p->n_points, E = p->n_edges;
-        const size_t n6 = 6 * (size_t)S.np, dim = n6 + 3 * (size_t)S.nl;
-        l.est = B.take(8 * (7 * NP + 3 * NL)); l.bk = B.take(8 * (7 * NP + 3 * NL));
-        l.robust = B.take(E); l.level1 = B.take(E);
-        l.err = B.take(24 * E);
-        l.lrec = B.take(32 * (S.pl_k.size() + 1)); l.lomr = B.take(24 * (S.pl_k.size() + 1)); l.Rl = B.take(72 * (size_t)S.np + 8);
-        l.Hpp = B.take(288 * (size_t)S.np + 8); l.Hll = B.take(72 * (size_t)S.nl + 8);
-        l.b = B.take(8 * dim + 8); l.x = B.take(8 * dim + 8);
-        l.npad = (int)((n6 + 15) & ~(size_t)15);
-        {
-            const size_t ldlt_bytes = ((size_t)l.npad * (l.npad + 1) + (size_t)l.npad * 17 + 4 * (size_t)l.npad + 2 * 16 * 17 + 16) * 8;
-            l.ldlt_lds = ldlt_bytes <= 159 * 1024 ? 1 : 0;
-            // the register-resident form (k_ldlt_reg) serves every window of up to 40 free keyframes
-            if (l.npad <= 16 * kLrMaxNb) l.ldlt_lds = 2;
-        }
-        // (beyond LDS the reduced system is factorised in place: k_schur writes it with leading dimension npad)
-        l.Hs = B.take(l.ldlt_lds == 1 ? 8 * n6 * n6 + 8 : 8 * (size_t)l.npad * l.npad + 8, 256); l.bs = B.take(8 * n6 + 8);
-        l.tmp = B.take(8 * n6 + 8);
-        l.n_part = std::max(1, (int)((S.nl + lm_per_block - 1) / lm_per_block));
-        l.scal = B.take(64); l.part = B.take(16 * (size_t)std::max(S.nl, 1) + 8);
-        l.ldlt = B.take(8);
-    }
-    const size_t o_res = B.take(0);
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        WinLayout &l = L[i];
-        const size_t NP = p->n_poses, NL = p->n_points, E = p->n_edges;
-        l.st = B.take(sizeof(LmState), 64);
-        l.out_Tcw = B.take(64 * NP, 64); l.out_xyz = B.take(12 * NL, 64); l.out_outlier = B.take(E, 64);
-        l.out_chi2 = want_chi2 ? B.take(8 * E, 64) : 0;
-    }
-    const size_t res_bytes = B.size - o_res;
-    if ((st = s->arena.alloc(B.size + 256))) return st;
-    if ((st = s->h_in.alloc(o_cont + cont_bytes + 256))) return st;
-    if ((st = s->h_stage.alloc(res_bytes + 256))) return st;
+
+    // ---- arena: layout, allocation, staging + upload (parallel), descriptors
+    ArenaPlan A;
+    plan_arena(problems, act, passes, lay, n_all_tasks, want_chi2, A);
+    if ((st = s->arena.alloc(A.bytes + 256))) return st;
+    if ((st = s->h_in.alloc(A.o_cont + A.cont_bytes + 256))) return st;
+    if ((st = s->h_stage.alloc(A.res_bytes + 256))) return st;
     if ((st = s->h_abort.alloc((size_t)nw + 1))) return st;
     uint8_t *base = s->arena.p, *hin = s->h_in.p;
     int32_t *d_abort = nullptr;
@@ -2644,361 +2935,60 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
         s->h_abort.p[i] = 0;
         any_flag |= problems[act[i]].stop_flag != nullptr;
     }
-    lap("layout + arena");
-
-    // ---- staging (parallel) + descriptors
-    LbaWin *hw = reinterpret_cast<LbaWin *>(hin + o_wins);
-    struct GroupDims {
-        bool any_lds = false, any_glob = false, any_reg = false;
-        int mx_E = 0, mx_pts = 0, mx_npad_glob = 0, mx_npad_lds = 0, mx_npad_reg = 0;
-    } gd[2];
-    std::vector<uint8_t> up_fail(nw, 0);
-    for_windows([&](int i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        const Pass &S = passes[i];
-        const WinLayout &l = L[i];
-        const size_t NP = p->n_poses, NL = p->n_points, E = p->n_edges;
-        memcpy(hin + l.in_Tcw, p->pose_Tcw, 64 * NP);
-        memcpy(hin + l.in_xyz, p->point_xyz, 12 * NL);
-        memcpy(hin + l.in_obs, p->edge_obs, 12 * E);
-        memcpy(hin + l.in_w, p->edge_inv_sigma2, 4 * E);
-        memcpy(hin + l.e_pose, p->edge_pose, 4 * E);
-        memcpy(hin + l.e_point, p->edge_point, 4 * E);
-        memcpy(hin + l.e_stereo, p->edge_stereo, E);
-        auto put = [&](size_t off, const std::vector<int32_t> &v) {
-            if (!v.empty()) memcpy(hin + off, v.data(), v.size() * 4);
-        };
-        put(l.pl_pos, S.pl_pos); put(l.hpose, S.hpose); put(l.hpoint, S.hpoint);
-        put(l.pt_off, S.pt_off); put(l.pt_k, S.pt_k); put(l.ps_off, S.ps_off); put(l.ps_k, S.ps_k);
-        put(l.pl_off, S.pl_off); put(l.pl_k, S.pl_ph);
-        put(l.it_ka, S.it_ka); put(l.it_kb, S.it_kb); put(l.it_l, S.it_l); put(l.blk_off, S.blk_off);
-        put(l.sr_o0, S.sr_o0); put(l.sr_info, S.sr_info); put(l.sr_ij, S.sr_ij);
-        // the window's staged region goes to the device as soon as it is assembled: its upload overlaps the staging of the
-        // other windows (one copy of everything after the staging cost 0.4 ms more per 32-window call)
-        const size_t r0 = l.in_Tcw, r1 = i + 1 < nw ? L[i + 1].in_Tcw : o_tasks;
-        if (hipSetDevice(s->device) != hipSuccess || hipMemcpyAsync(base + r0, hin + r0, r1 - r0, hipMemcpyHostToDevice, s->stream) != hipSuccess)
-            up_fail[i] = 1;
-    });
-    for (int i = 0; i < nw; ++i)
-        if (up_fail[i]) {
-            set_error("LocalBA: upload of window %d failed", act[i]);
-            return AOS2_ERR_HIP;
-        }
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        const Pass &S = passes[i];
-        const WinLayout &l = L[i];
-        LbaWin &W = hw[i];
-        memset(&W, 0, sizeof(W));
-        W.n_poses = p->n_poses; W.n_points = p->n_points; W.n_edges = p->n_edges;
-        W.np = S.np; W.nl = S.nl; W.n_items = (int)l.n_items;
-        W.iters1 = p->iters_first; W.iters2 = p->iters_second;
-        W.in_Tcw = (const float *)(base + l.in_Tcw); W.in_xyz = (const float *)(base + l.in_xyz);
-        W.in_obs = (const float *)(base + l.in_obs); W.in_w = (const float *)(base + l.in_w);
-        W.pose = (double *)(base + l.est); W.point = W.pose + 7 * (size_t)p->n_poses;
-        W.bk = (double *)(base + l.bk);
-        W.est_n = 7 * p->n_poses + 3 * p->n_points;
-        W.e_pose = (const int32_t *)(base + l.e_pose); W.e_point = (const int32_t *)(base + l.e_point);
-
-        W.e_stereo = base + l.e_stereo; W.e_robust = base + l.robust; W.e_level1 = base + l.level1;
-        W.err = (double *)(base + l.err);
-        W.cam.fx = (double)p->fx; W.cam.fy = (double)p->fy; W.cam.cx = (double)p->cx; W.cam.cy = (double)p->cy;
-        W.cam.bf = (double)p->bf; W.cam.bf_f = p->bf;
-        W.cam.delta_mono = (double)(float)std::sqrt(5.991);
-        W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
-        W.pl_pos = (const int32_t *)(base + l.pl_pos);
-        W.hpose = (const int32_t *)(base + l.hpose); W.hpoint = (const int32_t *)(base + l.hpoint);
-        W.pt_off = (const int32_t *)(base + l.pt_off); W.pt_k = (const int32_t *)(base + l.pt_k);
-        W.ps_off = (const int32_t *)(base + l.ps_off); W.ps_k = (const int32_t *)(base + l.ps_k);
-        W.pl_off = (const int32_t *)(base + l.pl_off); W.pl_ph = (const int32_t *)(base + l.pl_k);
-        W.it_ka = (const int32_t *)(base + l.it_ka); W.it_kb = (const int32_t *)(base + l.it_kb);
-        W.it_l = (const int32_t *)(base + l.it_l); W.blk_off = (const int32_t *)(base + l.blk_off);
-        W.sr_o0 = (const int32_t *)(base + l.sr_o0); W.sr_info = (const int32_t *)(base + l.sr_info); W.sr_ij = (const int32_t *)(base + l.sr_ij);
-        W.n_srows = (int)S.sr_o0.size();
-        W.lrec = (double *)(base + l.lrec); W.lomr = (double *)(base + l.lomr); W.Rl = (double *)(base + l.Rl); W.Hpp = (double *)(base + l.Hpp);
-        W.Hll = (double *)(base + l.Hll); W.b = (double *)(base + l.b); W.x = (double *)(base + l.x);
-        W.Hs = (double *)(base + l.Hs); W.bs = (double *)(base + l.bs);
-        W.tmp = (double *)(base + l.tmp); W.scal = (double *)(base + l.scal); W.part = (double *)(base + l.part);
-        W.n_part = l.n_part;
-        W.ldlt = (double *)(base + l.ldlt); W.npad = l.npad; W.ldlt_lds = l.ldlt_lds;
-        W.hs_ld = l.ldlt_lds == 1 ? 6 * S.np : l.npad;
-        W.st = (LmState *)(base + l.st);
-        W.abort_word = d_abort + i;
-        W.out_Tcw = (float *)(base + l.out_Tcw); W.out_xyz = (float *)(base + l.out_xyz);
-        W.out_outlier = base + l.out_outlier;
-        W.out_chi2 = want_chi2 ? (double *)(base + l.out_chi2) : nullptr;
-        GroupDims &D = gd[i >= goff[1] ? 1 : 0];
-        if (S.np > 0) {
-            if (l.ldlt_lds == 2) {
-                D.any_reg = true;
-                D.mx_npad_reg = std::max(D.mx_npad_reg, l.npad);
-            } else if (l.ldlt_lds) {
-                D.any_lds = true;
-                D.mx_npad_lds = std::max(D.mx_npad_lds, l.npad);
-            } else {
-                D.any_glob = true;
-                D.mx_npad_glob = std::max(D.mx_npad_glob, l.npad);
-            }
-        }
-        D.mx_E = std::max(D.mx_E, p->n_edges);
-        D.mx_pts = std::max(D.mx_pts, std::max(p->n_points, p->n_poses));
-    }
-    lap("staging");
-    hipStream_t q = s->stream;
-    // the task lists of the groups, one after the other: [schur | points | lin] per group
-    const SchurTask *d_schur_tasks[2], *d_pts_tasks[2], *d_lin_tasks[2];
-    {
-        size_t o = o_tasks;
-        for (int g = 0; g < G; ++g)
-            for (int k = 0; k < 3; ++k) {
-                const std::vector<SchurTask> &v = k == 0 ? *tasks_g[g] : k == 1 ? *pts_tasks_g[g] : *lin_tasks_g[g];
-                (k == 0 ? d_schur_tasks : k == 1 ? d_pts_tasks : d_lin_tasks)[g] = (const SchurTask *)(base + o);
-                if (!v.empty()) memcpy(hin + o, v.data(), sizeof(SchurTask) * v.size());
-                o += sizeof(SchurTask) * v.size();
-            }
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(base + o_tasks, hin + o_tasks, staged_bytes - o_tasks, hipMemcpyHostToDevice, q));   // the task lists, the descriptors
-    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
-    const LbaWin *dw = (const LbaWin *)(base + o_wins);
-    auto blocks = [](size_t n, int t) { return (unsigned)((n + t - 1) / t); };
-    hipStream_t gq[2] = {s->stream, s->stream_b}, gq2[2] = {s->stream2, s->stream2_b};
-    hipEvent_t gfork[2] = {s->ev_fork, s->ev_fork_b}, gjoin[2] = {s->ev_join, s->ev_join_b};
-    if (G == 2) {   // the second group's stream starts behind the upload
-        AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(gq[1], s->ev_up, 0));
-    }
-    // What a launch sequence runs on: the descriptor array its task lists index (`wins`), the first descriptor and the number of
-    // windows of the kernels that take one workgroup row per window (`blk`, nw), the lists, the largest dimensions, the streams
-    struct Prog {
-        const LbaWin *wins, *blk;
-        int nw;
-        const SchurTask *schur, *pts, *lin;
-        size_t n_schur, n_pts, n_lin;
-        GroupDims D;
-        hipStream_t q, q2;
-        hipEvent_t fork, join;
-    };
-    auto enqueue_points = [&](const Prog &P, int solve) {
-        if (walk)
-            hipLaunchKernelGGL(k_points_walk, dim3((unsigned)P.n_pts), dim3(128), 0, P.q, P.wins, P.pts, solve);
-        else
-            hipLaunchKernelGGL(k_points, dim3((unsigned)P.n_pts), dim3(256), 0, P.q, P.wins, P.pts, solve);
-    };
-    auto enqueue_lin = [&](const Prog &P, int init) {
-        if (!P.n_lin) return;
-        if (walk)
-            hipLaunchKernelGGL(k_lin<true>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
-        else
-            hipLaunchKernelGGL(k_lin<false>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
-    };
-    auto enqueue_init = [&](const Prog &P) {
-        enqueue_points(P, 0);
-        enqueue_lin(P, 1);
-        hipLaunchKernelGGL(k_lm_init, dim3(P.nw), dim3(1024), 0, P.q, P.blk);
-    };
-    // one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of two kinds)
-    bool stagger_pending = G == 2;
-    auto enqueue_trial = [&](const Prog &P, bool first_group) {
-        const GroupDims &D = P.D;
-        if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
-        if (first_group && stagger_pending) {   // the other group starts here: half a trial behind
-            (void)hipEventRecord(s->ev_stag, gq[0]);
-            (void)hipStreamWaitEvent(gq[1], s->ev_stag, 0);
-            stagger_pending = false;
-        }
-        // the forms of the reduced-system kernel work on different windows: side by side (one of them on a stream of its own)
-        const bool both = D.any_glob && (D.any_lds || D.any_reg);
-        if (both) {
-            (void)hipEventRecord(P.fork, P.q);
-            (void)hipStreamWaitEvent(P.q2, P.fork, 0);
-        }
-        if (D.any_lds) {
-            const size_t need = ((size_t)D.mx_npad_lds * (D.mx_npad_lds + 1) + (size_t)D.mx_npad_lds * 17 + 4 * (size_t)D.mx_npad_lds + 2 * 16 * 17 + 16) * sizeof(double);
-            hipLaunchKernelGGL(k_ldlt_lds, dim3(P.nw), dim3(512), need, both ? P.q2 : P.q, P.blk);
-        }
-        if (D.any_reg)
-            hipLaunchKernelGGL(k_ldlt_reg, dim3(P.nw), dim3(kLrThreads), ldlt_reg_lds_doubles(D.mx_npad_reg) * sizeof(double), both ? P.q2 : P.q, P.blk);
-        if (D.any_glob)
-            hipLaunchKernelGGL(k_ldlt_dev, dim3(P.nw), dim3(512), ((size_t)D.mx_npad_glob * 17 + 4 * (size_t)D.mx_npad_glob + 3 * 16 * 17 + 16) * sizeof(double), P.q,
-                               P.blk);
-        if (both) {
-            (void)hipEventRecord(P.join, P.q2);
-            (void)hipStreamWaitEvent(P.q, P.join, 0);
-        }
-        enqueue_points(P, 1);   // + the LM decision in its last workgroup
-        enqueue_lin(P, 0);
-    };
-    auto enqueue_transition = [&](const Prog &P) {
-        hipLaunchKernelGGL(k_transition, dim3(blocks(P.D.mx_E, 256), P.nw), dim3(256), 0, P.q, P.blk);
-    };
-    Prog PG[2];
-    for (int g = 0; g < G; ++g)
-        PG[g] = Prog{dw, dw + goff[g], goff[g + 1] - goff[g], d_schur_tasks[g], d_pts_tasks[g], d_lin_tasks[g], tasks_g[g]->size(), pts_tasks_g[g]->size(),
-                     lin_tasks_g[g]->size(), gd[g], gq[g], gq2[g], gfork[g], gjoin[g]};
-    // results (and states) come back as one copy; the host forwards pbStopFlag into the mapped abort words meanwhile
-    auto finish = [&](const Prog *progs, int n_progs) -> int {
-        for (int g = 0; g < n_progs; ++g) {
-            const Prog &P = progs[g];
-            hipLaunchKernelGGL(k_final, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk);
-        }
-        if (n_progs == 2) {
-            AOS2_HIP_CHECK(hipEventRecord(s->ev_done_b, gq[1]));
-            AOS2_HIP_CHECK(hipStreamWaitEvent(q, s->ev_done_b, 0));
-        }
-        AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
-        AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, base + o_res, res_bytes, hipMemcpyDeviceToHost, q));
-        if (any_flag) {
-            AOS2_HIP_CHECK(hipEventRecord(s->ev[2], q));
-            while (hipEventQuery(s->ev[2]) == hipErrorNotReady)
-                for (int i = 0; i < nw; ++i)
-                    if (stop_requested(problems + act[i])) __atomic_store_n(&s->h_abort.p[i], 1, __ATOMIC_RELAXED);
-        }
-        AOS2_HIP_CHECK(hipStreamSynchronize(q));
-        AOS2_HIP_CHECK(hipGetLastError());
-        return AOS2_OK;
-    };
+    if ((st = stage_and_upload(s, pool, problems, act, passes, A))) return st;
+    LbaWin *hw = reinterpret_cast<LbaWin *>(hin + A.o_wins);
+    GroupDims gd[2];
     int max_i1 = 0, max_i2 = 0;
     for (int i = 0; i < nw; ++i) {
-        max_i1 = std::max(max_i1, problems[act[i]].iters_first);
-        max_i2 = std::max(max_i2, problems[act[i]].iters_second);
+        const aos2_lba_problem_t &p = problems[act[i]];
+        describe_window(hw[i], base, p, passes[i], A.L[i], d_abort + i, want_chi2);
+        gd[i >= goff[1] ? 1 : 0].add(p, passes[i], A.L[i]);
+        max_i1 = std::max(max_i1, p.iters_first);
+        max_i2 = std::max(max_i2, p.iters_second);
     }
+    hipStream_t q = s->stream;
+    // the task lists of the groups, one after the other: [schur | points | lin] per group
+    DevTasks dt[2];
+    {
+        size_t o = A.o_tasks;
+        for (int g = 0; g < G; ++g) dt[g] = put_tasks(TL[g], hin, base, o);
+    }
+    AOS2_HIP_CHECK(hipMemcpyAsync(base + A.o_tasks, hin + A.o_tasks, A.staged_bytes - A.o_tasks, hipMemcpyHostToDevice, q));   // the task lists, the descriptors
+    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
+    if (G == 2) {   // the second group's stream starts behind the upload
+        AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
+        AOS2_HIP_CHECK(hipStreamWaitEvent(s->stream_b, s->ev_up, 0));
+    }
+
+    // ---- the program
     rg = std::make_unique<RoctxRange>("LocalBA::optimize(5) + outlier pass + optimize(10) + inlier check (one device program)");
-    // The program: as many trials as iterations per optimisation -- what every window needs whose steps are all accepted.  A window
+    // As many trials as iterations per optimisation -- what every window needs whose steps are all accepted.  A window
     // with rejected steps is not finished when the program ends: it leaves with the others' results and gets a continuation round
-    // sized for what it still needs, together with the (few) windows like it, compacted (below).  Rounds 2-4 enqueued one spare
+    // sized for what it still needs, together with the (few) windows like it, compacted (continuation_round).  Rounds 2-4 enqueued one spare
     // trial per optimisation for EVERY window instead (AOS2_LBA_SPARE_SLOTS=1): 13 % of the launches of a batch whose windows need none.
     const int spare = getenv("AOS2_LBA_SPARE_SLOTS") ? atoi(getenv("AOS2_LBA_SPARE_SLOTS")) : 0;
-    const int slots1 = max_i1 > 0 ? max_i1 + spare : 0, slots2 = max_i2 > 0 ? max_i2 + spare : 0;
-    s->last_trial_slots = slots1 + slots2;
-    s->last_window_slots = (long long)(slots1 + slots2) * nw;
+    const int iters[2] = {max_i1, max_i2}, slots[2] = {max_i1 > 0 ? max_i1 + spare : 0, max_i2 > 0 ? max_i2 + spare : 0};
+    s->last_trial_slots = slots[0] + slots[1];
+    s->last_window_slots = (long long)(slots[0] + slots[1]) * nw;
     s->last_host_rounds = 1;
+    const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
+    LaunchCtx C{s, walk, G == 2};
+    Prog PG[2];
     for (int g = 0; g < G; ++g) {
-        const Prog &P = PG[g];
-        hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, s->debug_stop_at_poll);
-        if (max_i1 > 0) {
-            enqueue_init(P);
-            for (int t = 0; t < slots1; ++t) enqueue_trial(P, g == 0);
-        }
-        enqueue_transition(P);
-        if (max_i2 > 0) {
-            enqueue_init(P);
-            for (int t = 0; t < slots2; ++t) enqueue_trial(P, g == 0);
-        }
+        PG[g] = make_prog(dw, dw + goff[g], goff[g + 1] - goff[g], TL[g], dt[g], gd[g], group_streams(s, g));
+        enqueue_program(C, PG[g], g == 0, iters, slots);
     }
-    if ((st = finish(PG, G))) return st;
-    lap("program");
-    auto state_of = [&](int i) { return reinterpret_cast<const LmState *>(s->h_stage.p + (L[i].st - o_res)); };
+    const Batch Bt{problems, act, passes, A, lay, hw, any_flag};
+    if ((st = finish(s, PG, G, Bt))) return st;
+
+    // ---- continuation rounds, write-back
     for (int round = 0;; ++round) {
-        // the windows that are not finished, what they still need at most if no further step is rejected
-        std::vector<int> todo;
-        int need1 = 0, need2 = 0;
-        bool before_second = false;
-        for (int i = 0; i < nw; ++i) {
-            const LmState *ls = state_of(i);
-            if (ls->phase == 3) continue;
-            todo.push_back(i);
-            if (ls->phase == 0) need1 = std::max(need1, std::max(1, ls->iters_max[0] - ls->it));
-            if (ls->phase <= 1) before_second = true;
-            if (ls->phase == 2) need2 = std::max(need2, std::max(1, ls->iters_max[1] - ls->it));
-        }
-        if (todo.empty()) break;
-        if (round > 64) {   // 2 x 10 iterations x 10 trials at most: cannot happen
-            set_error("internal: LocalBA program did not finish");
-            return AOS2_ERR_ARG;
-        }
-        if (before_second) need2 = std::max(need2, max_i2);
-        // their descriptors, compacted, and task lists that address them by position
-        TaskLists TC;
-        build_tasks(todo, [](int k) { return k; }, TC);
-        size_t tc_bytes = sizeof(SchurTask) * (TC.schur.size() + TC.pts.size() + TC.lin.size());
-        static const bool force_one_queue = getenv("AOS2_LBA_CONT_ONE_QUEUE") != nullptr;   // (test hook: the fallback below on every continuation)
-        if (force_one_queue || sizeof(LbaWin) * todo.size() + tc_bytes > cont_bytes) {   // (the dealing is not monotone on subsets: should one pad past the bound,
-            build_tasks(todo, [](int k) { return k; }, TC, true);      //  one unpadded queue always fits -- its length is the subset's sum)
-            tc_bytes = sizeof(SchurTask) * (TC.schur.size() + TC.pts.size() + TC.lin.size());
-        }
-        if (sizeof(LbaWin) * todo.size() + tc_bytes > cont_bytes) {
-            set_error("internal: continuation region");
-            return AOS2_ERR_ARG;
-        }
-        uint8_t *hc = hin + o_cont;
-        Prog PC;
-        PC.D = GroupDims();
-        for (size_t k = 0; k < todo.size(); ++k) {
-            const int i = todo[k];
-            reinterpret_cast<LbaWin *>(hc)[k] = hw[i];
-            const WinLayout &l = L[i];
-            const Pass &S = passes[i];
-            if (S.np > 0) {
-                if (l.ldlt_lds == 2) {
-                    PC.D.any_reg = true;
-                    PC.D.mx_npad_reg = std::max(PC.D.mx_npad_reg, l.npad);
-                } else if (l.ldlt_lds) {
-                    PC.D.any_lds = true;
-                    PC.D.mx_npad_lds = std::max(PC.D.mx_npad_lds, l.npad);
-                } else {
-                    PC.D.any_glob = true;
-                    PC.D.mx_npad_glob = std::max(PC.D.mx_npad_glob, l.npad);
-                }
-            }
-            PC.D.mx_E = std::max(PC.D.mx_E, problems[act[i]].n_edges);
-            PC.D.mx_pts = std::max(PC.D.mx_pts, std::max(problems[act[i]].n_points, problems[act[i]].n_poses));
-        }
-        size_t o = sizeof(LbaWin) * todo.size();
-        const SchurTask *dt[3];
-        const std::vector<SchurTask> *tv[3] = {&TC.schur, &TC.pts, &TC.lin};
-        for (int k = 0; k < 3; ++k) {
-            dt[k] = (const SchurTask *)(base + o_cont + o);
-            if (!tv[k]->empty()) memcpy(hc + o, tv[k]->data(), sizeof(SchurTask) * tv[k]->size());
-            o += sizeof(SchurTask) * tv[k]->size();
-        }
-        AOS2_HIP_CHECK(hipMemcpyAsync(base + o_cont, hc, o, hipMemcpyHostToDevice, q));
-        PC.wins = PC.blk = (const LbaWin *)(base + o_cont);
-        PC.nw = (int)todo.size();
-        PC.schur = dt[0]; PC.pts = dt[1]; PC.lin = dt[2];
-        PC.n_schur = TC.schur.size(); PC.n_pts = TC.pts.size(); PC.n_lin = TC.lin.size();
-        PC.q = gq[0]; PC.q2 = gq2[0]; PC.fork = gfork[0]; PC.join = gjoin[0];
-        for (int t = 0; t < need1; ++t) enqueue_trial(PC, false);
-        if (before_second) {
-            enqueue_transition(PC);
-            enqueue_init(PC);
-        }
-        for (int t = 0; t < need2; ++t) enqueue_trial(PC, false);
-        s->last_trial_slots += need1 + need2;
-        s->last_window_slots += (long long)(need1 + need2) * (long long)todo.size();
-        s->last_host_rounds++;
-        if ((st = finish(&PC, 1))) return st;
+        bool done;
+        if ((st = continuation_round(C, Bt, max_i2, round, &done))) return st;
+        if (done) break;
     }
-    lap("continuation");
     rg = std::make_unique<RoctxRange>("LocalBA::write-back");
-    if (getenv("AOS2_LBA_TRACE"))
-        for (int i = 0; i < nw; ++i) {
-            const LmState *ls = state_of(i);
-            for (int t = 0; t < ls->ntr; ++t)
-                fprintf(stderr, "[lba] win %d trial %2d lambda %.6e chi %.9e -> %.9e rho %.6e\n", i, t, ls->tr_lambda[t], ls->tr_cur[t], ls->tr_temp[t], ls->tr_rho[t]);
-        }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = problems + act[i];
-        aos2_lba_result_t *r = results + act[i];
-        const WinLayout &l = L[i];
-        const uint8_t *hb = s->h_stage.p;
-        const LmState *ls = state_of(i);
-        memcpy(r->pose_Tcw, hb + (l.out_Tcw - o_res), 64 * (size_t)p->n_poses);
-        memcpy(r->point_xyz, hb + (l.out_xyz - o_res), 12 * (size_t)p->n_points);
-        if (r->edge_outlier) memcpy(r->edge_outlier, hb + (l.out_outlier - o_res), (size_t)p->n_edges);
-        if (r->edge_chi2) memcpy(r->edge_chi2, hb + (l.out_chi2 - o_res), 8 * (size_t)p->n_edges);
-        r->iters_done_first = ls->iters_done[0];
-        r->iters_done_second = ls->iters_done[1];
-        r->trials_first = ls->trials[0];
-        r->trials_second = ls->trials[1];
-        r->final_chi2 = ls->final_chi2;
-        r->final_lambda = ls->final_lambda;
-        r->polls = ls->polls;
-        r->stop_poll = ls->stop_poll;
-        r->ms_device = ms;
-    }
-    lap("write-back");
+    write_back(s, Bt, results);
     return AOS2_OK;
 }
 

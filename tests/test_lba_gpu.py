@@ -236,8 +236,8 @@ def _same(a, b):
 
 
 def test_lba_batch_equals_single_windows(pkg, oracle, gpu):
-    """aos2_lba_solve_batch: windows of different sizes (reduced systems in LDS and in device memory, a window without
-    free keyframes' worth of points, different iteration needs) solved in one call give bit for bit what each gives
+    """aos2_lba_solve_batch: windows of different sizes (reduced systems of 2 to 25 free keyframes, all in the register form
+    k_ldlt_reg; a window without free keyframes' worth of points; different iteration needs) solved in one call give bit for bit what each gives
     alone, and match the oracle."""
     cfgs = [dict(seed=21, n_local=4, n_fixed=3, n_points=150), dict(seed=22, n_local=25, n_fixed=5, n_points=700),
             dict(seed=23, n_local=9, n_fixed=0, n_points=400, include_kf0=True, stereo_frac=0.3),
@@ -362,7 +362,7 @@ def test_lba_landmark_kernel_layouts_agree(pkg, oracle, gpu, monkeypatch):
 
 def test_lba_many_free_keyframes(pkg, oracle, gpu):
     """More than 42 free keyframes (reduced camera system > 256 rows): EuRoC / KITTI windows reach this size; the
-    factorisation then runs out of device memory instead of LDS."""
+    factorisation then runs in place in device memory (k_ldlt_dev) instead of in registers."""
     for cfg in (dict(seed=31, n_local=48, n_fixed=6, n_points=900), dict(seed=32, n_local=70, n_fixed=10, n_points=1200, stereo_frac=0.5)):
         prob = pkg.synth.synth_lba_problem(**cfg)
         assert int((prob["pose_fixed"] == 0).sum()) > 42
@@ -371,6 +371,24 @@ def test_lba_many_free_keyframes(pkg, oracle, gpu):
         assert got["status"] == 0 and got["iters"] == want["iters"]
         assert close(got["pose_Tcw"], want["pose_Tcw"]) and close(got["point_xyz"], want["point_xyz"])
         assert (got["edge_outlier"] == want["edge_outlier"]).all()
+
+
+def test_lba_batch_with_both_reduced_system_forms(pkg, oracle, gpu):
+    """A batch with windows on both sides of 40 free keyframes: k_ldlt_reg and k_ldlt_dev run side by side on two streams in every
+    trial.  Every window equals the oracle and gives the bits it gives alone."""
+    cfgs = [dict(seed=33, n_local=48, n_fixed=6, n_points=900), dict(seed=34, n_local=12, n_fixed=4, n_points=500),
+            dict(seed=35, n_local=30, n_fixed=8, n_points=800, stereo_frac=0.5)]
+    probs = [pkg.synth.synth_lba_problem(**c) for c in cfgs]
+    nfree = [int((p["pose_fixed"] == 0).sum()) for p in probs]
+    assert min(nfree) <= 40 < max(nfree)
+    batch = pkg.LocalBA().LocalBundleAdjustmentBatch(probs)
+    for p, got in zip(probs, batch):
+        want = oracle.lba_solve(p)
+        alone = pkg.LocalBA().LocalBundleAdjustment(p)
+        assert got["status"] == 0 and got["iters"] == want["iters"]
+        assert close(got["pose_Tcw"], want["pose_Tcw"]) and close(got["point_xyz"], want["point_xyz"])
+        assert (got["edge_outlier"] == want["edge_outlier"]).all()
+        assert _same(got, alone)
 
 
 def _check_abort(got, want):
@@ -505,17 +523,18 @@ def test_lba_bench_windows_vs_oracle(pkg, oracle, gpu, monkeypatch, layout):
 
 
 def test_lba_mixed_window_batch_vs_oracle(pkg, oracle, gpu):
-    """A batch of DIFFERENT windows (synth.lba_window_mix: reduced systems inside and beyond LDS, sparse and dense covisibility) and
+    """A batch of DIFFERENT windows (synth.lba_window_mix: reduced systems of 10 to 40 free keyframes, sparse and dense covisibility) and
     two hand-made extremes -- three keyframes sharing every point (off-diagonal blocks of > 256 items: k_schur's BIG units) and a
     window whose second keyframe pair shares nothing (an empty block still gets its zeros): every window equals the oracle, and
-    the batch gives the bits of the windows solved alone (task lists, PACK units, the two reduced-system kernels side by side)."""
+    the batch gives the bits of the windows solved alone (task lists, PACK units).  The two reduced-system kernels side by side:
+    test_lba_batch_with_both_reduced_system_forms."""
     mix = pkg.synth.lba_window_mix(3, 6)
     for m in mix:
         m["n_points"] = 1500 + m["n_points"] // 6
     probs = [pkg.synth.synth_lba_problem(**m) for m in mix]
     probs.append(pkg.synth.synth_lba_problem(seed=61, n_local=3, n_fixed=1, n_points=1400, obs_per_point=4))
     nfree = [int((p["pose_fixed"] == 0).sum()) for p in probs]
-    assert min(nfree) <= 21 < max(nfree)   # both forms of the reduced-system kernel
+    assert min(nfree) <= 21 < max(nfree)   # small and large reduced systems
     big = probs[-1]
     free = np.flatnonzero(big["pose_fixed"] == 0)
     both = np.intersect1d(big["edge_point"][big["edge_pose"] == free[0]], big["edge_point"][big["edge_pose"] == free[1]])

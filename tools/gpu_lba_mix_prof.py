@@ -1,6 +1,6 @@
 """One LocalBA batch of N windows, solved 3 times (run under rocprofv3 --kernel-trace --stats: profiles/README.md).
 LBA_MIX = het   : synth.lba_window_mix (bench.py's default step: 10-40 local keyframes, 2-6 k points)
-          het26 : the same mix with the local keyframes capped at 26 (every reduced system fits LDS)
+          het26 : the same mix with the local keyframes capped at 26 (reduced systems of at most 160 rows)
           hom   : round 3's batch (SURVEY 8(d)-size windows, 4 distinct, tiled)"""
 import os
 import sys

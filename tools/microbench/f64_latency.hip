@@ -1,4 +1,4 @@
-// Single-wave latencies that bound the serial pivot chain of the reduced-system LDL^T (csrc/lba.hip: k_ldlt_lds):
+// Single-wave latencies that bound the serial pivot chain of the reduced-system LDL^T (csrc/lba.hip: k_ldlt_dev; csrc/ldlt_reg.h):
 // dependent v_fma_f64, IEEE f64 division, v_rcp_f64 + 2 Newton steps, v_readlane -> VALU use, LDS write -> broadcast read.
 // hipcc --offload-arch=gfx950 -O3 f64_latency.hip -o f64_latency && ./f64_latency
 #include <hip/hip_runtime.h>
