@@ -400,14 +400,9 @@ static int frames_init(aos2_frames *f)
     // member arrays
     const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap, n = B * cap;
     size_t sz = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = (sz + 255) & ~(size_t)255;
-        sz = o + bytes;
-        return o;
-    };
-    const size_t o_x = take(4 * n), o_y = take(4 * n), o_a = take(4 * n), o_oct = take(4 * n), o_ur = take(4 * n), o_dp = take(4 * n);
-    const size_t o_go = take(4 * B * (kFrGridCells + 1)), o_gi = take(4 * n), o_mp = take(4 * n), o_seen = take(4 * n);
-    const size_t o_st = take(n), o_out = take(n), o_T = take(64 * B);
+    const size_t o_x = carve(sz, 4 * n), o_y = carve(sz, 4 * n), o_a = carve(sz, 4 * n), o_oct = carve(sz, 4 * n), o_ur = carve(sz, 4 * n), o_dp = carve(sz, 4 * n);
+    const size_t o_go = carve(sz, 4 * B * (kFrGridCells + 1)), o_gi = carve(sz, 4 * n), o_mp = carve(sz, 4 * n), o_seen = carve(sz, 4 * n);
+    const size_t o_st = carve(sz, n), o_out = carve(sz, n), o_T = carve(sz, 64 * B);
     if ((st = f->mem.alloc(sz + 256))) return st;
     AOS2_HIP_CHECK(hipMemsetAsync(f->mem.p, 0, sz, f->stream));
     uint8_t *m = f->mem.p;
@@ -443,16 +438,11 @@ static int frames_scratch(aos2_frames *f, int nq_cap, int n_local, FrScratch &X)
 {
     const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap;
     size_t sz = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = (sz + 255) & ~(size_t)255;
-        sz = o + bytes;
-        return o;
-    };
     const size_t nq = B * (size_t)nq_cap, nl = B * (size_t)n_local;
-    const size_t o_sl = take(sizeof(QuerySlot) * nq), o_ch = take(4 * nq), o_m = take(4 * B * cap), o_bin = take(4 * B * cap);
-    const size_t o_nm = take(4 * B), o_rec = take(sizeof(QueryRec) * nq);
-    const size_t o_iv = take(nl), o_ho = take(nl), o_px = take(4 * nl), o_py = take(4 * nl), o_pr = take(4 * nl), o_vc = take(4 * nl);
-    const size_t o_pl = take(4 * nl), o_di = take(4 * nl);
+    const size_t o_sl = carve(sz, sizeof(QuerySlot) * nq), o_ch = carve(sz, 4 * nq), o_m = carve(sz, 4 * B * cap), o_bin = carve(sz, 4 * B * cap);
+    const size_t o_nm = carve(sz, 4 * B), o_rec = carve(sz, sizeof(QueryRec) * nq);
+    const size_t o_iv = carve(sz, nl), o_ho = carve(sz, nl), o_px = carve(sz, 4 * nl), o_py = carve(sz, 4 * nl), o_pr = carve(sz, 4 * nl), o_vc = carve(sz, 4 * nl);
+    const size_t o_pl = carve(sz, 4 * nl), o_di = carve(sz, 4 * nl);
     int st;
     if ((st = f->scratch.alloc(sz + 256))) return st;
     uint8_t *m = f->scratch.p;

@@ -2115,6 +2115,9 @@ using namespace aos2;
 // LDS budget of the fixed-point resolve kernels (two int32 copies of B[n_f]): default dynamic-LDS limit
 constexpr size_t kFixLdsBytes = 44 * 1024;   // + the 16 KB overflow arena of resolve_fixpoint_impl: within the 64 KB of a workgroup
 
+struct ArenaBind { void *field; size_t tok; };                         // a pointer field and the region offset it will point at
+struct ArenaFetch { void *dst; const uint8_t *src; size_t bytes; };    // a result on its way to the caller's array
+
 struct aos2_matcher {
     float nnratio;
     int check_ori;
@@ -2125,6 +2128,8 @@ struct aos2_matcher {
     DevBuf<uint8_t> arena;     // one call's inputs | scratch | results (struct Arena)
     PinnedBuf<uint8_t> h_in;   // page-locked: the inputs on their way up
     PinnedBuf<uint8_t> h_out;  // page-locked: the results on their way back
+    std::vector<ArenaBind> binds;      // Arena: the pointer fields the call in progress has registered, and its pending
+    std::vector<ArenaFetch> fetches;   // results (kept by the handle like h_in / h_out: no allocation after the first calls)
     DevBuf<uint32_t> part;     // hamming partials
     DevBuf<uint64_t> pool;     // candidate entries of the projection searches (8 B each)
     DevBuf<float> fr_angle;    // aos2_matcher_search_by_bow_frames: dense key angles of the two frame batches
@@ -2150,81 +2155,129 @@ static int matcher_init(aos2_matcher *m)
     return AOS2_OK;
 }
 
-// bump allocator over one device arena: uploads host arrays, returns device pointers
+// stage B of a search over a frame of n_f features: the parallel fixed-point kernel while its two LDS copies of B[n_f] fit,
+// else (or with AOS2_SERIAL_RESOLVE=1) the one-wave sequential loop
+static bool use_fix_resolve(const aos2_matcher *m, int n_f) { return (size_t)n_f * 8 <= kFixLdsBytes && !m->serial_resolve; }
+
+// room for `entries` candidate entries in the handle's pool -> pool.  Entry offsets are 32-bit: 2^31 entries = 16 GiB of the
+// device's 288 GB; beyond that AOS2_ERR_CAPACITY, below it only the allocation itself can fail.
+static int pool_reserve(aos2_matcher *m, size_t entries, const char *what, Entry *&pool)
+{
+    if (entries > ((size_t)1 << 31) - 2) {
+        set_error("%s: %zu candidate entries exceed the pool's index range", what, entries);
+        return AOS2_ERR_CAPACITY;
+    }
+    if (int st = m->pool.alloc(entries + 1)) return st;
+    pool = reinterpret_cast<Entry *>(m->pool.p);
+    return AOS2_OK;
+}
+
+// bump allocation in a buffer of 256-byte aligned pieces: the offset of the next `bytes`, `size` grows past them
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t carve(size_t &size, size_t bytes)
+{
+    const size_t off = up256(size);
+    size = off + bytes;
+    return off;
+}
+
 // One call's memory: three regions of the handle's device arena.
-//   inputs  (push / push_hole): assembled in the handle's page-locked host buffer and uploaded with ONE asynchronous
+//   inputs  (in / hole): assembled in the handle's page-locked host buffer and uploaded with ONE asynchronous
 //           copy; the buffer persists between calls, so after the first calls nothing is allocated;
-//   scratch (reserve): device only, zeroed by a device memset (never travels);
-//   results (reserve_out): device only, zeroed; fetch() + finish() bring ALL results back with one copy into a
+//   scratch (scratch): device only, zeroed by a device memset (never travels);
+//   results (out): device only, zeroed; fetch() + finish() bring ALL results back with one copy into a
 //           page-locked bounce buffer and scatter them to the caller's arrays.
 // (Earlier the whole arena, scratch included, was staged in a pageable vector and uploaded, and every result array
 // was a pageable copy of its own: 6.9 ms of host time around 0.06 ms of kernels for 64 SearchByBoW pairs.)
-// Offsets carry their region in the top bits; dev<T>() resolves them once every region's size is known, so all
-// push / reserve calls of a function come before its first dev<T>() / upload().
+// Where a region starts is known only once every array of the call is staged, and the device arena may move when it
+// grows.  So the call that stages an array also names the device-pointer field (of a *Dev struct, or a local) that is
+// to point at it, and alloc() -- directly or through upload() -- fills all those fields.  The fields are registered by
+// address: they must stay where they are until then (size a vector of per-item structs before its loop), and they
+// hold nothing before.  Staging after alloc() aborts (late()).
 struct Arena {
     aos2_matcher *m;
-    static constexpr size_t kScr = (size_t)1 << 62, kOut = (size_t)1 << 61, kMask = kOut - 1;
+    static constexpr size_t kScr = (size_t)1 << 62, kOut = (size_t)1 << 61, kMask = kOut - 1;   // region of an offset: its top bits
     size_t in_size = 0, scr_size = 0, out_size = 0;
-    mutable bool frozen = false;
+    bool frozen = false;
     int err = AOS2_OK;
-    struct Fetch { void *dst; const uint8_t *src; size_t bytes; };
-    std::vector<Fetch> fetches;
-    static size_t up(size_t x) { return (x + 255) & ~(size_t)255; }
-    void late(const char *what) const
+    explicit Arena(aos2_matcher *m_) : m(m_)
+    {
+        m->binds.clear();
+        m->fetches.clear();
+    }
+    void late() const
     {
         if (!frozen) return;
-        fprintf(stderr, "aos2 matcher arena: %s after the layout was fixed\n", what);
+        fprintf(stderr, "aos2 matcher arena: an array staged after the layout was fixed\n");
         abort();
     }
     size_t push(const void *src, size_t bytes)
     {
-        late("push");
-        const size_t off = up(in_size);
-        if (off + bytes > m->h_in.n) {   // grow the page-locked buffer (kept by the handle), contents preserved
+        late();
+        const size_t old = in_size, off = carve(in_size, bytes);
+        if (in_size > m->h_in.n) {   // grow the page-locked buffer (kept by the handle), contents preserved
             PinnedBuf<uint8_t> nb;
-            const int st = nb.alloc(std::max((off + bytes) * 2, (size_t)1 << 20));
+            const int st = nb.alloc(std::max(in_size * 2, (size_t)1 << 20));
             if (st) {
                 err = st;
+                in_size = old;
                 return 0;
             }
-            if (in_size) memcpy(nb.p, m->h_in.p, in_size);
+            if (old) memcpy(nb.p, m->h_in.p, old);
             m->h_in.release();
             m->h_in = nb;
-            nb.p = nullptr;
-            nb.n = 0;
         }
-        if (off > in_size) memset(m->h_in.p + in_size, 0, off - in_size);
+        if (off > old) memset(m->h_in.p + old, 0, off - old);
         if (bytes) {
             if (src) memcpy(m->h_in.p + off, src, bytes);
             else memset(m->h_in.p + off, 0, bytes);
         }
-        in_size = off + bytes;
         return off;
     }
-    size_t push_hole(size_t bytes) { return push(nullptr, bytes); }   // input the host fills through hostptr()
-    uint8_t *hostptr(size_t off) const { return m->h_in.p + off; }
-    size_t reserve(size_t bytes)
+    // `field` will point at `tok`, the region offset that in() / hole() / scratch() / out() returned for an array
+    // (plus a few bytes: a second field into that array)
+    template <class F>
+    size_t bind(F *&field, size_t tok)
     {
-        late("reserve");
-        const size_t off = up(scr_size);
-        scr_size = off + bytes;
-        return kScr | off;
+        late();
+        m->binds.push_back(ArenaBind{&field, tok});
+        return tok;
     }
-    size_t reserve_out(size_t bytes)
+    // input: `bytes` of the host array `src`, of the field's element type
+    template <class F, class T>
+    size_t in(F *&field, const T *src, size_t bytes)
     {
-        late("reserve_out");
-        const size_t off = up(out_size);
-        out_size = off + bytes;
-        return kOut | off;
+        static_assert(std::is_same<std::remove_const_t<F>, T>::value, "the field and the host array differ in type");
+        return bind(field, push(src, bytes));
     }
-    size_t scr_base() const { return up(in_size); }
-    size_t out_base() const { return scr_base() + up(scr_size); }
-    size_t total() const { return out_base() + up(out_size); }
+    // input the host writes later, through fill_hole(): zero until then
+    template <class F>
+    size_t hole(F *&field, size_t bytes) { return bind(field, push(nullptr, bytes)); }
+    template <class F>
+    size_t scratch(F *&field, size_t bytes) { return bind(field, kScr | carve(scr_size, bytes)); }
+    template <class F>
+    size_t out(F *&field, size_t bytes) { return bind(field, kOut | carve(out_size, bytes)); }
+    size_t scr_base() const { return up256(in_size); }
+    size_t out_base() const { return scr_base() + up256(scr_size); }
+    size_t total() const { return out_base() + up256(out_size); }
+    // fixes the layout, sizes the device arena and points every registered field at its array
     int alloc()
     {
         frozen = true;
         if (err) return err;
-        return m->arena.alloc(total() + 256);
+        if (int st = m->arena.alloc(total() + 256)) return st;
+        for (const ArenaBind &b : m->binds) {
+            const size_t base = (b.tok & kScr) ? scr_base() : (b.tok & kOut) ? out_base() : 0;
+            const uint8_t *p = m->arena.p + base + (b.tok & kMask);
+            memcpy(b.field, &p, sizeof p);   // (every object pointer has this representation; the field's own type is F *)
+        }
+        m->binds.clear();
+        return AOS2_OK;
+    }
+    // after alloc(): the host's bytes for a hole (structs that hold bound device pointers)
+    void fill_hole(const void *d_hole, const void *src, size_t bytes)
+    {
+        memcpy(m->h_in.p + (static_cast<const uint8_t *>(d_hole) - m->arena.p), src, bytes);
     }
     int upload()
     {
@@ -2234,29 +2287,19 @@ struct Arena {
         if (total() > scr_base()) AOS2_HIP_CHECK(hipMemsetAsync(m->arena.p + scr_base(), 0, total() - scr_base(), m->stream));
         return AOS2_OK;
     }
-    template <typename T>
-    T *dev(size_t off) const
+    // the device array `d_src` (a bound field; normally a result, so that all of them are neighbours) -> dst, delivered by finish()
+    void fetch(void *dst, const void *d_src, size_t bytes)
     {
-        frozen = true;
-        const size_t base = (off & kScr) ? scr_base() : (off & kOut) ? out_base() : 0;
-        return reinterpret_cast<T *>(m->arena.p + base + (off & kMask));
-    }
-    // result at `off` (normally from reserve_out, so that all results are neighbours) -> dst, delivered by finish()
-    void fetch(void *dst, size_t off, size_t bytes)
-    {
-        if (bytes) fetches.push_back(Fetch{dst, dev<uint8_t>(off), bytes});
-    }
-    void fetch_dev(void *dst, const void *d_src, size_t bytes)
-    {
-        if (bytes) fetches.push_back(Fetch{dst, static_cast<const uint8_t *>(d_src), bytes});
+        if (bytes) m->fetches.push_back(ArenaFetch{dst, static_cast<const uint8_t *>(d_src), bytes});
     }
     // one device-to-host copy of the span the results occupy (they are neighbours in the arena; if they are not, one
     // copy each) into the page-locked bounce buffer, a wait for the stream, then the scatter to the caller's arrays
     int finish()
     {
+        std::vector<ArenaFetch> &fetches = m->fetches;
         const uint8_t *lo = nullptr, *hi = nullptr;
         size_t sum = 0;
-        for (const Fetch &f : fetches) {
+        for (const ArenaFetch &f : fetches) {
             if (!lo || f.src < lo) lo = f.src;
             if (!hi || f.src + f.bytes > hi) hi = f.src + f.bytes;
             sum += (f.bytes + 15) & ~(size_t)15;
@@ -2269,7 +2312,7 @@ struct Arena {
             if (span) AOS2_HIP_CHECK(hipMemcpyAsync(m->h_out.p, lo, span, hipMemcpyDeviceToHost, m->stream));
         } else {
             size_t o = 0;
-            for (const Fetch &f : fetches) {
+            for (const ArenaFetch &f : fetches) {
                 AOS2_HIP_CHECK(hipMemcpyAsync(m->h_out.p + o, f.src, f.bytes, hipMemcpyDeviceToHost, m->stream));
                 o += (f.bytes + 15) & ~(size_t)15;
             }
@@ -2277,48 +2320,47 @@ struct Arena {
         AOS2_HIP_CHECK(hipStreamSynchronize(m->stream));
         AOS2_HIP_CHECK(hipGetLastError());
         size_t o = 0;
-        for (const Fetch &f : fetches) {
+        for (const ArenaFetch &f : fetches) {
             memcpy(f.dst, one ? m->h_out.p + (f.src - lo) : m->h_out.p + o, f.bytes);
             o += (f.bytes + 15) & ~(size_t)15;
         }
         fetches.clear();
         return AOS2_OK;
     }
+    // the timed bracket of a call: begin() | the call's kernels | end() = finish() + their device time in last_ms
+    int begin()
+    {
+        AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+        return AOS2_OK;
+    }
+    int end()
+    {
+        AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
+        if (int st = finish()) return st;
+        (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
+        return AOS2_OK;
+    }
 };
 
-static void fill_frame(Arena &A, const aos2_frame_view_t *f, size_t off[12])
+// stages the frame's arrays and describes them in F (whose pointer fields the arena fills: F stays where it is until then)
+static void frame_dev(Arena &A, const aos2_frame_view_t *f, FrameDev &F)
 {
     const size_t n = (size_t)f->n_f;
-    off[0] = A.push(f->desc_f, n * 32);
-    off[1] = A.push(f->kp_x, n * 4);
-    off[2] = A.push(f->kp_y, n * 4);
-    off[3] = A.push(f->kp_angle, n * 4);
-    off[4] = A.push(f->u_right, n * 4);
-    off[5] = A.push(f->scale_factors, (size_t)f->n_levels * 4);
-    off[6] = A.push(f->kp_octave, n * 4);
-    off[7] = A.push(f->grid_off, (size_t)(GRID_COLS * GRID_ROWS + 1) * 4);
-    off[8] = A.push(f->grid_idx, (size_t)f->grid_off[GRID_COLS * GRID_ROWS] * 4);
-    off[9] = A.push(f->f_mp_state, n);
-}
-
-static FrameDev frame_dev(const Arena &A, const aos2_frame_view_t *f, const size_t off[12])
-{
-    FrameDev F{};
+    F = FrameDev{};
     F.n_f = f->n_f;
     F.n_levels = f->n_levels;
-    F.desc_f = A.dev<uint8_t>(off[0]);
-    F.kp_x = A.dev<float>(off[1]);
-    F.kp_y = A.dev<float>(off[2]);
-    F.kp_angle = A.dev<float>(off[3]);
-    F.u_right = A.dev<float>(off[4]);
-    F.scale_factors = A.dev<float>(off[5]);
-    F.kp_octave = A.dev<int32_t>(off[6]);
-    F.grid_off = A.dev<int32_t>(off[7]);
-    F.grid_idx = A.dev<int32_t>(off[8]);
-    F.f_mp_state = A.dev<uint8_t>(off[9]);
+    A.in(F.desc_f, f->desc_f, n * 32);
+    A.in(F.kp_x, f->kp_x, n * 4);
+    A.in(F.kp_y, f->kp_y, n * 4);
+    A.in(F.kp_angle, f->kp_angle, n * 4);
+    A.in(F.u_right, f->u_right, n * 4);
+    A.in(F.scale_factors, f->scale_factors, (size_t)f->n_levels * 4);
+    A.in(F.kp_octave, f->kp_octave, n * 4);
+    A.in(F.grid_off, f->grid_off, (size_t)(GRID_COLS * GRID_ROWS + 1) * 4);
+    A.in(F.grid_idx, f->grid_idx, (size_t)f->grid_off[GRID_COLS * GRID_ROWS] * 4);
+    A.in(F.f_mp_state, f->f_mp_state, n);
     F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y;
     F.grid_w_inv = f->grid_w_inv; F.grid_h_inv = f->grid_h_inv;
-    return F;
 }
 
 static int check_frame(const aos2_frame_view_t *f)
@@ -2377,6 +2419,34 @@ static int check_levels(const int32_t *lv, int n, int n_levels, const char *what
             return AOS2_ERR_ARG;
         }
     return AOS2_OK;
+}
+
+// merge-join of two FeatureVectors (SearchByBoW :181-258, SearchForTriangulation :691-772): for every vocabulary node
+// both sides hold, each(i1, b0, bc) for the side-1 features i1 under it, in node order; b0 / bc = where side 2 lists its
+// features under that node (node_idx2[b0 .. b0 + bc)).  The visiting order is the reference's.  False: a side-1 feature
+// index outside [0, n1).
+template <class Each>
+static bool fv_join(int n_nodes1, const int32_t *id1, const int32_t *off1, const int32_t *idx1, int n1, int n_nodes2,
+                    const int32_t *id2, const int32_t *off2, Each each)
+{
+    int i1 = 0, i2 = 0;
+    while (i1 < n_nodes1 && i2 < n_nodes2) {
+        const int a = id1[i1], b = id2[i2];
+        if (a == b) {
+            const int b0 = off2[i2], bc = off2[i2 + 1] - b0;
+            for (int k = off1[i1]; k < off1[i1 + 1]; ++k) {
+                if (idx1[k] < 0 || idx1[k] >= n1) return false;
+                each(idx1[k], b0, bc);
+            }
+            i1++;
+            i2++;
+        } else if (a < b) {
+            while (i1 < n_nodes1 && id1[i1] < b) i1++;  // lower_bound
+        } else {
+            while (i2 < n_nodes2 && id2[i2] < a) i2++;
+        }
+    }
+    return true;
 }
 
 }  // namespace aos2
@@ -2478,17 +2548,19 @@ int aos2_matcher_hamming_best2(aos2_matcher_t *m, const uint8_t *q, int nq, cons
     int st = matcher_init(m);
     if (st) return st;
     Arena A{m};
-    const size_t oq = A.push(q, (size_t)nq * 32), ot = A.push(t, (size_t)nt * 32);
-    const size_t o1 = A.reserve((size_t)nq * 4), o2 = A.reserve((size_t)nq * 4), o3 = A.reserve((size_t)nq * 4);
+    const uint8_t *d_q, *d_t;
+    int32_t *d_bi, *d_bd, *d_sd;
+    A.in(d_q, q, (size_t)nq * 32);
+    A.in(d_t, t, (size_t)nt * 32);
+    A.scratch(d_bi, (size_t)nq * 4);
+    A.scratch(d_bd, (size_t)nq * 4);
+    A.scratch(d_sd, (size_t)nq * 4);
     if ((st = A.upload())) return st;
-    st = hamming_run(m, A.dev<uint8_t>(oq), nq, A.dev<uint8_t>(ot), nt, A.dev<int32_t>(o1), A.dev<int32_t>(o2),
-                     A.dev<int32_t>(o3), 1, nullptr);
-    if (st) return st;
-    A.fetch(best_idx, o1, (size_t)nq * 4);
-    A.fetch(best_dist, o2, (size_t)nq * 4);
-    A.fetch(second_dist, o3, (size_t)nq * 4);
-    if ((st = A.finish())) return st;
-    return AOS2_OK;
+    if ((st = hamming_run(m, d_q, nq, d_t, nt, d_bi, d_bd, d_sd, 1, nullptr))) return st;
+    A.fetch(best_idx, d_bi, (size_t)nq * 4);
+    A.fetch(best_dist, d_bd, (size_t)nq * 4);
+    A.fetch(second_dist, d_sd, (size_t)nq * 4);
+    return A.finish();
 }
 
 // shared by SearchByBoW(KF, F) (kf_kf = 0, match_out[p] has n_f entries) and SearchByBoW(KF1, KF2)
@@ -2502,8 +2574,7 @@ static int bow_run(aos2_matcher_t *m, const aos2_bow_pair_t *pairs, const uint8_
     int st = matcher_init(m);
     if (st) return st;
     Arena A{m};
-    struct Off { size_t o[13]; int nq; };
-    std::vector<Off> offs(n_pairs);
+    std::vector<BowPairDev> dev(n_pairs);
     std::vector<BowQuery> queries;
     int max_nf = 0, max_q = 0;
     for (int p = 0; p < n_pairs; ++p) {
@@ -2512,110 +2583,74 @@ static int bow_run(aos2_matcher_t *m, const aos2_bow_pair_t *pairs, const uint8_
             set_error("bad BoW pair %d", p);
             return AOS2_ERR_ARG;
         }
-        // merge-join of the two FeatureVectors (:181-258) on the host: the visiting order of the
-        // KF features and the bucket each one is compared against
+        // on the host: the visiting order of the KF features and the bucket each one is compared against
         queries.clear();
         size_t ent = 0;
-        int ik = 0, jf = 0;
-        while (ik < P.n_nodes_kf && jf < P.n_nodes_f) {
-            const int idk = P.node_id_kf[ik], idf = P.node_id_f[jf];
-            if (idk == idf) {
-                const int b0 = P.node_off_f[jf], bc = P.node_off_f[jf + 1] - b0;
-                for (int a = P.node_off_kf[ik]; a < P.node_off_kf[ik + 1]; ++a) {
-                    const int kf = P.node_idx_kf[a];
-                    if (kf < 0 || kf >= P.n_kf) {
-                        set_error("BoW pair %d: feature index out of range", p);
-                        return AOS2_ERR_ARG;
-                    }
-                    if (!P.kf_has_mp[kf]) continue;  // no map point / bad (:194-198)
-                    queries.push_back(BowQuery{kf, b0, bc, (int32_t)ent});
-                    ent += (size_t)bc;
-                }
-                ik++;
-                jf++;
-            } else if (idk < idf) {
-                while (ik < P.n_nodes_kf && P.node_id_kf[ik] < idf) ik++;  // lower_bound
-            } else {
-                while (jf < P.n_nodes_f && P.node_id_f[jf] < idk) jf++;
-            }
+        const bool in_range = fv_join(P.n_nodes_kf, P.node_id_kf, P.node_off_kf, P.node_idx_kf, P.n_kf, P.n_nodes_f, P.node_id_f,
+                                      P.node_off_f, [&](int kf, int b0, int bc) {
+                                          if (!P.kf_has_mp[kf]) return;  // no map point / bad (:194-198)
+                                          queries.push_back(BowQuery{kf, b0, bc, (int32_t)ent});
+                                          ent += (size_t)bc;
+                                      });
+        if (!in_range) {
+            set_error("BoW pair %d: feature index out of range", p);
+            return AOS2_ERR_ARG;
         }
         if (ent > (size_t)1 << 28) {
             set_error("BoW pair %d needs %zu distance entries", p, ent);
             return AOS2_ERR_ARG;
         }
-        Off &o = offs[p];
-        o.nq = (int)queries.size();
-        if (!dev_inputs) {
-            o.o[0] = A.push(P.desc_kf, (size_t)P.n_kf * 32);
-            o.o[1] = A.push(P.desc_f, (size_t)P.n_f * 32);
-            o.o[2] = A.push(P.angle_kf, (size_t)P.n_kf * 4);
-            o.o[3] = A.push(P.angle_f, (size_t)P.n_f * 4);
+        BowPairDev &D = dev[p];
+        D.n_kf = P.n_kf; D.n_f = P.n_f; D.n_queries = (int)queries.size();
+        D.kf_kf = kf_kf;
+        if (dev_inputs) {
+            D.desc_kf = P.desc_kf; D.desc_f = P.desc_f; D.angle_kf = P.angle_kf; D.angle_f = P.angle_f;
+        } else {
+            A.in(D.desc_kf, P.desc_kf, (size_t)P.n_kf * 32);
+            A.in(D.desc_f, P.desc_f, (size_t)P.n_f * 32);
+            A.in(D.angle_kf, P.angle_kf, (size_t)P.n_kf * 4);
+            A.in(D.angle_f, P.angle_f, (size_t)P.n_f * 4);
         }
-        o.o[4] = A.push(P.node_idx_f, (size_t)(P.n_nodes_f ? P.node_off_f[P.n_nodes_f] : 0) * 4);
-        o.o[5] = A.push(queries.data(), queries.size() * sizeof(BowQuery));
-        o.o[6] = A.reserve(ent * sizeof(Entry) + 8);
-        o.o[7] = A.reserve_out((size_t)P.n_f * 4 + 4);  // match_f
-        o.o[8] = A.reserve((size_t)P.n_f * 4 + 4);  // bin_f
-        o.o[9] = A.reserve_out(4);                      // nmatches
-        o.o[12] = A.reserve(queries.size() * 4 + 4);  // choice (parallel stage B)
+        A.in(D.node_idx_f, P.node_idx_f, (size_t)(P.n_nodes_f ? P.node_off_f[P.n_nodes_f] : 0) * 4);
+        A.in(D.queries, queries.data(), queries.size() * sizeof(BowQuery));
+        A.scratch(D.entries, ent * sizeof(Entry) + 8);
+        A.out(D.match_f, (size_t)P.n_f * 4 + 4);
+        A.scratch(D.bin_f, (size_t)P.n_f * 4 + 4);
+        A.out(D.nmatches, 4);
+        A.scratch(D.choice, queries.size() * 4 + 4);   // (parallel stage B)
         if (kf_kf) {
-            o.o[10] = A.push(f_has_mp[p], (size_t)P.n_f);
-            o.o[11] = A.reserve_out((size_t)P.n_kf * 8 + 8);  // match_1 | bin_1
+            A.in(D.f_has_mp, f_has_mp[p], (size_t)P.n_f);
+            const size_t m1 = A.out(D.match_1, (size_t)P.n_kf * 8 + 8);   // match_1 | bin_1
+            A.bind(D.bin_1, m1 + (size_t)P.n_kf * 4);
         }
         max_nf = std::max(max_nf, P.n_f);
-        max_q = std::max(max_q, o.nq);
+        max_q = std::max(max_q, D.n_queries);
     }
     if (max_nf > 60000) {
         set_error("n_f %d exceeds the LDS flag table (60000)", max_nf);
         return AOS2_ERR_ARG;
     }
-    const size_t opairs = A.push_hole(sizeof(BowPairDev) * n_pairs);
+    const BowPairDev *d_pairs;
+    A.hole(d_pairs, sizeof(BowPairDev) * n_pairs);
     if ((st = A.alloc())) return st;
-    std::vector<BowPairDev> dev(n_pairs);
-    for (int p = 0; p < n_pairs; ++p) {
-        const aos2_bow_pair_t &P = pairs[p];
-        const Off &o = offs[p];
-        BowPairDev &D = dev[p];
-        D.n_kf = P.n_kf; D.n_f = P.n_f; D.n_queries = o.nq;
-        if (dev_inputs) {
-            D.desc_kf = P.desc_kf; D.desc_f = P.desc_f; D.angle_kf = P.angle_kf; D.angle_f = P.angle_f;
-        } else {
-            D.desc_kf = A.dev<uint8_t>(o.o[0]); D.desc_f = A.dev<uint8_t>(o.o[1]);
-            D.angle_kf = A.dev<float>(o.o[2]); D.angle_f = A.dev<float>(o.o[3]);
-        }
-        D.node_idx_f = A.dev<int32_t>(o.o[4]); D.queries = A.dev<BowQuery>(o.o[5]); D.entries = A.dev<Entry>(o.o[6]);
-        D.match_f = A.dev<int32_t>(o.o[7]); D.bin_f = A.dev<uint32_t>(o.o[8]); D.nmatches = A.dev<int32_t>(o.o[9]);
-        D.kf_kf = kf_kf;
-        D.choice = A.dev<int32_t>(o.o[12]);
-        D.f_has_mp = nullptr; D.match_1 = nullptr; D.bin_1 = nullptr;
-        if (kf_kf) {
-            D.f_has_mp = A.dev<uint8_t>(o.o[10]);
-            D.match_1 = A.dev<int32_t>(o.o[11]);
-            D.bin_1 = D.match_1 + P.n_kf;
-        }
-    }
-    memcpy(A.hostptr(opairs), dev.data(), sizeof(BowPairDev) * n_pairs);
+    A.fill_hole(d_pairs, dev.data(), sizeof(BowPairDev) * n_pairs);
     if ((st = A.upload())) return st;
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    if (max_q > 0)
-        hipLaunchKernelGGL(bow_distances_kernel, dim3(max_q, n_pairs), dim3(64), 0, m->stream, A.dev<BowPairDev>(opairs));
-    if ((size_t)max_nf * 8 <= kFixLdsBytes && !m->serial_resolve)
-        hipLaunchKernelGGL(bow_resolve_fix_kernel, dim3(n_pairs), dim3(512), (size_t)max_nf * 8 + 16, m->stream,
-                           A.dev<BowPairDev>(opairs), m->nnratio, m->check_ori);
+    if ((st = A.begin())) return st;
+    if (max_q > 0) hipLaunchKernelGGL(bow_distances_kernel, dim3(max_q, n_pairs), dim3(64), 0, m->stream, d_pairs);
+    if (use_fix_resolve(m, max_nf))
+        hipLaunchKernelGGL(bow_resolve_fix_kernel, dim3(n_pairs), dim3(512), (size_t)max_nf * 8 + 16, m->stream, d_pairs,
+                           m->nnratio, m->check_ori);
     else
-        hipLaunchKernelGGL(bow_resolve_kernel, dim3(n_pairs), dim3(64), (size_t)max_nf + 16, m->stream,
-                           A.dev<BowPairDev>(opairs), m->nnratio, m->check_ori);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
+        hipLaunchKernelGGL(bow_resolve_kernel, dim3(n_pairs), dim3(64), (size_t)max_nf + 16, m->stream, d_pairs, m->nnratio,
+                           m->check_ori);
     for (int p = 0; p < n_pairs; ++p) {
         if (!kf_kf)
-            A.fetch(match_f[p], offs[p].o[7], (size_t)pairs[p].n_f * 4);
+            A.fetch(match_f[p], dev[p].match_f, (size_t)pairs[p].n_f * 4);
         else
-            A.fetch(match_f[p], offs[p].o[11], (size_t)pairs[p].n_kf * 4);
-        A.fetch(&nmatches[p], offs[p].o[9], 4);
+            A.fetch(match_f[p], dev[p].match_1, (size_t)pairs[p].n_kf * 4);
+        A.fetch(&nmatches[p], dev[p].nmatches, 4);
     }
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    return A.end();
 }
 
 int aos2_matcher_search_by_bow(aos2_matcher_t *m, const aos2_bow_pair_t *pairs, int n_pairs, int32_t *const *match_f,
@@ -2750,9 +2785,9 @@ int aos2_matcher_search_for_triangulation(aos2_matcher_t *m, const aos2_triang_p
     int st = matcher_init(m);
     if (st) return st;
     Arena A{m};
-    struct Off { size_t o[20]; int nq; };
-    std::vector<Off> offs(n_pairs);
+    std::vector<TriPairDev> dev(n_pairs);
     std::vector<TriQuery> queries;
+    std::vector<int32_t> init;
     int max_q = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const aos2_triang_pair_t &P = pairs[p];
@@ -2761,78 +2796,55 @@ int aos2_matcher_search_for_triangulation(aos2_matcher_t *m, const aos2_triang_p
             return AOS2_ERR_ARG;
         }
         queries.clear();
-        int i1 = 0, i2 = 0;
-        while (i1 < P.n_nodes1 && i2 < P.n_nodes2) {  // merge-join of the FeatureVectors (:691-772)
-            const int a = P.node_id1[i1], b = P.node_id2[i2];
-            if (a == b) {
-                const int b0 = P.node_off2[i2], bc = P.node_off2[i2 + 1] - b0;
-                for (int k = P.node_off1[i1]; k < P.node_off1[i1 + 1]; ++k) {
-                    const int idx1 = P.node_idx1[k];
-                    if (idx1 < 0 || idx1 >= P.n1) {
-                        set_error("triangulation pair %d: feature index out of range", p);
-                        return AOS2_ERR_ARG;
-                    }
-                    if (P.has_mp1[idx1]) continue;                            // :700-703
-                    if (only_stereo && !(P.u_right1[idx1] >= 0)) continue;    // :705-709
-                    queries.push_back(TriQuery{idx1, b0, bc});
-                }
-                i1++;
-                i2++;
-            } else if (a < b) {
-                while (i1 < P.n_nodes1 && P.node_id1[i1] < b) i1++;
-            } else {
-                while (i2 < P.n_nodes2 && P.node_id2[i2] < a) i2++;
-            }
+        const bool in_range = fv_join(P.n_nodes1, P.node_id1, P.node_off1, P.node_idx1, P.n1, P.n_nodes2, P.node_id2, P.node_off2,
+                                      [&](int idx1, int b0, int bc) {
+                                          if (P.has_mp1[idx1]) return;                            // :700-703
+                                          if (only_stereo && !(P.u_right1[idx1] >= 0)) return;    // :705-709
+                                          queries.push_back(TriQuery{idx1, b0, bc});
+                                      });
+        if (!in_range) {
+            set_error("triangulation pair %d: feature index out of range", p);
+            return AOS2_ERR_ARG;
         }
-        Off &o = offs[p];
-        o.nq = (int)queries.size();
         const size_t n1 = (size_t)P.n1, n2 = (size_t)P.n2;
-        o.o[0] = A.push(P.desc1, n1 * 32); o.o[1] = A.push(P.desc2, n2 * 32); o.o[2] = A.push(P.has_mp2, n2);
-        o.o[3] = A.push(P.x1, n1 * 4); o.o[4] = A.push(P.y1, n1 * 4); o.o[5] = A.push(P.angle1, n1 * 4);
-        o.o[6] = A.push(P.u_right1, n1 * 4);
-        o.o[7] = A.push(P.x2, n2 * 4); o.o[8] = A.push(P.y2, n2 * 4); o.o[9] = A.push(P.angle2, n2 * 4);
-        o.o[10] = A.push(P.u_right2, n2 * 4); o.o[11] = A.push(P.octave2, n2 * 4);
-        o.o[12] = A.push(P.scale_factors2, (size_t)P.n_levels2 * 4);
-        o.o[13] = A.push(P.level_sigma2_2, (size_t)P.n_levels2 * 4);
-        o.o[14] = A.push(P.node_idx2, (size_t)(P.n_nodes2 ? P.node_off2[P.n_nodes2] : 0) * 4);
-        o.o[15] = A.push(queries.data(), queries.size() * sizeof(TriQuery));
-        std::vector<int32_t> init(n1 + 1, -1);
-        o.o[16] = A.push(init.data(), (n1 + 1) * 4);  // match12 = -1 (:681)
-        o.o[17] = A.reserve(8);
-        max_q = std::max(max_q, o.nq);
-    }
-    const size_t opairs = A.push_hole(sizeof(TriPairDev) * n_pairs);
-    if ((st = A.alloc())) return st;
-    std::vector<TriPairDev> dev(n_pairs);
-    for (int p = 0; p < n_pairs; ++p) {
-        const aos2_triang_pair_t &P = pairs[p];
-        const Off &o = offs[p];
         TriPairDev &D = dev[p];
-        D.n1 = P.n1; D.n2 = P.n2; D.n_queries = o.nq; D.only_stereo = only_stereo;
-        D.desc1 = A.dev<uint8_t>(o.o[0]); D.desc2 = A.dev<uint8_t>(o.o[1]); D.has_mp2 = A.dev<uint8_t>(o.o[2]);
-        D.x1 = A.dev<float>(o.o[3]); D.y1 = A.dev<float>(o.o[4]); D.angle1 = A.dev<float>(o.o[5]); D.u_right1 = A.dev<float>(o.o[6]);
-        D.x2 = A.dev<float>(o.o[7]); D.y2 = A.dev<float>(o.o[8]); D.angle2 = A.dev<float>(o.o[9]); D.u_right2 = A.dev<float>(o.o[10]);
-        D.octave2 = A.dev<int32_t>(o.o[11]); D.scale_factors2 = A.dev<float>(o.o[12]); D.level_sigma2_2 = A.dev<float>(o.o[13]);
+        D.n1 = P.n1; D.n2 = P.n2; D.n_queries = (int)queries.size(); D.only_stereo = only_stereo;
         memcpy(D.F12, P.F12, sizeof(D.F12));
         D.ex = P.ex; D.ey = P.ey;
-        D.node_idx2 = A.dev<int32_t>(o.o[14]); D.queries = A.dev<TriQuery>(o.o[15]);
-        D.match12 = A.dev<int32_t>(o.o[16]); D.nmatches = A.dev<int32_t>(o.o[17]);
+        A.in(D.desc1, P.desc1, n1 * 32);
+        A.in(D.desc2, P.desc2, n2 * 32);
+        A.in(D.has_mp2, P.has_mp2, n2);
+        A.in(D.x1, P.x1, n1 * 4);
+        A.in(D.y1, P.y1, n1 * 4);
+        A.in(D.angle1, P.angle1, n1 * 4);
+        A.in(D.u_right1, P.u_right1, n1 * 4);
+        A.in(D.x2, P.x2, n2 * 4);
+        A.in(D.y2, P.y2, n2 * 4);
+        A.in(D.angle2, P.angle2, n2 * 4);
+        A.in(D.u_right2, P.u_right2, n2 * 4);
+        A.in(D.octave2, P.octave2, n2 * 4);
+        A.in(D.scale_factors2, P.scale_factors2, (size_t)P.n_levels2 * 4);
+        A.in(D.level_sigma2_2, P.level_sigma2_2, (size_t)P.n_levels2 * 4);
+        A.in(D.node_idx2, P.node_idx2, (size_t)(P.n_nodes2 ? P.node_off2[P.n_nodes2] : 0) * 4);
+        A.in(D.queries, queries.data(), queries.size() * sizeof(TriQuery));
+        init.assign(n1 + 1, -1);
+        A.in(D.match12, init.data(), (n1 + 1) * 4);  // match12 = -1 (:681)
+        A.scratch(D.nmatches, 8);
+        max_q = std::max(max_q, D.n_queries);
     }
-    memcpy(A.hostptr(opairs), dev.data(), sizeof(TriPairDev) * n_pairs);
+    TriPairDev *d_pairs;
+    A.hole(d_pairs, sizeof(TriPairDev) * n_pairs);
+    if ((st = A.alloc())) return st;
+    A.fill_hole(d_pairs, dev.data(), sizeof(TriPairDev) * n_pairs);
     if ((st = A.upload())) return st;
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    if (max_q > 0)
-        hipLaunchKernelGGL(triang_match_kernel, dim3(max_q, n_pairs), dim3(64), 0, m->stream, A.dev<TriPairDev>(opairs));
-    hipLaunchKernelGGL(triang_finish_kernel, dim3(n_pairs), dim3(64), 0, m->stream, A.dev<TriPairDev>(opairs), m->check_ori);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
+    if ((st = A.begin())) return st;
+    if (max_q > 0) hipLaunchKernelGGL(triang_match_kernel, dim3(max_q, n_pairs), dim3(64), 0, m->stream, d_pairs);
+    hipLaunchKernelGGL(triang_finish_kernel, dim3(n_pairs), dim3(64), 0, m->stream, d_pairs, m->check_ori);
     for (int p = 0; p < n_pairs; ++p) {
-        if (pairs[p].n1 > 0)
-            A.fetch_dev(match12[p], dev[p].match12, (size_t)pairs[p].n1 * 4);
-        A.fetch_dev(&nmatches[p], dev[p].nmatches, 4);
+        if (pairs[p].n1 > 0) A.fetch(match12[p], dev[p].match12, (size_t)pairs[p].n1 * 4);
+        A.fetch(&nmatches[p], dev[p].nmatches, 4);
     }
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    return A.end();
 }
 
 int aos2_compute_distinctive_descriptors(aos2_matcher_t *m, int n_points, const int32_t *off, const uint8_t *desc,
@@ -2856,16 +2868,40 @@ int aos2_compute_distinctive_descriptors(aos2_matcher_t *m, int n_points, const 
     int st = matcher_init(m);
     if (st) return st;
     Arena A{m};
-    const size_t o0 = A.push(off, (size_t)(n_points + 1) * 4), o1 = A.push(desc, total * 32), o2 = A.reserve((size_t)n_points * 4);
+    const int32_t *d_off;
+    const uint8_t *d_desc;
+    int32_t *d_best;
+    A.in(d_off, off, (size_t)(n_points + 1) * 4);
+    A.in(d_desc, desc, total * 32);
+    A.scratch(d_best, (size_t)n_points * 4);
     if ((st = A.upload())) return st;
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(distinctive_kernel, dim3(n_points), dim3(64), 0, m->stream, n_points, A.dev<int32_t>(o0),
-                       A.dev<uint8_t>(o1), A.dev<int32_t>(o2));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(best_idx, A.dev<int32_t>(o2), (size_t)n_points * 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(distinctive_kernel, dim3(n_points), dim3(64), 0, m->stream, n_points, d_off, d_desc, d_best);
+    A.fetch(best_idx, d_best, (size_t)n_points * 4);
+    return A.end();
+}
+
+// one SearchByProjection(Frame, map points) problem -- the single call, or an item of the batch: the frame and the map
+// points, the results, then the scratch of the two stages
+static void proj_mp_item(Arena &A, const aos2_frame_view_t *f, const aos2_proj_mp_t *p, ProjMpItem &it)
+{
+    const size_t n = (size_t)p->n_mp;
+    frame_dev(A, f, it.F);
+    ProjMpDev &P = it.P;
+    P = ProjMpDev{};
+    P.n_mp = p->n_mp;
+    A.in(P.track_in_view, p->track_in_view, n);
+    A.in(P.desc, p->desc, n * 32);
+    A.in(P.has_obs, p->has_obs, n);
+    A.in(P.pred_level, p->pred_level, n * 4);
+    A.in(P.view_cos, p->view_cos, n * 4);
+    A.in(P.proj_x, p->proj_x, n * 4);
+    A.in(P.proj_y, p->proj_y, n * 4);
+    A.in(P.proj_xr, p->proj_xr, n * 4);
+    A.out(it.match_f, (size_t)f->n_f * 4 + 4);
+    A.out(it.nmatches, 8);   // nmatches, and a word for the entry counter / overflow flag of the single call
+    A.scratch(it.slots, (n + 1) * sizeof(QuerySlot));
+    A.scratch(it.choice, (n + 1) * 4);
 }
 
 int aos2_matcher_search_by_projection(aos2_matcher_t *m, const aos2_frame_view_t *f, const aos2_proj_mp_t *p, float th,
@@ -2884,15 +2920,10 @@ int aos2_matcher_search_by_projection(aos2_matcher_t *m, const aos2_frame_view_t
     if ((st = check_levels(p->pred_level, p->n_mp, f->n_levels, "pred_level", p->track_in_view))) return st;
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t fo[12];
-    fill_frame(A, f, fo);
-    const size_t n = (size_t)p->n_mp;
-    const size_t o0 = A.push(p->track_in_view, n), o1 = A.push(p->desc, n * 32), o2 = A.push(p->has_obs, n);
-    const size_t o3 = A.push(p->pred_level, n * 4), o4 = A.push(p->view_cos, n * 4), o5 = A.push(p->proj_x, n * 4);
-    const size_t o6 = A.push(p->proj_y, n * 4), o7 = A.push(p->proj_xr, n * 4);
-    const size_t om = A.reserve_out((size_t)f->n_f * 4 + 4), on = A.reserve_out(8);
-    const size_t oslots = A.reserve((size_t)(p->n_mp + 1) * sizeof(QuerySlot));
-    const size_t ochoice = A.reserve((size_t)(p->n_mp + 1) * 4);
+    ProjMpItem it{};
+    proj_mp_item(A, f, p, it);
+    const FrameDev &F = it.F;
+    const ProjMpDev &P = it.P;
     // Entry pool.  Usual sizes: every query owns a slice that holds the whole frame (one pass, no counting).  Large local
     // maps (n_mp x n_f x 8 B beyond 64 MB): the pool is sized from the REAL window populations -- count pass, scan, fill
     // pass -- starting from a budget of 64 entries per query and, if the windows of this call hold more (the scan reports
@@ -2902,48 +2933,35 @@ int aos2_matcher_search_by_projection(aos2_matcher_t *m, const aos2_frame_view_t
     size_t pool_cap = two_pass ? std::max<size_t>((size_t)p->n_mp * 64, 1024) : worst;
     if (const char *e = getenv("AOS2_PROJ_POOL_BUDGET")) pool_cap = two_pass ? (size_t)std::max(1, atoi(e)) : pool_cap;   // (tests: force the retry)
     if ((st = A.upload())) return st;
-    FrameDev F = frame_dev(A, f, fo);
-    ProjMpDev P{};
-    P.n_mp = p->n_mp;
-    P.track_in_view = A.dev<uint8_t>(o0); P.desc = A.dev<uint8_t>(o1); P.has_obs = A.dev<uint8_t>(o2);
-    P.pred_level = A.dev<int32_t>(o3); P.view_cos = A.dev<float>(o4); P.proj_x = A.dev<float>(o5);
-    P.proj_y = A.dev<float>(o6); P.proj_xr = A.dev<float>(o7);
-    int32_t *d_used = A.dev<int32_t>(on) + 1;
-    QuerySlot *d_slots = A.dev<QuerySlot>(oslots);
+    int32_t *d_used = it.nmatches + 1;
     for (int attempt = 0;; ++attempt) {
-        if (pool_cap > ((size_t)1 << 31) - 2) {
-            set_error("projection search: %zu candidate entries exceed the pool's index range", pool_cap);
-            return AOS2_ERR_CAPACITY;
-        }
-        if ((st = m->pool.alloc(pool_cap + 1))) return st;
-        Entry *d_pool = reinterpret_cast<Entry *>(m->pool.p);
+        Entry *d_pool;
+        if ((st = pool_reserve(m, pool_cap, "projection search", d_pool))) return st;
         AOS2_HIP_CHECK(hipMemsetAsync(d_used, 0, 4, m->stream));
-        if (attempt == 0) AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+        if (attempt == 0 && (st = A.begin())) return st;   // (a second attempt is timed with the first)
         if (p->n_mp > 0) {
             if (!two_pass)
-                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, d_slots, d_pool, d_used,
+                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, it.slots, d_pool, d_used,
                                    (int)pool_cap, 0);
             else {
-                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, d_slots, d_pool, d_used,
+                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, it.slots, d_pool, d_used,
                                    (int)pool_cap, 1);
-                hipLaunchKernelGGL(frames_scan_slots_kernel, dim3(1), dim3(256), 0, m->stream, d_slots, (const int32_t *)nullptr,
+                hipLaunchKernelGGL(frames_scan_slots_kernel, dim3(1), dim3(256), 0, m->stream, it.slots, (const int32_t *)nullptr,
                                    p->n_mp, (int)pool_cap, d_used);
-                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, d_slots, d_pool, d_used,
+                hipLaunchKernelGGL(proj_mp_entries_kernel, dim3(p->n_mp), dim3(64), 0, m->stream, F, P, th, it.slots, d_pool, d_used,
                                    (int)pool_cap, 2);
             }
         }
-        if ((size_t)f->n_f * 8 <= kFixLdsBytes && !m->serial_resolve)
+        if (use_fix_resolve(m, f->n_f))
             hipLaunchKernelGGL(proj_mp_resolve_fix_kernel, dim3(1), dim3(1024), (size_t)f->n_f * 8 + 16, m->stream, F, P, m->nnratio,
-                               d_slots, reinterpret_cast<const Entry *>(d_pool), A.dev<int32_t>(om), A.dev<int32_t>(on),
-                               A.dev<int32_t>(ochoice));
+                               it.slots, d_pool, it.match_f, it.nmatches, it.choice);
         else   // the one-wave sequential loop: frames with more features than the LDS copy of B holds, or AOS2_SERIAL_RESOLVE=1
-            hipLaunchKernelGGL(proj_mp_resolve_kernel, dim3(1), dim3(64), (size_t)f->n_f + 16, m->stream, F, P, m->nnratio, d_slots,
-                               reinterpret_cast<const Entry *>(d_pool), A.dev<int32_t>(om), A.dev<int32_t>(on));
-        AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
+            hipLaunchKernelGGL(proj_mp_resolve_kernel, dim3(1), dim3(64), (size_t)f->n_f + 16, m->stream, F, P, m->nnratio, it.slots,
+                               d_pool, it.match_f, it.nmatches);
         int32_t tail[2] = {0, 0};   // nmatches, overflow word
-        A.fetch(match_f, om, (size_t)f->n_f * 4);
-        A.fetch(tail, on, 8);
-        if ((st = A.finish())) return st;
+        A.fetch(match_f, it.match_f, (size_t)f->n_f * 4);
+        A.fetch(tail, it.nmatches, 8);
+        if ((st = A.end())) return st;
         if (two_pass && (size_t)tail[1] > pool_cap && attempt == 0) {   // the windows hold tail[1] entries: once more, exactly sized
             pool_cap = (size_t)tail[1];
             continue;
@@ -2951,7 +2969,6 @@ int aos2_matcher_search_by_projection(aos2_matcher_t *m, const aos2_frame_view_t
         *nmatches = tail[0];
         break;
     }
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
     return AOS2_OK;
 }
 
@@ -2980,76 +2997,45 @@ int aos2_matcher_search_by_projection_batch(aos2_matcher_t *m, const aos2_frame_
         max_mp = std::max(max_mp, problems[i].n_mp);
         max_nf = std::max(max_nf, frames[i].n_f);
     }
-    // (entry offsets are 32-bit: 2^31 entries = 16 GiB of the device's 288 GB; what actually limits a call is the allocation)
-    if (pool_cap > ((size_t)1 << 31) - 2) {
-        set_error("batched projection search: %zu candidate entries exceed the pool's index range", pool_cap);
-        return AOS2_ERR_CAPACITY;
-    }
     if ((st = matcher_init(m))) return st;
+    Entry *d_pool;
+    if ((st = pool_reserve(m, pool_cap, "batched projection search", d_pool))) return st;
     Arena A{m};
-    struct Off { size_t fo[12], o[8], om, on, oslots, ochoice; };
-    std::vector<Off> offs(n_problems);
-    for (int i = 0; i < n_problems; ++i) {
-        const aos2_proj_mp_t *p = &problems[i];
-        Off &o = offs[i];
-        fill_frame(A, &frames[i], o.fo);
-        const size_t n = (size_t)p->n_mp;
-        o.o[0] = A.push(p->track_in_view, n); o.o[1] = A.push(p->desc, n * 32); o.o[2] = A.push(p->has_obs, n);
-        o.o[3] = A.push(p->pred_level, n * 4); o.o[4] = A.push(p->view_cos, n * 4); o.o[5] = A.push(p->proj_x, n * 4);
-        o.o[6] = A.push(p->proj_y, n * 4); o.o[7] = A.push(p->proj_xr, n * 4);
-        o.om = A.reserve_out((size_t)frames[i].n_f * 4 + 4);
-        o.on = A.reserve_out(8);
-        o.oslots = A.reserve((n + 1) * sizeof(QuerySlot));
-        o.ochoice = A.reserve((n + 1) * 4);
-    }
-    const size_t oitems = A.push_hole(sizeof(ProjMpItem) * (size_t)n_problems);
-    const size_t oused = A.reserve_out((size_t)n_problems * 256 + 8);   // one counter per problem, 256 B apart
-    if ((st = m->pool.alloc(pool_cap + 1))) return st;
-    if ((st = A.alloc())) return st;
     std::vector<ProjMpItem> items(n_problems);
     size_t pool_next = 0;
     for (int i = 0; i < n_problems; ++i) {
-        const aos2_proj_mp_t *p = &problems[i];
-        const Off &o = offs[i];
         ProjMpItem &it = items[i];
-        it.F = frame_dev(A, &frames[i], o.fo);
-        it.P = ProjMpDev{};
-        it.P.n_mp = p->n_mp;
-        it.P.track_in_view = A.dev<uint8_t>(o.o[0]); it.P.desc = A.dev<uint8_t>(o.o[1]); it.P.has_obs = A.dev<uint8_t>(o.o[2]);
-        it.P.pred_level = A.dev<int32_t>(o.o[3]); it.P.view_cos = A.dev<float>(o.o[4]); it.P.proj_x = A.dev<float>(o.o[5]);
-        it.P.proj_y = A.dev<float>(o.o[6]); it.P.proj_xr = A.dev<float>(o.o[7]);
-        it.slots = A.dev<QuerySlot>(o.oslots);
-        it.match_f = A.dev<int32_t>(o.om);
-        it.nmatches = A.dev<int32_t>(o.on);
-        it.choice = A.dev<int32_t>(o.ochoice);
-        it.pool_used = A.dev<int32_t>(oused) + 64 * (size_t)i;
-        it.pool_cap = (int32_t)((size_t)p->n_mp * (size_t)std::min(frames[i].n_f, 512));
+        proj_mp_item(A, &frames[i], &problems[i], it);
+        it.pool_cap = (int32_t)((size_t)problems[i].n_mp * (size_t)std::min(frames[i].n_f, 512));
         it.pool_base = (int32_t)pool_next;
         pool_next += (size_t)it.pool_cap;
     }
-    memcpy(A.hostptr(oitems), items.data(), sizeof(ProjMpItem) * (size_t)n_problems);
+    const ProjMpItem *d_items;
+    int32_t *d_used;
+    A.hole(d_items, sizeof(ProjMpItem) * (size_t)n_problems);
+    const size_t used_tok = A.out(d_used, (size_t)n_problems * 256 + 8);   // one counter per problem, 256 B apart
+    for (int i = 0; i < n_problems; ++i) A.bind(items[i].pool_used, used_tok + 256 * (size_t)i);
+    if ((st = A.alloc())) return st;
+    A.fill_hole(d_items, items.data(), sizeof(ProjMpItem) * (size_t)n_problems);
     if ((st = A.upload())) return st;
-    int32_t *d_used = A.dev<int32_t>(oused);
     AOS2_HIP_CHECK(hipMemsetAsync(d_used, 0, (size_t)n_problems * 256, m->stream));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+    if ((st = A.begin())) return st;
     if (max_mp > 0)
-        hipLaunchKernelGGL(proj_mp_entries_batch_kernel, dim3(max_mp, n_problems), dim3(64), 0, m->stream,
-                           A.dev<ProjMpItem>(oitems), th, reinterpret_cast<Entry *>(m->pool.p));
-    if ((size_t)max_nf * 8 <= kFixLdsBytes && !m->serial_resolve)
-        hipLaunchKernelGGL(proj_mp_resolve_fix_batch_kernel, dim3(n_problems), dim3(256), (size_t)max_nf * 8 + 16, m->stream,
-                           A.dev<ProjMpItem>(oitems), m->nnratio, reinterpret_cast<const Entry *>(m->pool.p));
+        hipLaunchKernelGGL(proj_mp_entries_batch_kernel, dim3(max_mp, n_problems), dim3(64), 0, m->stream, d_items, th,
+                           d_pool);
+    if (use_fix_resolve(m, max_nf))
+        hipLaunchKernelGGL(proj_mp_resolve_fix_batch_kernel, dim3(n_problems), dim3(256), (size_t)max_nf * 8 + 16, m->stream, d_items,
+                           m->nnratio, d_pool);
     else
-        hipLaunchKernelGGL(proj_mp_resolve_batch_kernel, dim3(n_problems), dim3(64), (size_t)max_nf + 16, m->stream,
-                           A.dev<ProjMpItem>(oitems), m->nnratio, reinterpret_cast<const Entry *>(m->pool.p));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
+        hipLaunchKernelGGL(proj_mp_resolve_batch_kernel, dim3(n_problems), dim3(64), (size_t)max_nf + 16, m->stream, d_items,
+                           m->nnratio, d_pool);
     std::vector<int32_t> used((size_t)n_problems * 64);
-    A.fetch(used.data(), oused, (size_t)n_problems * 256);
+    A.fetch(used.data(), d_used, (size_t)n_problems * 256);
     for (int i = 0; i < n_problems; ++i) {
-        A.fetch(match_f[i], offs[i].om, (size_t)frames[i].n_f * 4);
-        A.fetch(&nmatches[i], offs[i].on, 4);
+        A.fetch(match_f[i], items[i].match_f, (size_t)frames[i].n_f * 4);
+        A.fetch(&nmatches[i], items[i].nmatches, 4);
     }
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
+    if ((st = A.end())) return st;
     for (int i = 0; i < n_problems; ++i)
         if (used[(size_t)i * 64] > 0) {   // overflow flag = a window population that did not fit its slice
             set_error("batched projection search: a search window of problem %d holds %d features, more than the %d "
@@ -3076,49 +3062,45 @@ int aos2_matcher_search_by_projection_last(aos2_matcher_t *m, const aos2_frame_v
     if ((st = check_levels(p->last_octave, p->n_last, cur->n_levels, "last_octave", p->last_valid))) return st;
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t fo[12];
-    fill_frame(A, cur, fo);
-    const size_t n = (size_t)p->n_last;
-    const size_t o0 = A.push(p->last_valid, n), o1 = A.push(p->desc, n * 32), o2 = A.push(p->has_obs, n);
-    const size_t o3 = A.push(p->world_pos, n * 12), o4 = A.push(p->last_angle, n * 4), o5 = A.push(p->last_octave, n * 4);
-    const size_t om = A.reserve_out((size_t)cur->n_f * 4 + 4), ob = A.reserve((size_t)cur->n_f * 4 + 4), on = A.reserve_out(8);
-    const size_t oslots = A.reserve((size_t)(p->n_last + 1) * sizeof(QuerySlot));
-    const size_t ochoice = A.reserve((size_t)(p->n_last + 1) * 4);
-    const size_t pool_cap = (size_t)p->n_last * (size_t)cur->n_f;
-    if (pool_cap > ((size_t)1 << 31) - 2) {   // (32-bit entry offsets: 16 GiB of the device's 288 GB)
-        set_error("projection search of %d points x %d features exceeds the pool's index range", p->n_last, cur->n_f);
-        return AOS2_ERR_CAPACITY;
-    }
-    if ((st = m->pool.alloc(pool_cap + 1))) return st;
-    if ((st = A.upload())) return st;
-    FrameDev F = frame_dev(A, cur, fo);
+    const size_t n = (size_t)p->n_last, pool_cap = n * (size_t)cur->n_f;
+    FrameDev F;
+    frame_dev(A, cur, F);
     ProjLastDev P{};
     P.n_last = p->n_last;
-    P.last_valid = A.dev<uint8_t>(o0); P.desc = A.dev<uint8_t>(o1); P.has_obs = A.dev<uint8_t>(o2);
-    P.world_pos = A.dev<float>(o3); P.last_angle = A.dev<float>(o4); P.last_octave = A.dev<int32_t>(o5);
+    A.in(P.last_valid, p->last_valid, n);
+    A.in(P.desc, p->desc, n * 32);
+    A.in(P.has_obs, p->has_obs, n);
+    A.in(P.world_pos, p->world_pos, n * 12);
+    A.in(P.last_angle, p->last_angle, n * 4);
+    A.in(P.last_octave, p->last_octave, n * 4);
     memcpy(P.Tcw, p->Tcw, sizeof(P.Tcw));
     memcpy(P.Tlw, p->Tlw, sizeof(P.Tlw));
     P.fx = p->fx; P.fy = p->fy; P.cx = p->cx; P.cy = p->cy; P.mb = p->mb; P.mbf = p->mbf;
-    int32_t *d_used = A.dev<int32_t>(on) + 1;
-    AOS2_HIP_CHECK(hipMemsetAsync(d_used, 0, 4, m->stream));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+    int32_t *d_match, *d_n, *d_choice;
+    uint32_t *d_bin;
+    QuerySlot *d_slots;
+    A.out(d_match, (size_t)cur->n_f * 4 + 4);
+    A.scratch(d_bin, (size_t)cur->n_f * 4 + 4);
+    A.out(d_n, 8);   // nmatches, entry counter
+    A.scratch(d_slots, (n + 1) * sizeof(QuerySlot));
+    A.scratch(d_choice, (n + 1) * 4);
+    Entry *d_pool;
+    if ((st = pool_reserve(m, pool_cap, "projection search from the last frame", d_pool))) return st;
+    if ((st = A.upload())) return st;
+    AOS2_HIP_CHECK(hipMemsetAsync(d_n + 1, 0, 4, m->stream));
+    if ((st = A.begin())) return st;
     if (p->n_last > 0)
-        hipLaunchKernelGGL(proj_last_entries_kernel, dim3(p->n_last), dim3(64), 0, m->stream, F, P, th, mono ? 1 : 0,
-                           A.dev<QuerySlot>(oslots), reinterpret_cast<Entry *>(m->pool.p), d_used, (int)pool_cap);
-    if ((size_t)cur->n_f * 8 <= kFixLdsBytes && !m->serial_resolve)
+        hipLaunchKernelGGL(proj_last_entries_kernel, dim3(p->n_last), dim3(64), 0, m->stream, F, P, th, mono ? 1 : 0, d_slots,
+                           d_pool, d_n + 1, (int)pool_cap);
+    if (use_fix_resolve(m, cur->n_f))
         hipLaunchKernelGGL(proj_last_resolve_fix_kernel, dim3(1), dim3(1024), (size_t)cur->n_f * 8 + 16, m->stream, F, P,
-                           m->check_ori, A.dev<QuerySlot>(oslots), reinterpret_cast<const Entry *>(m->pool.p),
-                           A.dev<int32_t>(om), A.dev<uint32_t>(ob), A.dev<int32_t>(on), A.dev<int32_t>(ochoice));
+                           m->check_ori, d_slots, d_pool, d_match, d_bin, d_n, d_choice);
     else
         hipLaunchKernelGGL(proj_last_resolve_kernel, dim3(1), dim3(64), (size_t)cur->n_f + 16, m->stream, F, P, m->check_ori,
-                           A.dev<QuerySlot>(oslots), reinterpret_cast<const Entry *>(m->pool.p), A.dev<int32_t>(om),
-                           A.dev<uint32_t>(ob), A.dev<int32_t>(on));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch(match_f, om, (size_t)cur->n_f * 4);
-    A.fetch(nmatches, on, 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+                           d_slots, d_pool, d_match, d_bin, d_n);
+    A.fetch(match_f, d_match, (size_t)cur->n_f * 4);
+    A.fetch(nmatches, d_n, 4);
+    return A.end();
 }
 
 // ---- projection family -------------------------------------------------
@@ -3133,37 +3115,33 @@ static int check_points(const aos2_proj_points_t *p, int mode)
     return AOS2_OK;
 }
 
-static ProjGenDev points_dev(Arena &A, const aos2_proj_points_t *p, int mode, int n_levels)
+// stages the point set and describes it in P (bound by the arena, like a frame).  Modes 0-4 are the searches; mode 5 is
+// Frame::isInFrustum, which has no descriptors: positions, ranges, normals and the first camera only.  An optional
+// array the caller left out (check_points says which a mode needs) stays a null pointer.
+static void points_dev(Arena &A, const aos2_proj_points_t *p, int mode, int n_levels, ProjGenDev &P)
 {
     const size_t n = (size_t)p->n_pts;
-    ProjGenDev P{};
+    const bool search = mode != 5;
+    P = ProjGenDev{};
     P.n_pts = p->n_pts;
     P.mode = mode;
-    const size_t o0 = A.push(p->valid, n), o1 = A.push(p->desc, n * 32), o2 = A.push(p->pos, n * 12);
-    const size_t o3 = A.push(p->max_dist, n * 4), o4 = A.push(p->min_dist, n * 4);
-    const size_t o5 = p->normal ? A.push(p->normal, n * 12) : 0, o6 = p->q_angle ? A.push(p->q_angle, n * 4) : 0;
-    const size_t o7 = p->inv_level_sigma2 ? A.push(p->inv_level_sigma2, (size_t)n_levels * 4) : 0;
-    // device pointers are resolved after the arena is uploaded: keep offsets in the pointer fields for now
-    P.valid = reinterpret_cast<const uint8_t *>(o0); P.desc = reinterpret_cast<const uint8_t *>(o1);
-    P.pos = reinterpret_cast<const float *>(o2); P.max_dist = reinterpret_cast<const float *>(o3);
-    P.min_dist = reinterpret_cast<const float *>(o4); P.normal = reinterpret_cast<const float *>(o5);
-    P.q_angle = reinterpret_cast<const float *>(o6); P.inv_level_sigma2 = reinterpret_cast<const float *>(o7);
+    if (search) {
+        A.in(P.valid, p->valid, n);
+        A.in(P.desc, p->desc, n * 32);
+    }
+    A.in(P.pos, p->pos, n * 12);
+    A.in(P.max_dist, p->max_dist, n * 4);
+    A.in(P.min_dist, p->min_dist, n * 4);
+    if (p->normal) A.in(P.normal, p->normal, n * 12);
+    if (search && p->q_angle) A.in(P.q_angle, p->q_angle, n * 4);
+    if (search && p->inv_level_sigma2) A.in(P.inv_level_sigma2, p->inv_level_sigma2, (size_t)n_levels * 4);
     memcpy(P.R, p->R, sizeof(P.R)); memcpy(P.t, p->t, sizeof(P.t)); memcpy(P.Ow, p->Ow, sizeof(P.Ow));
-    memcpy(P.R2, p->R2, sizeof(P.R2)); memcpy(P.t2, p->t2, sizeof(P.t2));
+    if (search) {
+        memcpy(P.R2, p->R2, sizeof(P.R2)); memcpy(P.t2, p->t2, sizeof(P.t2));
+        P.th = p->th;
+    }
     P.fx = p->fx; P.fy = p->fy; P.cx = p->cx; P.cy = p->cy; P.bf = p->bf;
     P.log_scale_factor = p->log_scale_factor;
-    P.th = p->th;
-    return P;
-}
-
-static void points_resolve(const Arena &A, ProjGenDev &P)
-{
-    auto fix = [&](auto *&ptr) {
-        using T = std::remove_reference_t<decltype(ptr)>;
-        ptr = reinterpret_cast<T>(A.m->arena.p + reinterpret_cast<size_t>(ptr));
-    };
-    fix(P.valid); fix(P.desc); fix(P.pos); fix(P.max_dist); fix(P.min_dist); fix(P.normal); fix(P.q_angle);
-    fix(P.inv_level_sigma2);
 }
 
 // independent points: modes 0 (Fuse), 1 (Fuse with Scw)
@@ -3182,21 +3160,18 @@ int aos2_matcher_fuse(aos2_matcher_t *m, const aos2_frame_view_t *kf, const aos2
     if (p->n_pts == 0) return AOS2_OK;
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t fo[12];
-    fill_frame(A, kf, fo);
-    ProjGenDev P = points_dev(A, p, mode, kf->n_levels);
-    const size_t ob = A.reserve((size_t)p->n_pts * 8 + 8);
+    FrameDev F;
+    ProjGenDev P;
+    int32_t *d_best;   // best_idx | best_dist
+    frame_dev(A, kf, F);
+    points_dev(A, p, mode, kf->n_levels, P);
+    A.scratch(d_best, (size_t)p->n_pts * 8 + 8);
     if ((st = A.upload())) return st;
-    points_resolve(A, P);
-    FrameDev F = frame_dev(A, kf, fo);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(projgen_best_kernel, dim3(p->n_pts), dim3(64), 0, m->stream, F, P, TH_LOW, A.dev<int32_t>(ob),
-                       A.dev<int32_t>(ob) + p->n_pts);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(best_idx, A.dev<int32_t>(ob), (size_t)p->n_pts * 4);
-    A.fetch_dev(best_dist, A.dev<int32_t>(ob) + p->n_pts, (size_t)p->n_pts * 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(projgen_best_kernel, dim3(p->n_pts), dim3(64), 0, m->stream, F, P, TH_LOW, d_best, d_best + p->n_pts);
+    A.fetch(best_idx, d_best, (size_t)p->n_pts * 4);
+    A.fetch(best_dist, d_best + p->n_pts, (size_t)p->n_pts * 4);
+    if ((st = A.end())) return st;
     if (n_fused) {
         int c = 0;
         for (int i = 0; i < p->n_pts; ++i) c += best_idx[i] >= 0;
@@ -3223,31 +3198,29 @@ int aos2_matcher_search_by_sim3(aos2_matcher_t *m, const aos2_frame_view_t *kf1,
     if (p12->n_pts == 0) return AOS2_OK;
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t f1o[12], f2o[12];
-    fill_frame(A, kf1, f1o);
-    fill_frame(A, kf2, f2o);
-    ProjGenDev P12 = points_dev(A, p12, 3, kf2->n_levels), P21 = points_dev(A, p21, 3, kf1->n_levels);
     const size_t n1 = (size_t)p12->n_pts, n2 = (size_t)p21->n_pts;
-    const size_t o1 = A.reserve((n1 + 1) * 8), o2 = A.reserve((n2 + 1) * 8), om = A.reserve((n1 + 1) * 4), on = A.reserve(8);
+    FrameDev F1, F2;
+    ProjGenDev P12, P21;
+    int32_t *d_best1, *d_best2, *d_match, *d_n;
+    frame_dev(A, kf1, F1);
+    frame_dev(A, kf2, F2);
+    points_dev(A, p12, 3, kf2->n_levels, P12);
+    points_dev(A, p21, 3, kf1->n_levels, P21);
+    A.scratch(d_best1, (n1 + 1) * 8);
+    A.scratch(d_best2, (n2 + 1) * 8);
+    A.scratch(d_match, (n1 + 1) * 4);
+    A.scratch(d_n, 8);
     if ((st = A.upload())) return st;
-    points_resolve(A, P12);
-    points_resolve(A, P21);
-    FrameDev F1 = frame_dev(A, kf1, f1o), F2 = frame_dev(A, kf2, f2o);
-    AOS2_HIP_CHECK(hipMemsetAsync(A.dev<int32_t>(on), 0, 8, m->stream));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(projgen_best_kernel, dim3((unsigned)n1), dim3(64), 0, m->stream, F2, P12, TH_HIGH, A.dev<int32_t>(o1),
-                       A.dev<int32_t>(o1) + n1);
+    AOS2_HIP_CHECK(hipMemsetAsync(d_n, 0, 8, m->stream));
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(projgen_best_kernel, dim3((unsigned)n1), dim3(64), 0, m->stream, F2, P12, TH_HIGH, d_best1, d_best1 + n1);
     if (n2 > 0)
-        hipLaunchKernelGGL(projgen_best_kernel, dim3((unsigned)n2), dim3(64), 0, m->stream, F1, P21, TH_HIGH, A.dev<int32_t>(o2),
-                           A.dev<int32_t>(o2) + n2);
-    hipLaunchKernelGGL(sim3_agree_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, A.dev<int32_t>(o1),
-                       A.dev<int32_t>(o2), (int)n1, (int)n2, A.dev<int32_t>(om), A.dev<int32_t>(on));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(match12, A.dev<int32_t>(om), n1 * 4);
-    A.fetch_dev(n_found, A.dev<int32_t>(on), 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+        hipLaunchKernelGGL(projgen_best_kernel, dim3((unsigned)n2), dim3(64), 0, m->stream, F1, P21, TH_HIGH, d_best2, d_best2 + n2);
+    hipLaunchKernelGGL(sim3_agree_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, d_best1, d_best2, (int)n1,
+                       (int)n2, d_match, d_n);
+    A.fetch(match12, d_match, n1 * 4);
+    A.fetch(n_found, d_n, 4);
+    return A.end();
 }
 
 int aos2_frame_assign_features_to_grid(aos2_matcher_t *m, int n, const float *kp_x, const float *kp_y, float min_x,
@@ -3266,18 +3239,19 @@ int aos2_frame_assign_features_to_grid(aos2_matcher_t *m, int n, const float *kp
     if (st) return st;
     constexpr int NC = GRID_COLS * GRID_ROWS;
     Arena A{m};
-    const size_t ox = A.push(kp_x, (size_t)n * 4), oy = A.push(kp_y, (size_t)n * 4);
-    const size_t oo = A.reserve((size_t)(NC + 1) * 4), oi = A.reserve((size_t)n * 4 + 4);
+    const float *d_x, *d_y;
+    int32_t *d_off, *d_idx;
+    A.in(d_x, kp_x, (size_t)n * 4);
+    A.in(d_y, kp_y, (size_t)n * 4);
+    A.scratch(d_off, (size_t)(NC + 1) * 4);
+    A.scratch(d_idx, (size_t)n * 4 + 4);
     if ((st = A.upload())) return st;
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(assign_grid_kernel, dim3(1), dim3(256), (size_t)(NC + 1) * 4 + (size_t)n * 2 + 16, m->stream, n,
-                       A.dev<float>(ox), A.dev<float>(oy), min_x, min_y, grid_w_inv, grid_h_inv, A.dev<int32_t>(oo),
-                       A.dev<int32_t>(oi));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(grid_off, A.dev<int32_t>(oo), (size_t)(NC + 1) * 4);
-    if (n > 0) A.fetch_dev(grid_idx, A.dev<int32_t>(oi), (size_t)n * 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(assign_grid_kernel, dim3(1), dim3(256), (size_t)(NC + 1) * 4 + (size_t)n * 2 + 16, m->stream, n, d_x, d_y,
+                       min_x, min_y, grid_w_inv, grid_h_inv, d_off, d_idx);
+    A.fetch(grid_off, d_off, (size_t)(NC + 1) * 4);
+    if (n > 0) A.fetch(grid_idx, d_idx, (size_t)n * 4);
+    if ((st = A.end())) return st;
     if (n_in_grid) *n_in_grid = grid_off[NC];
     return AOS2_OK;
 }
@@ -3299,18 +3273,20 @@ int aos2_frame_stereo_from_rgbd(aos2_matcher_t *m, int n, const float *kp_x, con
     int st = matcher_init(m);
     if (st) return st;
     Arena A{m};
-    const size_t ox = A.push(kp_x, (size_t)n * 4), oy = A.push(kp_y, (size_t)n * 4), ou = A.push(kpun_x, (size_t)n * 4);
-    const size_t od = A.push(depth_img, (size_t)stride * h * 4), oo = A.reserve((size_t)n * 8 + 8);
+    const float *d_x, *d_y, *d_xun, *d_img;
+    float *d_out;   // u_right | depth
+    A.in(d_x, kp_x, (size_t)n * 4);
+    A.in(d_y, kp_y, (size_t)n * 4);
+    A.in(d_xun, kpun_x, (size_t)n * 4);
+    A.in(d_img, depth_img, (size_t)stride * h * 4);
+    A.scratch(d_out, (size_t)n * 8 + 8);
     if ((st = A.upload())) return st;
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(stereo_from_rgbd_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, n, A.dev<float>(ox),
-                       A.dev<float>(oy), A.dev<float>(ou), A.dev<float>(od), stride, mbf, A.dev<float>(oo), A.dev<float>(oo) + n);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(u_right, A.dev<float>(oo), (size_t)n * 4);
-    A.fetch_dev(depth, A.dev<float>(oo) + n, (size_t)n * 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(stereo_from_rgbd_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, n, d_x, d_y, d_xun, d_img, stride,
+                       mbf, d_out, d_out + n);
+    A.fetch(u_right, d_out, (size_t)n * 4);
+    A.fetch(depth, d_out + n, (size_t)n * 4);
+    return A.end();
 }
 
 int aos2_frame_is_in_frustum(aos2_matcher_t *m, const aos2_proj_points_t *p, float min_x, float max_x, float min_y,
@@ -3335,41 +3311,24 @@ int aos2_frame_is_in_frustum(aos2_matcher_t *m, const aos2_proj_points_t *p, flo
     if ((st = matcher_init(m))) return st;
     Arena A{m};
     const size_t n = (size_t)p->n_pts;
-    ProjGenDev P{};
-    {
-        P.n_pts = p->n_pts;
-        P.mode = 5;
-        const size_t o2 = A.push(p->pos, n * 12), o3 = A.push(p->max_dist, n * 4), o4 = A.push(p->min_dist, n * 4),
-                     o5 = A.push(p->normal, n * 12);
-        P.pos = reinterpret_cast<const float *>(o2); P.max_dist = reinterpret_cast<const float *>(o3);
-        P.min_dist = reinterpret_cast<const float *>(o4); P.normal = reinterpret_cast<const float *>(o5);
-        memcpy(P.R, p->R, sizeof(P.R)); memcpy(P.t, p->t, sizeof(P.t)); memcpy(P.Ow, p->Ow, sizeof(P.Ow));
-        P.fx = p->fx; P.fy = p->fy; P.cx = p->cx; P.cy = p->cy; P.bf = p->bf;
-        P.log_scale_factor = p->log_scale_factor;
-    }
-    const size_t oo = A.reserve(n * 24 + 64);
+    ProjGenDev P;
+    float *d_px;   // proj_x | proj_y | proj_xr | view_cos | pred_level | track_in_view
+    points_dev(A, p, 5, n_levels, P);
+    A.scratch(d_px, n * 24 + 64);
     if ((st = A.upload())) return st;
-    uint8_t *base = m->arena.p;
-    P.pos = reinterpret_cast<const float *>(base + reinterpret_cast<size_t>(P.pos));
-    P.max_dist = reinterpret_cast<const float *>(base + reinterpret_cast<size_t>(P.max_dist));
-    P.min_dist = reinterpret_cast<const float *>(base + reinterpret_cast<size_t>(P.min_dist));
-    P.normal = reinterpret_cast<const float *>(base + reinterpret_cast<size_t>(P.normal));
-    float *d_px = A.dev<float>(oo), *d_py = d_px + n, *d_pr = d_py + n, *d_vc = d_pr + n;
+    float *d_py = d_px + n, *d_pr = d_py + n, *d_vc = d_pr + n;
     int32_t *d_lv = reinterpret_cast<int32_t *>(d_vc + n);
     uint8_t *d_iv = reinterpret_cast<uint8_t *>(d_lv + n);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+    if ((st = A.begin())) return st;
     hipLaunchKernelGGL(is_in_frustum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, P, min_x, max_x, min_y,
                        max_y, n_levels, viewing_cos_limit, d_iv, d_px, d_py, d_pr, d_lv, d_vc);
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(proj_x, d_px, n * 4);
-    A.fetch_dev(proj_y, d_py, n * 4);
-    A.fetch_dev(proj_xr, d_pr, n * 4);
-    A.fetch_dev(view_cos, d_vc, n * 4);
-    A.fetch_dev(pred_level, d_lv, n * 4);
-    A.fetch_dev(track_in_view, d_iv, n);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    A.fetch(proj_x, d_px, n * 4);
+    A.fetch(proj_y, d_py, n * 4);
+    A.fetch(proj_xr, d_pr, n * 4);
+    A.fetch(view_cos, d_vc, n * 4);
+    A.fetch(pred_level, d_lv, n * 4);
+    A.fetch(track_in_view, d_iv, n);
+    return A.end();
 }
 
 // greedy modes 2 (SearchByProjection(pKF, Scw, ...)) and 4 (SearchByProjection(CurrentFrame, pKF, ...))
@@ -3385,44 +3344,36 @@ static int projgen_serial(aos2_matcher_t *m, const aos2_frame_view_t *f, const a
     if ((st = check_points(p, mode))) return st;
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t fo[12];
-    fill_frame(A, f, fo);
-    ProjGenDev P = points_dev(A, p, mode, f->n_levels);
-    const size_t om = A.reserve((size_t)f->n_f * 4 + 4), ob = A.reserve((size_t)f->n_f * 4 + 4), on = A.reserve(8);
-    const size_t oslots = A.reserve((size_t)(p->n_pts + 1) * sizeof(QuerySlot));
-    const size_t ochoice = A.reserve((size_t)(p->n_pts + 1) * 4);
+    // one slice of n_f entries per point, so that no window can overflow its slice
     const size_t pool_cap = (size_t)p->n_pts * (size_t)f->n_f;
-    // one slice of n_f entries per point, so that no window can overflow its slice (entry offsets are 32-bit: 2^31 entries =
-    // 16 GiB of the device's 288 GB; beyond that AOS2_ERR_CAPACITY, below it only the allocation itself can fail)
-    if (pool_cap > ((size_t)1 << 31) - 2) {
-        set_error("projection search of %d points x %d features: %zu candidate entries exceed the pool's index range", p->n_pts, f->n_f, pool_cap);
-        return AOS2_ERR_CAPACITY;
-    }
-    if ((st = m->pool.alloc(pool_cap + 1))) return st;
+    FrameDev F;
+    ProjGenDev P;
+    int32_t *d_match, *d_bin, *d_n, *d_choice;
+    QuerySlot *d_slots;
+    frame_dev(A, f, F);
+    points_dev(A, p, mode, f->n_levels, P);
+    A.scratch(d_match, (size_t)f->n_f * 4 + 4);
+    A.scratch(d_bin, (size_t)f->n_f * 4 + 4);
+    A.scratch(d_n, 8);   // nmatches, entry counter
+    A.scratch(d_slots, (size_t)(p->n_pts + 1) * sizeof(QuerySlot));
+    A.scratch(d_choice, (size_t)(p->n_pts + 1) * 4);
+    Entry *d_pool;
+    if ((st = pool_reserve(m, pool_cap, "projection search from a keyframe", d_pool))) return st;
     if ((st = A.upload())) return st;
-    points_resolve(A, P);
-    FrameDev F = frame_dev(A, f, fo);
-    int32_t *d_used = A.dev<int32_t>(on) + 1;
-    AOS2_HIP_CHECK(hipMemsetAsync(d_used, 0, 4, m->stream));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
+    AOS2_HIP_CHECK(hipMemsetAsync(d_n + 1, 0, 4, m->stream));
+    if ((st = A.begin())) return st;
     if (p->n_pts > 0)
-        hipLaunchKernelGGL(projgen_entries_kernel, dim3(p->n_pts), dim3(64), 0, m->stream, F, P, A.dev<QuerySlot>(oslots),
-                           reinterpret_cast<Entry *>(m->pool.p), d_used, (int)pool_cap);
-    if ((size_t)f->n_f * 8 <= kFixLdsBytes && !m->serial_resolve)
+        hipLaunchKernelGGL(projgen_entries_kernel, dim3(p->n_pts), dim3(64), 0, m->stream, F, P, d_slots, d_pool, d_n + 1,
+                           (int)pool_cap);
+    if (use_fix_resolve(m, f->n_f))
         hipLaunchKernelGGL(projgen_resolve_fix_kernel, dim3(1), dim3(1024), (size_t)f->n_f * 8 + 16, m->stream, F, P, thr, check_ori,
-                       A.dev<QuerySlot>(oslots), reinterpret_cast<const Entry *>(m->pool.p), A.dev<int32_t>(om),
-                       A.dev<int32_t>(ob), A.dev<int32_t>(on), A.dev<int32_t>(ochoice));
+                           d_slots, d_pool, d_match, d_bin, d_n, d_choice);
     else
-        hipLaunchKernelGGL(projgen_resolve_kernel, dim3(1), dim3(64), (size_t)f->n_f + 16, m->stream, F, P, thr, check_ori,
-                       A.dev<QuerySlot>(oslots), reinterpret_cast<const Entry *>(m->pool.p), A.dev<int32_t>(om),
-                       A.dev<int32_t>(ob), A.dev<int32_t>(on));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    if (f->n_f > 0)
-        A.fetch_dev(match_f, A.dev<int32_t>(om), (size_t)f->n_f * 4);
-    A.fetch_dev(nmatches, A.dev<int32_t>(on), 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+        hipLaunchKernelGGL(projgen_resolve_kernel, dim3(1), dim3(64), (size_t)f->n_f + 16, m->stream, F, P, thr, check_ori, d_slots,
+                           d_pool, d_match, d_bin, d_n);
+    if (f->n_f > 0) A.fetch(match_f, d_match, (size_t)f->n_f * 4);
+    A.fetch(nmatches, d_n, 4);
+    return A.end();
 }
 
 int aos2_matcher_search_by_projection_kf(aos2_matcher_t *m, const aos2_frame_view_t *kf, const aos2_proj_points_t *p,
@@ -3459,38 +3410,32 @@ int aos2_matcher_search_for_initialization(aos2_matcher_t *m, const aos2_frame_v
     }
     if ((st = matcher_init(m))) return st;
     Arena A{m};
-    size_t fo[12];
-    fill_frame(A, f2, fo);
-    const size_t n = (size_t)n1;
-    const size_t o0 = A.push(desc1, n * 32), o1 = A.push(octave1, n * 4), o2 = A.push(angle1, n * 4), o3 = A.push(prev_xy, n * 8);
-    const size_t om = A.reserve(n * 8 + 8), on = A.reserve(8);
-    const size_t oslots = A.reserve((n + 1) * sizeof(QuerySlot));
-    const size_t pool_cap = n * (size_t)f2->n_f;
-    if (pool_cap > ((size_t)1 << 31) - 2) {   // (32-bit entry offsets: 16 GiB of the device's 288 GB)
-        set_error("initialization search of %d x %d features exceeds the pool's index range", n1, f2->n_f);
-        return AOS2_ERR_CAPACITY;
-    }
-    if ((st = m->pool.alloc(pool_cap + 1))) return st;
-    if ((st = A.upload())) return st;
-    FrameDev F = frame_dev(A, f2, fo);
+    const size_t n = (size_t)n1, pool_cap = n * (size_t)f2->n_f;
+    FrameDev F;
     InitDev P{};
+    int32_t *d_match, *d_n;   // match12 | match21; nmatches, entry counter
+    QuerySlot *d_slots;
+    frame_dev(A, f2, F);
     P.n1 = n1;
-    P.desc1 = A.dev<uint8_t>(o0); P.octave1 = A.dev<int32_t>(o1); P.angle1 = A.dev<float>(o2); P.prev_xy = A.dev<float>(o3);
     P.window = (float)window_size;
-    int32_t *d_used = A.dev<int32_t>(on) + 1;
-    AOS2_HIP_CHECK(hipMemsetAsync(d_used, 0, 4, m->stream));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[0], m->stream));
-    hipLaunchKernelGGL(init_entries_kernel, dim3(n1), dim3(64), 0, m->stream, F, P, A.dev<QuerySlot>(oslots),
-                       reinterpret_cast<Entry *>(m->pool.p), d_used, (int)pool_cap);
-    hipLaunchKernelGGL(init_resolve_kernel, dim3(1), dim3(64), (size_t)f2->n_f * 4 + 16, m->stream, F, P, m->nnratio,
-                       m->check_ori, A.dev<QuerySlot>(oslots), reinterpret_cast<const Entry *>(m->pool.p), A.dev<int32_t>(om),
-                       A.dev<int32_t>(om) + n1, A.dev<int32_t>(on));
-    AOS2_HIP_CHECK(hipEventRecord(m->ev[1], m->stream));
-    A.fetch_dev(match12, A.dev<int32_t>(om), n * 4);
-    A.fetch_dev(nmatches, A.dev<int32_t>(on), 4);
-    if ((st = A.finish())) return st;
-    (void)hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]);
-    return AOS2_OK;
+    A.in(P.desc1, desc1, n * 32);
+    A.in(P.octave1, octave1, n * 4);
+    A.in(P.angle1, angle1, n * 4);
+    A.in(P.prev_xy, prev_xy, n * 8);
+    A.scratch(d_match, n * 8 + 8);
+    A.scratch(d_n, 8);
+    A.scratch(d_slots, (n + 1) * sizeof(QuerySlot));
+    Entry *d_pool;
+    if ((st = pool_reserve(m, pool_cap, "initialization search", d_pool))) return st;
+    if ((st = A.upload())) return st;
+    AOS2_HIP_CHECK(hipMemsetAsync(d_n + 1, 0, 4, m->stream));
+    if ((st = A.begin())) return st;
+    hipLaunchKernelGGL(init_entries_kernel, dim3(n1), dim3(64), 0, m->stream, F, P, d_slots, d_pool, d_n + 1, (int)pool_cap);
+    hipLaunchKernelGGL(init_resolve_kernel, dim3(1), dim3(64), (size_t)f2->n_f * 4 + 16, m->stream, F, P, m->nnratio, m->check_ori,
+                       d_slots, d_pool, d_match, d_match + n1, d_n);
+    A.fetch(match12, d_match, n * 4);
+    A.fetch(nmatches, d_n, 4);
+    return A.end();
 }
 
 }  // extern "C"

@@ -52,6 +52,50 @@ def test_search_by_bow_vs_oracle(pkg, oracle, gpu):
     assert n == int(g["nmatches"]) and (match == g["match"]).all()
 
 
+def test_hamming_best2_device_vs_bruteforce(pkg, gpu):
+    """aos2_matcher_hamming_best2_device: queries, targets and results are device arrays used in place (several query
+    blocks and target splits, neither size a multiple of its tile; an exact tie goes to the lowest index)"""
+    import torch
+    rng = np.random.default_rng(1)
+    S = pkg.synth
+    nq, nt = 513, 4099
+    q, t = S.synth_descriptors(rng, nq), S.synth_descriptors(rng, nt)
+    t[: nq // 2] = S.flip_bits(rng, q[: nq // 2], 0.05)
+    t[5] = t[3]
+    dq, dt = torch.from_numpy(q).cuda(), torch.from_numpy(t).cuda()
+    out = torch.full((3, nq), -7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ms = pkg.Matcher().hamming_best2_device(dq.data_ptr(), nq, dt.data_ptr(), nt, out[0].data_ptr(), out[1].data_ptr(),
+                                            out[2].data_ptr(), iters=2)
+    bi, bd, sd = out.cpu().numpy()
+    D = np.unpackbits(q[:, None, :] ^ t[None, :, :], axis=2).sum(axis=2)
+    assert (bi == D.argmin(axis=1)).all() and (bd == D.min(axis=1)).all() and (sd == np.sort(D, axis=1)[:, 1]).all()
+    assert ms > 0
+
+
+def test_search_by_bow_device_vs_oracle(pkg, oracle, gpu):
+    """aos2_matcher_search_by_bow_device: descriptors and key angles of the pairs are device arrays used in place, the
+    FeatureVectors and kf_has_mp stay host arrays -- several pairs of different sizes in one call, one of them with a
+    single vocabulary node (every feature in one bucket)"""
+    import torch
+    S = pkg.synth
+    probs = [S.synth_bow_problem(80, 700, 640, n_nodes=50), S.synth_bow_problem(81, 300, 900, n_nodes=1, nnratio=0.7),
+             S.synth_bow_problem(82, 1000, 130, n_nodes=7)]
+    keep, pairs = [], []
+    for p in probs:
+        d = {k: p[k] for k in ("kf_has_mp", "node_id_kf", "node_off_kf", "node_idx_kf", "node_id_f", "node_off_f", "node_idx_f")}
+        d["n_kf"], d["n_f"] = len(p["desc_kf"]), len(p["desc_f"])
+        for k, dt in (("desc_kf", np.uint8), ("desc_f", np.uint8), ("angle_kf", np.float32), ("angle_f", np.float32)):
+            keep.append(torch.from_numpy(np.ascontiguousarray(p[k], dt)).cuda())
+            d[k] = keep[-1].data_ptr()
+        pairs.append(d)
+    torch.cuda.synchronize()
+    res = pkg.Matcher(0.7, True).SearchByBoWDevice(pairs)
+    for p, (n, match) in zip(probs, res):
+        on, om = oracle.search_by_bow(p)
+        assert n == on and (match == om).all() and n > 0
+
+
 def test_search_by_projection_vs_oracle(pkg, oracle, gpu):
     S = pkg.synth
     for seed in range(6):
