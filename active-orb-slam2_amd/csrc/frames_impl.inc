@@ -830,11 +830,7 @@ __global__ __launch_bounds__(256) void frames_triang_match_kernel(FramesDev A, F
         const int32_t *bucket = fv_idx2 + o2 + f_beg;
         const Desc d1 = load_desc(A.desc + (o1 + i1) * 32);
         const float kx = A.kp_x[o1 + i1], ky = A.kp_y[o1 + i1];
-        // epipolar line l = x1' F12 (:142-144)
-        const float a = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[0]), __fmul_rn(ky, P.F12[3])), P.F12[6]);
-        const float b = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[1]), __fmul_rn(ky, P.F12[4])), P.F12[7]);
-        const float c = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[2]), __fmul_rn(ky, P.F12[5])), P.F12[8]);
-        const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+        const EpiLine line = epi_line(P.F12, kx, ky);
         int bestDist = TH_LOW;
         for (int j = 0; j < f_cnt; ++j) {
             const int idx2 = bucket[j];
@@ -843,18 +839,10 @@ __global__ __launch_bounds__(256) void frames_triang_match_kernel(FramesDev A, F
             if (only_stereo && !bStereo2) continue;
             const int dist = hamming(d1, load_desc(B.desc + (o2 + idx2) * 32));
             if (dist > TH_LOW || dist > bestDist) continue;           // :734
-            const float x2 = B.kp_x[o2 + idx2], y2 = B.kp_y[o2 + idx2];
-            const int oct = B.kp_octave[o2 + idx2];
-            const float sf = B.scale_factors[oct];
-            if (!bStereo1 && !bStereo2) {                             // too close to the epipole (:739-745)
-                const float dx = __fsub_rn(P.ex, x2), dy = __fsub_rn(P.ey, y2);
-                if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.0f, sf)) continue;
-            }
-            const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, x2), __fmul_rn(b, y2)), c);   // CheckDistEpipolarLine :139-157
-            if (den == 0.0f) continue;
-            const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-            const float sigma2 = __fmul_rn(sf, sf);                   // mvLevelSigma2[i] = mvScaleFactor[i] * mvScaleFactor[i] (ORBextractor.cc:420)
-            if (!((double)dsqr < __dmul_rn(3.84, (double)sigma2))) continue;
+            const float sf = B.scale_factors[B.kp_octave[o2 + idx2]];
+            // mvLevelSigma2[i] = mvScaleFactor[i] * mvScaleFactor[i] (ORBextractor.cc:420)
+            if (!epi_admits(line, B.kp_x[o2 + idx2], B.kp_y[o2 + idx2], !bStereo1 && !bStereo2, P.ex, P.ey, sf, __fmul_rn(sf, sf)))
+                continue;
             best = idx2;
             bestDist = dist;
         }
@@ -866,37 +854,9 @@ __global__ __launch_bounds__(256) void frames_triang_match_kernel(FramesDev A, F
 __global__ __launch_bounds__(64) void frames_triang_finish_kernel(FramesDev A, FramesDev B, const FrTriPair *__restrict__ pairs, int check_ori,
                                                                   int32_t *__restrict__ match12, int32_t *__restrict__ nmatches)
 {
-    __shared__ int histo[HISTO];
     const FrTriPair &P = pairs[blockIdx.x];
-    const int lane = threadIdx.x, n1 = A.n[P.kf1];
-    const float *ang1 = A.kp_angle + (size_t)P.kf1 * A.cap, *ang2 = B.kp_angle + (size_t)P.kf2 * B.cap;
-    int32_t *m12 = match12 + (size_t)blockIdx.x * A.cap;
-    if (lane < HISTO) histo[lane] = 0;
-    __syncthreads();
-    int cnt = 0;
-    for (int i = lane; i < n1; i += 64) {
-        const int m2 = m12[i];
-        if (m2 >= 0) {
-            cnt++;
-            if (check_ori) atomicAdd(&histo[rot_bin(__fsub_rn(ang1[i], ang2[m2]))], 1);
-        }
-    }
-    __syncthreads();
-    cnt = wave_sum_i32(cnt);
-    if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        for (int i = lane; i < n1; i += 64) {
-            const int m2 = m12[i];
-            if (m2 >= 0) {
-                const int bin = rot_bin(__fsub_rn(ang1[i], ang2[m2]));
-                if (bin != i1 && bin != i2 && bin != i3) m12[i] = -1;
-            }
-        }
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) cnt -= histo[i];
-    }
-    if (lane == 0) nmatches[blockIdx.x] = cnt;
+    triang_finish_body(A.n[P.kf1], A.kp_angle + (size_t)P.kf1 * A.cap, B.kp_angle + (size_t)P.kf2 * B.cap,
+                       match12 + (size_t)blockIdx.x * A.cap, nmatches + blockIdx.x, check_ori);
 }
 
 __device__ const uint8_t k_valid_one = 1;

@@ -44,6 +44,9 @@ __device__ __forceinline__ int hamming(const Desc &a, const Desc &b)
     return d;
 }
 
+// Hamming distance of a key; "no candidate" reads as 256, above every real distance
+__device__ __forceinline__ int key_dist(uint32_t k) { return k == KEY_NONE ? 256 : (int)(k >> 20); }
+
 // merge two (smallest, second smallest) pairs
 __device__ __forceinline__ void merge2(uint32_t &k1, uint32_t &k2, uint32_t o1, uint32_t o2)
 {
@@ -138,8 +141,8 @@ __global__ void hamming_merge_kernel(const uint32_t *__restrict__ part1, const u
     uint32_t k1 = KEY_NONE, k2 = KEY_NONE;
     for (int s = 0; s < splits; ++s) merge2(k1, k2, part1[(size_t)s * nq + qi], part2[(size_t)s * nq + qi]);
     best_idx[qi] = k1 == KEY_NONE ? -1 : (int32_t)(k1 & 0xfffff);
-    best_dist[qi] = k1 == KEY_NONE ? 256 : (int32_t)(k1 >> 20);
-    second_dist[qi] = k2 == KEY_NONE ? 256 : (int32_t)(k2 >> 20);
+    best_dist[qi] = key_dist(k1);
+    second_dist[qi] = key_dist(k2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -179,6 +182,51 @@ __device__ __forceinline__ void three_maxima(const int *histo, int &ind1, int &i
     }
 }
 
+// The rotation-consistency verdict of a finished histogram: bit b of `culled` = bin b is none of the three maxima, `removed`
+// = the pushed entries of those bins -- nmatches drops once per pushed entry (:281, :650, :1459-1460), not once per match.
+struct RotCull {
+    uint32_t culled;
+    int removed;
+};
+
+__device__ __forceinline__ RotCull rot_cull(const int *histo)
+{
+    int i1, i2, i3;
+    three_maxima(histo, i1, i2, i3);
+    RotCull c{0, 0};
+    for (int i = 0; i < HISTO; ++i)
+        if (i != i1 && i != i2 && i != i3) {
+            c.culled |= 1u << i;
+            c.removed += histo[i];
+        }
+    return c;
+}
+
+// Reset the matches of the culled bins to `null_v`; thread `tid` of `nt` takes every nt-th element.
+// bins[i] = bit mask of the bins element i was pushed into (it goes if ANY of them is culled)
+__device__ __forceinline__ void cull_by_mask(uint32_t culled, const uint32_t *bins, int32_t *match, int n, int tid, int nt,
+                                             int32_t null_v)
+{
+    for (int i = tid; i < n; i += nt)
+        if (bins[i] & culled) match[i] = null_v;
+}
+
+// bin1[i] = bin + 1 of element i, 0 = never pushed.  Returns how many still-set matches this thread reset (a caller
+// whose matches can be withdrawn after the push counts its drops with it; the others ignore it).
+__device__ __forceinline__ int cull_by_bin1(uint32_t culled, const int32_t *bin1, int32_t *match, int n, int tid, int nt,
+                                            int32_t null_v)
+{
+    int drop = 0;
+    for (int i = tid; i < n; i += nt) {
+        const int bn = bin1[i];
+        if (bn > 0 && ((culled >> (bn - 1)) & 1u)) {
+            drop += match[i] >= 0;
+            match[i] = null_v;
+        }
+    }
+    return drop;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Two-stage structure of the three search methods (SURVEY.md App. E option (a)):
 //   stage A (parallel, one wave per query): enumerate the query's candidates in the reference's
@@ -194,6 +242,46 @@ struct Entry {
     uint32_t key;      // dist << 20 | position, KEY_NONE = rejected before the distance test
     uint32_t payload;  // feature index | octave << 24
 };
+
+// Stage B, one query: the two smallest keys among the candidates `admit` lets through.  Every lane keeps the two smallest of
+// its own candidates (and their payloads), the wave reduces the keys; keys are unique (they carry the visiting position), so
+// a key names the lane that holds its payload.  A caller that never asks for payload2() leaves my2 / p2 dead, and the
+// compiler drops their bookkeeping.
+struct WaveBest2 {
+    uint32_t k1, k2;            // the wave's smallest / second smallest key (uniform), KEY_NONE = none
+    uint32_t my1, my2, p1, p2;  // this lane's own two and their payloads
+    __device__ __forceinline__ uint32_t payload1() const { return read_owner(p1, __ballot(my1 == k1)); }   // k1 != KEY_NONE
+    __device__ __forceinline__ uint32_t payload2() const                                                    // k2 != KEY_NONE
+    {
+        const unsigned long long first = __ballot(my1 == k2);   // the wave's second is some lane's first or second
+        return first ? read_owner(p1, first) : read_owner(p2, __ballot(my2 == k2));
+    }
+};
+
+// ent[0 .. cnt) = the query's entries, e = this lane's entry of the first 64 (prefetched); admit(entry) is asked for the
+// entries inside the list only
+template <class Admit>
+__device__ __forceinline__ WaveBest2 wave_best2(const Entry *__restrict__ ent, int cnt, Entry e, int lane, Admit admit)
+{
+    WaveBest2 r;
+    r.my1 = r.my2 = KEY_NONE;
+    r.p1 = r.p2 = 0;
+    for (int j0 = 0; j0 < cnt; j0 += 64) {
+        if (j0 > 0) e = (j0 + lane < cnt) ? ent[j0 + lane] : Entry{KEY_NONE, 0};
+        if (j0 + lane < cnt && admit(e)) {
+            if (e.key < r.my1) {
+                r.my2 = r.my1; r.p2 = r.p1;
+                r.my1 = e.key; r.p1 = e.payload;
+            } else if (e.key < r.my2) {
+                r.my2 = e.key; r.p2 = e.payload;
+            }
+        }
+    }
+    r.k1 = r.my1;
+    r.k2 = r.my2;
+    wave_min2(r.k1, r.k2);
+    return r;
+}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -227,22 +315,37 @@ __device__ __forceinline__ Best2 best2_unpack(unsigned long long b1, unsigned lo
     return Best2{(uint32_t)(b1 >> 32), (uint32_t)(b2 >> 32), (uint32_t)b1, (uint32_t)b2};
 }
 
-// 8 entries per memory round trip (a window / bucket rarely holds more); all B reads are issued together
+// entries [j0, j0 + W) of a list of cnt, KEY_NONE beyond its end: W loads in one memory round trip
+template <int W>
+__device__ __forceinline__ void load_entries(const Entry *ent, int j0, int cnt, Entry (&eb)[W])
+{
+#pragma unroll
+    for (int u = 0; u < W; ++u) eb[u] = j0 + u < cnt ? ent[j0 + u] : Entry{KEY_NONE, 0};
+}
+
+// the valid entries of eb[] that are free for query q (B[feature] >= q) go into the running pair; all B reads are issued together
+template <int W>
+__device__ __forceinline__ void scan_free(const Entry (&eb)[W], const int32_t *B, int q, uint32_t idx_mask,
+                                          unsigned long long &b1, unsigned long long &b2)
+{
+    int bv[W];
+#pragma unroll
+    for (int u = 0; u < W; ++u) bv[u] = eb[u].key != KEY_NONE ? B[eb[u].payload & idx_mask] : -1;
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+        const bool free_ = eb[u].key != KEY_NONE && bv[u] >= q;
+        best2_insert(b1, b2, free_ ? ((unsigned long long)eb[u].key << 32) | eb[u].payload : ~0ull);
+    }
+}
+
+// a whole list in global memory, 8 entries per round trip (a window / bucket rarely holds more)
 __device__ __forceinline__ void scan_best2_free(const Entry *__restrict__ ent, int cnt, const int32_t *B, int q,
                                                 uint32_t idx_mask, unsigned long long &b1, unsigned long long &b2)
 {
     for (int j0 = 0; j0 < cnt; j0 += 8) {
         Entry eb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) eb[u] = j0 + u < cnt ? ent[j0 + u] : Entry{KEY_NONE, 0};
-        int bv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) bv[u] = eb[u].key != KEY_NONE ? B[eb[u].payload & idx_mask] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const bool free_ = eb[u].key != KEY_NONE && bv[u] >= q;
-            best2_insert(b1, b2, free_ ? ((unsigned long long)eb[u].key << 32) | eb[u].payload : ~0ull);
-        }
+        load_entries(ent, j0, cnt, eb);
+        scan_free(eb, B, q, idx_mask, b1, b2);
     }
 }
 
@@ -293,8 +396,7 @@ __device__ __forceinline__ void resolve_fixpoint_impl(int n_f, int n_q, int32_t 
             int nvalid = 0;
             for (int j0 = 0; j0 < ccnt[j]; j0 += 8) {
                 Entry eb[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) eb[u] = j0 + u < ccnt[j] ? cent[j][j0 + u] : Entry{KEY_NONE, 0};
+                load_entries(cent[j], j0, ccnt[j], eb);
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
                     if (eb[u].key != KEY_NONE) {
@@ -314,8 +416,7 @@ __device__ __forceinline__ void resolve_fixpoint_impl(int n_f, int n_q, int32_t 
                     int w = 0;
                     for (int j0 = 0; j0 < ccnt[j] && w < extra; j0 += 8) {
                         Entry eb[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) eb[u] = j0 + u < ccnt[j] ? cent[j][j0 + u] : Entry{KEY_NONE, 0};
+                        load_entries(cent[j], j0, ccnt[j], eb);
 #pragma unroll
                         for (int u = 0; u < 8; ++u)
                             if (eb[u].key != KEY_NONE && w < extra) ovf_arena[off + w++] = eb[u];
@@ -336,29 +437,14 @@ __device__ __forceinline__ void resolve_fixpoint_impl(int n_f, int n_q, int32_t 
 #pragma unroll
             for (int j = 0; j < QPT; ++j) {
                 const int q = tid + NT * j;
-                int bv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) bv[u] = ce[j][u].key != KEY_NONE ? Bc[ce[j][u].payload & idx_mask] : -1;
                 unsigned long long b1 = ~0ull, b2 = ~0ull;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const bool free_ = ce[j][u].key != KEY_NONE && bv[u] >= q;
-                    best2_insert(b1, b2, free_ ? ((unsigned long long)ce[j][u].key << 32) | ce[j][u].payload : ~0ull);
-                }
+                scan_free(ce[j], Bc, q, idx_mask, b1, b2);
                 if (covf[j]) {   // more than 8 valid candidates
                     if (covo[j] >= 0) {
                         for (int t0 = 0; t0 < covn[j]; t0 += 4) {   // 4 entries (and their B lookups) in flight
                             Entry e[4];
-                            int bv[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) e[u] = t0 + u < covn[j] ? ovf_arena[covo[j] + t0 + u] : Entry{KEY_NONE, 0};
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) bv[u] = e[u].key != KEY_NONE ? Bc[e[u].payload & idx_mask] : -1;
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                const bool free_ = e[u].key != KEY_NONE && bv[u] >= q;
-                                best2_insert(b1, b2, free_ ? ((unsigned long long)e[u].key << 32) | e[u].payload : ~0ull);
-                            }
+                            load_entries(ovf_arena + covo[j], t0, covn[j], e);
+                            scan_free(e, Bc, q, idx_mask, b1, b2);
                         }
                     } else {
                         b1 = b2 = ~0ull;
@@ -410,6 +496,14 @@ __device__ __forceinline__ void resolve_fixpoint(int n_f, int n_q, int32_t *lds,
         resolve_fixpoint_impl<NT, false>(n_f, n_q, lds, choice, idx_mask, initB, ent_of, accept, blocks);
 }
 
+// after the fixed point: the workgroup's sum of the threads' counts of accepted queries (*total zeroed before the resolve)
+__device__ __forceinline__ int block_total(int *total, int cnt)
+{
+    if (cnt) atomicAdd(total, cnt);
+    __syncthreads();
+    return *total;
+}
+
 // SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&)  :159-288
 struct BowQuery {
     int32_t kf_idx;   // realIdxKF
@@ -435,6 +529,17 @@ struct BowPairDev {
     int32_t *bin_1;           // n_kf scratch: rotHist bin + 1 of a matched KF1 feature
     int32_t *choice;          // n_queries scratch of the parallel stage B
 };
+
+// rotation consistency of both forms (:263-283, :632-652) by `nt` threads; returns the pushed entries it removed
+__device__ __forceinline__ int bow_cull(const BowPairDev &P, const int *histo, int tid, int nt)
+{
+    const RotCull c = rot_cull(histo);
+    if (!P.kf_kf)
+        cull_by_mask(c.culled, P.bin_f, P.match_f, P.n_f, tid, nt, -1);
+    else
+        cull_by_bin1(c.culled, P.bin_1, P.match_1, P.n_kf, tid, nt, -1);
+    return c.removed;
+}
 
 // stage A: grid = (max queries, pairs); one wave per query
 __global__ __launch_bounds__(64) void bow_distances_kernel(const BowPairDev *__restrict__ pairs)
@@ -518,27 +623,13 @@ __global__ __launch_bounds__(64) void bow_resolve_kernel(const BowPairDev *__res
             q2 = query_at(qi + 2);
             e2 = fetch(q2);
         }
-        uint32_t k1 = KEY_NONE, k2 = KEY_NONE, p1 = 0;
-        for (int j0 = 0; j0 < q.f_cnt; j0 += 64) {
-            if (j0 > 0) e = (j0 + lane < q.f_cnt) ? P.entries[q.ent_off + j0 + lane] : Entry{KEY_NONE, 0};
-            if (j0 + lane < q.f_cnt && !taken[e.payload]) {  // vpMapPointMatches[realIdxF] (:209)
-                if (e.key < k1) {
-                    k2 = k1;
-                    k1 = e.key;
-                    p1 = e.payload;
-                } else if (e.key < k2)
-                    k2 = e.key;
-            }
-        }
-        const uint32_t my1 = k1;
-        wave_min2(k1, k2);
-        const int bestDist1 = k1 == KEY_NONE ? 256 : (int)(k1 >> 20);
-        const int bestDist2 = k2 == KEY_NONE ? 256 : (int)(k2 >> 20);
+        const WaveBest2 b = wave_best2(P.entries + q.ent_off, q.f_cnt, e, lane,
+                                       [&](const Entry &c) { return !taken[c.payload]; });  // vpMapPointMatches[realIdxF] (:209)
+        const int bestDist1 = key_dist(b.k1), bestDist2 = key_dist(b.k2);
         // (KF, F): bestDist1 <= TH_LOW (:237); (KF, KF): bestDist1 < TH_LOW (:599)
         const bool low = P.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW;
         if (low && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
-            const unsigned long long own = __ballot(my1 == k1);
-            const int bestIdxF = (int)read_owner(p1, own);
+            const int bestIdxF = (int)b.payload1();
             if (lane == 0) {
                 taken[bestIdxF] = 1;
                 int bin = 0;
@@ -559,25 +650,7 @@ __global__ __launch_bounds__(64) void bow_resolve_kernel(const BowPairDev *__res
         }
     }
     __syncthreads();
-    if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        uint32_t culled = 0;
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) {
-                culled |= 1u << i;
-                nmatches -= histo[i];  // one decrement per pushed entry (:281, :650)
-            }
-        if (!P.kf_kf) {
-            for (int i = lane; i < P.n_f; i += 64)
-                if (P.bin_f[i] & culled) P.match_f[i] = -1;
-        } else {
-            for (int i = lane; i < P.n_kf; i += 64) {
-                const int bn = P.bin_1[i];
-                if (bn > 0 && ((culled >> (bn - 1)) & 1u)) P.match_1[i] = -1;
-            }
-        }
-    }
+    if (check_ori) nmatches -= bow_cull(P, histo, lane, 64);
     if (lane == 0) *P.nmatches = nmatches;
 }
 
@@ -612,8 +685,7 @@ __global__ __launch_bounds__(512) void bow_resolve_fix_kernel(const BowPairDev *
             return (const Entry *)(P.entries + bq.ent_off);
         },
         [&](int, const Best2 &b) {
-            const int bestDist1 = b.k1 == KEY_NONE ? 256 : (int)(b.k1 >> 20);
-            const int bestDist2 = b.k2 == KEY_NONE ? 256 : (int)(b.k2 >> 20);
+            const int bestDist1 = key_dist(b.k1), bestDist2 = key_dist(b.k2);
             // (KF, F): bestDist1 <= TH_LOW (:237); (KF, KF): bestDist1 < TH_LOW (:599)
             const bool low = P.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW;
             return (low && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) ? (int)b.p1 : -1;
@@ -638,28 +710,8 @@ __global__ __launch_bounds__(512) void bow_resolve_fix_kernel(const BowPairDev *
         }
         ++cnt;
     }
-    if (cnt) atomicAdd(&total, cnt);
-    __syncthreads();
-    int nmatches = total;
-    if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        uint32_t culled = 0;
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) {
-                culled |= 1u << i;
-                nmatches -= histo[i];  // one decrement per pushed entry (:281, :650)
-            }
-        if (!P.kf_kf) {
-            for (int i = tid; i < P.n_f; i += NT)
-                if (P.bin_f[i] & culled) P.match_f[i] = -1;
-        } else {
-            for (int i = tid; i < P.n_kf; i += NT) {
-                const int bn = P.bin_1[i];
-                if (bn > 0 && ((culled >> (bn - 1)) & 1u)) P.match_1[i] = -1;
-            }
-        }
-    }
+    int nmatches = block_total(&total, cnt);
+    if (check_ori) nmatches -= bow_cull(P, histo, tid, NT);
     if (tid == 0) *P.nmatches = nmatches;
 }
 
@@ -687,6 +739,36 @@ struct TriPairDev {
     int32_t *nmatches;
 };
 
+// epipolar line l = x1' F12 of a KF1 point in KF2 (:142-144) and den = a^2 + b^2
+struct EpiLine {
+    float a, b, c, den;
+};
+
+__device__ __forceinline__ EpiLine epi_line(const float *F12, float kx, float ky)
+{
+    EpiLine l;
+    l.a = __fadd_rn(__fadd_rn(__fmul_rn(kx, F12[0]), __fmul_rn(ky, F12[3])), F12[6]);
+    l.b = __fadd_rn(__fadd_rn(__fmul_rn(kx, F12[1]), __fmul_rn(ky, F12[4])), F12[7]);
+    l.c = __fadd_rn(__fadd_rn(__fmul_rn(kx, F12[2]), __fmul_rn(ky, F12[5])), F12[8]);
+    l.den = __fadd_rn(__fmul_rn(l.a, l.a), __fmul_rn(l.b, l.b));
+    return l;
+}
+
+// the geometric gate of a KF2 candidate at (x2, y2): a pair without stereo on either side must not sit on the epipole (ex, ey)
+// (:739-745; sf = scale factor of the candidate's level), then CheckDistEpipolarLine (:139-157; sigma2 = its level's sigma^2)
+__device__ __forceinline__ bool epi_admits(const EpiLine &l, float x2, float y2, bool both_mono, float ex, float ey, float sf,
+                                           float sigma2)
+{
+    if (both_mono) {
+        const float dx = __fsub_rn(ex, x2), dy = __fsub_rn(ey, y2);
+        if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.0f, sf)) return false;
+    }
+    const float num = __fadd_rn(__fadd_rn(__fmul_rn(l.a, x2), __fmul_rn(l.b, y2)), l.c);
+    if (l.den == 0.0f) return false;
+    const float dsqr = __fdiv_rn(__fmul_rn(num, num), l.den);
+    return (double)dsqr < __dmul_rn(3.84, (double)sigma2);
+}
+
 __global__ __launch_bounds__(64) void triang_match_kernel(const TriPairDev *__restrict__ pairs)
 {
     const TriPairDev &P = pairs[blockIdx.y];
@@ -696,11 +778,7 @@ __global__ __launch_bounds__(64) void triang_match_kernel(const TriPairDev *__re
     const Desc d1 = load_desc(P.desc1 + (size_t)q.idx1 * 32);
     const float kx = P.x1[q.idx1], ky = P.y1[q.idx1];
     const bool bStereo1 = P.u_right1[q.idx1] >= 0;
-    // epipolar line l = x1' F12 (:142-144)
-    const float a = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[0]), __fmul_rn(ky, P.F12[3])), P.F12[6]);
-    const float b = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[1]), __fmul_rn(ky, P.F12[4])), P.F12[7]);
-    const float c = __fadd_rn(__fadd_rn(__fmul_rn(kx, P.F12[2]), __fmul_rn(ky, P.F12[5])), P.F12[8]);
-    const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+    const EpiLine line = epi_line(P.F12, kx, ky);
     uint32_t key = KEY_NONE, pay = 0;
     for (int j = lane; j < q.f_cnt; j += 64) {
         const int idx2 = P.node_idx2[q.f_beg + j];
@@ -709,17 +787,10 @@ __global__ __launch_bounds__(64) void triang_match_kernel(const TriPairDev *__re
         if (P.only_stereo && !bStereo2) continue;
         const int dist = hamming(d1, load_desc(P.desc2 + (size_t)idx2 * 32));
         if (dist > TH_LOW) continue;                         // :734 (bestDist never exceeds TH_LOW)
-        const float x2 = P.x2[idx2], y2 = P.y2[idx2];
         const int oct = P.octave2[idx2];
-        if (!bStereo1 && !bStereo2) {                        // too close to the epipole (:739-745)
-            const float dx = __fsub_rn(P.ex, x2), dy = __fsub_rn(P.ey, y2);
-            if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.0f, P.scale_factors2[oct])) continue;
-        }
-        // CheckDistEpipolarLine :139-157
-        const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, x2), __fmul_rn(b, y2)), c);
-        if (den == 0.0f) continue;
-        const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-        if (!((double)dsqr < __dmul_rn(3.84, (double)P.level_sigma2_2[oct]))) continue;
+        if (!epi_admits(line, P.x2[idx2], P.y2[idx2], !bStereo1 && !bStereo2, P.ex, P.ey, P.scale_factors2[oct],
+                        P.level_sigma2_2[oct]))
+            continue;
         const uint32_t k = ((uint32_t)dist << 20) | (0xFFFFFu - (uint32_t)j);
         if (k < key) {
             key = k;
@@ -735,38 +806,39 @@ __global__ __launch_bounds__(64) void triang_match_kernel(const TriPairDev *__re
     }
 }
 
-// rotation consistency (:776-808) + count, one wave per pair
-__global__ __launch_bounds__(64) void triang_finish_kernel(const TriPairDev *__restrict__ pairs, int check_ori)
+// rotation consistency (:776-808) + count of one pair by one wave: match12[0 .. n1) against the angle rows of the two keyframes;
+// the bin of a match is recomputed from its two angles
+__device__ __forceinline__ void triang_finish_body(int n1, const float *angle1, const float *angle2, int32_t *match12, int32_t *nmatches_out, int check_ori)
 {
     __shared__ int histo[HISTO];
-    const TriPairDev &P = pairs[blockIdx.x];
     const int lane = threadIdx.x;
     if (lane < HISTO) histo[lane] = 0;
     __syncthreads();
     int cnt = 0;
-    for (int i = lane; i < P.n1; i += 64) {
-        const int m2 = P.match12[i];
+    for (int i = lane; i < n1; i += 64) {
+        const int m2 = match12[i];
         if (m2 >= 0) {
             cnt++;
-            if (check_ori) atomicAdd(&histo[rot_bin(__fsub_rn(P.angle1[i], P.angle2[m2]))], 1);
+            if (check_ori) atomicAdd(&histo[rot_bin(__fsub_rn(angle1[i], angle2[m2]))], 1);
         }
     }
     __syncthreads();
     cnt = wave_sum_i32(cnt);
     if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        for (int i = lane; i < P.n1; i += 64) {
-            const int m2 = P.match12[i];
-            if (m2 >= 0) {
-                const int bin = rot_bin(__fsub_rn(P.angle1[i], P.angle2[m2]));
-                if (bin != i1 && bin != i2 && bin != i3) P.match12[i] = -1;
-            }
+        const RotCull c = rot_cull(histo);
+        for (int i = lane; i < n1; i += 64) {
+            const int m2 = match12[i];
+            if (m2 >= 0 && ((c.culled >> rot_bin(__fsub_rn(angle1[i], angle2[m2]))) & 1u)) match12[i] = -1;
         }
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) cnt -= histo[i];
+        cnt -= c.removed;
     }
-    if (lane == 0) *P.nmatches = cnt;
+    if (lane == 0) *nmatches_out = cnt;
+}
+
+__global__ __launch_bounds__(64) void triang_finish_kernel(const TriPairDev *__restrict__ pairs, int check_ori)
+{
+    const TriPairDev &P = pairs[blockIdx.x];
+    triang_finish_body(P.n1, P.angle1, P.angle2, P.match12, P.nmatches, check_ori);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -946,48 +1018,68 @@ struct QueryRec {
 };
 static_assert(sizeof(QueryRec) == 24, "QueryRec layout");
 
-// best / second of one query in stage B; e = entries of the first 64 candidates (prefetched)
+__device__ __forceinline__ QueryRec query_rec(float u, float v, float radius, float ur, int minL, int maxL, int row)
+{
+    QueryRec r;
+    r.u = u; r.v = v; r.radius = radius; r.ur = ur;
+    r.minL = (int16_t)minL; r.maxL = (int16_t)maxL; r.row = row;
+    return r;
+}
+
+// Stage A, fill pass of the two-pass form with the counting pass's record: slot + record, then straight to the window
+// (desc = the descriptor table the record's row refers to)
+__device__ __forceinline__ void fill_from_record(const FrameDev &F, const uint8_t *desc, const QuerySlot *slots,
+                                                 const QueryRec *rec, Entry *pool, int i, int lane)
+{
+    const QuerySlot sl = slots[i];
+    if (sl.cnt <= 0) return;
+    const QueryRec r = rec[i];
+    const Window w = window_cells(F, r.u, r.v, r.radius);
+    window_entries(F, w, load_desc(desc + (size_t)r.row * 32), r.u, r.v, r.radius, r.minL, r.maxL, r.ur, r.radius, lane,
+                   pool + sl.ent_off);
+}
+
+// Stage A: where the `pop` (> 0) entries of query i go.  One-pass form (phase 0): query i of n owns a fixed slice of its
+// problem's region [pool_base, pool_base + pool_cap) -- no shared counter: ~100 k same-address atomics serialised in one L2
+// channel (0.94 ms for 64 frames); a window that does not fit its slice raises the sticky overflow word for the host.  Fill
+// pass of the two-pass form (phase 2): the slot the scan assigned, if the counting pass saw the same population.
+// Returns {pop, offset}, or cnt = -1: no room (the caller writes no entries).
+__device__ __forceinline__ QuerySlot claim_slot(const QuerySlot *slots, int i, int n, int pop, int pool_base, int pool_cap,
+                                                int phase, int32_t *pool_used, int lane)
+{
+    const int stride = phase == 2 ? pop : pool_cap / max(n, 1);
+    const int off = phase == 2 ? slots[i].ent_off : pool_base + i * stride;
+    if (pop > stride && lane == 0) overflow_note(pool_used, pop);
+    if (pop <= stride && (phase != 2 || slots[i].cnt == pop)) return QuerySlot{pop, off};
+    return QuerySlot{-1, 0};
+}
+
+// best / second of one query in the stage B of the window searches
 struct Pick {
     uint32_t k1, k2;
-    int idx1, oct1, oct2;
+    int idx1, oct1, oct2;   // feature and octave of the best, octave of the second; -1 = none
 };
 
+// candidates whose feature holds a map point with observations (state 2) are skipped -- with skip_any, any map point (state != 0)
 __device__ __forceinline__ Pick pick_best2(const Entry *__restrict__ ent, int cnt, Entry e, const uint8_t *state,
                                            int lane, bool skip_any = false)
 {
-    uint32_t k1 = KEY_NONE, k2 = KEY_NONE, p1 = 0, p2 = 0;
-    for (int j0 = 0; j0 < cnt; j0 += 64) {
-        if (j0 > 0) e = (j0 + lane < cnt) ? ent[j0 + lane] : Entry{KEY_NONE, 0};
-        const uint8_t stv = (j0 + lane < cnt && e.key != KEY_NONE) ? state[e.payload & 0xffffffu] : (uint8_t)2;
-        if (j0 + lane < cnt && e.key != KEY_NONE && (skip_any ? stv == 0 : stv != 2)) {  // Observations()>0 skip / any map point
-            if (e.key < k1) {
-                k2 = k1; p2 = p1;
-                k1 = e.key; p1 = e.payload;
-            } else if (e.key < k2) {
-                k2 = e.key; p2 = e.payload;
-            }
-        }
-    }
+    const WaveBest2 b = wave_best2(ent, cnt, e, lane, [&](const Entry &c) {
+        if (c.key == KEY_NONE) return false;
+        const uint8_t stv = state[c.payload & 0xffffffu];
+        return skip_any ? stv == 0 : stv != 2;
+    });
     Pick r;
-    r.k1 = k1;
-    r.k2 = k2;
-    wave_min2(r.k1, r.k2);
+    r.k1 = b.k1;
+    r.k2 = b.k2;
     r.idx1 = -1;
     r.oct1 = r.oct2 = -1;
-    // keys are unique (unique position): find the owners' payloads
-    const unsigned long long own1 = __ballot(k1 == r.k1 && r.k1 != KEY_NONE);
-    if (own1) {
-        const uint32_t pl = read_owner(p1, own1);
+    if (b.k1 != KEY_NONE) {
+        const uint32_t pl = b.payload1();
         r.idx1 = (int)(pl & 0xffffffu);
         r.oct1 = (int)(pl >> 24);
     }
-    if (r.k2 != KEY_NONE) {
-        const unsigned long long o2a = __ballot(k1 == r.k2), o2b = __ballot(k2 == r.k2);
-        if (o2a)
-            r.oct2 = (int)(read_owner(p1, o2a) >> 24);
-        else if (o2b)
-            r.oct2 = (int)(read_owner(p2, o2b) >> 24);
-    }
+    if (b.k2 != KEY_NONE) r.oct2 = (int)(b.payload2() >> 24);
     return r;
 }
 
@@ -1038,6 +1130,18 @@ struct SlotStream {
     }
 };
 
+// the ent_of of resolve_fixpoint for the searches whose stage A wrote slots into a pool
+struct SlotEntries {
+    const QuerySlot *slots;
+    const Entry *pool;
+    __device__ __forceinline__ const Entry *operator()(int q, int &cnt) const
+    {
+        const QuerySlot s = slots[q];
+        cnt = s.cnt;
+        return pool + s.ent_off;
+    }
+};
+
 struct ProjMpDev {
     int n_mp;
     const uint8_t *track_in_view, *desc, *has_obs;
@@ -1066,13 +1170,8 @@ __device__ __forceinline__ void proj_mp_entries_body(const FrameDev &F, const Pr
                                                      int phase = 0, QueryRec *rec = nullptr)
 {
     const int lane = kSolo ? 0 : (int)(threadIdx.x & 63);   // a wave per query (workgroups may hold several waves)
-    if (phase == 2 && rec) {   // fill pass with the counting pass's record (QueryRec): slot + record, then straight to the window
-        const QuerySlot sl = slots[i];
-        if (sl.cnt <= 0) return;
-        const QueryRec r = rec[i];
-        const Window w = window_cells(F, r.u, r.v, r.radius);
-        window_entries(F, w, load_desc(P.desc + (size_t)r.row * 32), r.u, r.v, r.radius, r.minL, r.maxL, r.ur, r.radius, lane,
-                       pool + sl.ent_off);
+    if (phase == 2 && rec) {
+        fill_from_record(F, P.desc, slots, rec, pool, i, lane);
         return;
     }
     QuerySlot s{0, 0};
@@ -1085,26 +1184,16 @@ __device__ __forceinline__ void proj_mp_entries_body(const FrameDev &F, const Pr
                 s.cnt = pop;
                 if (rec && lane == 0) {
                     const int lvl = P.pred_level[i];
-                    QueryRec r;
-                    r.u = P.proj_x[i]; r.v = P.proj_y[i]; r.radius = rs; r.ur = P.proj_xr[i];
-                    r.minL = (int16_t)(lvl - 1); r.maxL = (int16_t)lvl; r.row = P.desc_idx ? P.desc_idx[i] : i;
-                    rec[i] = r;
+                    rec[i] = query_rec(P.proj_x[i], P.proj_y[i], rs, P.proj_xr[i], lvl - 1, lvl, P.desc_idx ? P.desc_idx[i] : i);
                 }
             } else if (pop > 0) {
-                // query i owns a fixed slice of the pool (no shared counter: same-address atomics serialise in L2)
-                const int stride = phase == 2 ? pop : pool_cap / max(P.n_mp, 1);
-                int off = phase == 2 ? slots[i].ent_off - pool_base : i * stride;
-                if (pop > stride && lane == 0) overflow_note(pool_used, pop);   // overflow flag for the host (batched form)
-                if (pop <= stride && (phase != 2 || slots[i].cnt == pop)) {
+                s = claim_slot(slots, i, P.n_mp, pop, pool_base, pool_cap, phase, pool_used, lane);
+                if (s.cnt > 0) {
                     const int lvl = P.pred_level[i];
-                    off += pool_base;
                     const size_t drow = P.desc_idx ? (size_t)P.desc_idx[i] : (size_t)i;
                     window_entries(F, w, load_desc(P.desc + drow * 32), P.proj_x[i], P.proj_y[i], rs, lvl - 1, lvl,
-                                   P.proj_xr[i], rs, lane, pool + off);
-                    s.cnt = pop;
-                    s.ent_off = off;
-                } else
-                    s.cnt = -1;  // pool exhausted (cannot happen: the pool holds n_mp * n_f entries)
+                                   P.proj_xr[i], rs, lane, pool + s.ent_off);
+                }
             }
         }
     }
@@ -1142,8 +1231,7 @@ __device__ __forceinline__ void proj_mp_resolve_body(const FrameDev &F, const Pr
         Q.next(iMP, s, e);
         if (s.cnt <= 0) continue;  // not in view, empty window (vIndices.empty()) -- nothing to do
         const Pick b = pick_best2(pool + s.ent_off, s.cnt, e, state, lane);
-        const int bestDist = b.k1 == KEY_NONE ? 256 : (int)(b.k1 >> 20);
-        const int bestDist2 = b.k2 == KEY_NONE ? 256 : (int)(b.k2 >> 20);
+        const int bestDist = key_dist(b.k1), bestDist2 = key_dist(b.k2);
         if (bestDist <= TH_HIGH) {
             if (b.oct1 == b.oct2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2)) continue;
             if (lane == 0) {
@@ -1179,14 +1267,9 @@ __device__ __forceinline__ void proj_mp_resolve_fix_body(const FrameDev &F, cons
     if (tid == 0) total = 0;
     resolve_fixpoint<NT>(
         F.n_f, P.n_mp, fix_lds, choice, 0xffffffu, [&](int i) { return F.f_mp_state[i] == 2 ? -1 : INT_MAX; },
-        [&](int q, int &cnt) {
-            const QuerySlot s = slots[q];
-            cnt = s.cnt;
-            return pool + s.ent_off;
-        },
+        SlotEntries{slots, pool},
         [&](int, const Best2 &b) {
-            const int bestDist = b.k1 == KEY_NONE ? 256 : (int)(b.k1 >> 20);
-            const int bestDist2 = b.k2 == KEY_NONE ? 256 : (int)(b.k2 >> 20);
+            const int bestDist = key_dist(b.k1), bestDist2 = key_dist(b.k2);
             const int oct1 = b.k1 == KEY_NONE ? -1 : (int)(b.p1 >> 24), oct2 = b.k2 == KEY_NONE ? -1 : (int)(b.p2 >> 24);
             if (bestDist <= TH_HIGH && !(oct1 == oct2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2)))
                 return (int)(b.p1 & 0xffffffu);
@@ -1201,9 +1284,8 @@ __device__ __forceinline__ void proj_mp_resolve_fix_body(const FrameDev &F, cons
             ++cnt;
         }
     }
-    if (cnt) atomicAdd(&total, cnt);
-    __syncthreads();
-    if (tid == 0) *nmatches_out = total;
+    const int nmatches = block_total(&total, cnt);
+    if (tid == 0) *nmatches_out = nmatches;
 }
 
 __global__ __launch_bounds__(1024) void proj_mp_resolve_fix_kernel(FrameDev F, ProjMpDev P, float nnratio,
@@ -1271,13 +1353,8 @@ __device__ __forceinline__ void proj_last_entries_body(const FrameDev &F, const 
                                                        int i, int pool_base = 0, int phase = 0, QueryRec *rec = nullptr)
 {
     const int lane = kSolo ? 0 : (int)(threadIdx.x & 63);   // a wave per query (workgroups may hold several waves)
-    if (phase == 2 && rec) {   // fill pass with the counting pass's record: slot + record, then straight to the window
-        const QuerySlot sl = slots[i];
-        if (sl.cnt <= 0) return;
-        const QueryRec r = rec[i];
-        const Window w = window_cells(F, r.u, r.v, r.radius);
-        window_entries(F, w, load_desc(P.desc + (size_t)r.row * 32), r.u, r.v, r.radius, r.minL, r.maxL, r.ur, r.radius, lane,
-                       pool + sl.ent_off);
+    if (phase == 2 && rec) {
+        fill_from_record(F, P.desc, slots, rec, pool, i, lane);
         return;
     }
     QuerySlot s{0, 0};
@@ -1329,26 +1406,15 @@ __device__ __forceinline__ void proj_last_entries_body(const FrameDev &F, const 
             const Window w = window_cells(F, u, v, radius);
             if (w.ok) {
                 const int pop = kSolo ? window_population_solo(F, w) : window_population(F, w, lane);
+                const float ur = __fsub_rn(u, __fmul_rn(P.mbf, invzc));
                 if (pop > 0 && (phase == 1 || kSolo)) {
                     s.cnt = pop;
-                    if (rec && lane == 0) {
-                        QueryRec r;
-                        r.u = u; r.v = v; r.radius = radius; r.ur = __fsub_rn(u, __fmul_rn(P.mbf, invzc));
-                        r.minL = (int16_t)minL; r.maxL = (int16_t)maxL; r.row = row;
-                        rec[i] = r;
-                    }
+                    if (rec && lane == 0) rec[i] = query_rec(u, v, radius, ur, minL, maxL, row);
                 } else if (pop > 0) {
-                    const int stride = phase == 2 ? pop : pool_cap / max(P.n_last, 1);
-                    const int off = phase == 2 ? slots[i].ent_off : pool_base + i * stride;
-                    if (pop > stride && lane == 0) overflow_note(pool_used, pop);
-                    if (pop <= stride && (phase != 2 || slots[i].cnt == pop)) {
-                        const float ur = __fsub_rn(u, __fmul_rn(P.mbf, invzc));
+                    s = claim_slot(slots, i, P.n_last, pop, pool_base, pool_cap, phase, pool_used, lane);
+                    if (s.cnt > 0)
                         window_entries(F, w, load_desc(P.desc + (size_t)row * 32), u, v, radius, minL, maxL, ur, radius, lane,
-                                       pool + off);
-                        s.cnt = pop;
-                        s.ent_off = off;
-                    } else
-                        s.cnt = -1;
+                                       pool + s.ent_off);
                 }
             }
         }
@@ -1387,8 +1453,7 @@ __global__ __launch_bounds__(64) void proj_last_resolve_kernel(FrameDev F, ProjL
         Q.next(i, s, e);
         if (s.cnt <= 0) continue;
         const Pick b = pick_best2(pool + s.ent_off, s.cnt, e, state, lane);
-        const int bestDist = b.k1 == KEY_NONE ? 256 : (int)(b.k1 >> 20);
-        if (bestDist <= TH_HIGH) {
+        if (key_dist(b.k1) <= TH_HIGH) {
             if (lane == 0) {
                 match_f[b.idx1] = i;
                 state[b.idx1] = P.has_obs[i] ? 2 : 1;
@@ -1407,16 +1472,9 @@ __global__ __launch_bounds__(64) void proj_last_resolve_kernel(FrameDev F, ProjL
     }
     __syncthreads();
     if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        uint32_t culled = 0;
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) {
-                culled |= 1u << i;
-                nmatches -= histo[i];
-            }
-        for (int i = lane; i < F.n_f; i += 64)
-            if (bin_f[i] & culled) match_f[i] = -2;  // set to NULL (:1459)
+        const RotCull c = rot_cull(histo);
+        cull_by_mask(c.culled, bin_f, match_f, F.n_f, lane, 64, -2);  // set to NULL (:1459)
+        nmatches -= c.removed;
     }
     if (lane == 0) *nmatches_out = nmatches;
 }
@@ -1440,11 +1498,7 @@ __device__ __forceinline__ void proj_last_resolve_fix_body(const FrameDev &F, co
     if (tid == 0) total = 0;
     resolve_fixpoint<NT>(
         F.n_f, P.n_last, fix_lds, choice, 0xffffffu, [&](int i) { return F.f_mp_state[i] == 2 ? -1 : INT_MAX; },
-        [&](int q, int &cnt) {
-            const QuerySlot s = slots[q];
-            cnt = s.cnt;
-            return pool + s.ent_off;
-        },
+        SlotEntries{slots, pool},
         [&](int, const Best2 &b) { return (b.k1 != KEY_NONE && (int)(b.k1 >> 20) <= TH_HIGH) ? (int)(b.p1 & 0xffffffu) : -1; },
         [&](int q) { return proj_last_blocks(P, q); });
     int cnt = 0;
@@ -1462,20 +1516,11 @@ __device__ __forceinline__ void proj_last_resolve_fix_body(const FrameDev &F, co
             ++cnt;
         }
     }
-    if (cnt) atomicAdd(&total, cnt);
-    __syncthreads();
-    int nmatches = total;
+    int nmatches = block_total(&total, cnt);
     if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        uint32_t culled = 0;
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) {
-                culled |= 1u << i;
-                nmatches -= histo[i];
-            }
-        for (int i = tid; i < F.n_f; i += NT)
-            if (bin_f[i] & culled) match_f[i] = -2;  // set to NULL (:1459)
+        const RotCull c = rot_cull(histo);
+        cull_by_mask(c.culled, bin_f, match_f, F.n_f, tid, NT, -2);  // set to NULL (:1459)
+        nmatches -= c.removed;
     }
     if (tid == 0) *nmatches_out = nmatches;
 }
@@ -1851,21 +1896,14 @@ __global__ __launch_bounds__(64) void projgen_entries_kernel(FrameDev F, ProjGen
         const Window w = window_cells(F, S.u, S.v, S.radius);
         if (w.ok) {
             const int pop = window_population(F, w, lane);
-            if (pop > 0) {
-                const int stride = pool_cap / max(P.n_pts, 1);   // query i owns pool[i * stride ..): no shared counter
-                const int off = i * stride;
-                if (pop > stride && lane == 0) overflow_note(pool_used, pop);
-                if (pop <= stride) {
-                    // mode 2: levels [pred-1, pred] tested per candidate (:379-382) == the level filter of the
-                    // Frame version; mode 4: GetFeaturesInArea(u, v, radius, pred-1, pred+1) (:1537).  A level
-                    // window starting at 0 or below disables only the lower test, like bCheckLevels (Frame.cc:379).
-                    const int lo = S.level - 1, hi = P.mode == 4 ? S.level + 1 : S.level;
-                    window_entries(F, w, load_desc(P.desc + (size_t)i * 32), S.u, S.v, S.radius, lo, hi, 0.0f,
-                                   __builtin_huge_valf(), lane, pool + off);
-                    s.cnt = pop;
-                    s.ent_off = off;
-                } else
-                    s.cnt = -1;
+            if (pop > 0) s = claim_slot(slots, i, P.n_pts, pop, 0, pool_cap, 0, pool_used, lane);
+            if (s.cnt > 0) {
+                // mode 2: levels [pred-1, pred] tested per candidate (:379-382) == the level filter of the
+                // Frame version; mode 4: GetFeaturesInArea(u, v, radius, pred-1, pred+1) (:1537).  A level
+                // window starting at 0 or below disables only the lower test, like bCheckLevels (Frame.cc:379).
+                const int lo = S.level - 1, hi = P.mode == 4 ? S.level + 1 : S.level;
+                window_entries(F, w, load_desc(P.desc + (size_t)i * 32), S.u, S.v, S.radius, lo, hi, 0.0f,
+                               __builtin_huge_valf(), lane, pool + s.ent_off);
             }
         }
     }
@@ -1897,8 +1935,7 @@ __global__ __launch_bounds__(64) void projgen_resolve_kernel(FrameDev F, ProjGen
         Q.next(i, s, e);
         if (s.cnt <= 0) continue;
         const Pick b = pick_best2(pool + s.ent_off, s.cnt, e, state, lane, true);
-        const int bestDist = b.k1 == KEY_NONE ? 256 : (int)(b.k1 >> 20);
-        if (bestDist <= thr) {
+        if (key_dist(b.k1) <= thr) {
             if (lane == 0) {
                 match_f[b.idx1] = i;
                 state[b.idx1] = 1;
@@ -1914,14 +1951,9 @@ __global__ __launch_bounds__(64) void projgen_resolve_kernel(FrameDev F, ProjGen
     }
     __syncthreads();
     if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) nmatches -= histo[i];
-        for (int i = lane; i < F.n_f; i += 64) {
-            const int bn = bin_f[i] - 1;
-            if (bn >= 0 && bn != i1 && bn != i2 && bn != i3) match_f[i] = -2;  // set to NULL (:1589)
-        }
+        const RotCull c = rot_cull(histo);
+        cull_by_bin1(c.culled, bin_f, match_f, F.n_f, lane, 64, -2);  // set to NULL (:1589)
+        nmatches -= c.removed;
     }
     if (lane == 0) *nmatches_out = nmatches;
 }
@@ -1945,11 +1977,7 @@ __global__ __launch_bounds__(1024) void projgen_resolve_fix_kernel(FrameDev F, P
     if (tid == 0) total = 0;
     resolve_fixpoint<NT>(
         F.n_f, P.n_pts, fix_lds, choice, 0xffffffu, [&](int i) { return F.f_mp_state[i] != 0 ? -1 : INT_MAX; },
-        [&](int q, int &cnt) {
-            const QuerySlot s = slots[q];
-            cnt = s.cnt;
-            return pool + s.ent_off;
-        },
+        SlotEntries{slots, pool},
         [&](int, const Best2 &b) { return (b.k1 != KEY_NONE && (int)(b.k1 >> 20) <= thr) ? (int)(b.p1 & 0xffffffu) : -1; },
         [&](int) { return true; });
     int cnt = 0;
@@ -1964,18 +1992,11 @@ __global__ __launch_bounds__(1024) void projgen_resolve_fix_kernel(FrameDev F, P
         }
         ++cnt;
     }
-    if (cnt) atomicAdd(&total, cnt);
-    __syncthreads();
-    int nmatches = total;
+    int nmatches = block_total(&total, cnt);
     if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(histo, i1, i2, i3);
-        for (int i = 0; i < HISTO; ++i)
-            if (i != i1 && i != i2 && i != i3) nmatches -= histo[i];
-        for (int i = tid; i < F.n_f; i += NT) {
-            const int bn = bin_f[i] - 1;
-            if (bn >= 0 && bn != i1 && bn != i2 && bn != i3) match_f[i] = -2;  // set to NULL (:1589)
-        }
+        const RotCull c = rot_cull(histo);
+        cull_by_bin1(c.culled, bin_f, match_f, F.n_f, tid, NT, -2);  // set to NULL (:1589)
+        nmatches -= c.removed;
     }
     if (tid == 0) *nmatches_out = nmatches;
 }
@@ -2005,18 +2026,11 @@ __global__ __launch_bounds__(64) void init_entries_kernel(FrameDev F2, InitDev P
         const Window w = window_cells(F2, x, y, P.window);
         if (w.ok) {
             const int pop = window_population(F2, w, lane);
-            if (pop > 0) {
-                const int stride = pool_cap / max(P.n1, 1);
-                const int off = i * stride;
-                if (pop > stride && lane == 0) overflow_note(pool_used, pop);
-                if (pop <= stride) {
-                    const int lvl = P.octave1[i];
-                    window_entries(F2, w, load_desc(P.desc1 + (size_t)i * 32), x, y, P.window, lvl, lvl, 0.0f,
-                                   __builtin_huge_valf(), lane, pool + off);
-                    s.cnt = pop;
-                    s.ent_off = off;
-                } else
-                    s.cnt = -1;
+            if (pop > 0) s = claim_slot(slots, i, P.n1, pop, 0, pool_cap, 0, pool_used, lane);
+            if (s.cnt > 0) {
+                const int lvl = P.octave1[i];
+                window_entries(F2, w, load_desc(P.desc1 + (size_t)i * 32), x, y, P.window, lvl, lvl, 0.0f,
+                               __builtin_huge_valf(), lane, pool + s.ent_off);
             }
         }
     }
@@ -2051,28 +2065,14 @@ __global__ __launch_bounds__(64) void init_resolve_kernel(FrameDev F2, InitDev P
         Entry e;
         Q.next(i1, s, e);
         if (s.cnt <= 0) continue;
-        uint32_t k1 = KEY_NONE, k2 = KEY_NONE, p1 = 0;
-        for (int j0 = 0; j0 < s.cnt; j0 += 64) {
-            if (j0 > 0) e = (j0 + lane < s.cnt) ? pool[s.ent_off + j0 + lane] : Entry{KEY_NONE, 0};
-            if (j0 + lane < s.cnt && e.key != KEY_NONE) {
-                const uint32_t dist = e.key >> 20;
-                if ((uint32_t)md[e.payload & 0xffffffu] > dist) {  // !(vMatchedDistance[i2] <= dist)
-                    if (e.key < k1) {
-                        k2 = k1;
-                        k1 = e.key;
-                        p1 = e.payload;
-                    } else if (e.key < k2)
-                        k2 = e.key;
-                }
-            }
-        }
-        const uint32_t my1 = k1;
-        wave_min2(k1, k2);
-        if (k1 == KEY_NONE) continue;
-        const int bestDist = (int)(k1 >> 20);
-        const float second = k2 == KEY_NONE ? 2147483648.0f : (float)(int)(k2 >> 20);  // (float)INT_MAX
+        const WaveBest2 b = wave_best2(pool + s.ent_off, s.cnt, e, lane, [&](const Entry &c) {   // !(vMatchedDistance[i2] <= dist)
+            return c.key != KEY_NONE && (uint32_t)md[c.payload & 0xffffffu] > (c.key >> 20);
+        });
+        if (b.k1 == KEY_NONE) continue;
+        const int bestDist = (int)(b.k1 >> 20);
+        const float second = b.k2 == KEY_NONE ? 2147483648.0f : (float)(int)(b.k2 >> 20);  // (float)INT_MAX
         if (bestDist <= TH_LOW && (float)bestDist < __fmul_rn(second, nnratio)) {
-            const int bestIdx2 = (int)(read_owner(p1, __ballot(my1 == k1)) & 0xffffffu);
+            const int bestIdx2 = (int)(b.payload1() & 0xffffffu);
             const int prev = (int)m21[bestIdx2];
             if (lane == 0) {
                 if (prev > 0) match12[prev - 1] = -1;
@@ -2092,18 +2092,9 @@ __global__ __launch_bounds__(64) void init_resolve_kernel(FrameDev F2, InitDev P
     __threadfence_block();
     __syncthreads();
     if (check_ori) {
-        int i1m, i2m, i3m;
-        three_maxima(histo, i1m, i2m, i3m);
-        int drop = 0;
-        for (int i = lane; i < P.n1; i += 64) {
-            const int bn = bin_1[i] - 1;
-            if (bn >= 0 && bn != i1m && bn != i2m && bn != i3m && match12[i] >= 0) {  // :497-501
-                match12[i] = -1;
-                drop++;
-            }
-        }
-        drop = wave_sum_i32(drop);
-        nmatches -= drop;
+        // a stolen match is already -1 and its histogram entry stays: count the matches actually reset (:497-501), not the entries
+        const int drop = cull_by_bin1(rot_cull(histo).culled, bin_1, match12, P.n1, lane, 64, -1);
+        nmatches -= wave_sum_i32(drop);
     }
     if (lane == 0) *nmatches_out = nmatches;
 }

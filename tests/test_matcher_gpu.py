@@ -516,3 +516,95 @@ def test_projection_searches_beyond_a_gibibyte_of_candidates(pkg, oracle, gpu):
     n, match = m.SearchByProjectionReloc(f, p, 100)
     on, om = oracle.search_by_projection_reloc(f, p, 100, True)
     assert n == on and (match == om).all() and n > 500
+
+
+def test_search_by_projection_batch_sequential_stage_b(pkg, oracle, gpu, monkeypatch):
+    """the one-wave sequential stage B of the batched SearchByProjection(F, vpMapPoints, th) (AOS2_SERIAL_RESOLVE=1, read
+    when the handle is created) == the oracle per frame == the fixed-point form of the same call, on frames whose map
+    points truly compete (~7 per feature; every window holding every feature) with blocking and non-blocking takers mixed"""
+    S = pkg.synth
+    batches = [[S.synth_proj_mp_problem(220 + s, n_f=60, n_mp=400, th=12.0) for s in range(3)],
+               [S.synth_proj_mp_problem(230 + s, n_f=8, n_mp=300, th=40.0, w=160, h=120) for s in range(3)]]
+    for probs in batches:
+        frames, mps = [p[0] for p in probs], [p[1] for p in probs]
+        for mp in mps:
+            mp["has_obs"] = (np.arange(len(mp["has_obs"])) % 3 != 0).astype(np.uint8)
+        th, ratio = float(mps[0]["th"]), float(mps[0]["nnratio"])
+        fix = pkg.Matcher(ratio, True).SearchByProjectionBatch(frames, mps, th=th)
+        monkeypatch.setenv("AOS2_SERIAL_RESOLVE", "1")
+        ser = pkg.Matcher(ratio, True).SearchByProjectionBatch(frames, mps, th=th)
+        monkeypatch.delenv("AOS2_SERIAL_RESOLVE")
+        for (f, mp), (n, match), (nf, matchf) in zip(probs, ser, fix):
+            on, om = oracle.search_by_projection_mp(f, mp)
+            assert n == on and (match == om).all() and on > 0
+            assert nf == n and (matchf == match).all()
+
+
+def _both_stage_b(monkeypatch, run):
+    """run() with the fixed-point stage B, then with the sequential one (the handle reads the switch when it is created)"""
+    out = [run()]
+    monkeypatch.setenv("AOS2_SERIAL_RESOLVE", "1")
+    out.append(run())
+    monkeypatch.delenv("AOS2_SERIAL_RESOLVE")
+    return out
+
+
+def test_rotation_cull_small_problems_every_search(pkg, oracle, gpu, monkeypatch):
+    """The rotation-consistency epilogue of every search on a problem of <= 300 features where it really removes matches
+    (seeds chosen with the oracle: fewer matches with the check than without; -2 marks where the search writes them), in all
+    three storage forms: a bit mask per feature (SearchByBoW (KF,F), SearchByProjection(Current, Last)), bin + 1 per element
+    (SearchByBoW (KF,KF), the relocalisation search, SearchForInitialization) and bins recomputed from the angles
+    (SearchForTriangulation); both stage B forms where two exist."""
+    S = pkg.synth
+
+    def ori(p, v):
+        return dict(p, check_orientation=int(v))
+
+    p = S.synth_bow_problem(300, 300, 280, n_nodes=12)
+    on, om = oracle.search_by_bow(p)
+    assert p["check_orientation"] and on < oracle.search_by_bow(ori(p, 0))[0]
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(float(p["nnratio"]), True).SearchByBoW(p)):
+        assert n == on and (match == om).all()
+
+    p = S.synth_bow_kf_problem(300, 300, 280, n_nodes=12)
+    on, om = oracle.search_by_bow_kf(p)
+    assert p["check_orientation"] and on < oracle.search_by_bow_kf(ori(p, 0))[0]
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(float(p["nnratio"]), True).SearchByBoWKF(p)):
+        assert n == on and (match == om).all()
+
+    cur, p = S.synth_proj_last_problem(393, n=300, th=7.0)
+    on, om = oracle.search_by_projection_last(cur, p)
+    assert p["check_orientation"] and on < oracle.search_by_projection_last(cur, ori(p, 0))[0] and (om == -2).any()
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(0.9, True).SearchByProjectionLast(cur, p, 7.0, int(p["mono"]))):
+        assert n == on and (match == om).all()
+
+    # a feature pushed more than once (zero-observation points are overwritten, :1432): nmatches counts every push, the
+    # feature keeps one bit per pushed bin and is reset if ANY of them is culled (:1459-1460)
+    cur, p = S.synth_proj_last_problem(300, n=300, th=15.0)
+    p["has_obs"] = np.zeros_like(p["has_obs"])
+    fn, fm = oracle.search_by_projection_last(cur, ori(p, 0))
+    assert fn > (fm >= 0).sum()
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(0.9, False).SearchByProjectionLast(cur, ori(p, 0), 15.0, int(p["mono"]))):
+        assert n == fn and (match == fm).all() and n > (match >= 0).sum()
+    on, om = oracle.search_by_projection_last(cur, p)
+    assert p["check_orientation"] and on < fn and (om == -2).any()
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(0.9, True).SearchByProjectionLast(cur, p, 15.0, int(p["mono"]))):
+        assert n == on and (match == om).all()
+
+    f, p = S.synth_proj_gen_problem(300, n_f=300, n_pts=300, cfg="tum", th=10)
+    on, om = oracle.search_by_projection_reloc(f, p, 100, True)
+    assert on < oracle.search_by_projection_reloc(f, p, 100, False)[0] and (om == -2).any()
+    for n, match in _both_stage_b(monkeypatch, lambda: pkg.Matcher(0.9, True).SearchByProjectionReloc(f, p, 100)):
+        assert n == on and (match == om).all()
+
+    f2, q = S.synth_init_problem(300, 300, 300)
+    on, om = oracle.search_for_initialization(f2, q, 100, 0.9, True)
+    assert on < oracle.search_for_initialization(f2, q, 100, 0.9, False)[0]
+    n, match = pkg.Matcher(0.9, True).SearchForInitialization(f2, q, 100)
+    assert n == on and (match == om).all()
+
+    p = S.synth_triang_problem(300, 300, 300, n_nodes=8)
+    on, om = oracle.search_for_triangulation(p)
+    assert p["check_orientation"] and on < oracle.search_for_triangulation(ori(p, 0))[0]
+    n, match = pkg.Matcher(0.6, True).SearchForTriangulation(p)
+    assert n == on and (match == om).all()
