@@ -103,6 +103,8 @@ def lib():
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_sincos_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
+        L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
         if hasattr(L, "aos2_matcher_create"):
             L.aos2_matcher_create.argtypes = [cf, ci, ci, C.POINTER(vp)]
             L.aos2_matcher_destroy.argtypes = [vp]
@@ -161,6 +163,7 @@ def lib():
             L.aos2_frames_device_ptr.argtypes = [vp, ci]
             L.aos2_frames_search_for_triangulation.argtypes = [vp, vp, vp, ci, ci, vp, vp]
             L.aos2_frames_fuse.argtypes = [vp, vp, ci, ci, vp, vp, cf, vp, vp]
+            L.aos2_frames_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp]
             L.aos2_frames_device_ptr.restype = vp
             L.aos2_frames_build.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, ci, C.c_size_t, cf, cf, cf, cf, cf]
             L.aos2_frames_build_stereo.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, cf, cf, cf, cf, cf]
@@ -778,6 +781,47 @@ def debug_sincos_host(angle_rad):
     return s.value, c.value
 
 
+# ---- the loop body of LocalMapping::CreateNewMapPoints (include/aos2.h: aos2_triangulate_matches and friends)
+TRI_NO_MATCH, TRI_ACCEPTED, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_DEPTH1, TRI_DEPTH2, TRI_REPROJ1, TRI_REPROJ2, TRI_ZERO_DIST, TRI_SCALE, \
+    TRI_SUPERSEDED = range(11)
+
+
+class _TriangGeom(C.Structure):
+    _fields_ = [("Tcw1", C.c_float * 16), ("Tcw2", C.c_float * 16)] + \
+               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "mb1", "mbf1", "fx2", "fy2", "cx2", "cy2", "mb2", "mbf2")] + \
+               [("n_levels", C.c_int32), ("scale_factors1", C.c_float * 8), ("scale_factors2", C.c_float * 8)]
+
+
+# aos2_triang_obs_t: mvKeysUn[i].pt, mvKeys[i].pt, mvuRight[i], mvDepth[i], mvKeysUn[i].octave
+TRIANG_OBS = np.dtype([("ux", "<f4"), ("uy", "<f4"), ("kx", "<f4"), ("ky", "<f4"), ("u_right", "<f4"), ("depth", "<f4"), ("octave", "<i4")])
+
+
+def _triang_args(kf1, kf2, obs1, obs2):
+    """kf1 / kf2: dicts with Tcw (4x4), fx fy cx cy mb mbf, scale_factors; obs1 / obs2: TRIANG_OBS arrays of the n matches"""
+    g = _TriangGeom()
+    sf1, sf2 = (np.asarray(k["scale_factors"], np.float32) for k in (kf1, kf2))
+    if len(sf1) != len(sf2) or len(sf1) > 8:
+        raise ValueError("both keyframes carry the same (at most 8) pyramid levels")
+    g.n_levels = len(sf1)
+    for tag, k, sf in (("1", kf1, sf1), ("2", kf2, sf2)):
+        setattr(g, "Tcw" + tag, (C.c_float * 16)(*[float(v) for v in np.asarray(k["Tcw"], np.float32).reshape(16)]))
+        for name in ("fx", "fy", "cx", "cy", "mb", "mbf"):
+            setattr(g, name + tag, float(np.float32(k[name])))
+        setattr(g, "scale_factors" + tag, (C.c_float * 8)(*[float(v) for v in sf]))
+    obs1, obs2 = np.ascontiguousarray(obs1, TRIANG_OBS), np.ascontiguousarray(obs2, TRIANG_OBS)
+    if obs1.shape != obs2.shape or obs1.ndim != 1:
+        raise ValueError("one observation of each keyframe per match")
+    n = len(obs1)
+    return g, n, obs1, obs2, np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+
+
+def debug_triangulate_host(kf1, kf2, obs1, obs2):
+    """aos2_debug_triangulate_host: the routine of the device kernels on the CPU -> (status uint8 [n], x3D float32 [n][3])"""
+    g, n, obs1, obs2, x3D, status = _triang_args(kf1, kf2, obs1, obs2)
+    _check(lib().aos2_debug_triangulate_host(C.byref(g), n, _p(obs1), _p(obs2), _p(x3D), _p(status)))
+    return status, x3D
+
+
 def debug_sincos_device(angles, device=0):
     a = np.ascontiguousarray(angles, np.float32)
     s = np.zeros_like(a)
@@ -1148,6 +1192,13 @@ class Matcher:
         _check(self.L.aos2_matcher_search_by_projection_reloc(self.h, C.byref(fv), C.byref(pp), int(orb_dist), _p(match), _p(n)))
         return int(n[0]), match[: frame["n_f"]]
 
+    def TriangulateMatches(self, kf1, kf2, obs1, obs2):
+        """aos2_triangulate_matches: the loop body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:290-436) for the matches of
+        ONE (KF1, KF2) pair; arguments as debug_triangulate_host -> (status uint8 [n], x3D float32 [n][3])"""
+        g, n, obs1, obs2, x3D, status = _triang_args(kf1, kf2, obs1, obs2)
+        _check(self.L.aos2_triangulate_matches(self.h, C.byref(g), n, _p(obs1), _p(obs2), _p(x3D), _p(status)))
+        return status, x3D
+
 
 # ------------------------------------------------------------------------------------------ local BA
 class _LbaProblem(C.Structure):
@@ -1451,6 +1502,14 @@ class Frames:
         """aos2_frames_fuse: target int32 [n] host (frames of this batch), d_rows device [n][n_pts] table rows (-1 = rejected by the loop head)"""
         target = np.ascontiguousarray(target, np.int32)
         _check(self.L.aos2_frames_fuse(self.h, C.byref(table), len(target), int(n_pts), target.ctypes.data, d_rows, float(th), d_best_idx, d_best_dist))
+
+    def TriangulateMatches(self, other, kf1, kf2, d_match12, d_x3D, d_status, d_nnew, first_wins=True):
+        """aos2_frames_triangulate_matches: the loop body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:290-436) for the pairs
+        (frame kf1[p] of this batch, frame kf2[p] of `other`) and the d_match12 [n][cap] SearchForTriangulation wrote for them; results in
+        d_x3D float32 [n][cap][3], d_status uint8 [n][cap] (capi.TRI_*), d_nnew int32 [n]: device addresses (ints)"""
+        kf1, kf2 = np.ascontiguousarray(kf1, np.int32), np.ascontiguousarray(kf2, np.int32)
+        _check(self.L.aos2_frames_triangulate_matches(self.h, other.h, len(kf1), kf1.ctypes.data, kf2.ctypes.data, d_match12, int(bool(first_wins)),
+                                                      d_x3D, d_status, d_nnew))
 
     def wait_for_stream(self, hip_stream=None):
         """device-side ordering: what is enqueued on the batch from now on runs behind the work on `hip_stream` so far"""

@@ -520,6 +520,24 @@ class KeyFrameWork:
         self.match12, self.best_idx, self.best_dist, self.nm = (h.numpy() for h in self.h_out)   # (views of the page-locked arrays)
         self.rev_idx, self.rev_dist = (h.numpy() for h in self.h_rev)
 
+    def triangulate(self, first_wins: bool = True):
+        """After run(): the loop body of CreateNewMapPoints (src/LocalMapping.cc:290-436) on the d_match12 of the triangulation pairs --
+        one aos2_frames_triangulate_matches for all of them, the matches never leave the device.  first_wins: the neighbours of a
+        keyframe in their order, as the reference's sequential loop couples them.  Results (host copies): x3D [pairs][cap][3],
+        tri_status [pairs][cap] (capi.TRI_*), nnew [pairs].  Not part of run(): the timed step is unchanged."""
+        tc, t = self.tc, self.tc.torch
+        if not hasattr(self, "d_x3D"):
+            PT, cap1 = self.d_match12.shape
+            self.d_x3D = t.zeros((PT, cap1, 3), dtype=t.float32, device=tc.dev)
+            self.d_tri_status = t.zeros((PT, cap1), dtype=t.uint8, device=tc.dev)
+            self.d_nnew = t.zeros((PT,), dtype=t.int32, device=tc.dev)
+            t.cuda.synchronize()   # (the zero fills must not land on the call's output)
+        tc.last.TriangulateMatches(self.kfs, self.t_kf1, self.t_kf2, self.d_match12.data_ptr(), self.d_x3D.data_ptr(),
+                                   self.d_tri_status.data_ptr(), self.d_nnew.data_ptr(), first_wins=first_wins)
+        tc.last.wait()   # (asynchronous keyframe calls: completes it)
+        self.x3D, self.tri_status, self.nnew = self.d_x3D.cpu().numpy(), self.d_tri_status.cpu().numpy(), self.d_nnew.cpu().numpy()
+        return self
+
     def snapshot(self):
         """the inputs (by reference) and the last results (copies), for oracle/parity.py"""
         import types

@@ -4,6 +4,7 @@
 #include "aos2_common.h"
 #include "octree.h"
 #include "sincos_exact.h"
+#include "triangulate.h"
 
 namespace aos2 {
 __global__ void sincos_kernel(const float *a, int n, float *s, float *c)
@@ -11,9 +12,39 @@ __global__ void sincos_kernel(const float *a, int n, float *s, float *c)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) sincos_exact(a[i], &s[i], &c[i]);
 }
+
+int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
+                 const uint8_t *status)
+{
+    if (!g || n < 0 || (n > 0 && (!obs1 || !obs2 || !x3D || !status)) || g->n_levels < 2 || g->n_levels > 8) {
+        set_error("bad argument (geometry, per-match arrays, 2..8 pyramid levels)");
+        return AOS2_ERR_ARG;
+    }
+    for (int k = 0; k < n; ++k)
+        if (obs1[k].octave < 0 || obs1[k].octave >= g->n_levels || obs2[k].octave < 0 || obs2[k].octave >= g->n_levels) {
+            set_error("match %d: octaves (%d, %d) outside the %d pyramid levels", k, obs1[k].octave, obs2[k].octave, g->n_levels);
+            return AOS2_ERR_ARG;
+        }
+    return AOS2_OK;
+}
 }  // namespace aos2
 
 extern "C" {
+
+int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, float *x3D,
+                                uint8_t *status)
+{
+    using namespace aos2;
+    if (int st = triang_check(g, n, obs1, obs2, x3D, status)) return st;
+    const TriKf K1 = {g->Tcw1, g->fx1, g->fy1, g->cx1, g->cy1, g->mb1, g->mbf1, g->scale_factors1};
+    const TriKf K2 = {g->Tcw2, g->fx2, g->fy2, g->cx2, g->cy2, g->mb2, g->mbf2, g->scale_factors2};
+    for (int k = 0; k < n; ++k) {
+        const aos2_triang_obs_t &a = obs1[k], &b = obs2[k];
+        status[k] = (uint8_t)triangulate_pair(K1, K2, TriObs{a.ux, a.uy, a.kx, a.ky, a.u_right, a.depth, a.octave},
+                                              TriObs{b.ux, b.uy, b.kx, b.ky, b.u_right, b.depth, b.octave}, x3D + 3 * (size_t)k);
+    }
+    return AOS2_OK;
+}
 
 int aos2_debug_octree_host(const int16_t *xs, const int16_t *ys, const uint8_t *score, int n, int minX, int maxX,
                            int minY, int maxY, int N, int32_t *out_idx, int cap)

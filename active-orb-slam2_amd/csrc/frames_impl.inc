@@ -493,8 +493,10 @@ void aos2_frames_destroy(aos2_frames_t *f)
         (void)hipStreamSynchronize(f->stream);
         f->mem.release(); f->tables.release(); f->scratch.release(); f->pool.release(); f->pose_mem.release();
         f->h_io.release(); f->h_overflow.release(); f->kf_host.release(); f->kf_dev.release(); f->kf_host2.release(); f->kf_dev2.release();
+        f->kf_host3.release(); f->kf_dev3.release();
         if (f->kf_ev_tri) (void)hipEventDestroy(f->kf_ev_tri);
         if (f->kf_ev_fuse) (void)hipEventDestroy(f->kf_ev_fuse);
+        if (f->kf_ev_new) (void)hipEventDestroy(f->kf_ev_new);
         for (auto &e : f->ev) (void)hipEventDestroy(e);
         if (f->order_ev) (void)hipEventDestroy(f->order_ev);
         if (f->ext_ev) (void)hipEventDestroy(f->ext_ev);

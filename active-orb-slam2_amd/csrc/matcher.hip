@@ -3432,3 +3432,4 @@ int aos2_matcher_search_for_initialization(aos2_matcher_t *m, const aos2_frame_v
 }  // extern "C"
 
 #include "frames_impl.inc"
+#include "frames_triangulate.inc"

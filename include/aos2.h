@@ -846,6 +846,55 @@ int aos2_frames_fuse(aos2_frames_t *kfs, const aos2_map_points_dev_t *mps, int n
  * complete. */
 int aos2_frames_set_async_keyframe_calls(aos2_frames_t *f, int on);
 
+/* The loop body of void LocalMapping::CreateNewMapPoints()  src/LocalMapping.cc:290-436 for every matched pair: the parallax test
+ * (:303-323), the linear triangulation (cv::SVD of the 4x4, :325-343), the KeyFrame::UnprojectStereo fallbacks (:344-351,
+ * src/KeyFrame.cc:676-692) and the depth / reprojection / scale-consistency gates (:355-435) that decide whether a MapPoint is born.
+ * `new MapPoint`, AddObservation and the rest of :438-453 stay with the caller.  What happened to a feature of keyframe 1: */
+#define AOS2_TRI_NO_MATCH 0      /* match12 < 0, or a feature index >= N */
+#define AOS2_TRI_ACCEPTED 1      /* x3D is a new map point */
+#define AOS2_TRI_LOW_PARALLAX 2  /* no stereo and very low parallax (:352-353); also UnprojectStereo of a feature with mvDepth <= 0 */
+#define AOS2_TRI_W_ZERO 3        /* x3D.at<float>(3) == 0 (:337) */
+#define AOS2_TRI_DEPTH1 4        /* z1 <= 0 (:359) */
+#define AOS2_TRI_DEPTH2 5        /* z2 <= 0 (:363) */
+#define AOS2_TRI_REPROJ1 6       /* reprojection error in keyframe 1 (:372-391) */
+#define AOS2_TRI_REPROJ2 7       /* reprojection error in keyframe 2 (:398-417) */
+#define AOS2_TRI_ZERO_DIST 8     /* dist1 == 0 || dist2 == 0 (:426) */
+#define AOS2_TRI_SCALE 9         /* scale consistency (:434) */
+#define AOS2_TRI_SUPERSEDED 10   /* passed every gate, but an earlier pair of the same keyframe 1 created the feature's point (first_wins) */
+/* Device-resident form, for n_pairs (frame kf1[p] of `a`, frame kf2[p] of `b`) pairs and the d_match12 that
+ * aos2_frames_search_for_triangulation wrote for them (vMatchedIndices = its non-negative entries).  The two batches may have
+ * different cameras; the mbf of the stereo reprojection term is keyframe 1's in both keyframes, as in :384 and :410.
+ * first_wins != 0 restores the coupling between the neighbours of one keyframe that a batched search at one snapshot cannot have:
+ * the reference searches neighbour p + 1 after the points of neighbour p were added, and SearchForTriangulation skips a feature of
+ * keyframe 1 that holds a map point (src/ORBmatcher.cc:700-703).  The pairs of the call that share kf1 are one CreateNewMapPoints
+ * call, in call order = neighbour order: the first accepted pair of a feature keeps it, later accepted ones become
+ * AOS2_TRI_SUPERSEDED (exact, because the features of keyframe 1 are searched independently: vbMatched2 is never set).
+ * d_x3D: DEVICE [n_pairs][cap of a][3], defined where the status is not 0, 2 or 3 (zeros there); d_status: DEVICE [n_pairs][cap of a];
+ * d_nnew: DEVICE [n_pairs] = entries with status 1 (nnew, :453).  Pairs outside the batches are rejected with AOS2_ERR_ARG before
+ * anything runs.  Ordered behind b's stream; with aos2_frames_set_async_keyframe_calls(a, 1) it returns after enqueueing (kf1 / kf2
+ * are copied before it returns; its staging buffer is its own, so the three keyframe calls of a handle may all be in flight). */
+int aos2_frames_triangulate_matches(aos2_frames_t *a, aos2_frames_t *b, int n_pairs, const int32_t *kf1, const int32_t *kf2,
+                                    const int32_t *d_match12, int first_wins, float *d_x3D, uint8_t *d_status,
+                                    int32_t *d_nnew);
+/* Host-pointer form for ONE (KF1, KF2) pair and its n matches (the shim's route, host/NewMapPoints.h): the members the loop reads */
+typedef struct {
+    float Tcw1[16], Tcw2[16];                       /* mTcw of both keyframes, row-major 4x4 */
+    float fx1, fy1, cx1, cy1, mb1, mbf1;            /* mpCurrentKeyFrame */
+    float fx2, fy2, cx2, cy2, mb2, mbf2;            /* pKF2 */
+    int32_t n_levels;                               /* <= 8 */
+    float scale_factors1[8], scale_factors2[8];     /* mvScaleFactors (mvLevelSigma2 = their squares, ORBextractor.cc:420) */
+} aos2_triang_geom_t;
+typedef struct {
+    float ux, uy;      /* mvKeysUn[i].pt */
+    float kx, ky;      /* mvKeys[i].pt (KeyFrame::UnprojectStereo reads the distorted key) */
+    float u_right;     /* mvuRight[i] */
+    float depth;       /* mvDepth[i] */
+    int32_t octave;    /* mvKeysUn[i].octave */
+} aos2_triang_obs_t;
+/* obs1 / obs2: host [n], match k = (feature of KF1, feature of KF2); x3D: host [n][3], status: host [n] (never 0 or 10) */
+int aos2_triangulate_matches(aos2_matcher_t *m, const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,
+                             const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
+
 /* ------------------------------------------------------------------------------------------
  * Replay of a fixed call sequence (csrc/replay.hip).  No single reference function: the per-frame body of Tracking::Track on its
  * usual path -- Frame::Frame (src/Frame.cc:116-172), TrackWithMotionModel (src/Tracking.cc:860-1039: SearchByProjection,
@@ -894,6 +943,9 @@ int aos2_debug_octree_host(const int16_t *xs, const int16_t *ys, const uint8_t *
 /* rBRIEF steering sin/cos (csrc/sincos_exact.h) evaluated on the host / on the device */
 void aos2_debug_sincos_host(float angle_rad, float *s, float *c);
 int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int device);
+/* aos2_triangulate_matches on the HOST with the routine the device kernels also run (csrc/triangulate.h); needs no device */
+int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,
+                                const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
  * T_out[i] = exp(upd[i]) * T[i]  (upd: 6 doubles omega | upsilon, T: 7 doubles qx qy qz qw tx ty tz), and
  * x[i] = (H[i] + lambda[i] I)^-1 b[i] with Hb[i] = 21 doubles (upper triangle of H, row by row) + 6 doubles b;
