@@ -105,6 +105,8 @@ def lib():
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.aos2_debug_sim3_host.argtypes = [vp, vp, ci]
+        L.aos2_sim3_ransac.argtypes = [vp, vp, vp, ci]
         if hasattr(L, "aos2_matcher_create"):
             L.aos2_matcher_create.argtypes = [cf, ci, ci, C.POINTER(vp)]
             L.aos2_matcher_destroy.argtypes = [vp]
@@ -822,6 +824,79 @@ def debug_triangulate_host(kf1, kf2, obs1, obs2):
     return status, x3D
 
 
+# ---- the RANSAC of Sim3Solver (include/aos2.h: aos2_sim3_ransac, aos2_debug_sim3_host)
+class _Sim3Problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("X3Dc1", C.c_void_p), ("X3Dc2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")] + \
+               [("fix_scale", C.c_int32), ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
+                ("draws", C.c_void_p)]
+
+
+class _Sim3Result(C.Structure):
+    _fields_ = [("ransac_max_its", C.c_int32), ("first_success", C.c_int32), ("best_iteration", C.c_int32), ("best_inliers", C.c_int32),
+                ("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float),
+                ("inliers", C.c_void_p), ("counts", C.c_void_p)]
+
+
+def sim3_random_int(rng, lo, hi):
+    """DUtils::Random::RandomInt(min, max) (Thirdparty/DBoW2/DUtils/Random.cpp:47-50): d = max - min + 1,
+    int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min, with rand() taken from `rng` (a numpy Generator)"""
+    d = hi - lo + 1
+    return int((float(rng.integers(0, 2 ** 31)) / (2147483647.0 + 1.0)) * d) + lo
+
+
+def sim3_draws(rng, n, max_iterations):
+    """the draws of max_iterations iterations of Sim3Solver::iterate (:166-177) over n correspondences, in iteration order:
+    int32 [max_iterations][3], draw i of an iteration = RandomInt(0, n - 1 - i); zeros when n < 3 (nothing to draw from)"""
+    d = np.zeros((max_iterations, 3), np.int32)
+    if n >= 3:
+        for k in range(max_iterations):
+            for i in range(3):
+                d[k, i] = sim3_random_int(rng, 0, n - 1 - i)
+    return d
+
+
+def _sim3_args(problems, sentinel=None):
+    """problems: dicts with X3Dc1 / X3Dc2 [n][3], max_err1 / max_err2 [n], K1 / K2 = (fx, fy, cx, cy), fix_scale, probability,
+    min_inliers, max_iterations, draws [max_iterations][3]"""
+    P, R, keep, outs = (_Sim3Problem * max(1, len(problems)))(), (_Sim3Result * max(1, len(problems)))(), [], []
+    for i, q in enumerate(problems):
+        arr = [np.ascontiguousarray(q[k], np.float32) for k in ("X3Dc1", "X3Dc2", "max_err1", "max_err2")]
+        draws = np.ascontiguousarray(q["draws"], np.int32)
+        n, its = len(arr[0]), int(q["max_iterations"])
+        if arr[0].shape != (n, 3) or arr[1].shape != (n, 3) or arr[2].shape != (n,) or arr[3].shape != (n,) or draws.shape != (max(its, 0), 3):
+            raise ValueError("problem %d: X3Dc [n][3], max_err [n], draws [max_iterations][3]" % i)
+        inl = np.full(n, 0 if sentinel is None else sentinel, np.uint8)
+        counts = np.full(max(its, 0), -1 if sentinel is None else sentinel, np.int32)
+        keep += arr + [draws]
+        outs.append((inl, counts))
+        P[i].n = n
+        P[i].X3Dc1, P[i].X3Dc2, P[i].max_err1, P[i].max_err2, P[i].draws = (a.ctypes.data for a in arr + [draws])
+        for tag, K in (("1", q["K1"]), ("2", q["K2"])):
+            for name, v in zip(("fx", "fy", "cx", "cy"), K):
+                setattr(P[i], name + tag, float(np.float32(v)))
+        P[i].fix_scale, P[i].probability = int(bool(q["fix_scale"])), float(q["probability"])
+        P[i].min_inliers, P[i].max_iterations = int(q["min_inliers"]), its
+        R[i].inliers, R[i].counts = inl.ctypes.data, counts.ctypes.data
+        if sentinel is not None:
+            R[i].ransac_max_its = R[i].first_success = R[i].best_iteration = R[i].best_inliers = sentinel
+    return P, R, keep, outs
+
+
+def _sim3_results(R, outs):
+    return [dict(ransac_max_its=R[i].ransac_max_its, first_success=R[i].first_success, best_iteration=R[i].best_iteration,
+                 best_inliers=R[i].best_inliers, T12=np.array(R[i].T12, np.float32).reshape(4, 4), R12=np.array(R[i].R12, np.float32).reshape(3, 3),
+                 t12=np.array(R[i].t12, np.float32), s12=np.float32(R[i].s12), inliers=inl, counts=counts)
+            for i, (inl, counts) in enumerate(outs)]
+
+
+def debug_sim3_host(problems):
+    """aos2_debug_sim3_host: the routine of the device kernels on the CPU -> one dict per problem (the fields of aos2_sim3_result_t)"""
+    P, R, keep, outs = _sim3_args(problems)
+    _check(lib().aos2_debug_sim3_host(P, R, len(problems)))
+    return _sim3_results(R, outs)
+
+
 def debug_sincos_device(angles, device=0):
     a = np.ascontiguousarray(angles, np.float32)
     s = np.zeros_like(a)
@@ -1198,6 +1273,14 @@ class Matcher:
         g, n, obs1, obs2, x3D, status = _triang_args(kf1, kf2, obs1, obs2)
         _check(self.L.aos2_triangulate_matches(self.h, C.byref(g), n, _p(obs1), _p(obs2), _p(x3D), _p(status)))
         return status, x3D
+
+    def Sim3Ransac(self, problems, sentinel=None):
+        """aos2_sim3_ransac: the RANSAC of Sim3Solver (src/Sim3Solver.cc) for a batch of loop candidates; problems as debug_sim3_host
+        -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in self.sim3_last for a caller that expects a refusal)"""
+        P, R, keep, outs = _sim3_args(problems, sentinel)
+        self.sim3_last = (R, outs)
+        _check(self.L.aos2_sim3_ransac(self.h, P, R, len(problems)))
+        return _sim3_results(R, outs)
 
 
 # ------------------------------------------------------------------------------------------ local BA

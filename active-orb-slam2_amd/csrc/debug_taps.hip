@@ -1,9 +1,12 @@
 // Test taps: host/device execution of shared primitives so parity tests can pin them in isolation.
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "aos2_common.h"
 #include "octree.h"
 #include "sincos_exact.h"
+#include "sim3.h"
 #include "triangulate.h"
 
 namespace aos2 {
@@ -27,6 +30,64 @@ int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *ob
         }
     return AOS2_OK;
 }
+
+// mRansacMaxIts (SetRansacParameters, src/Sim3Solver.cc:125-135).  A quotient that is no int (NaN when epsilon > 1, infinite when
+// probability is 1 or epsilon^3 vanishes against 1) converts the way the x86 instruction does it for the reference: INT_MIN.
+static int32_t sim3_ransac_its(int n, double probability, int min_inliers, int max_iterations)
+{
+    const float epsilon = (float)min_inliers / n;
+    int nIterations;
+    if (min_inliers == n) nIterations = 1;
+    else {
+        const double v = ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3)));
+        nIterations = (v >= -2147483648.0 && v <= 2147483647.0) ? (int)v : INT32_MIN;
+    }
+    return std::max(1, std::min(nIterations, max_iterations));
+}
+
+int sim3_check(const aos2_sim3_problem_t *problems, const aos2_sim3_result_t *results, int n_problems, int32_t *its, uint8_t *run)
+{
+    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
+        set_error("bad argument (0..64 problems and their results)");
+        return AOS2_ERR_ARG;
+    }
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_sim3_problem_t &P = problems[p];
+        if (P.n < 0 || P.max_iterations < 1 || (P.n > 0 && (!P.X3Dc1 || !P.X3Dc2 || !P.max_err1 || !P.max_err2 || !results[p].inliers))) {
+            set_error("problem %d: bad argument (n >= 0, max_iterations >= 1, the per-correspondence arrays)", p);
+            return AOS2_ERR_ARG;
+        }
+        its[p] = sim3_ransac_its(P.n, P.probability, P.min_inliers, P.max_iterations);
+        run[p] = P.n >= P.min_inliers;
+        if (!run[p]) continue;
+        if (P.n < 3 || !P.draws) {
+            set_error("problem %d: %d correspondences to draw triples from, or no draws", p, P.n);
+            return AOS2_ERR_ARG;
+        }
+        for (int k = 0; k < P.max_iterations; ++k)
+            for (int i = 0; i < 3; ++i) {
+                const int32_t r = P.draws[3 * (size_t)k + i];
+                if (r < 0 || r > P.n - 1 - i) {
+                    set_error("problem %d: draw %d of iteration %d is %d, outside [0, %d]", p, i, k, r, P.n - 1 - i);
+                    return AOS2_ERR_ARG;
+                }
+            }
+    }
+    return AOS2_OK;
+}
+
+void sim3_result_clear(const aos2_sim3_problem_t &P, int32_t its, aos2_sim3_result_t &R)
+{
+    uint8_t *inl = R.inliers;
+    int32_t *counts = R.counts;
+    R = aos2_sim3_result_t{};
+    R.inliers = inl;
+    R.counts = counts;
+    R.ransac_max_its = its;
+    R.first_success = R.best_iteration = -1;
+    if (P.n > 0) memset(inl, 0, (size_t)P.n);
+    if (counts) std::fill(counts, counts + P.max_iterations, -1);
+}
 }  // namespace aos2
 
 extern "C" {
@@ -42,6 +103,48 @@ int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_t
         const aos2_triang_obs_t &a = obs1[k], &b = obs2[k];
         status[k] = (uint8_t)triangulate_pair(K1, K2, TriObs{a.ux, a.uy, a.kx, a.ky, a.u_right, a.depth, a.octave},
                                               TriObs{b.ux, b.uy, b.kx, b.ky, b.u_right, b.depth, b.octave}, x3D + 3 * (size_t)k);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems)
+{
+    using namespace aos2;
+    int32_t its[64];
+    uint8_t run[64];
+    if (int st = sim3_check(problems, results, n_problems, its, run)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_sim3_problem_t &P = problems[p];
+        aos2_sim3_result_t &R = results[p];
+        sim3_result_clear(P, its[p], R);
+        if (!run[p]) continue;
+        const Sim3Cam K1 = {P.fx1, P.fy1, P.cx1, P.cy1}, K2 = {P.fx2, P.fy2, P.cx2, P.cy2};
+        Sim3Scan scan;
+        for (int it = 0; it < its[p]; ++it) {
+            Sim3Model m;
+            sim3_model_of(P.n, P.X3Dc1, P.X3Dc2, P.draws, it, P.fix_scale != 0, m);
+            std::vector<uint8_t> flags((size_t)P.n);
+            int32_t count = 0;
+            for (int i = 0; i < P.n; ++i)
+                count += flags[i] = sim3_inlier(m.T12, m.T21, K1, K2, P.X3Dc1 + 3 * (size_t)i, P.X3Dc2 + 3 * (size_t)i, P.max_err1[i], P.max_err2[i]);
+            if (R.counts) R.counts[it] = count;
+            const bool done = scan.step(it, count, P.min_inliers);
+            if (scan.best_iteration == it) {   // :185-190
+                memcpy(R.inliers, flags.data(), flags.size());
+                for (int r = 0; r < 3; ++r) {
+                    memcpy(R.T12 + 4 * r, m.T12 + 4 * r, 16);
+                    R.T12[12 + r] = 0.0f;
+                }
+                R.T12[15] = 1.0f;
+                memcpy(R.R12, m.R, sizeof m.R);
+                memcpy(R.t12, m.t, sizeof m.t);
+                R.s12 = m.s;
+            }
+            if (done) break;
+        }
+        R.first_success = scan.first_success;
+        R.best_iteration = scan.best_iteration;
+        R.best_inliers = scan.best_inliers;
     }
     return AOS2_OK;
 }

@@ -527,6 +527,39 @@ int aos2_matcher_search_by_sim3(aos2_matcher_t *m, const aos2_frame_view_t *kf1,
                                 const aos2_frame_view_t *kf2, const aos2_proj_points_t *p12,
                                 const aos2_proj_points_t *p21, int32_t *match12, int32_t *n_found);
 
+/* The RANSAC of Sim3Solver (src/Sim3Solver.cc: SetRansacParameters :114-138, iterate :140-207, ComputeSim3 :226-337, CheckInliers
+ * :340-364) for a batch of candidate keyframes of LoopClosing::ComputeSim3 (src/LoopClosing.cc:276-303), between SearchByBoW (:267)
+ * and SearchBySim3 (:325).  The random triples are an input, so the hypotheses are independent: every hypothesis of every problem
+ * is computed in one pass and the solver's sequential loop (:183-199) is replayed over the inlier counts.  The arithmetic is
+ * csrc/sim3.h. */
+typedef struct {
+    int32_t n;                       /* correspondences that survived the constructor's gates (:62-103): N */
+    const float *X3Dc1, *X3Dc2;      /* host [n][3]: mvX3Dc1 / mvX3Dc2 = Rcw*X3Dw + tcw, formed by the caller (:94-98) */
+    const float *max_err1, *max_err2;/* host [n]: 9.210 * mvLevelSigma2[octave] as float (:84-88); the class keeps them in a
+                                      * vector<size_t> (include/Sim3Solver.h:78-79), host/Sim3Solver.h passes those whole numbers */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;   /* mK1, mK2 */
+    int32_t fix_scale;               /* mbFixScale */
+    double probability; int32_t min_inliers, max_iterations;   /* SetRansacParameters (:114); max_iterations >= 1 */
+    const int32_t *draws;            /* host [max_iterations][3]: draw i of an iteration = RandomInt(0, n-1-i) (:168); not read when
+                                      * n < min_inliers */
+} aos2_sim3_problem_t;
+typedef struct {
+    int32_t ransac_max_its;          /* mRansacMaxIts after :125-135 (a quotient that is no int converts as x86 does: INT_MIN, so 1) */
+    int32_t first_success;           /* 0-based iteration at which iterate() would return a Sim3, -1 = never */
+    int32_t best_iteration, best_inliers;   /* the solver's mBest* state when it stops (at first_success, or after ransac_max_its);
+                                             * best_iteration = -1 when nothing ran */
+    float T12[16], R12[9], t12[3], s12;     /* mBestT12 / mBestRotation / mBestTranslation / mBestScale (zeros when nothing ran) */
+    uint8_t *inliers;                /* host [n], caller-allocated: mvbBestInliers */
+    int32_t *counts;                 /* host [max_iterations] or NULL: mnInliersi per iteration that ran, -1 beyond the stop */
+} aos2_sim3_result_t;
+/* n_problems <= 64; n_problems == 0 is AOS2_OK.  n < min_inliers (:146-150): ransac_max_its as computed, first_success = -1,
+ * best_inliers = 0, no inlier flag set, nothing launched for that problem.  The three indices of iteration k follow from draws[k] by
+ * the swap-with-back removal of :163-177.  A draw outside [0, n-1-i], n < 0, n < 3 with something to run, max_iterations < 1 or a
+ * missing array is AOS2_ERR_ARG, reported before anything runs (no result is written).  A degenerate triple is no error: its model
+ * holds NaNs, every comparison of :356 is false and its count is 0, as in the reference.  Hypotheses after first_success are
+ * computed by the batch but reported as if they had not run.  Synchronous. */
+int aos2_sim3_ransac(aos2_matcher_t *m, const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems);
+
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*>
  *         &sAlreadyFound, const float th, const int ORBdist)  :1472-1599 (relocalisation).
  * Points = pKF->GetMapPointMatches() (valid = pMP && !isBad() && !sAlreadyFound.count(pMP));
@@ -946,6 +979,9 @@ int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int
 /* aos2_triangulate_matches on the HOST with the routine the device kernels also run (csrc/triangulate.h); needs no device */
 int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,
                                 const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
+/* aos2_sim3_ransac on the HOST with the routine the device kernels also run (csrc/sim3.h); needs no device.  It stops computing at
+ * first_success, where the device reports as if it had. */
+int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
  * T_out[i] = exp(upd[i]) * T[i]  (upd: 6 doubles omega | upsilon, T: 7 doubles qx qy qz qw tx ty tz), and
  * x[i] = (H[i] + lambda[i] I)^-1 b[i] with Hb[i] = 21 doubles (upper triangle of H, row by row) + 6 doubles b;
