@@ -101,6 +101,7 @@ def lib():
             L.aos2_vocabulary_score.argtypes = [vp, vp, vp, ci, vp, vp, ci, C.POINTER(C.c_double)]
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
+        L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         L.aos2_debug_sincos_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
@@ -639,6 +640,15 @@ class Extractor:
         sc = np.zeros(max(n.value, 1), np.uint8)
         _check(self.L.aos2_extractor_debug_candidates(self.h, image, level, _p(xs), _p(ys), _p(sc), len(xs), C.byref(n)))
         return xs[: n.value], ys[: n.value], sc[: n.value]
+
+    def debug_plan(self, w, h):
+        """aos2_debug_extractor_plan: the plan for w x h images, computed on the host (no device) -> dict(levels int64 [nlevels][4] =
+        w, h, pitch, off; cells int32 [n][6] = level, vx0, vy0, cw, ch, slot_off; pyr_bytes; slot_total)"""
+        levels, totals, n = np.zeros((self.nlevels, 4), np.int64), np.zeros(2, np.int64), C.c_int(0)
+        _check(self.L.aos2_debug_extractor_plan(self.h, int(w), int(h), _p(levels), None, 0, C.byref(n), _p(totals)))
+        cells = np.zeros((max(n.value, 1), 6), np.int32)
+        _check(self.L.aos2_debug_extractor_plan(self.h, int(w), int(h), _p(levels), _p(cells), len(cells), C.byref(n), _p(totals)))
+        return dict(levels=levels, cells=cells[: n.value], pyr_bytes=int(totals[0]), slot_total=int(totals[1]))
 
     def set_chunks(self, n):
         _check(self.L.aos2_extractor_set_chunks(self.h, n))

@@ -55,17 +55,24 @@ struct OctDevScratch {
     size_t cand_stride, node_stride;  // per image
 };
 
+// Launch arguments that travel together (host side only: the launchers unpack them, the kernels' parameter lists are flat).
+// A batch of images: level 0 = the caller's (device) images, img0_stride bytes apart; level l >= 1 of image b at
+// pyr + b * pyr_bytes + LevelDev::off
+struct ImagePlanes { const uint8_t *img0; size_t img0_stride; int pitch0; uint8_t *pyr; size_t pyr_bytes; };
+struct ResizeTables { const int *xofs, *xab, *yofs, *yab; };   // cv::resize coefficients of every level (LevelDev::tab_x / tab_y)
+// pyramid_fused_kernel: per (level, tile column / row) {own0, own1, need0, need1}, and the size of its LDS buffers
+struct PyrTiles { const int4 *tile_x, *tile_y; int ntx, nty, buf_pitch, buf_rows; size_t lds; };
+// fast_cells_kernel: LDS tile pitch / rows, score map pitch, LDS bytes, survivor list / kept capacity
+struct FastTile { int TP, TH, SP; size_t lds; int list_cap, keep_cap; };
+// the octree's selection: sel[batch][sel_stride] (cap_level entries per level), sel_cnt[batch][n_levels]
+struct SelLists { uint32_t *sel; size_t sel_stride; int cap_level; int32_t *sel_cnt; };
+
 int upload_constants(const int8_t *pattern, const int *umax, const int *gauss7, hipStream_t st);
-void launch_resize(const uint8_t *src_base, size_t src_img_stride, int src_pitch, uint8_t *pyr, size_t pyr_stride,
-                   const LevelDev &src, const LevelDev &dst, const int *xofs, const int *xab, const int *yofs,
-                   const int *yab, int batch, hipStream_t st);
-void launch_pyramid_fused(const uint8_t *img0, size_t img0_stride, int pitch0, uint8_t *pyr, size_t pyr_stride,
-                          const LevelDev *levels, int nlevels, const int4 *tile_x, const int4 *tile_y, int ntx, int nty,
-                          const int *xofs, const int *xab, const int *yofs, const int *yab, int buf_pitch, int buf_rows,
-                          size_t lds_bytes, int batch, hipStream_t st);
-void launch_fast(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                 const LevelDev *levels, const CellDev *cells, int n_cells,
-                 int ini_th, int min_th, int TP, int TH, int SP, size_t lds_bytes, int list_cap, int keep_cap,
+// level `level` (>= 1) of every image from level `level - 1`; `levels` is the host copy of the level table
+void launch_resize(const ImagePlanes &pl, const LevelDev *levels, int level, const ResizeTables &tab, int batch, hipStream_t st);
+void launch_pyramid_fused(const ImagePlanes &pl, const LevelDev *levels, int nlevels, const PyrTiles &tiles, const ResizeTables &tab,
+                          int batch, hipStream_t st);
+void launch_fast(const ImagePlanes &pl, const CellDev *cells, int n_cells, int ini_th, int min_th, const FastTile &tile,
                  uint32_t *slots, size_t slot_stride, int32_t *cell_cnt, int batch, hipStream_t st);
 // LDS working set of one octree job with n candidates and target N (OctCompact layout in
 // octree_kernel: packed candidates | perm | tmp | 16-byte node arena | two pairs arrays)
@@ -86,16 +93,12 @@ struct OctImageLayout {
 // each: OctImageLayout::off[l] is level l's offset INSIDE its workgroup, total the largest pair.  The per-job kernel reserves the
 // level-0 size for every level; the pairs hold 1.3-1.6 x as many jobs per compute unit in workgroups no larger than two level-0 jobs.
 int prepare_octree_pair_kernel(int total_lds);
-void launch_octree_pairs(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                         int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                         int32_t *sel_level_cnt, int cap_level, const OctImageLayout &lay, hipStream_t st);
-void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                   int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                   int32_t *sel_level_cnt, int cap_level, int lds_bytes, hipStream_t st);
-void launch_describe(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                     const LevelDev *levels, int n_levels,
-                     const uint32_t *sel, size_t sel_stride, int cap_level, const int32_t *sel_level_cnt,
-                     aos2_keypoint_t *kps, uint8_t *desc, int cap, int32_t *n_out, int batch,
-                     unsigned long long umax_nibbles, int32_t *status, hipStream_t st);
+// `pair` (or null: one job per workgroup with lds_bytes, of which group_levels levels keep 4 waves -- the helper-wave form)
+void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels, int n_levels, int batch,
+                   const OctDevScratch &scr, const SelLists &sel, const OctImageLayout *pair, int lds_bytes, int group_levels,
+                   hipStream_t st);
+void launch_describe(const ImagePlanes &pl, const LevelDev *levels, int n_levels, const SelLists &sel, aos2_keypoint_t *kps,
+                     uint8_t *desc, int cap, int32_t *n_out, int batch, unsigned long long umax_nibbles, int32_t *status,
+                     hipStream_t st);
 
 }  // namespace aos2

@@ -1190,10 +1190,13 @@ __global__ __launch_bounds__(256) void pyramid_fused_kernel(const uint8_t *__res
 }
 
 // host launchers -------------------------------------------------------------------------------
-void launch_resize(const uint8_t *src_base, size_t src_img_stride, int src_pitch, uint8_t *pyr, size_t pyr_stride,
-                   const LevelDev &src, const LevelDev &dst, const int *xofs, const int *xab, const int *yofs,
-                   const int *yab, int batch, hipStream_t st)
+void launch_resize(const ImagePlanes &pl, const LevelDev *levels, int level, const ResizeTables &tab, int batch, hipStream_t st)
 {
+    const LevelDev &src = levels[level - 1], &dst = levels[level];
+    const bool from0 = level == 1;   // level 0 is the caller's image
+    const uint8_t *src_base = from0 ? pl.img0 : pl.pyr + src.off;
+    const size_t src_img_stride = from0 ? pl.img0_stride : pl.pyr_bytes;
+    const int src_pitch = from0 ? pl.pitch0 : src.pitch;
     const int nquads = (dst.w + 3) / 4;
     const uint32_t inv_nquads = 0xFFFFFFFFu / (uint32_t)nquads + 1u;
     const uint32_t items = (uint32_t)nquads * (uint32_t)batch;   // < 2^32 / nquads (checked by the caller's plan)
@@ -1203,46 +1206,45 @@ void launch_resize(const uint8_t *src_base, size_t src_img_stride, int src_pitch
     const bool wide = (int)std::ceil(3.0 * rx) + 1 > 7;
     dim3 blk(256), grd((items + 255) / 256, (dst.h + band - 1) / band);
     if (wide)
-        hipLaunchKernelGGL(resize_level_kernel<true>, grd, blk, 0, st, src_base, src_img_stride, src_pitch, pyr, pyr_stride, src,
-                           dst, xofs, xab, yofs, yab, batch, nquads, inv_nquads, band);
+        hipLaunchKernelGGL(resize_level_kernel<true>, grd, blk, 0, st, src_base, src_img_stride, src_pitch, pl.pyr, pl.pyr_bytes, src,
+                           dst, tab.xofs, tab.xab, tab.yofs, tab.yab, batch, nquads, inv_nquads, band);
     else
-        hipLaunchKernelGGL(resize_level_kernel<false>, grd, blk, 0, st, src_base, src_img_stride, src_pitch, pyr, pyr_stride, src,
-                           dst, xofs, xab, yofs, yab, batch, nquads, inv_nquads, band);
+        hipLaunchKernelGGL(resize_level_kernel<false>, grd, blk, 0, st, src_base, src_img_stride, src_pitch, pl.pyr, pl.pyr_bytes, src,
+                           dst, tab.xofs, tab.xab, tab.yofs, tab.yab, batch, nquads, inv_nquads, band);
 }
 
-void launch_pyramid_fused(const uint8_t *img0, size_t img0_stride, int pitch0, uint8_t *pyr, size_t pyr_stride,
-                          const LevelDev *levels, int nlevels, const int4 *tile_x, const int4 *tile_y, int ntx, int nty,
-                          const int *xofs, const int *xab, const int *yofs, const int *yab, int buf_pitch, int buf_rows,
-                          size_t lds_bytes, int batch, hipStream_t st)
+void launch_pyramid_fused(const ImagePlanes &pl, const LevelDev *levels, int nlevels, const PyrTiles &t, const ResizeTables &tab,
+                          int batch, hipStream_t st)
 {
-    hipLaunchKernelGGL(pyramid_fused_kernel, dim3(ntx * nty, batch), dim3(256), lds_bytes, st, img0, img0_stride, pitch0, pyr,
-                       pyr_stride, levels, nlevels, tile_x, tile_y, ntx, nty, xofs, xab, yofs, yab, buf_pitch, buf_rows, batch);
+    hipLaunchKernelGGL(pyramid_fused_kernel, dim3(t.ntx * t.nty, batch), dim3(256), t.lds, st, pl.img0, pl.img0_stride, pl.pitch0,
+                       pl.pyr, pl.pyr_bytes, levels, nlevels, t.tile_x, t.tile_y, t.ntx, t.nty, tab.xofs, tab.xab, tab.yofs, tab.yab,
+                       t.buf_pitch, t.buf_rows, batch);
 }
 
-void launch_fast(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                 const LevelDev * /*levels: the cell records carry their level's plane offset and pitch*/, const CellDev *cells, int n_cells,
-                 int ini_th, int min_th, int TP, int TH, int SP, size_t lds_bytes, int list_cap, int keep_cap,
+// (the cell records carry their level's plane offset and pitch: no level table)
+void launch_fast(const ImagePlanes &pl, const CellDev *cells, int n_cells, int ini_th, int min_th, const FastTile &t,
                  uint32_t *slots, size_t slot_stride, int32_t *cell_cnt, int batch, hipStream_t st)
 {
     dim3 blk(64), grd((batch + 7) & ~7, n_cells);
-    hipLaunchKernelGGL(fast_cells_kernel, grd, blk, lds_bytes, st, img0, img0_stride, pitch0, pyr, pyr_stride, cells, n_cells, ini_th,
-                       min_th, TP, TH, SP, slots, slot_stride, cell_cnt, list_cap, keep_cap, batch);
+    hipLaunchKernelGGL(fast_cells_kernel, grd, blk, t.lds, st, pl.img0, pl.img0_stride, pl.pitch0, (const uint8_t *)pl.pyr,
+                       pl.pyr_bytes, cells, n_cells, ini_th, min_th, t.TP, t.TH, t.SP, slots, slot_stride, cell_cnt, t.list_cap,
+                       t.keep_cap, batch);
 }
 
-void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                   int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                   int32_t *sel_level_cnt, int cap_level, int lds_bytes, hipStream_t st)
+// pair: the pair kernel with that layout.  Else the per-job kernel; group_levels = levels whose jobs keep 4 waves: the two largest
+// for a few frames per call (a level-0 job 116 -> 101 us: the three partition passes 58 -> 44 us); for batches the jobs of a launch
+// fill the device anyway and idle helper waves only take slots from the kernels of the other streams (measured: -0.012 ms on the
+// stage, nothing on the step).
+void launch_octree(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels, int n_levels, int batch,
+                   const OctDevScratch &scr, const SelLists &sel, const OctImageLayout *pair, int lds_bytes, int group_levels,
+                   hipStream_t st)
 {
-    const int jobs = batch * n_levels;
-    // levels whose jobs keep 4 waves: the two largest for a few frames per call (a level-0 job 116 -> 101 us: the three
-    // partition passes 58 -> 44 us); for batches the jobs of a launch fill the device anyway and idle helper waves only take
-    // slots from the kernels of the other streams (measured: -0.012 ms on the stage, nothing on the step).
-    // AOS2_OCT_GROUP_LEVELS overrides (tests).
-    const char *gv = getenv("AOS2_OCT_GROUP_LEVELS");
-    const int group_env = gv ? atoi(gv) : -1;
-    const int group_levels = group_env >= 0 ? group_env : (batch < 8 ? 2 : 0);
-    hipLaunchKernelGGL(octree_kernel, dim3(jobs), dim3(256), (size_t)lds_bytes, st, dense, dense_stride, gather,
-                       levels, n_levels, batch, scr, sel, sel_stride, sel_level_cnt, cap_level, lds_bytes, group_levels);
+    if (pair)
+        hipLaunchKernelGGL(octree_pair_kernel, dim3(batch * ((n_levels + 1) / 2)), dim3(128), (size_t)pair->total, st, dense,
+                           dense_stride, gather, levels, n_levels, batch, scr, sel.sel, sel.sel_stride, sel.sel_cnt, sel.cap_level, *pair);
+    else
+        hipLaunchKernelGGL(octree_kernel, dim3(batch * n_levels), dim3(256), (size_t)lds_bytes, st, dense, dense_stride, gather,
+                           levels, n_levels, batch, scr, sel.sel, sel.sel_stride, sel.sel_cnt, sel.cap_level, lds_bytes, group_levels);
 }
 
 int prepare_octree_pair_kernel(int total_lds)
@@ -1250,30 +1252,23 @@ int prepare_octree_pair_kernel(int total_lds)
     return (int)hipFuncSetAttribute((const void *)octree_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, total_lds);
 }
 
-void launch_octree_pairs(uint32_t *dense, size_t dense_stride, const OctGather &gather, const LevelDev *levels,
-                         int n_levels, int batch, const OctDevScratch &scr, uint32_t *sel, size_t sel_stride,
-                         int32_t *sel_level_cnt, int cap_level, const OctImageLayout &lay, hipStream_t st)
-{
-    hipLaunchKernelGGL(octree_pair_kernel, dim3(batch * ((n_levels + 1) / 2)), dim3(128), (size_t)lay.total, st, dense, dense_stride,
-                       gather, levels, n_levels, batch, scr, sel, sel_stride, sel_level_cnt, cap_level, lay);
-}
-
-void launch_describe(const uint8_t *img0, size_t img0_stride, int pitch0, const uint8_t *pyr, size_t pyr_stride,
-                     const LevelDev *levels, int n_levels,
-                     const uint32_t *sel, size_t sel_stride, int cap_level, const int32_t *sel_level_cnt,
-                     aos2_keypoint_t *kps, uint8_t *desc, int cap, int32_t *n_out, int batch,
-                     unsigned long long umax_nibbles, int32_t *status, hipStream_t st)
+void launch_describe(const ImagePlanes &pl, const LevelDev *levels, int n_levels, const SelLists &sel, aos2_keypoint_t *kps,
+                     uint8_t *desc, int cap, int32_t *n_out, int batch, unsigned long long umax_nibbles, int32_t *status,
+                     hipStream_t st)
 {
     // waves of DK_FEW keypoints while they all fit on the chip at once (256 CUs x 28 waves), of DK_BATCH beyond
     const bool few = (long long)batch * ((cap + DK_FEW - 1) / DK_FEW) <= 2 * 7168;
     const int dk = few ? DK_FEW : DK_BATCH, groups = (cap + dk - 1) / dk;
     dim3 blk(64), grd((unsigned)(((batch + 7) & ~7) * groups));
+    const uint8_t *pyr = pl.pyr;
+    const uint32_t *s = sel.sel;
+    const int32_t *cnt = sel.sel_cnt;
     if (few)
-        hipLaunchKernelGGL(describe_kernel<DK_FEW>, grd, blk, 0, st, img0, img0_stride, pitch0, pyr, pyr_stride, levels, n_levels, sel,
-                           sel_stride, cap_level, sel_level_cnt, kps, desc, cap, n_out, umax_nibbles, status, batch, groups);
+        hipLaunchKernelGGL(describe_kernel<DK_FEW>, grd, blk, 0, st, pl.img0, pl.img0_stride, pl.pitch0, pyr, pl.pyr_bytes, levels,
+                           n_levels, s, sel.sel_stride, sel.cap_level, cnt, kps, desc, cap, n_out, umax_nibbles, status, batch, groups);
     else
-        hipLaunchKernelGGL(describe_kernel<DK_BATCH>, grd, blk, 0, st, img0, img0_stride, pitch0, pyr, pyr_stride, levels, n_levels, sel,
-                           sel_stride, cap_level, sel_level_cnt, kps, desc, cap, n_out, umax_nibbles, status, batch, groups);
+        hipLaunchKernelGGL(describe_kernel<DK_BATCH>, grd, blk, 0, st, pl.img0, pl.img0_stride, pl.pitch0, pyr, pl.pyr_bytes, levels,
+                           n_levels, s, sel.sel_stride, sel.cap_level, cnt, kps, desc, cap, n_out, umax_nibbles, status, batch, groups);
 }
 
 }  // namespace aos2

@@ -7,18 +7,14 @@
 #include <cstdint>
 
 #include "../../include/aos2.h"
+#include "extractor_kernels.h"
 
 namespace aos2 {
 
 constexpr int kStereoMaxLevels = 16;
 
 // mvImagePyramid of one eye for a batch of images, as the extractor keeps it in HBM.
-struct PyrView {
-    const uint8_t *img0;   // level 0 = the (device) input images
-    size_t img0_stride;    // bytes between images
-    int pitch0;
-    const uint8_t *pyr;    // levels >= 1: pyr + image * pyr_bytes + off[level]
-    size_t pyr_bytes;
+struct PyrView : ImagePlanes {   // level 0 = the (device) input images; levels >= 1: pyr + image * pyr_bytes + off[level]
     int nlevels;
     int w[kStereoMaxLevels], h[kStereoMaxLevels], pitch[kStereoMaxLevels];
     size_t off[kStereoMaxLevels];

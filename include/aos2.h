@@ -180,7 +180,10 @@ int aos2_compute_stereo_matches_device(aos2_extractor_t *left, aos2_extractor_t 
  * aos2_extractor_wait) runs behind them.  The kernels read BOTH extractors' pyramid blocks: the next extraction of either
  * extractor waits for them on the device, on every stream it uses, before it rewrites the pyramids -- the calls can be
  * pipelined without a host wait in between.  The keypoint / descriptor / count / output buffers of the call are the
- * caller's to keep untouched until left's stream has drained.  No device time is recorded. */
+ * caller's to keep untouched until left's stream has drained.  No device time is recorded.
+ * An extractor is paired with one partner at a time: pairing either eye with a third extractor ends the earlier pairing.  The
+ * ordering above is kept for calls that were executed; for a call that was RECORDED (aos2_capture_begin) with the earlier
+ * partner it ends there, so wait for the replays of such a recording before that partner extracts again. */
 int aos2_compute_stereo_matches_device_async(aos2_extractor_t *left, aos2_extractor_t *right, int batch,
                                              const aos2_keypoint_t *d_kp_left, const uint8_t *d_desc_left,
                                              const int32_t *d_n_left, const aos2_keypoint_t *d_kp_right,
@@ -973,6 +976,12 @@ int aos2_png_unfilter(uint8_t *rows, int h, int stride, int bpp);
  * also runs (csrc/octree.h).  Returns the number of kept candidates (indices in out_idx) or <0. */
 int aos2_debug_octree_host(const int16_t *xs, const int16_t *ys, const uint8_t *score, int n,
                            int minX, int maxX, int minY, int maxY, int N, int32_t *out_idx, int cap);
+/* The extractor's plan for w x h images (level planes, FAST grid cells, slot offsets) as the host computes it; needs no device.
+ * levels[nlevels][4] = w, h, pitch, byte offset of the plane in one image's pyramid block; cells[cell_cap][6] = level, vx0, vy0,
+ * cw, ch, slot_off (NULL: only *n_cells is returned); totals[2] = pyramid bytes, candidate slots per image.  Fails like an extract
+ * call of that size would: AOS2_ERR_TOO_SMALL, AOS2_ERR_ARG. */
+int aos2_debug_extractor_plan(const aos2_extractor_t *e, int w, int h, int64_t *levels, int32_t *cells, int cell_cap,
+                              int *n_cells, int64_t *totals);
 /* rBRIEF steering sin/cos (csrc/sincos_exact.h) evaluated on the host / on the device */
 void aos2_debug_sincos_host(float angle_rad, float *s, float *c);
 int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int device);

@@ -72,6 +72,54 @@ def test_keypoint_capacity_bound_covers_the_octree(pkg, oracle):
     assert len(sel) == 28 > 20 + 3
 
 
+def _check_plan(P, levels, level_sizes):
+    """the properties of an extractor plan (Extractor.debug_plan) that hold for every geometry"""
+    lv, cells = P["levels"], P["cells"]
+    assert len(lv) == levels and (np.diff(cells[:, 0]) >= 0).all() and set(cells[:, 0]) == set(range(levels))
+    end = 0
+    for l in range(levels):
+        lw, lh, pitch, off = (int(v) for v in lv[l])
+        assert (lw, lh) == level_sizes[l]
+        # planes: pitch a multiple of 16 with room for a 32-bit load past the row end, 256-byte aligned, ascending, disjoint
+        assert pitch % 16 == 0 and pitch >= lw + 4 and off % 256 == 0 and off >= end
+        end = off + pitch * (lh + 1)
+        # the cells tile [19, w - 19) x [19, h - 19) exactly once (src/ORBextractor.cc:768-806), none wider than a FAST tile
+        cover = np.zeros((lh, lw), np.int32)
+        for _, x0, y0, cw, ch, _ in cells[cells[:, 0] == l]:
+            assert 0 < cw <= 64 and ch > 0 and x0 >= 19 and y0 >= 19 and x0 + cw <= lw - 19 and y0 + ch <= lh - 19
+            cover[y0:y0 + ch, x0:x0 + cw] += 1
+        want = np.zeros((lh, lw), np.int32)
+        want[19:lh - 19, 19:lw - 19] = 1
+        assert (cover == want).all()
+    assert end <= P["pyr_bytes"]
+    slots = ((cells[:, 3] + 1) // 2).astype(np.int64) * ((cells[:, 4] + 1) // 2)
+    assert (cells[:, 5] == np.concatenate([[0], np.cumsum(slots)[:-1]])).all()
+    assert P["slot_total"] == (int(slots.sum()) + 63) // 64 * 64
+
+
+@pytest.mark.parametrize("w,h,scale,levels,nfeatures", [
+    (640, 480, 1.2, 8, 1000), (1241, 376, 1.2, 8, 2000), (752, 480, 1.2, 8, 1200), (401, 323, 1.3, 5, 500),
+    (200, 180, 1.1, 8, 300), (517, 333, 1.2, 8, 700), (838, 118, 1.2, 2, 100), (640, 480, 2.0, 3, 500)])
+def test_extractor_plan_without_a_device(pkg, oracle, w, h, scale, levels, nfeatures):
+    """aos2_debug_extractor_plan: level planes, grid cells and slot offsets are host arithmetic, checked here without a GPU -- level
+    sizes against the oracle's pyramid, the cells against the reference's grid rule, the layout against what the kernels assume."""
+    ref = oracle.Extractor(nfeatures=nfeatures, scale_factor=scale, nlevels=levels)
+    ref.extract(pkg.synth.synth_image(1, w, h))
+    sizes = [ref.level_size(l)[:2] for l in range(levels)]
+    _check_plan(pkg.Extractor(nfeatures=nfeatures, scale_factor=scale, nlevels=levels).debug_plan(w, h), levels, sizes)
+    # the two refusals, and the tap still answers afterwards (it plans aside and never touches the handle's own plan: the commit
+    # point of an extract call, which needs a device, is not what this checks)
+    ex, fresh = pkg.Extractor(), pkg.Extractor().debug_plan(640, 480)
+    for (bw, bh), code in (((100, 100), pkg.capi.AOS2_ERR_TOO_SMALL), ((4001, 480), pkg.capi.AOS2_ERR_ARG)):
+        with pytest.raises(pkg.capi.AosError) as err:
+            ex.debug_plan(bw, bh)
+        assert err.value.code == code
+        again = ex.debug_plan(640, 480)
+        assert all(np.array_equal(again[k], fresh[k]) for k in fresh)
+    if (w, h, scale, levels) == (640, 480, 1.2, 8):
+        _check_plan(again, levels, sizes)
+
+
 def test_bad_arguments_and_missing_device(pkg):
     capi = pkg.capi
     with pytest.raises(capi.AosError) as e:

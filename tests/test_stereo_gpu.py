@@ -97,6 +97,32 @@ def test_stereo_edge_cases(pkg, oracle, gpu):
         pkg.ComputeStereoMatches(xl, x3, kl, dl, kr, dr, mb, mbf)
 
 
+def test_stereo_partner_changes_and_destroy_order(pkg, oracle, gpu):
+    """An extractor that has been the other eye of several partners: every pairing is undone when one of the two is paired anew
+    or destroyed, so no handle is left pointing at a partner that is gone (any destroy order, any later use of the survivors)."""
+    S = pkg.synth
+    mb, mbf = _params(S, "tum")
+    left, right, _ = S.synth_stereo_pair(5, 320, 240)
+    eL, eR, kl, dl, kr, dr = _oracle_pair(oracle, left, right, 500)
+    want = oracle.compute_stereo_matches(eL, eR, kl, dl, kr, dr, mb, mbf)
+    L, R1, R2 = (pkg.Extractor(nfeatures=500) for _ in range(3))
+    assert L(left)[0].tobytes() == kl.tobytes()
+    first = R1(right)
+    assert first[0].tobytes() == kr.tobytes() and first[1].tobytes() == dr.tobytes() and R2(right)[1].tobytes() == dr.tobytes()
+    for R in (R1, R2):
+        ur, dp = pkg.ComputeStereoMatches(L, R, kl, dl, kr, dr, mb, mbf)
+        assert ur.tobytes() == want[0].tobytes() and dp.tobytes() == want[1].tobytes()
+    L.close()
+    again = R1(right)
+    assert again[0].tobytes() == first[0].tobytes() and again[1].tobytes() == first[1].tobytes()
+    # R2 as the left eye of R1 (both hold the right image)
+    our, odp, _ = oracle.compute_stereo_matches(eR, eR, kr, dr, kr, dr, mb, mbf)
+    ur, dp = pkg.ComputeStereoMatches(R2, R1, kr, dr, kr, dr, mb, mbf)
+    assert ur.tobytes() == our.tobytes() and dp.tobytes() == odp.tobytes()
+    R1.close()
+    R2.close()
+
+
 def test_stereo_batch_device_matches_host_api(pkg, oracle, gpu):
     """[batch][cap] device arrays straight from extract_batch_device -> ComputeStereoMatches, no host hop."""
     import torch
