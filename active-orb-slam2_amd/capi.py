@@ -93,6 +93,7 @@ def lib():
             for nm in ("k", "levels", "scoring", "weighting", "nodes", "empty"):
                 getattr(L, "aos2_vocabulary_" + nm).argtypes = [vp]
             L.aos2_vocabulary_size.argtypes = [vp]
+            L.aos2_vocabulary_get_nodes.argtypes = [vp] * 6
             L.aos2_vocabulary_size.restype = C.c_uint
             L.aos2_vocabulary_transform.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(ci), vp, vp, vp, C.POINTER(ci), vp, vp]
             L.aos2_vocabulary_transform_device.argtypes = [vp, ci, vp, vp, ci, ci] + [vp] * 9
@@ -707,6 +708,14 @@ class Vocabulary:
         g = lambda n: getattr(self.L, "aos2_vocabulary_" + n)(self.h)  # noqa: E731
         return dict(k=g("k"), L=g("levels"), scoring=g("scoring"), weighting=g("weighting"), nodes=g("nodes"),
                     words=int(g("size")))
+
+    def nodes(self):
+        """m_nodes, root included -> dict(parent, is_leaf (= no children), word_id, weight, desc)"""
+        n = self.L.aos2_vocabulary_nodes(self.h)
+        r = dict(parent=np.zeros(n, np.int32), is_leaf=np.zeros(n, np.uint8), word_id=np.zeros(n, np.uint32),
+                 weight=np.zeros(n, np.float64), desc=np.zeros((n, 32), np.uint8))
+        _check(self.L.aos2_vocabulary_get_nodes(self.h, *[_p(r[k]) for k in ("parent", "is_leaf", "word_id", "weight", "desc")]))
+        return r
 
     def empty(self):
         return bool(self.L.aos2_vocabulary_empty(self.h))

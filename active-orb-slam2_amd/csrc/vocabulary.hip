@@ -487,9 +487,12 @@ int aos2_vocabulary_save_binary(const aos2_vocabulary_t *v, const char *filename
     return f.good() ? AOS2_OK : AOS2_ERR_ARG;
 }
 
-// loadFromTextFile (:1351-1431).  `while(!f.eof()) getline` turns the empty string after a final newline
-// into one more node (every `>>` fails -> parent 0, not a leaf by flag, zero descriptor, weight 0, no
-// word): a childless child of the root that stops the features that land on it.  Reproduced.
+// loadFromTextFile (:1351-1431).  A refused header leaves what the reference leaves: m_nodes and m_words cleared and
+// m_k, m_L overwritten before the check (:1359-1375), scoring and weighting untouched.  `while(!f.eof()) getline` turns
+// the empty string after a final newline into one more node.  Only its zero weight is defined there: the stream is empty,
+// so no `>>` stores anything, and `pid` and `nIsLeaf` are read unassigned.  Here it is a child of the
+// root with a zero descriptor, and a word, as in the reference build the suite pins against: it stops the features
+// that land on it and size() counts it.
 int aos2_vocabulary_load_text(aos2_vocabulary_t *v, const char *filename)
 {
     if (!v || !filename) {
@@ -504,9 +507,11 @@ int aos2_vocabulary_load_text(aos2_vocabulary_t *v, const char *filename)
     std::string s;
     std::getline(f, s);
     std::stringstream ss(s);
-    int k = -1, L = -1, n1 = -1, n2 = -1;
+    int k = 0, L = 0, n1 = -1, n2 = -1;
     ss >> k >> L >> n1 >> n2;
     if (k < 0 || k > 20 || L < 1 || L > 10 || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3) {
+        voc_reset(v);
+        v->k = k; v->L = L;
         set_error("Vocabulary loading failure: This is not a correct text file!");
         return AOS2_ERR_ARG;
     }
@@ -530,7 +535,7 @@ int aos2_vocabulary_load_text(aos2_vocabulary_t *v, const char *filename)
         }
         double w = 0;
         sn >> w;
-        if (sn.fail() && snode.empty()) { pid = 0; leaf = 0; w = 0; }
+        if (sn.fail() && snode.empty()) { pid = 0; leaf = 1; w = 0; }
         if (pid < 0 || (uint32_t)pid >= nid) {
             voc_reset(v);
             set_error("%s: node %u has parent %d", filename, nid, pid);
@@ -547,6 +552,23 @@ int aos2_vocabulary_scoring(const aos2_vocabulary_t *v) { return v ? v->scoring 
 int aos2_vocabulary_weighting(const aos2_vocabulary_t *v) { return v ? v->weighting : 0; }
 int aos2_vocabulary_nodes(const aos2_vocabulary_t *v) { return v ? (int)v->nodes.size() : 0; }
 unsigned aos2_vocabulary_size(const aos2_vocabulary_t *v) { return v ? v->n_words : 0; }
+int aos2_vocabulary_get_nodes(const aos2_vocabulary_t *v, int32_t *parent, uint8_t *is_leaf, uint32_t *word_id, double *weight,
+                              uint8_t *desc)
+{
+    if (!v) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    for (size_t i = 0; i < v->nodes.size(); ++i) {
+        const HostNode &n = v->nodes[i];
+        if (parent) parent[i] = (int32_t)n.parent;
+        if (is_leaf) is_leaf[i] = n.children.empty() ? 1 : 0;
+        if (word_id) word_id[i] = n.word_id;
+        if (weight) weight[i] = n.weight;
+        if (desc) memcpy(desc + i * 32, n.desc, 32);
+    }
+    return AOS2_OK;
+}
 int aos2_vocabulary_empty(const aos2_vocabulary_t *v) { return !v || v->n_words == 0; }
 float aos2_vocabulary_last_device_ms(const aos2_vocabulary_t *v) { return v ? v->last_ms : 0.0f; }
 void *aos2_vocabulary_stream(aos2_vocabulary_t *v)

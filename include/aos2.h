@@ -239,7 +239,8 @@ void aos2_vocabulary_destroy(aos2_vocabulary_t *v);
 /* bool loadFromBinaryFile(filename) :1456-1496 / loadFromTextFile :1351-1431 (src/System.cc:89-92),
  * saveToBinaryFile :1500-1521.  Both loaders reproduce the reference's `while(!f.eof())` tail
  * (binary: the last record is appended twice; text: a final newline yields one more, childless,
- * zero-weight child of the root) -- see DESIGN.md §5.5. */
+ * zero-weight child of the root, counted as a word) -- see DESIGN.md §5.5.  A text header the reference refuses
+ * leaves the vocabulary empty with k and L taken from that header. */
 int aos2_vocabulary_load_binary(aos2_vocabulary_t *v, const char *filename);
 int aos2_vocabulary_load_text(aos2_vocabulary_t *v, const char *filename);
 int aos2_vocabulary_save_binary(const aos2_vocabulary_t *v, const char *filename);
@@ -256,6 +257,10 @@ int aos2_vocabulary_weighting(const aos2_vocabulary_t *v);  /* getWeightingType(
 int aos2_vocabulary_nodes(const aos2_vocabulary_t *v);      /* m_nodes.size() */
 unsigned aos2_vocabulary_size(const aos2_vocabulary_t *v);  /* size() = number of words */
 int aos2_vocabulary_empty(const aos2_vocabulary_t *v);      /* empty() */
+/* Read-only view of m_nodes, root (node 0) included: aos2_vocabulary_nodes() entries each of parent, isLeaf() (no children),
+ * word id, weight and 32 descriptor bytes.  Any pointer may be NULL. */
+int aos2_vocabulary_get_nodes(const aos2_vocabulary_t *v, int32_t *parent, uint8_t *is_leaf, uint32_t *word_id,
+                              double *weight, uint8_t *desc);
 
 /* void transform(const vector<TDescriptor>& features, BowVector&, FeatureVector&, int levelsup)
  * :1140-1187 (Frame::ComputeBoW src/Frame.cc:424-431 and KeyFrame::ComputeBoW call it with

@@ -1,6 +1,6 @@
 /* TEST INFRASTRUCTURE (oracle) -- CPU restatement of the DBoW2 vocabulary path ORB-SLAM2 uses
- * (SURVEY.md §8(f) rank 3).  PARITY UNPINNED: the reference's DBoW2 needs OpenCV and cannot be built
- * here, and the vocabulary file is absent; this file restates the algorithm from
+ * (SURVEY.md §8(f) rank 3).  Pinned bit for bit against the reference's own DBoW2 sources (oracle/_ref/dbow2_ref,
+ * tests/test_dbow2_ref_cpu.py); the vocabulary file is absent.  It restates the algorithm from
  *   Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h  transform :1140-1187 (vector) and :1215-1260 (one
  *   feature), loadFromTextFile :1351-1431, loadFromBinaryFile :1456-1496, saveToBinaryFile :1500-1521,
  *   Thirdparty/DBoW2/DBoW2/FORB.cpp distance :81-100,
@@ -76,6 +76,18 @@ int orc_vocab_scoring(const orc_vocab_t *v) { return v->scoring; }
 int orc_vocab_weighting(const orc_vocab_t *v) { return v->weighting; }
 int orc_vocab_nodes(const orc_vocab_t *v) { return v->n_nodes; }
 int orc_vocab_size(const orc_vocab_t *v) { return v->n_words; } /* size() = m_words.size() */
+/* m_nodes, root included: n_nodes entries each; any pointer may be NULL */
+void orc_vocab_get_nodes(const orc_vocab_t *v, int32_t *parent, uint8_t *is_leaf, uint32_t *word_id, double *weight, uint8_t *desc)
+{
+    for (int i = 0; i < v->n_nodes; ++i) {
+        const vnode_t *n = &v->nodes[i];
+        if (parent) parent[i] = (int32_t)n->parent;
+        if (is_leaf) is_leaf[i] = n->nchild == 0;
+        if (word_id) word_id[i] = n->word_id;
+        if (weight) weight[i] = n->weight;
+        if (desc) memcpy(desc + (size_t)i * 32, n->desc, 32);
+    }
+}
 
 /* one record of either loader: nodes arrive in id order, children in order of appearance */
 static void append_node(orc_vocab_t *v, int nid, uint32_t parent, const uint8_t *desc, double weight, int is_leaf)
@@ -163,18 +175,22 @@ int orc_vocab_save_binary(const orc_vocab_t *v, const char *path)
     return 0;
 }
 
-/* loadFromTextFile :1351-1431.  `while(!f.eof()) getline` also turns the empty string after the final
- * newline into a node: every `>>` fails and leaves 0 (C++11), i.e. parent 0, not a leaf by flag, all-zero
- * descriptor (FORB::fromString :120-135 on a fresh Mat -- taken as zero here), weight 0, no word. */
+/* loadFromTextFile :1351-1431.  A refused header has already cleared m_nodes / m_words and overwritten m_k, m_L
+ * (:1359-1375); scoring and weighting stay.  `while(!f.eof()) getline` also turns the empty string after the final
+ * newline into a node.  Its weight is 0 (Node()); its parent and leaf flag are read unassigned in the reference (no `>>`
+ * stores anything from an empty stream) and its descriptor comes from a fresh Mat: taken as parent 0, a word, all-zero
+ * descriptor -- what the reference build the suite pins against does where the last record is a child of the root. */
 int orc_vocab_load_text(orc_vocab_t *v, const char *path)
 {
     FILE *f = fopen(path, "r");
     if (!f) return -1;
     size_t cap = 1 << 12;
     char *line = (char *)malloc(cap);
-    int n1, n2, k, L;
+    int n1 = -1, n2 = -1, k = 0, L = 0;
     if (!fgets(line, (int)cap, f) || sscanf(line, "%d %d %d %d", &k, &L, &n1, &n2) != 4 || k < 0 || k > 20 || L < 1 || L > 10 ||
         n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3) {
+        vocab_clear(v);
+        v->k = k; v->L = L;
         free(line);
         fclose(f);
         return -2;
@@ -199,7 +215,8 @@ int orc_vocab_load_text(orc_vocab_t *v, const char *path)
             leaf = (int)strtol(p, &p, 10);
             for (int i = 0; i < 32; ++i) d[i] = (uint8_t)strtol(p, &p, 10);
             w = strtod(p, &p);
-        }
+        } else
+            leaf = 1;
         if (pid < 0 || pid >= nid) {
             free(line);
             fclose(f);

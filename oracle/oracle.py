@@ -86,6 +86,8 @@ def lib():
         L.orc_vocab_destroy.argtypes = [C.c_void_p]
         for name in ("k", "L", "scoring", "weighting", "nodes", "size"):
             getattr(L, "orc_vocab_" + name).argtypes = [C.c_void_p]
+        L.orc_vocab_get_nodes.argtypes = [C.c_void_p] * 6
+        L.orc_vocab_get_nodes.restype = None
         L.orc_vocab_set_nodes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.orc_vocab_load_binary.argtypes = [C.c_void_p, C.c_char_p]
         L.orc_vocab_save_binary.argtypes = [C.c_void_p, C.c_char_p]
@@ -595,6 +597,14 @@ class Vocabulary:
     def info(self):
         g = lambda n: getattr(self.L_, "orc_vocab_" + n)(self.h)  # noqa: E731
         return dict(k=g("k"), L=g("L"), scoring=g("scoring"), weighting=g("weighting"), nodes=g("nodes"), words=g("size"))
+
+    def nodes(self):
+        """m_nodes, root included -> dict(parent, is_leaf (= no children), word_id, weight, desc)"""
+        n = self.L_.orc_vocab_nodes(self.h)
+        r = dict(parent=np.zeros(n, np.int32), is_leaf=np.zeros(n, np.uint8), word_id=np.zeros(n, np.uint32),
+                 weight=np.zeros(n, np.float64), desc=np.zeros((n, 32), np.uint8))
+        self.L_.orc_vocab_get_nodes(self.h, *[_p(r[k]) for k in ("parent", "is_leaf", "word_id", "weight", "desc")])
+        return r
 
     def transform(self, desc, levelsup=4):
         """-> dict(bow_word, bow_value, fv_node, fv_off, fv_idx, word_of, node_of) or None if the vocabulary is empty"""

@@ -251,6 +251,8 @@ int orc_vocab_scoring(const orc_vocab_t *v);
 int orc_vocab_weighting(const orc_vocab_t *v);
 int orc_vocab_nodes(const orc_vocab_t *v); /* m_nodes.size() (root included) */
 int orc_vocab_size(const orc_vocab_t *v);  /* size() = number of words */
+void orc_vocab_get_nodes(const orc_vocab_t *v, int32_t *parent, uint8_t *is_leaf, uint32_t *word_id, double *weight,
+                         uint8_t *desc); /* m_nodes, root included; any pointer may be NULL */
 int orc_vocab_set_nodes(orc_vocab_t *v, int k, int L, int scoring, int weighting, int n, const int32_t *parent,
                         const uint8_t *desc, const double *weight, const uint8_t *is_leaf);
 int orc_vocab_load_binary(orc_vocab_t *v, const char *path);

@@ -1,6 +1,9 @@
 """Generates the committed golden fixtures from the ORACLE (the reference has no golden vectors of
 its own and cannot be built here: SURVEY.md F4/F5, so these pin the oracle against regressions and
 give the GPU tests oracle-free expectations).  Run from the repo root:  python tests/golden/make_golden.py
+The dbow2_ref_*.npz fixtures are the exception: they record the reference's own DBoW2 (oracle/_ref/dbow2_ref, built by
+__graft_entry__.build() where the reference's sources are present);  python tests/golden/make_golden.py dbow2_ref
+writes only those.
 """
 import os
 import sys
@@ -16,6 +19,23 @@ pkg = g.load_package()
 O = g.load_oracle()
 S = pkg.synth
 OUT = os.path.dirname(os.path.abspath(__file__))
+
+
+def dbow2_ref_fixtures():
+    """dbow2_ref_*.npz: the cases of tests/dbow2_cases.py run through the reference driver; data only."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dbow2_cases as D
+    assert D.live_binary(), D.SKIP_REASON
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, cases in D.fixture_cases().items():
+            D.save_fixture(os.path.join(OUT, name), [(c, D.run_ref(c, tmp)) for c in cases])
+            print(name, len(cases), "cases", os.path.getsize(os.path.join(OUT, name)), "bytes")
+
+
+if sys.argv[1:] == ["dbow2_ref"]:
+    dbow2_ref_fixtures()
+    sys.exit(0)
 
 
 def extractor_case(name, img, nfeatures, nlevels):
@@ -112,3 +132,4 @@ f2, q = S.synth_init_problem(42, 500, 520)
 n, m = O.search_for_initialization(f2, q, 100, 0.9, True)
 np.savez_compressed(os.path.join(OUT, "init_500.npz"), n=n, match=m, **{"f_" + k: v for k, v in f2.items()},
                     **{"q_" + k: v for k, v in q.items()})
+dbow2_ref_fixtures()

@@ -116,7 +116,8 @@ def test_file_loaders_and_score(pkg, oracle, gpu, tmp_path):
     assert V2.loadFromBinaryFile(ob) and O2.load_binary(pb)
     assert V2.info() == O2.info() and V2.info()["nodes"] == V.info()["nodes"] + 1 and V2.info()["words"] == V.info()["words"] + 1
     _same(V2.transform(d1, 2), ref)
-    # text format (loadFromTextFile), with and without the final newline
+    # text format (loadFromTextFile), with and without the final newline: the record formed after it is one more
+    # node and, as in the reference build (tests/test_dbow2_ref_gpu.py), one more word
     lines = ["10 3 0 0"]
     for i in range(len(voc["parent"])):
         lines.append(f'{voc["parent"][i]} {int(voc["is_leaf"][i])} ' + " ".join(str(int(x)) for x in voc["desc"][i]) +
@@ -127,6 +128,7 @@ def test_file_loaders_and_score(pkg, oracle, gpu, tmp_path):
         V3, O3 = pkg.Vocabulary(), oracle.Vocabulary()
         assert V3.loadFromTextFile(pt) and O3.load_text(pt)
         assert V3.info() == O3.info() and V3.info()["nodes"] == V.info()["nodes"] + extra
+        assert V3.info()["words"] == V.info()["words"] + extra
         _same(V3.transform(d1, 2), O3.transform(d1, 2))
     assert not pkg.Vocabulary().loadFromBinaryFile(tmp_path / "missing.bin")
     # L1 score (KeyFrameDatabase / LoopClosing): self-score 1, symmetric, equal to the oracle's
