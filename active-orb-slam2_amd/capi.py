@@ -104,6 +104,7 @@ def lib():
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         L.aos2_debug_sincos_device.argtypes = [vp, ci, vp, vp, ci]
+        L.aos2_debug_wave_ops_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
@@ -922,6 +923,26 @@ def debug_sincos_device(angles, device=0):
     c = np.zeros_like(a)
     _check(lib().aos2_debug_sincos_device(_p(a), len(a), _p(s), _p(c), device))
     return s, c
+
+
+WAVE_OPS_I = ("dpp_u32_B1", "dpp_u32_4E", "dpp_u32_141", "dpp_u32_140", "dpp_i32_B1", "dpp_i32_4E", "dpp_i32_141", "dpp_i32_140",
+              "row_sum", "sum", "max", "row_min", "min", "incl_scan", "block_excl_scan", "block_total")
+WAVE_OPS_D = ("dpp_f64_B1", "dpp_f64_4E", "dpp_f64_141", "dpp_f64_140", "row_sum_f64", "readlane_0", "readlane_63")
+
+
+def debug_wave_ops_device(vi, vd, device=0):
+    """test tap: every primitive of csrc/wave_ops.h; vi (int32), vd (float64) [cases][nt], nt = 128 or 256 threads per workgroup
+    -> dict name -> [cases][nt] (WAVE_OPS_I as int32, the row / wave min as uint32; WAVE_OPS_D as float64)"""
+    vi = np.ascontiguousarray(vi, np.int32); vd = np.ascontiguousarray(vd, np.float64)
+    assert vi.ndim == 2 and vi.shape == vd.shape
+    oi = np.zeros(vi.shape + (len(WAVE_OPS_I),), np.int32)
+    od = np.zeros(vi.shape + (len(WAVE_OPS_D),), np.float64)
+    _check(lib().aos2_debug_wave_ops_device(_p(vi), _p(vd), vi.shape[0], vi.shape[1], _p(oi), _p(od), device))
+    out = {k: oi[..., j].copy() for j, k in enumerate(WAVE_OPS_I)}
+    out.update({k: od[..., j].copy() for j, k in enumerate(WAVE_OPS_D)})
+    for k in ("row_min", "min"):
+        out[k] = out[k].view(np.uint32)
+    return out
 
 
 def debug_pose_blocks_device(upd, T, Hb, lam, x0, device=0):

@@ -8,12 +8,51 @@
 #include "sincos_exact.h"
 #include "sim3.h"
 #include "triangulate.h"
+#include "wave_ops.h"
 
 namespace aos2 {
 __global__ void sincos_kernel(const float *a, int n, float *s, float *c)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) sincos_exact(a[i], &s[i], &c[i]);
+}
+
+// Every primitive of wave_ops.h on one int and one double per thread: a workgroup of NT threads per case, kWaveOpsI ints and
+// kWaveOpsD doubles per thread (the order below is the layout capi.py names).
+constexpr int kWaveOpsI = 16, kWaveOpsD = 7;
+template <int NT>
+__global__ __launch_bounds__(NT) void wave_ops_kernel(const int32_t *vi, const double *vd, int32_t *out_i, double *out_d)
+{
+    __shared__ int32_t wsum[NT / 64];
+    const size_t t = (size_t)blockIdx.x * NT + threadIdx.x;
+    const int v = vi[t];
+    const double d = vd[t];
+    int32_t *oi = out_i + kWaveOpsI * t;
+    double *od = out_d + kWaveOpsD * t;
+    oi[0] = (int32_t)dpp_u32<0xB1>((uint32_t)v);
+    oi[1] = (int32_t)dpp_u32<0x4E>((uint32_t)v);
+    oi[2] = (int32_t)dpp_u32<0x141>((uint32_t)v);
+    oi[3] = (int32_t)dpp_u32<0x140>((uint32_t)v);
+    oi[4] = dpp_i32<0xB1>(v);
+    oi[5] = dpp_i32<0x4E>(v);
+    oi[6] = dpp_i32<0x141>(v);
+    oi[7] = dpp_i32<0x140>(v);
+    oi[8] = wave_row_sum_i32(v);
+    oi[9] = wave_sum_i32(v);
+    oi[10] = wave_max_i32(v);
+    oi[11] = (int32_t)wave_row_min_u32((uint32_t)v);
+    oi[12] = (int32_t)wave_min_u32((uint32_t)v);
+    oi[13] = wave_incl_scan_i32(v);
+    int total;
+    oi[14] = block_excl_scan_i32<NT>(v, wsum, total);
+    oi[15] = total;
+    od[0] = dpp_f64<0xB1>(d);
+    od[1] = dpp_f64<0x4E>(d);
+    od[2] = dpp_f64<0x141>(d);
+    od[3] = dpp_f64<0x140>(d);
+    od[4] = row_sum_f64(d);
+    od[5] = readlane_f64(d, 0);
+    od[6] = readlane_f64(d, 63);
 }
 
 int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
@@ -176,6 +215,30 @@ int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int
     AOS2_HIP_CHECK(hipMemcpy(s, ds.p, sizeof(float) * n, hipMemcpyDeviceToHost));
     AOS2_HIP_CHECK(hipMemcpy(c, dc.p, sizeof(float) * n, hipMemcpyDeviceToHost));
     da.release(); ds.release(); dc.release();
+    return AOS2_OK;
+}
+
+int aos2_debug_wave_ops_device(const int32_t *vi, const double *vd, int n_cases, int nt, int32_t *out_i, double *out_d, int device)
+{
+    using namespace aos2;
+    if (!vi || !vd || !out_i || !out_d || n_cases < 1 || (nt != 128 && nt != 256)) {
+        set_error("bad argument (the four arrays, >= 1 cases, 128 or 256 threads: the sizes the library scans with)");
+        return AOS2_ERR_ARG;
+    }
+    int st;
+    if ((st = bind_device(device))) return st;
+    const size_t n = (size_t)n_cases * nt;
+    DevBuf<int32_t> di, doi;
+    DevBuf<double> dd, dod;
+    if ((st = di.alloc(n)) || (st = dd.alloc(n)) || (st = doi.alloc(kWaveOpsI * n)) || (st = dod.alloc(kWaveOpsD * n))) return st;
+    AOS2_HIP_CHECK(hipMemcpy(di.p, vi, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    AOS2_HIP_CHECK(hipMemcpy(dd.p, vd, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (nt == 128) hipLaunchKernelGGL(wave_ops_kernel<128>, dim3(n_cases), dim3(128), 0, 0, di.p, dd.p, doi.p, dod.p);
+    else hipLaunchKernelGGL(wave_ops_kernel<256>, dim3(n_cases), dim3(256), 0, 0, di.p, dd.p, doi.p, dod.p);
+    AOS2_HIP_CHECK(hipDeviceSynchronize());
+    AOS2_HIP_CHECK(hipMemcpy(out_i, doi.p, sizeof(int32_t) * kWaveOpsI * n, hipMemcpyDeviceToHost));
+    AOS2_HIP_CHECK(hipMemcpy(out_d, dod.p, sizeof(double) * kWaveOpsD * n, hipMemcpyDeviceToHost));
+    di.release(); dd.release(); doi.release(); dod.release();
     return AOS2_OK;
 }
 

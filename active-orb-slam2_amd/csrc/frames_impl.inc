@@ -75,30 +75,18 @@ __global__ __launch_bounds__(256) void frames_scan_slots_kernel(QuerySlot *__res
                                                                 int nq_cap, int share, int32_t *__restrict__ overflow)
 {
     __shared__ int32_t wsum[4];
-    __shared__ int32_t carry;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     QuerySlot *sl = slots + (size_t)b * nq_cap;
     const int nq = nq_of ? min(nq_of[b], nq_cap) : nq_cap;
-    if (tid == 0) carry = 0;
-    __syncthreads();
+    int carry = 0;   // entries of the chunks before this one (uniform)
     for (int q0 = 0; q0 < nq; q0 += 256) {
         const int q = q0 + tid;
         const int v = q < nq ? max(sl[q].cnt, 0) : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        const int excl = carry + woff + x - v;
+        int total;
+        const int excl = carry + block_excl_scan_i32<256>(v, wsum, total);
         if (q < nq) sl[q].ent_off = (int)((size_t)b * share) + excl;
-        __syncthreads();
-        if (tid == 255) carry = excl + v;
-        __syncthreads();
+        carry += total;
+        __syncthreads();   // wsum is read before the next chunk writes it
     }
     if (carry > share) {
         for (int q = tid; q < nq; q += 256) sl[q].cnt = 0;

@@ -23,33 +23,22 @@ __global__ __launch_bounds__(NT) void frames_pose_optimization_kernel(FramesDev 
     extern __shared__ __attribute__((aligned(16))) double sh[];  // po_lds_bytes(NT)
     __shared__ int s_cnt;
     __shared__ int32_t wsum[NT / 64];
-    __shared__ int32_t carry;
     __shared__ double s_pose[7];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const size_t o = (size_t)b * S.cap;
     const int n = S.n[b];
     if (tid == 0) {
-        carry = 0;
         double qt[7];
         pose_from_Tcw(S.Tcw + 16 * (size_t)b, qt);
         for (int k = 0; k < 7; ++k) s_pose[k] = qt[k];
     }
-    __syncthreads();
+    int carry = 0;   // correspondences of the chunks before this one (uniform)
     for (int i0 = 0; i0 < n; i0 += NT) {
         const int i = i0 + tid;
         const int row = i < n ? S.mp[o + i] : -1;
         const int v = row >= 0 ? 1 : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        const int k = carry + woff + x - v;
+        int total;
+        const int k = carry + block_excl_scan_i32<NT>(v, wsum, total);
         if (v) {
             const size_t d = o + k;
             const float ur = S.u_right[o + i];
@@ -62,9 +51,8 @@ __global__ __launch_bounds__(NT) void frames_pose_optimization_kernel(FramesDev 
             Q.feat_of[d] = i;
             S.outlier[o + i] = 0;            // pFrame->mvbOutlier[i] = false (:283, :320)
         }
-        __syncthreads();
-        if (tid == NT - 1) carry = k + v;
-        __syncthreads();
+        carry += total;
+        __syncthreads();   // wsum is read before the next chunk writes it
     }
     PoseProbDev P;
     P.n = carry;

@@ -37,6 +37,7 @@
 
 #include "lba_math.h"
 #include "ldlt_reg.h"
+#include "wave_ops.h"
 
 namespace aos2 {
 
@@ -929,26 +930,6 @@ __device__ __forceinline__ void lin_points_walk(const LbaWin &W, int l)
     }
     for (int i = 0; i < 9; ++i) W.Hll[9 * (size_t)l + i] = H[i];
     for (int i = 0; i < 3; ++i) W.b[6 * (size_t)W.np + 3 * (size_t)l + i] = bl[i];
-}
-
-// Sum of `v` over the 16 lanes of a DPP row (xor butterfly: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror):
-// VALU speed, no LDS.  Every lane of the row ends with the row's total (lanes may differ in the last bit: the butterfly
-// adds in a lane-dependent order; callers read one fixed lane per row).
-template <int kCtrl>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp((int)b, (int)b, kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(b >> 32), (int)(b >> 32), kCtrl, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double row_sum_f64(double v)
-{
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    v += dpp_f64<0x140>(v);
-    return v;
 }
 
 // acc[K] of every thread of an NT-thread workgroup -> their sums (returned in threads e < K).  16-lane DPP row sums, then

@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_ops.h"
+
 namespace aos2 {
 
 typedef double lr_double4_t __attribute__((ext_vector_type(4)));
@@ -54,15 +56,6 @@ __host__ __device__ constexpr size_t ldlt_reg_lds_doubles(int npad)
 }
 constexpr size_t kLrMaxDynLds = ldlt_reg_lds_doubles(16 * kLrMaxNb) * sizeof(double);   // 149 248 B at 40 free keyframes
 static_assert(kLrMaxDynLds + 64 <= 160 * 1024, "k_ldlt_reg: dynamic + static LDS beyond a CU's 160 KB");
-
-// value of `v` in lane `src` (wave-uniform index), uniform result
-__device__ __forceinline__ double readlane_f64(double v, int src)
-{
-    const long long bits = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(bits & 0xffffffffll), src);
-    const int hi = __builtin_amdgcn_readlane((int)(bits >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // 1 / d within 1 ulp: v_rcp_f64 + two Newton steps (34 cycles; the IEEE division takes 67)
 __device__ __forceinline__ double lr_rcp(double d)

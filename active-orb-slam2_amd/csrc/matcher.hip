@@ -58,18 +58,12 @@ __device__ __forceinline__ void merge2(uint32_t &k1, uint32_t &k2, uint32_t o1, 
 // Two smallest keys of the wave, result uniform.  The serial matcher loops sit on this latency, so
 // no LDS crossbar (ds_bpermute) is used: four DPP butterfly steps reduce each 16-lane row at VALU
 // speed (every step merges two disjoint lane sets), then the four row results are read into SGPRs.
-template <int kCtrl>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xf, 0xf, false);
-}
-
 __device__ __forceinline__ void wave_min2(uint32_t &k1, uint32_t &k2)
 {
-    merge2(k1, k2, dpp_mov<0xB1>(k1), dpp_mov<0xB1>(k2));    // quad_perm [1,0,3,2]
-    merge2(k1, k2, dpp_mov<0x4E>(k1), dpp_mov<0x4E>(k2));    // quad_perm [2,3,0,1]
-    merge2(k1, k2, dpp_mov<0x141>(k1), dpp_mov<0x141>(k2));  // row_half_mirror
-    merge2(k1, k2, dpp_mov<0x140>(k1), dpp_mov<0x140>(k2));  // row_mirror
+    merge2(k1, k2, dpp_u32<0xB1>(k1), dpp_u32<0xB1>(k2));    // quad_perm [1,0,3,2]
+    merge2(k1, k2, dpp_u32<0x4E>(k1), dpp_u32<0x4E>(k2));    // quad_perm [2,3,0,1]
+    merge2(k1, k2, dpp_u32<0x141>(k1), dpp_u32<0x141>(k2));  // row_half_mirror
+    merge2(k1, k2, dpp_u32<0x140>(k1), dpp_u32<0x140>(k2));  // row_mirror
     uint32_t a1 = __builtin_amdgcn_readlane(k1, 0), a2 = __builtin_amdgcn_readlane(k2, 0);
     merge2(a1, a2, __builtin_amdgcn_readlane(k1, 16), __builtin_amdgcn_readlane(k2, 16));
     merge2(a1, a2, __builtin_amdgcn_readlane(k1, 32), __builtin_amdgcn_readlane(k2, 32));
@@ -1668,16 +1662,8 @@ __device__ __forceinline__ void assign_grid_body(int n, const float *__restrict_
         own[k] = cnt[tid * kPer + k];
         tsum += own[k];
     }
-    int x = tsum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();   // (also: every thread has read its counts before the offsets overwrite them)
-    int excl = x - tsum;
-    for (int w = 0; w < wave; ++w) excl += wsum[w];
+    int total;
+    int excl = block_excl_scan_i32<256>(tsum, wsum, total);   // (its barrier also: every thread has read its counts before the offsets overwrite them)
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
         const int c = tid * kPer + k;

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include "wave_ops.h"
 // always inlined on the device: the LDS instantiation relies on address-space inference (ds_*
 // instead of flat_* accesses), which stops at call boundaries
 #define AOS2_OCT_HD __host__ __device__ __forceinline__
@@ -126,42 +127,11 @@ __device__ inline void coop_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)
 __device__ inline unsigned long long coop_ballot(bool p) { return __ballot(p); }
 __device__ inline int coop_popc(unsigned long long m) { return __popcll(m); }
 __device__ inline int coop_shfl(int v, int src) { return __shfl(v, src); }   // lane-varying source: ds_bpermute_b32
-// Wave reductions / scans on DPP (4 + 2 row-level steps, no LDS round trips; __shfl_xor / __shfl_up compile to
-// ds_bpermute_b32, i.e. 6 dependent LDS accesses per call -- these helpers sit on the jobs' serial path).
-__device__ inline int coop_row_reduce_add(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);   // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);   // row_mirror
-    return v;   // every lane: the sum of its row of 16
-}
-__device__ inline int coop_sum(int v)
-{
-    v = coop_row_reduce_add(v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
-}
-__device__ inline int coop_max(int v)   // v >= 0
-{
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ inline int coop_excl_scan(int v)  // exclusive prefix sum over the lanes
-{
-    int x = v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1 (lanes without a source add 0)
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);   // row_shr:8  -> inclusive scan inside each row
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-    return x - v;
-}
+// Wave reductions / scans: wave_ops.h (DPP, no LDS round trips -- these helpers sit on the jobs' serial path).
+__device__ inline int coop_row_reduce_add(int v) { return wave_row_sum_i32(v); }   // every lane: the sum of its row of 16
+__device__ inline int coop_sum(int v) { return wave_sum_i32(v); }
+__device__ inline int coop_max(int v) { return wave_max_i32(v); }   // v >= 0
+__device__ inline int coop_excl_scan(int v) { return wave_incl_scan_i32(v) - v; }  // exclusive prefix sum over the lanes
 __device__ inline int coop_ffs(unsigned long long m) { return __ffsll((long long)m) - 1; }
 #else
 inline int coop_lane() { return 0; }

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "lba_math.h"
+#include "wave_ops.h"
 
 namespace aos2 {
 
@@ -143,15 +144,6 @@ __device__ __forceinline__ double swap_add(double x, double y)
     return pair_f64(lo[0], hi[0]) + pair_f64(lo[1], hi[1]);
 }
 
-template <int kCtrl>
-__device__ __forceinline__ double po_dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp((int)b, (int)b, kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(b >> 32), (int)(b >> 32), kCtrl, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // fixed-order workgroup sum of the 28 doubles of every thread -> fin[28] in LDS, readable by every thread after return
 // (bit-reproducible: the order is a function of the lane number only).  Per wave a reduce-scatter: the two halves of the
 // wave exchange halves of the values (28 -> 14 per lane, v_permlane32_swap), the 16-lane rows again (-> 7 per lane,
@@ -170,14 +162,7 @@ __device__ __forceinline__ void block_sum28(double (&v)[kPoSum], double *part /*
 #pragma unroll
     for (int i = 0; i < 7; ++i) g[i] = swap_add<false>(h[i], h[7 + i]);    // row r of the wave: values 7 r .. 7 r + 6
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double x = g[i];
-        x += po_dpp_f64<0xB1>(x);    // quad_perm [1, 0, 3, 2]
-        x += po_dpp_f64<0x4E>(x);    // quad_perm [2, 3, 0, 1]
-        x += po_dpp_f64<0x141>(x);   // row_half_mirror
-        x += po_dpp_f64<0x140>(x);   // row_mirror
-        g[i] = x;
-    }
+    for (int i = 0; i < 7; ++i) g[i] = row_sum_f64(g[i]);
     if ((lane & 15) == 0) {
         double *dst = part + wave * kPoSum + 7 * (lane >> 4);
 #pragma unroll

@@ -12,41 +12,13 @@
 #include "stereo.h"
 
 #include "aos2_common.h"
+#include "wave_ops.h"
 
 namespace aos2 {
 namespace {
 
 constexpr int TH_HIGH = 100, TH_LOW = 50;  // src/ORBmatcher.cc:37-38
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;
-
-template <int kCtrl>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t k)
-{
-    k = min(k, dpp_u32<0xB1>(k));
-    k = min(k, dpp_u32<0x4E>(k));
-    k = min(k, dpp_u32<0x141>(k));
-    k = min(k, dpp_u32<0x140>(k));
-    uint32_t a = __builtin_amdgcn_readlane(k, 0);
-    a = min(a, (uint32_t)__builtin_amdgcn_readlane(k, 16));
-    a = min(a, (uint32_t)__builtin_amdgcn_readlane(k, 32));
-    a = min(a, (uint32_t)__builtin_amdgcn_readlane(k, 48));
-    return a;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-    v += (int)dpp_u32<0xB1>((uint32_t)v);
-    v += (int)dpp_u32<0x4E>((uint32_t)v);
-    v += (int)dpp_u32<0x141>((uint32_t)v);
-    v += (int)dpp_u32<0x140>((uint32_t)v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
-}
 
 __device__ __forceinline__ const uint8_t *level_plane(const PyrView &P, int image, int level, int &pitch)
 {

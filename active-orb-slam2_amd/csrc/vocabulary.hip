@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "aos2_common.h"
+#include "wave_ops.h"
 
 using namespace aos2;
 
@@ -44,20 +45,6 @@ struct HostNode {
     uint32_t word_id = 0;
     std::vector<uint32_t> children;
 };
-
-template <int kCtrl>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t row_min_u32(uint32_t k)  // min over the 16 lanes of a DPP row, in every lane
-{
-    k = min(k, dpp_u32<0xB1>(k));
-    k = min(k, dpp_u32<0x4E>(k));
-    k = min(k, dpp_u32<0x141>(k));
-    k = min(k, dpp_u32<0x140>(k));
-    return k;
-}
 
 // ---- descent: word, node at level L - levelsup and weight of every feature
 __global__ __launch_bounds__(256) void voc_descend_kernel(const VocRec *__restrict__ rec, const double *__restrict__ slot_weight,
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(256) void voc_descend_kernel(const VocRec *__restri
                 }
             }
         }
-        const uint32_t best = row_min_u32(key);
+        const uint32_t best = wave_row_min_u32(key);
         // the lane owning the winner broadcasts its record tail to the 16-lane group
         const int owner = (lane & ~15) | (int)((best & 0xFFFFu) & 15u);
         const int w_first = __shfl(b_first, owner), w_cnt = __shfl(b_cnt, owner);
@@ -158,31 +145,12 @@ struct AssembleOut {
     int32_t *n_fv;        // [batch]
 };
 
-// block-wide exclusive scan of one int per thread (256 threads)
-__device__ int block_excl_scan(int v, int *sh, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return off + x - v;
-}
-
 __global__ __launch_bounds__(256) void voc_assemble_kernel(const uint32_t *__restrict__ word_of, const uint32_t *__restrict__ node_of,
                                                            const double *__restrict__ weight_of, const int32_t *__restrict__ n_feat,
                                                            int cap, int np2, int tf, int must, int l2, AssembleOut O)
 {
     extern __shared__ unsigned long long keys[];
-    __shared__ int sh[4];
+    __shared__ int32_t sh[4];   // block_excl_scan_i32: a barrier after every call, before the next one writes it
     __shared__ double s_norm;
     const int b = blockIdx.x;
     const int n = n_feat[b];
@@ -205,16 +173,18 @@ __global__ __launch_bounds__(256) void voc_assemble_kernel(const uint32_t *__res
         const bool valid = k != NONE;
         const bool head = valid && (t == 0 || (uint32_t)(keys[t - 1] >> 32) != (uint32_t)(k >> 32));
         int tot;
-        const int pos = carry + block_excl_scan(head ? 1 : 0, sh, tot);
+        const int pos = carry + block_excl_scan_i32<256>(head ? 1 : 0, sh, tot);
         if (valid) O.fv_idx[base + t] = (int32_t)(uint32_t)k;
         if (head) {
             O.fv_node[base + pos] = (int32_t)(uint32_t)(k >> 32);
             O.fv_off[(size_t)b * (cap + 1) + pos] = t;
         }
         carry += tot;
+        __syncthreads();
         int tv;
-        block_excl_scan(valid ? 1 : 0, sh, tv);
+        block_excl_scan_i32<256>(valid ? 1 : 0, sh, tv);
         kept += tv;
+        __syncthreads();
     }
     if (threadIdx.x == 0) {
         O.fv_off[(size_t)b * (cap + 1) + carry] = kept;
@@ -238,7 +208,7 @@ __global__ __launch_bounds__(256) void voc_assemble_kernel(const uint32_t *__res
         const uint32_t w = (uint32_t)(k >> 32);
         const bool head = valid && (t == 0 || (uint32_t)(keys[t - 1] >> 32) != w);
         int tot;
-        const int pos = carry + block_excl_scan(head ? 1 : 0, sh, tot);
+        const int pos = carry + block_excl_scan_i32<256>(head ? 1 : 0, sh, tot);
         if (head) {
             // addWeight (:30-42): the word's weight added once per occurrence, in arrival order
             const double wt = weight_of[base + (uint32_t)k];
@@ -249,6 +219,7 @@ __global__ __launch_bounds__(256) void voc_assemble_kernel(const uint32_t *__res
             O.bow_value[base + pos] = v;
         }
         carry += tot;
+        __syncthreads();
     }
     const int nb = carry;
     __syncthreads();

@@ -990,6 +990,11 @@ int aos2_debug_extractor_plan(const aos2_extractor_t *e, int w, int h, int64_t *
 /* rBRIEF steering sin/cos (csrc/sincos_exact.h) evaluated on the host / on the device */
 void aos2_debug_sincos_host(float angle_rad, float *s, float *c);
 int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int device);
+/* Every wave / workgroup primitive of csrc/wave_ops.h on caller-supplied per-thread inputs: one workgroup of nt threads (128 or 256,
+ * the sizes the library's workgroup scans run with) per case; vi, vd [n_cases][nt]; out_i [n_cases][nt][16] = dpp_u32 and dpp_i32
+ * under 0xB1, 0x4E, 0x141, 0x140, row sum, wave sum, wave max, row min, wave min, inclusive scan, block_excl_scan_i32<nt> and its
+ * total; out_d [n_cases][nt][7] = dpp_f64 under the four words, row_sum_f64, readlane_f64 of lanes 0 and 63. */
+int aos2_debug_wave_ops_device(const int32_t *vi, const double *vd, int n_cases, int nt, int32_t *out_i, double *out_d, int device);
 /* aos2_triangulate_matches on the HOST with the routine the device kernels also run (csrc/triangulate.h); needs no device */
 int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,
                                 const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
