@@ -106,6 +106,7 @@ def lib():
         L.aos2_debug_sincos_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_wave_ops_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
+        L.aos2_debug_lba_reduced_solve_device.argtypes = [ci] + [vp] * 12 + [ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
         L.aos2_debug_sim3_host.argtypes = [vp, vp, ci]
@@ -954,6 +955,29 @@ def debug_pose_blocks_device(upd, T, Hb, lam, x0, device=0):
     To = np.zeros((n, 7)); ok = np.zeros(n, np.uint8)
     _check(lib().aos2_debug_pose_blocks_device(_p(upd), _p(T), _p(To), _p(Hb), _p(lam), _p(x), _p(ok), n, device))
     return To, x, ok
+
+
+def debug_lba_reduced_solve_device(cases, device=0):
+    """test tap: LocalBA's reduced-system kernels alone, all cases in one launch of each.  cases: dicts with form (0 = k_ldlt_dev,
+    2 = k_ldlt_reg), H (n x n, n = 6 np), bs, b_pose, x0, scale0 (n each: what x / scale_terms hold on entry), lam, T (np x 7)
+    -> one dict per case: ok, x, scale_terms (n), T_out, T_backup (np x 7)"""
+    cat = lambda k, dt=np.float64: np.ascontiguousarray(np.concatenate([np.asarray(c[k], dt).ravel() for c in cases]))
+    nps = np.array([np.asarray(c["bs"]).size // 6 for c in cases], np.int32)
+    for c, q in zip(cases, nps):
+        assert np.asarray(c["H"]).shape == (6 * q, 6 * q) and np.asarray(c["T"]).shape == (q, 7)
+        assert all(np.asarray(c[k]).shape == (6 * q,) for k in ("bs", "b_pose", "x0", "scale0"))
+    form = np.array([c["form"] for c in cases], np.int32)
+    H, bs, bp, T, x, sc = cat("H"), cat("bs"), cat("b_pose"), cat("T"), cat("x0"), cat("scale0")
+    lam = np.array([c["lam"] for c in cases], np.float64)
+    To, Tb, ok = np.zeros_like(T), np.zeros_like(T), np.zeros(len(cases), np.uint8)
+    _check(lib().aos2_debug_lba_reduced_solve_device(len(cases), _p(nps), _p(form), _p(H), _p(bs), _p(bp), _p(lam), _p(T), _p(x), _p(To), _p(Tb),
+                                                     _p(sc), _p(ok), device))
+    out, o6, o7 = [], 0, 0
+    for q, k in zip(nps, ok):
+        out.append(dict(ok=int(k), x=x[o6:o6 + 6 * q].copy(), scale_terms=sc[o6:o6 + 6 * q].copy(),
+                        T_out=To[o7:o7 + 7 * q].reshape(q, 7).copy(), T_backup=Tb[o7:o7 + 7 * q].reshape(q, 7).copy()))
+        o6 += 6 * q; o7 += 7 * q
+    return out
 
 
 # ------------------------------------------------------------------------------------------ matcher

@@ -1328,6 +1328,14 @@ void k_schur(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ task
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double __attribute__((address_space(1))) gdouble_t;
 constexpr int kTileBatch = 4;
+// doubles of dynamic LDS ldlt_body needs (W, the four vectors, T_k^T of two panels, the staged diagonal block, 16 of slack) ...
+__host__ __device__ constexpr size_t ldlt_dev_lds_doubles(int npad) { return (size_t)npad * 17 + 4 * (size_t)npad + 3 * 16 * 17 + 16; }
+// ... and the largest window that fits a CU's 160 KB with the kernel's static LDS: npad = 928, 154 free keyframes.  A larger window is
+// refused on the host (build_structures) before anything is enqueued.
+constexpr int kLdMaxNpad = 928, kLdMaxNp = kLdMaxNpad / 6;
+constexpr size_t kLdMaxDynLds = ldlt_dev_lds_doubles(kLdMaxNpad) * sizeof(double);   // 162 560 B
+static_assert(kLdMaxDynLds + 64 <= 160 * 1024 && ldlt_dev_lds_doubles(kLdMaxNpad + 16) * sizeof(double) + 64 > 160 * 1024,
+              "k_ldlt_dev: kLdMaxNpad is the largest padded size whose dynamic + static LDS fits a CU's 160 KB");
 __device__ __forceinline__ void ldlt_body(const LbaWin &Wn, double *sm)
 {
     constexpr int NT = 512, NW = 8;
@@ -1769,6 +1777,23 @@ __global__ __launch_bounds__(256) void k_final(const LbaWin *__restrict__ wins)
 }
 
 // ---------------------------------------------------------------------------------------------------------- host
+// The reduced-system kernels take their LDS dynamically (the panel and the vectors of the largest window of a launch): each
+// kernel's cap is declared once per device binding, and every launch goes through enqueue_ldlt, which sizes it
+static int ldlt_declare_lds()
+{
+    AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_dev, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdMaxDynLds));
+    AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLrMaxDynLds));
+    return AOS2_OK;
+}
+// Both forms over the descriptors blk[0 .. nw): a window returns early from the kernel that is not its form.  mx_npad_reg /
+// mx_npad_dev: the largest padded size among the windows of that form, 0 = none (the kernel is not launched)
+static void enqueue_ldlt(const LbaWin *blk, int nw, int mx_npad_reg, int mx_npad_dev, hipStream_t q_reg, hipStream_t q_dev)
+{
+    if (mx_npad_reg > 0)
+        hipLaunchKernelGGL(k_ldlt_reg, dim3(nw), dim3(kLrThreads), ldlt_reg_lds_doubles(mx_npad_reg) * sizeof(double), q_reg, blk);
+    if (mx_npad_dev > 0) hipLaunchKernelGGL(k_ldlt_dev, dim3(nw), dim3(512), ldlt_dev_lds_doubles(mx_npad_dev) * sizeof(double), q_dev, blk);
+}
+
 int lba_handle_init(aos2_lba *s)
 {
     int st = bind_device(s->device);
@@ -1784,9 +1809,7 @@ int lba_handle_init(aos2_lba *s)
         AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
         AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
     }
-    // the reduced-system kernels take their LDS dynamically: the panel and the vectors of the largest window of a launch
-    AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_dev, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLrMaxDynLds));
+    if ((st = ldlt_declare_lds())) return st;
     s->dev_ready = true;
     return AOS2_OK;
 }
@@ -2155,6 +2178,11 @@ static int build_structures(WindowPool &pool, const aos2_lba_problem_t *problems
             set_error("problem %d: two edges connect the same keyframe and map point", ids ? ids[i] : i);
             return AOS2_ERR_ARG;
         }
+    for (int i = 0; i < n; ++i)
+        if (passes[i].np > kLdMaxNp) {   // (k_ldlt_dev's panel and vectors would not fit a CU's LDS: kLdMaxDynLds)
+            set_error("problem %d: %d free keyframes, the reduced-system solve takes at most %d", ids ? ids[i] : i, passes[i].np, kLdMaxNp);
+            return AOS2_ERR_ARG;
+        }
     return AOS2_OK;
 }
 
@@ -2453,11 +2481,7 @@ static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
         (void)hipEventRecord(P.fork, P.q);
         (void)hipStreamWaitEvent(P.q2, P.fork, 0);
     }
-    if (D.any_reg)
-        hipLaunchKernelGGL(k_ldlt_reg, dim3(P.nw), dim3(kLrThreads), ldlt_reg_lds_doubles(D.mx_npad_reg) * sizeof(double), both ? P.q2 : P.q, P.blk);
-    if (D.any_glob)
-        hipLaunchKernelGGL(k_ldlt_dev, dim3(P.nw), dim3(512), ((size_t)D.mx_npad_glob * 17 + 4 * (size_t)D.mx_npad_glob + 3 * 16 * 17 + 16) * sizeof(double), P.q,
-                           P.blk);
+    enqueue_ldlt(P.blk, P.nw, D.any_reg ? D.mx_npad_reg : 0, D.any_glob ? D.mx_npad_glob : 0, both ? P.q2 : P.q, P.q);
     if (both) {
         (void)hipEventRecord(P.join, P.q2);
         (void)hipStreamWaitEvent(P.q, P.join, 0);
@@ -2981,6 +3005,103 @@ int aos2_lba_solve(aos2_lba_t *s, const aos2_lba_problem_t *p, aos2_lba_result_t
     }
     const int st = aos2_lba_solve_batch(s, p, r, 1);
     return st ? st : r->status;
+}
+
+// Test tap: k_ldlt_reg / k_ldlt_dev alone.  One hand-made window descriptor and state per case -- only the members the two kernels read --
+// over a padded matrix filled like k_schur and k_prepare leave it; launched through enqueue_ldlt like a trial's.
+int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const int32_t *form, const double *H, const double *bs, const double *b_pose,
+                                        const double *lambda, const double *T, double *x, double *T_out, double *T_backup, double *scale_terms,
+                                        uint8_t *ok, int device)
+{
+    if (n_cases < 1 || !np || !form || !H || !bs || !b_pose || !lambda || !T || !x || !T_out || !T_backup || !scale_terms || !ok) {
+        set_error("aos2_debug_lba_reduced_solve_device: bad argument");
+        return AOS2_ERR_ARG;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        if (form[c] != kLdltDev && form[c] != kLdltReg) {
+            set_error("aos2_debug_lba_reduced_solve_device: case %d: form %d (0 = k_ldlt_dev, 2 = k_ldlt_reg)", c, form[c]);
+            return AOS2_ERR_ARG;
+        }
+        if (np[c] < 1 || np[c] > (form[c] == kLdltReg ? 16 * kLrMaxNb / 6 : kLdMaxNp)) {
+            set_error("aos2_debug_lba_reduced_solve_device: case %d: %d free keyframes, form %d takes 1..%d", c, np[c], form[c],
+                      form[c] == kLdltReg ? 16 * kLrMaxNb / 6 : kLdMaxNp);
+            return AOS2_ERR_ARG;
+        }
+    }
+    int st = bind_device(device);
+    if (st) return st;
+    if ((st = ldlt_declare_lds())) return st;
+    // regions of a case in one buffer (offsets in bytes)
+    struct CaseLayout {
+        size_t Hs, bs, b, x, tmp, scal, pose, bk, hpose, st;
+        int n, npad;
+    };
+    std::vector<CaseLayout> L(n_cases);
+    Bump B;
+    const size_t o_wins = B.take(sizeof(LbaWin) * (size_t)n_cases);
+    int mx_npad[2] = {0, 0};   // register form, device-memory form
+    for (int c = 0; c < n_cases; ++c) {
+        CaseLayout &l = L[c];
+        l.n = 6 * np[c];
+        l.npad = (l.n + 15) & ~15;
+        int &mx = mx_npad[form[c] == kLdltReg ? 0 : 1];
+        mx = std::max(mx, l.npad);
+        const size_t n8 = 8 * (size_t)l.n, p56 = 56 * (size_t)np[c];
+        l.Hs = B.take(8 * (size_t)l.npad * l.npad); l.bs = B.take(n8); l.b = B.take(n8); l.x = B.take(n8); l.tmp = B.take(n8);
+        l.scal = B.take(64); l.pose = B.take(p56); l.bk = B.take(p56); l.hpose = B.take(4 * (size_t)np[c]); l.st = B.take(sizeof(LmState));
+    }
+    std::vector<uint8_t> host(B.size, 0);
+    DevBuf<uint8_t> dev;
+    if ((st = dev.alloc(B.size))) return st;
+    size_t oH = 0, ov = 0, oT = 0;   // the case's place in the caller's arrays (doubles)
+    for (int c = 0; c < n_cases; ++c) {
+        const CaseLayout &l = L[c];
+        const int n = l.n, npad = l.npad;
+        double *Hs = (double *)(host.data() + l.Hs);
+        for (int r = 0; r < npad; ++r)
+            for (int q = 0; q < npad; ++q) Hs[(size_t)r * npad + q] = r < n && q < n ? H[oH + (size_t)r * n + q] : r == q ? 1.0 : 0.0;
+        memcpy(host.data() + l.bs, bs + ov, 8 * (size_t)n);
+        memcpy(host.data() + l.b, b_pose + ov, 8 * (size_t)n);
+        memcpy(host.data() + l.x, x + ov, 8 * (size_t)n);
+        memcpy(host.data() + l.tmp, scale_terms + ov, 8 * (size_t)n);
+        ((double *)(host.data() + l.scal))[3] = -1.0;   // (neither kernel ran: ok = 255)
+        memcpy(host.data() + l.pose, T + oT, 56 * (size_t)np[c]);
+        memset(host.data() + l.bk, 0xFF, 56 * (size_t)np[c]);   // (NaNs: the backup is the kernel's)
+        for (int i = 0; i < np[c]; ++i) ((int32_t *)(host.data() + l.hpose))[i] = i;
+        LmState *S = (LmState *)(host.data() + l.st);
+        S->run = 1;
+        S->lambda = lambda[c];
+        LbaWin &W = ((LbaWin *)(host.data() + o_wins))[c];
+        W.np = np[c]; W.npad = npad; W.hs_ld = npad; W.ldlt_form = (LdltForm)form[c];
+        W.Hs = (double *)(dev.p + l.Hs); W.bs = (double *)(dev.p + l.bs); W.b = (double *)(dev.p + l.b); W.x = (double *)(dev.p + l.x);
+        W.tmp = (double *)(dev.p + l.tmp); W.scal = (double *)(dev.p + l.scal);
+        W.pose = (double *)(dev.p + l.pose); W.bk = (double *)(dev.p + l.bk); W.n_poses = np[c];
+        W.hpose = (const int32_t *)(dev.p + l.hpose);
+        W.st = (LmState *)(dev.p + l.st);
+        oH += (size_t)n * n; ov += n; oT += 7 * (size_t)np[c];
+    }
+    st = [&]() -> int {
+        AOS2_HIP_CHECK(hipMemcpy(dev.p, host.data(), B.size, hipMemcpyHostToDevice));
+        enqueue_ldlt((const LbaWin *)(dev.p + o_wins), n_cases, mx_npad[0], mx_npad[1], 0, 0);
+        AOS2_HIP_CHECK(hipGetLastError());
+        AOS2_HIP_CHECK(hipDeviceSynchronize());
+        AOS2_HIP_CHECK(hipMemcpy(host.data(), dev.p, B.size, hipMemcpyDeviceToHost));
+        return AOS2_OK;
+    }();
+    dev.release();
+    if (st) return st;
+    ov = oT = 0;
+    for (int c = 0; c < n_cases; ++c) {
+        const CaseLayout &l = L[c];
+        memcpy(x + ov, host.data() + l.x, 8 * (size_t)l.n);
+        memcpy(scale_terms + ov, host.data() + l.tmp, 8 * (size_t)l.n);
+        memcpy(T_out + oT, host.data() + l.pose, 56 * (size_t)np[c]);
+        memcpy(T_backup + oT, host.data() + l.bk, 56 * (size_t)np[c]);
+        const double s3 = ((const double *)(host.data() + l.scal))[3];
+        ok[c] = s3 == 1.0 ? 1 : s3 == 0.0 ? 0 : 255;
+        ov += l.n; oT += 7 * (size_t)np[c];
+    }
+    return AOS2_OK;
 }
 
 }  // extern "C"

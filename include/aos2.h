@@ -665,8 +665,9 @@ void aos2_lba_destroy(aos2_lba_t *s);
  * The whole procedure (both optimisations, the outlier pass, the inlier check) runs on the device without a host
  * round trip per Levenberg-Marquardt trial; *stop_flag is forwarded to the device while the call waits and is
  * evaluated exactly where g2o evaluates terminate() (optimization_algorithm_levenberg.cpp:149,
- * sparse_optimizer.cpp:372) and where Optimizer.cc:663-666 reads it.  Any number of free keyframes: the reduced camera
- * system is factorised in LDS up to 21 of them, in device memory beyond. */
+ * sparse_optimizer.cpp:372) and where Optimizer.cc:663-666 reads it.  Up to 154 free keyframes: the reduced camera
+ * system is factorised in registers up to 40 of them, in device memory beyond, where the panel of the 155th would no longer fit a
+ * compute unit's LDS (AOS2_ERR_ARG, before anything runs). */
 int aos2_lba_solve(aos2_lba_t *s, const aos2_lba_problem_t *p, aos2_lba_result_t *r);
 /* `n_problems` independent windows (several maps, or an offline pass over many windows; SURVEY.md section 8(e):
  * LocalBA = replicas only) in one call: every kernel covers all windows, so their latency-bound Levenberg-Marquardt
@@ -1007,6 +1008,16 @@ int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t
  * ok[i] = 0 where a pivot was not positive (x[i] is left as passed in) */
 int aos2_debug_pose_blocks_device(const double *upd, const double *T, double *T_out, const double *Hb, const double *lambda,
                                   double *x, uint8_t *ok, int n, int device);
+/* The two kernels that solve LocalBA's reduced camera system (csrc/lba.hip: k_ldlt_reg, k_ldlt_dev), alone, with their epilogue: n_cases
+ * independent systems H x = bs in ONE launch of each kernel, sized and launched like a Levenberg-Marquardt trial's.  Case c: np[c] free
+ * keyframes, n = 6 np[c]; form[c] = 2: k_ldlt_reg (np <= 40), 0: k_ldlt_dev (np <= 154); H: n x n, both triangles (the tap pads it the
+ * way the Schur kernel leaves it); the cases' H, bs, b_pose (n each), T (7 per pose: qx qy qz qw tx ty tz) back to back; lambda[c].
+ * Out: ok[c] = 1, or 0 on a zero / NaN pivot (255: no kernel touched the case); x = the solution; T_out[i] = exp(x_i) T[i];
+ * T_backup = T; scale_terms = x (lambda x + b_pose).  x and scale_terms are in/out: a failed case leaves what the caller passed,
+ * T_out = T_backup = T.  AOS2_ERR_ARG (before a device is looked for): a NULL, n_cases < 1, np out of the form's range, another form. */
+int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const int32_t *form, const double *H, const double *bs,
+                                        const double *b_pose, const double *lambda, const double *T, double *x, double *T_out,
+                                        double *T_backup, double *scale_terms, uint8_t *ok, int device);
 
 #ifdef __cplusplus
 }

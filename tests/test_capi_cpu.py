@@ -393,3 +393,48 @@ def test_lba_window_builder_on_a_hand_made_graph(tmp_path):
                            "-I", os.path.join(ROOT, "include"), "-o", exe])
     out = subprocess.check_output([exe], text=True)
     assert "lba_window_test ok: 5 keyframes (3 optimised), 3 points, 8 edges" in out
+
+
+def test_reduced_solve_tap_and_lba_size_limit_refuse_on_the_host(pkg):
+    """aos2_debug_lba_reduced_solve_device checks its arguments before it looks for a device: a NULL, no cases, np < 1, the register
+    form beyond 40 free keyframes, the device-memory form beyond the 154 whose LDS a compute unit holds, an unknown form.  The same
+    limit refuses a LocalBA window in the host phase that aos2_lba_solve_batch runs before it enqueues anything."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ldlt_ref
+    capi = pkg.capi
+    L = capi.lib()
+    H, b = np.eye(6), np.ones(6)
+    T = np.array([[0, 0, 0, 1.0, 0, 0, 0]])
+
+    def one(form, q, **kw):
+        c = dict(form=form, H=np.eye(6 * q), bs=np.ones(6 * q), b_pose=np.ones(6 * q), x0=np.zeros(6 * q), scale0=np.zeros(6 * q), lam=1.0,
+                 T=np.tile(T, (q, 1)))
+        c.update(kw)
+        return c
+
+    for bad in (one(2, 41), one(0, 155), one(1, 1), one(3, 1), one(-1, 1)):
+        with pytest.raises(capi.AosError) as e:
+            capi.debug_lba_reduced_solve_device([bad])
+        assert e.value.code == capi.AOS2_ERR_ARG, bad["form"]
+    f = L.aos2_debug_lba_reduced_solve_device
+    q1, f2 = np.array([1], np.int32), np.array([2], np.int32)
+    lam, x, To, Tb, sc, ok = np.ones(1), np.zeros(6), np.zeros(7), np.zeros(7), np.zeros(6), np.zeros(1, np.uint8)
+    args = [q1, f2, H, b, b, lam, T, x, To, Tb, sc, ok]
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    for k in range(len(args)):   # every pointer in turn
+        a = list(args)
+        a[k] = None
+        assert f(1, *[p(v) for v in a], 0) == capi.AOS2_ERR_ARG, k
+    assert f(0, *[p(v) for v in args], 0) == capi.AOS2_ERR_ARG
+    z = np.zeros(1, np.int32)
+    assert f(1, p(z), *[p(v) for v in args[1:]], 0) == capi.AOS2_ERR_ARG   # np = 0
+    if pkg.device_count() == 0:   # good arguments get as far as the device
+        with pytest.raises(capi.AosError) as e:
+            capi.debug_lba_reduced_solve_device([one(2, 40), one(0, 154)])
+        assert e.value.code == capi.AOS2_ERR_NO_DEVICE
+    # a LocalBA window: 154 free keyframes pass the host phase, 155 do not
+    capi.lba_host_phase([ldlt_ref.lba_star_window(154)], 1)
+    with pytest.raises(capi.AosError) as e:
+        capi.lba_host_phase([ldlt_ref.lba_star_window(155)], 1)
+    assert e.value.code == capi.AOS2_ERR_ARG and "155 free keyframes" in str(e.value)
