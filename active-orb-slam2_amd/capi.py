@@ -1595,7 +1595,7 @@ class Frames:
         B, cap = self.batch, self.cap
         shape, dt = {0: ((B, cap), np.int32), 1: ((B, cap), np.uint8), 2: ((B, 16), np.float32), 3: ((B, cap), np.float32),
                      4: ((B, cap), np.float32), 5: ((B, 64 * 48 + 1), np.int32), 6: ((B, cap), np.int32), 7: ((B, cap), np.float32),
-                     8: ((B, cap), np.float32)}[what]
+                     8: ((B, cap), np.float32)}.get(what, ((B, cap), np.int32))   # (any other id: the library refuses it, whatever the size)
         a = np.zeros(shape, dt)
         _check(self.L.aos2_frames_get(self.h, what, _p(a), a.nbytes))
         return a

@@ -6,6 +6,7 @@
 // entry points are the aos2_frames_* functions of include/aos2.h.
 #pragma once
 #include "aos2_common.h"
+#include "regions.h"
 
 namespace aos2 {
 
@@ -73,33 +74,43 @@ struct MapPointsDev {
     const float *min_dist, *max_dist;   // n
 };
 
+inline MapPointsDev map_points_dev(const aos2_map_points_dev_t *t)
+{
+    MapPointsDev M;
+    M.n = t->n; M.pos = t->pos; M.desc = t->desc; M.has_obs = t->has_obs; M.normal = t->normal;
+    M.min_dist = t->min_dist; M.max_dist = t->max_dist;
+    return M;
+}
+
+// Staging of one kind of keyframe call: what the host assembles, page-locked, and its device copy, both kept by the handle.
+// `uploaded` lies behind the last upload (created by the first asynchronous call): the host buffer is rewritten only after it.
+struct KfStage {
+    PinnedBuf<uint8_t> host;
+    DevBuf<uint8_t> dev;
+    size_t bytes = 0;   // what the call in progress stages: fixed when its buffers are sized, uploaded as that
+    hipEvent_t uploaded = nullptr;
+};
+enum { kKfTriang, kKfFuse, kKfNewPoints, kKfKinds };   // SearchForTriangulation, Fuse, TriangulateMatches
+
 }  // namespace aos2
 
 struct aos2_frames {
     int device = 0;
     bool dev_ready = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {};
     hipEvent_t order_ev = nullptr;   // ordering only (no timing): recorded on this batch's stream for a batch that reads its members
     hipEvent_t ext_ev = nullptr;     // recorded on a caller's stream by aos2_frames_wait_for_stream
     aos2::FramesDev D = {};
     int32_t *d_overflow = nullptr;   // sticky: largest per-frame window population that exceeded the entry pool's share
     aos2::DevBuf<uint8_t> mem;       // the per-frame member arrays
     aos2::DevBuf<float> tables;      // scale factors | inverse level sigma2
+    aos2::PinnedBuf<float> h_tables; // ... as aos2_frames_build assembles them
     // scratch of the searches that run on this batch (sized at the first use)
     aos2::DevBuf<uint8_t> scratch;
     aos2::DevBuf<uint64_t> pool;     // candidate entries (8 B each)
     aos2::DevBuf<uint8_t> pose_mem;  // PoseOptimization problem arrays
-    aos2::PinnedBuf<uint8_t> h_io;   // small page-locked staging (poses, counts)
     aos2::PinnedBuf<int32_t> h_overflow;   // d_overflow: written by the kernels, read by aos2_frames_wait
-    aos2::PinnedBuf<uint8_t> kf_host;   // keyframe work (triangulation pairs, fuse targets): staging ...
-    aos2::DevBuf<uint8_t> kf_dev;       // ... and its device copy
-    aos2::PinnedBuf<uint8_t> kf_host2;  // the same for aos2_frames_fuse (SearchForTriangulation and Fuse of one handle may both be in flight)
-    aos2::DevBuf<uint8_t> kf_dev2;
-    aos2::PinnedBuf<uint8_t> kf_host3;  // ... and for aos2_frames_triangulate_matches (pairs, first-wins groups)
-    aos2::DevBuf<uint8_t> kf_dev3;
+    aos2::KfStage kf[aos2::kKfKinds];   // one slot per kind: a handle's SearchForTriangulation, Fuse and TriangulateMatches may all be in flight
     bool kf_async = false;              // aos2_frames_set_async_keyframe_calls: the keyframe entry points return after enqueueing
-    hipEvent_t kf_ev_tri = nullptr, kf_ev_fuse = nullptr, kf_ev_new = nullptr;   // behind the upload of the staging buffer of the last call of each kind
     float dist[5] = {0, 0, 0, 0, 0};   // mDistCoef for the next aos2_frames_build (aos2_frames_set_distortion)
-    float last_ms[4] = {};
 };

@@ -370,35 +370,22 @@ __global__ void frames_set_state_kernel(FramesDev S, MapPointsDev M)
     S.mp_state[o] = (i < S.n[b] && row >= 0) ? (M.has_obs[row] ? 2 : 1) : 0;
 }
 
-static MapPointsDev map_points_dev(const aos2_map_points_dev_t *t)
-{
-    MapPointsDev M;
-    M.n = t->n; M.pos = t->pos; M.desc = t->desc; M.has_obs = t->has_obs; M.normal = t->normal;
-    M.min_dist = t->min_dist; M.max_dist = t->max_dist;
-    return M;
-}
-
 static int frames_init(aos2_frames *f)
 {
     int st = bind_device(f->device);
     if (st) return st;
     if (f->dev_ready) return AOS2_OK;
     if (int st_ = stream_create(&f->stream, false)) return st_;
-    for (auto &e : f->ev) AOS2_HIP_CHECK(hipEventCreate(&e));
     // member arrays
-    const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap, n = B * cap;
-    size_t sz = 0;
-    const size_t o_x = carve(sz, 4 * n), o_y = carve(sz, 4 * n), o_a = carve(sz, 4 * n), o_oct = carve(sz, 4 * n), o_ur = carve(sz, 4 * n), o_dp = carve(sz, 4 * n);
-    const size_t o_go = carve(sz, 4 * B * (kFrGridCells + 1)), o_gi = carve(sz, 4 * n), o_mp = carve(sz, 4 * n), o_seen = carve(sz, 4 * n);
-    const size_t o_st = carve(sz, n), o_out = carve(sz, n), o_T = carve(sz, 64 * B);
-    if ((st = f->mem.alloc(sz + 256))) return st;
-    AOS2_HIP_CHECK(hipMemsetAsync(f->mem.p, 0, sz, f->stream));
-    uint8_t *m = f->mem.p;
-    f->D.kp_x = (float *)(m + o_x); f->D.kp_y = (float *)(m + o_y); f->D.kp_angle = (float *)(m + o_a);
-    f->D.kp_octave = (int32_t *)(m + o_oct); f->D.u_right = (float *)(m + o_ur); f->D.depth = (float *)(m + o_dp);
-    f->D.grid_off = (int32_t *)(m + o_go); f->D.grid_idx = (int32_t *)(m + o_gi);
-    f->D.mp = (int32_t *)(m + o_mp); f->D.mp_seen = (int32_t *)(m + o_seen);
-    f->D.mp_state = m + o_st; f->D.outlier = m + o_out; f->D.Tcw = (float *)(m + o_T);
+    FramesDev &D = f->D;
+    const size_t B = (size_t)D.batch, n = B * (size_t)D.cap;
+    Regions<13> R;
+    R.add(D.kp_x, n); R.add(D.kp_y, n); R.add(D.kp_angle, n); R.add(D.kp_octave, n); R.add(D.u_right, n); R.add(D.depth, n);
+    R.add(D.grid_off, B * (kFrGridCells + 1)); R.add(D.grid_idx, n); R.add(D.mp, n); R.add(D.mp_seen, n);
+    R.add(D.mp_state, n); R.add(D.outlier, n); R.add(D.Tcw, 16 * B);
+    if ((st = f->mem.alloc(R.bytes() + 256))) return st;
+    AOS2_HIP_CHECK(hipMemsetAsync(f->mem.p, 0, R.bytes(), f->stream));
+    R.bind(f->mem.p);
     // the sticky overflow word lives in page-locked HOST memory the kernels write through (rarely: only when a frame's windows did
     // not fit): aos2_frames_wait reads it after the stream has drained, without a copy -- a 4-byte device-to-host copy behind the
     // last kernel cost ~35 us of a single frame's 0.68 ms
@@ -406,7 +393,7 @@ static int frames_init(aos2_frames *f)
     memset(f->h_overflow.p, 0, 16 * sizeof(int32_t));
     f->d_overflow = f->h_overflow.p;
     if ((st = f->tables.alloc(64))) return st;
-    if ((st = f->h_io.alloc(4096))) return st;
+    if ((st = f->h_tables.alloc(16))) return st;
     f->dev_ready = true;
     return AOS2_OK;
 }
@@ -422,24 +409,21 @@ struct FrScratch {
     int share;
 };
 
+// The two searches lay the one `scratch` buffer out differently (their query and local-point counts differ): each runs to
+// its end on the batch's stream before the next one starts there, so neither sees the other's layout.
 static int frames_scratch(aos2_frames *f, int nq_cap, int n_local, FrScratch &X)
 {
-    const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap;
-    size_t sz = 0;
+    const size_t B = (size_t)f->D.batch, nf = B * (size_t)f->D.cap;
     const size_t nq = B * (size_t)nq_cap, nl = B * (size_t)n_local;
-    const size_t o_sl = carve(sz, sizeof(QuerySlot) * nq), o_ch = carve(sz, 4 * nq), o_m = carve(sz, 4 * B * cap), o_bin = carve(sz, 4 * B * cap);
-    const size_t o_nm = carve(sz, 4 * B), o_rec = carve(sz, sizeof(QueryRec) * nq);
-    const size_t o_iv = carve(sz, nl), o_ho = carve(sz, nl), o_px = carve(sz, 4 * nl), o_py = carve(sz, 4 * nl), o_pr = carve(sz, 4 * nl), o_vc = carve(sz, 4 * nl);
-    const size_t o_pl = carve(sz, 4 * nl), o_di = carve(sz, 4 * nl);
+    LocalDev &L = X.L;
+    Regions<14> R;
+    R.add(X.slots, nq); R.add(X.choice, nq); R.add(X.match_f, nf); R.add(X.bin_f, nf); R.add(X.nmatches, B); R.add(X.rec, nq);
+    R.add(L.in_view, nl); R.add(L.has_obs, nl); R.add(L.proj_x, nl); R.add(L.proj_y, nl); R.add(L.proj_xr, nl); R.add(L.view_cos, nl);
+    R.add(L.pred_level, nl); R.add(L.desc_idx, nl);
     int st;
-    if ((st = f->scratch.alloc(sz + 256))) return st;
-    uint8_t *m = f->scratch.p;
-    X.slots = (QuerySlot *)(m + o_sl); X.choice = (int32_t *)(m + o_ch); X.match_f = (int32_t *)(m + o_m);
-    X.bin_f = (uint32_t *)(m + o_bin); X.nmatches = (int32_t *)(m + o_nm); X.rec = (QueryRec *)(m + o_rec);
-    X.L.n_local = n_local; X.L.local = nullptr;
-    X.L.in_view = m + o_iv; X.L.has_obs = m + o_ho; X.L.proj_x = (float *)(m + o_px); X.L.proj_y = (float *)(m + o_py);
-    X.L.proj_xr = (float *)(m + o_pr); X.L.view_cos = (float *)(m + o_vc); X.L.pred_level = (int32_t *)(m + o_pl);
-    X.L.desc_idx = (int32_t *)(m + o_di);
+    if ((st = f->scratch.alloc(R.bytes() + 256))) return st;
+    R.bind(f->scratch.p);
+    L.n_local = n_local; L.local = nullptr;
     // entry pool: `share` entries per frame = its queries x the average window population budgeted (the windows of
     // a frame share it; AOS2_FRAMES_WINDOW_BUDGET, default 64 features per window on average)
     int budget = 64;
@@ -452,6 +436,86 @@ static int frames_scratch(aos2_frames *f, int nq_cap, int n_local, FrScratch &X)
     if ((st = f->pool.alloc(share * B + 1))) return st;
     X.pool = reinterpret_cast<Entry *>(f->pool.p);
     X.share = (int)share;
+    return AOS2_OK;
+}
+
+// One Frame member array as include/aos2.h documents it (AOS2_FRAMES_*): where it lies, its element size, its elements per
+// frame, and whether aos2_frames_get copies it out (the others are "device pointer only").  An unknown id has no array.
+struct FrameMember {
+    const void *p;
+    size_t elem, per_frame;
+    bool gettable;
+};
+
+template <class T>
+static FrameMember member_of(const T *p, size_t per_frame, bool gettable) { return FrameMember{p, sizeof(T), per_frame, gettable}; }
+
+static FrameMember frame_member(const FramesDev &D, int what)
+{
+    const size_t cap = (size_t)D.cap;
+    switch (what) {
+    case AOS2_FRAMES_MAP_POINTS: return member_of(D.mp, cap, true);
+    case AOS2_FRAMES_OUTLIER: return member_of(D.outlier, cap, true);
+    case AOS2_FRAMES_TCW: return member_of(D.Tcw, 16, true);
+    case AOS2_FRAMES_U_RIGHT: return member_of(D.u_right, cap, true);
+    case AOS2_FRAMES_DEPTH: return member_of(D.depth, cap, true);
+    case AOS2_FRAMES_GRID_OFF: return member_of(D.grid_off, kFrGridCells + 1, true);
+    case AOS2_FRAMES_GRID_IDX: return member_of(D.grid_idx, cap, true);
+    case AOS2_FRAMES_KEYS_UN_X: return member_of(D.kp_x, cap, true);
+    case AOS2_FRAMES_KEYS_UN_Y: return member_of(D.kp_y, cap, true);
+    case AOS2_FRAMES_KEYS_ANGLE: return member_of(D.kp_angle, cap, false);
+    case AOS2_FRAMES_KEYS_OCTAVE: return member_of(D.kp_octave, cap, false);
+    default: return FrameMember{nullptr, 0, 0, false};
+    }
+}
+
+// `s` waits for everything enqueued on the producer batch's stream so far: the kernels the caller puts on `s` read members
+// (mvpMapPoints, mvbOutlier, mTcw, keys) that the work on the producer's own stream may still be writing -- in a tracking loop
+// the previous CurrentFrame batch becomes LastFrame while its PoseOptimization is in flight.  The entry points take the
+// producer as a read-only batch; the event it lends to the ordering is the handle's bookkeeping, none of its members: hence
+// the const_cast, here and nowhere else.
+static int order_behind(hipStream_t s, const aos2_frames *producer)
+{
+    aos2_frames *p = const_cast<aos2_frames *>(producer);
+    if (!p->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&p->order_ev, hipEventDisableTiming));
+    AOS2_HIP_CHECK(hipEventRecord(p->order_ev, p->stream));
+    AOS2_HIP_CHECK(hipStreamWaitEvent(s, p->order_ev, 0));
+    return AOS2_OK;
+}
+
+// A keyframe call stages its host arrays through its slot of the batch: kf_stage_begin, the host fill, (order_behind,)
+// kf_stage_upload, the kernels, kf_call_end.
+//
+// the slot's last upload is over (asynchronous calls), both buffers hold `count` elements -> the page-locked one, to be filled
+template <class T>
+static int kf_stage_begin(KfStage &k, size_t count, T *&host)
+{
+    if (k.uploaded) AOS2_HIP_CHECK(hipEventSynchronize(k.uploaded));
+    k.bytes = sizeof(T) * count;
+    if (int st = k.host.alloc(k.bytes)) return st;
+    if (int st = k.dev.alloc(k.bytes)) return st;
+    host = reinterpret_cast<T *>(k.host.p);
+    return AOS2_OK;
+}
+
+// the filled buffer goes to the device on the batch's stream -> its device copy; an asynchronous call marks the upload's end
+template <class T>
+static int kf_stage_upload(aos2_frames *f, KfStage &k, const T *&dev)
+{
+    AOS2_HIP_CHECK(hipMemcpyAsync(k.dev.p, k.host.p, k.bytes, hipMemcpyHostToDevice, f->stream));
+    if (f->kf_async) {
+        if (!k.uploaded) AOS2_HIP_CHECK(hipEventCreateWithFlags(&k.uploaded, hipEventDisableTiming));
+        AOS2_HIP_CHECK(hipEventRecord(k.uploaded, f->stream));
+    }
+    dev = reinterpret_cast<const T *>(k.dev.p);
+    return AOS2_OK;
+}
+
+// the kernels are enqueued: a synchronous call waits for them, an asynchronous one leaves that to aos2_frames_wait
+static int kf_call_end(aos2_frames *f)
+{
+    AOS2_HIP_CHECK(hipGetLastError());
+    if (!f->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(f->stream));
     return AOS2_OK;
 }
 
@@ -480,12 +544,11 @@ void aos2_frames_destroy(aos2_frames_t *f)
         (void)hipSetDevice(f->device);
         (void)hipStreamSynchronize(f->stream);
         f->mem.release(); f->tables.release(); f->scratch.release(); f->pool.release(); f->pose_mem.release();
-        f->h_io.release(); f->h_overflow.release(); f->kf_host.release(); f->kf_dev.release(); f->kf_host2.release(); f->kf_dev2.release();
-        f->kf_host3.release(); f->kf_dev3.release();
-        if (f->kf_ev_tri) (void)hipEventDestroy(f->kf_ev_tri);
-        if (f->kf_ev_fuse) (void)hipEventDestroy(f->kf_ev_fuse);
-        if (f->kf_ev_new) (void)hipEventDestroy(f->kf_ev_new);
-        for (auto &e : f->ev) (void)hipEventDestroy(e);
+        f->h_tables.release(); f->h_overflow.release();
+        for (KfStage &k : f->kf) {
+            k.host.release(); k.dev.release();
+            if (k.uploaded) (void)hipEventDestroy(k.uploaded);
+        }
         if (f->order_ev) (void)hipEventDestroy(f->order_ev);
         if (f->ext_ev) (void)hipEventDestroy(f->ext_ev);
         (void)hipStreamDestroy(f->stream);
@@ -502,20 +565,7 @@ void *aos2_frames_stream(aos2_frames_t *f)
 const void *aos2_frames_device_ptr(aos2_frames_t *f, int what)
 {
     if (!f || !f->dev_ready) return nullptr;
-    switch (what) {
-    case AOS2_FRAMES_MAP_POINTS: return f->D.mp;
-    case AOS2_FRAMES_OUTLIER: return f->D.outlier;
-    case AOS2_FRAMES_TCW: return f->D.Tcw;
-    case AOS2_FRAMES_U_RIGHT: return f->D.u_right;
-    case AOS2_FRAMES_DEPTH: return f->D.depth;
-    case AOS2_FRAMES_GRID_OFF: return f->D.grid_off;
-    case AOS2_FRAMES_GRID_IDX: return f->D.grid_idx;
-    case AOS2_FRAMES_KEYS_UN_X: return f->D.kp_x;
-    case AOS2_FRAMES_KEYS_UN_Y: return f->D.kp_y;
-    case AOS2_FRAMES_KEYS_ANGLE: return f->D.kp_angle;
-    case AOS2_FRAMES_KEYS_OCTAVE: return f->D.kp_octave;
-    default: return nullptr;
-    }
+    return frame_member(f->D, what).p;
 }
 
 int aos2_frames_wait(aos2_frames_t *f)
@@ -547,31 +597,6 @@ int aos2_frames_wait(aos2_frames_t *f)
 static int frames_build_any(aos2_frames_t *f, aos2_extractor_t *e, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
                             const int32_t *d_n, int cap, int w, int h, const float *d_depth, int depth_stride,
                             size_t depth_image_stride, const float *d_u_right, const float *d_depth_kp, float fx, float fy, float cx,
-                            float cy, float mbf);
-
-int aos2_frames_build(aos2_frames_t *f, aos2_extractor_t *e, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
-                      const int32_t *d_n, int cap, int w, int h, const float *d_depth, int depth_stride,
-                      size_t depth_image_stride, float fx, float fy, float cx, float cy, float mbf)
-{
-    return frames_build_any(f, e, batch, d_kps, d_desc, d_n, cap, w, h, d_depth, depth_stride, depth_image_stride, nullptr, nullptr, fx, fy,
-                            cx, cy, mbf);
-}
-
-int aos2_frames_build_stereo(aos2_frames_t *f, aos2_extractor_t *e_left, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
-                             const int32_t *d_n, int cap, int w, int h, const float *d_u_right, const float *d_depth_kp, float fx,
-                             float fy, float cx, float cy, float mbf)
-{
-    if (!d_u_right || !d_depth_kp) {
-        set_error("bad argument (mvuRight / mvDepth of ComputeStereoMatches)");
-        return AOS2_ERR_ARG;
-    }
-    return frames_build_any(f, e_left, batch, d_kps, d_desc, d_n, cap, w, h, nullptr, w, (size_t)w * h, d_u_right, d_depth_kp, fx, fy, cx,
-                            cy, mbf);
-}
-
-static int frames_build_any(aos2_frames_t *f, aos2_extractor_t *e, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
-                            const int32_t *d_n, int cap, int w, int h, const float *d_depth, int depth_stride,
-                            size_t depth_image_stride, const float *d_u_right, const float *d_depth_kp, float fx, float fy, float cx,
                             float cy, float mbf)
 {
     if (!f || !e || !d_kps || !d_desc || !d_n || batch != f->D.batch || cap != f->D.cap || w <= 0 || h <= 0 ||
@@ -588,7 +613,7 @@ static int frames_build_any(aos2_frames_t *f, aos2_extractor_t *e, int batch, co
         return AOS2_ERR_ARG;
     }
     // mvScaleFactors, mvInvLevelSigma2 (Frame.cc:94-100 copies them from the extractor)
-    float *ht = reinterpret_cast<float *>(f->h_io.p + 1024);
+    float *ht = f->h_tables.p;   // [0, 8) scale factors, [8, 16) inverse level sigma2
     memcpy(ht, aos2_extractor_scale_factors(e), sizeof(float) * L);
     memcpy(ht + 8, aos2_extractor_inv_sigma2(e), sizeof(float) * L);
     AOS2_HIP_CHECK(hipMemcpyAsync(f->tables.p, ht, sizeof(float) * 16, hipMemcpyHostToDevice, f->stream));
@@ -615,6 +640,26 @@ static int frames_build_any(aos2_frames_t *f, aos2_extractor_t *e, int batch, co
                        d_depth_kp);
     AOS2_HIP_CHECK(hipGetLastError());
     return AOS2_OK;
+}
+
+int aos2_frames_build(aos2_frames_t *f, aos2_extractor_t *e, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
+                      const int32_t *d_n, int cap, int w, int h, const float *d_depth, int depth_stride,
+                      size_t depth_image_stride, float fx, float fy, float cx, float cy, float mbf)
+{
+    return frames_build_any(f, e, batch, d_kps, d_desc, d_n, cap, w, h, d_depth, depth_stride, depth_image_stride, nullptr, nullptr, fx, fy,
+                            cx, cy, mbf);
+}
+
+int aos2_frames_build_stereo(aos2_frames_t *f, aos2_extractor_t *e_left, int batch, const aos2_keypoint_t *d_kps, const uint8_t *d_desc,
+                             const int32_t *d_n, int cap, int w, int h, const float *d_u_right, const float *d_depth_kp, float fx,
+                             float fy, float cx, float cy, float mbf)
+{
+    if (!d_u_right || !d_depth_kp) {
+        set_error("bad argument (mvuRight / mvDepth of ComputeStereoMatches)");
+        return AOS2_ERR_ARG;
+    }
+    return frames_build_any(f, e_left, batch, d_kps, d_desc, d_n, cap, w, h, nullptr, w, (size_t)w * h, d_u_right, d_depth_kp, fx, fy, cx,
+                            cy, mbf);
 }
 
 // Frame::ComputeImageBounds (src/Frame.cc:463-493): once per camera, four points, on the host
@@ -675,26 +720,17 @@ int aos2_frames_get(aos2_frames_t *f, int what, void *dst, size_t bytes)
     }
     int st = bind_device(f->device);
     if (st) return st;
-    const size_t n = (size_t)f->D.batch * f->D.cap;
-    const void *src = nullptr;
-    size_t have = 0;
-    switch (what) {
-    case AOS2_FRAMES_MAP_POINTS: src = f->D.mp; have = 4 * n; break;
-    case AOS2_FRAMES_OUTLIER: src = f->D.outlier; have = n; break;
-    case AOS2_FRAMES_TCW: src = f->D.Tcw; have = 64 * (size_t)f->D.batch; break;
-    case AOS2_FRAMES_U_RIGHT: src = f->D.u_right; have = 4 * n; break;
-    case AOS2_FRAMES_DEPTH: src = f->D.depth; have = 4 * n; break;
-    case AOS2_FRAMES_GRID_OFF: src = f->D.grid_off; have = 4 * (size_t)f->D.batch * (kFrGridCells + 1); break;
-    case AOS2_FRAMES_GRID_IDX: src = f->D.grid_idx; have = 4 * n; break;
-    case AOS2_FRAMES_KEYS_UN_X: src = f->D.kp_x; have = 4 * n; break;
-    case AOS2_FRAMES_KEYS_UN_Y: src = f->D.kp_y; have = 4 * n; break;
-    default: set_error("unknown member %d", what); return AOS2_ERR_ARG;
+    const FrameMember m = frame_member(f->D, what);
+    if (!m.gettable) {
+        set_error("unknown member %d", what);
+        return AOS2_ERR_ARG;
     }
+    const size_t have = m.elem * m.per_frame * (size_t)f->D.batch;
     if (bytes != have) {
         set_error("member %d holds %zu bytes, %zu requested", what, have, bytes);
         return AOS2_ERR_ARG;
     }
-    AOS2_HIP_CHECK(hipMemcpyAsync(dst, src, have, hipMemcpyDeviceToHost, f->stream));
+    AOS2_HIP_CHECK(hipMemcpyAsync(dst, m.p, have, hipMemcpyDeviceToHost, f->stream));
     AOS2_HIP_CHECK(hipStreamSynchronize(f->stream));
     return AOS2_OK;
 }
@@ -714,16 +750,7 @@ int aos2_frames_search_by_projection_last(aos2_frames_t *cur, const aos2_frames_
     const MapPointsDev M = map_points_dev(mps);
     hipStream_t q = cur->stream;
     const int B = C.batch;
-    if (last != cur) {
-        // the kernels below read LastFrame's mvpMapPoints / mvbOutlier / mTcw / keys, which the work enqueued on last's own
-        // stream may still be writing (in a tracking loop the previous CurrentFrame batch becomes LastFrame while its
-        // PoseOptimization is in flight): cur's stream waits for everything enqueued on last's stream so far
-        aos2_frames *lw = const_cast<aos2_frames *>(last);
-        if (!lw->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&lw->order_ev, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(lw->order_ev, lw->stream));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(q, lw->order_ev, 0));
-    }
-    AOS2_HIP_CHECK(hipEventRecord(cur->ev[0], q));
+    if (last != cur && (st = order_behind(q, last))) return st;
     AOS2_HIP_CHECK(hipMemsetAsync(X.slots, 0, sizeof(QuerySlot) * (size_t)B * Lf.cap, q));
     if (B >= 8)   // a thread per query; a few frames fill the device better with a wave per query
         hipLaunchKernelGGL(frames_last_count_kernel, dim3((Lf.cap + 255) / 256, B), dim3(256), 0, q, C, Lf, M, th, mono ? 1 : 0, X.slots, X.rec);
@@ -741,7 +768,6 @@ int aos2_frames_search_by_projection_last(aos2_frames_t *cur, const aos2_frames_
     else
         hipLaunchKernelGGL(frames_last_resolve_kernel<512>, dim3(B), dim3(512), (size_t)C.cap * 8 + 16, q, C, Lf, M, check_orientation ? 1 : 0,
                            X.slots, X.pool, X.match_f, X.bin_f, X.nmatches, X.choice, d_nmatches);
-    AOS2_HIP_CHECK(hipEventRecord(cur->ev[1], q));
     AOS2_HIP_CHECK(hipGetLastError());
     return AOS2_OK;
 }
@@ -954,36 +980,24 @@ int aos2_frames_search_for_triangulation(aos2_frames_t *a, aos2_frames_t *b, con
             set_error("pair %d names keyframes (%d, %d) outside the batches", p, q->kf1[p], q->kf2[p]);
             return AOS2_ERR_ARG;
         }
-    // the pair records: page-locked staging of the batch, then its own device buffer (kept by the handle)
-    const size_t bytes = sizeof(FrTriPair) * (size_t)n;
-    if (a->kf_ev_tri) AOS2_HIP_CHECK(hipEventSynchronize(a->kf_ev_tri));   // (asynchronous calls: the staging buffer's last upload is over)
-    if ((st = a->kf_host.alloc(bytes))) return st;
-    if ((st = a->kf_dev.alloc(bytes))) return st;
-    FrTriPair *h = reinterpret_cast<FrTriPair *>(a->kf_host.p);
+    // the pair records
+    KfStage &stage = a->kf[kKfTriang];
+    FrTriPair *h;
+    if ((st = kf_stage_begin(stage, (size_t)n, h))) return st;
     for (int p = 0; p < n; ++p) {
         h[p].kf1 = q->kf1[p]; h[p].kf2 = q->kf2[p];
         memcpy(h[p].F12, q->F12 + 9 * (size_t)p, 36);
         h[p].ex = q->epipole[2 * p]; h[p].ey = q->epipole[2 * p + 1];
     }
     hipStream_t s = a->stream;
-    if (b != a) {   // the members of `b` may still be written on its own stream
-        if (!b->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&b->order_ev, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(b->order_ev, b->stream));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(s, b->order_ev, 0));
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(a->kf_dev.p, h, bytes, hipMemcpyHostToDevice, s));
-    if (a->kf_async) {
-        if (!a->kf_ev_tri) AOS2_HIP_CHECK(hipEventCreateWithFlags(&a->kf_ev_tri, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(a->kf_ev_tri, s));
-    }
-    const FrTriPair *dp = reinterpret_cast<const FrTriPair *>(a->kf_dev.p);
+    if (b != a && (st = order_behind(s, b))) return st;
+    const FrTriPair *dp;
+    if ((st = kf_stage_upload(a, stage, dp))) return st;
     hipLaunchKernelGGL(frames_triang_match_kernel, dim3((a->D.cap + 255) / 256, n), dim3(256), 0, s, a->D, b->D, dp, q->d_node_of1,
                        FrFvDev{q->d_fv_node1, q->d_fv_off1, q->d_fv_idx1, q->d_n_fv1}, q->d_fv_node2, q->d_fv_off2,
                        q->d_fv_idx2, q->d_n_fv2, only_stereo ? 1 : 0, d_match12);
     hipLaunchKernelGGL(frames_triang_finish_kernel, dim3(n), dim3(64), 0, s, a->D, b->D, dp, check_orientation ? 1 : 0, d_match12, d_nmatches);
-    AOS2_HIP_CHECK(hipGetLastError());
-    if (!a->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(s));   // (asynchronous: aos2_frames_wait(a) completes the call)
-    return AOS2_OK;
+    return kf_call_end(a);
 }
 
 int aos2_frames_fuse(aos2_frames_t *kfs, const aos2_map_points_dev_t *mps, int n_problems, int n_pts, const int32_t *target,
@@ -1002,22 +1016,15 @@ int aos2_frames_fuse(aos2_frames_t *kfs, const aos2_map_points_dev_t *mps, int n
             set_error("problem %d names keyframe %d outside the batch", p, target[p]);
             return AOS2_ERR_ARG;
         }
-    const size_t bytes = 4 * (size_t)n_problems;
-    if (kfs->kf_ev_fuse) AOS2_HIP_CHECK(hipEventSynchronize(kfs->kf_ev_fuse));
-    if ((st = kfs->kf_host2.alloc(bytes))) return st;
-    if ((st = kfs->kf_dev2.alloc(bytes))) return st;
-    memcpy(kfs->kf_host2.p, target, bytes);
-    hipStream_t s = kfs->stream;
-    AOS2_HIP_CHECK(hipMemcpyAsync(kfs->kf_dev2.p, kfs->kf_host2.p, bytes, hipMemcpyHostToDevice, s));
-    if (kfs->kf_async) {
-        if (!kfs->kf_ev_fuse) AOS2_HIP_CHECK(hipEventCreateWithFlags(&kfs->kf_ev_fuse, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(kfs->kf_ev_fuse, s));
-    }
-    hipLaunchKernelGGL(frames_fuse_kernel, dim3((n_pts + 255) / 256, n_problems), dim3(256), 0, s, kfs->D, map_points_dev(mps),
-                       reinterpret_cast<const int32_t *>(kfs->kf_dev2.p), d_rows, n_pts, th, d_best_idx, d_best_dist);
-    AOS2_HIP_CHECK(hipGetLastError());
-    if (!kfs->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(s));
-    return AOS2_OK;
+    KfStage &stage = kfs->kf[kKfFuse];
+    int32_t *h;
+    if ((st = kf_stage_begin(stage, (size_t)n_problems, h))) return st;
+    memcpy(h, target, 4 * (size_t)n_problems);
+    const int32_t *d_target;
+    if ((st = kf_stage_upload(kfs, stage, d_target))) return st;
+    hipLaunchKernelGGL(frames_fuse_kernel, dim3((n_pts + 255) / 256, n_problems), dim3(256), 0, kfs->stream, kfs->D, map_points_dev(mps),
+                       d_target, d_rows, n_pts, th, d_best_idx, d_best_dist);
+    return kf_call_end(kfs);
 }
 
 int aos2_frames_set_async_keyframe_calls(aos2_frames_t *f, int on)
@@ -1073,7 +1080,6 @@ int aos2_frames_search_local_points(aos2_frames_t *f, const aos2_map_points_dev_
     const MapPointsDev M = map_points_dev(mps);
     hipStream_t q = f->stream;
     const int B = S.batch;
-    AOS2_HIP_CHECK(hipEventRecord(f->ev[2], q));
     hipLaunchKernelGGL(frames_frustum_kernel, dim3(B), dim3(256), 0, q, S, M, X.L, 0.5f);
     if (B >= 8)
         hipLaunchKernelGGL(frames_local_count_kernel, dim3((n_local + 255) / 256, B), dim3(256), 0, q, S, M, X.L, th, X.slots, X.rec);
@@ -1084,7 +1090,6 @@ int aos2_frames_search_local_points(aos2_frames_t *f, const aos2_map_points_dev_
     hipLaunchKernelGGL(frames_local_entries_kernel, dim3((n_local + kEntryWaves - 1) / kEntryWaves, B), dim3(64 * kEntryWaves), 0, q, S, M, X.L, th, X.slots, X.pool, f->d_overflow, 2, X.rec);
     hipLaunchKernelGGL(frames_local_resolve_kernel, dim3(B), dim3(512), (size_t)S.cap * 8 + 16, q, S, M, X.L, nnratio, X.slots, X.pool,
                        X.match_f, X.nmatches, X.choice, d_nmatches);
-    AOS2_HIP_CHECK(hipEventRecord(f->ev[3], q));
     AOS2_HIP_CHECK(hipGetLastError());
     return AOS2_OK;
 }

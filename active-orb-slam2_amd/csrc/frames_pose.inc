@@ -6,7 +6,6 @@
 namespace aos2 {
 
 struct PoseBatchDev {
-    PoseProbDev *probs;      // [B] (unused by the fused kernel)
     float *Xw, *obs, *w;     // [B][cap] x 3, 3, 1
     double *err;             // [B][cap]
     uint8_t *stereo, *l1, *rb, *out;   // [B][cap]
@@ -86,23 +85,13 @@ extern "C" int aos2_frames_pose_optimization(aos2_frames_t *f, const aos2_map_po
     int st = bind_device(f->device);
     if (st) return st;
     const size_t B = (size_t)f->D.batch, cap = (size_t)f->D.cap, n = B * cap;
-    size_t sz = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = (sz + 255) & ~(size_t)255;
-        sz = o + bytes;
-        return o;
-    };
-    const size_t o_pr = take(sizeof(PoseProbDev) * B), o_x = take(12 * n), o_ob = take(12 * n), o_w = take(4 * n), o_er = take(8 * n);
-    const size_t o_s = take(n), o_l1 = take(n), o_rb = take(n), o_out = take(n), o_f = take(4 * n), o_po = take(56 * B), o_c = take(8 * B);
-    if ((st = f->pose_mem.alloc(sz + 256))) return st;
-    uint8_t *m = f->pose_mem.p;
     PoseBatchDev Q;
-    Q.probs = (PoseProbDev *)(m + o_pr); Q.Xw = (float *)(m + o_x); Q.obs = (float *)(m + o_ob); Q.w = (float *)(m + o_w);
-    Q.err = (double *)(m + o_er); Q.stereo = m + o_s; Q.l1 = m + o_l1; Q.rb = m + o_rb; Q.out = m + o_out;
-    Q.feat_of = (int32_t *)(m + o_f); Q.pose_out = (double *)(m + o_po); Q.counts = (int32_t *)(m + o_c);
-    MapPointsDev M;
-    M.n = mps->n; M.pos = mps->pos; M.desc = mps->desc; M.has_obs = mps->has_obs; M.normal = mps->normal;
-    M.min_dist = mps->min_dist; M.max_dist = mps->max_dist;
+    Regions<11> R;
+    R.add(Q.Xw, 3 * n); R.add(Q.obs, 3 * n); R.add(Q.w, n); R.add(Q.err, n);
+    R.add(Q.stereo, n); R.add(Q.l1, n); R.add(Q.rb, n); R.add(Q.out, n); R.add(Q.feat_of, n); R.add(Q.pose_out, 7 * B); R.add(Q.counts, 2 * B);
+    if ((st = f->pose_mem.alloc(R.bytes() + 256))) return st;
+    R.bind(f->pose_mem.p);
+    const MapPointsDev M = map_points_dev(mps);
     hipStream_t q = f->stream;
     const size_t po_lds = kPoLds;
     // 256 threads per frame, 4 edge slots per thread.  (512 threads x 2 slots and 1024 x 1 were measured -- the template

@@ -178,11 +178,10 @@ int aos2_frames_triangulate_matches(aos2_frames_t *a, aos2_frames_t *b, int n_pa
             return AOS2_ERR_ARG;
         }
     // staging (page-locked, then the handle's own device copy): kf1 | kf2 | group offsets | the pairs group by group
-    const size_t words = 4 * (size_t)n + 1, bytes = 4 * words;
-    if (a->kf_ev_new) AOS2_HIP_CHECK(hipEventSynchronize(a->kf_ev_new));   // (asynchronous calls: the staging buffer's last upload is over)
-    if ((st = a->kf_host3.alloc(bytes))) return st;
-    if ((st = a->kf_dev3.alloc(bytes))) return st;
-    int32_t *h = reinterpret_cast<int32_t *>(a->kf_host3.p);
+    const size_t words = 4 * (size_t)n + 1;
+    KfStage &stage = a->kf[kKfNewPoints];
+    int32_t *h;
+    if ((st = kf_stage_begin(stage, words, h))) return st;
     int32_t *h_kf1 = h, *h_kf2 = h + n, *h_off = h + 2 * n, *h_grp;
     memcpy(h_kf1, kf1, 4 * (size_t)n);
     memcpy(h_kf2, kf2, 4 * (size_t)n);
@@ -216,25 +215,15 @@ int aos2_frames_triangulate_matches(aos2_frames_t *a, aos2_frames_t *b, int n_pa
         h_off[n] = n;
     }
     hipStream_t s = a->stream;
-    if (b != a) {   // the members of `b` may still be written on its own stream
-        if (!b->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&b->order_ev, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(b->order_ev, b->stream));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(s, b->order_ev, 0));
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(a->kf_dev3.p, h, bytes, hipMemcpyHostToDevice, s));
-    if (a->kf_async) {
-        if (!a->kf_ev_new) AOS2_HIP_CHECK(hipEventCreateWithFlags(&a->kf_ev_new, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(a->kf_ev_new, s));
-    }
+    if (b != a && (st = order_behind(s, b))) return st;
+    const int32_t *d;
+    if ((st = kf_stage_upload(a, stage, d))) return st;
     AOS2_HIP_CHECK(hipMemsetAsync(d_nnew, 0, 4 * (size_t)n, s));
-    const int32_t *d = reinterpret_cast<const int32_t *>(a->kf_dev3.p);
     const int cap = a->D.cap;
     hipLaunchKernelGGL(frames_triangulate_kernel, dim3((cap + 255) / 256, n), dim3(256), 0, s, a->D, b->D, d, d + n, d_match12, d_x3D, d_status);
     hipLaunchKernelGGL(frames_triangulate_resolve_kernel, dim3((cap + 255) / 256, n_groups), dim3(256), 0, s, cap, d + 2 * n,
                        d + 2 * n + n_groups + 1, d_status, d_nnew);
-    AOS2_HIP_CHECK(hipGetLastError());
-    if (!a->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(s));   // (asynchronous: aos2_frames_wait(a) completes the call)
-    return AOS2_OK;
+    return kf_call_end(a);
 }
 
 int aos2_triangulate_matches(aos2_matcher_t *m, const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "aos2_common.h"
+#include "regions.h"
 #include "wave_ops.h"
 
 namespace aos2 {
@@ -2147,15 +2148,6 @@ static int pool_reserve(aos2_matcher *m, size_t entries, const char *what, Entry
     if (int st = m->pool.alloc(entries + 1)) return st;
     pool = reinterpret_cast<Entry *>(m->pool.p);
     return AOS2_OK;
-}
-
-// bump allocation in a buffer of 256-byte aligned pieces: the offset of the next `bytes`, `size` grows past them
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t carve(size_t &size, size_t bytes)
-{
-    const size_t off = up256(size);
-    size = off + bytes;
-    return off;
 }
 
 // One call's memory: three regions of the handle's device arena.

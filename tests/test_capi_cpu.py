@@ -395,6 +395,33 @@ def test_lba_window_builder_on_a_hand_made_graph(tmp_path):
     assert "lba_window_test ok: 5 keyframes (3 optimised), 3 points, 8 edges" in out
 
 
+def test_region_list_offsets_and_binding(tmp_path):
+    """aos2::Regions (csrc/regions.h), the typed region list of the frame batch's buffers, as a stand-alone program under the address
+    and undefined-behaviour sanitizers: 256-byte offsets, disjoint regions in order of registration (one of them empty), bytes(),
+    what bind() writes into the fields, the same layout from the same calls (tests/cpp/regions_test.cpp)."""
+    import subprocess
+    exe = str(tmp_path / "regions_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "regions_test.cpp"), "-I", os.path.join(ROOT, "active-orb-slam2_amd", "csrc"),
+                           "-o", exe])
+    out = subprocess.check_output([exe], text=True)
+    assert "regions_test ok: 7 regions, 1536 bytes" in out
+
+
+def test_frame_members_of_a_batch_that_was_never_built(pkg):
+    """aos2_frames_get / aos2_frames_device_ptr on a batch without a build: whatever the id -- the gettable 0-8, the device-pointer-only
+    9 and 10, ids the header does not define -- the one answers with an argument error and the other with NULL, and no device is looked
+    for.  (Both return before they consult the member table: that is test_every_member_by_copy_and_by_device_pointer's, on a GPU.)"""
+    capi = pkg.capi
+    f = capi.Frames(2, 64)
+    for what in [-1] + list(range(12)) + [9999]:
+        with pytest.raises(capi.AosError) as e:
+            f.get(what)
+        assert e.value.code == capi.AOS2_ERR_ARG, what
+        assert f.device_ptr(what) == 0, what
+        assert f.L.aos2_frames_device_ptr(f.h, what) is None, what
+
+
 def test_reduced_solve_tap_and_lba_size_limit_refuse_on_the_host(pkg):
     """aos2_debug_lba_reduced_solve_device checks its arguments before it looks for a device: a NULL, no cases, np < 1, the register
     form beyond 40 free keyframes, the device-memory form beyond the 154 whose LDS a compute unit holds, an unknown form.  The same

@@ -119,6 +119,46 @@ def test_chain_stage_by_stage_vs_oracle(pkg, oracle, ochain, gpu, seed, batch, c
     assert (tc.d_nm.cpu().numpy() == nm).all()
 
 
+def test_every_member_by_copy_and_by_device_pointer(pkg, gpu):
+    """After a chain step: aos2_frames_get of every gettable member (ids 0-8) gives the bytes that lie behind aos2_frames_device_ptr, in
+    the element type and shape include/aos2.h documents; ids 9 and 10 are device pointer only: get refuses them, and their arrays hold
+    the extractor's keypoint angles and octaves."""
+    capi, F = pkg.capi, pkg.capi.Frames
+    scen = pkg.scenario.tracking_scenario(2, 3, n_unique=3)
+    tc = pkg.chain.TrackingChain(scen, n_local=800)
+    tc.step()
+    tc.wait()
+    B, cap, c, H = tc.B, tc.cap, tc.cur, capi.hip_runtime()
+
+    def behind(what, per_frame, dtype):
+        a = np.zeros((B, per_frame), dtype)
+        p = c.device_ptr(what)
+        assert p != 0, what
+        assert H.hipMemcpy(a.ctypes.data, p, a.nbytes, capi.HIP_D2H) == 0
+        return a
+
+    documented = {F.MAP_POINTS: (cap, np.int32), F.OUTLIER: (cap, np.uint8), F.TCW: (16, np.float32), F.U_RIGHT: (cap, np.float32),
+                  F.DEPTH: (cap, np.float32), F.GRID_OFF: (64 * 48 + 1, np.int32), F.GRID_IDX: (cap, np.int32),
+                  F.KEYS_UN_X: (cap, np.float32), F.KEYS_UN_Y: (cap, np.float32)}
+    assert sorted(documented) == list(range(9))
+    for what, (per_frame, dtype) in documented.items():
+        got = c.get(what)
+        assert got.dtype == dtype and got.shape == (B, per_frame), what
+        assert got.tobytes() == behind(what, per_frame, dtype).tobytes(), what
+    assert (c.get(F.MAP_POINTS) >= 0).sum() > 100 * B and (c.get(F.GRID_OFF)[:, -1] > 500).all()   # (the members hold a tracked frame)
+    for what in (F.KEYS_ANGLE, F.KEYS_OCTAVE):
+        with pytest.raises(capi.AosError) as e:
+            c.get(what)
+        assert e.value.code == capi.AOS2_ERR_ARG
+    n = tc.d_n.cpu().numpy()
+    kps = tc.d_kps.cpu().numpy().view(np.uint8).reshape(B, cap, 28).copy().view(capi.KP_DTYPE).reshape(B, cap)
+    angle, octave = behind(F.KEYS_ANGLE, cap, np.float32), behind(F.KEYS_OCTAVE, cap, np.int32)
+    for b in range(B):
+        assert n[b] > 500
+        assert angle[b, :n[b]].tobytes() == kps["angle"][b, :n[b]].tobytes() and (octave[b, :n[b]] == kps["octave"][b, :n[b]]).all()
+    assert len(np.unique(octave[0, :n[0]])) > 3 and len(np.unique(angle[0, :n[0]])) > 100
+
+
 def test_chain_tiled_batch_and_window_budget(pkg, gpu, monkeypatch):
     """a tiled batch (frames repeat) gives repeated results; an entry pool that is too small is reported, not ignored"""
     scen = pkg.scenario.tracking_scenario(3, 16, n_unique=4)

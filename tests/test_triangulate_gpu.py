@@ -176,6 +176,34 @@ def test_repeatable_and_the_asynchronous_form_equals_the_synchronous(world):
         a.fr.set_async_keyframe_calls(False)
 
 
+def test_asynchronous_staging_grows_behind_a_call_in_flight(pkg, world):
+    """Asynchronous keyframe calls on a handle whose staging holds nothing yet: 2 pairs, then all 6 without a wait in between -- the
+    second call has to grow the page-locked and the device staging buffer while the upload and the kernels of the first may still be
+    in flight -- then one wait.  Both calls give the synchronous call's bytes."""
+    c, a = world
+    want6 = a.triangulate(a, c["kf1"], c["kf2"], c["match12"], True)
+    want2 = a.triangulate(a, c["kf1"][:2], c["kf2"][:2], c["match12"][:2], True)
+    b = Batch(pkg, c["scene"], (0, 1, 2, 3), R.CAM_A, cap=100)   # (the world's own handle has staged 6 pairs before)
+    torch = b.t
+
+    def buffers(P):
+        m = np.full((P, b.cap), -1, np.int32)
+        m[:, : c["match12"].shape[1]] = c["match12"][:P]
+        return (torch.from_numpy(m).to("cuda:0"), torch.full((P, b.cap, 3), 7.0, dtype=torch.float32, device="cuda:0"),
+                torch.full((P, b.cap), 99, dtype=torch.uint8, device="cuda:0"), torch.full((P,), -5, dtype=torch.int32, device="cuda:0"))
+
+    o2, o6 = buffers(2), buffers(6)
+    torch.cuda.synchronize()
+    b.fr.set_async_keyframe_calls(True)
+    for P, (d_m, x, st, nn) in ((2, o2), (6, o6)):
+        b.fr.TriangulateMatches(b.fr, c["kf1"][:P], c["kf2"][:P], d_m.data_ptr(), x.data_ptr(), st.data_ptr(), nn.data_ptr(), first_wins=True)
+    b.fr.wait()
+    for want, (d_m, x, st, nn) in ((want2, o2), (want6, o6)):
+        got = (st.cpu().numpy(), x.cpu().numpy(), nn.cpu().numpy())
+        assert all(g.tobytes() == w.tobytes() for g, w in zip(got, want[:3]))
+    assert (want6[0] == R.ACCEPTED).sum() > (want2[0] == R.ACCEPTED).sum() > 0
+
+
 def test_bad_pairs_are_rejected_before_anything_runs(pkg, world):
     c, a = world
     torch = a.t
