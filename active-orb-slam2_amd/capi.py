@@ -111,6 +111,10 @@ def lib():
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
         L.aos2_debug_sim3_host.argtypes = [vp, vp, ci]
         L.aos2_sim3_ransac.argtypes = [vp, vp, vp, ci]
+        L.aos2_debug_sim3_opt_host.argtypes = [vp, vp, ci]
+        L.aos2_optimize_sim3.argtypes = [vp, vp, vp, ci]
+        L.aos2_optimize_sim3_last_device_ms.argtypes = [vp]
+        L.aos2_optimize_sim3_last_device_ms.restype = cf
         if hasattr(L, "aos2_matcher_create"):
             L.aos2_matcher_create.argtypes = [cf, ci, ci, C.POINTER(vp)]
             L.aos2_matcher_destroy.argtypes = [vp]
@@ -918,6 +922,60 @@ def debug_sim3_host(problems):
     return _sim3_results(R, outs)
 
 
+# ---- Optimizer::OptimizeSim3 (include/aos2.h: aos2_optimize_sim3, aos2_debug_sim3_opt_host)
+class _Sim3OptProblem(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")] + \
+               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")] + \
+               [("q12", C.c_double * 4), ("t12", C.c_double * 3), ("s12", C.c_double), ("th2", C.c_float), ("fix_scale", C.c_int32)]
+
+
+class _Sim3OptResult(C.Structure):
+    _fields_ = [("q12", C.c_double * 4), ("t12", C.c_double * 3), ("s12", C.c_double), ("outlier", C.c_void_p),
+                ("n_bad", C.c_int32), ("n_inliers", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2)]
+
+
+def _sim3_opt_args(problems, sentinel=None):
+    """problems: dicts with X1c / X2c [n][3], obs1 / obs2 [n][2], inv_sigma2_1 / inv_sigma2_2 [n], K1 / K2 = (fx, fy, cx, cy),
+    q12 (x, y, z, w), t12, s12 (float64), th2, fix_scale"""
+    P, R, keep, outs = (_Sim3OptProblem * max(1, len(problems)))(), (_Sim3OptResult * max(1, len(problems)))(), [], []
+    names = ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")
+    for i, q in enumerate(problems):
+        arr = [np.ascontiguousarray(q[k], np.float32) for k in names]
+        n = len(arr[0])
+        if [a.shape for a in arr] != [(n, 3), (n, 3), (n, 2), (n, 2), (n,), (n,)]:
+            raise ValueError("problem %d: X [n][3], obs [n][2], inv_sigma2 [n]" % i)
+        out = np.full(n, 0 if sentinel is None else sentinel, np.uint8)
+        keep += arr
+        outs.append(out)
+        P[i].n = n
+        for k, a in zip(names, arr):
+            setattr(P[i], k, a.ctypes.data)
+        for tag, K in (("1", q["K1"]), ("2", q["K2"])):
+            for name, v in zip(("fx", "fy", "cx", "cy"), K):
+                setattr(P[i], name + tag, float(np.float32(v)))
+        P[i].q12 = (C.c_double * 4)(*[float(v) for v in q["q12"]])
+        P[i].t12 = (C.c_double * 3)(*[float(v) for v in q["t12"]])
+        P[i].s12, P[i].th2, P[i].fix_scale = float(q["s12"]), float(np.float32(q["th2"])), int(bool(q["fix_scale"]))
+        R[i].outlier = out.ctypes.data
+        if sentinel is not None:
+            C.memset(C.byref(R[i]), sentinel, _Sim3OptResult.outlier.offset)
+            R[i].n_bad = R[i].n_inliers = sentinel
+    return P, R, keep, outs
+
+
+def _sim3_opt_results(R, outs):
+    return [dict(q12=np.array(R[i].q12, np.float64), t12=np.array(R[i].t12, np.float64), s12=np.float64(R[i].s12), outlier=out,
+                 n_bad=R[i].n_bad, n_inliers=R[i].n_inliers, iterations=tuple(R[i].iterations), trials=tuple(R[i].trials))
+            for i, out in enumerate(outs)]
+
+
+def debug_sim3_opt_host(problems):
+    """aos2_debug_sim3_opt_host: the routine of the device kernel on the CPU -> one dict per problem (the fields of aos2_sim3_opt_result_t)"""
+    P, R, keep, outs = _sim3_opt_args(problems)
+    _check(lib().aos2_debug_sim3_opt_host(P, R, len(problems)))
+    return _sim3_opt_results(R, outs)
+
+
 def debug_sincos_device(angles, device=0):
     a = np.ascontiguousarray(angles, np.float32)
     s = np.zeros_like(a)
@@ -1521,6 +1579,18 @@ class LocalBA:
 
     def pose_last_device_ms(self):
         return float(self.L.aos2_pose_optimization_last_device_ms(self.h))
+
+    def OptimizeSim3(self, problems, sentinel=None):
+        """aos2_optimize_sim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1047-1242) for a batch of loop candidates; problems as
+        debug_sim3_opt_host -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in self.sim3_opt_last for a caller
+        that expects a refusal)"""
+        P, R, keep, outs = _sim3_opt_args(problems, sentinel)
+        self.sim3_opt_last = (R, outs)
+        _check(self.L.aos2_optimize_sim3(self.h, P, R, len(problems)))
+        return _sim3_opt_results(R, outs)
+
+    def sim3_opt_last_device_ms(self):
+        return float(self.L.aos2_optimize_sim3_last_device_ms(self.h))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 // ORB_SLAM2::Optimizer with the REFERENCE's signatures for the two hot methods (include/Optimizer.h:45-47):
 //   void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap);
 //   int  static PoseOptimization(Frame *pFrame);
+//   int  static OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
+//                            const bool bFixScale);   (:55; declared here, body in OptimizeSim3.h, which needs g2o::Sim3 complete)
 // The bodies are what a maintainer puts into src/Optimizer.cc: aos2::LbaWindow (LbaWindow.h) turns the covisibility neighbourhood
 // into the POD problem of include/aos2.h (what :457-654 build as std::lists and a g2o graph), ONE C-ABI call replaces :656-744,
 // and the write-back of :746-778 consumes its result.  LocalMapping.cc:81 and Tracking.cc:870,
@@ -32,12 +34,18 @@ inline LbaRecord &lba_record()
 }
 }  // namespace aos2
 
+namespace g2o {
+struct Sim3;
+}
+
 namespace ORB_SLAM2 {
 
 class Optimizer {
 public:
     void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap);
     int static PoseOptimization(Frame *pFrame);
+    static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
+                            const bool bFixScale);
 };
 
 // src/Optimizer.cc:454-779.  The window comes from aos2::LbaWindow (LbaWindow.h: one walk, hash membership, rows = the C ABI's arrays),

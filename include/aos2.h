@@ -734,6 +734,35 @@ int aos2_pose_optimization(aos2_lba_t *s, const aos2_pose_problem_t *problems, a
 /* device time (ms, HIP events) of the kernel of the last aos2_pose_optimization call */
 float aos2_pose_optimization_last_device_ms(const aos2_lba_t *s);
 
+/* int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
+ * const bool bFixScale)  src/Optimizer.cc:1047-1242, for a batch of loop candidates of LoopClosing::ComputeSim3 (:355, between
+ * SearchBySim3 and SearchByProjection): both optimisations and the outlier pass of every problem in ONE launch, one workgroup per
+ * problem.  The arithmetic is csrc/sim3_opt.h (g2o's central-difference Jacobians kept). */
+typedef struct {
+    int32_t n;                          /* correspondences that passed :1100-1137, in order of i */
+    const float *X1c, *X2c;             /* host [n][3]: P3D1c, P3D2c as the caller forms them (:1119, :1127) */
+    const float *obs1, *obs2;           /* host [n][2]: kpUn1.pt, kpUn2.pt */
+    const float *inv_sigma2_1, *inv_sigma2_2;   /* host [n] */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    double q12[4], t12[3], s12;         /* g2oS12 in: quaternion (x, y, z, w), translation, scale */
+    float th2; int32_t fix_scale;
+} aos2_sim3_opt_problem_t;
+typedef struct {
+    double q12[4], t12[3], s12;         /* g2oS12 out; the input, bit for bit, when the call returns through :1212 */
+    uint8_t *outlier;                   /* host [n], caller-allocated: 1 = vpMatches1[idx] set to NULL (:1197 or :1231) */
+    int32_t n_bad, n_inliers;           /* nBad of the first pass; the return value */
+    int32_t iterations[2], trials[2];   /* diagnostics only: LM iterations / trials of the two optimize() calls.  At convergence the
+                                         * sign of rho is rounding noise, so these are NOT reproducible across implementations */
+} aos2_sim3_opt_result_t;
+/* n_problems <= 64; n_problems == 0 is AOS2_OK.  n == 0: nothing runs, n_inliers = n_bad = 0, S12 out = S12 in.  1 <= n < 10: the
+ * first optimisation and its outlier pass run as in the reference and the call returns through :1212 (n_inliers = 0, S12 out = S12
+ * in, the flags of the first pass set).  A NULL array with n > 0, n < 0 or th2 <= 0 is AOS2_ERR_ARG, reported before anything runs
+ * (no result is written).  Synchronous on the handle's stream.  Results are a function of the problem alone: bit-identical from
+ * call to call and whatever else is in the batch. */
+int aos2_optimize_sim3(aos2_lba_t *s, const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
+/* device time (ms, HIP events) of the kernel of the last aos2_optimize_sim3 call */
+float aos2_optimize_sim3_last_device_ms(const aos2_lba_t *s);
+
 /* ------------------------------------------------------------------------------------------
  * Device-resident frame batches: the per-frame chain of Tracking::Track (src/Tracking.cc:862-870, 963-1027, 1302-1352)
  *   ORBextractor::operator() -> Frame::Frame -> SearchByProjection(Current, Last) -> PoseOptimization
@@ -1002,6 +1031,8 @@ int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_t
 /* aos2_sim3_ransac on the HOST with the routine the device kernels also run (csrc/sim3.h); needs no device.  It stops computing at
  * first_success, where the device reports as if it had. */
 int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems);
+/* aos2_optimize_sim3 on the HOST: the same header (csrc/sim3_opt.h) run serially, edges summed in index order; needs no device */
+int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
  * T_out[i] = exp(upd[i]) * T[i]  (upd: 6 doubles omega | upsilon, T: 7 doubles qx qy qz qw tx ty tz), and
  * x[i] = (H[i] + lambda[i] I)^-1 b[i] with Hb[i] = 21 doubles (upper triangle of H, row by row) + 6 doubles b;
