@@ -159,6 +159,7 @@ def lib():
             L.aos2_lba_set_window_groups.argtypes = [vp, ci]
             L.aos2_lba_last_program.argtypes = [vp, vp, vp]
             L.aos2_lba_debug_host_phase.argtypes = [vp, ci, ci, vp, vp]
+            L.aos2_debug_lba_assemble_device.argtypes = [vp, vp, ci, ci, ci, vp, vp]
             if hasattr(L, "aos2_pose_optimization"):
                 L.aos2_pose_optimization.argtypes = [vp, vp, vp, ci]
                 L.aos2_pose_optimization_last_device_ms.argtypes = [vp]
@@ -1424,6 +1425,14 @@ class _LbaResult(C.Structure):
                 ("polls", C.c_int32), ("stop_poll", C.c_int32)]
 
 
+class _LbaSystem(C.Structure):
+    _fields_ = [("np", C.c_int32), ("nl", C.c_int32), ("npad", C.c_int32), ("phase", C.c_int32), ("trials_first", C.c_int32),
+                ("iters_done_first", C.c_int32), ("n_units", C.c_int32), ("lam", C.c_double), ("current_chi", C.c_double),
+                ("hpose", C.c_void_p), ("hpoint", C.c_void_p), ("blk_off", C.c_void_p), ("units", C.c_void_p), ("pose", C.c_void_p),
+                ("point", C.c_void_p), ("e_level1", C.c_void_p), ("e_robust", C.c_void_p), ("Hpp_init", C.c_void_p), ("b_init", C.c_void_p),
+                ("b_p", C.c_void_p), ("Hll", C.c_void_p), ("b_l", C.c_void_p), ("Hs", C.c_void_p), ("bs", C.c_void_p)]
+
+
 class _PoseProblem(C.Structure):
     _fields_ = [("n", C.c_int32), ("Xw", C.c_void_p), ("obs", C.c_void_p), ("stereo", C.c_void_p),
                 ("inv_sigma2", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
@@ -1528,6 +1537,41 @@ class LocalBA:
     def solve_prepared(self, prep):
         _check(self.L.aos2_lba_solve_batch(self.h, C.byref(prep["S"]), C.byref(prep["R"]), prep["n"]))
         return prep["R"]
+
+    LAYOUTS = {"slots": 0, "walk": 1}
+
+    def debug_assemble(self, probs, layout="slots", stage=0, lam=None, iters=(5, 10)):
+        """test tap aos2_debug_lba_assemble_device: the reduced system of a trial as k_lin / k_lm_init / k_schur assemble it, for a batch
+        of windows -> one dict per window (include/aos2.h: aos2_lba_system_t; Hs is npad x npad, Hpp_init np x 6 x 6, Hll nl x 3 x 3)"""
+        n = len(probs)
+        keep = []
+        S, R, O = (_LbaProblem * n)(), (_LbaResult * n)(), (_LbaSystem * n)()
+        bufs = []
+        for i in range(n):
+            self._fill(S[i], R[i], probs[i], None, iters, keep)
+            q, m, E = S[i].n_poses, S[i].n_points, S[i].n_edges
+            npad = (6 * q + 15) // 16 * 16
+            b = dict(hpose=np.zeros(q, np.int32), hpoint=np.zeros(m, np.int32), blk_off=np.zeros(q * (q + 1) // 2 + 1, np.int32),
+                     units=np.zeros(q + q * (q - 1) // 2 + 1, np.int32), pose=np.zeros((q, 7)), point=np.zeros((m, 3)),
+                     e_level1=np.zeros(E, np.uint8), e_robust=np.zeros(E, np.uint8), Hpp_init=np.zeros(36 * q), b_init=np.zeros(6 * q),
+                     b_p=np.zeros(6 * q), Hll=np.zeros(9 * m), b_l=np.zeros(3 * m), Hs=np.zeros(npad * npad), bs=np.zeros(6 * q))
+            for k, a in b.items():
+                setattr(O[i], k, a.ctypes.data)
+            bufs.append(b)
+        lam_a = None if lam is None else np.ascontiguousarray(lam, np.float64)
+        assert lam_a is None or lam_a.shape == (n,)
+        _check(self.L.aos2_debug_lba_assemble_device(self.h, C.byref(S), n, self.LAYOUTS.get(layout, layout), int(stage),
+                                                     None if lam_a is None else _p(lam_a), C.byref(O)))
+        out = []
+        for o, b in zip(O, bufs):
+            q, m, npad = o.np, o.nl, o.npad
+            out.append(dict(np=q, nl=m, npad=npad, phase=o.phase, trials_first=o.trials_first, iters_done_first=o.iters_done_first,
+                            lam=o.lam, current_chi=o.current_chi, hpose=b["hpose"][:q], hpoint=b["hpoint"][:m],
+                            blk_off=b["blk_off"][:q * (q + 1) // 2 + 1], units=b["units"][:o.n_units], pose=b["pose"], point=b["point"],
+                            e_level1=b["e_level1"], e_robust=b["e_robust"], Hpp_init=b["Hpp_init"][:36 * q].reshape(q, 6, 6),
+                            b_init=b["b_init"][:6 * q], b_p=b["b_p"][:6 * q], Hll=b["Hll"][:9 * m].reshape(m, 3, 3), b_l=b["b_l"][:3 * m],
+                            Hs=b["Hs"][:npad * npad].reshape(npad, npad), bs=b["bs"][:6 * q]))
+        return out
 
     def set_host_threads(self, n):
         _check(self.L.aos2_lba_set_host_threads(self.h, int(n)))

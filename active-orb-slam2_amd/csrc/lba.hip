@@ -2465,11 +2465,15 @@ static void enqueue_init(const LaunchCtx &C, const Prog &P)
     enqueue_lin(C, P, 1);
     hipLaunchKernelGGL(k_lm_init, dim3(P.nw), dim3(1024), 0, P.q, P.blk);
 }
+static void enqueue_schur(const Prog &P)
+{
+    if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
+}
 // one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of both kinds)
 static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
 {
     const GroupDims &D = P.D;
-    if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
+    enqueue_schur(P);
     if (first_group && C.stagger_pending) {   // the other group starts here: half a trial behind
         (void)hipEventRecord(C.s->ev_stag, C.s->stream);
         (void)hipStreamWaitEvent(C.s->stream_b, C.s->ev_stag, 0);
@@ -2619,11 +2623,16 @@ static int stage_and_upload(aos2_lba *s, WindowPool &pool, const aos2_lba_proble
     return AOS2_OK;
 }
 
+static void enqueue_prepare(const LaunchCtx &C, const Prog &P)
+{
+    hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, C.s->debug_stop_at_poll);
+}
+
 // The whole procedure of a group's windows: optimisation k gets slots[k] trials and runs if any window of the call asks for
 // iterations (iters[k] > 0)
 static void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const int (&iters)[2], const int (&slots)[2])
 {
-    hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, C.s->debug_stop_at_poll);
+    enqueue_prepare(C, P);
     for (int k = 0; k < 2; ++k) {
         if (k == 1) enqueue_transition(P);
         if (iters[k] > 0) {
@@ -2631,6 +2640,85 @@ static void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const
             for (int t = 0; t < slots[k]; ++t) enqueue_trial(C, P, first_group);
         }
     }
+}
+
+// The host phase of a call up to the upload (aos2_lba_solve_batch and the assembly tap share it): the index structures of the windows
+// `act` (a pool thread per window), the task lists of the G groups, the arena, staging + upload, the descriptors
+struct Uploaded {
+    std::vector<Pass> *passes = nullptr;   // the handle's (LbaCache)
+    TaskLists TL[2];
+    ArenaPlan A;
+    LbaWin *hw = nullptr;                  // the host's copy of the descriptors
+    GroupDims gd[2];
+    DevTasks dt[2];
+    int max_i1 = 0, max_i2 = 0;
+    bool any_flag = false;
+};
+static int build_and_upload(aos2_lba *s, const aos2_lba_problem_t *problems, const std::vector<int> &act, const int (&goff)[3], int G, const LmLayout &lay,
+                            bool want_chi2, Uploaded &U)
+{
+    const int nw = (int)act.size();
+    int st;
+    // ---- per-window structure (host; windows in parallel when there are several), the groups' task lists
+    auto rg = std::make_unique<RoctxRange>("LocalBA::buildStructure (index mapping, edge lists, Schur items)");
+    if (!s->lba_cache) s->lba_cache = new LbaCache();
+    std::vector<Pass> &passes = static_cast<LbaCache *>(s->lba_cache)->passes;
+    U.passes = &passes;
+    if ((int)passes.size() < nw) passes.resize(nw);
+    WindowPool &pool = static_cast<LbaCache *>(s->lba_cache)->pool;
+    if (nw > 1) pool.start(lba_host_threads(s, nw));
+    if ((st = build_structures(pool, problems, act.data(), nw, passes))) return st;
+    rg = std::make_unique<RoctxRange>("LocalBA::stage + upload");
+    TaskLists(&TL)[2] = U.TL;
+    size_t n_all_tasks = 0;
+    for (int g = 0; g < G; ++g) {
+        std::vector<int> ids(goff[g + 1] - goff[g]);
+        std::iota(ids.begin(), ids.end(), goff[g]);
+        build_tasks(passes, ids, false, lay, TL[g]);   // (the groups' kernels index the whole descriptor array)
+        n_all_tasks += TL[g].size();
+    }
+
+    // ---- arena: layout, allocation, staging + upload (parallel), descriptors
+    ArenaPlan &A = U.A;
+    plan_arena(problems, act, passes, lay, n_all_tasks, want_chi2, A);
+    if ((st = s->arena.alloc(A.bytes + 256))) return st;
+    if ((st = s->h_in.alloc(A.o_cont + A.cont_bytes + 256))) return st;
+    if ((st = s->h_stage.alloc(A.res_bytes + 256))) return st;
+    if ((st = s->h_abort.alloc((size_t)nw + 1))) return st;
+    uint8_t *base = s->arena.p, *hin = s->h_in.p;
+    int32_t *d_abort = nullptr;
+    AOS2_HIP_CHECK(hipHostGetDevicePointer((void **)&d_abort, s->h_abort.p, 0));
+    bool &any_flag = U.any_flag;
+    any_flag = false;
+    for (int i = 0; i < nw; ++i) {
+        s->h_abort.p[i] = 0;
+        any_flag |= problems[act[i]].stop_flag != nullptr;
+    }
+    if ((st = stage_and_upload(s, pool, problems, act, passes, A))) return st;
+    LbaWin *hw = U.hw = reinterpret_cast<LbaWin *>(hin + A.o_wins);
+    GroupDims(&gd)[2] = U.gd;
+    int &max_i1 = U.max_i1, &max_i2 = U.max_i2;
+    for (int i = 0; i < nw; ++i) {
+        const aos2_lba_problem_t &p = problems[act[i]];
+        describe_window(hw[i], base, p, passes[i], A.L[i], d_abort + i, want_chi2);
+        gd[i >= goff[1] ? 1 : 0].add(p, passes[i], A.L[i]);
+        max_i1 = std::max(max_i1, p.iters_first);
+        max_i2 = std::max(max_i2, p.iters_second);
+    }
+    hipStream_t q = s->stream;
+    // the task lists of the groups, one after the other: [schur | points | lin] per group
+    DevTasks(&dt)[2] = U.dt;
+    {
+        size_t o = A.o_tasks;
+        for (int g = 0; g < G; ++g) dt[g] = put_tasks(TL[g], hin, base, o);
+    }
+    AOS2_HIP_CHECK(hipMemcpyAsync(base + A.o_tasks, hin + A.o_tasks, A.staged_bytes - A.o_tasks, hipMemcpyHostToDevice, q));   // the task lists, the descriptors
+    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
+    if (G == 2) {   // the second group's stream starts behind the upload
+        AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
+        AOS2_HIP_CHECK(hipStreamWaitEvent(s->stream_b, s->ev_up, 0));
+    }
+    return AOS2_OK;
 }
 
 // what the steps after the upload work on
@@ -2907,66 +2995,16 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     if (const char *e = getenv("AOS2_LBA_LAYOUT")) walk = !strcmp(e, "walk");
     const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
 
-    // ---- per-window structure (host; windows in parallel when there are several), the groups' task lists
-    auto rg = std::make_unique<RoctxRange>("LocalBA::buildStructure (index mapping, edge lists, Schur items)");
-    if (!s->lba_cache) s->lba_cache = new LbaCache();
-    std::vector<Pass> &passes = static_cast<LbaCache *>(s->lba_cache)->passes;
-    if ((int)passes.size() < nw) passes.resize(nw);
-    WindowPool &pool = static_cast<LbaCache *>(s->lba_cache)->pool;
-    if (nw > 1) pool.start(lba_host_threads(s, nw));
-    if ((st = build_structures(pool, problems, act.data(), nw, passes))) return st;
-    rg = std::make_unique<RoctxRange>("LocalBA::stage + upload");
-    TaskLists TL[2];
-    size_t n_all_tasks = 0;
-    for (int g = 0; g < G; ++g) {
-        std::vector<int> ids(goff[g + 1] - goff[g]);
-        std::iota(ids.begin(), ids.end(), goff[g]);
-        build_tasks(passes, ids, false, lay, TL[g]);   // (the groups' kernels index the whole descriptor array)
-        n_all_tasks += TL[g].size();
-    }
-
-    // ---- arena: layout, allocation, staging + upload (parallel), descriptors
-    ArenaPlan A;
-    plan_arena(problems, act, passes, lay, n_all_tasks, want_chi2, A);
-    if ((st = s->arena.alloc(A.bytes + 256))) return st;
-    if ((st = s->h_in.alloc(A.o_cont + A.cont_bytes + 256))) return st;
-    if ((st = s->h_stage.alloc(A.res_bytes + 256))) return st;
-    if ((st = s->h_abort.alloc((size_t)nw + 1))) return st;
-    uint8_t *base = s->arena.p, *hin = s->h_in.p;
-    int32_t *d_abort = nullptr;
-    AOS2_HIP_CHECK(hipHostGetDevicePointer((void **)&d_abort, s->h_abort.p, 0));
-    bool any_flag = false;
-    for (int i = 0; i < nw; ++i) {
-        s->h_abort.p[i] = 0;
-        any_flag |= problems[act[i]].stop_flag != nullptr;
-    }
-    if ((st = stage_and_upload(s, pool, problems, act, passes, A))) return st;
-    LbaWin *hw = reinterpret_cast<LbaWin *>(hin + A.o_wins);
-    GroupDims gd[2];
-    int max_i1 = 0, max_i2 = 0;
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t &p = problems[act[i]];
-        describe_window(hw[i], base, p, passes[i], A.L[i], d_abort + i, want_chi2);
-        gd[i >= goff[1] ? 1 : 0].add(p, passes[i], A.L[i]);
-        max_i1 = std::max(max_i1, p.iters_first);
-        max_i2 = std::max(max_i2, p.iters_second);
-    }
-    hipStream_t q = s->stream;
-    // the task lists of the groups, one after the other: [schur | points | lin] per group
-    DevTasks dt[2];
-    {
-        size_t o = A.o_tasks;
-        for (int g = 0; g < G; ++g) dt[g] = put_tasks(TL[g], hin, base, o);
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(base + A.o_tasks, hin + A.o_tasks, A.staged_bytes - A.o_tasks, hipMemcpyHostToDevice, q));   // the task lists, the descriptors
-    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
-    if (G == 2) {   // the second group's stream starts behind the upload
-        AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(s->stream_b, s->ev_up, 0));
-    }
+    // ---- per-window structure, task lists, arena, staging + upload, descriptors
+    Uploaded U;
+    if ((st = build_and_upload(s, problems, act, goff, G, lay, want_chi2, U))) return st;
+    const std::vector<Pass> &passes = *U.passes;
+    const ArenaPlan &A = U.A;
+    const int max_i1 = U.max_i1, max_i2 = U.max_i2;
+    uint8_t *base = s->arena.p;
 
     // ---- the program
-    rg = std::make_unique<RoctxRange>("LocalBA::optimize(5) + outlier pass + optimize(10) + inlier check (one device program)");
+    auto rg = std::make_unique<RoctxRange>("LocalBA::optimize(5) + outlier pass + optimize(10) + inlier check (one device program)");
     // As many trials as iterations per optimisation -- what every window needs whose steps are all accepted.  A window
     // with rejected steps is not finished when the program ends: it leaves with the others' results and gets a continuation round
     // sized for what it still needs, together with the (few) windows like it, compacted (continuation_round).  Rounds 2-4 enqueued one spare
@@ -2980,10 +3018,10 @@ int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2
     LaunchCtx C{s, walk, G == 2};
     Prog PG[2];
     for (int g = 0; g < G; ++g) {
-        PG[g] = make_prog(dw, dw + goff[g], goff[g + 1] - goff[g], TL[g], dt[g], gd[g], group_streams(s, g));
+        PG[g] = make_prog(dw, dw + goff[g], goff[g + 1] - goff[g], U.TL[g], U.dt[g], U.gd[g], group_streams(s, g));
         enqueue_program(C, PG[g], g == 0, iters, slots);
     }
-    const Batch Bt{problems, act, passes, A, lay, hw, any_flag};
+    const Batch Bt{problems, act, passes, A, lay, U.hw, U.any_flag};
     if ((st = finish(s, PG, G, Bt))) return st;
 
     // ---- continuation rounds, write-back
@@ -3100,6 +3138,113 @@ int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const in
         const double s3 = ((const double *)(host.data() + l.scal))[3];
         ok[c] = s3 == 1.0 ? 1 : s3 == 0.0 ? 0 : 255;
         ov += l.n; oT += 7 * (size_t)np[c];
+    }
+    return AOS2_OK;
+}
+
+// Test tap: the system a Levenberg-Marquardt trial solves, as the shipped kernels assemble it.  The host phase is aos2_lba_solve_batch's
+// (build_and_upload), the launches go through its helpers; one group, the landmark layout as the caller says.
+int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int stage, const double *lambda,
+                                   aos2_lba_system_t *out)
+{
+    if (!s || !problems || !out || n_problems < 1 || (layout != 0 && layout != 1) || (stage != 0 && stage != 1)) {
+        set_error("aos2_debug_lba_assemble_device: bad argument (layout 0 = slots, 1 = walk; stage 0 or 1)");
+        return AOS2_ERR_ARG;
+    }
+    for (int w = 0; w < n_problems; ++w) {
+        const aos2_lba_problem_t *p = problems + w;
+        const aos2_lba_system_t *o = out + w;
+        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id || !p->point_xyz || !p->point_id ||
+            !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo || !p->edge_inv_sigma2 || p->iters_first < 1 ||
+            (stage == 1 && p->iters_second < 1) || !o->hpose || !o->hpoint || !o->pose || !o->point || !o->e_level1 || !o->e_robust || !o->Hpp_init ||
+            !o->b_init || !o->b_p || !o->Hll || !o->b_l || !o->Hs || !o->bs || !o->blk_off || !o->units) {
+            set_error("aos2_debug_lba_assemble_device: bad problem or output %d", w);
+            return AOS2_ERR_ARG;
+        }
+    }
+    int st;
+    {   // what the host phase refuses, before a device is looked for
+        std::vector<Pass> probe(n_problems);
+        WindowPool serial;
+        if ((st = build_structures(serial, problems, nullptr, n_problems, probe))) return st;
+        for (int w = 0; w < n_problems; ++w)
+            if (probe[w].np < 1) {
+                set_error("aos2_debug_lba_assemble_device: problem %d has no free keyframe with an edge", w);
+                return AOS2_ERR_ARG;
+            }
+    }
+    if ((st = lba_handle_init(s))) return st;
+    const int nw = n_problems;
+    std::vector<int> act(nw);
+    std::iota(act.begin(), act.end(), 0);
+    const int goff[3] = {0, nw, nw};
+    const bool walk = layout == 1;
+    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
+    Uploaded U;
+    if ((st = build_and_upload(s, problems, act, goff, 1, lay, false, U))) return st;
+    const std::vector<Pass> &passes = *U.passes;
+    const ArenaPlan &A = U.A;
+    uint8_t *base = s->arena.p;
+    // Hpp and the pose part of b as the first linearisation left them, copied aside between k_lm_init and k_schur
+    std::vector<size_t> o_snap(nw);
+    Bump SB;
+    for (int i = 0; i < nw; ++i) o_snap[i] = SB.take(8 * 42 * (size_t)passes[i].np);
+    DevBuf<uint8_t> snap;
+    if ((st = snap.alloc(SB.size))) return st;
+    std::vector<uint8_t> host(A.bytes), hsnap(SB.size);
+    st = [&]() -> int {
+        const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
+        LaunchCtx C{s, walk, false};
+        const Prog P = make_prog(dw, dw, nw, U.TL[0], U.dt[0], U.gd[0], group_streams(s, 0));
+        enqueue_prepare(C, P);
+        if (stage == 1) {
+            enqueue_init(C, P);
+            for (int t = 0; t < U.max_i1; ++t) enqueue_trial(C, P, true);
+            enqueue_transition(P);
+        }
+        enqueue_init(C, P);
+        for (int i = 0; i < nw; ++i) {
+            const size_t n36 = 8 * 36 * (size_t)passes[i].np, n6 = 8 * 6 * (size_t)passes[i].np;
+            if (lambda && lambda[i] > 0) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].st + offsetof(LmState, lambda), lambda + i, 8, hipMemcpyHostToDevice, P.q));
+            AOS2_HIP_CHECK(hipMemcpyAsync(snap.p + o_snap[i], base + A.L[i].Hpp, n36, hipMemcpyDeviceToDevice, P.q));
+            AOS2_HIP_CHECK(hipMemcpyAsync(snap.p + o_snap[i] + n36, base + A.L[i].b, n6, hipMemcpyDeviceToDevice, P.q));
+        }
+        enqueue_schur(P);
+        AOS2_HIP_CHECK(hipGetLastError());
+        AOS2_HIP_CHECK(hipStreamSynchronize(P.q));
+        AOS2_HIP_CHECK(hipMemcpy(host.data(), base, A.bytes, hipMemcpyDeviceToHost));
+        AOS2_HIP_CHECK(hipMemcpy(hsnap.data(), snap.p, SB.size, hipMemcpyDeviceToHost));
+        return AOS2_OK;
+    }();
+    snap.release();
+    if (st) return st;
+    for (int i = 0; i < nw; ++i) {
+        const aos2_lba_problem_t &p = problems[i];
+        const Pass &S = passes[i];
+        const WinLayout &l = A.L[i];
+        aos2_lba_system_t &o = out[i];
+        const uint8_t *h = host.data();
+        const LmState *ls = (const LmState *)(h + l.st);
+        const size_t np = S.np, nl = S.nl, npad = l.npad;
+        o.np = S.np; o.nl = S.nl; o.npad = l.npad;
+        o.phase = ls->phase; o.trials_first = ls->trials[0]; o.iters_done_first = ls->iters_done[0];
+        o.lambda = ls->lambda; o.current_chi = ls->currentChi;
+        memcpy(o.hpose, S.hpose.data(), 4 * np);
+        memcpy(o.hpoint, S.hpoint.data(), 4 * nl);
+        memcpy(o.blk_off, S.blk_off.data(), 4 * (np * (np + 1) / 2 + 1));
+        o.n_units = (int32_t)S.units.size();
+        memcpy(o.units, S.units.data(), 4 * S.units.size());
+        memcpy(o.pose, h + l.est, 8 * 7 * (size_t)p.n_poses);
+        memcpy(o.point, h + l.est + 8 * 7 * (size_t)p.n_poses, 8 * 3 * (size_t)p.n_points);
+        memcpy(o.e_level1, h + l.level1, (size_t)p.n_edges);
+        memcpy(o.e_robust, h + l.robust, (size_t)p.n_edges);
+        memcpy(o.Hpp_init, hsnap.data() + o_snap[i], 8 * 36 * np);
+        memcpy(o.b_init, hsnap.data() + o_snap[i] + 8 * 36 * np, 8 * 6 * np);
+        memcpy(o.b_p, h + l.b, 8 * 6 * np);
+        memcpy(o.Hll, h + l.Hll, 8 * 9 * nl);
+        memcpy(o.b_l, h + l.b + 8 * 6 * np, 8 * 3 * nl);
+        memcpy(o.Hs, h + l.Hs, 8 * npad * npad);
+        memcpy(o.bs, h + l.bs, 8 * 6 * np);
     }
     return AOS2_OK;
 }

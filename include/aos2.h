@@ -1050,6 +1050,37 @@ int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const in
                                         const double *b_pose, const double *lambda, const double *T, double *x, double *T_out,
                                         double *T_backup, double *scale_terms, uint8_t *ok, int device);
 
+/* The reduced camera system of a LocalBA trial as the shipped kernels assemble it (csrc/lba.hip: k_lin, k_lm_init, k_schur), read before
+ * anything solves it.  The host phase is aos2_lba_solve_batch's, the kernels are enqueued through its helpers, all windows as one group.
+ * layout: 0 = slots (k_lin<false> + k_points), 1 = walk (k_lin<true> + k_points_walk) -- as given, whatever the batch size or AOS2_LBA_LAYOUT.
+ * stage 0: k_prepare, the start of the first optimisation (residual pass, k_lin with init = 1, k_lm_init), one k_schur.
+ * stage 1: the program of aos2_lba_solve_batch for iters_first trials of the first optimisation, k_transition, the start of the second
+ *          optimisation, one k_schur.  A window whose first optimisation rejected a step is not there yet: phase, trials_first and
+ *          iters_done_first say so (phase 2, trials_first == iters_done_first).
+ * lambda: NULL, or one value per window copied into the window's state behind k_lm_init (<= 0: computeLambdaInit's value stays).
+ * The stop flags of the problems are ignored.  The caller sizes the arrays of out[w] by the problem: np <= n_poses, nl <= n_points,
+ * npad = 6 np rounded up to 16; the tap fills their first np / nl / ... entries.
+ * AOS2_ERR_ARG (before a device is looked for): a NULL, n_problems < 1, another layout or stage, iters_first < 1 (iters_second < 1 at
+ * stage 1), a window the host phase of the solve refuses, a window without a free keyframe. */
+typedef struct {
+    int32_t np, nl, npad;             /* out: free keyframes / landmarks with an edge, padded size of Hs */
+    int32_t phase;                    /* out: LmState::phase (0 at stage 0, 2 at stage 1) */
+    int32_t trials_first, iters_done_first;
+    int32_t n_units;                  /* out: k_schur's work units of the window */
+    double lambda, current_chi;       /* out: LmState::lambda / currentChi when k_schur ran */
+    int32_t *hpose, *hpoint;          /* [np] / [nl]: hidx -> index into the problem's poses / points */
+    int32_t *blk_off;                 /* [np (np + 1) / 2 + 1]: first item of every (i1 <= i2) block, upper triangle row by row */
+    int32_t *units;                   /* [np + np (np - 1) / 2]: unit codes, kind << 28 | argument (0 DIAG: i; 1 BIG: block rank; 2 PACK: first row) */
+    double *pose, *point;             /* [7 n_poses] qx qy qz qw tx ty tz, [3 n_points]: the estimates the system is linearised at */
+    uint8_t *e_level1, *e_robust;     /* [n_edges] as the device holds them */
+    double *Hpp_init, *b_init;        /* [36 np], [6 np]: Hpp and b_p as the first linearisation (lin_poses_body) left them, before k_schur */
+    double *b_p;                      /* [6 np]: b_p as k_schur's DIAG units re-formed it (their Hpp is inside the diagonal blocks of Hs) */
+    double *Hll, *b_l;                /* [9 nl], [3 nl] */
+    double *Hs, *bs;                  /* [npad x npad] both triangles, tail included; [6 np] */
+} aos2_lba_system_t;
+int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int stage,
+                                   const double *lambda, aos2_lba_system_t *out);
+
 #ifdef __cplusplus
 }
 #endif

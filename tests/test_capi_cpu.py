@@ -465,3 +465,58 @@ def test_reduced_solve_tap_and_lba_size_limit_refuse_on_the_host(pkg):
     with pytest.raises(capi.AosError) as e:
         capi.lba_host_phase([ldlt_ref.lba_star_window(155)], 1)
     assert e.value.code == capi.AOS2_ERR_ARG and "155 free keyframes" in str(e.value)
+
+
+def test_assembly_tap_refuses_on_the_host(pkg):
+    """aos2_debug_lba_assemble_device checks its arguments before it looks for a device: a NULL, no problems, another layout or stage,
+    iterations < 1, a window the host phase of the solve refuses (an edge out of range, two edges between one keyframe and one landmark,
+    155 free keyframes) or one without a free keyframe."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ldlt_ref
+    import lba_system_ref as S
+    capi = pkg.capi
+    ba = capi.LocalBA()
+    win = S.make_window(1, 2, 2, S.sees_counts(3))
+
+    def refused(w, text=None, **kw):
+        with pytest.raises(capi.AosError) as e:
+            ba.debug_assemble([win, w], **kw)
+        assert e.value.code == capi.AOS2_ERR_ARG, (kw, str(e.value))
+        assert text is None or text in str(e.value), str(e.value)
+
+    for kw in (dict(layout=2), dict(layout=-1), dict(stage=2), dict(stage=-1), dict(iters=(0, 10)), dict(stage=1, iters=(5, 0))):
+        refused(win, **kw)
+    ep = win["edge_pose"].copy()
+    ep[3] = win["n_poses"]
+    refused(dict(win, edge_pose=ep), "out of range")
+    dup = dict(win, edge_pose=np.r_[win["edge_pose"], win["edge_pose"][:1]], edge_point=np.r_[win["edge_point"], win["edge_point"][:1]],
+               edge_obs=np.r_[win["edge_obs"], win["edge_obs"][:1]], edge_stereo=np.r_[win["edge_stereo"], win["edge_stereo"][:1]],
+               edge_inv_sigma2=np.r_[win["edge_inv_sigma2"], win["edge_inv_sigma2"][:1]], n_edges=win["n_edges"] + 1)
+    refused(dup, "same keyframe and map point")
+    refused(ldlt_ref.lba_star_window(155), "155 free keyframes")
+    refused(dict(win, pose_fixed=np.ones(win["n_poses"], np.uint8)), "no free keyframe")
+    f = capi.lib().aos2_debug_lba_assemble_device
+    S_, R_, O_ = (capi._LbaProblem * 1)(), (capi._LbaResult * 1)(), (capi._LbaSystem * 1)()
+    keep = []
+    ba._fill(S_[0], R_[0], win, None, (5, 10), keep)
+    bufs = {k: np.zeros(4096, np.float64) for k, _ in capi._LbaSystem._fields_[9:]}
+    for k, a in bufs.items():
+        setattr(O_[0], k, a.ctypes.data)
+    assert f(None, C.byref(S_), 1, 0, 0, None, C.byref(O_)) == capi.AOS2_ERR_ARG
+    assert f(ba.h, None, 1, 0, 0, None, C.byref(O_)) == capi.AOS2_ERR_ARG
+    assert f(ba.h, C.byref(S_), 1, 0, 0, None, None) == capi.AOS2_ERR_ARG
+    assert f(ba.h, C.byref(S_), 0, 0, 0, None, C.byref(O_)) == capi.AOS2_ERR_ARG
+    for k in bufs:   # every output array in turn
+        setattr(O_[0], k, None)
+        assert f(ba.h, C.byref(S_), 1, 0, 0, None, C.byref(O_)) == capi.AOS2_ERR_ARG, k
+        setattr(O_[0], k, bufs[k].ctypes.data)
+    for k in ("pose_Tcw", "edge_obs", "point_id"):   # ... and inputs of the problem
+        old = getattr(S_[0], k)
+        setattr(S_[0], k, None)
+        assert f(ba.h, C.byref(S_), 1, 0, 0, None, C.byref(O_)) == capi.AOS2_ERR_ARG, k
+        setattr(S_[0], k, old)
+    if pkg.device_count() == 0:   # good arguments get as far as the device
+        with pytest.raises(capi.AosError) as e:
+            ba.debug_assemble([win])
+        assert e.value.code == capi.AOS2_ERR_NO_DEVICE
