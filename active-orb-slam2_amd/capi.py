@@ -111,6 +111,11 @@ def lib():
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
         L.aos2_debug_sim3_host.argtypes = [vp, vp, ci]
         L.aos2_sim3_ransac.argtypes = [vp, vp, vp, ci]
+        L.aos2_debug_pnp_host.argtypes = [vp, vp, ci]
+        L.aos2_debug_pnp_set.argtypes = [ci, vp, ci, vp]
+        L.aos2_debug_pnp_scan.argtypes = [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp]
+        L.aos2_pnp_ransac.argtypes = [vp, vp, vp, ci]
+        L.aos2_pnp_ransac_parameters.argtypes = [ci, C.c_double, ci, ci, ci, cf, vp, vp, vp]
         L.aos2_debug_sim3_opt_host.argtypes = [vp, vp, ci]
         L.aos2_optimize_sim3.argtypes = [vp, vp, vp, ci]
         L.aos2_optimize_sim3_last_device_ms.argtypes = [vp]
@@ -923,6 +928,106 @@ def debug_sim3_host(problems):
     return _sim3_results(R, outs)
 
 
+# ---- the RANSAC of PnPsolver (include/aos2.h: aos2_pnp_ransac, aos2_debug_pnp_host, aos2_pnp_ransac_parameters)
+class _PnpProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("P3Dw", C.c_void_p), ("P2D", C.c_void_p), ("max_err", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")] + \
+               [("min_inliers", C.c_int32), ("min_set", C.c_int32), ("first_iteration", C.c_int32), ("n_iterations", C.c_int32),
+                ("draws", C.c_void_p), ("best_inliers_in", C.c_int32), ("best_in", C.c_void_p)]
+
+
+class _PnpResult(C.Structure):
+    _fields_ = [("returned_at", C.c_int32), ("Tcw", C.c_float * 16), ("n_inliers", C.c_int32), ("inliers", C.c_void_p),
+                ("best_iteration", C.c_int32), ("best_inliers", C.c_int32), ("best_Tcw", C.c_float * 16), ("best", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
+def pnp_ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4):
+    """aos2_pnp_ransac_parameters: SetRansacParameters (src/PnPsolver.cc:121-157; the defaults of include/PnPsolver.h:63) ->
+    (mRansacMinInliers, mRansacEpsilon, mRansacMaxIts) as adjusted for n correspondences"""
+    mi, eps, its = C.c_int32(), C.c_float(), C.c_int32()
+    _check(lib().aos2_pnp_ransac_parameters(int(n), float(probability), int(min_inliers), int(max_iterations), int(min_set), float(np.float32(epsilon)),
+                                            C.byref(mi), C.byref(eps), C.byref(its)))
+    return mi.value, np.float32(eps.value), its.value
+
+
+def pnp_draws(rng, n, n_iterations, min_set):
+    """the draws of n_iterations iterations of PnPsolver::iterate (:191-201) over n correspondences, in iteration order:
+    int32 [n_iterations][min_set], draw i of an iteration = RandomInt(0, n - 1 - i); zeros when n < min_set (nothing to draw from)"""
+    d = np.zeros((n_iterations, min_set), np.int32)
+    if n >= min_set:
+        for k in range(n_iterations):
+            for i in range(min_set):
+                d[k, i] = sim3_random_int(rng, 0, n - 1 - i)
+    return d
+
+
+def _pnp_args(problems, sentinel=None, with_counts=True):
+    """problems: dicts with P3Dw [n][3], P2D [n][2], max_err [n], K = (fx, fy, cx, cy), min_inliers (adjusted), min_set, n_iterations,
+    draws [n_iterations][min_set], and optionally the carried state first_iteration, best_inliers_in, best_in [n]"""
+    P, R, keep, outs = (_PnpProblem * max(1, len(problems)))(), (_PnpResult * max(1, len(problems)))(), [], []
+    for i, q in enumerate(problems):
+        arr = [np.ascontiguousarray(q[k], np.float32) for k in ("P3Dw", "P2D", "max_err")]
+        n, its, ms = len(arr[0]), int(q["n_iterations"]), int(q["min_set"])
+        draws = np.ascontiguousarray(q["draws"], np.int32)
+        if arr[0].shape != (n, 3) or arr[1].shape != (n, 2) or arr[2].shape != (n,) or draws.shape != (max(its, 0), ms):
+            raise ValueError("problem %d: P3Dw [n][3], P2D [n][2], max_err [n], draws [n_iterations][min_set]" % i)
+        fill = 0 if sentinel is None else sentinel
+        inl, best = np.full(n, fill, np.uint8), np.full(n, fill, np.uint8)
+        counts = np.full(max(its, 0), -1 if sentinel is None else sentinel, np.int32) if with_counts else None
+        keep += arr + [draws]
+        outs.append((inl, best, counts))
+        P[i].n = n
+        P[i].P3Dw, P[i].P2D, P[i].max_err, P[i].draws = (a.ctypes.data for a in arr + [draws])
+        for name, v in zip(("fx", "fy", "cx", "cy"), q["K"]):
+            setattr(P[i], name, float(np.float32(v)))
+        P[i].min_inliers, P[i].min_set, P[i].n_iterations = int(q["min_inliers"]), ms, its
+        P[i].first_iteration, P[i].best_inliers_in = int(q.get("first_iteration", 0)), int(q.get("best_inliers_in", 0))
+        if q.get("best_in") is not None:
+            bi = np.ascontiguousarray(q["best_in"], np.uint8)
+            if bi.shape != (n,):
+                raise ValueError("problem %d: best_in [n]" % i)
+            keep.append(bi)
+            P[i].best_in = bi.ctypes.data
+        R[i].inliers, R[i].best = inl.ctypes.data, best.ctypes.data
+        R[i].counts = counts.ctypes.data if with_counts else None
+        if sentinel is not None:
+            C.memset(C.byref(R[i]), sentinel, _PnpResult.inliers.offset)
+            C.memset(C.byref(R[i], _PnpResult.best_iteration.offset), sentinel, _PnpResult.best.offset - _PnpResult.best_iteration.offset)
+    return P, R, keep, outs
+
+
+def _pnp_results(R, outs):
+    return [dict(returned_at=R[i].returned_at, Tcw=np.array(R[i].Tcw, np.float32).reshape(4, 4), n_inliers=R[i].n_inliers, inliers=inl,
+                 best_iteration=R[i].best_iteration, best_inliers=R[i].best_inliers, best_Tcw=np.array(R[i].best_Tcw, np.float32).reshape(4, 4),
+                 best=best, counts=counts)
+            for i, (inl, best, counts) in enumerate(outs)]
+
+
+def debug_pnp_set(n, row):
+    """aos2_debug_pnp_set: the indices the draws of one iteration select, as csrc/pnp.h forms them"""
+    row = np.ascontiguousarray(row, np.int32)
+    out = np.zeros(len(row), np.int32)
+    _check(lib().aos2_debug_pnp_set(int(n), _p(row), len(row), _p(out)))
+    return [int(i) for i in out]
+
+
+def debug_pnp_scan(first_iteration, counts, refined, refined_carried, min_inliers, best_inliers_in=0):
+    """aos2_debug_pnp_scan: the loop of iterate() over tables -> (returned_at, best_iteration, best_inliers)"""
+    counts, refined = np.ascontiguousarray(counts, np.int32), np.ascontiguousarray(refined, np.int32)
+    r = [C.c_int32() for _ in range(3)]
+    _check(lib().aos2_debug_pnp_scan(int(first_iteration), len(counts), _p(counts), _p(refined), int(refined_carried), int(min_inliers),
+                                     int(best_inliers_in), *[C.byref(x) for x in r]))
+    return tuple(x.value for x in r)
+
+
+def debug_pnp_host(problems, with_counts=True):
+    """aos2_debug_pnp_host: the routine of the device kernels on the CPU -> one dict per problem (the fields of aos2_pnp_result_t)"""
+    P, R, keep, outs = _pnp_args(problems, None, with_counts)
+    _check(lib().aos2_debug_pnp_host(P, R, len(problems)))
+    return _pnp_results(R, outs)
+
+
 # ---- Optimizer::OptimizeSim3 (include/aos2.h: aos2_optimize_sim3, aos2_debug_sim3_opt_host)
 class _Sim3OptProblem(C.Structure):
     _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")] + \
@@ -1307,6 +1412,15 @@ class Matcher:
 
 
     # ---- projection family; f / p: synth_proj_gen_problem()-style dicts
+    def PnpRansac(self, problems, sentinel=None, with_counts=True):
+        """aos2_pnp_ransac: the RANSAC of PnPsolver (src/PnPsolver.cc) for a batch of relocalisation candidates; problems as
+        debug_pnp_host -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in self.pnp_last for a caller that
+        expects a refusal)"""
+        P, R, keep, outs = _pnp_args(problems, sentinel, with_counts)
+        self.pnp_last = (R, outs)
+        _check(self.L.aos2_pnp_ransac(self.h, P, R, len(problems)))
+        return _pnp_results(R, outs)
+
     def Fuse(self, kf, p, sim3=False):
         """search part of Fuse (src/ORBmatcher.cc:825-975, sim3: :977-1100) -> (nFused, best_idx, best_dist)"""
         keep = []

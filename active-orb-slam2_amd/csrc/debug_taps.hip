@@ -5,6 +5,7 @@
 
 #include "aos2_common.h"
 #include "octree.h"
+#include "pnp.h"
 #include "sincos_exact.h"
 #include "sim3.h"
 #include "triangulate.h"
@@ -127,9 +128,172 @@ void sim3_result_clear(const aos2_sim3_problem_t &P, int32_t its, aos2_sim3_resu
     if (P.n > 0) memset(inl, 0, (size_t)P.n);
     if (counts) std::fill(counts, counts + P.max_iterations, -1);
 }
+
+// a double on its way into an int the way the x86 conversion does it for the reference: INT_MIN where it does not fit
+static int32_t x86_int(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN; }
+
+int pnp_check(const aos2_pnp_problem_t *problems, const aos2_pnp_result_t *results, int n_problems, uint8_t *run)
+{
+    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
+        set_error("bad argument (0..64 problems and their results)");
+        return AOS2_ERR_ARG;
+    }
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_pnp_problem_t &P = problems[p];
+        if (P.n < 0 || P.min_set < 4 || P.min_set > 16 || P.first_iteration < 0 || P.first_iteration > P.n_iterations || P.best_inliers_in < 0 ||
+            (P.n > 0 && (!P.P3Dw || !P.P2D || !P.max_err || !results[p].inliers || !results[p].best)) ||
+            (P.best_inliers_in > 0 && (!P.best_in || P.n == 0))) {
+            set_error("problem %d: bad argument (n >= 0, 4 <= min_set <= 16, 0 <= first_iteration <= n_iterations, the per-correspondence "
+                      "arrays, best_in with best_inliers_in > 0)", p);
+            return AOS2_ERR_ARG;
+        }
+        run[p] = P.n >= P.min_inliers && P.first_iteration < P.n_iterations;
+        if (!run[p]) continue;
+        if (P.n < P.min_set || !P.draws) {
+            set_error("problem %d: %d correspondences to draw sets of %d from, or no draws", p, P.n, P.min_set);
+            return AOS2_ERR_ARG;
+        }
+        for (int k = P.first_iteration; k < P.n_iterations; ++k)
+            for (int i = 0; i < P.min_set; ++i) {
+                const int32_t r = P.draws[(size_t)P.min_set * k + i];
+                if (r < 0 || r > P.n - 1 - i) {
+                    set_error("problem %d: draw %d of iteration %d is %d, outside [0, %d]", p, i, k, r, P.n - 1 - i);
+                    return AOS2_ERR_ARG;
+                }
+            }
+    }
+    return AOS2_OK;
+}
+
+void pnp_result_clear(const aos2_pnp_problem_t &P, aos2_pnp_result_t &R)
+{
+    uint8_t *inl = R.inliers, *best = R.best;
+    int32_t *counts = R.counts;
+    R = aos2_pnp_result_t{};
+    R.inliers = inl;
+    R.best = best;
+    R.counts = counts;
+    R.returned_at = R.best_iteration = -1;
+    R.best_inliers = P.best_inliers_in;
+    if (P.n > 0) {
+        memset(inl, 0, (size_t)P.n);
+        if (P.best_inliers_in > 0) memmove(best, P.best_in, (size_t)P.n);
+        else memset(best, 0, (size_t)P.n);
+    }
+    if (counts) std::fill(counts, counts + P.n_iterations, -1);
+}
 }  // namespace aos2
 
 extern "C" {
+
+int aos2_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                               int32_t *ransac_min_inliers, float *ransac_epsilon, int32_t *ransac_max_its)
+{
+    using namespace aos2;
+    if (n < 0 || !ransac_min_inliers || !ransac_epsilon || !ransac_max_its) {
+        set_error("bad argument (n >= 0, the three outputs)");
+        return AOS2_ERR_ARG;
+    }
+    int nMinInliers = x86_int((double)((float)n * epsilon));   // int = N * mRansacEpsilon, a float product (:134)
+    if (nMinInliers < min_inliers) nMinInliers = min_inliers;
+    if (nMinInliers < min_set) nMinInliers = min_set;
+    if (epsilon < (float)nMinInliers / n) epsilon = (float)nMinInliers / n;
+    int nIterations;
+    if (nMinInliers == n) nIterations = 1;
+    else nIterations = x86_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
+    *ransac_min_inliers = nMinInliers;
+    *ransac_epsilon = epsilon;
+    *ransac_max_its = std::max(1, std::min(nIterations, max_iterations));
+    return AOS2_OK;
+}
+
+int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices)
+{
+    using namespace aos2;
+    if (!row || !indices || min_set < 0 || n < min_set) {
+        set_error("bad argument (the two arrays, 0 <= min_set <= n)");
+        return AOS2_ERR_ARG;
+    }
+    for (int i = 0; i < min_set; ++i)
+        if (row[i] < 0 || row[i] > n - 1 - i) {
+            set_error("draw %d is %d, outside [0, %d]", i, row[i], n - 1 - i);
+            return AOS2_ERR_ARG;
+        }
+    int k = 0;
+    PnpSetDraws{n, min_set, row}.each([&](int i) { indices[k++] = i; });
+    return AOS2_OK;
+}
+
+int aos2_debug_pnp_scan(int first_iteration, int n_iterations, const int32_t *counts, const int32_t *refined, int32_t refined_carried,
+                        int min_inliers, int best_inliers_in, int32_t *returned_at, int32_t *best_iteration, int32_t *best_inliers)
+{
+    using namespace aos2;
+    if (first_iteration < 0 || first_iteration > n_iterations || (n_iterations > 0 && (!counts || !refined)) || !returned_at || !best_iteration ||
+        !best_inliers) {
+        set_error("bad argument (0 <= first_iteration <= n_iterations, the two tables, the three outputs)");
+        return AOS2_ERR_ARG;
+    }
+    PnpScan scan(best_inliers_in);
+    for (int it = first_iteration; it < n_iterations; ++it)
+        if (scan.step(it, counts[it], min_inliers) &&
+            scan.refined(it, scan.best_iteration < 0 ? refined_carried : refined[scan.best_iteration], min_inliers))
+            break;
+    *returned_at = scan.returned_at;
+    *best_iteration = scan.best_iteration;
+    *best_inliers = scan.best_inliers;
+    return AOS2_OK;
+}
+
+int aos2_debug_pnp_host(const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems)
+{
+    using namespace aos2;
+    uint8_t run[64];
+    if (int st = pnp_check(problems, results, n_problems, run)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_pnp_problem_t &P = problems[p];
+        aos2_pnp_result_t &R = results[p];
+        pnp_result_clear(P, R);
+        if (!run[p]) continue;
+        const PnpCam K = {P.fx, P.fy, P.cx, P.cy};
+        const PnpPts pts = {P.P3Dw, P.P2D, P.max_err};
+        PnpLocal<12, 12> ws;
+        std::vector<uint8_t> flags((size_t)P.n), rflags((size_t)P.n);
+        PnpScan scan(P.best_inliers_in);
+        bool refined_is_current = false;   // Refine() of the set R.best holds: Rr, rcount, rflags
+        double Rr[12];
+        int32_t rcount = 0;
+        for (int it = P.first_iteration; it < P.n_iterations; ++it) {
+            double Rt[12];
+            pnp_compute_pose(PnpSetDraws{P.n, P.min_set, P.draws + (size_t)P.min_set * it}, pts, K, ws, Rt, Rt + 9);
+            int32_t count = 0;
+            for (int i = 0; i < P.n; ++i) count += flags[i] = pnp_inlier(Rt, K, pts, i);
+            if (R.counts) R.counts[it] = count;
+            const int32_t before = scan.best_iteration;
+            if (!scan.step(it, count, P.min_inliers)) continue;
+            if (scan.best_iteration != before) {   // :212-224
+                memcpy(R.best, flags.data(), flags.size());
+                pnp_Tcw(Rt, R.best_Tcw);
+                refined_is_current = false;
+            }
+            if (!refined_is_current) {   // Refine() (:260-305)
+                pnp_compute_pose(PnpSetFlags{P.n, R.best}, pts, K, ws, Rr, Rr + 9);
+                rcount = 0;
+                for (int i = 0; i < P.n; ++i) rcount += rflags[i] = pnp_inlier(Rr, K, pts, i);
+                refined_is_current = true;
+            }
+            if (scan.refined(it, rcount, P.min_inliers)) {
+                pnp_Tcw(Rr, R.Tcw);
+                R.n_inliers = rcount;
+                memcpy(R.inliers, rflags.data(), rflags.size());
+                break;
+            }
+        }
+        R.returned_at = scan.returned_at;
+        R.best_iteration = scan.best_iteration;
+        R.best_inliers = scan.best_inliers;
+    }
+    return AOS2_OK;
+}
 
 int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, float *x3D,
                                 uint8_t *status)

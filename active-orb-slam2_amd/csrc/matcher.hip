@@ -3412,3 +3412,4 @@ int aos2_matcher_search_for_initialization(aos2_matcher_t *m, const aos2_frame_v
 #include "frames_impl.inc"
 #include "frames_triangulate.inc"
 #include "sim3_ransac.inc"
+#include "pnp_ransac.inc"

@@ -568,6 +568,53 @@ typedef struct {
  * computed by the batch but reported as if they had not run.  Synchronous. */
 int aos2_sim3_ransac(aos2_matcher_t *m, const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems);
 
+/* The RANSAC of PnPsolver (src/PnPsolver.cc: SetRansacParameters :121-157, iterate :165-258, Refine :260-305, CheckInliers :308-339,
+ * compute_pose :477-525 = EPnP) for a batch of relocalisation candidates of Tracking::Relocalization (src/Tracking.cc:1521-1700),
+ * between SearchByBoW (:1557) and PoseOptimization (:1620).  The random minimal sets are an input, so every hypothesis of every
+ * problem is independent, and Refine() is a function of the best set alone: all hypotheses, then the Refine() of every iteration
+ * that sets a new best, are computed in one pass and the solver's sequential loop (:182-239) is replayed over the inlier counts and
+ * those memoised results.  The arithmetic is csrc/pnp.h.
+ *
+ * SetRansacParameters (:121-157) as a pure host function, no device: the adjusted mRansacMinInliers, mRansacEpsilon, mRansacMaxIts.
+ * A quotient (or N*epsilon) that is no int converts as x86 does (INT_MIN, so 1: item 9's rule).  n < 0 or a missing output is
+ * AOS2_ERR_ARG. */
+int aos2_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                               int32_t *ransac_min_inliers, float *ransac_epsilon, int32_t *ransac_max_its);
+typedef struct {
+    int32_t n;                       /* N: correspondences the constructor kept (:79-101) */
+    const float *P3Dw, *P2D, *max_err;   /* host [n][3], [n][2], [n]: mvP3Dw, mvP2D (mvKeysUn[i].pt), mvMaxError = mvSigma2 * th2, a
+                                          * float product (:156) */
+    float fx, fy, cx, cy;            /* F.fx ...; widened to the class's double fu fv uc vc (:104-107) */
+    int32_t min_inliers, min_set;    /* the ADJUSTED mRansacMinInliers (aos2_pnp_ransac_parameters); 4 <= min_set <= 16 */
+    int32_t first_iteration, n_iterations;   /* the call replays iterations [first_iteration, n_iterations) of the solver (0-based
+                                              * values of mnIterations before its increment, :185) */
+    const int32_t *draws;            /* host [n_iterations][min_set]: draw i of an iteration = RandomInt(0, n-1-i) (:193); rows below
+                                      * first_iteration are not read */
+    int32_t best_inliers_in;         /* the solver's state carried in: mnBestInliers (0 at the start) ... */
+    const uint8_t *best_in;          /* ... and mvbBestInliers [n] (NULL when best_inliers_in == 0) */
+} aos2_pnp_problem_t;
+typedef struct {
+    int32_t returned_at;             /* iteration at which iterate() returns a refined pose (:226-236), -1 = ran to n_iterations */
+    float Tcw[16];                   /* mRefinedTcw (:294-300) */
+    int32_t n_inliers;               /* mnRefinedInliers */
+    uint8_t *inliers;                /* host [n], caller-allocated: mvbRefinedInliers (zeros while returned_at < 0) */
+    int32_t best_iteration, best_inliers;   /* mnBestInliers where the call stops and the iteration that set it; best_iteration =
+                                             * -1: the carried-in best still stands */
+    float best_Tcw[16];              /* mBestTcw (:217-223); zeros while best_iteration < 0 (the caller keeps its own) */
+    uint8_t *best;                   /* host [n], caller-allocated: mvbBestInliers (best_in while best_iteration < 0) */
+    int32_t *counts;                 /* host [n_iterations] or NULL: mnInliersi of the iterations that ran, -1 elsewhere */
+} aos2_pnp_result_t;
+/* n_problems <= 64; n_problems == 0 is AOS2_OK.  Checked before anything runs, AOS2_ERR_ARG with no result byte written: a draw
+ * outside [0, n-1-i], n < 0, n < min_set with something to run, min_set outside [4, 16], a missing array, first_iteration < 0 or
+ * > n_iterations, best_inliers_in < 0, best_inliers_in > 0 without best_in.  n < min_inliers (:173-177) or first_iteration ==
+ * n_iterations: nothing is launched for that problem, returned_at = -1, counts -1.  A degenerate minimal set is no error: its model
+ * holds NaNs, every comparison of :329 is false and its count is 0.  Iterations behind returned_at are computed by the batch but
+ * reported as not run.  A result is a function of its problem alone: the same bytes whatever else is in the batch.  A call resumed
+ * with first_iteration = returned_at + 1 (or n_iterations), best_inliers_in = best_inliers and best_in = best gives what the
+ * uninterrupted loop gives; an iteration with count >= min_inliers that does not beat the carried best runs Refine() on the carried
+ * set.  Synchronous. */
+int aos2_pnp_ransac(aos2_matcher_t *m, const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems);
+
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*>
  *         &sAlreadyFound, const float th, const int ORBdist)  :1472-1599 (relocalisation).
  * Points = pKF->GetMapPointMatches() (valid = pMP && !isBad() && !sAlreadyFound.count(pMP));
@@ -1031,6 +1078,15 @@ int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_t
 /* aos2_sim3_ransac on the HOST with the routine the device kernels also run (csrc/sim3.h); needs no device.  It stops computing at
  * first_success, where the device reports as if it had. */
 int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t *results, int n_problems);
+/* aos2_pnp_ransac on the HOST with the routine the device kernels also run (csrc/pnp.h), serially; needs no device.  It stops
+ * computing at returned_at and calls Refine() where the loop does, memoised per best set. */
+int aos2_debug_pnp_host(const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems);
+/* the indices that the draws `row` [min_set] select from 0..n-1 (src/PnPsolver.cc:188-201) as csrc/pnp.h forms them -> indices */
+int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices);
+/* the loop of PnPsolver::iterate (:182-239) as csrc/pnp.h replays it over tables: counts [n_iterations] (read from first_iteration),
+ * refined [n_iterations] = the inlier count Refine() finds on the set of that iteration, refined_carried that of the carried-in set */
+int aos2_debug_pnp_scan(int first_iteration, int n_iterations, const int32_t *counts, const int32_t *refined, int32_t refined_carried,
+                        int min_inliers, int best_inliers_in, int32_t *returned_at, int32_t *best_iteration, int32_t *best_inliers);
 /* aos2_optimize_sim3 on the HOST: the same header (csrc/sim3_opt.h) run serially, edges summed in index order; needs no device */
 int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
