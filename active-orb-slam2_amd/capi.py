@@ -105,6 +105,7 @@ def lib():
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         L.aos2_debug_sincos_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_wave_ops_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
+        L.aos2_debug_row_sums_scatter_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
         L.aos2_debug_lba_reduced_solve_device.argtypes = [ci] + [vp] * 12 + [ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
@@ -1108,6 +1109,18 @@ def debug_wave_ops_device(vi, vd, device=0):
     for k in ("row_min", "min"):
         out[k] = out[k].view(np.uint32)
     return out
+
+
+def debug_row_sums_scatter_device(v, device=0):
+    """test tap: row_sums_scatter_f64<K> of csrc/wave_ops.h by one wave; v (float64) [64][K], K = 7, 36 or 42
+    -> (every lane's slots [64][ceil(K / 16)], owner [K][2] = (lane of a row, slot) of the total of value i)"""
+    v = np.ascontiguousarray(v, np.float64)
+    assert v.ndim == 2 and v.shape[0] == 64
+    K = v.shape[1]
+    out = np.zeros((64, (K + 15) // 16), np.float64)
+    owner = np.zeros((K, 2), np.int32)
+    _check(lib().aos2_debug_row_sums_scatter_device(_p(v), K, _p(out), _p(owner), device))
+    return out, owner
 
 
 def debug_pose_blocks_device(upd, T, Hb, lam, x0, device=0):

@@ -56,6 +56,39 @@ __global__ __launch_bounds__(NT) void wave_ops_kernel(const int32_t *vi, const d
     od[6] = readlane_f64(d, 63);
 }
 
+// row_sums_scatter_f64<K> by one wave: every lane's K values in, every lane's slots out
+template <int K>
+__global__ __launch_bounds__(64) void row_sums_scatter_kernel(const double *v, double *out)
+{
+    double a[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) a[i] = v[K * threadIdx.x + i];
+    row_sums_scatter_f64<K>(a);
+#pragma unroll
+    for (int s = 0; s < row_scatter_slots(K); ++s) out[row_scatter_slots(K) * threadIdx.x + s] = a[s];
+}
+
+template <int K>
+int row_sums_scatter_run(const double *v, double *out, int32_t *owner)
+{
+    constexpr int S = row_scatter_slots(K);
+    int st;
+    DevBuf<double> dv, dout;
+    if ((st = dv.alloc(64 * K)) || (st = dout.alloc(64 * S))) return st;
+    AOS2_HIP_CHECK(hipMemcpy(dv.p, v, sizeof(double) * 64 * K, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(row_sums_scatter_kernel<K>, dim3(1), dim3(64), 0, 0, dv.p, dout.p);
+    AOS2_HIP_CHECK(hipDeviceSynchronize());
+    AOS2_HIP_CHECK(hipMemcpy(out, dout.p, sizeof(double) * 64 * S, hipMemcpyDeviceToHost));
+    dv.release(); dout.release();
+    for (int i = 0; i < K; ++i) {
+        int li = 0, s = 0;
+        row_scatter_owner<K>(i, li, s);
+        owner[2 * i] = li;
+        owner[2 * i + 1] = s;
+    }
+    return AOS2_OK;
+}
+
 int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
                  const uint8_t *status)
 {
@@ -404,6 +437,17 @@ int aos2_debug_wave_ops_device(const int32_t *vi, const double *vd, int n_cases,
     AOS2_HIP_CHECK(hipMemcpy(out_d, dod.p, sizeof(double) * kWaveOpsD * n, hipMemcpyDeviceToHost));
     di.release(); dd.release(); doi.release(); dod.release();
     return AOS2_OK;
+}
+
+int aos2_debug_row_sums_scatter_device(const double *v, int K, double *out, int32_t *owner, int device)
+{
+    using namespace aos2;
+    if (!v || !out || !owner || (K != 7 && K != 36 && K != 42)) {
+        set_error("bad argument (the three arrays, K = 7, 36 or 42)");
+        return AOS2_ERR_ARG;
+    }
+    if (int st = bind_device(device)) return st;
+    return K == 7 ? row_sums_scatter_run<7>(v, out, owner) : K == 36 ? row_sums_scatter_run<36>(v, out, owner) : row_sums_scatter_run<42>(v, out, owner);
 }
 
 // PNG scanline filters undone in place (PNG specification, section 9: None / Sub / Up / Average / Paeth): `rows` = h rows of

@@ -932,22 +932,19 @@ __device__ __forceinline__ void lin_points_walk(const LbaWin &W, int l)
     for (int i = 0; i < 3; ++i) W.b[6 * (size_t)W.np + 3 * (size_t)l + i] = bl[i];
 }
 
-// acc[K] of every thread of an NT-thread workgroup -> their sums (returned in threads e < K).  16-lane DPP row sums, then
+// acc[K] of every thread of an NT-thread workgroup -> their sums (returned in threads e < K).  16-lane DPP row sums (as a
+// reduce-scatter: the lanes of a row share the K totals and each writes its own), then
 // the row totals of each value through LDS in row order: a fixed order (bit-reproducible), NT / 16 x K doubles of LDS.
 // n_items = work items of the workgroup (thread t had one iff t < n_items): waves without any skip their share, and rows
 // without any are left out of the final sums (they would add +0.0).
 template <int K, int NT = 256>
 __device__ __forceinline__ double workgroup_sum_k256(double (&acc)[K], double *red /* (NT / 16) x (K + 1) */, int n_items)
 {
-    const int lane = threadIdx.x & 63, row = threadIdx.x >> 4, wave = threadIdx.x >> 6;
+    const int row = threadIdx.x >> 4, wave = threadIdx.x >> 6;
     const int rows_used = min(NT / 16, (n_items + 15) >> 4);
     if (wave * 64 < n_items) {   // wave-uniform
-#pragma unroll
-        for (int i = 0; i < K; ++i) acc[i] = row_sum_f64(acc[i]);
-        if ((lane & 15) == 0) {
-#pragma unroll
-            for (int i = 0; i < K; ++i) red[row * (K + 1) + i] = acc[i];
-        }
+        row_sums_scatter_f64<K>(acc);
+        row_scatter_store<K>(acc, red + row * (K + 1));
     }
     __syncthreads();
     double sum = 0;
@@ -1242,12 +1239,8 @@ void k_schur(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ task
             s_ij[row] = ij;
         }
         if (li < (info & 255)) schur_item<false>(W, o0 + li, lambda, n6, W.Rl + 9 * (size_t)(ij & 0xffff), W.Rl + 9 * (size_t)(ij >> 16), acc);
-#pragma unroll
-        for (int i = 0; i < 36; ++i) acc[i] = row_sum_f64(acc[i]);
-        if (li == 0) {
-#pragma unroll
-            for (int i = 0; i < 36; ++i) red[row * 43 + i] = acc[i];
-        }
+        row_sums_scatter_f64<36>(acc);
+        row_scatter_store<36>(acc, red + row * 43);
         __syncthreads();
         // a block's rows are neighbours inside the unit: its first row's slot adds them in row order
         for (int rr = wave; rr < 16; rr += NT / 64) {

@@ -24,12 +24,25 @@ __device__ __forceinline__ int dpp_i32(int v)
 {
     return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xf, 0xf, false);
 }
+// the same move for a double, two 32-bit moves.  `old` (the value of lanes without a source) is 0 with bound_ctrl: every lane has
+// a source under the words this header uses with it, so it is never read -- and with `v` there the compiler copied both halves
+// with a plain v_mov_b32 in front of every DPP move (the destination is tied to `old`)
 template <int kCtrl>
 __device__ __forceinline__ double dpp_f64(double v)
 {
     const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp((int)b, (int)b, kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(b >> 32), (int)(b >> 32), kCtrl, 0xf, 0xf, false);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, kCtrl, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), kCtrl, 0xf, 0xf, true);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// lanes of the banks in kBanks (bank q = the quad of lanes 4 q .. 4 q + 3 of every row): v of the lane kCtrl names; the other
+// lanes: `old`.  The enabled lanes must have a source under kCtrl.
+template <int kCtrl, int kBanks>
+__device__ __forceinline__ double dpp_f64_banks(double old, double v)
+{
+    const long long o = __double_as_longlong(old), b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)b, kCtrl, 0xf, kBanks, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(b >> 32), kCtrl, 0xf, kBanks, false);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
@@ -96,6 +109,89 @@ __device__ __forceinline__ double row_sum_f64(double v)
     v += dpp_f64<0x141>(v);
     v += dpp_f64<0x140>(v);
     return v;
+}
+
+// ---- K row sums at once as a reduce-scatter: the totals of row_sum_f64 (the same operands in the same tree, so the same bits)
+// without forming every total in every lane.  The four levels pair lane ^ 1, lane ^ 2, lane ^ 4, lane ^ 8; at a level a lane keeps
+// one value of each pair of its remaining values and hands the other one to its partner, who adds it to the one it kept:
+// n values become ceil(n / 2) (an unpaired last value is added the butterfly's way), and after the fourth level the total of
+// every value sits in slot s of the lanes row_scatter_index names.  IEEE addition is commutative, so which of the two lanes
+// adds does not show in the bits.
+constexpr int row_scatter_count(int K, int level) { return level == 0 ? K : ((K + (1 << level) - 1) >> level); }
+// slots a lane holds after row_sums_scatter_f64<K>
+constexpr int row_scatter_slots(int K) { return row_scatter_count(K, 4); }
+// the value whose total slot s of lane li of a row (li = lane & 15) holds afterwards.  Every value has a (li, s); the totals of
+// values that were unpaired at some level sit in several lanes (the same bits in each).
+template <int K>
+__host__ __device__ constexpr int row_scatter_index(int s, int li)
+{
+    constexpr int n0 = K, n1 = row_scatter_count(K, 1), n2 = row_scatter_count(K, 2), n3 = row_scatter_count(K, 3);   // values before a level
+    int idx = s;
+    idx = ((n3 & 1) && idx == n3 / 2) ? n3 - 1 : 2 * idx + ((li >> 3) & 1);
+    idx = ((n2 & 1) && idx == n2 / 2) ? n2 - 1 : 2 * idx + ((li >> 2) & 1);
+    idx = ((n1 & 1) && idx == n1 / 2) ? n1 - 1 : 2 * idx + ((li >> 1) & 1);
+    idx = ((n0 & 1) && idx == n0 / 2) ? n0 - 1 : 2 * idx + (li & 1);
+    return idx;
+}
+// the first (li, s) that holds value i
+template <int K>
+__host__ __device__ constexpr void row_scatter_owner(int i, int &li, int &s)
+{
+    for (li = 0; li < 16; ++li)
+        for (s = 0; s < row_scatter_slots(K); ++s)
+            if (row_scatter_index<K>(s, li) == i) return;
+}
+
+// one pair of a level with partner lane ^ 1 / lane ^ 2: `up` = the lane's bit of the level
+template <int kCtrl>
+__device__ __forceinline__ double row_scatter_pair_quad(double a, double b, bool up)
+{
+    const double keep = up ? b : a, send = up ? a : b;
+    return keep + dpp_f64<kCtrl>(send);
+}
+// one pair of a level with partner lane ^ 4 / lane ^ 8: a bank is a quad, so the bank mask selects between the lane's own value
+// and the partner's.  kLo = the banks whose bit of the level is 0; they take a from kFromUp, the others b from kFromLo
+template <int kFromUp, int kFromLo, int kLo>
+__device__ __forceinline__ double row_scatter_pair_banks(double a, double b)
+{
+    const double x = dpp_f64_banks<kFromLo, 0xf & ~kLo>(a, b);   // lower lanes: own a; upper lanes: the partner's b
+    const double y = dpp_f64_banks<kFromUp, kLo>(b, a);          // lower lanes: the partner's a; upper lanes: own b
+    return x + y;
+}
+// v + v of lane ^ 4 (values that differ between the lanes of a quad: row_half_mirror would not do)
+__device__ __forceinline__ double row_scatter_single_4(double v)
+{
+    return v + dpp_f64_banks<0x114, 0xa>(dpp_f64_banks<0x104, 0x5>(v, v), v);   // row_shl:4 into banks 0, 2; row_shr:4 into banks 1, 3
+}
+
+template <int K, int N>
+__device__ __forceinline__ void row_sums_scatter_f64(double (&v)[N])   // v[0 .. K) -> v[0 .. row_scatter_slots(K))
+{
+    static_assert(K >= 1 && K <= N, "K values of the array");
+    const int lane = threadIdx.x & 15;
+    constexpr int n0 = K, n1 = row_scatter_count(K, 1), n2 = row_scatter_count(K, 2), n3 = row_scatter_count(K, 3);
+    const bool up0 = lane & 1, up1 = lane & 2;
+#pragma unroll
+    for (int m = 0; m < n0 / 2; ++m) v[m] = row_scatter_pair_quad<0xB1>(v[2 * m], v[2 * m + 1], up0);
+    if (n0 & 1) v[n0 / 2] = v[n0 - 1] + dpp_f64<0xB1>(v[n0 - 1]);
+#pragma unroll
+    for (int m = 0; m < n1 / 2; ++m) v[m] = row_scatter_pair_quad<0x4E>(v[2 * m], v[2 * m + 1], up1);
+    if (n1 & 1) v[n1 / 2] = v[n1 - 1] + dpp_f64<0x4E>(v[n1 - 1]);
+#pragma unroll
+    for (int m = 0; m < n2 / 2; ++m) v[m] = row_scatter_pair_banks<0x104, 0x114, 0x5>(v[2 * m], v[2 * m + 1]);   // row_shl:4, row_shr:4
+    if (n2 & 1) v[n2 / 2] = row_scatter_single_4(v[n2 - 1]);
+#pragma unroll
+    for (int m = 0; m < n3 / 2; ++m) v[m] = row_scatter_pair_banks<0x128, 0x128, 0x3>(v[2 * m], v[2 * m + 1]);   // row_ror:8 = lane ^ 8
+    if (n3 & 1) v[n3 / 2] = v[n3 - 1] + dpp_f64<0x128>(v[n3 - 1]);
+}
+// the totals into out[i], i = the value's index (LDS or memory; lanes that hold the same total write the same bits)
+template <int K, int N, int S = 0>
+__device__ __forceinline__ void row_scatter_store(const double (&v)[N], double *out)
+{
+    if constexpr (S < row_scatter_slots(K)) {   // (a slot per instantiation: v is indexed by constants only and stays in registers)
+        out[row_scatter_index<K>(S, threadIdx.x & 15)] = v[S];
+        row_scatter_store<K, N, S + 1>(v, out);
+    }
 }
 
 __device__ __forceinline__ int wave_incl_scan_i32(int v)  // inclusive prefix sum over the lanes

@@ -1072,6 +1072,10 @@ int aos2_debug_sincos_device(const float *angles, int n, float *s, float *c, int
  * under 0xB1, 0x4E, 0x141, 0x140, row sum, wave sum, wave max, row min, wave min, inclusive scan, block_excl_scan_i32<nt> and its
  * total; out_d [n_cases][nt][7] = dpp_f64 under the four words, row_sum_f64, readlane_f64 of lanes 0 and 63. */
 int aos2_debug_wave_ops_device(const int32_t *vi, const double *vd, int n_cases, int nt, int32_t *out_i, double *out_d, int device);
+/* row_sums_scatter_f64<K> of csrc/wave_ops.h (K = 7, 36 or 42) run by one wave: v [64][K], a lane's K values; out [64][slots] = every
+ * lane's slots afterwards (slots = ceil(K / 16)); owner [K][2] = the lane of a row (0 .. 15) and the slot that row_scatter_owner
+ * names for the total of value i. */
+int aos2_debug_row_sums_scatter_device(const double *v, int K, double *out, int32_t *owner, int device);
 /* aos2_triangulate_matches on the HOST with the routine the device kernels also run (csrc/triangulate.h); needs no device */
 int aos2_debug_triangulate_host(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1,
                                 const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
