@@ -107,6 +107,8 @@ def lib():
         L.aos2_debug_wave_ops_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
         L.aos2_debug_row_sums_scatter_device.argtypes = [vp, ci, vp, vp, ci]
         L.aos2_debug_pose_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
+        if hasattr(L, "aos2_debug_pose_pass_device"):
+            L.aos2_debug_pose_pass_device.argtypes = [vp, ci, ci, ci]
         L.aos2_debug_lba_reduced_solve_device.argtypes = [ci] + [vp] * 12 + [ci]
         L.aos2_debug_triangulate_host.argtypes = [vp, ci, vp, vp, vp, vp]
         L.aos2_triangulate_matches.argtypes = [vp, vp, ci, vp, vp, vp, vp]
@@ -1132,6 +1134,45 @@ def debug_pose_blocks_device(upd, T, Hb, lam, x0, device=0):
     To = np.zeros((n, 7)); ok = np.zeros(n, np.uint8)
     _check(lib().aos2_debug_pose_blocks_device(_p(upd), _p(T), _p(To), _p(Hb), _p(lam), _p(x), _p(ok), n, device))
     return To, x, ok
+
+
+class _PosePassCase(C.Structure):
+    _fields_ = [("n", C.c_int32), ("form", C.c_int32), ("it", C.c_int32), ("Xw", C.c_void_p), ("obs", C.c_void_p), ("inv_sigma2", C.c_void_p),
+                ("stereo", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("pose", C.c_double * 7), ("level1", C.c_void_p), ("robust", C.c_void_p), ("outlier", C.c_void_p), ("chi2", C.c_void_p),
+                ("sums", C.c_double * 28), ("pose_out", C.c_double * 7), ("Tcw", C.c_float * 16), ("n_bad", C.c_int32), ("n_inliers", C.c_int32)]
+
+
+POSE_PASS_FORMS = ((4, 256, 1024), (8, 256, 2048), (9, 128, 1152), (0, 256, None))   # form -> (kEpt, NT, largest n)
+
+
+def debug_pose_pass_device(cases, mode, device=0):
+    """test tap: pose_optimization_body of csrc/pose_opt.hip, one workgroup per case in the instantiation POSE_PASS_FORMS[case["form"]].
+    cases: synth_pose_problem()-style dicts (n, Xw, obs, stereo, inv_sigma2, fx .. bf) with form, pose (7 doubles qx qy qz qw tx ty tz) and,
+    optional, it (0), level1 (zeros), robust (ones), outlier (zeros), chi2 (zeros), [n] each.  mode 1: one edge pass -> sums (28: H upper
+    triangle, b, robust chi2), chi2 [n]; mode 2: the reclassification of round it -> outlier, level1, robust, chi2, n_bad; mode 0: the
+    whole procedure -> outlier, n_bad, n_inliers, pose_out, Tcw.  -> one dict per case with all of them"""
+    n_cases = len(cases)
+    S = (_PosePassCase * max(n_cases, 1))()
+    keep = []
+    for s, c in zip(S, cases):
+        n = int(c["n"])
+        s.n, s.form, s.it = n, int(c["form"]), int(c.get("it", 0))
+        arrs = {}
+        for name, dt, fill in (("Xw", np.float32, None), ("obs", np.float32, None), ("inv_sigma2", np.float32, None), ("stereo", np.uint8, None),
+                               ("level1", np.uint8, 0), ("robust", np.uint8, 1), ("outlier", np.uint8, 0), ("chi2", np.float64, 0)):
+            a = np.full(n, fill, dt) if c.get(name) is None else np.array(c[name], dt, order="C").reshape(-1)
+            assert a.size == n * (3 if name in ("Xw", "obs") else 1), name
+            a = np.concatenate([a, np.zeros(1, dt)])   # (never an empty array)
+            arrs[name] = a
+            setattr(s, name, a.ctypes.data)
+        keep.append(arrs)
+        s.fx, s.fy, s.cx, s.cy, s.bf = (float(np.float32(c[k])) for k in ("fx", "fy", "cx", "cy", "bf"))
+        s.pose = (C.c_double * 7)(*[float(x) for x in np.asarray(c["pose"], np.float64).reshape(7)])
+    _check(lib().aos2_debug_pose_pass_device(C.byref(S) if n_cases else None, n_cases, int(mode), device))
+    return [dict(sums=np.array(list(s.sums), np.float64), pose_out=np.array(list(s.pose_out), np.float64), Tcw=np.array(list(s.Tcw), np.float32),
+                 n_bad=int(s.n_bad), n_inliers=int(s.n_inliers), **{k: a[k][:s.n].copy() for k in ("level1", "robust", "outlier", "chi2")})
+            for s, a in zip(S, keep)]
 
 
 def debug_lba_reduced_solve_device(cases, device=0):

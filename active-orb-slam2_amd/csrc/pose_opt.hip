@@ -30,6 +30,13 @@ struct PoseProbDev {
     int32_t *counts;              // [0] n_bad, [1] n_inliers
 };
 
+// What aos2_debug_pose_pass_device asks of pose_optimization_body<.., .., true>: one edge pass (mode 1) or the reclassification of
+// round `it` (mode 2) at pose_in, with the flags and the stored chi2 the caller left in P.level1 / robust / outlier / err.
+struct PoseTap {
+    int mode, it, form;           // (form: which instantiation runs the case; the launches of the others pass it by)
+    double *sums;                 // 28, mode 1: fin
+};
+
 __device__ __forceinline__ void po_edge_error(const double *qt, const float *Xf, const float *obf, int stereo,
                                               const PoseProbDev &P, double er[3])
 {
@@ -192,8 +199,11 @@ __device__ __forceinline__ void block_sum28(double (&v)[kPoSum], double *part /*
 // NT: threads of the workgroup (256, or 512 / 1024 for the latency-bound small batches: fewer edges per thread = a shorter
 // dependent chain per pass; the per-thread edge order and the order of the wave sums are functions of NT, so results of
 // different NT agree to rounding, not bit for bit -- a batch always runs ONE variant).
-template <int kEpt, int NT = 256>
-__device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, double *sh, int *s_cnt)
+// kTap (aos2_debug_pose_pass_device only): the edge state comes from P's arrays instead of the constants of the first round; `pass`
+// (mode 1) or the reclassification of round tap->it (mode 2) runs once at pose_in -- the LM trials are not compiled -- and the edge
+// state goes back to the arrays.
+template <int kEpt, int NT = 256, bool kTap = false>
+__device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, double *sh, int *s_cnt, const PoseTap *tap = nullptr)
 {
     constexpr int EPT = kEpt > 0 ? kEpt : 1;
     constexpr bool kReg = kEpt > 0;
@@ -226,8 +236,16 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
             Rbr[j] = 1;
             Outr[j] = 0;
             Cr[j] = 0;
+            if constexpr (kTap) {
+                if (in) {
+                    L1r[j] = P.level1[e];
+                    Rbr[j] = P.robust[e];
+                    Outr[j] = P.outlier[e];
+                    Cr[j] = P.err[e];
+                }
+            }
         }
-    } else {
+    } else if constexpr (!kTap) {
         PO_FOR_EDGES(j, e) {
             L1(j, e) = 0;
             Rb(j, e) = 1;
@@ -238,7 +256,7 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
     double qt[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) qt[k] = P.pose_in[k];
-    if (n < 3) {  // nInitialCorrespondences < 3 (:355-356): the pose stays, mvbOutlier was already reset (:283, :320)
+    if (!kTap && n < 3) {  // nInitialCorrespondences < 3 (:355-356): the pose stays, mvbOutlier was already reset (:283, :320)
         for (int e = tid; e < n; e += NT) P.outlier[e] = 0;   // (the register copies above never reach memory here)
         if (tid == 0) {
 #pragma unroll
@@ -478,11 +496,20 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
     int nBad = 0, cur = 0;
     double *fin0 = sh + (NT / 64) * kPoSum;   // two result buffers of the sums
     double xs[6] = {0, 0, 0, 0, 0, 0};   // the solver's x: persists over trials and rounds
-    for (int it = 0; it < 4; ++it) {
+    int it0 = 0;
+    if constexpr (kTap) {
+        it0 = tap->it;
+        if (tap->mode == 1) {
+            pass(qt, fin0);
+            if (tid < kPoSum) tap->sums[tid] = fin0[tid];
+            it0 = 4;   // (no reclassification)
+        }
+    }
+    for (int it = it0; it < 4; ++it) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) qt[k] = P.pose_in[k];  // every round restarts from pFrame->mTcw (:368)
         const int n_active = n - nBad;   // the edges not at level 1
-        if (n_active > 0) {
+        if (!kTap && n_active > 0) {
             int nBadLM = 0;
             bool ok = true, have = false;   // have: Hb / currentChi / the stored chi2 belong to the current pose
             double lambda = 0, ni = 2, currentChi = 0;
@@ -590,11 +617,19 @@ __device__ __forceinline__ void pose_optimization_body(const PoseProbDev &P, dou
         __syncthreads();
         nBad = *s_cnt;
         __syncthreads();
-        if (n < 10) break;  // optimizer.edges().size() < 10
+        if (kTap || n < 10) break;  // optimizer.edges().size() < 10
     }
     if (kReg) {
 #pragma unroll EPT
         PO_FOR_EDGES(j, e) P.outlier[e] = Outr[j];
+        if constexpr (kTap) {
+#pragma unroll EPT
+            PO_FOR_EDGES(j, e) {
+                P.level1[e] = L1r[j];
+                P.robust[e] = Rbr[j];
+                P.err[e] = Cr[j];
+            }
+        }
     }
     if (tid == 0) {
 #pragma unroll
@@ -768,6 +803,135 @@ int aos2_debug_pose_blocks_device(const double *upd, const double *T, double *T_
     AOS2_HIP_CHECK(hipMemcpy(ok, dk.p, N, hipMemcpyDeviceToHost));
     d.release();
     dk.release();
+    return AOS2_OK;
+}
+
+}  // extern "C"
+
+// aos2_debug_pose_pass_device: pose_optimization_body in a chosen instantiation, one workgroup per case.  The launch of a form covers all
+// cases; a workgroup whose case asked for another form leaves at once.
+template <int kForm, int kEpt, int NT, bool kTap>
+__global__ __launch_bounds__(NT) void pose_pass_tap_kernel(const PoseProbDev *__restrict__ probs, const PoseTap *__restrict__ taps)
+{
+    extern __shared__ __attribute__((aligned(16))) double sh[];  // po_lds_bytes(NT)
+    __shared__ int s_cnt;
+    const PoseTap tap = taps[blockIdx.x];
+    if (tap.form != kForm) return;
+    const PoseProbDev P = probs[blockIdx.x];
+    pose_optimization_body<kEpt, NT, kTap>(P, sh, &s_cnt, &tap);
+}
+
+template <bool kTap>
+static void pose_pass_tap_launch(int form, int n_cases, const PoseProbDev *probs, const PoseTap *taps)
+{
+    const dim3 g((unsigned)n_cases);
+    if (form == 0) hipLaunchKernelGGL((pose_pass_tap_kernel<0, 4, 256, kTap>), g, dim3(256), po_lds_bytes(256), 0, probs, taps);
+    if (form == 1) hipLaunchKernelGGL((pose_pass_tap_kernel<1, 8, 256, kTap>), g, dim3(256), po_lds_bytes(256), 0, probs, taps);
+    if (form == 2) hipLaunchKernelGGL((pose_pass_tap_kernel<2, 9, 128, kTap>), g, dim3(128), po_lds_bytes(128), 0, probs, taps);
+    if (form == 3) hipLaunchKernelGGL((pose_pass_tap_kernel<3, 0, 256, kTap>), g, dim3(256), po_lds_bytes(256), 0, probs, taps);
+}
+
+extern "C" {
+
+int aos2_debug_pose_pass_device(aos2_pose_pass_case_t *cases, int n_cases, int mode, int device)
+{
+    static const int form_max[4] = {256 * 4, 256 * 8, 128 * 9, INT32_MAX};
+    if (!cases || n_cases < 1 || mode < 0 || mode > 2) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    for (int i = 0; i < n_cases; ++i) {
+        const aos2_pose_pass_case_t &c = cases[i];
+        if (c.form < 0 || c.form > 3 || c.n < 0 || c.n > form_max[c.form] || c.it < 0 || c.it > 3 || !c.Xw || !c.obs || !c.inv_sigma2 ||
+            !c.stereo || !c.level1 || !c.robust || !c.outlier || !c.chi2) {
+            set_error("bad pose pass case %d", i);
+            return AOS2_ERR_ARG;
+        }
+    }
+    int st;
+    if ((st = bind_device(device))) return st;
+    // one buffer: per case Xw | obs | w | chi2 | stereo | level1 | robust | outlier (16-byte aligned parts), then the descriptors and results
+    struct Off { size_t xw, obs, w, err, st, l1, rb, out; };
+    std::vector<Off> offs((size_t)n_cases);
+    size_t size = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = size;
+        size = (size + bytes + 15) & ~(size_t)15;
+        return o;
+    };
+    for (int i = 0; i < n_cases; ++i) {
+        const size_t n = (size_t)cases[i].n;
+        Off &o = offs[i];
+        o.xw = take(12 * n + 4); o.obs = take(12 * n + 4); o.w = take(4 * n + 4); o.err = take(8 * n + 8);
+        o.st = take(n + 1); o.l1 = take(n + 1); o.rb = take(n + 1); o.out = take(n + 1);
+    }
+    const size_t N = (size_t)n_cases;
+    const size_t o_probs = take(sizeof(PoseProbDev) * N), o_taps = take(sizeof(PoseTap) * N);
+    const size_t o_pose = take(56 * N), o_cnt = take(8 * N), o_sums = take(8 * (size_t)kPoSum * N);
+    std::vector<uint8_t> h(size, 0);
+    DevBuf<uint8_t> d;
+    if ((st = d.alloc(size))) return st;
+    uint8_t *base = d.p;
+    PoseProbDev *probs = reinterpret_cast<PoseProbDev *>(h.data() + o_probs);
+    PoseTap *taps = reinterpret_cast<PoseTap *>(h.data() + o_taps);
+    bool used[4] = {false, false, false, false};
+    for (int i = 0; i < n_cases; ++i) {
+        const aos2_pose_pass_case_t &c = cases[i];
+        const size_t n = (size_t)c.n;
+        const Off &o = offs[i];
+        memcpy(h.data() + o.xw, c.Xw, 12 * n);
+        memcpy(h.data() + o.obs, c.obs, 12 * n);
+        memcpy(h.data() + o.w, c.inv_sigma2, 4 * n);
+        memcpy(h.data() + o.err, c.chi2, 8 * n);
+        memcpy(h.data() + o.st, c.stereo, n);
+        memcpy(h.data() + o.l1, c.level1, n);
+        memcpy(h.data() + o.rb, c.robust, n);
+        memcpy(h.data() + o.out, c.outlier, n);
+        PoseProbDev &D = probs[i];
+        D.n = c.n;
+        D.Xw = (const float *)(base + o.xw); D.obs = (const float *)(base + o.obs);
+        D.w = (const float *)(base + o.w); D.stereo = base + o.st;
+        D.err = (double *)(base + o.err); D.level1 = base + o.l1; D.robust = base + o.rb; D.outlier = base + o.out;
+        D.pose_out = (double *)(base + o_pose) + 7 * (size_t)i; D.counts = (int32_t *)(base + o_cnt) + 2 * (size_t)i;
+        D.fx = (double)c.fx; D.fy = (double)c.fy; D.cx = (double)c.cx; D.cy = (double)c.cy; D.bf = (double)c.bf;
+        for (int k = 0; k < 7; ++k) D.pose_in[k] = c.pose[k];
+        taps[i].mode = mode;
+        taps[i].it = c.it;
+        taps[i].form = c.form;
+        taps[i].sums = (double *)(base + o_sums) + (size_t)kPoSum * (size_t)i;
+        used[c.form] = true;
+    }
+    hipError_t e = hipMemcpy(base, h.data(), size, hipMemcpyHostToDevice);
+    for (int form = 0; form < 4 && e == hipSuccess; ++form) {
+        if (!used[form]) continue;
+        if (mode == 0)
+            pose_pass_tap_launch<false>(form, n_cases, (const PoseProbDev *)(base + o_probs), (const PoseTap *)(base + o_taps));
+        else
+            pose_pass_tap_launch<true>(form, n_cases, (const PoseProbDev *)(base + o_probs), (const PoseTap *)(base + o_taps));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h.data(), base, size, hipMemcpyDeviceToHost);
+    d.release();
+    if (e != hipSuccess) {
+        set_error("pose pass tap failed: %s", hipGetErrorString(e));
+        return AOS2_ERR_HIP;
+    }
+    for (int i = 0; i < n_cases; ++i) {
+        aos2_pose_pass_case_t &c = cases[i];
+        const size_t n = (size_t)c.n;
+        const Off &o = offs[i];
+        memcpy(c.chi2, h.data() + o.err, 8 * n);
+        memcpy(c.level1, h.data() + o.l1, n);
+        memcpy(c.robust, h.data() + o.rb, n);
+        memcpy(c.outlier, h.data() + o.out, n);
+        memcpy(c.sums, h.data() + o_sums + 8 * (size_t)kPoSum * (size_t)i, 8 * (size_t)kPoSum);
+        memcpy(c.pose_out, h.data() + o_pose + 56 * (size_t)i, 56);
+        const int32_t *cnt = reinterpret_cast<const int32_t *>(h.data() + o_cnt) + 2 * (size_t)i;
+        c.n_bad = cnt[0];
+        c.n_inliers = cnt[1];
+        pose_to_Tcw(c.pose_out, c.Tcw);
+    }
     return AOS2_OK;
 }
 

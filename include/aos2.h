@@ -1099,6 +1099,30 @@ int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_res
  * ok[i] = 0 where a pivot was not positive (x[i] is left as passed in) */
 int aos2_debug_pose_blocks_device(const double *upd, const double *T, double *T_out, const double *Hb, const double *lambda,
                                   double *x, uint8_t *ok, int n, int device);
+/* pose_optimization_body of csrc/pose_opt.hip itself, one workgroup per case, in the instantiation the case names:
+ * form 0 = <4,256> (n <= 1024), 1 = <8,256> (n <= 2048), 2 = <9,128> (n <= 1152), 3 = <0,256> (edges in global memory, any n).
+ * mode 1, edge pass: `pass` once at `pose` with level1 / robust as given -> sums (21 upper-triangle entries of H row by row, 6 of b,
+ *         the robust chi2) and chi2 = the stored per-edge chi2 (an edge at level 1: as passed in form 3, 0 in the register forms).
+ * mode 2, outlier pass: the reclassification of round `it` once at `pose`, from level1 / robust / outlier / chi2 as given -> the flags
+ *         and chi2 as they stand afterwards, n_bad (n_inliers = n - n_bad).
+ * mode 0, whole procedure: the body unchanged (the flags and chi2 passed in are ignored) -> outlier, n_bad, n_inliers, pose_out and
+ *         Tcw = Converter::toCvMat(pose_out); level1 / robust / chi2 come back as the procedure left them in form 3, as passed otherwise.
+ * In modes 1 and 2 pose_out = pose and the LM trials do not run.  AOS2_ERR_ARG (before a device is looked for): a NULL, n_cases < 1,
+ * another form or mode, n < 0 or above the form's limit, it outside 0..3. */
+typedef struct {
+    int32_t n, form, it;
+    const float *Xw, *obs, *inv_sigma2;   /* as in aos2_pose_problem_t */
+    const uint8_t *stereo;
+    float fx, fy, cx, cy, bf;
+    double pose[7];                   /* qx qy qz qw tx ty tz */
+    uint8_t *level1, *robust, *outlier;   /* [n] in / out */
+    double *chi2;                     /* [n] in / out */
+    double sums[28];                  /* out (mode 1) */
+    double pose_out[7];               /* out */
+    float Tcw[16];                    /* out */
+    int32_t n_bad, n_inliers;         /* out */
+} aos2_pose_pass_case_t;
+int aos2_debug_pose_pass_device(aos2_pose_pass_case_t *cases, int n_cases, int mode, int device);
 /* The two kernels that solve LocalBA's reduced camera system (csrc/lba.hip: k_ldlt_reg, k_ldlt_dev), alone, with their epilogue: n_cases
  * independent systems H x = bs in ONE launch of each kernel, sized and launched like a Levenberg-Marquardt trial's.  Case c: np[c] free
  * keyframes, n = 6 np[c]; form[c] = 2: k_ldlt_reg (np <= 40), 0: k_ldlt_dev (np <= 154); H: n x n, both triangles (the tap pads it the

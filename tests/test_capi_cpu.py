@@ -520,3 +520,48 @@ def test_assembly_tap_refuses_on_the_host(pkg):
         with pytest.raises(capi.AosError) as e:
             ba.debug_assemble([win])
         assert e.value.code == capi.AOS2_ERR_NO_DEVICE
+
+
+def test_pose_pass_tap_refuses_on_the_host(pkg):
+    """aos2_debug_pose_pass_device checks its arguments before it looks for a device: a NULL (the case list, every array of a case), no
+    cases, an unknown form or mode, n above the form's limit (1024, 2048, 1152; none for the form that leaves the edges in memory) or
+    below 0, a round outside 0..3."""
+    capi = pkg.capi
+    p = pkg.synth.synth_pose_problem(1, n=40)
+    good = dict(p, form=0, pose=pkg.synth.tcw_to_qt(p["Tcw"]))
+
+    def refused(case, mode=1):
+        with pytest.raises(capi.AosError) as e:
+            capi.debug_pose_pass_device([good, case], mode)
+        assert e.value.code == capi.AOS2_ERR_ARG, (mode, str(e.value))
+
+    for mode in (-1, 3):
+        refused(good, mode)
+    for kw in (dict(form=-1), dict(form=4), dict(it=-1), dict(it=4)):
+        refused(dict(good, **kw))
+    for form, limit in ((0, 1024), (1, 2048), (2, 1152)):
+        big = pkg.synth.synth_pose_problem(2, n=limit + 1)
+        refused(dict(big, form=form, pose=good["pose"]))
+    f = capi.lib().aos2_debug_pose_pass_device
+    assert f(None, 1, 1, 0) == capi.AOS2_ERR_ARG
+    S_ = (capi._PosePassCase * 1)()
+    bufs = {k: np.zeros(256, np.float64) for k in ("Xw", "obs", "inv_sigma2", "stereo", "level1", "robust", "outlier", "chi2")}
+    S_[0].n, S_[0].form, S_[0].it = 40, 0, 0
+    S_[0].pose = (C.c_double * 7)(0, 0, 0, 1, 0, 0, 0)
+    for k, a in bufs.items():
+        setattr(S_[0], k, a.ctypes.data)
+    assert f(C.byref(S_), 0, 1, 0) == capi.AOS2_ERR_ARG and f(C.byref(S_), -1, 1, 0) == capi.AOS2_ERR_ARG
+    S_[0].n = -1
+    assert f(C.byref(S_), 1, 1, 0) == capi.AOS2_ERR_ARG
+    S_[0].n = 40
+    for k in bufs:   # every array in turn
+        setattr(S_[0], k, None)
+        assert f(C.byref(S_), 1, 1, 0) == capi.AOS2_ERR_ARG, k
+        setattr(S_[0], k, bufs[k].ctypes.data)
+    if pkg.device_count() == 0:   # good arguments get as far as the device
+        for form, n in ((0, 1024), (1, 2048), (2, 1152), (3, 5000)):
+            big = pkg.synth.synth_pose_problem(2, n=n)
+            with pytest.raises(capi.AosError) as e:
+                capi.debug_pose_pass_device([dict(big, form=form, pose=good["pose"])], 1)
+            assert e.value.code == capi.AOS2_ERR_NO_DEVICE
+        assert f(C.byref(S_), 1, 1, 0) == capi.AOS2_ERR_NO_DEVICE
