@@ -119,6 +119,11 @@ def lib():
         L.aos2_debug_pnp_scan.argtypes = [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp]
         L.aos2_pnp_ransac.argtypes = [vp, vp, vp, ci]
         L.aos2_pnp_ransac_parameters.argtypes = [ci, C.c_double, ci, ci, ci, cf, vp, vp, vp]
+        L.aos2_debug_initializer_host.argtypes = [vp, vp, ci]
+        L.aos2_debug_initializer_svd.argtypes = [vp, ci, ci, vp, vp, vp]
+        L.aos2_debug_initializer_rng.argtypes = [ci, vp]
+        L.aos2_debug_initializer_inv33.argtypes = [vp, vp, C.POINTER(C.c_double)]
+        L.aos2_initializer_initialize.argtypes = [vp, vp, vp, ci]
         L.aos2_debug_sim3_opt_host.argtypes = [vp, vp, ci]
         L.aos2_optimize_sim3.argtypes = [vp, vp, vp, ci]
         L.aos2_optimize_sim3_last_device_ms.argtypes = [vp]
@@ -1031,6 +1036,121 @@ def debug_pnp_host(problems, with_counts=True):
     return _pnp_results(R, outs)
 
 
+# ---- Initializer::Initialize (include/aos2.h: aos2_initializer_initialize, aos2_debug_initializer_host)
+AOS2_INIT_OK, AOS2_INIT_NO_MODEL = 0, 1
+
+
+class _InitProblem(C.Structure):
+    _fields_ = [("n_keys1", C.c_int32), ("n_keys2", C.c_int32), ("keys1", C.c_void_p), ("keys2", C.c_void_p), ("n_matches", C.c_int32),
+                ("matches", C.c_void_p), ("sigma", C.c_float), ("iterations", C.c_int32), ("sets", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_parallax")] + [("min_triangulated", C.c_int32)]
+
+
+class _InitResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("initialized", C.c_int32), ("used_homography", C.c_int32), ("SH", C.c_float), ("SF", C.c_float),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("best_iteration_h", C.c_int32), ("best_iteration_f", C.c_int32),
+                ("inliers_h", C.c_void_p), ("inliers_f", C.c_void_p), ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("P3D", C.c_void_p),
+                ("triangulated", C.c_void_p), ("n_good", C.c_int32 * 8), ("parallax", C.c_float * 8), ("n_hypotheses", C.c_int32)]
+
+
+_INIT_SCALARS = ("status", "initialized", "used_homography", "SH", "SF", "best_iteration_h", "best_iteration_f", "n_hypotheses")
+_INIT_ARRAYS = (("H21", np.float32), ("F21", np.float32), ("R21", np.float32), ("t21", np.float32), ("n_good", np.int32),
+                ("parallax", np.float32))
+
+
+def initializer_sets(rng, n_matches, iterations):
+    """mvSets (src/Initializer.cc:78-97): per iteration 8 indices drawn without replacement by RandomInt(0, size - 1) and the
+    swap-with-back removal; int32 [iterations][8]"""
+    sets = np.zeros((iterations, 8), np.int32)
+    for it in range(iterations):
+        avail = list(range(n_matches))
+        for j in range(8):
+            r = sim3_random_int(rng, 0, len(avail) - 1)
+            sets[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def _init_args(problems, sentinel=None):
+    """problems: dicts with keys1 [n1][2], keys2 [n2][2], matches [n][2], sets [iterations][8], K = (fx, fy, cx, cy) and optionally
+    sigma (1.0), min_parallax (1.0), min_triangulated (50)"""
+    P, R, keep, outs = (_InitProblem * max(1, len(problems)))(), (_InitResult * max(1, len(problems)))(), [], []
+    for i, q in enumerate(problems):
+        k1, k2 = np.ascontiguousarray(q["keys1"], np.float32), np.ascontiguousarray(q["keys2"], np.float32)
+        mt, sets = np.ascontiguousarray(q["matches"], np.int32), np.ascontiguousarray(q["sets"], np.int32)
+        if k1.ndim != 2 or k1.shape[1] != 2 or k2.ndim != 2 or k2.shape[1] != 2 or mt.ndim != 2 or mt.shape[1] != 2 or sets.ndim != 2 or sets.shape[1] != 8:
+            raise ValueError("problem %d: keys1 [n1][2], keys2 [n2][2], matches [n][2], sets [iterations][8]" % i)
+        fill = 0 if sentinel is None else sentinel
+        out = (np.full(len(mt), fill, np.uint8), np.full(len(mt), fill, np.uint8), np.full((len(k1), 3), 0, np.float32), np.full(len(k1), fill, np.uint8))
+        if sentinel is not None:
+            out[2].view(np.uint8)[...] = sentinel
+        keep += [k1, k2, mt, sets]
+        outs.append(out)
+        P[i].n_keys1, P[i].n_keys2, P[i].n_matches = len(k1), len(k2), int(q.get("n_matches", len(mt)))
+        P[i].iterations = int(q.get("iterations", len(sets)))
+        P[i].keys1, P[i].keys2, P[i].matches, P[i].sets = (a.ctypes.data if a.size else None for a in (k1, k2, mt, sets))
+        P[i].sigma, P[i].min_parallax = float(np.float32(q.get("sigma", 1.0))), float(np.float32(q.get("min_parallax", 1.0)))
+        P[i].min_triangulated = int(q.get("min_triangulated", 50))
+        for name, v in zip(("fx", "fy", "cx", "cy"), q["K"]):
+            setattr(P[i], name, float(np.float32(v)))
+        if sentinel is not None:
+            C.memset(C.byref(R[i]), sentinel, C.sizeof(_InitResult))
+        R[i].inliers_h, R[i].inliers_f, R[i].P3D, R[i].triangulated = (a.ctypes.data for a in out)
+        for name in q.get("null", ()):   # (tests: a missing array)
+            setattr(R[i] if name in ("inliers_h", "inliers_f", "P3D", "triangulated") else P[i], name, None)
+    return P, R, keep, outs
+
+
+def _init_results(R, outs):
+    res = []
+    for i, (ih, jf, p3d, tri) in enumerate(outs):
+        d = {k: getattr(R[i], k) for k in _INIT_SCALARS}
+        d.update({k: np.array(getattr(R[i], k), t).reshape((3, 3) if k in ("H21", "F21", "R21") else -1) for k, t in _INIT_ARRAYS})
+        d["SH"], d["SF"] = np.float32(d["SH"]), np.float32(d["SF"])
+        d.update(inliers_h=ih, inliers_f=jf, P3D=p3d, triangulated=tri)
+        res.append(d)
+    return res
+
+
+init_last = None   # (result structs, result arrays, the structs' bytes before the call) of the last initializer call
+
+
+def debug_initializer_host(problems, sentinel=None):
+    """aos2_debug_initializer_host: the routines of the device kernels on the CPU -> one dict per problem (aos2_initializer_result_t).
+    `sentinel` pre-fills the result buffers; they stay in capi.init_last for a caller that expects an error"""
+    global init_last
+    P, R, keep, outs = _init_args(problems, sentinel)
+    init_last = (R, outs, [bytes(R[i]) for i in range(len(problems))])
+    _check(lib().aos2_debug_initializer_host(P, R, len(problems)))
+    return _init_results(R, outs)
+
+
+def debug_initializer_svd(A):
+    """aos2_debug_initializer_svd: cv::SVDecomp of a float matrix as csrc/initializer.h runs it -> (left [n1][m], w [n], right [n][n])"""
+    A = np.ascontiguousarray(A, np.float32)
+    rows, cols = A.shape
+    wide = rows < cols
+    n, m = (rows, cols) if wide else (cols, rows)
+    left, w, right = np.zeros((cols if wide else n, m), np.float32), np.zeros(n, np.float32), np.zeros((n, n), np.float32)
+    _check(lib().aos2_debug_initializer_svd(_p(A), rows, cols, _p(left), _p(w), _p(right)))
+    return left, w, right
+
+
+def debug_initializer_rng(n):
+    """the first n values of cv::RNG(0x12345678).next() as csrc/initializer.h generates them"""
+    out = np.zeros(n, np.uint32)
+    _check(lib().aos2_debug_initializer_rng(int(n), _p(out)))
+    return out
+
+
+def debug_initializer_inv33(S):
+    """cv::Mat::inv() and cv::determinant of a float 3x3 -> (inverse, determinant)"""
+    S, inv, det = np.ascontiguousarray(S, np.float32), np.zeros((3, 3), np.float32), C.c_double()
+    _check(lib().aos2_debug_initializer_inv33(_p(S), _p(inv), C.byref(det)))
+    return inv, det.value
+
+
 # ---- Optimizer::OptimizeSim3 (include/aos2.h: aos2_optimize_sim3, aos2_debug_sim3_opt_host)
 class _Sim3OptProblem(C.Structure):
     _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")] + \
@@ -1466,6 +1586,15 @@ class Matcher:
 
 
     # ---- projection family; f / p: synth_proj_gen_problem()-style dicts
+    def InitializerInitialize(self, problems, sentinel=None):
+        """aos2_initializer_initialize: Initializer::Initialize (src/Initializer.cc) for a batch of monocular sequences; problems as
+        debug_initializer_host -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in self.init_last for a caller
+        that expects an error and wants to see them untouched)"""
+        P, R, keep, outs = _init_args(problems, sentinel)
+        self.init_last = (R, outs, [bytes(R[i]) for i in range(len(problems))])
+        _check(self.L.aos2_initializer_initialize(self.h, P, R, len(problems)))
+        return _init_results(R, outs)
+
     def PnpRansac(self, problems, sentinel=None, with_counts=True):
         """aos2_pnp_ransac: the RANSAC of PnPsolver (src/PnPsolver.cc) for a batch of relocalisation candidates; problems as
         debug_pnp_host -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in self.pnp_last for a caller that

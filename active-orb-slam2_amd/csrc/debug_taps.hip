@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "aos2_common.h"
+#include "initializer.h"
 #include "octree.h"
 #include "pnp.h"
 #include "sincos_exact.h"
@@ -215,6 +216,83 @@ void pnp_result_clear(const aos2_pnp_problem_t &P, aos2_pnp_result_t &R)
     }
     if (counts) std::fill(counts, counts + P.n_iterations, -1);
 }
+
+int initializer_check(const aos2_initializer_problem_t *problems, const aos2_initializer_result_t *results, int n_problems)
+{
+    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
+        set_error("bad argument (0..64 problems and their results)");
+        return AOS2_ERR_ARG;
+    }
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_initializer_problem_t &P = problems[p];
+        const aos2_initializer_result_t &R = results[p];
+        if (P.n_keys1 < 1 || P.n_keys2 < 1 || !P.keys1 || !P.keys2 || P.n_matches < 8 || !P.matches || P.iterations < 1 || !P.sets ||
+            !(P.sigma > 0) || !R.inliers_h || !R.inliers_f || !R.P3D || !R.triangulated) {
+            set_error("problem %d: bad argument (the keys of both frames, n_matches >= 8, iterations >= 1 with their sets, sigma > 0, the four "
+                      "result arrays)", p);
+            return AOS2_ERR_ARG;
+        }
+        for (int i = 0; i < P.n_matches; ++i) {
+            const int32_t a = P.matches[2 * i], b = P.matches[2 * i + 1];
+            if (a < 0 || a >= P.n_keys1 || b < 0 || b >= P.n_keys2) {
+                set_error("problem %d: match %d is (%d, %d), outside the frames' %d and %d keys", p, i, a, b, P.n_keys1, P.n_keys2);
+                return AOS2_ERR_ARG;
+            }
+        }
+        for (size_t k = 0; k < (size_t)P.iterations * 8; ++k)
+            if (P.sets[k] < 0 || P.sets[k] >= P.n_matches) {
+                set_error("problem %d: entry %d of set %d is %d, outside [0, %d)", p, (int)(k % 8), (int)(k / 8), P.sets[k], P.n_matches);
+                return AOS2_ERR_ARG;
+            }
+    }
+    return AOS2_OK;
+}
+
+void initializer_result_clear(const aos2_initializer_problem_t &P, aos2_initializer_result_t &R)
+{
+    uint8_t *ih = R.inliers_h, *jf = R.inliers_f, *tri = R.triangulated;
+    float *p3d = R.P3D;
+    R = aos2_initializer_result_t{};
+    R.inliers_h = ih;
+    R.inliers_f = jf;
+    R.P3D = p3d;
+    R.triangulated = tri;
+    R.best_iteration_h = R.best_iteration_f = -1;
+    memset(ih, 0, (size_t)P.n_matches);
+    memset(jf, 0, (size_t)P.n_matches);
+    memset(p3d, 0, 12 * (size_t)P.n_keys1);
+    memset(tri, 0, (size_t)P.n_keys1);
+}
+
+// FindHomography / FindFundamental (:124-223) of one problem, serially: score, matrix (18 floats for H: H21 | H12), flags -> iteration
+static int initializer_find_host(bool is_h, const aos2_initializer_problem_t &P, const InitPts &pts, float *score, float *model, uint8_t *flags)
+{
+    InitLocal ws;
+    const float invS = init_inv_sigma2(P.sigma);
+    std::vector<float> scores((size_t)P.iterations), models((size_t)P.iterations * 18);
+    for (int it = 0; it < P.iterations; ++it) {
+        float *M = models.data() + 18 * (size_t)it;
+        if (is_h) init_model_h(pts, P.sets + 8 * (size_t)it, ws, M, M + 9);
+        else init_model_f(pts, P.sets + 8 * (size_t)it, ws, M);
+        float s = 0;
+        for (int i = 0; i < P.n_matches; ++i) {
+            float a, b;
+            init_terms(is_h, M, invS, pts, i, a, b);
+            s += a;
+            s += b;
+        }
+        scores[(size_t)it] = s;
+    }
+    const int best = init_pick(scores.data(), P.iterations, score);
+    if (best >= 0) {
+        memcpy(model, models.data() + 18 * (size_t)best, 18 * sizeof(float));
+        for (int i = 0; i < P.n_matches; ++i) {
+            float a, b;
+            flags[i] = init_terms(is_h, model, invS, pts, i, a, b);
+        }
+    }
+    return best;
+}
 }  // namespace aos2
 
 extern "C" {
@@ -325,6 +403,130 @@ int aos2_debug_pnp_host(const aos2_pnp_problem_t *problems, aos2_pnp_result_t *r
         R.best_iteration = scan.best_iteration;
         R.best_inliers = scan.best_inliers;
     }
+    return AOS2_OK;
+}
+
+int aos2_debug_initializer_host(const aos2_initializer_problem_t *problems, aos2_initializer_result_t *results, int n_problems)
+{
+    using namespace aos2;
+    if (int st = initializer_check(problems, results, n_problems)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_initializer_problem_t &P = problems[p];
+        aos2_initializer_result_t &R = results[p];
+        initializer_result_clear(P, R);
+        float nrm1[4], nrm2[4];
+        for (int axis = 0; axis < 2; ++axis) {
+            init_normalize_axis(P.keys1, P.n_keys1, axis, nrm1 + 2 * axis, nrm1 + 2 * axis + 1);
+            init_normalize_axis(P.keys2, P.n_keys2, axis, nrm2 + 2 * axis, nrm2 + 2 * axis + 1);
+        }
+        const InitPts pts = {P.keys1, P.keys2, P.matches, nrm1, nrm2};
+        float H[18] = {}, F[18] = {};
+        R.best_iteration_h = initializer_find_host(true, P, pts, &R.SH, H, R.inliers_h);
+        R.best_iteration_f = initializer_find_host(false, P, pts, &R.SF, F, R.inliers_f);
+        memcpy(R.H21, H, sizeof R.H21);
+        memcpy(R.F21, F, sizeof R.F21);
+        const float RH = R.SH / (R.SH + R.SF);
+        R.used_homography = (double)RH > 0.40;   // (a float against the double 0.40)
+        if ((R.used_homography ? R.best_iteration_h : R.best_iteration_f) < 0) {
+            R.status = AOS2_INIT_NO_MODEL;
+            continue;
+        }
+        const uint8_t *inl = R.used_homography ? R.inliers_h : R.inliers_f;
+        int N = 0;
+        for (int i = 0; i < P.n_matches; ++i) N += inl[i] != 0;
+        const InitCam cam = {P.fx, P.fy, P.cx, P.cy};
+        InitLocal ws;
+        float Rs[72], ts[24];
+        if (R.used_homography) R.n_hypotheses = init_hyps_h(R.H21, cam, ws, Rs, ts) ? 8 : 0;
+        else {
+            init_hyps_f(R.F21, cam, ws, Rs, ts);
+            R.n_hypotheses = 4;
+        }
+        if (R.n_hypotheses == 0) continue;
+        const float th2 = init_th2(P.sigma);
+        std::vector<std::vector<float>> P3D((size_t)R.n_hypotheses, std::vector<float>(3 * (size_t)P.n_keys1, 0.0f));
+        std::vector<std::vector<uint8_t>> good((size_t)R.n_hypotheses, std::vector<uint8_t>((size_t)P.n_keys1, 0));
+        for (int h = 0; h < R.n_hypotheses; ++h) {
+            InitRT S;
+            init_rt_setup(Rs + 9 * h, ts + 3 * h, cam, S);
+            std::vector<float> cosines;
+            for (int i = 0; i < P.n_matches; ++i) {
+                if (!inl[i]) continue;
+                const int k1 = P.matches[2 * i], k2 = P.matches[2 * i + 1];
+                float x[3], c = 0;
+                const int code = init_rt_point(S, cam, th2, P.keys1[2 * k1], P.keys1[2 * k1 + 1], P.keys2[2 * k2], P.keys2[2 * k2 + 1], x, &c);
+                if (code & INIT_RT_CLEARS) good[h][k1] = 0;
+                if (code & INIT_RT_GOOD) {
+                    cosines.push_back(c);
+                    memcpy(&P3D[h][3 * (size_t)k1], x, 12);
+                }
+                if (code & INIT_RT_SETS) good[h][k1] = 1;
+            }
+            R.n_good[h] = (int32_t)cosines.size();
+            if (!cosines.empty()) {
+                const size_t idx = std::min<size_t>(50, cosines.size() - 1);
+                std::vector<uint32_t> keys(cosines.size());
+                for (size_t k = 0; k < keys.size(); ++k) keys[k] = init_float_key(cosines[k]);
+                std::nth_element(keys.begin(), keys.begin() + idx, keys.end());
+                R.parallax[h] = init_parallax_deg(init_key_float(keys[idx]));
+            }
+        }
+        const int pick = R.used_homography ? init_decide_h(R.n_good, R.parallax, N, P.min_parallax, P.min_triangulated)
+                                           : init_decide_f(R.n_good, R.parallax, N, P.min_parallax, P.min_triangulated);
+        if (pick < 0) continue;
+        R.initialized = 1;
+        memcpy(R.R21, Rs + 9 * pick, sizeof R.R21);
+        memcpy(R.t21, ts + 3 * pick, sizeof R.t21);
+        memcpy(R.P3D, P3D[pick].data(), 12 * (size_t)P.n_keys1);
+        memcpy(R.triangulated, good[pick].data(), (size_t)P.n_keys1);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_initializer_svd(const float *A, int rows, int cols, float *left, float *w, float *right)
+{
+    using namespace aos2;
+    if (!A || !left || !w || !right || rows < 1 || rows > 16 || cols < 1 || cols > 9 || !(rows >= cols || rows + 1 == cols)) {
+        set_error("bad argument (the four arrays, rows <= 16, cols <= 9, rows >= cols or rows + 1 == cols)");
+        return AOS2_ERR_ARG;
+    }
+    InitLocal ws;
+    const bool wide = rows < cols;
+    const int n = wide ? rows : cols, m = wide ? cols : rows, n1 = wide ? cols : n;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < m; ++k) ws.A(i, k) = wide ? A[i * cols + k] : A[k * cols + i];
+    init_jacobi(ws, m, n);
+    init_svd_tail(ws, m, n, n1);
+    for (int i = 0; i < n1; ++i)
+        for (int k = 0; k < m; ++k) left[i * m + k] = ws.A(i, k);
+    for (int i = 0; i < n; ++i) {
+        w[i] = (float)ws.W(i);
+        for (int k = 0; k < n; ++k) right[i * n + k] = ws.V(i, k);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_initializer_rng(int n, uint32_t *out)
+{
+    using namespace aos2;
+    if (n < 0 || (n > 0 && !out)) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    InitRng rng{0x12345678};
+    for (int i = 0; i < n; ++i) out[i] = rng.next();
+    return AOS2_OK;
+}
+
+int aos2_debug_initializer_inv33(const float *S, float *inv, double *det)
+{
+    using namespace aos2;
+    if (!S || !inv || !det) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    init_inv33(S, inv);
+    *det = init_det33(S);
     return AOS2_OK;
 }
 

@@ -3413,3 +3413,4 @@ int aos2_matcher_search_for_initialization(aos2_matcher_t *m, const aos2_frame_v
 #include "frames_triangulate.inc"
 #include "sim3_ransac.inc"
 #include "pnp_ransac.inc"
+#include "initializer_ransac.inc"

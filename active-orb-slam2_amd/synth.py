@@ -804,3 +804,95 @@ def synth_pose_problem(seed: int, n: int = 800, cfg: str = "kitti", stereo_frac:
     return dict(n=n, Xw=Xw.astype(np.float32), obs=obs, stereo=stereo.astype(np.uint8),
                 inv_sigma2=(np.float32(1.0) / (sf[lvl] * sf[lvl])).astype(np.float32),
                 fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, Tcw=T.astype(np.float32).reshape(16))
+
+
+TWO_VIEW_KINDS = ("planar", "general", "rotation", "low_parallax", "static")
+TWO_VIEW_K = (517.3, 516.5, 318.6, 255.3)
+
+
+def synth_two_view(seed: int, kind: str = "general", n_matches: int = 120, n_extra: int = 0, outlier_frac: float = 0.0,
+                   noise: float = 0.0, iterations: int = 200, w: int = 640, h: int = 480, opposite: bool = False):
+    """Two monocular frames for Initializer::Initialize (src/Initializer.cc): the undistorted keys of the reference frame and the
+    current one, the matches in mvMatches12 order (sorted by the first key), the mvSets of `iterations` iterations (:78-97, drawn
+    from the seed the way DUtils::Random::RandomInt does), and the motion that made them (R21, t21: x2 = R21 x1 + t21, |t21| = 1
+    for the comparison; a zero vector where the camera does not move).
+    kind: "planar" (all points on one tilted plane), "general" (depths spread over 2..8 m), "rotation" (no translation),
+    "low_parallax" (a baseline of 4 mm), "static" (the second frame repeats the first).  A share `outlier_frac` of the matches gets
+    a second key anywhere in the image, every key of a match gets Gaussian pixel noise of `noise` pixels, and `n_extra` unmatched
+    keys per frame sit between the matched ones.  `opposite` (planar only) puts the second camera behind the plane, looking back at it:
+    the d' = -d2 solutions of the homography decomposition (hypotheses 4..7 of ReconstructH)."""
+    if kind not in TWO_VIEW_KINDS:
+        raise ValueError("kind must be one of %s" % (TWO_VIEW_KINDS,))
+    rng = np.random.default_rng([seed, TWO_VIEW_KINDS.index(kind), 0x2F1E])
+    fx, fy, cx, cy = TWO_VIEW_K
+
+    def rodrigues(rv):
+        th_ = np.linalg.norm(rv)
+        if th_ == 0:
+            return np.eye(3)
+        Kx = np.array([[0, -rv[2], rv[1]], [rv[2], 0, -rv[0]], [-rv[1], rv[0], 0]]) / th_
+        return np.eye(3) + np.sin(th_) * Kx + (1 - np.cos(th_)) * Kx @ Kx
+
+    R = np.eye(3) if kind == "static" else rodrigues(rng.normal(0, 0.03, 3) if kind != "rotation" else rng.normal(0, 0.08, 3))
+    tdir = rng.normal(0, 1, 3) * np.array([1.0, 0.5, 0.05])   # (sideways: the epipole, where the parallax vanishes, stays outside the image)
+    if kind == "planar":   # along the plane: the second solution of the decomposition then puts part of the plane behind a camera
+        a = rng.uniform(0, 2 * np.pi)
+        tdir = np.array([np.cos(a), np.sin(a), rng.uniform(-0.1, 0.1)])
+    tdir /= np.linalg.norm(tdir)
+    base = dict(planar=rng.uniform(0.35, 0.5), general=rng.uniform(0.35, 0.5), rotation=0.0, low_parallax=0.004, static=0.0)[kind]
+    t = tdir * base
+    if opposite and kind == "planar":
+        # (drawn after everything above, so that the scenes without it keep their values)
+        rng2 = np.random.default_rng([seed, 0x0BB0])
+        R = rodrigues(rng2.normal(0, 0.03, 3)) @ np.diag([-1.0, 1.0, -1.0])
+        t = -R @ np.array([rng2.uniform(-0.5, 0.5), rng2.uniform(-0.5, 0.5), rng2.uniform(6.5, 7.5)])
+    pts1, pts2 = [], []
+    normal = np.array([rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15), -1.0])
+    normal /= np.linalg.norm(normal)
+    d_plane = rng.uniform(3.0, 4.0)
+    while len(pts1) < n_matches:
+        u, v = rng.uniform(16, w - 16), rng.uniform(16, h - 16)
+        if kind == "planar" and np.hypot(u - cx, v - cy) < 140:
+            continue   # the decomposition's second solution translates along the plane normal: its epipole is near the centre
+        ray = np.array([(u - cx) / fx, (v - cy) / fy, 1.0])
+        z = -d_plane / (normal @ ray) if kind == "planar" else rng.uniform(2.0, 8.0)
+        X2 = R @ (ray * z) + t
+        if z <= 0.5 or X2[2] <= 0.5:
+            continue
+        u2, v2 = fx * X2[0] / X2[2] + cx, fy * X2[1] / X2[2] + cy
+        if not (16 <= u2 < w - 16 and 16 <= v2 < h - 16):
+            continue
+        pts1.append((u, v))
+        pts2.append((u2, v2))
+    pts1, pts2 = np.array(pts1), np.array(pts2)
+    if kind == "static":
+        pts2 = pts1.copy()
+    elif noise > 0:
+        pts1 = pts1 + rng.normal(0, noise, pts1.shape)
+        pts2 = pts2 + rng.normal(0, noise, pts2.shape)
+    outlier = np.zeros(n_matches, bool)
+    n_out = int(round(outlier_frac * n_matches))
+    if n_out:
+        outlier[rng.choice(n_matches, n_out, replace=False)] = True
+        pts2[outlier] = np.stack([rng.uniform(16, w - 16, n_out), rng.uniform(16, h - 16, n_out)], 1)
+    # the matched keys interleaved with the unmatched ones: slot[i] = where match i's key sits in its frame
+    n_keys = n_matches + n_extra
+    slot1, slot2 = np.sort(rng.choice(n_keys, n_matches, replace=False)), rng.permutation(n_keys)[:n_matches]
+    keys1 = np.stack([rng.uniform(16, w - 16, n_keys), rng.uniform(16, h - 16, n_keys)], 1)
+    keys2 = np.stack([rng.uniform(16, w - 16, n_keys), rng.uniform(16, h - 16, n_keys)], 1)
+    keys1[slot1], keys2[slot2] = pts1, pts2
+    if kind == "static":
+        keys2 = keys1.copy()
+        slot2 = slot1.copy()
+    matches = np.stack([slot1, slot2], 1).astype(np.int32)
+    sets = np.zeros((iterations, 8), np.int32)
+    for it in range(iterations):
+        avail = list(range(n_matches))
+        for j in range(8):
+            r = int((float(rng.integers(0, 2 ** 31)) / 2147483648.0) * len(avail))   # RandomInt(0, size - 1)
+            sets[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    tn = np.linalg.norm(t)
+    return dict(kind=kind, keys1=keys1.astype(np.float32), keys2=keys2.astype(np.float32), matches=matches, sets=sets, K=TWO_VIEW_K,
+                sigma=1.0, min_parallax=1.0, min_triangulated=50, R21=R, t21=t / tn if tn > 0 else t, outlier=outlier)

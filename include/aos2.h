@@ -615,6 +615,49 @@ typedef struct {
  * set.  Synchronous. */
 int aos2_pnp_ransac(aos2_matcher_t *m, const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems);
 
+/* Initializer::Initialize (src/Initializer.cc:44-121) for a batch of monocular sequences, behind SearchForInitialization of
+ * Tracking::MonocularInitialization (src/Tracking.cc:695, :709): Normalize over all keys of both frames, the homography and the
+ * fundamental matrix of every minimal set (ComputeH21 / ComputeF21), CheckHomography / CheckFundamental of each over every match,
+ * the pick of the best of each, RH = SH / (SH + SF), then ReconstructH (eight hypotheses) or ReconstructF (four) with CheckRT of
+ * every hypothesis over every inlier.  The minimal sets are an input (mvSets), so every hypothesis is independent.  The arithmetic
+ * is csrc/initializer.h. */
+#define AOS2_INIT_OK 0
+#define AOS2_INIT_NO_MODEL 1         /* no hypothesis of the chosen model scored above 0: the reference's next cv::Mat product asserts */
+typedef struct {
+    int32_t n_keys1, n_keys2;        /* mvKeys1.size(), mvKeys2.size() */
+    const float *keys1, *keys2;      /* host [n_keys][2]: mvKeysUn[i].pt of the reference and the current frame */
+    int32_t n_matches;               /* mvMatches12.size(), >= 8 */
+    const int32_t *matches;          /* host [n_matches][2]: (first, second) in mvMatches12 order */
+    float sigma;                     /* mSigma (1.0) */
+    int32_t iterations;              /* mMaxIterations (200) */
+    const int32_t *sets;             /* host [iterations][8]: mvSets, indices into matches */
+    float fx, fy, cx, cy;            /* mK */
+    float min_parallax;              /* 1.0 (:116, :118) */
+    int32_t min_triangulated;        /* 50 */
+} aos2_initializer_problem_t;
+typedef struct {
+    int32_t status;                  /* AOS2_INIT_OK or AOS2_INIT_NO_MODEL (then everything below the scores is zero) */
+    int32_t initialized;             /* what Initialize() returns */
+    int32_t used_homography;         /* RH > 0.40 */
+    float SH, SF;
+    float H21[9], F21[9];            /* the winners (zeros without one) */
+    int32_t best_iteration_h, best_iteration_f;   /* the iterations that set them, -1 without one */
+    uint8_t *inliers_h, *inliers_f;  /* host [n_matches], caller-allocated: vbMatchesInliersH / F */
+    float R21[9], t21[3];            /* zeros unless initialized (the reference leaves empty Mats) */
+    float *P3D;                      /* host [n_keys1][3], caller-allocated: vP3D; rows that are not written are zero */
+    uint8_t *triangulated;           /* host [n_keys1], caller-allocated: vbTriangulated */
+    int32_t n_good[8];               /* nGood of CheckRT per hypothesis, in the reference's order */
+    float parallax[8];               /* its parallax in degrees */
+    int32_t n_hypotheses;            /* 8 (ReconstructH), 4 (ReconstructF), 0: ReconstructH left at d1/d2 < 1.00001, or no model */
+} aos2_initializer_result_t;
+/* n_problems <= 64; n_problems == 0 is AOS2_OK.  Checked before anything runs, AOS2_ERR_ARG with no result byte written: a NULL,
+ * n_matches < 8, a match index outside its frame, a set entry outside [0, n_matches), iterations < 1, sigma <= 0 (or NaN).
+ * Degenerate input is no error: a set that repeats a match, collinear points, a static camera give NaN or zero scores that never
+ * win the pick; when that leaves the chosen model without a matrix, status = AOS2_INIT_NO_MODEL and initialized = 0.  A result is
+ * a function of its problem alone: the same bytes whatever else is in the batch.  Synchronous. */
+int aos2_initializer_initialize(aos2_matcher_t *m, const aos2_initializer_problem_t *problems, aos2_initializer_result_t *results,
+                                int n_problems);
+
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*>
  *         &sAlreadyFound, const float th, const int ORBdist)  :1472-1599 (relocalisation).
  * Points = pKF->GetMapPointMatches() (valid = pMP && !isBad() && !sAlreadyFound.count(pMP));
@@ -1091,6 +1134,18 @@ int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices)
  * refined [n_iterations] = the inlier count Refine() finds on the set of that iteration, refined_carried that of the carried-in set */
 int aos2_debug_pnp_scan(int first_iteration, int n_iterations, const int32_t *counts, const int32_t *refined, int32_t refined_carried,
                         int min_inliers, int best_inliers_in, int32_t *returned_at, int32_t *best_iteration, int32_t *best_inliers);
+/* aos2_initializer_initialize on the HOST with the routines the device kernels also run (csrc/initializer.h), serially; needs no
+ * device */
+int aos2_debug_initializer_host(const aos2_initializer_problem_t *problems, aos2_initializer_result_t *results, int n_problems);
+/* cv::SVDecomp(A, w, u, vt, FULL_UV) of a float rows x cols matrix as csrc/initializer.h runs it (16x9, 8x9, 3x3; rows <= 16,
+ * cols <= 9, and rows >= cols or rows + 1 == cols).  The Jacobi works on n rows of length m: (n, m) = (cols, rows) for a tall or
+ * square matrix (At = A^T), (rows, cols) for a wide one (A itself).  left [n1][m] = the rows after the tail loop (n1 = n, or cols
+ * for a wide matrix: its last row is the completion vector), w [n], right [n][n] = the accumulated rotations. */
+int aos2_debug_initializer_svd(const float *A, int rows, int cols, float *left, float *w, float *right);
+/* the first n values of cv::RNG(0x12345678).next() as csrc/initializer.h generates them */
+int aos2_debug_initializer_rng(int n, uint32_t *out);
+/* cv::Mat::inv() and cv::determinant of a float 3x3 (row-major) */
+int aos2_debug_initializer_inv33(const float *S, float *inv, double *det);
 /* aos2_optimize_sim3 on the HOST: the same header (csrc/sim3_opt.h) run serially, edges summed in index order; needs no device */
 int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
