@@ -78,6 +78,20 @@ struct LmState {
 // k_ldlt_dev (in place in device memory, any size)
 enum LdltForm : int { kLdltDev = 0, kLdltReg = 2 };
 
+// What the one-thread-per-landmark kernels need of an edge before they can go to its keyframe, packed and kept in the order of the
+// landmarks' edge lists (position a of LbaWin::pt_k: a landmark's records are neighbours): two 16-byte loads in place of the
+// index pt_k[a] and, behind it, eight scattered loads of the per-edge arrays.  Copies: the per-edge arrays stay what every other
+// kernel reads.  k_prepare builds the records, k_transition keeps the flags in step with e_robust / e_level1.
+struct EdgeRec {
+    float obs[3], w;   // in_obs, in_w of the edge
+    int32_t pose;      // e_pose
+    int32_t pl_pos;    // pl_pos
+    uint32_t flags;    // kEdgeStereo | kEdgeRobust | kEdgeLevel1
+    uint32_t pad_;
+};
+static_assert(sizeof(EdgeRec) == 32, "an edge record is two 16-byte loads");
+constexpr uint32_t kEdgeStereo = 1, kEdgeRobust = 2, kEdgeLevel1 = 4;
+
 // device-side view of one window
 struct LbaWin {
     int n_poses, n_points, n_edges, np, nl, n_items;
@@ -117,7 +131,7 @@ struct LbaWin {
     double *scal;                    // [3] solve ok
     double *part;                    // per-landmark sums of k_points: chi2 terms [0, nl), scale terms [nl, 2 nl)
     int n_part;                      // workgroups of a k_points launch for this window
-    double *ldlt;                    // (unused: 8 bytes of the arena per window)
+    EdgeRec *erec;                   // per position of pt_k: the edge's record (the walk layout's kernels)
     int npad;                        // 6 np rounded up to a multiple of 16
     LdltForm ldlt_form;
     int hs_ld;                       // leading dimension of Hs: always npad now (both forms take the padded matrix)
@@ -138,6 +152,22 @@ struct SchurTask {
     int32_t w;      // window (-1: padding)
     int32_t code;   // k_schur: kind << 28 | argument; k_lin: kind << 28 | block; k_points: block
 };
+
+// an edge record as its two 16-byte halves: {obs[3], w} and {pose, pl_pos, flags, -}
+typedef float flt4_t __attribute__((ext_vector_type(4)));
+typedef int int4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void erec_load(const LbaWin &W, int a, flt4_t &lo, int4_t &hi)
+{
+    const EdgeRec *r = W.erec + a;
+    lo = *reinterpret_cast<const flt4_t *>(r);
+    hi = *(reinterpret_cast<const int4_t *>(r) + 1);
+}
+__device__ __forceinline__ void erec_store(const LbaWin &W, int a, flt4_t lo, int4_t hi)
+{
+    EdgeRec *r = W.erec + a;
+    *reinterpret_cast<flt4_t *>(r) = lo;
+    *(reinterpret_cast<int4_t *>(r) + 1) = hi;
+}
 
 // bool SparseOptimizer::terminate(): counts the evaluation, latches the flag
 // `seen` >= 0: the value of the flag read by the caller shortly before (the word lives in host memory: a read is a PCIe
@@ -203,6 +233,11 @@ __global__ __launch_bounds__(256) void k_prepare(const LbaWin *__restrict__ wins
         for (int d = 0; d < 3; ++d) W.err[3 * (size_t)i + d] = 0.0;
         W.e_robust[i] = 1;
         W.e_level1[i] = 0;
+        // the record of position i of the landmarks' edge lists (every edge is in the list once)
+        const int k = W.pt_k[i];
+        const flt4_t lo = {W.in_obs[3 * (size_t)k], W.in_obs[3 * (size_t)k + 1], W.in_obs[3 * (size_t)k + 2], W.in_w[k]};
+        const int4_t hi = {W.e_pose[k], W.pl_pos[k], (int)((W.e_stereo[k] ? kEdgeStereo : 0) | kEdgeRobust), 0};
+        erec_store(W, i, lo, hi);
     }
     if (blockIdx.x == 0 && W.hs_ld == W.npad) {   // reduced system stored padded (k_ldlt_reg, k_ldlt_dev): the identity tail of the matrix, once
         const int n = 6 * W.np, npad = W.npad;
@@ -680,107 +715,140 @@ __global__ __launch_bounds__(256) void k_points(const LbaWin *__restrict__ wins,
     if (solve) points_tail<256>(W);
 }
 
+// The keyframe state of the window a landmark workgroup of the walks belongs to, staged in LDS: the poses (7 doubles each) and, for a
+// trial's back-substitution, the update x (6) and the linearisation's rotation Rl (9) of every free keyframe -- at most ~80 keyframes
+// that every edge of the workgroup's landmarks gathers from.  The last level of the walks' dependent gathers then reads LDS.
+// A window whose state is larger than kWalkLdsBytes reads device memory as before (a choice per workgroup; both from one body).
+// 16 KB per workgroup: with 12 waves per compute unit (three per SIMD) that is 3 workgroups of k_lin / 6 of k_points_walk, 48 / 96 of
+// the unit's 160 KB -- the registers bound the residency, not the LDS.
+constexpr int kWalkLdsBytes = 16 * 1024;
+extern __shared__ double walk_sm[];   // the dynamic LDS of k_points_walk and k_lin<true>
+__host__ __device__ constexpr int walk_lds_bytes(int n_poses, int np) { return 8 * (7 * n_poses + 15 * np); }
+__device__ __forceinline__ void walk_stage(const LbaWin &W, double *sm, bool with_x)
+{
+    const int n7 = 7 * W.n_poses, n6 = 6 * W.np, n9 = 9 * W.np;
+    for (int i = threadIdx.x; i < n7; i += blockDim.x) sm[i] = W.pose[i];
+    if (with_x) {
+        for (int i = threadIdx.x; i < n6; i += blockDim.x) sm[n7 + i] = W.x[i];
+        for (int i = threadIdx.x; i < n9; i += blockDim.x) sm[n7 + n6 + i] = W.Rl[i];
+    }
+    __syncthreads();
+}
+
 // The same work with one thread per landmark walking its edges (128-thread workgroups): the layout for many windows per
 // launch, where the landmarks alone fill the device and idle slots, barriers and LDS round trips only cost (32 windows of
 // 24 k edges: 4.4 ms against 6.4 ms).  Per landmark the operations and their order are those of k_points, so both layouts
 // leave the same bits.
+template <bool kLds>
+__device__ __forceinline__ void points_walk_body(const LbaWin &W, int l, int solve, int hp, int a0, int a1, int e0, int e1)
+{
+    const int n6 = 6 * W.np;
+    const double *s_pose = walk_sm, *s_x = walk_sm + 7 * W.n_poses, *s_Rl = s_x + n6;
+    double sc = 0, chi = 0;
+    double *X = W.point + 3 * (size_t)hp;
+    double Xv[3] = {X[0], X[1], X[2]};
+    if (solve) {
+        const double lambda = W.st->lambda;
+        double cl[3] = {W.b[n6 + 3 * l], W.b[n6 + 3 * l + 1], W.b[n6 + 3 * l + 2]};
+        // The walk is a chain of dependent gathers (edge list -> edge -> keyframe); kWalkChunk edges are fetched level by
+        // level together, then their terms are added in edge order (the same sums, a quarter of the round trips).
+        for (int a = a0; a < a1; a += kWalkChunk) {
+            int ka[kWalkChunk], i1[kWalkChunk];   // (positions in the list = the indices of the dense Hpl array)
+#pragma unroll
+            for (int u = 0; u < kWalkChunk; ++u) ka[u] = min(a + u, a1 - 1);
+#pragma unroll
+            for (int u = 0; u < kWalkChunk; ++u) i1[u] = W.pl_ph[ka[u]];
+            dbl4_t rec[kWalkChunk];
+            double xp[kWalkChunk][6], Rr[kWalkChunk][9];
+#pragma unroll
+            for (int u = 0; u < kWalkChunk; ++u) rec[u] = lrec_load(W, ka[u]);
+#pragma unroll
+            for (int u = 0; u < kWalkChunk; ++u) {
+#pragma unroll
+                for (int r = 0; r < 6; ++r) xp[u][r] = -(kLds ? s_x[6 * i1[u] + r] : W.x[6 * i1[u] + r]);
+#pragma unroll
+                for (int i = 0; i < 9; ++i) Rr[u][i] = kLds ? s_Rl[9 * i1[u] + i] : W.Rl[9 * (size_t)i1[u] + i];
+            }
+#pragma unroll
+            for (int u = 0; u < kWalkChunk; ++u) {
+                if (a + u >= a1) break;
+                double v[3];
+                lrec_backsub(W.cam, rec[u], Rr[u], xp[u], v);
+                for (int c = 0; c < 3; ++c) cl[c] += v[c];
+            }
+        }
+        double Dm[9], Dinv[9];
+        for (int i = 0; i < 9; ++i) Dm[i] = W.Hll[9 * (size_t)l + i];
+        Dm[0] += lambda; Dm[4] += lambda; Dm[8] += lambda;
+        mat3_inverse(Dm, Dinv);
+        double *Xb = W.bk + 7 * (size_t)W.n_poses + 3 * (size_t)hp;
+        for (int r = 0; r < 3; ++r) {
+            const double xl = Dinv[r * 3] * cl[0] + Dinv[r * 3 + 1] * cl[1] + Dinv[r * 3 + 2] * cl[2];
+            W.x[n6 + 3 * l + r] = xl;
+            store_dev(Xb + r, Xv[r]);   // push()
+            Xv[r] += xl;
+            store_dev(X + r, Xv[r]);
+            sc += xl * (lambda * xl + W.b[n6 + 3 * l + r]);
+        }
+    }
+    for (int a = e0; a < e1; a += kWalkChunkE) {
+        // the edges' records lie at their positions in the list (EdgeRec): one level of loads, then the keyframes
+        flt4_t lo[kWalkChunkE];
+        int4_t hi[kWalkChunkE];
+        double T[kWalkChunkE][7];
+#pragma unroll
+        for (int u = 0; u < kWalkChunkE; ++u) erec_load(W, min(a + u, e1 - 1), lo[u], hi[u]);
+#pragma unroll
+        for (int u = 0; u < kWalkChunkE; ++u)
+#pragma unroll
+            for (int i = 0; i < 7; ++i) T[u][i] = kLds ? s_pose[7 * hi[u].x + i] : W.pose[7 * (size_t)hi[u].x + i];
+#pragma unroll
+        for (int u = 0; u < kWalkChunkE; ++u) {
+            if (a + u >= e1) break;
+            const uint32_t fl = (uint32_t)hi[u].z;
+            if (fl & kEdgeLevel1) continue;   // an inactive edge keeps its _error
+            double p[3], er[3];
+            se3_map(T[u], Xv, p);
+            const int stereo = fl & kEdgeStereo;
+            const double ob[3] = {(double)lo[u].x, (double)lo[u].y, (double)lo[u].z};
+            edge_error(W.cam, p, ob, stereo, er);   // (_error is not stored: LmState::err_at)
+            double c = edge_chi2(er, (double)lo[u].w, stereo ? 3 : 2);
+            if (fl & kEdgeRobust) {
+                double rho[2];
+                robustify(c, stereo ? W.cam.delta_stereo : W.cam.delta_mono, rho);
+                c = rho[0];
+            }
+            chi += c;
+        }
+    }
+    store_dev(W.part + l, chi);
+    store_dev(W.part + W.nl + l, sc);
+}
+
 __global__ __launch_bounds__(128) void k_points_walk(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks, int solve)
 {
     const SchurTask tk = tasks[blockIdx.x];
     const LbaWin &W = wins[tk.w];
     if (!(solve ? W.st->run : W.st->initp)) return;
     const int l = tk.code * blockDim.x + threadIdx.x;
-    const int n6 = 6 * W.np;
-    if (l < W.nl) {
-        double sc = 0, chi = 0;
-        double *X = W.point + 3 * (size_t)W.hpoint[l];
-        double Xv[3] = {X[0], X[1], X[2]};
+    const bool has = l < W.nl;
+    // the landmark's first-level loads are requested before the keyframe state is staged: they travel together
+    int hp = 0, a0 = 0, a1 = 0, e0 = 0, e1 = 0;
+    if (has) {
+        hp = W.hpoint[l];
+        e0 = W.pt_off[l];
+        e1 = W.pt_off[l + 1];
         if (solve) {
-            const double lambda = W.st->lambda;
-            double cl[3] = {W.b[n6 + 3 * l], W.b[n6 + 3 * l + 1], W.b[n6 + 3 * l + 2]};
-            // The walk is a chain of dependent gathers (edge list -> edge -> keyframe); kWalkChunk edges are fetched level by
-            // level together, then their terms are added in edge order (the same sums, a quarter of the round trips).
-            const int a0 = W.pl_off[l], a1 = W.pl_off[l + 1];
-            for (int a = a0; a < a1; a += kWalkChunk) {
-                int ka[kWalkChunk], i1[kWalkChunk];   // (positions in the list = the indices of the dense Hpl array)
-#pragma unroll
-                for (int u = 0; u < kWalkChunk; ++u) ka[u] = min(a + u, a1 - 1);
-#pragma unroll
-                for (int u = 0; u < kWalkChunk; ++u) i1[u] = W.pl_ph[ka[u]];
-                dbl4_t rec[kWalkChunk];
-                double xp[kWalkChunk][6], Rr[kWalkChunk][9];
-#pragma unroll
-                for (int u = 0; u < kWalkChunk; ++u) rec[u] = lrec_load(W, ka[u]);
-#pragma unroll
-                for (int u = 0; u < kWalkChunk; ++u) {
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) xp[u][r] = -W.x[6 * i1[u] + r];
-#pragma unroll
-                    for (int i = 0; i < 9; ++i) Rr[u][i] = W.Rl[9 * (size_t)i1[u] + i];
-                }
-#pragma unroll
-                for (int u = 0; u < kWalkChunk; ++u) {
-                    if (a + u >= a1) break;
-                    double v[3];
-                    lrec_backsub(W.cam, rec[u], Rr[u], xp[u], v);
-                    for (int c = 0; c < 3; ++c) cl[c] += v[c];
-                }
-            }
-            double Dm[9], Dinv[9];
-            for (int i = 0; i < 9; ++i) Dm[i] = W.Hll[9 * (size_t)l + i];
-            Dm[0] += lambda; Dm[4] += lambda; Dm[8] += lambda;
-            mat3_inverse(Dm, Dinv);
-            double *Xb = W.bk + 7 * (size_t)W.n_poses + 3 * (size_t)W.hpoint[l];
-            for (int r = 0; r < 3; ++r) {
-                const double xl = Dinv[r * 3] * cl[0] + Dinv[r * 3 + 1] * cl[1] + Dinv[r * 3 + 2] * cl[2];
-                W.x[n6 + 3 * l + r] = xl;
-                store_dev(Xb + r, Xv[r]);   // push()
-                Xv[r] += xl;
-                store_dev(X + r, Xv[r]);
-                sc += xl * (lambda * xl + W.b[n6 + 3 * l + r]);
-            }
+            a0 = W.pl_off[l];
+            a1 = W.pl_off[l + 1];
         }
-        const int e0 = W.pt_off[l], e1 = W.pt_off[l + 1];
-        for (int a = e0; a < e1; a += kWalkChunkE) {
-            int e[kWalkChunkE], ep[kWalkChunkE];
-            uint8_t lv1[kWalkChunkE], ste[kWalkChunkE], rob[kWalkChunkE];
-            double T[kWalkChunkE][7], ob[kWalkChunkE][3], ew[kWalkChunkE];
-#pragma unroll
-            for (int u = 0; u < kWalkChunkE; ++u) e[u] = W.pt_k[min(a + u, e1 - 1)];
-#pragma unroll
-            for (int u = 0; u < kWalkChunkE; ++u) {
-                ep[u] = W.e_pose[e[u]];
-                lv1[u] = W.e_level1[e[u]];
-                ste[u] = W.e_stereo[e[u]];
-                rob[u] = W.e_robust[e[u]];
-                ew[u] = (double)W.in_w[e[u]];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) ob[u][i] = (double)W.in_obs[3 * (size_t)e[u] + i];
-            }
-#pragma unroll
-            for (int u = 0; u < kWalkChunkE; ++u)
-#pragma unroll
-                for (int i = 0; i < 7; ++i) T[u][i] = W.pose[7 * (size_t)ep[u] + i];
-#pragma unroll
-            for (int u = 0; u < kWalkChunkE; ++u) {
-                if (a + u >= e1) break;
-                if (lv1[u]) continue;   // an inactive edge keeps its _error
-                double p[3], er[3];
-                se3_map(T[u], Xv, p);
-                const int stereo = ste[u];
-                edge_error(W.cam, p, ob[u], stereo, er);   // (_error is not stored: LmState::err_at)
-                double c = edge_chi2(er, ew[u], stereo ? 3 : 2);
-                if (rob[u]) {
-                    double rho[2];
-                    robustify(c, stereo ? W.cam.delta_stereo : W.cam.delta_mono, rho);
-                    c = rho[0];
-                }
-                chi += c;
-            }
-        }
-        store_dev(W.part + l, chi);
-        store_dev(W.part + W.nl + l, sc);
     }
+    const bool lds = walk_lds_bytes(W.n_poses, W.np) <= kWalkLdsBytes;   // (the same for every thread of the workgroup)
+    if (lds) {
+        walk_stage(W, walk_sm, solve != 0);
+        if (has) points_walk_body<true>(W, l, solve, hp, a0, a1, e0, e1);
+    } else if (has)
+        points_walk_body<false>(W, l, solve, hp, a0, a1, e0, e1);
     if (solve) points_tail<128>(W);
 }
 
@@ -876,40 +944,32 @@ __device__ __forceinline__ void lin_points_body(const LbaWin &W, int blk)
 
 // the same with one thread per landmark walking its edges (see k_points_walk); the per-edge terms are formed and added in
 // the same order, so Hll, b_l and Hpl carry the same bits
+template <bool kLds>
 __device__ __forceinline__ void lin_points_walk(const LbaWin &W, int l)
 {
-    if (l >= W.nl) return;
+    const double *s_pose = walk_sm;
+    const int e0 = W.pt_off[l], e1 = W.pt_off[l + 1];
     const double *X = W.point + 3 * (size_t)W.hpoint[l];
     const double Xv[3] = {X[0], X[1], X[2]};
     double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
-    const int e0 = W.pt_off[l], e1 = W.pt_off[l + 1];
     for (int a = e0; a < e1; a += kWalkChunkLin) {
         // kWalkChunkLin edges fetched level by level together (see k_points_walk), linearised and added in edge order
-        int kk[kWalkChunkLin], ep[kWalkChunkLin], ph[kWalkChunkLin];
-        uint8_t lv1[kWalkChunkLin], ste[kWalkChunkLin], rob[kWalkChunkLin];
-        double T[kWalkChunkLin][7], er[kWalkChunkLin][3], ew[kWalkChunkLin];
+        flt4_t lo[kWalkChunkLin];
+        int4_t hi[kWalkChunkLin];
+        double T[kWalkChunkLin][7];
 #pragma unroll
-        for (int u = 0; u < kWalkChunkLin; ++u) kk[u] = W.pt_k[min(a + u, e1 - 1)];
-#pragma unroll
-        for (int u = 0; u < kWalkChunkLin; ++u) {
-            ep[u] = W.e_pose[kk[u]];
-            ph[u] = W.pl_pos[kk[u]];
-            lv1[u] = W.e_level1[kk[u]];
-            ste[u] = W.e_stereo[kk[u]];
-            rob[u] = W.e_robust[kk[u]];
-            ew[u] = (double)W.in_w[kk[u]];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) er[u][i] = (double)W.in_obs[3 * (size_t)kk[u] + i];   // (the observation; the residual is re-formed below)
-        }
+        for (int u = 0; u < kWalkChunkLin; ++u) erec_load(W, min(a + u, e1 - 1), lo[u], hi[u]);
 #pragma unroll
         for (int u = 0; u < kWalkChunkLin; ++u)
 #pragma unroll
-            for (int i = 0; i < 7; ++i) T[u][i] = W.pose[7 * (size_t)ep[u] + i];
+            for (int i = 0; i < 7; ++i) T[u][i] = kLds ? s_pose[7 * hi[u].x + i] : W.pose[7 * (size_t)hi[u].x + i];
 #pragma unroll
         for (int u = 0; u < kWalkChunkLin; ++u) {
             if (a + u >= e1) break;
-            if (lv1[u]) continue;
-            const int stereo = ste[u];
+            const uint32_t fl = (uint32_t)hi[u].z;
+            if (fl & kEdgeLevel1) continue;
+            const int stereo = fl & kEdgeStereo;
+            const double ob[3] = {(double)lo[u].x, (double)lo[u].y, (double)lo[u].z};   // (the observation; the residual is re-formed below)
             double p[3], R[9];
             se3_map(T[u], Xv, p);
             rot_from_quat(T[u], R);
@@ -917,17 +977,20 @@ __device__ __forceinline__ void lin_points_walk(const LbaWin &W, int l)
             jac_point(W.cam, R, p, stereo, Ja);
             double omr[3], wo;
             double res[3];
-            edge_error(W.cam, p, er[u], stereo, res);
-            edge_weights_of(W.cam, res, ew[u], rob[u], stereo, omr, wo);
+            edge_error(W.cam, p, ob, stereo, res);
+            edge_weights_of(W.cam, res, (double)lo[u].w, (fl & kEdgeRobust) != 0, stereo, omr, wo);
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 bl[r] += Ja[r] * omr[0] + Ja[3 + r] * omr[1] + Ja[6 + r] * omr[2];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) H[r * 3 + c] += Ja[r] * wo * Ja[c] + Ja[3 + r] * wo * Ja[3 + c] + Ja[6 + r] * wo * Ja[6 + c];
             }
-            if (ph[u] >= 0) lrec_store(W, ph[u], p, wo, stereo, omr);
+            if (hi[u].y >= 0) lrec_store(W, hi[u].y, p, wo, stereo, omr);
         }
     }
+    // (the addresses below are formed here, from the index alone: formed ahead of the loop -- for both forms of the body at once -- they
+    // hold two registers across it, which at this kernel's 168 registers for three waves per SIMD is 12 bytes of scratch: tools/lba_kernel_resources.py)
+    asm volatile("" : "+v"(l));
     for (int i = 0; i < 9; ++i) W.Hll[9 * (size_t)l + i] = H[i];
     for (int i = 0; i < 3; ++i) W.b[6 * (size_t)W.np + 3 * (size_t)l + i] = bl[i];
 }
@@ -1006,8 +1069,8 @@ __device__ __forceinline__ void lin_poses_body(const LbaWin &W, int ph, int init
 // workgroups of ALL windows start before any keyframe workgroup: their walks are the long
 // dependent chains of the launch (33 of its 54 us on 32 windows when they queued behind the keyframe workgroups of the
 // windows before them), the keyframe workgroups fill in behind.
-// (three waves per SIMD: 174 -> 168 registers for 12 bytes of scratch per lane; the walk moves scattered bytes and gains from the third
-// wave: 36.2 -> 34.4 us on 32 windows.  k_points_walk, 172 registers, does not: 34.2 -> 35.0 us, left at two.)
+// (three waves per SIMD, asked for: the walk gained from the third wave, 36.2 -> 34.4 us on 32 windows.  168 registers, no scratch; k_points_walk
+// reaches three waves unasked, at 166.  What keeps both at that limit depends on the register allocator: tools/lba_kernel_resources.py checks it.)
 template <bool kWalk>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_lin(const LbaWin *__restrict__ wins, const SchurTask *__restrict__ tasks, int init)
 {
@@ -1018,9 +1081,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const bool keyframe = (tk.code >> 28) != 0;
     if (keyframe)
         lin_poses_body(W, blk, init);
-    else if (kWalk)
-        lin_points_walk(W, blk * 256 + threadIdx.x);
-    else
+    else if (kWalk) {
+        const int l = blk * 256 + threadIdx.x;
+        const bool has = l < W.nl;
+        // (the landmark's own first loads are not requested ahead of the staging as in k_points_walk: the three registers they hold across
+        // it cost this kernel 20 bytes of scratch)
+        if (walk_lds_bytes(W.n_poses, W.np) <= kWalkLdsBytes) {
+            walk_stage(W, walk_sm, false);
+            if (has) lin_points_walk<true>(W, l);
+        } else if (has)
+            lin_points_walk<false>(W, l);
+    } else
         lin_points_body(W, blk);
 }
 
@@ -1710,9 +1781,12 @@ __global__ __launch_bounds__(256) void k_transition(const LbaWin *__restrict__ w
     LmState *st = W.st;
     if (!st->xmark) return;
     const int err_at = st->err_at;   // (reset by the workgroup that finishes last: after every workgroup's read)
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    // (a thread takes the edge at its position of the landmarks' edge lists -- every edge is there once --, so that it can keep the
+    // position's record in step)
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
     int keep = 0;
-    if (e < W.n_edges) {
+    if (a < W.n_edges) {
+        const int e = W.pt_k[a];
         const int stereo = W.e_stereo[e];
         double p[3], er[3];
         se3_map(W.pose + 7 * (size_t)W.e_pose[e], W.point + 3 * (size_t)W.e_point[e], p);
@@ -1725,6 +1799,7 @@ __global__ __launch_bounds__(256) void k_transition(const LbaWin *__restrict__ w
             if (pp >= 0) lrec_mask(W, pp);
         }
         W.e_robust[e] = 0;
+        W.erec[a].flags = (W.erec[a].flags & ~kEdgeRobust) | (bad ? kEdgeLevel1 : 0);
         keep = bad ? 0 : 1;
     }
     const unsigned long long m = __ballot(keep);
@@ -2079,7 +2154,7 @@ struct WinLayout {
     size_t in_Tcw, in_xyz, in_obs, in_w, e_pose, e_point, e_stereo, pl_pos, hpose, hpoint, pt_off, pt_k, ps_off, ps_k,
         pl_off, pl_k, it_ka, it_kb, it_l, blk_off, sr_o0, sr_info, sr_ij;
     // device only
-    size_t est, bk, robust, level1, err, lrec, lomr, Rl, Hpp, Hll, b, x, Hs, bs, tmp, scal, part, ldlt;
+    size_t est, bk, robust, level1, err, lrec, lomr, Rl, Hpp, Hll, b, x, Hs, bs, tmp, scal, part, erec;
     // results (downloaded)
     size_t out_Tcw, out_xyz, out_outlier, out_chi2, st;
     int n_part, npad;
@@ -2239,7 +2314,7 @@ static void layout_scratch(const aos2_lba_problem_t &p, const Pass &S, const LmL
     l.tmp = B.take(8 * n6 + 8);
     l.n_part = lay.points_blocks(S);
     l.scal = B.take(64); l.part = B.take(16 * (size_t)std::max(S.nl, 1) + 8);
-    l.ldlt = B.take(8);
+    l.erec = B.take(sizeof(EdgeRec) * (E + 1));
 }
 
 // the regions that come back in one copy: the window's state, then its results
@@ -2284,7 +2359,7 @@ static void describe_window(LbaWin &W, uint8_t *base, const aos2_lba_problem_t &
     W.Hs = (double *)(base + l.Hs); W.bs = (double *)(base + l.bs);
     W.tmp = (double *)(base + l.tmp); W.scal = (double *)(base + l.scal); W.part = (double *)(base + l.part);
     W.n_part = l.n_part;
-    W.ldlt = (double *)(base + l.ldlt); W.npad = l.npad; W.ldlt_form = l.ldlt_form;
+    W.erec = (EdgeRec *)(base + l.erec); W.npad = l.npad; W.ldlt_form = l.ldlt_form;
     W.hs_ld = l.npad;
     W.st = (LmState *)(base + l.st);
     W.abort_word = abort_word;
@@ -2299,6 +2374,7 @@ static void describe_window(LbaWin &W, uint8_t *base, const aos2_lba_problem_t &
 struct GroupDims {
     bool any_glob = false, any_reg = false;
     int mx_E = 0, mx_pts = 0, mx_npad_glob = 0, mx_npad_reg = 0;
+    int walk_lds = 0;   // dynamic LDS of the walks: the largest keyframe state among the windows that stage it (walk_lds_bytes)
     void add(const aos2_lba_problem_t &p, const Pass &S, const WinLayout &l)
     {
         if (S.np > 0) {
@@ -2312,6 +2388,7 @@ struct GroupDims {
         }
         mx_E = std::max(mx_E, p.n_edges);
         mx_pts = std::max(mx_pts, std::max(p.n_points, p.n_poses));
+        if (walk_lds_bytes(p.n_poses, S.np) <= kWalkLdsBytes) walk_lds = std::max(walk_lds, walk_lds_bytes(p.n_poses, S.np));
     }
 };
 
@@ -2440,7 +2517,7 @@ static unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
 static void enqueue_points(const LaunchCtx &C, const Prog &P, int solve)
 {
     if (C.walk)
-        hipLaunchKernelGGL(k_points_walk, dim3((unsigned)P.n_pts), dim3(128), 0, P.q, P.wins, P.pts, solve);
+        hipLaunchKernelGGL(k_points_walk, dim3((unsigned)P.n_pts), dim3(128), (size_t)P.D.walk_lds, P.q, P.wins, P.pts, solve);
     else
         hipLaunchKernelGGL(k_points, dim3((unsigned)P.n_pts), dim3(256), 0, P.q, P.wins, P.pts, solve);
 }
@@ -2448,7 +2525,7 @@ static void enqueue_lin(const LaunchCtx &C, const Prog &P, int init)
 {
     if (!P.n_lin) return;
     if (C.walk)
-        hipLaunchKernelGGL(k_lin<true>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
+        hipLaunchKernelGGL(k_lin<true>, dim3((unsigned)P.n_lin), dim3(256), (size_t)P.D.walk_lds, P.q, P.wins, P.lin, init);
     else
         hipLaunchKernelGGL(k_lin<false>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
 }
