@@ -77,6 +77,7 @@ public:
     }
 
     aos2_vocabulary_t *handle() { return h_; }
+    const aos2_vocabulary_t *handle() const { return h_; }
 
 private:
     aos2_vocabulary_t *h_ = nullptr;

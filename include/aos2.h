@@ -292,6 +292,88 @@ int aos2_vocabulary_score(const aos2_vocabulary_t *v, const uint32_t *w1, const 
                           const uint32_t *w2, const double *v2, int n2, double *score);
 
 /* ------------------------------------------------------------------------------------------
+ * KeyFrameDatabase  (include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc)
+ * The step in front of Tracking::Relocalization (src/Tracking.cc:1528) and LoopClosing::ComputeSim3 (src/LoopClosing.cc:143):
+ * which keyframes they work on.  A database holds SLOTS: a slot is a keyframe's BowVector (word ids ascending, double values)
+ * resident in HBM.  A slot is PUT when the keyframe gets its BowVector, ADDED by add(), ERASED by erase() (it leaves the
+ * queries and keeps its BowVector) and DROPPED when its row is freed.  There is no limit on keyframes or on words per keyframe.
+ * DESIGN.md section 2 item 13 (reloc_score, "shares a word"), section 4 (layout), section 5 (kernels).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aos2_kfdb aos2_kfdb_t;
+#define AOS2_KFDB_LOOP 0          /* DetectLoopCandidates           src/KeyFrameDatabase.cc:76-197 */
+#define AOS2_KFDB_RELOC 1         /* DetectRelocalizationCandidates :199-309 */
+#define AOS2_KFDB_NEIGHBOURS 10   /* GetBestCovisibilityKeyFrames(10) :151, :265 */
+
+/* KeyFrameDatabase(const ORBVocabulary&) :33-37: the scoring type (only L1_NORM, as aos2_vocabulary_score; anything else is
+ * AOS2_ERR_ARG) and the word count (mvInvertedFile.resize(voc.size())) are taken from `voc`, which is not kept. */
+int aos2_kfdb_create(const aos2_vocabulary_t *voc, int device, aos2_kfdb_t **out);
+void aos2_kfdb_destroy(aos2_kfdb_t *db);
+/* pKF->mBowVec of a new keyframe (KeyFrame::ComputeBoW): n >= 0 words, ids ascending without repeats and below the vocabulary's
+ * word count (else AOS2_ERR_ARG).  *slot = the new slot; reloc_score = 0.0f, no neighbours, not added.  Needs no device. */
+int aos2_kfdb_put(aos2_kfdb_t *db, const uint32_t *words, const double *values, int n, int32_t *slot);
+/* `batch` rows as aos2_vocabulary_transform_device wrote them (d_words / d_values [batch][cap], d_n_bow [batch]), ordered behind
+ * the stream of `voc` (may be NULL: the caller has waited).  slots [batch]. */
+int aos2_kfdb_put_device(aos2_kfdb_t *db, aos2_vocabulary_t *voc, int batch, const uint32_t *d_words, const double *d_values,
+                         const int32_t *d_n_bow, int cap, int32_t *slots);
+/* add(KeyFrame*) :40-46: the slot takes the next value of a 64-bit add counter (its place in every inverted list).  Adding an
+ * added slot is AOS2_ERR_ARG (the reference never does it and would count the keyframe twice). */
+int aos2_kfdb_add(aos2_kfdb_t *db, int32_t slot);
+/* erase(KeyFrame*) :48-67; erasing a slot that is not added does nothing, as there */
+int aos2_kfdb_erase(aos2_kfdb_t *db, int32_t slot);
+/* frees the row (~KeyFrame); an added slot is erased first.  The slot number may be handed out again. */
+int aos2_kfdb_drop(aos2_kfdb_t *db, int32_t slot);
+/* clear() :69-73: un-adds everything; the slots stay put */
+int aos2_kfdb_clear(aos2_kfdb_t *db);
+int aos2_kfdb_size(const aos2_kfdb_t *db);             /* number of added slots */
+int64_t aos2_kfdb_arena_capacity(const aos2_kfdb_t *db);   /* entries the device arena holds now (0 before the first device call) */
+/* GetBestCovisibilityKeyFrames(10) of n slots: neigh [n][10] slot numbers in that order, -1 padded.  Resident: the caller
+ * refreshes the rows it changes.  A neighbour that is not put (or dropped later) takes no part. */
+int aos2_kfdb_set_neighbours(aos2_kfdb_t *db, int n, const int32_t *slots, const int32_t *neigh);
+
+typedef struct {
+    int32_t mode;             /* AOS2_KFDB_LOOP / AOS2_KFDB_RELOC */
+    int32_t slot;             /* >= 0: the query is this slot's BowVector (put is enough); < 0: words / values */
+    const uint32_t *words;    /* [n_words] ascending;  host arrays, or device arrays with on_device = 1 */
+    const double *values;
+    int32_t n_words;
+    int32_t on_device;
+    float min_score;          /* LOOP: minScore (:76) */
+    int32_t n_excluded;       /* LOOP: spConnectedKeyFrames (:78) as slots, host; entries that are not added are ignored */
+    const int32_t *excluded;
+} aos2_kfdb_query_t;
+
+typedef struct {
+    int32_t *candidates;      /* vpLoopCandidates :179-196 / vpRelocCandidates :292-308, in order; caller-allocated [cap_candidates] */
+    int32_t cap_candidates;
+    int32_t n_candidates;
+    int32_t n_sharing;        /* lKFsSharingWords.size() :107 / :224 */
+    int32_t max_common_words; /* :113-118 / :228-233 */
+    int32_t min_common_words; /* (int)(maxCommonWords * 0.8f) :120 / :235 */
+    int32_t n_scored;         /* nscores :131 / :248 */
+    int32_t n_matched;        /* lScoreAndMatch.size() :141 / :255 */
+    float best_acc_score;     /* bestAccScore :145-173 / :259-287 (its start value when nothing is matched) */
+    /* optional (NULL: not wanted), in list order.  The scored list: the slots with words > minCommonWords (:129 / :246) */
+    int32_t *scored_slot, *scored_words;
+    float *scored_score;
+    int32_t cap_scored;
+    /* the sharing list lKFsSharingWords with mnLoopWords / mnRelocWords */
+    int32_t *sharing_slot, *sharing_words;
+    int32_t cap_sharing;
+} aos2_kfdb_result_t;
+
+/* DetectLoopCandidates :76-197 / DetectRelocalizationCandidates :199-309 for nq queries in one call.  The RELOC queries of a
+ * call take effect on reloc_score (mRelocScore :250, read at :276) in index order.  nq == 0 and an empty database are AOS2_OK.
+ * AOS2_ERR_ARG (a NULL, a bad mode, a slot that is not put, a negative count or capacity, query words that do not ascend) is
+ * reported before anything runs and leaves every result byte as it was.  AOS2_ERR_CAPACITY: a list did not fit; the counts
+ * hold what is needed, the lists are filled up to their capacities, and reloc_score has been updated. */
+int aos2_kfdb_detect(aos2_kfdb_t *db, const aos2_kfdb_query_t *queries, aos2_kfdb_result_t *results, int nq);
+/* The loop of LoopClosing::DetectLoop (src/LoopClosing.cc:126-140): scores [n] = (float) score(query, slots[i]) (put is enough)
+ * and *min_score = their minimum starting from 1.  mode, min_score and excluded of the query are not read. */
+int aos2_kfdb_scores(aos2_kfdb_t *db, const aos2_kfdb_query_t *query, const int32_t *slots, int n, float *scores,
+                     float *min_score);
+float aos2_kfdb_last_device_ms(const aos2_kfdb_t *db);   /* device time of the last detect / scores call (HIP events) */
+
+/* ------------------------------------------------------------------------------------------
  * ORBmatcher  (include/ORBmatcher.h:37-102, src/ORBmatcher.cc)
  * The C++ shim snapshots the Frame / KeyFrame / MapPoint fields each method reads into the SoA
  * views below and maps the returned indices back to MapPoint*.
@@ -1128,6 +1210,12 @@ int aos2_debug_sim3_host(const aos2_sim3_problem_t *problems, aos2_sim3_result_t
 /* aos2_pnp_ransac on the HOST with the routine the device kernels also run (csrc/pnp.h), serially; needs no device.  It stops
  * computing at returned_at and calls Refine() where the loop does, memoised per best set. */
 int aos2_debug_pnp_host(const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems);
+/* aos2_kfdb_detect / aos2_kfdb_scores on the HOST with the routines the device kernels also run (csrc/kfdb.h), over a literal
+ * inverted file (mvInvertedFile: one list of slots per word, in add order), on one core; need no device unless a query's
+ * arrays are on the device.  They read and write the same reloc_score as the device calls. */
+int aos2_debug_kfdb_host(aos2_kfdb_t *db, const aos2_kfdb_query_t *queries, aos2_kfdb_result_t *results, int nq);
+int aos2_debug_kfdb_scores_host(aos2_kfdb_t *db, const aos2_kfdb_query_t *query, const int32_t *slots, int n, float *scores,
+                                float *min_score);
 /* the indices that the draws `row` [min_set] select from 0..n-1 (src/PnPsolver.cc:188-201) as csrc/pnp.h forms them -> indices */
 int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices);
 /* the loop of PnPsolver::iterate (:182-239) as csrc/pnp.h replays it over tables: counts [n_iterations] (read from first_iteration),
