@@ -1175,6 +1175,37 @@ static int check_stereo_args(const aos2_extractor *l, const aos2_extractor *r, i
     return AOS2_OK;
 }
 
+// The keypoint records the kernels may be given (aos2.h, "domain of ComputeStereoMatches"): with them the 11 x 11 left window
+// (:592) and the 11 x 21 right window (:609) stay inside mvImagePyramid[levelL] and both scale tables are indexed in range.  The
+// reference throws from rowRange / colRange at the same records.  Host arrays only: the device-resident forms state it as
+// their precondition.
+static int check_stereo_keypoints(const aos2_extractor *l, const aos2_keypoint_t *kl, int n_left, const aos2_keypoint_t *kr,
+                                  int n_right)
+{
+    const int nlevels = l->par.nlevels, rows = l->plan.levels[0].h;
+    const float *inv = l->par.mvInvScaleFactor;
+    for (int i = 0; i < n_left; ++i) {
+        const aos2_keypoint_t &k = kl[i];
+        if (k.octave < 0 || k.octave >= nlevels || !std::isfinite(k.x) || !std::isfinite(k.y))
+            return AOS2_FAIL(AOS2_ERR_ARG, "ComputeStereoMatches: left keypoint %d: octave out of range or position not finite", i);
+        const LevelDev &L = l->plan.levels[k.octave];
+        const float cu = roundf(k.x * inv[k.octave]), cv = roundf(k.y * inv[k.octave]);
+        if (!(k.y > -1.0f && k.y < (float)rows) || !(cv >= 5.0f && cv <= (float)(L.h - 6)) || !(cu >= 5.0f && cu <= (float)(L.w - 6)))
+            return AOS2_FAIL(AOS2_ERR_ARG, "ComputeStereoMatches: left keypoint %d: the 11 x 11 window leaves level %d", i, k.octave);
+    }
+    for (int i = 0; i < n_right; ++i) {
+        const aos2_keypoint_t &k = kr[i];
+        if (k.octave < 0 || k.octave >= nlevels || !std::isfinite(k.y))
+            return AOS2_FAIL(AOS2_ERR_ARG, "ComputeStereoMatches: right keypoint %d: octave out of range or y not finite", i);
+        for (int lv = std::max(k.octave - 1, 0); lv <= std::min(k.octave + 1, nlevels - 1); ++lv) {
+            const float cu = roundf(k.x * inv[lv]);   // < 0: refused by iniu (:604); >= 10: cuR0 - 10 is a column of the plane
+            if (cu >= 0.0f && cu < 10.0f)
+                return AOS2_FAIL(AOS2_ERR_ARG, "ComputeStereoMatches: right keypoint %d: the search window leaves level %d", i, lv);
+        }
+    }
+    return AOS2_OK;
+}
+
 static int stereo_run(aos2_extractor *l, aos2_extractor *r, int first_image, int batch, const aos2_keypoint_t *d_kpl,
                       const uint8_t *d_dl, const int32_t *d_nl, const aos2_keypoint_t *d_kpr, const uint8_t *d_dr,
                       const int32_t *d_nr, int cap, int max_n_left, float mb, float mbf, float *d_ur, float *d_depth, bool sync = true)
@@ -1266,6 +1297,7 @@ int aos2_compute_stereo_matches(aos2_extractor_t *left, aos2_extractor_t *right,
     const bool form_ok = n_left >= 0 && n_right >= 0 && (n_left == 0 || (kp_left && desc_left && u_right && depth)) &&
                          (n_right == 0 || (kp_right && desc_right));
     if ((st = check_stereo_args(left, right, image, 1, mb, form_ok))) return st;
+    if ((st = check_stereo_keypoints(left, kp_left, n_left, kp_right, n_right))) return st;
     if (n_left == 0) return AOS2_OK;
     if ((st = bind_device(left->par.device))) return st;
     if ((st = finish_device(left)) || (st = finish_device(right))) return st;

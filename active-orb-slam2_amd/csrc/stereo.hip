@@ -6,9 +6,12 @@
 // does the 11x11 SAD slide over 11 offsets (:586-620) from a 11x21 right window staged in LDS,
 // the parabola fit (:625-633) and the depth (:636-648).  A second kernel (one workgroup per image)
 // finds the median SAD by rank counting and applies thDist = 1.5*1.4*median (:654-668).
-// The row table vRowIndices of the reference is replaced by evaluating its membership predicate
-// (floor(y-r) <= row <= ceil(y+r)) directly: candidates are visited in ascending iR either way,
-// and the key dist<<20|iR keeps the reference's first-strictly-smaller tie rule.
+// The row table vRowIndices of the reference (:505-522) is built by stereo_rows_kernel, one workgroup
+// per image: a count pass, a scan over the rows and a fill pass, with the bands clamped to the image.
+// The fill order inside a row is whatever the atomics give, not the reference's ascending iR; the key
+// dist<<20|iR makes the minimum independent of it and keeps the first-strictly-smaller tie rule.
+// The kernels check nothing about the keypoint records: the windows stay inside the planes only for
+// records in the domain stated in include/aos2.h, which the host-pointer entry enforces.
 #include "stereo.h"
 
 #include "aos2_common.h"

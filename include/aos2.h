@@ -160,7 +160,17 @@ int aos2_extractor_pyramid_level(aos2_extractor_t *e, int image, int level, int 
  * mb = baseline in metres (minZ, :526), mbf = baseline * fx (:527).
  * Outputs mvuRight[n_left], mvDepth[n_left]; -1 = no stereo match (:498).
  * When no left keypoint passes the SAD stage the reference reads vDistIdx[0] of an empty vector
- * (:655); here that case leaves every output at -1. */
+ * (:655); here that case leaves every output at -1.
+ * Domain of ComputeStereoMatches.  With (w_l, h_l) the size of mvImagePyramid[l], inv = mvInvScaleFactors and round()
+ * half away from zero:
+ *   left keypoint:  0 <= octave < nlevels; x, y finite; 0 <= (int)y < rows of level 0;
+ *                   5 <= round(x * inv[octave]) <= w_octave - 6 and 5 <= round(y * inv[octave]) <= h_octave - 6;
+ *   right keypoint: 0 <= octave < nlevels; y finite; for every existing level l in octave-1 .. octave+1,
+ *                   round(x * inv[l]) is negative (refused by iniu < 0, :604) or at least 10.
+ * Inside it the 11 x 11 left window (:592) and the 11 x 21 right window (:609) stay inside the level; outside it the
+ * reference throws from rowRange / colRange.  Every keypoint the extractor writes is inside it.  This call checks the
+ * records on the host and returns AOS2_ERR_ARG, with the outputs untouched and nothing uploaded or launched, when one is
+ * outside. */
 int aos2_compute_stereo_matches(aos2_extractor_t *left, aos2_extractor_t *right, int image,
                                 const aos2_keypoint_t *kp_left, const uint8_t *desc_left, int n_left,
                                 const aos2_keypoint_t *kp_right, const uint8_t *desc_right,
@@ -168,7 +178,9 @@ int aos2_compute_stereo_matches(aos2_extractor_t *left, aos2_extractor_t *right,
 /* Batched, fully device-resident form: the arrays are exactly what
  * aos2_extractor_extract_batch_device() wrote for the two eyes ([batch][cap] keypoints,
  * [batch][cap][32] descriptors, [batch] counts; descriptor blocks 16-byte aligned); image b of the
- * call = image b of both extractors' last batch.  d_u_right / d_depth are [batch][cap]. */
+ * call = image b of both extractors' last batch.  d_u_right / d_depth are [batch][cap].
+ * Precondition: every record lies in the domain above.  The device-resident forms cannot look at the records and do not
+ * check it; arrays written by aos2_extractor_extract_batch_device() satisfy it, anything else is the caller's to verify. */
 int aos2_compute_stereo_matches_device(aos2_extractor_t *left, aos2_extractor_t *right, int batch,
                                        const aos2_keypoint_t *d_kp_left, const uint8_t *d_desc_left,
                                        const int32_t *d_n_left, const aos2_keypoint_t *d_kp_right,

@@ -90,6 +90,19 @@ def test_stereo_edge_cases(pkg, oracle, gpu):
     our, odp, on = oracle.compute_stereo_matches(eL, eR, kl, dl, kl, dl, mb, mbf)
     ur, dp = pkg.ComputeStereoMatches(xl, xr, kl, dl, kl, dl, mb, mbf)
     assert on > 100 and (ur == -1).all() and ur.tobytes() == our.tobytes()
+    # records whose windows would leave the planes (include/aos2.h, the domain of ComputeStereoMatches) -> argument error
+    eR.extract(right)
+    xr(right)
+    for side, field, value in (("l", "x", 3.0), ("l", "y", 237.0), ("l", "octave", 8), ("l", "y", np.nan),
+                               ("r", "x", 5.0), ("r", "octave", -1), ("r", "y", np.inf)):
+        a, b = kl.copy(), kr.copy()
+        (a if side == "l" else b)[field][7] = value
+        with pytest.raises(pkg.AosError) as err:
+            pkg.ComputeStereoMatches(xl, xr, a, dl, b, dr, mb, mbf)
+        assert err.value.code == pkg.capi.AOS2_ERR_ARG
+    our, odp, _ = oracle.compute_stereo_matches(eL, eR, kl, dl, kr, dr, mb, mbf)
+    ur, dp = pkg.ComputeStereoMatches(xl, xr, kl, dl, kr, dr, mb, mbf)
+    assert ur.tobytes() == our.tobytes() and dp.tobytes() == odp.tobytes()
     # left/right extractors that differ -> argument error
     x3 = pkg.Extractor(nfeatures=500, nlevels=4)
     x3(left)
