@@ -145,6 +145,13 @@ def lib():
         L.aos2_optimize_sim3.argtypes = [vp, vp, vp, ci]
         L.aos2_optimize_sim3_last_device_ms.argtypes = [vp]
         L.aos2_optimize_sim3_last_device_ms.restype = cf
+        L.aos2_debug_essential_graph_host.argtypes = [vp, vp, ci]
+        L.aos2_optimize_essential_graph.argtypes = [vp, vp, vp, ci]
+        L.aos2_optimize_essential_graph_last_device_ms.argtypes = [vp]
+        L.aos2_optimize_essential_graph_last_device_ms.restype = cf
+        L.aos2_debug_essential_graph_profile.argtypes = [vp, ci, vp]
+        L.aos2_debug_essential_graph_arith_host.argtypes = [ci, vp, ci, vp]
+        L.aos2_debug_essential_graph_solve_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
         if hasattr(L, "aos2_matcher_create"):
             L.aos2_matcher_create.argtypes = [cf, ci, ci, C.POINTER(vp)]
             L.aos2_matcher_destroy.argtypes = [vp]
@@ -1369,6 +1376,86 @@ def debug_sim3_opt_host(problems):
     return _sim3_opt_results(R, outs)
 
 
+# ---- Optimizer::OptimizeEssentialGraph (include/aos2.h: aos2_optimize_essential_graph, aos2_debug_essential_graph_host)
+AOS2_EG_OK, AOS2_EG_NO_STEP, AOS2_ERR_EG_MEMORY = 0, 1, -6
+
+
+class _EssentialGraphProblem(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("Scw", C.c_void_p), ("fixed", C.c_int32), ("n_edges", C.c_int32), ("v0", C.c_void_p),
+                ("v1", C.c_void_p), ("Sji", C.c_void_p), ("fix_scale", C.c_int32), ("iterations", C.c_int32), ("n_points", C.c_int32),
+                ("Xw", C.c_void_p), ("ref", C.c_void_p)]
+
+
+class _EssentialGraphResult(C.Structure):
+    _fields_ = [("Scw", C.c_void_p), ("Tiw", C.c_void_p), ("Xw", C.c_void_p), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),
+                ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32), ("l_blocks", C.c_int32), ("status", C.c_int32)]
+
+
+def _essential_graph_args(problems, sentinel=None):
+    """problems: dicts with Scw [n_vertices][8] (q (x, y, z, w), t, s; float64), fixed, v0 / v1 [n_edges], Sji [n_edges][8], fix_scale,
+    iterations (20 when absent), Xw [n_points][3] (float32), ref [n_points].  A count may be forced apart from its arrays with
+    n_vertices / n_edges / n_points, an array left out with None (what the argument checks are tried with).  `sentinel` pre-fills
+    every result byte."""
+    n = max(1, len(problems))
+    P, R, keep, outs = (_EssentialGraphProblem * n)(), (_EssentialGraphResult * n)(), [], []
+    for i, q in enumerate(problems):
+        def arr(k, dt, cols):
+            if q.get(k) is None:
+                return None
+            a = np.ascontiguousarray(q[k], dt).reshape((-1, cols) if cols else (-1,))
+            keep.append(a)
+            return a
+        Scw, Sji, v0, v1 = arr("Scw", np.float64, 8), arr("Sji", np.float64, 8), arr("v0", np.int32, 0), arr("v1", np.int32, 0)
+        Xw, ref = arr("Xw", np.float32, 3), arr("ref", np.int32, 0)
+        if v0 is not None and v1 is not None and Sji is not None and not len(v0) == len(v1) == len(Sji):
+            raise ValueError("problem %d: v0, v1 [n_edges], Sji [n_edges][8]" % i)
+        if Xw is not None and ref is not None and len(Xw) != len(ref):
+            raise ValueError("problem %d: Xw [n_points][3], ref [n_points]" % i)
+        P[i].n_vertices = int(q.get("n_vertices", 0 if Scw is None else len(Scw)))
+        P[i].n_edges = int(q.get("n_edges", 0 if v0 is None else len(v0)))
+        P[i].n_points = int(q.get("n_points", 0 if Xw is None else len(Xw)))
+        P[i].fixed, P[i].fix_scale, P[i].iterations = int(q["fixed"]), int(bool(q["fix_scale"])), int(q.get("iterations", 20))
+        for k, a in (("Scw", Scw), ("Sji", Sji), ("v0", v0), ("v1", v1), ("Xw", Xw), ("ref", ref)):
+            setattr(P[i], k, a.ctypes.data if a is not None and a.size else None)
+        nv, npt = max(P[i].n_vertices, 0), max(P[i].n_points, 0)
+        fill = 0 if sentinel is None else sentinel
+        out = dict(Scw=np.frombuffer(bytes([fill]) * (64 * nv), np.float64).reshape(nv, 8).copy(),
+                   Tiw=np.frombuffer(bytes([fill]) * (64 * nv), np.float32).reshape(nv, 4, 4).copy(),
+                   Xw=np.frombuffer(bytes([fill]) * (12 * npt), np.float32).reshape(npt, 3).copy())
+        outs.append(out)
+        R[i].Scw, R[i].Tiw, R[i].Xw = out["Scw"].ctypes.data, out["Tiw"].ctypes.data, out["Xw"].ctypes.data
+        if q.get("null_result"):
+            setattr(R[i], q["null_result"], None)
+        if sentinel is not None:
+            off = _EssentialGraphResult.chi2_initial.offset
+            C.memset(C.byref(R[i], off), sentinel, C.sizeof(_EssentialGraphResult) - off)
+    return P, R, keep, outs
+
+
+def _essential_graph_results(R, outs):
+    return [dict(Scw=o["Scw"], Tiw=o["Tiw"], Xw=o["Xw"], chi2_initial=R[i].chi2_initial, chi2_final=R[i].chi2_final, iterations=R[i].iterations,
+                 trials=R[i].trials, rejected=R[i].rejected, l_blocks=R[i].l_blocks, status=R[i].status) for i, o in enumerate(outs)]
+
+
+def debug_essential_graph_host(problems, sentinel=None):
+    """aos2_debug_essential_graph_host: the arithmetic of the device path on the CPU with a skyline solve -> one dict per problem (the
+    fields of aos2_essential_graph_result_t)"""
+    P, R, keep, outs = _essential_graph_args(problems, sentinel)
+    debug_essential_graph_host.last = (R, outs)
+    _check(lib().aos2_debug_essential_graph_host(P, R, len(problems)))
+    return _essential_graph_results(R, outs)
+
+
+def debug_essential_graph_arith_host(what, values):
+    """aos2_debug_essential_graph_arith_host: "log" of Sim3s [n][8] -> [n][7]; "residual" of (C, S_v0, S_v1) [n][3][8] -> [n][7];
+    "lu3" of (W, t) [n][12] -> [n][3]"""
+    code, width, out_w = {"log": (0, 8, 7), "residual": (1, 24, 7), "lu3": (2, 12, 3)}[what]
+    a = np.ascontiguousarray(values, np.float64).reshape(-1, width)
+    out = np.zeros((len(a), out_w))
+    _check(lib().aos2_debug_essential_graph_arith_host(code, _p(a), len(a), _p(out)))
+    return out
+
+
 def debug_sincos_device(angles, device=0):
     a = np.ascontiguousarray(angles, np.float32)
     s = np.zeros_like(a)
@@ -2096,6 +2183,39 @@ class LocalBA:
 
     def sim3_opt_last_device_ms(self):
         return float(self.L.aos2_optimize_sim3_last_device_ms(self.h))
+
+    def optimize_essential_graph(self, problems, sentinel=None):
+        """aos2_optimize_essential_graph: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:782-1045) for a batch of pose graphs;
+        problems as debug_essential_graph_host -> one dict per problem.  `sentinel` pre-fills the result buffers (kept in
+        self.essential_graph_last for a caller that expects a refusal)"""
+        P, R, keep, outs = _essential_graph_args(problems, sentinel)
+        self.essential_graph_last = (R, outs)
+        _check(self.L.aos2_optimize_essential_graph(self.h, P, R, len(problems)))
+        return _essential_graph_results(R, outs)
+
+    def essential_graph_last_device_ms(self):
+        return float(self.L.aos2_optimize_essential_graph_last_device_ms(self.h))
+
+    def essential_graph_profile(self, on):
+        """aos2_debug_essential_graph_profile: switch the per-family events on / off -> the family ms of the last profiled call
+        (perturb + linearise, assemble, factor_solve, begin + trial, finish)"""
+        ms = (C.c_float * 5)()
+        _check(self.L.aos2_debug_essential_graph_profile(self.h, int(bool(on)), ms))
+        return [float(v) for v in ms]
+
+    def debug_essential_graph_solve(self, n_blocks, rows, cols, val, diag, b, lam, x0=None):
+        """aos2_debug_essential_graph_solve_device: the symbolic phase and k_eg_factor_solve alone -> (x, ok, l_blocks); x0 = what x
+        holds before (kept when the solve fails)"""
+        rows, cols = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(cols, np.int32)
+        val = np.ascontiguousarray(val, np.float64).reshape(-1, 49)
+        diag, b = np.ascontiguousarray(diag, np.float64).reshape(-1, 49), np.ascontiguousarray(b, np.float64).reshape(-1)
+        if len(diag) != n_blocks or len(b) != 7 * n_blocks or not len(rows) == len(cols) == len(val):
+            raise ValueError("diag [n_blocks][49], b [7 n_blocks], rows / cols / val one per triplet")
+        x = np.zeros(7 * n_blocks) if x0 is None else np.array(x0, np.float64).reshape(7 * n_blocks)
+        ok, lb = C.c_int32(-1), C.c_int32(-1)
+        _check(self.L.aos2_debug_essential_graph_solve_device(self.h, int(n_blocks), len(rows), _p(rows), _p(cols), _p(val), _p(diag), _p(b),
+                                                              float(lam), _p(x), C.byref(ok), C.byref(lb)))
+        return x, int(ok.value), int(lb.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------

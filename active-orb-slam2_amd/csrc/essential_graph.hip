@@ -1,0 +1,930 @@
+// Optimizer::OptimizeEssentialGraph on gfx950 for a batch of pose graphs (include/aos2.h: aos2_optimize_essential_graph; reference
+// src/Optimizer.cc:782-1045).  The arithmetic is csrc/essential_graph.h, shared with the host tap at the end of this file.
+//
+// The pattern of H does not change over the iterations, so the host works it out once per problem (eg_symbolic): the 7x7 block
+// pattern over the free vertices in ascending vertex order, the pattern of L by the elimination tree, for every block the list of
+// edges that add to it (in edge order), and for every column of L the blocks its trailing update lands in.  The values never
+// leave the device: an LM iteration is k_eg_perturb, k_eg_linearise, k_eg_assemble, k_eg_begin and up to ten (k_eg_factor_solve,
+// k_eg_trial) pairs, each of which returns at once when the iteration's trials are over; rho, lambda, ni and which estimates stay
+// are decided in k_eg_trial.  The host reads the control words once per iteration to stop enqueueing.
+#include <algorithm>
+#include <vector>
+
+#include "essential_graph.h"
+#include "wave_ops.h"
+
+namespace aos2 {
+
+constexpr int kEgThreads = 256, kEgRows = kEgThreads / 16;
+constexpr int kEgMaxVertices = 8192, kEgMaxProblems = 16, kEgHostMaxVertices = 512;
+constexpr size_t kEgArenaMax = (size_t)2 << 30;
+
+// (A + lambda I) x = b in 7x7 blocks.  Slot k < nf is the diagonal block of column k, slot nf + p the block rowidx[p] of the column c
+// with colptr[c] <= p < colptr[c + 1] (rows ascending, below the diagonal).  A block is 49 doubles, row-major.
+struct EgSystem {
+    int32_t nf, n_slots;
+    const int32_t *colptr, *rowidx;   // [nf + 1], [n_slots - nf]
+    const int32_t *upd_ptr, *upd_dst; // column k with rows r_0 < .. < r_{m-1}: upd_dst[upd_ptr[k] + j m - j (j - 1) / 2 + (i - j)] = the slot of block (r_i, r_j), i >= j
+    const double *H, *b;              // [n_slots][49], [7 nf]
+    double *L, *y, *x;                // the factor (same slots), the right-hand side on its way, the solution
+};
+
+struct EgDev {
+    int32_t nv, ne, np, fixed, fix_scale, pad;
+    const int32_t *v0, *v1;
+    const Sim3d *C, *S_in;            // the measurements [ne], vScw [nv]
+    Sim3d *est, *est_try, *pert;      // [nv], [nv], [nv][kEgPert]
+    double *J, *E;                    // [ne][2][49], [ne][7]
+    const int32_t *hidx, *free_v;     // [nv] hessian index or -1, [nf] its inverse
+    const int32_t *slot_ptr, *slot_list;   // [n_slots + 1], entries edge * 4 + kind (eg_block_term)
+    const int32_t *b_ptr, *b_list;         // [nf + 1], entries edge * 2 + side
+    EgSystem sys;
+    EgControl *ctl;
+    const float *Xw_in;
+    const int32_t *ref;
+    float *Tiw, *Xw_out;
+};
+
+// Workgroup sum of N doubles per thread, the result in every thread.  Row sums by DPP (lane 0 of a row of 16 is the one that is kept),
+// then every thread adds the 16 row partials in row order: the order depends on nothing but the thread number.  The second barrier
+// lets `part` be written again.
+template <int N>
+__device__ __forceinline__ void eg_block_sum(double (&v)[N], double *part)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = row_sum_f64(v[i]);
+    if ((tid & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) part[(tid >> 4) * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = part[i];
+        for (int r = 1; r < kEgRows; ++r) s += part[r * N + i];
+        v[i] = s;
+    }
+    __syncthreads();
+}
+
+// the transforms of a linearisation that belong to a vertex: grid over (vertex, 15): the 14 perturbed estimates with their inverses,
+// and the inverse of the estimate
+__global__ __launch_bounds__(kEgThreads) void k_eg_perturb(const EgDev *__restrict__ probs)
+{
+    const EgDev &P = probs[blockIdx.y];
+    if (!P.ctl->running) return;
+    const int item = blockIdx.x * kEgThreads + threadIdx.x;
+    if (item >= P.nv * 15) return;
+    const int v = item / 15, k = item % 15;
+    const Sim3d S = P.est[v];
+    Sim3d *out = P.pert + (size_t)v * kEgPert;
+    if (k == 14) {
+        Sim3d inv;
+        so_inverse(S, inv);
+        out[0] = inv;
+    } else if (P.hidx[v] >= 0) {   // (a fixed vertex is never perturbed)
+        Sim3d fwd, inv;
+        so_perturbed(S, k, P.fix_scale != 0, fwd, inv);
+        out[1 + 2 * k] = fwd;
+        out[2 + 2 * k] = inv;
+    }
+}
+
+// grid over (edge, 16): items 0..13 = column d of the Jacobian of side 0 / side 1 (two residuals each), item 14 = the stored residual
+__global__ __launch_bounds__(kEgThreads) void k_eg_linearise(const EgDev *__restrict__ probs)
+{
+    const EgDev &P = probs[blockIdx.y];
+    if (!P.ctl->running) return;
+    const int item = blockIdx.x * kEgThreads + threadIdx.x;
+    if (item >= P.ne * 16) return;
+    const int e = item >> 4, j = item & 15;
+    if (j == 15) return;
+    const int a = P.v0[e], b = P.v1[e];
+    const Sim3d C = P.C[e];
+    const Sim3d *pa = P.pert + (size_t)a * kEgPert, *pb = P.pert + (size_t)b * kEgPert;
+    if (j == 14) {
+        double er[7];
+        eg_residual(C, P.est[a], pb[0], er);
+        for (int r = 0; r < 7; ++r) P.E[(size_t)e * 7 + r] = er[r];
+        return;
+    }
+    const int side = j / 7, d = j % 7;
+    if (P.hidx[side ? b : a] < 0) return;   // the Jacobian of a fixed vertex is never read
+    eg_jacobian_column(C, P.est[a], pa, pb, side, d, P.J + ((size_t)e * 2 + side) * 49);
+}
+
+// grid over the entries of the blocks of H and the components of b: each is summed over its list of edges, in edge order
+__global__ __launch_bounds__(kEgThreads) void k_eg_assemble(const EgDev *__restrict__ probs)
+{
+    const EgDev &P = probs[blockIdx.y];
+    if (!P.ctl->running) return;
+    const long long item = (long long)blockIdx.x * kEgThreads + threadIdx.x, nH = (long long)P.sys.n_slots * 49;
+    if (item < nH) {
+        const int slot = (int)(item / 49), ent = (int)(item % 49), a = ent / 7, b = ent % 7;
+        double s = 0;
+        for (int q = P.slot_ptr[slot]; q < P.slot_ptr[slot + 1]; ++q) {
+            const int w = P.slot_list[q];
+            s += eg_block_term(P.J + (size_t)(w >> 2) * 98, w & 3, a, b);
+        }
+        const_cast<double *>(P.sys.H)[item] = s;
+    } else if (item < nH + (long long)P.sys.nf * 7) {
+        const int i = (int)(item - nH), h = i / 7, a = i % 7;
+        double s = 0;
+        for (int q = P.b_ptr[h]; q < P.b_ptr[h + 1]; ++q) {
+            const int w = P.b_list[q];
+            s -= eg_jte(P.J + (size_t)w * 49, P.E + (size_t)(w >> 1) * 7, a);
+        }
+        const_cast<double *>(P.sys.b)[i] = s;
+    }
+}
+
+// chi2 of the stored residuals, edge e in thread e % 256, and the start of the iteration; one workgroup per problem
+__global__ __launch_bounds__(kEgThreads) void k_eg_begin(const EgDev *__restrict__ probs)
+{
+    __shared__ double part[kEgRows];
+    const EgDev &P = probs[blockIdx.x];
+    if (!P.ctl->running) return;
+    double chi[1] = {0};
+    for (int e = threadIdx.x; e < P.ne; e += kEgThreads) chi[0] += eg_chi2(P.E + (size_t)e * 7);
+    eg_block_sum(chi, part);
+    if (threadIdx.x == 0) eg_iteration_begin(*P.ctl, chi[0]);
+}
+
+// Block-sparse LDL^T of H + lambda I in device memory and the solve, one workgroup per system, right-looking, no pivoting.  With
+// A = L D L^T, L's diagonal blocks the unit lower factors Ld_k of the 7x7 LDL^T and D the pivots, column k is
+//   1. Ld_k, D_k of the diagonal block (one thread, in LDS); z_k = Ld_k^-1 y_k
+//   2. L_rk = A_rk Ld_k^-T D_k^-1, a thread per row of a block; y_r -= L_rk z_k
+//   3. A_(ri, rj) -= L_(ri, k) D_k L_(rj, k)^T for every pair of rows of the column, a thread per entry
+// and afterwards x_k = Ld_k^-T (D_k^-1 z_k - sum over the column's rows of L_rk^T x_r) for k descending.  A zero or NaN pivot ends
+// it: solved = 0 and x keeps its values.
+__device__ __forceinline__ void eg_factor_solve(const EgSystem &S, double lambda, int32_t *solved)
+{
+    __shared__ double D[49], z[7], sums[8];
+    __shared__ int fail;
+    const int tid = threadIdx.x, nf = S.nf;
+    const size_t nL = (size_t)S.n_slots * 49, nD = (size_t)nf * 49;
+    for (size_t i = tid; i < nL; i += kEgThreads) {
+        double v = S.H[i];
+        if (i < nD && (i % 49) % 8 == 0) v += lambda;
+        S.L[i] = v;
+    }
+    for (int i = tid; i < 7 * nf; i += kEgThreads) S.y[i] = S.b[i];
+    if (tid == 0) fail = 0;
+    __syncthreads();
+    for (int k = 0; k < nf; ++k) {
+        if (tid < 49) D[tid] = S.L[(size_t)k * 49 + tid];
+        __syncthreads();
+        if (tid == 0) {
+            if (!eg_ldlt7(D)) fail = 1;
+            else {
+                double zz[7];
+                for (int r = 0; r < 7; ++r) {
+                    double s = S.y[7 * k + r];
+                    for (int m = 0; m < r; ++m) s -= D[r * 7 + m] * zz[m];
+                    zz[r] = s;
+                    z[r] = s;
+                }
+                for (int r = 0; r < 7; ++r) S.y[7 * k + r] = zz[r] / D[r * 7 + r];
+            }
+        }
+        __syncthreads();
+        if (fail) break;
+        if (tid < 49) S.L[(size_t)k * 49 + tid] = D[tid];
+        const int p0 = S.colptr[k], m = S.colptr[k + 1] - p0;
+        for (int it = tid; it < m * 7; it += kEgThreads) {
+            const int i = it / 7, a = it % 7;
+            double *blk = S.L + (size_t)(nf + p0 + i) * 49 + a * 7;
+            double w[7];
+            for (int c = 0; c < 7; ++c) {
+                double s = blk[c];
+                for (int q = 0; q < c; ++q) s -= w[q] * D[c * 7 + q];
+                w[c] = s;
+            }
+            double dot = 0;
+            for (int c = 0; c < 7; ++c) {
+                const double l = w[c] / D[c * 7 + c];
+                blk[c] = l;
+                dot += l * z[c];
+            }
+            S.y[7 * S.rowidx[p0 + i] + a] -= dot;
+        }
+        __syncthreads();
+        const int32_t *dst = S.upd_dst + S.upd_ptr[k];
+        for (int j = 0; j < m; ++j) {
+            const double *Lj = S.L + (size_t)(nf + p0 + j) * 49;
+            const int base = j * m - j * (j - 1) / 2;
+            for (int it = tid; it < (m - j) * 49; it += kEgThreads) {
+                const int i = j + it / 49, ent = it % 49, a = ent / 7, b = ent % 7;
+                const double *Li = S.L + (size_t)(nf + p0 + i) * 49 + a * 7;
+                double s = 0;
+                for (int c = 0; c < 7; ++c) s += (Li[c] * D[c * 7 + c]) * Lj[b * 7 + c];
+                S.L[(size_t)dst[base + (i - j)] * 49 + ent] -= s;
+            }
+        }
+        __syncthreads();
+    }
+    const bool ok = !fail;
+    if (ok) {
+        const int a = tid >> 4, l = tid & 15;
+        for (int k = nf - 1; k >= 0; --k) {
+            const int p0 = S.colptr[k], m = S.colptr[k + 1] - p0;
+            if (tid < 128) {   // two whole waves: row a < 7 of 16 lanes sums component a, a fixed lane of the row keeps it
+                double s = 0;
+                if (a < 7)
+                    for (int t = l; t < m * 7; t += 16) {
+                        const int i = t / 7, c = t % 7;
+                        s += S.L[(size_t)(nf + p0 + i) * 49 + c * 7 + a] * S.x[7 * S.rowidx[p0 + i] + c];
+                    }
+                s = row_sum_f64(s);
+                if (l == 0) sums[a] = s;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                const double *Ld = S.L + (size_t)k * 49;
+                double xv[7];
+                for (int r = 6; r >= 0; --r) {
+                    double s = S.y[7 * k + r] - sums[r];
+                    for (int q = r + 1; q < 7; ++q) s -= Ld[q * 7 + r] * xv[q];
+                    xv[r] = s;
+                }
+                for (int r = 0; r < 7; ++r) S.x[7 * k + r] = xv[r];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) *solved = ok;
+}
+
+__global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve(const EgDev *__restrict__ probs)
+{
+    const EgDev &P = probs[blockIdx.x];
+    EgControl *ctl = P.ctl;
+    if (!ctl->running || !ctl->open) return;
+    eg_factor_solve(P.sys, ctl->lm.lambda, &ctl->solved);
+}
+
+// the same on a system alone (aos2_debug_essential_graph_solve_device)
+__global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve_tap(EgSystem S, double lambda, int32_t *solved) { eg_factor_solve(S, lambda, solved); }
+
+// One trial, one workgroup per problem: the estimates of the free vertices after oplus(x) into est_try, the residuals and chi2 (edge e
+// in thread e % 256), the decision; est_try becomes est when the trial is accepted.
+__global__ __launch_bounds__(kEgThreads) void k_eg_trial(const EgDev *__restrict__ probs)
+{
+    __shared__ double part[kEgRows * 2];
+    __shared__ int accepted;
+    const EgDev &P = probs[blockIdx.x];
+    EgControl *ctl = P.ctl;
+    if (!ctl->running || !ctl->open) return;
+    const int tid = threadIdx.x, nf = P.sys.nf;
+    const double lambda = ctl->lm.lambda;
+    double sum[2] = {0, 0};   // chi2, sum of x (lambda x + b)
+    for (int h = tid; h < nf; h += kEgThreads) {
+        double u[7];
+        for (int r = 0; r < 7; ++r) u[r] = P.sys.x[7 * h + r];
+        const int v = P.free_v[h];
+        Sim3d T;
+        so_oplus(u, P.fix_scale != 0, P.est[v], T);
+        P.est_try[v] = T;
+    }
+    for (int i = tid; i < 7 * nf; i += kEgThreads) {
+        const double x = P.sys.x[i];
+        sum[1] += x * (lambda * x + P.sys.b[i]);
+    }
+    __syncthreads();
+    for (int e = tid; e < P.ne; e += kEgThreads) {
+        Sim3d inv;
+        so_inverse(P.est_try[P.v1[e]], inv);
+        double er[7];
+        eg_residual(P.C[e], P.est_try[P.v0[e]], inv, er);
+        sum[0] += eg_chi2(er);
+    }
+    eg_block_sum(sum, part);
+    if (tid == 0) accepted = eg_trial_decide(*ctl, sum[0], sum[1]);
+    __syncthreads();
+    if (accepted)
+        for (int h = tid; h < nf; h += kEgThreads) {
+            const int v = P.free_v[h];
+            P.est[v] = P.est_try[v];
+        }
+}
+
+// grid over max(vertices, points): the SE3 pose of a vertex, the corrected position of a point
+__global__ __launch_bounds__(kEgThreads) void k_eg_finish(const EgDev *__restrict__ probs)
+{
+    const EgDev &P = probs[blockIdx.y];
+    const int item = blockIdx.x * kEgThreads + threadIdx.x;
+    if (item < P.nv) eg_pose(P.est[item], P.Tiw + (size_t)item * 16);
+    if (item < P.np) {
+        const int r = P.ref[item];
+        eg_point(P.S_in[r], P.est[r], P.Xw_in + (size_t)item * 3, P.Xw_out + (size_t)item * 3);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- the symbolic phase (host)
+struct EgSymbolic {
+    int nf = 0;
+    std::vector<int32_t> colptr, rowidx, upd_ptr, upd_dst;
+    size_t l_blocks() const { return rowidx.size(); }
+    int slot(int row, int col) const   // row > col, present in the pattern of L
+    {
+        const int32_t *b = rowidx.data() + colptr[col], *e = rowidx.data() + colptr[col + 1];
+        return nf + (int)(std::lower_bound(b, e, row) - rowidx.data());
+    }
+};
+
+// the pattern of L for the lower-triangle blocks (hi[i], lo[i]) eliminated in ascending order: a column's rows are those of A's
+// column and, but for the column itself, those of every child in the elimination tree (parent = the first row of the column).
+// false: the factor and its update table would take more than max_bytes.
+static bool eg_symbolic(int nf, const std::vector<int32_t> &hi, const std::vector<int32_t> &lo, size_t max_bytes, EgSymbolic &Y)
+{
+    Y.nf = nf;
+    std::vector<std::vector<int32_t>> rows((size_t)nf);
+    for (size_t i = 0; i < hi.size(); ++i) rows[(size_t)lo[i]].push_back(hi[i]);
+    size_t n_l = 0, n_upd = 0;
+    for (int k = 0; k < nf; ++k) {
+        std::vector<int32_t> &r = rows[(size_t)k];
+        std::sort(r.begin(), r.end());
+        r.erase(std::unique(r.begin(), r.end()), r.end());
+        if (r.size() > 1) {
+            std::vector<int32_t> &par = rows[(size_t)r[0]];
+            par.insert(par.end(), r.begin() + 1, r.end());
+        }
+        n_l += r.size();
+        n_upd += r.size() * (r.size() + 1) / 2;
+        if ((n_l + (size_t)nf) * 49 * 8 * 2 + n_upd * 4 > max_bytes) return false;
+    }
+    Y.colptr.assign((size_t)nf + 1, 0);
+    Y.rowidx.clear();
+    Y.rowidx.reserve(n_l);
+    for (int k = 0; k < nf; ++k) {
+        Y.rowidx.insert(Y.rowidx.end(), rows[(size_t)k].begin(), rows[(size_t)k].end());
+        Y.colptr[(size_t)k + 1] = (int32_t)Y.rowidx.size();
+    }
+    Y.upd_ptr.assign((size_t)nf + 1, 0);
+    Y.upd_dst.clear();
+    Y.upd_dst.reserve(n_upd);
+    for (int k = 0; k < nf; ++k) {
+        const std::vector<int32_t> &r = rows[(size_t)k];
+        for (size_t j = 0; j < r.size(); ++j) {
+            Y.upd_dst.push_back(r[j]);
+            for (size_t i = j + 1; i < r.size(); ++i) Y.upd_dst.push_back(Y.slot(r[i], r[j]));
+        }
+        Y.upd_ptr[(size_t)k + 1] = (int32_t)Y.upd_dst.size();
+    }
+    return true;
+}
+
+// one problem as the host sees it: the hessian indices, the lower-triangle pairs of its edges, the lists of the assembly
+struct EgHostGraph {
+    int nf = 0;
+    bool runs = false;   // LM has something to do
+    std::vector<int32_t> hidx, free_v, hi, lo;
+    EgSymbolic Y;
+    std::vector<int32_t> slot_ptr, slot_list, b_ptr, b_list;
+};
+
+static void eg_indices(const aos2_essential_graph_problem_t &P, EgHostGraph &G)
+{
+    G.hidx.assign((size_t)P.n_vertices, -1);
+    G.free_v.clear();
+    for (int v = 0; v < P.n_vertices; ++v)
+        if (v != P.fixed) {
+            G.hidx[(size_t)v] = (int32_t)G.free_v.size();
+            G.free_v.push_back(v);
+        }
+    G.nf = (int)G.free_v.size();
+    G.runs = G.nf > 0 && P.n_edges > 0;
+    G.hi.clear();
+    G.lo.clear();
+    for (int e = 0; e < P.n_edges; ++e) {
+        const int a = G.hidx[(size_t)P.v0[e]], b = G.hidx[(size_t)P.v1[e]];
+        if (a >= 0 && b >= 0) {
+            G.hi.push_back(std::max(a, b));
+            G.lo.push_back(std::min(a, b));
+        }
+    }
+}
+
+// the edge lists of every slot of H and of every segment of b, in edge order (a counting sort by slot keeps it)
+static void eg_lists(const aos2_essential_graph_problem_t &P, EgHostGraph &G)
+{
+    const size_t n_slots = (size_t)G.nf + G.Y.l_blocks();
+    std::vector<int32_t> where, what, bwhere, bwhat;
+    for (int e = 0; e < P.n_edges; ++e) {
+        const int a = G.hidx[(size_t)P.v0[e]], b = G.hidx[(size_t)P.v1[e]];
+        if (a >= 0) {
+            where.push_back(a); what.push_back(e * 4);
+            bwhere.push_back(a); bwhat.push_back(e * 2);
+        }
+        if (b >= 0) {
+            where.push_back(b); what.push_back(e * 4 + 1);
+            bwhere.push_back(b); bwhat.push_back(e * 2 + 1);
+        }
+        if (a >= 0 && b >= 0) {
+            where.push_back(G.Y.slot(std::max(a, b), std::min(a, b)));
+            what.push_back(e * 4 + (a > b ? 2 : 3));
+        }
+    }
+    auto bucket = [](const std::vector<int32_t> &wh, const std::vector<int32_t> &wt, size_t n, std::vector<int32_t> &ptr, std::vector<int32_t> &list) {
+        ptr.assign(n + 1, 0);
+        for (int32_t w : wh) ptr[(size_t)w + 1]++;
+        for (size_t i = 0; i < n; ++i) ptr[i + 1] += ptr[i];
+        list.assign(wh.size(), 0);
+        std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);
+        for (size_t i = 0; i < wh.size(); ++i) list[(size_t)at[(size_t)wh[i]]++] = wt[i];
+    };
+    bucket(where, what, n_slots, G.slot_ptr, G.slot_list);
+    bucket(bwhere, bwhat, (size_t)G.nf, G.b_ptr, G.b_list);
+}
+
+static int eg_check(const aos2_essential_graph_problem_t *p, const aos2_essential_graph_result_t *r, int n_problems, int max_vertices)
+{
+    if (n_problems < 0 || n_problems > kEgMaxProblems || (n_problems > 0 && (!p || !r))) {
+        set_error("bad argument (0..%d problems and their results)", kEgMaxProblems);
+        return AOS2_ERR_ARG;
+    }
+    for (int i = 0; i < n_problems; ++i) {
+        const aos2_essential_graph_problem_t &P = p[i];
+        bool ok = P.n_vertices >= 1 && P.n_edges >= 0 && P.n_points >= 0 && P.iterations >= 1 && P.Scw && r[i].Scw && r[i].Tiw &&
+                  P.fixed >= 0 && P.fixed < P.n_vertices && (P.n_edges == 0 || (P.v0 && P.v1 && P.Sji)) &&
+                  (P.n_points == 0 || (P.Xw && P.ref && r[i].Xw));
+        for (int e = 0; ok && e < P.n_edges; ++e)
+            ok = P.v0[e] >= 0 && P.v0[e] < P.n_vertices && P.v1[e] >= 0 && P.v1[e] < P.n_vertices && P.v0[e] != P.v1[e];
+        for (int k = 0; ok && k < P.n_points; ++k) ok = P.ref[k] >= 0 && P.ref[k] < P.n_vertices;
+        if (!ok) {
+            set_error("problem %d: bad argument (counts >= 0, n_vertices >= 1, iterations >= 1, the arrays, fixed / v0 / v1 / ref in range, v0 != v1)", i);
+            return AOS2_ERR_ARG;
+        }
+    }
+    for (int i = 0; i < n_problems; ++i)
+        if (p[i].n_vertices > max_vertices || p[i].n_edges > (1 << 26)) {
+            set_error("problem %d: more than %d vertices or 2^26 edges", i, max_vertices);
+            return AOS2_ERR_CAPACITY;
+        }
+    return AOS2_OK;
+}
+
+static void eg_result_control(const EgControl &c, bool ran, int l_blocks, aos2_essential_graph_result_t &R)
+{
+    R.chi2_initial = ran ? c.chi2_initial : 0;
+    R.chi2_final = ran ? c.lm.currentChi : 0;
+    R.iterations = c.iterations;
+    R.trials = c.trials;
+    R.rejected = c.rejected;
+    R.l_blocks = l_blocks;
+    R.status = ran && c.accepted_first == 0 ? AOS2_EG_NO_STEP : AOS2_EG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the host tap
+// the scalar system in skyline storage: row i keeps columns first[i] .. i
+struct EgSkyline {
+    int n = 0;
+    std::vector<int> first;
+    std::vector<size_t> off;
+    std::vector<double> A, L, d, tmp;
+    double &a(std::vector<double> &M, int i, int j) { return M[off[(size_t)i] + (size_t)(j - first[(size_t)i])]; }
+
+    void shape(const EgHostGraph &G)
+    {
+        std::vector<int> minblk((size_t)G.nf);
+        for (int h = 0; h < G.nf; ++h) minblk[(size_t)h] = h;
+        for (size_t i = 0; i < G.hi.size(); ++i) minblk[(size_t)G.hi[i]] = std::min(minblk[(size_t)G.hi[i]], (int)G.lo[i]);
+        n = 7 * G.nf;
+        first.resize((size_t)n);
+        off.resize((size_t)n + 1);
+        size_t total = 0;
+        for (int i = 0; i < n; ++i) {
+            first[(size_t)i] = 7 * minblk[(size_t)(i / 7)];
+            off[(size_t)i] = total;
+            total += (size_t)(i - first[(size_t)i] + 1);
+        }
+        off[(size_t)n] = total;
+        A.assign(total, 0.0);
+        L.assign(total, 0.0);
+        d.assign((size_t)n, 0.0);
+        tmp.assign((size_t)n, 0.0);
+    }
+    // (A + lambda I) x = b by LDL^T inside the envelope, row by row; false = a zero or NaN pivot, x keeps its values
+    bool solve(double lambda, const std::vector<double> &b, std::vector<double> &x)
+    {
+        L = A;
+        for (int i = 0; i < n; ++i) {
+            const int fi = first[(size_t)i];
+            for (int j = fi; j < i; ++j) {
+                double s = a(L, i, j);
+                for (int k = std::max(fi, first[(size_t)j]); k < j; ++k) s -= tmp[(size_t)k] * a(L, j, k);
+                tmp[(size_t)j] = s;
+            }
+            double di = a(L, i, i) + lambda;
+            for (int j = fi; j < i; ++j) {
+                const double l = tmp[(size_t)j] / d[(size_t)j];
+                a(L, i, j) = l;
+                di -= tmp[(size_t)j] * l;
+            }
+            if (!(di == di) || di == 0) return false;
+            d[(size_t)i] = di;
+        }
+        std::vector<double> y((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            double s = b[(size_t)i];
+            for (int j = first[(size_t)i]; j < i; ++j) s -= a(L, i, j) * y[(size_t)j];
+            y[(size_t)i] = s;
+        }
+        for (int i = 0; i < n; ++i) y[(size_t)i] /= d[(size_t)i];
+        for (int i = n - 1; i >= 0; --i) {
+            const double xi = y[(size_t)i];
+            for (int j = first[(size_t)i]; j < i; ++j) y[(size_t)j] -= a(L, i, j) * xi;
+        }
+        x = y;
+        return true;
+    }
+};
+
+static const Sim3d *eg_sim3(const double *p) { return reinterpret_cast<const Sim3d *>(p); }
+
+static void eg_host_one(const aos2_essential_graph_problem_t &P, EgHostGraph &G, aos2_essential_graph_result_t &R)
+{
+    const int nv = P.n_vertices, ne = P.n_edges;
+    std::vector<Sim3d> est(eg_sim3(P.Scw), eg_sim3(P.Scw) + nv), trial_est;
+    const Sim3d *C = eg_sim3(P.Sji);
+    EgControl ctl;
+    eg_control_init(ctl, P.iterations, G.runs);
+    if (G.runs) {
+        EgSkyline K;
+        K.shape(G);
+        std::vector<Sim3d> pert((size_t)nv * kEgPert);
+        std::vector<double> J((size_t)ne * 98), E((size_t)ne * 7), b((size_t)K.n), x((size_t)K.n, 0.0);
+        const bool fix = P.fix_scale != 0;
+        while (ctl.running) {
+            for (int v = 0; v < nv; ++v) {
+                Sim3d *o = pert.data() + (size_t)v * kEgPert;
+                so_inverse(est[(size_t)v], o[0]);
+                if (G.hidx[(size_t)v] >= 0)
+                    for (int k = 0; k < 14; ++k) so_perturbed(est[(size_t)v], k, fix, o[1 + 2 * k], o[2 + 2 * k]);
+            }
+            std::fill(K.A.begin(), K.A.end(), 0.0);
+            std::fill(b.begin(), b.end(), 0.0);
+            double chi = 0;
+            for (int e = 0; e < ne; ++e) {
+                const int va = P.v0[e], vb = P.v1[e], h[2] = {G.hidx[(size_t)va], G.hidx[(size_t)vb]};
+                const Sim3d *pa = pert.data() + (size_t)va * kEgPert, *pb = pert.data() + (size_t)vb * kEgPert;
+                double *Je = J.data() + (size_t)e * 98, *Ee = E.data() + (size_t)e * 7;
+                eg_residual(C[e], est[(size_t)va], pb[0], Ee);
+                chi += eg_chi2(Ee);
+                for (int side = 0; side < 2; ++side)
+                    if (h[side] >= 0)
+                        for (int d = 0; d < 7; ++d) eg_jacobian_column(C[e], est[(size_t)va], pa, pb, side, d, Je + side * 49);
+                for (int side = 0; side < 2; ++side) {
+                    if (h[side] < 0) continue;
+                    for (int r = 0; r < 7; ++r) {
+                        for (int c = 0; c <= r; ++c) K.a(K.A, 7 * h[side] + r, 7 * h[side] + c) += eg_block_term(Je, side, r, c);
+                        b[(size_t)(7 * h[side] + r)] -= eg_jte(Je + side * 49, Ee, r);
+                    }
+                }
+                if (h[0] >= 0 && h[1] >= 0) {
+                    const int hi = std::max(h[0], h[1]), lo = std::min(h[0], h[1]), kind = h[0] > h[1] ? 2 : 3;
+                    for (int r = 0; r < 7; ++r)
+                        for (int c = 0; c < 7; ++c) K.a(K.A, 7 * hi + r, 7 * lo + c) += eg_block_term(Je, kind, r, c);
+                }
+            }
+            eg_iteration_begin(ctl, chi);
+            while (ctl.open) {
+                ctl.solved = K.solve(ctl.lm.lambda, b, x);
+                trial_est = est;
+                for (int hf = 0; hf < G.nf; ++hf) {
+                    double u[7];
+                    for (int r = 0; r < 7; ++r) u[r] = x[(size_t)(7 * hf + r)];
+                    const int v = G.free_v[(size_t)hf];
+                    so_oplus(u, fix, est[(size_t)v], trial_est[(size_t)v]);
+                }
+                double scale = 0, temp = 0;
+                for (int i = 0; i < K.n; ++i) scale += x[(size_t)i] * (ctl.lm.lambda * x[(size_t)i] + b[(size_t)i]);
+                for (int e = 0; e < ne; ++e) {
+                    Sim3d inv;
+                    so_inverse(trial_est[(size_t)P.v1[e]], inv);
+                    double er[7];
+                    eg_residual(C[e], trial_est[(size_t)P.v0[e]], inv, er);
+                    temp += eg_chi2(er);
+                }
+                if (eg_trial_decide(ctl, temp, scale)) est = trial_est;
+            }
+        }
+    }
+    eg_result_control(ctl, G.runs, (int)G.Y.l_blocks(), R);
+    memcpy(R.Scw, est.data(), sizeof(Sim3d) * (size_t)nv);
+    for (int v = 0; v < nv; ++v) eg_pose(est[(size_t)v], R.Tiw + (size_t)v * 16);
+    for (int k = 0; k < P.n_points; ++k) eg_point(eg_sim3(P.Scw)[P.ref[k]], est[(size_t)P.ref[k]], P.Xw + (size_t)k * 3, R.Xw + (size_t)k * 3);
+}
+
+static inline int eg_blocks(long long items) { return (int)std::max<long long>(1, (items + kEgThreads - 1) / kEgThreads); }
+
+}  // namespace aos2
+
+using namespace aos2;
+static_assert(sizeof(Sim3d) == 64, "a Sim3 is the 8 doubles of the C ABI");
+
+extern "C" {
+
+int aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, aos2_essential_graph_result_t *r, int n_problems)
+{
+    if (!s) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    int st = eg_check(p, r, n_problems, kEgMaxVertices);
+    if (st || n_problems == 0) return st;
+    const int n = n_problems;
+    // the symbolic phase, and everything the device reads, as one staged prefix of the arena
+    std::vector<EgHostGraph> G((size_t)n);
+    HostArena H;
+    struct Off { size_t v0, v1, C, S_in, est, est_try, pert, J, E, hidx, free_v, slot_ptr, slot_list, b_ptr, b_list, colptr, rowidx, upd_ptr, upd_dst, Hv, b, L, y, x, Xw_in, ref, Tiw, Xw_out; };
+    std::vector<Off> offs((size_t)n);
+    size_t budget = kEgArenaMax;
+    for (int i = 0; i < n; ++i) {
+        const aos2_essential_graph_problem_t &P = p[i];
+        EgHostGraph &g = G[(size_t)i];
+        eg_indices(P, g);
+        const size_t fixed_bytes = (size_t)P.n_vertices * (sizeof(Sim3d) * (3 + kEgPert) + 64 + 8) + (size_t)P.n_edges * (98 * 8 + 56 + 64 + 8 + 40) +
+                                   (size_t)P.n_points * 28 + 64 * 256;
+        if (fixed_bytes > budget || (g.runs && !eg_symbolic(g.nf, g.hi, g.lo, budget - fixed_bytes, g.Y))) {
+            set_error("problem %d: the graph and its factor do not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
+            return AOS2_ERR_EG_MEMORY;
+        }
+        if (!g.runs) {
+            g.Y = EgSymbolic();
+            g.Y.nf = g.nf;
+            g.Y.colptr.assign((size_t)g.nf + 1, 0);
+            g.Y.upd_ptr.assign((size_t)g.nf + 1, 0);
+        }
+        const size_t taken = fixed_bytes + (g.Y.l_blocks() + (size_t)g.nf) * 49 * 8 * 2 + g.Y.upd_dst.size() * 4;
+        if (taken > budget) {   // (a problem without LM keeps its diagonal blocks too)
+            set_error("problem %d: the batch does not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
+            return AOS2_ERR_EG_MEMORY;
+        }
+        budget -= taken;
+        eg_lists(P, g);
+    }
+    auto push_v = [&H](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
+    std::vector<EgControl> ctl0((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const aos2_essential_graph_problem_t &P = p[i];
+        const EgHostGraph &g = G[(size_t)i];
+        Off &o = offs[(size_t)i];
+        const size_t nv = (size_t)P.n_vertices, ne = (size_t)P.n_edges, np = (size_t)P.n_points;
+        o.v0 = H.push(P.v0, 4 * ne);
+        o.v1 = H.push(P.v1, 4 * ne);
+        o.C = H.push(P.Sji, 64 * ne);
+        o.S_in = H.push(P.Scw, 64 * nv);
+        o.est_try = H.push(P.Scw, 64 * nv);
+        o.hidx = push_v(g.hidx);
+        o.free_v = push_v(g.free_v);
+        o.slot_ptr = push_v(g.slot_ptr);
+        o.slot_list = push_v(g.slot_list);
+        o.b_ptr = push_v(g.b_ptr);
+        o.b_list = push_v(g.b_list);
+        o.colptr = push_v(g.Y.colptr);
+        o.rowidx = push_v(g.Y.rowidx);
+        o.upd_ptr = push_v(g.Y.upd_ptr);
+        o.upd_dst = push_v(g.Y.upd_dst);
+        o.Xw_in = H.push(P.Xw, 12 * np);
+        o.ref = H.push(P.ref, 4 * np);
+        eg_control_init(ctl0[(size_t)i], P.iterations, g.runs);
+    }
+    std::vector<EgDev> dev((size_t)n);
+    memset((void *)dev.data(), 0, sizeof(EgDev) * (size_t)n);
+    const size_t o_probs = H.push(dev.data(), sizeof(EgDev) * (size_t)n);
+    // what comes back, neighbours in the arena: the control words first (read once per iteration), then per problem Scw, Tiw, Xw.
+    // The estimates and the control words are staged (inputs), the rest is scratch.
+    const size_t o_ctl = H.push(ctl0.data(), sizeof(EgControl) * (size_t)n);
+    for (int i = 0; i < n; ++i) offs[(size_t)i].est = H.push(p[i].Scw, 64 * (size_t)p[i].n_vertices);
+    const size_t in_bytes = H.host_size;
+    for (int i = 0; i < n; ++i) {
+        offs[(size_t)i].Tiw = H.push(nullptr, 64 * (size_t)p[i].n_vertices);
+        offs[(size_t)i].Xw_out = H.push(nullptr, 12 * (size_t)p[i].n_points);
+    }
+    const size_t res_bytes = H.size - o_ctl;
+    for (int i = 0; i < n; ++i) {
+        const EgHostGraph &g = G[(size_t)i];
+        Off &o = offs[(size_t)i];
+        const size_t nv = (size_t)p[i].n_vertices, ne = (size_t)p[i].n_edges, n_slots = (size_t)g.nf + g.Y.l_blocks(), nx = 7 * (size_t)g.nf;
+        o.pert = H.push(nullptr, sizeof(Sim3d) * kEgPert * nv);
+        o.J = H.push(nullptr, 98 * 8 * ne);
+        o.E = H.push(nullptr, 56 * ne);
+        o.Hv = H.push(nullptr, 392 * n_slots);
+        o.L = H.push(nullptr, 392 * n_slots);
+        o.b = H.push(nullptr, 8 * nx);
+        o.y = H.push(nullptr, 8 * nx);
+        o.x = H.push(nullptr, 8 * nx);
+    }
+    if (H.size + 256 > kEgArenaMax + ((size_t)64 << 20)) {
+        set_error("the batch does not fit the %zu MiB a call may take", kEgArenaMax >> 20);
+        return AOS2_ERR_EG_MEMORY;
+    }
+    if ((st = lba_handle_init(s))) return st;
+    s->last_essential_graph_ms = 0;
+    if ((st = s->arena.alloc(H.size + 256))) return st;
+    if ((st = s->h_stage.alloc(res_bytes + 64))) return st;
+    uint8_t *base = s->arena.p;
+    long long max_v = 1, max_e = 1, max_asm = 1, max_fin = 1;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const aos2_essential_graph_problem_t &P = p[i];
+        const EgHostGraph &g = G[(size_t)i];
+        const Off &o = offs[(size_t)i];
+        EgDev &D = dev[(size_t)i];
+        D.nv = P.n_vertices; D.ne = P.n_edges; D.np = P.n_points; D.fixed = P.fixed; D.fix_scale = P.fix_scale != 0;
+        D.v0 = (const int32_t *)(base + o.v0); D.v1 = (const int32_t *)(base + o.v1);
+        D.C = (const Sim3d *)(base + o.C); D.S_in = (const Sim3d *)(base + o.S_in);
+        D.est = (Sim3d *)(base + o.est); D.est_try = (Sim3d *)(base + o.est_try); D.pert = (Sim3d *)(base + o.pert);
+        D.J = (double *)(base + o.J); D.E = (double *)(base + o.E);
+        D.hidx = (const int32_t *)(base + o.hidx); D.free_v = (const int32_t *)(base + o.free_v);
+        D.slot_ptr = (const int32_t *)(base + o.slot_ptr); D.slot_list = (const int32_t *)(base + o.slot_list);
+        D.b_ptr = (const int32_t *)(base + o.b_ptr); D.b_list = (const int32_t *)(base + o.b_list);
+        D.sys.nf = g.nf; D.sys.n_slots = g.nf + (int32_t)g.Y.l_blocks();
+        D.sys.colptr = (const int32_t *)(base + o.colptr); D.sys.rowidx = (const int32_t *)(base + o.rowidx);
+        D.sys.upd_ptr = (const int32_t *)(base + o.upd_ptr); D.sys.upd_dst = (const int32_t *)(base + o.upd_dst);
+        D.sys.H = (const double *)(base + o.Hv); D.sys.b = (const double *)(base + o.b);
+        D.sys.L = (double *)(base + o.L); D.sys.y = (double *)(base + o.y); D.sys.x = (double *)(base + o.x);
+        D.ctl = (EgControl *)(base + o_ctl) + i;
+        D.Xw_in = (const float *)(base + o.Xw_in); D.ref = (const int32_t *)(base + o.ref);
+        D.Tiw = (float *)(base + o.Tiw); D.Xw_out = (float *)(base + o.Xw_out);
+        max_v = std::max<long long>(max_v, P.n_vertices);
+        max_e = std::max<long long>(max_e, P.n_edges);
+        max_asm = std::max<long long>(max_asm, (long long)D.sys.n_slots * 49 + 7LL * g.nf);
+        max_fin = std::max<long long>(max_fin, std::max(P.n_vertices, P.n_points));
+        any = any || g.runs;
+    }
+    memcpy(H.own.data() + o_probs, dev.data(), sizeof(EgDev) * (size_t)n);
+    hipStream_t q = s->stream;
+    const EgDev *dprobs = (const EgDev *)(base + o_probs);
+    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
+    // x starts at zero: a first solve that fails applies the solver's vector as it stands
+    for (int i = 0; i < n; ++i)
+        if (G[(size_t)i].nf > 0) AOS2_HIP_CHECK(hipMemsetAsync(base + offs[(size_t)i].x, 0, 56 * (size_t)G[(size_t)i].nf, q));
+    EgControl *hctl = (EgControl *)s->h_stage.p;
+    int max_it = 0;
+    for (int i = 0; i < n; ++i)
+        if (G[(size_t)i].runs) max_it = std::max(max_it, (int)p[i].iterations);
+    // profiling (aos2_debug_essential_graph_profile): an event pair around every launch, summed per family after the call
+    std::vector<hipEvent_t> marks;
+    std::vector<int> mark_family;
+    auto family = [&](int f, bool begin) {
+        if (!s->eg_profile) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, q);
+        marks.push_back(e);
+        if (begin) mark_family.push_back(f);
+    };
+    for (int it = 0; any && it < max_it; ++it) {
+        family(0, true);
+        hipLaunchKernelGGL(k_eg_perturb, dim3(eg_blocks(max_v * 15), n), dim3(kEgThreads), 0, q, dprobs);
+        hipLaunchKernelGGL(k_eg_linearise, dim3(eg_blocks(max_e * 16), n), dim3(kEgThreads), 0, q, dprobs);
+        family(0, false);
+        family(1, true);
+        hipLaunchKernelGGL(k_eg_assemble, dim3(eg_blocks(max_asm), n), dim3(kEgThreads), 0, q, dprobs);
+        family(1, false);
+        family(3, true);
+        hipLaunchKernelGGL(k_eg_begin, dim3(n), dim3(kEgThreads), 0, q, dprobs);
+        family(3, false);
+        for (int t = 0; t < 10; ++t) {
+            family(2, true);
+            hipLaunchKernelGGL(k_eg_factor_solve, dim3(n), dim3(kEgThreads), 0, q, dprobs);
+            family(2, false);
+            family(3, true);
+            hipLaunchKernelGGL(k_eg_trial, dim3(n), dim3(kEgThreads), 0, q, dprobs);
+            family(3, false);
+        }
+        AOS2_HIP_CHECK(hipMemcpyAsync(hctl, base + o_ctl, sizeof(EgControl) * (size_t)n, hipMemcpyDeviceToHost, q));
+        AOS2_HIP_CHECK(hipStreamSynchronize(q));
+        AOS2_HIP_CHECK(hipGetLastError());
+        any = false;
+        for (int i = 0; i < n; ++i) any = any || hctl[i].running;
+    }
+    family(4, true);
+    hipLaunchKernelGGL(k_eg_finish, dim3(eg_blocks(max_fin), n), dim3(kEgThreads), 0, q, dprobs);
+    family(4, false);
+    AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, base + o_ctl, res_bytes, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    (void)hipEventElapsedTime(&s->last_essential_graph_ms, s->ev[0], s->ev[1]);
+    for (float &f : s->eg_family_ms) f = 0;
+    for (size_t k = 0; k < mark_family.size(); ++k) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, marks[2 * k], marks[2 * k + 1]) == hipSuccess) s->eg_family_ms[mark_family[k]] += ms;
+    }
+    for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+    const uint8_t *res = s->h_stage.p;
+    for (int i = 0; i < n; ++i) {
+        const Off &o = offs[(size_t)i];
+        EgControl c;
+        memcpy(&c, res + sizeof(EgControl) * (size_t)i, sizeof c);
+        eg_result_control(c, G[(size_t)i].runs, (int)G[(size_t)i].Y.l_blocks(), r[i]);
+        memcpy(r[i].Scw, res + (o.est - o_ctl), 64 * (size_t)p[i].n_vertices);
+        memcpy(r[i].Tiw, res + (o.Tiw - o_ctl), 64 * (size_t)p[i].n_vertices);
+        if (p[i].n_points > 0) memcpy(r[i].Xw, res + (o.Xw_out - o_ctl), 12 * (size_t)p[i].n_points);
+    }
+    return AOS2_OK;
+}
+
+float aos2_optimize_essential_graph_last_device_ms(const aos2_lba_t *s) { return s ? s->last_essential_graph_ms : 0.f; }
+
+int aos2_debug_essential_graph_profile(aos2_lba_t *s, int on, float *family_ms)
+{
+    if (!s) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    s->eg_profile = on != 0;
+    if (family_ms) memcpy(family_ms, s->eg_family_ms, sizeof s->eg_family_ms);
+    return AOS2_OK;
+}
+
+int aos2_debug_essential_graph_host(const aos2_essential_graph_problem_t *p, aos2_essential_graph_result_t *r, int n_problems)
+{
+    if (int st = eg_check(p, r, n_problems, kEgHostMaxVertices)) return st;
+    for (int i = 0; i < n_problems; ++i) {
+        EgHostGraph G;
+        eg_indices(p[i], G);
+        if (G.runs && !eg_symbolic(G.nf, G.hi, G.lo, kEgArenaMax, G.Y)) {
+            set_error("problem %d: the factor does not fit", i);
+            return AOS2_ERR_EG_MEMORY;
+        }
+        eg_host_one(p[i], G, r[i]);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_essential_graph_arith_host(int what, const double *in, int n, double *out)
+{
+    if (what < 0 || what > 2 || n < 0 || (n > 0 && (!in || !out))) {
+        set_error("bad argument (what 0..2, n >= 0, the arrays)");
+        return AOS2_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (what == 0)
+            eg_log(eg_sim3(in)[i], out + 7 * (size_t)i);
+        else if (what == 1) {
+            const Sim3d *S = eg_sim3(in) + 3 * (size_t)i;
+            Sim3d inv;
+            so_inverse(S[2], inv);
+            eg_residual(S[0], S[1], inv, out + 7 * (size_t)i);
+        } else
+            eg_lu3_solve(in + 12 * (size_t)i, in + 12 * (size_t)i + 9, out + 3 * (size_t)i);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols, const double *val,
+                                            const double *diag, const double *b, double lambda, double *x, int32_t *ok, int32_t *l_blocks)
+{
+    bool good = s && n_blocks >= 1 && n_blocks < kEgMaxVertices && n_off >= 0 && diag && b && x && ok && l_blocks && (n_off == 0 || (rows && cols && val));
+    for (int i = 0; good && i < n_off; ++i) good = cols[i] >= 0 && rows[i] > cols[i] && rows[i] < n_blocks;
+    if (!good) {
+        set_error("bad argument (1..%d blocks, triplets of the lower triangle, the arrays)", kEgMaxVertices - 1);
+        return AOS2_ERR_ARG;
+    }
+    EgSymbolic Y;
+    if (!eg_symbolic(n_blocks, std::vector<int32_t>(rows, rows + n_off), std::vector<int32_t>(cols, cols + n_off), kEgArenaMax, Y)) {
+        set_error("the factor does not fit");
+        return AOS2_ERR_EG_MEMORY;
+    }
+    const size_t n_slots = (size_t)n_blocks + Y.l_blocks(), nx = 7 * (size_t)n_blocks;
+    std::vector<double> Hv(n_slots * 49, 0.0);
+    memcpy(Hv.data(), diag, 392 * (size_t)n_blocks);
+    for (int i = 0; i < n_off; ++i) {
+        double *dst = Hv.data() + (size_t)Y.slot(rows[i], cols[i]) * 49;
+        for (int k = 0; k < 49; ++k) dst[k] += val[(size_t)i * 49 + k];
+    }
+    int st = lba_handle_init(s);
+    if (st) return st;
+    HostArena H;
+    auto push_v = [&H](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
+    const size_t o_colptr = push_v(Y.colptr), o_rowidx = push_v(Y.rowidx), o_upd_ptr = push_v(Y.upd_ptr), o_upd_dst = push_v(Y.upd_dst);
+    const size_t o_H = H.push(Hv.data(), 8 * Hv.size()), o_b = H.push(b, 8 * nx), o_x = H.push(x, 8 * nx);
+    const size_t in_bytes = H.host_size;
+    const size_t o_ok = H.push(nullptr, 4), o_L = H.push(nullptr, 8 * Hv.size()), o_y = H.push(nullptr, 8 * nx);
+    if ((st = s->arena.alloc(H.size + 256))) return st;
+    uint8_t *base = s->arena.p;
+    EgSystem S;
+    S.nf = n_blocks;
+    S.n_slots = (int32_t)n_slots;
+    S.colptr = (const int32_t *)(base + o_colptr); S.rowidx = (const int32_t *)(base + o_rowidx);
+    S.upd_ptr = (const int32_t *)(base + o_upd_ptr); S.upd_dst = (const int32_t *)(base + o_upd_dst);
+    S.H = (const double *)(base + o_H); S.b = (const double *)(base + o_b);
+    S.L = (double *)(base + o_L); S.y = (double *)(base + o_y); S.x = (double *)(base + o_x);
+    hipStream_t q = s->stream;
+    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(k_eg_factor_solve_tap, dim3(1), dim3(kEgThreads), 0, q, S, lambda, (int32_t *)(base + o_ok));
+    AOS2_HIP_CHECK(hipMemcpyAsync(x, base + o_x, 8 * nx, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(ok, base + o_ok, 4, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    *l_blocks = (int32_t)Y.l_blocks();
+    return AOS2_OK;
+}
+
+}  // extern "C"

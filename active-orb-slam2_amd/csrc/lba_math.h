@@ -380,6 +380,9 @@ struct aos2_lba {
     aos2::PinnedBuf<int32_t> h_abort;   // LocalBA: per-window abort words the kernels poll (mapped host memory)
     float last_pose_ms = 0;
     float last_sim3_opt_ms = 0;         // device time of the last aos2_optimize_sim3 (sim3_opt.hip)
+    float last_essential_graph_ms = 0;  // device time of the last aos2_optimize_essential_graph (essential_graph.hip)
+    bool eg_profile = false;            // ... with events around every launch, summed per kernel family (aos2_debug_essential_graph_profile)
+    float eg_family_ms[5] = {};
     int debug_stop_at_poll = 0;         // test hook: treat pbStopFlag as set from this poll on (0 = off)
     void *lba_cache = nullptr;          // LocalBA: host-side structure buffers kept between calls (lba.hip: LbaCache)
     int host_threads = 0;               // LocalBA: worker threads of the per-window host work (0 = default, aos2_lba_set_host_threads)

@@ -278,10 +278,15 @@ struct SoLm {
     // one trial: true = accepted (the estimate stays), false = pop.  rho is the caller's loop condition.
     __host__ __device__ bool decide(double tempChi, bool solved, const double *x, const double *Hb, double &rho)
     {
-        if (!solved) tempChi = 1.7976931348623157e308;
-        rho = currentChi - tempChi;
         double scale = 0.;
         for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + Hb[28 + j]);
+        return decide_scaled(tempChi, solved, scale, rho);
+    }
+    // the same decision for a system of any size: scale = the sum of x_j (lambda x_j + b_j) over all of it (essential_graph.h)
+    __host__ __device__ bool decide_scaled(double tempChi, bool solved, double scale, double &rho)
+    {
+        if (!solved) tempChi = 1.7976931348623157e308;
+        rho = currentChi - tempChi;
         scale += 1e-3;
         rho /= scale;
         if (rho > 0 && fabs(tempChi) <= 1.7976931348623157e308) {   // g2o_isfinite (false for NaN too)

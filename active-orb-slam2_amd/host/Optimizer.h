@@ -15,6 +15,7 @@
 #include <list>
 #include <map>
 #include <mutex>
+#include <set>
 #include <vector>
 
 #include "aos2_handles.h"
@@ -46,6 +47,11 @@ public:
     int static PoseOptimization(Frame *pFrame);
     static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
                             const bool bFixScale);
+#ifdef LOOPCLOSING_H   // (include/Optimizer.h:50-53 names LoopClosing::KeyFrameAndPose: declared where LoopClosing.h came first; body in OptimizeEssentialGraph.h)
+    void static OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose &CorrectedSim3, const std::map<KeyFrame *, std::set<KeyFrame *>> &LoopConnections,
+                                       const bool &bFixScale);
+#endif
 };
 
 // src/Optimizer.cc:454-779.  The window comes from aos2::LbaWindow (LbaWindow.h: one walk, hash membership, rows = the C ABI's arrays),

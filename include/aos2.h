@@ -947,6 +947,47 @@ int aos2_optimize_sim3(aos2_lba_t *s, const aos2_sim3_opt_problem_t *p, aos2_sim
 /* device time (ms, HIP events) of the kernel of the last aos2_optimize_sim3 call */
 float aos2_optimize_sim3_last_device_ms(const aos2_lba_t *s);
 
+/* void Optimizer::OptimizeEssentialGraph(Map*, KeyFrame *pLoopKF, KeyFrame *pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+ * bFixScale)  src/Optimizer.cc:782-1045, the pose graph of LoopClosing::CorrectLoop (:569): 20 Levenberg-Marquardt iterations over
+ * the Sim3 of every keyframe with a block-sparse LDL^T of H + lambda I in device memory (7x7 blocks, eliminated in ascending vertex
+ * order, no pivoting), then the SE3 poses (:992-1011) and the corrected map points (:1013-1044).  The caller gathers :798-984: the
+ * vertices, the edges in insertion order and their measurements.  The arithmetic is csrc/essential_graph.h (g2o's central-difference
+ * Jacobians kept). */
+#define AOS2_EG_OK 0
+#define AOS2_EG_NO_STEP 1         /* no trial of the first iteration was accepted: the poses are the input's */
+#define AOS2_ERR_EG_MEMORY (-6)   /* the factor of a graph (its fill) does not fit the memory a call may take, see aos2_last_error() */
+typedef struct {
+    int32_t n_vertices;          /* the not-bad keyframes, ascending mnId: index = g2o's hessian order */
+    const double *Scw;           /* [n_vertices][8]: q(x,y,z,w), t, s = vScw (:819-833) */
+    int32_t fixed;               /* index of pLoopKF */
+    int32_t n_edges;             /* in insertion order of :853-984 */
+    const int32_t *v0, *v1;      /* vertex 0 (nIDi), vertex 1 (nIDj / parent / loop edge / covisible) */
+    const double *Sji;           /* [n_edges][8]: the measurement, formed by the caller */
+    int32_t fix_scale, iterations;   /* bFixScale; 20 */
+    int32_t n_points;            /* map points that are not bad */
+    const float *Xw;             /* [n_points][3] GetWorldPos() */
+    const int32_t *ref;          /* [n_points] vertex index of nIDr (:1021-1030) */
+} aos2_essential_graph_problem_t;
+typedef struct {
+    double *Scw;                 /* [n_vertices][8] corrected Siw (the fixed one bit-identical to its input) */
+    float  *Tiw;                 /* [n_vertices][16] :1002-1008: R(q), t * (1./s) */
+    float  *Xw;                  /* [n_points][3] :1038-1040 */
+    double chi2_initial, chi2_final;
+    int32_t iterations, trials, rejected;   /* diagnostics, as in aos2_sim3_opt_result_t */
+    int32_t l_blocks;            /* 7x7 blocks of L below the diagonal: the fill the ordering produced */
+    int32_t status;              /* AOS2_EG_OK / AOS2_EG_NO_STEP (no trial of the first iteration was accepted) */
+} aos2_essential_graph_result_t;
+/* n_problems <= 16; 0 is AOS2_OK.  n_vertices <= 8192.  AOS2_ERR_ARG, before a device is looked for and with no result byte written:
+ * a NULL array with a non-zero count, a negative count, n_vertices < 1, fixed / v0 / v1 / ref out of range, v0 == v1, iterations < 1.
+ * AOS2_ERR_EG_MEMORY, before anything is enqueued: the memory of L is sized by the symbolic phase and the call's arena would pass
+ * 2 GiB.  n_edges == 0 or n_vertices == 1: no LM runs (chi2 = 0, no iterations), poses and points go through the recovery arithmetic
+ * with Scw out = Scw in.  Results are a function of the problem alone: bit-identical from call to call and whatever else is in the
+ * batch (no floating-point atomics: every block of H, and b, is summed from a host-built list of its edges in edge order). */
+int   aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_problem_t *p,
+                                    aos2_essential_graph_result_t *r, int n_problems);
+/* device time (ms, HIP events: first upload done to last kernel done) of the last aos2_optimize_essential_graph call */
+float aos2_optimize_essential_graph_last_device_ms(const aos2_lba_t *s);
+
 /* ------------------------------------------------------------------------------------------
  * Device-resident frame batches: the per-frame chain of Tracking::Track (src/Tracking.cc:862-870, 963-1027, 1302-1352)
  *   ORBextractor::operator() -> Frame::Frame -> SearchByProjection(Current, Last) -> PoseOptimization
@@ -1248,6 +1289,24 @@ int aos2_debug_initializer_rng(int n, uint32_t *out);
 int aos2_debug_initializer_inv33(const float *S, float *inv, double *det);
 /* aos2_optimize_sim3 on the HOST: the same header (csrc/sim3_opt.h) run serially, edges summed in index order; needs no device */
 int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
+/* aos2_optimize_essential_graph on the HOST: the same header (csrc/essential_graph.h) run serially with a skyline LDL^T of the scalar
+ * system; n_vertices <= 512 (else AOS2_ERR_CAPACITY); needs no device.  l_blocks is what the device's symbolic phase gives. */
+int aos2_debug_essential_graph_host(const aos2_essential_graph_problem_t *p, aos2_essential_graph_result_t *r, int n_problems);
+/* pieces of csrc/essential_graph.h on the HOST, n cases: what = 0: Sim3::log, in [n][8] (q x y z w, t, s) -> out [n][7];
+ * what = 1: EdgeSim3::computeError log(C * S_v0 * S_v1^-1), in [n][3][8] (C, S_v0, S_v1) -> out [n][7];
+ * what = 2: W.lu().solve(t) of a 3x3, in [n][12] (W row-major, t) -> out [n][3] */
+int aos2_debug_essential_graph_arith_host(int what, const double *in, int n, double *out);
+/* on != 0: later aos2_optimize_essential_graph calls on `s` put HIP events around every launch (slower).  family_ms (may be NULL)
+ * receives the device ms of the last such call per kernel family: [0] k_eg_perturb + k_eg_linearise, [1] k_eg_assemble,
+ * [2] k_eg_factor_solve, [3] k_eg_begin + k_eg_trial, [4] k_eg_finish (launches that return at once included). */
+int aos2_debug_essential_graph_profile(aos2_lba_t *s, int on, float *family_ms);
+/* The symbolic phase and k_eg_factor_solve of csrc/essential_graph.hip alone: x = (A + lambda I)^-1 b for the symmetric matrix of
+ * n_blocks x n_blocks 7x7 blocks whose lower-triangle blocks are given as triplets (rows[i] > cols[i]; a pair named twice is summed in
+ * the order given; val [n_off][49] row-major), diag [n_blocks][49], b and x [7 n_blocks].  *ok = 0: a zero or NaN pivot, x is left
+ * as passed in.  *l_blocks = the blocks of L below the diagonal.  1 <= n_blocks <= 8191. */
+int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols,
+                                            const double *val, const double *diag, const double *b, double lambda, double *x,
+                                            int32_t *ok, int32_t *l_blocks);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
  * T_out[i] = exp(upd[i]) * T[i]  (upd: 6 doubles omega | upsilon, T: 7 doubles qx qy qz qw tx ty tz), and
  * x[i] = (H[i] + lambda[i] I)^-1 b[i] with Hb[i] = 21 doubles (upper triangle of H, row by row) + 6 doubles b;
