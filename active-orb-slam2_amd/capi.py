@@ -152,6 +152,11 @@ def lib():
         L.aos2_debug_essential_graph_profile.argtypes = [vp, ci, vp]
         L.aos2_debug_essential_graph_arith_host.argtypes = [ci, vp, ci, vp]
         L.aos2_debug_essential_graph_solve_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.aos2_global_bundle_adjustment.argtypes = [vp, vp, vp, vp]
+        L.aos2_debug_global_ba_host.argtypes = [vp, vp, vp, ci]
+        L.aos2_debug_global_ba_solve_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.aos2_debug_global_ba_reduced_device.argtypes = [vp, vp, vp, C.c_double, ci, vp, vp, vp]
+        L.aos2_debug_global_ba_profile.argtypes = [vp, ci, vp]
         if hasattr(L, "aos2_matcher_create"):
             L.aos2_matcher_create.argtypes = [cf, ci, ci, C.POINTER(vp)]
             L.aos2_matcher_destroy.argtypes = [vp]
@@ -1991,6 +1996,66 @@ class _PoseResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_bad", C.c_int32), ("n_inliers", C.c_int32)]
 
 
+class _GbaOptions(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("robust", C.c_int32), ("huber_mono", C.c_float), ("huber_stereo", C.c_float)]
+
+
+class _GbaResult(C.Structure):
+    _fields_ = [("pose_Tcw", C.c_void_p), ("point_xyz", C.c_void_p), ("point_included", C.c_void_p),
+                ("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),
+                ("final_lambda", C.c_double), ("polls", C.c_int32), ("stop_poll", C.c_int32), ("h_blocks", C.c_int32),
+                ("l_blocks", C.c_int32), ("ms_device", C.c_float), ("status", C.c_int32)]
+
+
+GBA_HUBER = (float(np.float32(np.sqrt(5.99))), float(np.float32(np.sqrt(7.815))))       # Optimizer.cc:85-86
+GBA_HUBER_LOCAL_BA = (float(np.float32(np.sqrt(5.991))), float(np.float32(np.sqrt(7.815))))   # Optimizer.cc:570-571: what the oracle uses
+_GBA_SENTINEL_INT = -12345
+
+
+def _gba_args(prob, iterations, robust, huber, stop_flag, sentinel=None):
+    """the three structs of aos2_global_bundle_adjustment for a synth_lba_problem()-style dict; `sentinel` pre-fills the result"""
+    keep = []
+    s, o, r = _LbaProblem(), _GbaOptions(), _GbaResult()
+    s.n_poses, s.n_points, s.n_edges = prob["n_poses"], prob["n_points"], prob["n_edges"]
+    for name, dt in (("pose_Tcw", np.float32), ("pose_fixed", np.uint8), ("pose_id", np.int64), ("point_xyz", np.float32),
+                     ("point_id", np.int64), ("edge_pose", np.int32), ("edge_point", np.int32), ("edge_obs", np.float32),
+                     ("edge_stereo", np.uint8), ("edge_inv_sigma2", np.float32)):
+        if prob.get(name) is None:   # (a test of the argument checks)
+            continue
+        a = np.ascontiguousarray(prob[name], dt)
+        keep.append(a)
+        setattr(s, name, a.ctypes.data)
+    s.fx, s.fy, s.cx, s.cy, s.bf = (float(np.float32(prob[k])) for k in ("fx", "fy", "cx", "cy", "bf"))
+    if stop_flag is not None:
+        keep.append(stop_flag)
+        s.stop_flag = stop_flag.ctypes.data
+    o.iterations, o.robust, o.huber_mono, o.huber_stereo = int(iterations), int(bool(robust)), float(huber[0]), float(huber[1])
+    fill = 0 if sentinel is None else sentinel
+    Tout = np.full((max(s.n_poses, 1), 16), fill, np.float32)
+    Pout = np.full((max(s.n_points, 1), 3), fill, np.float32)
+    inc = np.full(max(s.n_points, 1), 0 if sentinel is None else 77, np.uint8)
+    r.pose_Tcw, r.point_xyz, r.point_included = Tout.ctypes.data, Pout.ctypes.data, inc.ctypes.data
+    if sentinel is not None:
+        r.iterations = r.trials = r.status = _GBA_SENTINEL_INT
+    return s, o, r, keep, (Tout[: s.n_poses], Pout[: s.n_points], inc[: s.n_points])
+
+
+def _gba_result(r, arrs):
+    Tout, Pout, inc = arrs
+    return dict(status=r.status, pose_Tcw=Tout, point_xyz=Pout, point_included=inc, iterations=r.iterations, trials=r.trials,
+                chi2_initial=r.chi2_initial, chi2_final=r.chi2_final, final_lambda=r.final_lambda, polls=r.polls,
+                stop_poll=r.stop_poll, h_blocks=r.h_blocks, l_blocks=r.l_blocks, ms_device=r.ms_device)
+
+
+def debug_global_ba_host(prob, iterations=10, robust=False, huber=GBA_HUBER, stop_flag=None, stop_at_poll=0, sentinel=None):
+    """aos2_debug_global_ba_host: the arithmetic and the lists of the device path run serially on the CPU with a skyline solve -> the
+    fields of aos2_gba_result_t"""
+    s, o, r, keep, arrs = _gba_args(prob, iterations, robust, huber, stop_flag, sentinel)
+    debug_global_ba_host.last = (r, arrs)
+    _check(lib().aos2_debug_global_ba_host(C.byref(s), C.byref(o), C.byref(r), int(stop_at_poll)))
+    return _gba_result(r, arrs)
+
+
 def lba_host_phase(probs, threads):
     """aos2_lba_debug_host_phase: (build ms, stage ms) of the host part of a LocalBA batch; needs no device"""
     n = len(probs)
@@ -2142,6 +2207,44 @@ class LocalBA:
 
     def debug_stop_at_poll(self, poll):
         _check(self.L.aos2_lba_debug_stop_at_poll(self.h, int(poll)))
+
+    def GlobalBundleAdjustment(self, prob, iterations=10, robust=False, huber=GBA_HUBER, stop_flag=None, sentinel=None):
+        """aos2_global_bundle_adjustment: Optimizer::BundleAdjustment (src/Optimizer.cc:41-237) on a synth_lba_problem()-style dict.
+        The defaults are LoopClosing::RunGlobalBundleAdjustment's; `sentinel` pre-fills the result (kept in self.global_ba_last for a
+        caller that expects a refusal)"""
+        s, o, r, keep, arrs = _gba_args(prob, iterations, robust, huber, stop_flag, sentinel)
+        self.global_ba_last = (r, arrs)
+        _check(self.L.aos2_global_bundle_adjustment(self.h, C.byref(s), C.byref(o), C.byref(r)))
+        return _gba_result(r, arrs)
+
+    def global_ba_profile(self, on):
+        """aos2_debug_global_ba_profile: switch the per-family events on / off -> the family ms of the last profiled call (linearise +
+        sums, landmarks + update, assemble, factor_solve, begin + trial_edges + decide, prepare + finish)"""
+        ms = (C.c_float * 6)()
+        _check(self.L.aos2_debug_global_ba_profile(self.h, int(bool(on)), ms))
+        return [float(v) for v in ms]
+
+    def debug_global_ba_solve(self, n_blocks, rows, cols, val, diag, b, lam, x0=None):
+        """aos2_debug_global_ba_solve_device: the symbolic phase and k_gba_factor_solve alone (6x6 blocks) -> (x, ok, l_blocks); x0 =
+        what x holds before (kept when the solve fails)"""
+        rows, cols = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(cols, np.int32)
+        val = np.ascontiguousarray(val, np.float64).reshape(-1, 36)
+        diag, b = np.ascontiguousarray(diag, np.float64).reshape(-1, 36), np.ascontiguousarray(b, np.float64).reshape(-1)
+        if len(diag) != n_blocks or len(b) != 6 * n_blocks or not len(rows) == len(cols) == len(val):
+            raise ValueError("diag [n_blocks][36], b [6 n_blocks], rows / cols / val one per triplet")
+        x = np.zeros(6 * n_blocks) if x0 is None else np.array(x0, np.float64).reshape(6 * n_blocks)
+        ok, lb = C.c_int32(-1), C.c_int32(-1)
+        _check(self.L.aos2_debug_global_ba_solve_device(self.h, int(n_blocks), len(rows), _p(rows), _p(cols), _p(val), _p(diag), _p(b),
+                                                        float(lam), _p(x), C.byref(ok), C.byref(lb)))
+        return x, int(ok.value), int(lb.value)
+
+    def debug_global_ba_reduced(self, prob, lam, n_free, robust=False, huber=GBA_HUBER):
+        """aos2_debug_global_ba_reduced_device: the reduced camera system of the first linearisation at lambda = lam as the device
+        assembles it -> (S [6 n_free][6 n_free] with lam on its diagonal, bs [6 n_free], h_blocks)"""
+        s, o, r, keep, arrs = _gba_args(prob, 1, robust, huber, None)
+        S, bs, hb = np.zeros((6 * n_free, 6 * n_free)), np.zeros(6 * n_free), C.c_int32(-1)
+        _check(self.L.aos2_debug_global_ba_reduced_device(self.h, C.byref(s), C.byref(o), float(lam), int(n_free), _p(S), _p(bs), C.byref(hb)))
+        return S, bs, int(hb.value)
 
     def PoseOptimization(self, problems):
         """int Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:239-452) for one dict or a list of

@@ -157,25 +157,6 @@ __host__ __device__ inline double eg_block_term(const double *J, int kind, int a
     return kind == 0 ? eg_jtj(J0, J0, a, b) : kind == 1 ? eg_jtj(J1, J1, a, b) : kind == 2 ? eg_jtj(J0, J1, a, b) : eg_jtj(J1, J0, a, b);
 }
 
-// LDL^T of a symmetric 7x7 (row-major, the lower triangle is read) in place: the unit lower factor below the diagonal, the pivots
-// on it.  No pivoting.  false = a pivot is zero or NaN (LinearSolverEigen's failure); negative pivots pass, as they do there.
-__host__ __device__ inline bool eg_ldlt7(double *a)
-{
-    for (int j = 0; j < 7; ++j) {
-        const double d = a[j * 7 + j];
-        if (!(d == d) || d == 0) return false;
-        const double rd = 1.0 / d;
-        double w[7];
-        for (int r = j + 1; r < 7; ++r) {
-            w[r] = a[r * 7 + j];
-            a[r * 7 + j] = w[r] * rd;
-        }
-        for (int r = j + 1; r < 7; ++r)
-            for (int c = j + 1; c <= r; ++c) a[r * 7 + c] -= a[r * 7 + j] * w[c];
-    }
-    return true;
-}
-
 // the control state of one optimize(iterations) call: where the decisions of sim3_opt.h's SoLm are kept between the kernels
 struct EgControl {
     SoLm lm;

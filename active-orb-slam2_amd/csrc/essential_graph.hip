@@ -10,8 +10,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_ldlt.h"
 #include "essential_graph.h"
-#include "wave_ops.h"
 
 namespace aos2 {
 
@@ -19,15 +19,9 @@ constexpr int kEgThreads = 256, kEgRows = kEgThreads / 16;
 constexpr int kEgMaxVertices = 8192, kEgMaxProblems = 16, kEgHostMaxVertices = 512;
 constexpr size_t kEgArenaMax = (size_t)2 << 30;
 
-// (A + lambda I) x = b in 7x7 blocks.  Slot k < nf is the diagonal block of column k, slot nf + p the block rowidx[p] of the column c
-// with colptr[c] <= p < colptr[c + 1] (rows ascending, below the diagonal).  A block is 49 doubles, row-major.
-struct EgSystem {
-    int32_t nf, n_slots;
-    const int32_t *colptr, *rowidx;   // [nf + 1], [n_slots - nf]
-    const int32_t *upd_ptr, *upd_dst; // column k with rows r_0 < .. < r_{m-1}: upd_dst[upd_ptr[k] + j m - j (j - 1) / 2 + (i - j)] = the slot of block (r_i, r_j), i >= j
-    const double *H, *b;              // [n_slots][49], [7 nf]
-    double *L, *y, *x;                // the factor (same slots), the right-hand side on its way, the solution
-};
+// (A + lambda I) x = b in 7x7 blocks, block_ldlt.h
+using EgSystem = BlockSystem;
+static_assert(kEgThreads == kBlockLdltThreads, "k_eg_factor_solve is one workgroup of block_factor_solve");
 
 struct EgDev {
     int32_t nv, ne, np, fixed, fix_scale, pad;
@@ -151,110 +145,8 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_begin(const EgDev *__restrict
     if (threadIdx.x == 0) eg_iteration_begin(*P.ctl, chi[0]);
 }
 
-// Block-sparse LDL^T of H + lambda I in device memory and the solve, one workgroup per system, right-looking, no pivoting.  With
-// A = L D L^T, L's diagonal blocks the unit lower factors Ld_k of the 7x7 LDL^T and D the pivots, column k is
-//   1. Ld_k, D_k of the diagonal block (one thread, in LDS); z_k = Ld_k^-1 y_k
-//   2. L_rk = A_rk Ld_k^-T D_k^-1, a thread per row of a block; y_r -= L_rk z_k
-//   3. A_(ri, rj) -= L_(ri, k) D_k L_(rj, k)^T for every pair of rows of the column, a thread per entry
-// and afterwards x_k = Ld_k^-T (D_k^-1 z_k - sum over the column's rows of L_rk^T x_r) for k descending.  A zero or NaN pivot ends
-// it: solved = 0 and x keeps its values.
-__device__ __forceinline__ void eg_factor_solve(const EgSystem &S, double lambda, int32_t *solved)
-{
-    __shared__ double D[49], z[7], sums[8];
-    __shared__ int fail;
-    const int tid = threadIdx.x, nf = S.nf;
-    const size_t nL = (size_t)S.n_slots * 49, nD = (size_t)nf * 49;
-    for (size_t i = tid; i < nL; i += kEgThreads) {
-        double v = S.H[i];
-        if (i < nD && (i % 49) % 8 == 0) v += lambda;
-        S.L[i] = v;
-    }
-    for (int i = tid; i < 7 * nf; i += kEgThreads) S.y[i] = S.b[i];
-    if (tid == 0) fail = 0;
-    __syncthreads();
-    for (int k = 0; k < nf; ++k) {
-        if (tid < 49) D[tid] = S.L[(size_t)k * 49 + tid];
-        __syncthreads();
-        if (tid == 0) {
-            if (!eg_ldlt7(D)) fail = 1;
-            else {
-                double zz[7];
-                for (int r = 0; r < 7; ++r) {
-                    double s = S.y[7 * k + r];
-                    for (int m = 0; m < r; ++m) s -= D[r * 7 + m] * zz[m];
-                    zz[r] = s;
-                    z[r] = s;
-                }
-                for (int r = 0; r < 7; ++r) S.y[7 * k + r] = zz[r] / D[r * 7 + r];
-            }
-        }
-        __syncthreads();
-        if (fail) break;
-        if (tid < 49) S.L[(size_t)k * 49 + tid] = D[tid];
-        const int p0 = S.colptr[k], m = S.colptr[k + 1] - p0;
-        for (int it = tid; it < m * 7; it += kEgThreads) {
-            const int i = it / 7, a = it % 7;
-            double *blk = S.L + (size_t)(nf + p0 + i) * 49 + a * 7;
-            double w[7];
-            for (int c = 0; c < 7; ++c) {
-                double s = blk[c];
-                for (int q = 0; q < c; ++q) s -= w[q] * D[c * 7 + q];
-                w[c] = s;
-            }
-            double dot = 0;
-            for (int c = 0; c < 7; ++c) {
-                const double l = w[c] / D[c * 7 + c];
-                blk[c] = l;
-                dot += l * z[c];
-            }
-            S.y[7 * S.rowidx[p0 + i] + a] -= dot;
-        }
-        __syncthreads();
-        const int32_t *dst = S.upd_dst + S.upd_ptr[k];
-        for (int j = 0; j < m; ++j) {
-            const double *Lj = S.L + (size_t)(nf + p0 + j) * 49;
-            const int base = j * m - j * (j - 1) / 2;
-            for (int it = tid; it < (m - j) * 49; it += kEgThreads) {
-                const int i = j + it / 49, ent = it % 49, a = ent / 7, b = ent % 7;
-                const double *Li = S.L + (size_t)(nf + p0 + i) * 49 + a * 7;
-                double s = 0;
-                for (int c = 0; c < 7; ++c) s += (Li[c] * D[c * 7 + c]) * Lj[b * 7 + c];
-                S.L[(size_t)dst[base + (i - j)] * 49 + ent] -= s;
-            }
-        }
-        __syncthreads();
-    }
-    const bool ok = !fail;
-    if (ok) {
-        const int a = tid >> 4, l = tid & 15;
-        for (int k = nf - 1; k >= 0; --k) {
-            const int p0 = S.colptr[k], m = S.colptr[k + 1] - p0;
-            if (tid < 128) {   // two whole waves: row a < 7 of 16 lanes sums component a, a fixed lane of the row keeps it
-                double s = 0;
-                if (a < 7)
-                    for (int t = l; t < m * 7; t += 16) {
-                        const int i = t / 7, c = t % 7;
-                        s += S.L[(size_t)(nf + p0 + i) * 49 + c * 7 + a] * S.x[7 * S.rowidx[p0 + i] + c];
-                    }
-                s = row_sum_f64(s);
-                if (l == 0) sums[a] = s;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                const double *Ld = S.L + (size_t)k * 49;
-                double xv[7];
-                for (int r = 6; r >= 0; --r) {
-                    double s = S.y[7 * k + r] - sums[r];
-                    for (int q = r + 1; q < 7; ++q) s -= Ld[q * 7 + r] * xv[q];
-                    xv[r] = s;
-                }
-                for (int r = 0; r < 7; ++r) S.x[7 * k + r] = xv[r];
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) *solved = ok;
-}
+// Block-sparse LDL^T of H + lambda I in device memory and the solve, one workgroup per system: block_ldlt.h with 7x7 blocks
+__device__ __forceinline__ void eg_factor_solve(const EgSystem &S, double lambda, int32_t *solved) { block_factor_solve<7>(S, lambda, solved); }
 
 __global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve(const EgDev *__restrict__ probs)
 {
@@ -322,57 +214,10 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_finish(const EgDev *__restric
 }
 
 // ---------------------------------------------------------------------------------------------- the symbolic phase (host)
-struct EgSymbolic {
-    int nf = 0;
-    std::vector<int32_t> colptr, rowidx, upd_ptr, upd_dst;
-    size_t l_blocks() const { return rowidx.size(); }
-    int slot(int row, int col) const   // row > col, present in the pattern of L
-    {
-        const int32_t *b = rowidx.data() + colptr[col], *e = rowidx.data() + colptr[col + 1];
-        return nf + (int)(std::lower_bound(b, e, row) - rowidx.data());
-    }
-};
-
-// the pattern of L for the lower-triangle blocks (hi[i], lo[i]) eliminated in ascending order: a column's rows are those of A's
-// column and, but for the column itself, those of every child in the elimination tree (parent = the first row of the column).
-// false: the factor and its update table would take more than max_bytes.
+using EgSymbolic = BlockSymbolic;
 static bool eg_symbolic(int nf, const std::vector<int32_t> &hi, const std::vector<int32_t> &lo, size_t max_bytes, EgSymbolic &Y)
 {
-    Y.nf = nf;
-    std::vector<std::vector<int32_t>> rows((size_t)nf);
-    for (size_t i = 0; i < hi.size(); ++i) rows[(size_t)lo[i]].push_back(hi[i]);
-    size_t n_l = 0, n_upd = 0;
-    for (int k = 0; k < nf; ++k) {
-        std::vector<int32_t> &r = rows[(size_t)k];
-        std::sort(r.begin(), r.end());
-        r.erase(std::unique(r.begin(), r.end()), r.end());
-        if (r.size() > 1) {
-            std::vector<int32_t> &par = rows[(size_t)r[0]];
-            par.insert(par.end(), r.begin() + 1, r.end());
-        }
-        n_l += r.size();
-        n_upd += r.size() * (r.size() + 1) / 2;
-        if ((n_l + (size_t)nf) * 49 * 8 * 2 + n_upd * 4 > max_bytes) return false;
-    }
-    Y.colptr.assign((size_t)nf + 1, 0);
-    Y.rowidx.clear();
-    Y.rowidx.reserve(n_l);
-    for (int k = 0; k < nf; ++k) {
-        Y.rowidx.insert(Y.rowidx.end(), rows[(size_t)k].begin(), rows[(size_t)k].end());
-        Y.colptr[(size_t)k + 1] = (int32_t)Y.rowidx.size();
-    }
-    Y.upd_ptr.assign((size_t)nf + 1, 0);
-    Y.upd_dst.clear();
-    Y.upd_dst.reserve(n_upd);
-    for (int k = 0; k < nf; ++k) {
-        const std::vector<int32_t> &r = rows[(size_t)k];
-        for (size_t j = 0; j < r.size(); ++j) {
-            Y.upd_dst.push_back(r[j]);
-            for (size_t i = j + 1; i < r.size(); ++i) Y.upd_dst.push_back(Y.slot(r[i], r[j]));
-        }
-        Y.upd_ptr[(size_t)k + 1] = (int32_t)Y.upd_dst.size();
-    }
-    return true;
+    return block_symbolic(nf, hi, lo, 49, max_bytes, Y);
 }
 
 // one problem as the host sees it: the hessian indices, the lower-triangle pairs of its edges, the lists of the assembly
@@ -477,70 +322,6 @@ static void eg_result_control(const EgControl &c, bool ran, int l_blocks, aos2_e
 }
 
 // ---------------------------------------------------------------------------------------------- the host tap
-// the scalar system in skyline storage: row i keeps columns first[i] .. i
-struct EgSkyline {
-    int n = 0;
-    std::vector<int> first;
-    std::vector<size_t> off;
-    std::vector<double> A, L, d, tmp;
-    double &a(std::vector<double> &M, int i, int j) { return M[off[(size_t)i] + (size_t)(j - first[(size_t)i])]; }
-
-    void shape(const EgHostGraph &G)
-    {
-        std::vector<int> minblk((size_t)G.nf);
-        for (int h = 0; h < G.nf; ++h) minblk[(size_t)h] = h;
-        for (size_t i = 0; i < G.hi.size(); ++i) minblk[(size_t)G.hi[i]] = std::min(minblk[(size_t)G.hi[i]], (int)G.lo[i]);
-        n = 7 * G.nf;
-        first.resize((size_t)n);
-        off.resize((size_t)n + 1);
-        size_t total = 0;
-        for (int i = 0; i < n; ++i) {
-            first[(size_t)i] = 7 * minblk[(size_t)(i / 7)];
-            off[(size_t)i] = total;
-            total += (size_t)(i - first[(size_t)i] + 1);
-        }
-        off[(size_t)n] = total;
-        A.assign(total, 0.0);
-        L.assign(total, 0.0);
-        d.assign((size_t)n, 0.0);
-        tmp.assign((size_t)n, 0.0);
-    }
-    // (A + lambda I) x = b by LDL^T inside the envelope, row by row; false = a zero or NaN pivot, x keeps its values
-    bool solve(double lambda, const std::vector<double> &b, std::vector<double> &x)
-    {
-        L = A;
-        for (int i = 0; i < n; ++i) {
-            const int fi = first[(size_t)i];
-            for (int j = fi; j < i; ++j) {
-                double s = a(L, i, j);
-                for (int k = std::max(fi, first[(size_t)j]); k < j; ++k) s -= tmp[(size_t)k] * a(L, j, k);
-                tmp[(size_t)j] = s;
-            }
-            double di = a(L, i, i) + lambda;
-            for (int j = fi; j < i; ++j) {
-                const double l = tmp[(size_t)j] / d[(size_t)j];
-                a(L, i, j) = l;
-                di -= tmp[(size_t)j] * l;
-            }
-            if (!(di == di) || di == 0) return false;
-            d[(size_t)i] = di;
-        }
-        std::vector<double> y((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            double s = b[(size_t)i];
-            for (int j = first[(size_t)i]; j < i; ++j) s -= a(L, i, j) * y[(size_t)j];
-            y[(size_t)i] = s;
-        }
-        for (int i = 0; i < n; ++i) y[(size_t)i] /= d[(size_t)i];
-        for (int i = n - 1; i >= 0; --i) {
-            const double xi = y[(size_t)i];
-            for (int j = first[(size_t)i]; j < i; ++j) y[(size_t)j] -= a(L, i, j) * xi;
-        }
-        x = y;
-        return true;
-    }
-};
-
 static const Sim3d *eg_sim3(const double *p) { return reinterpret_cast<const Sim3d *>(p); }
 
 static void eg_host_one(const aos2_essential_graph_problem_t &P, EgHostGraph &G, aos2_essential_graph_result_t &R)
@@ -551,8 +332,8 @@ static void eg_host_one(const aos2_essential_graph_problem_t &P, EgHostGraph &G,
     EgControl ctl;
     eg_control_init(ctl, P.iterations, G.runs);
     if (G.runs) {
-        EgSkyline K;
-        K.shape(G);
+        SkylineLdlt K;
+        K.shape(G.nf, G.hi, G.lo, 7);
         std::vector<Sim3d> pert((size_t)nv * kEgPert);
         std::vector<double> J((size_t)ne * 98), E((size_t)ne * 7), b((size_t)K.n), x((size_t)K.n, 0.0);
         const bool fix = P.fix_scale != 0;

@@ -74,7 +74,7 @@ __host__ __device__ inline void se3_map(const double qt[7], const double X[3], d
 }
 
 // T <- exp(upd) * T  (VertexSE3Expmap::oplusImpl, SE3Quat::exp se3quat.h:223-257, operator* :104-110)
-__device__ inline void se3_oplus(const double upd[6], double T[7])
+__host__ __device__ inline void se3_oplus(const double upd[6], double T[7])
 {
     const double *omega = upd, *ups = upd + 3;
     const double theta = sqrt(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
@@ -266,7 +266,7 @@ __device__ __forceinline__ void se3_oplus_fast(const double upd[6], double T[7])
     for (int i = 0; i < 3; ++i) T[4 + i] = e[4 + i] + rt[i];
 }
 
-__device__ inline void mat3_inverse(const double m[9], double inv[9])
+__host__ __device__ inline void mat3_inverse(const double m[9], double inv[9])
 {
     const double c00 = m[4] * m[8] - m[5] * m[7];
     const double c10 = m[5] * m[6] - m[3] * m[8];
@@ -284,14 +284,14 @@ __device__ inline void mat3_inverse(const double m[9], double inv[9])
     inv[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
-__device__ inline double edge_chi2(const double *er, double w, int D)
+__host__ __device__ inline double edge_chi2(const double *er, double w, int D)
 {
     double s = 0;
     for (int i = 0; i < D; ++i) s += er[i] * (w * er[i]);
     return s;
 }
 
-__device__ inline void robustify(double e, double delta, double rho[2])
+__host__ __device__ inline void robustify(double e, double delta, double rho[2])
 {
     const double dsqr = delta * delta;
     if (e <= dsqr) {
@@ -383,6 +383,9 @@ struct aos2_lba {
     float last_essential_graph_ms = 0;  // device time of the last aos2_optimize_essential_graph (essential_graph.hip)
     bool eg_profile = false;            // ... with events around every launch, summed per kernel family (aos2_debug_essential_graph_profile)
     float eg_family_ms[5] = {};
+    float last_gba_ms = 0;              // device time of the last aos2_global_bundle_adjustment (global_ba.hip)
+    bool gba_profile = false;           // ... with events around every family of launches (aos2_debug_global_ba_profile)
+    float gba_family_ms[6] = {};
     int debug_stop_at_poll = 0;         // test hook: treat pbStopFlag as set from this poll on (0 = off)
     void *lba_cache = nullptr;          // LocalBA: host-side structure buffers kept between calls (lba.hip: LbaCache)
     int host_threads = 0;               // LocalBA: worker threads of the per-window host work (0 = default, aos2_lba_set_host_threads)

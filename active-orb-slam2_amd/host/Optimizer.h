@@ -43,6 +43,10 @@ namespace ORB_SLAM2 {
 
 class Optimizer {
 public:
+    // include/Optimizer.h:40-44; bodies in GlobalBundleAdjustment.h, which needs KeyFrame::mTcwGBA / MapPoint::mPosGBA
+    void static BundleAdjustment(const std::vector<KeyFrame *> &vpKF, const std::vector<MapPoint *> &vpMP, int nIterations = 5, bool *pbStopFlag = NULL,
+                                 const unsigned long nLoopKF = 0, const bool bRobust = true);
+    void static GlobalBundleAdjustemnt(Map *pMap, int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
     void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap);
     int static PoseOptimization(Frame *pFrame);
     static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,

@@ -889,6 +889,44 @@ int aos2_lba_debug_host_phase(const aos2_lba_problem_t *problems, int n_problems
 int aos2_lba_debug_stop_at_poll(aos2_lba_t *s, int poll);
 
 /* ------------------------------------------------------------------------------------------
+ * Optimizer::BundleAdjustment / GlobalBundleAdjustemnt  (include/Optimizer.h:40-44, src/Optimizer.cc:41-237): the whole map,
+ * called by LoopClosing::RunGlobalBundleAdjustment (10 iterations, not robust) and Tracking::CreateInitialMapMonocular
+ * (20 iterations, robust).  Exactly initializeOptimization(); optimize(iterations): one Levenberg-Marquardt run, no outlier
+ * pass.  The reduced camera system is block-sparse (6x6 blocks: pairs of free keyframes that share a map point) and is
+ * factorised in device memory in ascending keyframe order, so the number of keyframes is bounded by memory alone.
+ * The arithmetic is csrc/global_ba.h.
+ * ------------------------------------------------------------------------------------------ */
+#define AOS2_ERR_GBA_MEMORY (-7)   /* the map or the factor of its reduced camera system does not fit the memory a call may take, see aos2_last_error() */
+typedef struct {
+    int32_t iterations;          /* nIterations (>= 1) */
+    int32_t robust;              /* bRobust: Huber kernels on the edges */
+    float huber_mono, huber_stereo;   /* thHuber2D = sqrt(5.99), thHuber3D = sqrt(7.815) as float (:85-86); LocalBA's are sqrt(5.991), sqrt(7.815) */
+} aos2_gba_options_t;
+typedef struct {
+    float *pose_Tcw;             /* n_poses x 16 out: Converter::toCvMat(SE3Quat) of every vertex, the fixed ones included (:199-211) */
+    float *point_xyz;            /* n_points x 3 out (:223-234) */
+    uint8_t *point_included;     /* n_points out: 0 = the point has no edge (removeVertex, :175-179): point_xyz equals the input bit for bit */
+    int32_t iterations, trials;  /* what optimize() returned; Levenberg-Marquardt trial steps (solves) */
+    double chi2_initial, chi2_final;   /* activeRobustChi2 of the first linearisation / after the last accepted step */
+    double final_lambda;
+    int32_t polls, stop_poll;    /* evaluations of pbStopFlag (SparseOptimizer::terminate()); the one that first saw it set, 0 = never */
+    int32_t h_blocks, l_blocks;  /* 6x6 blocks below the diagonal of the reduced system / of its factor (the fill of ascending order) */
+    float ms_device;             /* device time of the call (HIP events: upload done to last kernel done) */
+    int32_t status;              /* AOS2_OK */
+} aos2_gba_result_t;
+/* One map per call, on the problem description of LocalBundleAdjustment (iters_first / iters_second are ignored): hessian order =
+ * free keyframes with an edge by ascending pose_id, then points with an edge by ascending point_id; edges in array order (the
+ * caller emits a point's observations by ascending KeyFrame::mnId).  The stop flag is not read on entry: its first evaluation is
+ * the head of optimize()'s loop, the later ones the trial loop's and the loop head's again, as in g2o.  A set flag ends the call
+ * with the estimates of the last accepted step (AOS2_OK, stop_poll set); aos2_lba_debug_stop_at_poll applies.  n_edges == 0:
+ * nothing is optimised (iterations = 0), the poses go through the two conversions.
+ * AOS2_ERR_ARG, before anything runs and with no result byte written: iterations < 1, a delta <= 0, a NULL array with a non-zero
+ * count, an edge index out of range.  AOS2_ERR_GBA_MEMORY, before anything is enqueued: the call's arena would pass 2 GiB.
+ * A zero or NaN pivot is a failed trial (LinearSolverEigen's failure).  Results are a function of the problem alone: bit-identical
+ * from call to call (no floating-point atomics; every sum is taken in a fixed order from host-built lists). */
+int aos2_global_bundle_adjustment(aos2_lba_t *s, const aos2_lba_problem_t *p, const aos2_gba_options_t *o, aos2_gba_result_t *r);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer::PoseOptimization  (include/Optimizer.h:46, src/Optimizer.cc:239-452) -- SURVEY §8(f)
  * rank 1, called 1-3 times per frame right after each matcher call (Tracking.cc:870,994,1039).
  * One workgroup per frame runs the whole procedure on the device (4 rounds of up to 10
@@ -1307,6 +1345,26 @@ int aos2_debug_essential_graph_profile(aos2_lba_t *s, int on, float *family_ms);
 int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols,
                                             const double *val, const double *diag, const double *b, double lambda, double *x,
                                             int32_t *ok, int32_t *l_blocks);
+/* aos2_global_bundle_adjustment on the HOST: the same header (csrc/global_ba.h) and the same per-item functions run serially, the
+ * reduced system solved by a skyline LDL^T of the scalar system; n_poses <= 2048 (else AOS2_ERR_CAPACITY); needs no device.
+ * stop_at_poll as aos2_lba_debug_stop_at_poll.  h_blocks / l_blocks are what the device's symbolic phase gives; ms_device = 0. */
+int aos2_debug_global_ba_host(const aos2_lba_problem_t *p, const aos2_gba_options_t *o, aos2_gba_result_t *r, int stop_at_poll);
+/* The symbolic phase and k_gba_factor_solve of csrc/global_ba.hip alone: aos2_debug_essential_graph_solve_device for 6x6 blocks
+ * (val [n_off][36], diag [n_blocks][36], b and x [6 n_blocks]); 1 <= n_blocks <= 8192. */
+int aos2_debug_global_ba_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols,
+                                      const double *val, const double *diag, const double *b, double lambda, double *x,
+                                      int32_t *ok, int32_t *l_blocks);
+/* The reduced camera system of the FIRST linearisation at `lambda` as the device assembles it (k_gba_linearise, k_gba_sums,
+ * k_gba_landmarks, k_gba_assemble): S [6 n_free][6 n_free] row-major, both triangles filled from the stored lower one, with lambda on
+ * its diagonal (the Schur complement of H + lambda I), and bs [6 n_free].  n_free = the free keyframes with an edge, 1..512 (else
+ * AOS2_ERR_ARG); *h_blocks = its blocks below the diagonal. */
+int aos2_debug_global_ba_reduced_device(aos2_lba_t *s, const aos2_lba_problem_t *p, const aos2_gba_options_t *o, double lambda,
+                                        int32_t n_free, double *S, double *bs, int32_t *h_blocks);
+/* on != 0: later aos2_global_bundle_adjustment calls on `s` put HIP events around every family of launches (slower).  family_ms (may
+ * be NULL) receives the device ms of the last such call: [0] k_gba_linearise + k_gba_sums, [1] k_gba_landmarks + k_gba_update,
+ * [2] k_gba_assemble, [3] k_gba_factor_solve, [4] k_gba_begin + k_gba_trial_edges + k_gba_decide, [5] k_gba_prepare + k_gba_finish
+ * (launches that return at once included). */
+int aos2_debug_global_ba_profile(aos2_lba_t *s, int on, float *family_ms);
 /* building blocks of the pose solver (csrc/pose_opt.hip) on the device, n independent cases:
  * T_out[i] = exp(upd[i]) * T[i]  (upd: 6 doubles omega | upsilon, T: 7 doubles qx qy qz qw tx ty tz), and
  * x[i] = (H[i] + lambda[i] I)^-1 b[i] with Hb[i] = 21 doubles (upper triangle of H, row by row) + 6 doubles b;
