@@ -152,6 +152,8 @@ def lib():
         L.aos2_debug_essential_graph_profile.argtypes = [vp, ci, vp]
         L.aos2_debug_essential_graph_arith_host.argtypes = [ci, vp, ci, vp]
         L.aos2_debug_essential_graph_solve_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.aos2_debug_essential_graph_linearised_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.aos2_debug_essential_graph_trial_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.aos2_global_bundle_adjustment.argtypes = [vp, vp, vp, vp]
         L.aos2_debug_global_ba_host.argtypes = [vp, vp, vp, ci]
         L.aos2_debug_global_ba_solve_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
@@ -2319,6 +2321,36 @@ class LocalBA:
         _check(self.L.aos2_debug_essential_graph_solve_device(self.h, int(n_blocks), len(rows), _p(rows), _p(cols), _p(val), _p(diag), _p(b),
                                                               float(lam), _p(x), C.byref(ok), C.byref(lb)))
         return x, int(ok.value), int(lb.value)
+
+    def debug_essential_graph_linearised(self, problem):
+        """aos2_debug_essential_graph_linearised_device: the first linearisation of one problem as the device forms it -> dict(J
+        [ne][2][7][7] (a fixed side keeps the bytes 0x5A), E [ne][7], H [7 nf][7 nf], b [7 nf], chi2, chi2_initial, l_blocks)"""
+        P, R, keep, outs = _essential_graph_args([problem])
+        ne, nf = max(int(P[0].n_edges), 0), max(int(P[0].n_vertices) - 1, 0)
+        J, E = np.zeros((ne, 2, 7, 7)), np.zeros((ne, 7))
+        H, b, chi = np.zeros((7 * nf, 7 * nf)), np.zeros(7 * nf), np.zeros(2)
+        lb = C.c_int32(-1)
+        _check(self.L.aos2_debug_essential_graph_linearised_device(self.h, P, _p(J), _p(E), _p(H), _p(b), _p(chi), C.byref(lb)))
+        return dict(J=J, E=E, H=H, b=b, chi2=float(chi[0]), chi2_initial=float(chi[1]), l_blocks=int(lb.value))
+
+    EG_CONTROL_D = ("lambda", "ni", "currentChi", "iniChi", "rho", "chi2_initial")
+    EG_CONTROL_I = ("nBad", "qmax", "open", "running", "solved", "max_iterations", "iterations", "trials", "rejected", "accepted_first")
+
+    def debug_essential_graph_trial(self, problem, x, lam, current_chi, ni=2.0, solved=1, iterations=0, qmax=0):
+        """aos2_debug_essential_graph_trial_device: one k_eg_trial on one problem with the solver's vector x and the seeded control
+        words -> dict(est_try, est [nv][8], control (the words of EG_CONTROL_D / EG_CONTROL_I by name), tempChi, scale)"""
+        P, R, keep, outs = _essential_graph_args([problem])
+        nv, nf = max(int(P[0].n_vertices), 0), max(int(P[0].n_vertices) - 1, 0)
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        if len(x) != 7 * nf:
+            raise ValueError("x [7 (n_vertices - 1)]")
+        seed_d, seed_i = np.array([lam, current_chi, ni], np.float64), np.array([solved, iterations, qmax], np.int32)
+        est_try, est = np.zeros((nv, 8)), np.zeros((nv, 8))
+        cd, ci, sums = np.zeros(6), np.zeros(10, np.int32), np.zeros(2)
+        _check(self.L.aos2_debug_essential_graph_trial_device(self.h, P, _p(x), _p(seed_d), _p(seed_i), _p(est_try), _p(est), _p(cd), _p(ci), _p(sums)))
+        control = dict(zip(self.EG_CONTROL_D, (float(v) for v in cd)))
+        control.update(zip(self.EG_CONTROL_I, (int(v) for v in ci)))
+        return dict(est_try=est_try, est=est, control=control, tempChi=float(sums[0]), scale=float(sums[1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -160,12 +160,13 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve(const EgDev *__r
 __global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve_tap(EgSystem S, double lambda, int32_t *solved) { eg_factor_solve(S, lambda, solved); }
 
 // One trial, one workgroup per problem: the estimates of the free vertices after oplus(x) into est_try, the residuals and chi2 (edge e
-// in thread e % 256), the decision; est_try becomes est when the trial is accepted.
-__global__ __launch_bounds__(kEgThreads) void k_eg_trial(const EgDev *__restrict__ probs)
+// in thread e % 256), the decision; est_try becomes est when the trial is accepted.  kTap: the two sums the decision is taken on go to
+// tap[0], tap[1] as well (aos2_debug_essential_graph_trial_device).
+template <bool kTap>
+__device__ __forceinline__ void eg_trial(const EgDev &P, double *tap)
 {
     __shared__ double part[kEgRows * 2];
     __shared__ int accepted;
-    const EgDev &P = probs[blockIdx.x];
     EgControl *ctl = P.ctl;
     if (!ctl->running || !ctl->open) return;
     const int tid = threadIdx.x, nf = P.sys.nf;
@@ -192,6 +193,10 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_trial(const EgDev *__restrict
         sum[0] += eg_chi2(er);
     }
     eg_block_sum(sum, part);
+    if (kTap && tid == 0) {
+        tap[0] = sum[0];
+        tap[1] = sum[1];
+    }
     if (tid == 0) accepted = eg_trial_decide(*ctl, sum[0], sum[1]);
     __syncthreads();
     if (accepted)
@@ -200,6 +205,11 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_trial(const EgDev *__restrict
             P.est[v] = P.est_try[v];
         }
 }
+
+__global__ __launch_bounds__(kEgThreads) void k_eg_trial(const EgDev *__restrict__ probs) { eg_trial<false>(probs[blockIdx.x], nullptr); }
+
+// the same on one problem, with the sums (aos2_debug_essential_graph_trial_device)
+__global__ __launch_bounds__(kEgThreads) void k_eg_trial_tap(const EgDev *__restrict__ probs, double *tap) { eg_trial<true>(probs[0], tap); }
 
 // grid over max(vertices, points): the SE3 pose of a vertex, the corrected position of a point
 __global__ __launch_bounds__(kEgThreads) void k_eg_finish(const EgDev *__restrict__ probs)
@@ -321,6 +331,139 @@ static void eg_result_control(const EgControl &c, bool ran, int l_blocks, aos2_e
     R.status = ran && c.accepted_first == 0 ? AOS2_EG_NO_STEP : AOS2_EG_OK;
 }
 
+// the symbolic phase of a batch inside the memory a call may take: the indices, the pattern of L and the lists of every problem
+static int eg_host_phase(const aos2_essential_graph_problem_t *p, int n, std::vector<EgHostGraph> &G)
+{
+    size_t budget = kEgArenaMax;
+    for (int i = 0; i < n; ++i) {
+        const aos2_essential_graph_problem_t &P = p[i];
+        EgHostGraph &g = G[(size_t)i];
+        eg_indices(P, g);
+        const size_t fixed_bytes = (size_t)P.n_vertices * (sizeof(Sim3d) * (3 + kEgPert) + 64 + 8) + (size_t)P.n_edges * (98 * 8 + 56 + 64 + 8 + 40) +
+                                   (size_t)P.n_points * 28 + 64 * 256;
+        if (fixed_bytes > budget || (g.runs && !eg_symbolic(g.nf, g.hi, g.lo, budget - fixed_bytes, g.Y))) {
+            set_error("problem %d: the graph and its factor do not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
+            return AOS2_ERR_EG_MEMORY;
+        }
+        if (!g.runs) {
+            g.Y = EgSymbolic();
+            g.Y.nf = g.nf;
+            g.Y.colptr.assign((size_t)g.nf + 1, 0);
+            g.Y.upd_ptr.assign((size_t)g.nf + 1, 0);
+        }
+        const size_t taken = fixed_bytes + (g.Y.l_blocks() + (size_t)g.nf) * 49 * 8 * 2 + g.Y.upd_dst.size() * 4;
+        if (taken > budget) {   // (a problem without LM keeps its diagonal blocks too)
+            set_error("problem %d: the batch does not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
+            return AOS2_ERR_EG_MEMORY;
+        }
+        budget -= taken;
+        eg_lists(P, g);
+    }
+    return AOS2_OK;
+}
+
+// The layout of a call: what the host stages (a prefix of the arena: per problem the graph and its lists, the EgDev table, the
+// control words, the estimates), what comes back (neighbours, read together: the control words first, read once per iteration, then
+// per problem Scw, Tiw, Xw) and the scratch.  The call and the taps share it.
+struct EgLayout {
+    struct Off { size_t v0, v1, C, S_in, est, est_try, pert, J, E, hidx, free_v, slot_ptr, slot_list, b_ptr, b_list, colptr, rowidx, upd_ptr, upd_dst, Hv, b, L, y, x, Xw_in, ref, Tiw, Xw_out; };
+    HostArena H;
+    std::vector<Off> offs;
+    size_t o_probs = 0, o_ctl = 0, in_bytes = 0, res_bytes = 0;
+    long long max_v = 1, max_e = 1, max_asm = 1, max_fin = 1;   // the largest grids of the batch: vertices, edges, entries of H and b, finish items
+
+    void plan(const aos2_essential_graph_problem_t *p, int n, const std::vector<EgHostGraph> &G)
+    {
+        auto push_v = [this](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
+        offs.assign((size_t)n, Off());
+        std::vector<EgControl> ctl0((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const aos2_essential_graph_problem_t &P = p[i];
+            const EgHostGraph &g = G[(size_t)i];
+            Off &o = offs[(size_t)i];
+            const size_t nv = (size_t)P.n_vertices, ne = (size_t)P.n_edges, np = (size_t)P.n_points;
+            o.v0 = H.push(P.v0, 4 * ne);
+            o.v1 = H.push(P.v1, 4 * ne);
+            o.C = H.push(P.Sji, 64 * ne);
+            o.S_in = H.push(P.Scw, 64 * nv);
+            o.est_try = H.push(P.Scw, 64 * nv);
+            o.hidx = push_v(g.hidx);
+            o.free_v = push_v(g.free_v);
+            o.slot_ptr = push_v(g.slot_ptr);
+            o.slot_list = push_v(g.slot_list);
+            o.b_ptr = push_v(g.b_ptr);
+            o.b_list = push_v(g.b_list);
+            o.colptr = push_v(g.Y.colptr);
+            o.rowidx = push_v(g.Y.rowidx);
+            o.upd_ptr = push_v(g.Y.upd_ptr);
+            o.upd_dst = push_v(g.Y.upd_dst);
+            o.Xw_in = H.push(P.Xw, 12 * np);
+            o.ref = H.push(P.ref, 4 * np);
+            eg_control_init(ctl0[(size_t)i], P.iterations, g.runs);
+            max_v = std::max<long long>(max_v, P.n_vertices);
+            max_e = std::max<long long>(max_e, P.n_edges);
+            max_asm = std::max<long long>(max_asm, ((long long)g.nf + (long long)g.Y.l_blocks()) * 49 + 7LL * g.nf);
+            max_fin = std::max<long long>(max_fin, std::max(P.n_vertices, P.n_points));
+        }
+        std::vector<EgDev> zero((size_t)n);
+        memset((void *)zero.data(), 0, sizeof(EgDev) * (size_t)n);
+        o_probs = H.push(zero.data(), sizeof(EgDev) * (size_t)n);
+        // The estimates and the control words are staged (inputs), the rest is scratch.
+        o_ctl = H.push(ctl0.data(), sizeof(EgControl) * (size_t)n);
+        for (int i = 0; i < n; ++i) offs[(size_t)i].est = H.push(p[i].Scw, 64 * (size_t)p[i].n_vertices);
+        in_bytes = H.host_size;
+        for (int i = 0; i < n; ++i) {
+            offs[(size_t)i].Tiw = H.push(nullptr, 64 * (size_t)p[i].n_vertices);
+            offs[(size_t)i].Xw_out = H.push(nullptr, 12 * (size_t)p[i].n_points);
+        }
+        res_bytes = H.size - o_ctl;
+        for (int i = 0; i < n; ++i) {
+            const EgHostGraph &g = G[(size_t)i];
+            Off &o = offs[(size_t)i];
+            const size_t nv = (size_t)p[i].n_vertices, ne = (size_t)p[i].n_edges, n_slots = (size_t)g.nf + g.Y.l_blocks(), nx = 7 * (size_t)g.nf;
+            o.pert = H.push(nullptr, sizeof(Sim3d) * kEgPert * nv);
+            o.J = H.push(nullptr, 98 * 8 * ne);
+            o.E = H.push(nullptr, 56 * ne);
+            o.Hv = H.push(nullptr, 392 * n_slots);
+            o.L = H.push(nullptr, 392 * n_slots);
+            o.b = H.push(nullptr, 8 * nx);
+            o.y = H.push(nullptr, 8 * nx);
+            o.x = H.push(nullptr, 8 * nx);
+        }
+    }
+
+    // the EgDev table for the arena at `base`, written into the staged prefix -> where the kernels find it
+    const EgDev *bind(const aos2_essential_graph_problem_t *p, int n, const std::vector<EgHostGraph> &G, uint8_t *base)
+    {
+        std::vector<EgDev> dev((size_t)n);
+        memset((void *)dev.data(), 0, sizeof(EgDev) * (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const aos2_essential_graph_problem_t &P = p[i];
+            const EgHostGraph &g = G[(size_t)i];
+            const Off &o = offs[(size_t)i];
+            EgDev &D = dev[(size_t)i];
+            D.nv = P.n_vertices; D.ne = P.n_edges; D.np = P.n_points; D.fixed = P.fixed; D.fix_scale = P.fix_scale != 0;
+            D.v0 = (const int32_t *)(base + o.v0); D.v1 = (const int32_t *)(base + o.v1);
+            D.C = (const Sim3d *)(base + o.C); D.S_in = (const Sim3d *)(base + o.S_in);
+            D.est = (Sim3d *)(base + o.est); D.est_try = (Sim3d *)(base + o.est_try); D.pert = (Sim3d *)(base + o.pert);
+            D.J = (double *)(base + o.J); D.E = (double *)(base + o.E);
+            D.hidx = (const int32_t *)(base + o.hidx); D.free_v = (const int32_t *)(base + o.free_v);
+            D.slot_ptr = (const int32_t *)(base + o.slot_ptr); D.slot_list = (const int32_t *)(base + o.slot_list);
+            D.b_ptr = (const int32_t *)(base + o.b_ptr); D.b_list = (const int32_t *)(base + o.b_list);
+            D.sys.nf = g.nf; D.sys.n_slots = g.nf + (int32_t)g.Y.l_blocks();
+            D.sys.colptr = (const int32_t *)(base + o.colptr); D.sys.rowidx = (const int32_t *)(base + o.rowidx);
+            D.sys.upd_ptr = (const int32_t *)(base + o.upd_ptr); D.sys.upd_dst = (const int32_t *)(base + o.upd_dst);
+            D.sys.H = (const double *)(base + o.Hv); D.sys.b = (const double *)(base + o.b);
+            D.sys.L = (double *)(base + o.L); D.sys.y = (double *)(base + o.y); D.sys.x = (double *)(base + o.x);
+            D.ctl = (EgControl *)(base + o_ctl) + i;
+            D.Xw_in = (const float *)(base + o.Xw_in); D.ref = (const int32_t *)(base + o.ref);
+            D.Tiw = (float *)(base + o.Tiw); D.Xw_out = (float *)(base + o.Xw_out);
+        }
+        memcpy(H.own.data() + o_probs, dev.data(), sizeof(EgDev) * (size_t)n);
+        return (const EgDev *)(base + o_probs);
+    }
+};
+
 // ---------------------------------------------------------------------------------------------- the host tap
 static const Sim3d *eg_sim3(const double *p) { return reinterpret_cast<const Sim3d *>(p); }
 
@@ -400,6 +543,55 @@ static void eg_host_one(const aos2_essential_graph_problem_t &P, EgHostGraph &G,
 
 static inline int eg_blocks(long long items) { return (int)std::max<long long>(1, (items + kEgThreads - 1) / kEgThreads); }
 
+// ---------------------------------------------------------------------------------------------- the device taps
+// One problem through the call's own host phase and layout, and its first linearisation (k_eg_perturb, k_eg_linearise, k_eg_assemble,
+// k_eg_begin with running = 1) enqueued on the handle's stream.  J is pre-filled with the byte 0x5A: what no kernel writes keeps it.
+struct EgTap {
+    std::vector<EgHostGraph> G;
+    EgLayout Lay;
+    uint8_t *base = nullptr;
+    const EgDev *dprobs = nullptr;
+    size_t o_sums = 0;   // the two doubles of k_eg_trial_tap
+};
+
+static int eg_tap_linearise(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, EgTap &T)
+{
+    aos2_essential_graph_result_t none;
+    memset(&none, 0, sizeof none);
+    double dummy_d = 0;
+    float dummy_f = 0;
+    none.Scw = &dummy_d;   // (eg_check wants a result; the taps write none)
+    none.Tiw = none.Xw = &dummy_f;
+    if (!s || !p) {
+        set_error("bad argument (the handle, the problem)");
+        return AOS2_ERR_ARG;
+    }
+    int st = eg_check(p, &none, 1, kEgHostMaxVertices);
+    if (st) return st;
+    T.G.resize(1);
+    if ((st = eg_host_phase(p, 1, T.G))) return st;
+    if (!T.G[0].runs) {
+        set_error("bad argument (a problem with a free vertex and an edge)");
+        return AOS2_ERR_ARG;
+    }
+    T.Lay.plan(p, 1, T.G);
+    T.o_sums = T.Lay.H.push(nullptr, 16);
+    if ((st = lba_handle_init(s))) return st;
+    if ((st = s->arena.alloc(T.Lay.H.size + 256))) return st;
+    T.base = s->arena.p;
+    T.dprobs = T.Lay.bind(p, 1, T.G, T.base);
+    const EgLayout::Off &o = T.Lay.offs[0];
+    hipStream_t q = s->stream;
+    AOS2_HIP_CHECK(hipMemcpyAsync(T.base, T.Lay.H.data(), T.Lay.in_bytes, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipMemsetAsync(T.base + o.x, 0, 56 * (size_t)T.G[0].nf, q));
+    AOS2_HIP_CHECK(hipMemsetAsync(T.base + o.J, 0x5A, 98 * 8 * (size_t)p->n_edges, q));
+    hipLaunchKernelGGL(k_eg_perturb, dim3(eg_blocks(T.Lay.max_v * 15), 1), dim3(kEgThreads), 0, q, T.dprobs);
+    hipLaunchKernelGGL(k_eg_linearise, dim3(eg_blocks(T.Lay.max_e * 16), 1), dim3(kEgThreads), 0, q, T.dprobs);
+    hipLaunchKernelGGL(k_eg_assemble, dim3(eg_blocks(T.Lay.max_asm), 1), dim3(kEgThreads), 0, q, T.dprobs);
+    hipLaunchKernelGGL(k_eg_begin, dim3(1), dim3(kEgThreads), 0, q, T.dprobs);
+    return AOS2_OK;
+}
+
 }  // namespace aos2
 
 using namespace aos2;
@@ -418,128 +610,26 @@ int aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_prob
     const int n = n_problems;
     // the symbolic phase, and everything the device reads, as one staged prefix of the arena
     std::vector<EgHostGraph> G((size_t)n);
-    HostArena H;
-    struct Off { size_t v0, v1, C, S_in, est, est_try, pert, J, E, hidx, free_v, slot_ptr, slot_list, b_ptr, b_list, colptr, rowidx, upd_ptr, upd_dst, Hv, b, L, y, x, Xw_in, ref, Tiw, Xw_out; };
-    std::vector<Off> offs((size_t)n);
-    size_t budget = kEgArenaMax;
-    for (int i = 0; i < n; ++i) {
-        const aos2_essential_graph_problem_t &P = p[i];
-        EgHostGraph &g = G[(size_t)i];
-        eg_indices(P, g);
-        const size_t fixed_bytes = (size_t)P.n_vertices * (sizeof(Sim3d) * (3 + kEgPert) + 64 + 8) + (size_t)P.n_edges * (98 * 8 + 56 + 64 + 8 + 40) +
-                                   (size_t)P.n_points * 28 + 64 * 256;
-        if (fixed_bytes > budget || (g.runs && !eg_symbolic(g.nf, g.hi, g.lo, budget - fixed_bytes, g.Y))) {
-            set_error("problem %d: the graph and its factor do not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
-            return AOS2_ERR_EG_MEMORY;
-        }
-        if (!g.runs) {
-            g.Y = EgSymbolic();
-            g.Y.nf = g.nf;
-            g.Y.colptr.assign((size_t)g.nf + 1, 0);
-            g.Y.upd_ptr.assign((size_t)g.nf + 1, 0);
-        }
-        const size_t taken = fixed_bytes + (g.Y.l_blocks() + (size_t)g.nf) * 49 * 8 * 2 + g.Y.upd_dst.size() * 4;
-        if (taken > budget) {   // (a problem without LM keeps its diagonal blocks too)
-            set_error("problem %d: the batch does not fit the %zu MiB a call may take", i, kEgArenaMax >> 20);
-            return AOS2_ERR_EG_MEMORY;
-        }
-        budget -= taken;
-        eg_lists(P, g);
-    }
-    auto push_v = [&H](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
-    std::vector<EgControl> ctl0((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const aos2_essential_graph_problem_t &P = p[i];
-        const EgHostGraph &g = G[(size_t)i];
-        Off &o = offs[(size_t)i];
-        const size_t nv = (size_t)P.n_vertices, ne = (size_t)P.n_edges, np = (size_t)P.n_points;
-        o.v0 = H.push(P.v0, 4 * ne);
-        o.v1 = H.push(P.v1, 4 * ne);
-        o.C = H.push(P.Sji, 64 * ne);
-        o.S_in = H.push(P.Scw, 64 * nv);
-        o.est_try = H.push(P.Scw, 64 * nv);
-        o.hidx = push_v(g.hidx);
-        o.free_v = push_v(g.free_v);
-        o.slot_ptr = push_v(g.slot_ptr);
-        o.slot_list = push_v(g.slot_list);
-        o.b_ptr = push_v(g.b_ptr);
-        o.b_list = push_v(g.b_list);
-        o.colptr = push_v(g.Y.colptr);
-        o.rowidx = push_v(g.Y.rowidx);
-        o.upd_ptr = push_v(g.Y.upd_ptr);
-        o.upd_dst = push_v(g.Y.upd_dst);
-        o.Xw_in = H.push(P.Xw, 12 * np);
-        o.ref = H.push(P.ref, 4 * np);
-        eg_control_init(ctl0[(size_t)i], P.iterations, g.runs);
-    }
-    std::vector<EgDev> dev((size_t)n);
-    memset((void *)dev.data(), 0, sizeof(EgDev) * (size_t)n);
-    const size_t o_probs = H.push(dev.data(), sizeof(EgDev) * (size_t)n);
-    // what comes back, neighbours in the arena: the control words first (read once per iteration), then per problem Scw, Tiw, Xw.
-    // The estimates and the control words are staged (inputs), the rest is scratch.
-    const size_t o_ctl = H.push(ctl0.data(), sizeof(EgControl) * (size_t)n);
-    for (int i = 0; i < n; ++i) offs[(size_t)i].est = H.push(p[i].Scw, 64 * (size_t)p[i].n_vertices);
-    const size_t in_bytes = H.host_size;
-    for (int i = 0; i < n; ++i) {
-        offs[(size_t)i].Tiw = H.push(nullptr, 64 * (size_t)p[i].n_vertices);
-        offs[(size_t)i].Xw_out = H.push(nullptr, 12 * (size_t)p[i].n_points);
-    }
-    const size_t res_bytes = H.size - o_ctl;
-    for (int i = 0; i < n; ++i) {
-        const EgHostGraph &g = G[(size_t)i];
-        Off &o = offs[(size_t)i];
-        const size_t nv = (size_t)p[i].n_vertices, ne = (size_t)p[i].n_edges, n_slots = (size_t)g.nf + g.Y.l_blocks(), nx = 7 * (size_t)g.nf;
-        o.pert = H.push(nullptr, sizeof(Sim3d) * kEgPert * nv);
-        o.J = H.push(nullptr, 98 * 8 * ne);
-        o.E = H.push(nullptr, 56 * ne);
-        o.Hv = H.push(nullptr, 392 * n_slots);
-        o.L = H.push(nullptr, 392 * n_slots);
-        o.b = H.push(nullptr, 8 * nx);
-        o.y = H.push(nullptr, 8 * nx);
-        o.x = H.push(nullptr, 8 * nx);
-    }
-    if (H.size + 256 > kEgArenaMax + ((size_t)64 << 20)) {
+    if ((st = eg_host_phase(p, n, G))) return st;
+    EgLayout Lay;
+    Lay.plan(p, n, G);
+    if (Lay.H.size + 256 > kEgArenaMax + ((size_t)64 << 20)) {
         set_error("the batch does not fit the %zu MiB a call may take", kEgArenaMax >> 20);
         return AOS2_ERR_EG_MEMORY;
     }
     if ((st = lba_handle_init(s))) return st;
     s->last_essential_graph_ms = 0;
-    if ((st = s->arena.alloc(H.size + 256))) return st;
-    if ((st = s->h_stage.alloc(res_bytes + 64))) return st;
+    if ((st = s->arena.alloc(Lay.H.size + 256))) return st;
+    if ((st = s->h_stage.alloc(Lay.res_bytes + 64))) return st;
     uint8_t *base = s->arena.p;
-    long long max_v = 1, max_e = 1, max_asm = 1, max_fin = 1;
+    const EgDev *dprobs = Lay.bind(p, n, G, base);
+    const std::vector<EgLayout::Off> &offs = Lay.offs;
+    const size_t o_ctl = Lay.o_ctl, res_bytes = Lay.res_bytes;
+    const long long max_v = Lay.max_v, max_e = Lay.max_e, max_asm = Lay.max_asm, max_fin = Lay.max_fin;
     bool any = false;
-    for (int i = 0; i < n; ++i) {
-        const aos2_essential_graph_problem_t &P = p[i];
-        const EgHostGraph &g = G[(size_t)i];
-        const Off &o = offs[(size_t)i];
-        EgDev &D = dev[(size_t)i];
-        D.nv = P.n_vertices; D.ne = P.n_edges; D.np = P.n_points; D.fixed = P.fixed; D.fix_scale = P.fix_scale != 0;
-        D.v0 = (const int32_t *)(base + o.v0); D.v1 = (const int32_t *)(base + o.v1);
-        D.C = (const Sim3d *)(base + o.C); D.S_in = (const Sim3d *)(base + o.S_in);
-        D.est = (Sim3d *)(base + o.est); D.est_try = (Sim3d *)(base + o.est_try); D.pert = (Sim3d *)(base + o.pert);
-        D.J = (double *)(base + o.J); D.E = (double *)(base + o.E);
-        D.hidx = (const int32_t *)(base + o.hidx); D.free_v = (const int32_t *)(base + o.free_v);
-        D.slot_ptr = (const int32_t *)(base + o.slot_ptr); D.slot_list = (const int32_t *)(base + o.slot_list);
-        D.b_ptr = (const int32_t *)(base + o.b_ptr); D.b_list = (const int32_t *)(base + o.b_list);
-        D.sys.nf = g.nf; D.sys.n_slots = g.nf + (int32_t)g.Y.l_blocks();
-        D.sys.colptr = (const int32_t *)(base + o.colptr); D.sys.rowidx = (const int32_t *)(base + o.rowidx);
-        D.sys.upd_ptr = (const int32_t *)(base + o.upd_ptr); D.sys.upd_dst = (const int32_t *)(base + o.upd_dst);
-        D.sys.H = (const double *)(base + o.Hv); D.sys.b = (const double *)(base + o.b);
-        D.sys.L = (double *)(base + o.L); D.sys.y = (double *)(base + o.y); D.sys.x = (double *)(base + o.x);
-        D.ctl = (EgControl *)(base + o_ctl) + i;
-        D.Xw_in = (const float *)(base + o.Xw_in); D.ref = (const int32_t *)(base + o.ref);
-        D.Tiw = (float *)(base + o.Tiw); D.Xw_out = (float *)(base + o.Xw_out);
-        max_v = std::max<long long>(max_v, P.n_vertices);
-        max_e = std::max<long long>(max_e, P.n_edges);
-        max_asm = std::max<long long>(max_asm, (long long)D.sys.n_slots * 49 + 7LL * g.nf);
-        max_fin = std::max<long long>(max_fin, std::max(P.n_vertices, P.n_points));
-        any = any || g.runs;
-    }
-    memcpy(H.own.data() + o_probs, dev.data(), sizeof(EgDev) * (size_t)n);
+    for (int i = 0; i < n; ++i) any = any || G[(size_t)i].runs;
     hipStream_t q = s->stream;
-    const EgDev *dprobs = (const EgDev *)(base + o_probs);
-    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(base, Lay.H.data(), Lay.in_bytes, hipMemcpyHostToDevice, q));
     AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
     // x starts at zero: a first solve that fails applies the solver's vector as it stands
     for (int i = 0; i < n; ++i)
@@ -600,7 +690,7 @@ int aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_prob
     for (hipEvent_t e : marks) (void)hipEventDestroy(e);
     const uint8_t *res = s->h_stage.p;
     for (int i = 0; i < n; ++i) {
-        const Off &o = offs[(size_t)i];
+        const EgLayout::Off &o = offs[(size_t)i];
         EgControl c;
         memcpy(&c, res + sizeof(EgControl) * (size_t)i, sizeof c);
         eg_result_control(c, G[(size_t)i].runs, (int)G[(size_t)i].Y.l_blocks(), r[i]);
@@ -705,6 +795,90 @@ int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_o
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
     *l_blocks = (int32_t)Y.l_blocks();
+    return AOS2_OK;
+}
+
+int aos2_debug_essential_graph_linearised_device(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, double *J, double *E, double *H, double *b,
+                                                 double *chi2, int32_t *l_blocks)
+{
+    if (!J || !E || !H || !b || !chi2 || !l_blocks) {
+        set_error("bad argument (the outputs)");
+        return AOS2_ERR_ARG;
+    }
+    EgTap T;
+    int st = eg_tap_linearise(s, p, T);
+    if (st) return st;
+    const EgHostGraph &G = T.G[0];
+    const EgLayout::Off &o = T.Lay.offs[0];
+    const size_t ne = (size_t)p->n_edges, nf = (size_t)G.nf, n_slots = nf + G.Y.l_blocks(), n7 = 7 * nf;
+    std::vector<double> Hv(n_slots * 49);
+    EgControl c;
+    hipStream_t q = s->stream;
+    AOS2_HIP_CHECK(hipMemcpyAsync(J, T.base + o.J, 98 * 8 * ne, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(E, T.base + o.E, 56 * ne, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(Hv.data(), T.base + o.Hv, 8 * Hv.size(), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(b, T.base + o.b, 8 * n7, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    // dense: a diagonal slot as it is stored, a slot below the diagonal and its transpose
+    std::fill(H, H + n7 * n7, 0.0);
+    for (size_t sl = 0; sl < n_slots; ++sl) {
+        size_t row = sl, col = sl;
+        if (sl >= nf) {
+            const int pp = (int)(sl - nf);
+            row = (size_t)G.Y.rowidx[(size_t)pp];
+            col = (size_t)(std::upper_bound(G.Y.colptr.begin(), G.Y.colptr.end(), pp) - G.Y.colptr.begin()) - 1;
+        }
+        for (size_t a = 0; a < 7; ++a)
+            for (size_t cc = 0; cc < 7; ++cc) {
+                const double v = Hv[sl * 49 + a * 7 + cc];
+                H[(7 * row + a) * n7 + 7 * col + cc] = v;
+                if (sl >= nf) H[(7 * col + cc) * n7 + 7 * row + a] = v;
+            }
+    }
+    chi2[0] = c.lm.currentChi;
+    chi2[1] = c.chi2_initial;
+    *l_blocks = (int32_t)G.Y.l_blocks();
+    return AOS2_OK;
+}
+
+int aos2_debug_essential_graph_trial_device(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, const double *x, const double *seed_d,
+                                            const int32_t *seed_i, double *est_try, double *est, double *control_d, int32_t *control_i, double *sums)
+{
+    if (!x || !seed_d || !seed_i || !est_try || !est || !control_d || !control_i || !sums) {
+        set_error("bad argument (x, the seeds, the outputs)");
+        return AOS2_ERR_ARG;
+    }
+    EgTap T;
+    int st = eg_tap_linearise(s, p, T);
+    if (st) return st;
+    const EgLayout::Off &o = T.Lay.offs[0];
+    const size_t nv = (size_t)p->n_vertices, n7 = 7 * (size_t)T.G[0].nf;
+    hipStream_t q = s->stream;
+    EgControl c;
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    c.running = c.open = 1;
+    c.lm.lambda = seed_d[0];
+    c.lm.currentChi = seed_d[1];
+    c.lm.ni = seed_d[2];
+    c.solved = seed_i[0];
+    c.iterations = seed_i[1];
+    c.qmax = seed_i[2];
+    AOS2_HIP_CHECK(hipMemcpyAsync(T.base + T.Lay.o_ctl, &c, sizeof c, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(T.base + o.x, x, 8 * n7, hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(k_eg_trial_tap, dim3(1), dim3(kEgThreads), 0, q, T.dprobs, (double *)(T.base + T.o_sums));
+    AOS2_HIP_CHECK(hipMemcpyAsync(est_try, T.base + o.est_try, 64 * nv, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(est, T.base + o.est, 64 * nv, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(sums, T.base + T.o_sums, 16, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    const double cd[6] = {c.lm.lambda, c.lm.ni, c.lm.currentChi, c.lm.iniChi, c.rho, c.chi2_initial};
+    const int32_t ci[10] = {c.lm.nBad, c.qmax, c.open, c.running, c.solved, c.max_iterations, c.iterations, c.trials, c.rejected, c.accepted_first};
+    memcpy(control_d, cd, sizeof cd);
+    memcpy(control_i, ci, sizeof ci);
     return AOS2_OK;
 }
 

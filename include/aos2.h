@@ -1345,6 +1345,24 @@ int aos2_debug_essential_graph_profile(aos2_lba_t *s, int on, float *family_ms);
 int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols,
                                             const double *val, const double *diag, const double *b, double lambda, double *x,
                                             int32_t *ok, int32_t *l_blocks);
+/* The first linearisation of ONE problem as the device forms it: the host phase and the arena layout of aos2_optimize_essential_graph,
+ * then k_eg_perturb, k_eg_linearise, k_eg_assemble and k_eg_begin once on the input estimates.  n_vertices <= 512 (else
+ * AOS2_ERR_CAPACITY); a problem without a free vertex or without an edge is AOS2_ERR_ARG.  With nf = n_vertices - 1:
+ * J [n_edges][2][49] (side 0 / side 1, row-major 7x7; the device buffer is pre-filled with the byte 0x5A, and the Jacobian of a fixed
+ * side, which no kernel writes, comes back as that), E [n_edges][7], H [7 nf][7 nf] row-major in hessian order (the free vertices
+ * ascending): a diagonal block as stored, a stored block below the diagonal and its transpose, the fill-only blocks of L's pattern
+ * included, zero elsewhere; b [7 nf]; chi2 [2] = the control words' lm.currentChi and chi2_initial; *l_blocks as the call reports it. */
+int aos2_debug_essential_graph_linearised_device(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, double *J, double *E,
+                                                 double *H, double *b, double *chi2, int32_t *l_blocks);
+/* One k_eg_trial on ONE problem (limits as above) after the same linearisation (which gives b): x [7 nf] is uploaded as the solver's
+ * vector and the control words of an open trial are seeded, running = open = 1, seed_d [3] = lm.lambda, lm.currentChi, lm.ni,
+ * seed_i [3] = solved, iterations, qmax (max_iterations = the problem's iterations; the rest as k_eg_begin left it).  est_try and est
+ * [n_vertices][8] after the kernel; control_d [6] = lm.lambda, lm.ni, lm.currentChi, lm.iniChi, rho, chi2_initial; control_i [10] =
+ * lm.nBad, qmax, open, running, solved, max_iterations, iterations, trials, rejected, accepted_first; sums [2] = the kernel's chi2 of
+ * the trial estimates (before a failed solve replaces it by DBL_MAX) and its sum of x (lambda x + b). */
+int aos2_debug_essential_graph_trial_device(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, const double *x,
+                                            const double *seed_d, const int32_t *seed_i, double *est_try, double *est,
+                                            double *control_d, int32_t *control_i, double *sums);
 /* aos2_global_bundle_adjustment on the HOST: the same header (csrc/global_ba.h) and the same per-item functions run serially, the
  * reduced system solved by a skyline LDL^T of the scalar system; n_poses <= 2048 (else AOS2_ERR_CAPACITY); needs no device.
  * stop_at_poll as aos2_lba_debug_stop_at_poll.  h_blocks / l_blocks are what the device's symbolic phase gives; ms_device = 0. */

@@ -105,10 +105,10 @@ def oplus_all(u, fix_scale, est):
 
 
 # ---------------------------------------------------------------------------------------------- the optimisation
-def linearise(P, est, order, acc):
-    """computeActiveErrors, the central differences, constructQuadraticForm -> H [7 nv][7 nv] (the fixed vertex's rows stay zero),
-    b, chi2; the sums in the edge order `order`, accumulated in dtype `acc`"""
-    nv, fix = len(est), bool(P["fix_scale"])
+def jacobians(P, est, order):
+    """computeActiveErrors and the central differences of every edge, in the edge order `order` -> e [ne][7], J0, J1 [ne][7][7]
+    (the Jacobian of a fixed side is computed like any other; linearise does not use it)"""
+    fix = bool(P["fix_scale"])
     v0, v1, C = P["v0"][order], P["v1"][order], P["Sji"][order]
     e = residuals(C, est, v0, v1)
     scalar = 1.0 / (2 * DELTA)
@@ -123,6 +123,15 @@ def linearise(P, est, order, acc):
         CA = mul(C, est[v0])
         J0[:, :, d] = scalar * (log(mul(mul(C, plus[v0]), inv[v1])) - log(mul(mul(C, minus[v0]), inv[v1])))
         J1[:, :, d] = scalar * (log(mul(CA, inverse(plus)[v1])) - log(mul(CA, inverse(minus)[v1])))
+    return e, J0, J1
+
+
+def linearise(P, est, order, acc):
+    """computeActiveErrors, the central differences, constructQuadraticForm -> H [7 nv][7 nv] (the fixed vertex's rows stay zero),
+    b, chi2; the sums in the edge order `order`, accumulated in dtype `acc`"""
+    nv = len(est)
+    v0, v1 = P["v0"][order], P["v1"][order]
+    e, J0, J1 = jacobians(P, est, order)
     H = np.zeros((nv, nv, 7, 7), acc)
     b = np.zeros((nv, 7), acc)
     f0, f1 = v0 != P["fixed"], v1 != P["fixed"]

@@ -13,6 +13,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import essential_graph_ref as R  # noqa: E402
+import essential_graph_cases as K  # noqa: E402
+from essential_graph_cases import adjoint, inverse_left_jacobian, small_adjoint  # noqa: E402,F401
 
 SEED = 3
 DBL_EPSILON = 2.0 ** -52
@@ -84,41 +86,6 @@ def test_log_of_exp_gives_the_update_back(theta, sigma):
         # exp and log took the same lines: upsilon itself comes back (W_log differs from W_exp by the error of omega alone, which
         # the second term of the bound covers once more)
         assert np.abs(got[3:6] - ups).max() <= 2 * bound_ups
-
-
-def adjoint(S):
-    """S exp(u) S^-1 = exp(Ad u) for u = (omega, upsilon, sigma): omega' = R omega, upsilon' = s R upsilon + t x R omega - sigma t"""
-    Rm = R.rot_of((S[:4] / np.linalg.norm(S[:4]))[None])[0]
-    t, s = S[4:7], S[7]
-    Ad = np.zeros((7, 7))
-    Ad[:3, :3] = Rm
-    Ad[3:6, :3] = R.S3.skew(t) @ Rm
-    Ad[3:6, 3:6] = s * Rm
-    Ad[3:6, 6] = -t
-    Ad[6, 6] = 1
-    return Ad
-
-
-def small_adjoint(xi):
-    """ad_xi: the derivative of Ad(exp(h xi)) at h = 0"""
-    w, v, sg = xi[:3], xi[3:6], xi[6]
-    ad = np.zeros((7, 7))
-    ad[:3, :3] = R.S3.skew(w)
-    ad[3:6, :3] = R.S3.skew(v)
-    ad[3:6, 3:6] = R.S3.skew(w) + sg * np.eye(3)
-    ad[3:6, 6] = -v
-    return ad
-
-
-def inverse_left_jacobian(xi):
-    """log(exp(v) exp(xi)) = xi + Jl^-1(xi) v + O(v^2), Jl^-1 = sum B_n / n! ad^n (Bernoulli numbers, B_1 = -1/2)"""
-    bern = [1.0, -0.5, 1 / 6, 0, -1 / 30, 0, 1 / 42, 0, -1 / 30, 0, 5 / 66, 0, -691 / 2730, 0, 7 / 6]
-    ad, term, out, fact = small_adjoint(xi), np.eye(7), np.zeros((7, 7)), 1.0
-    for n, Bn in enumerate(bern):
-        if n:
-            term, fact = term @ ad, fact * n
-        out += Bn / fact * term
-    return out
 
 
 def test_central_difference_jacobian_agrees_with_the_closed_form():
@@ -386,3 +353,91 @@ def test_header_residual_agrees_with_the_restatement(pkg):
         print(len(est), "largest |e| %.3f" % np.abs(want).max(), "largest difference %.2e" % err, "bound %.2e" % bound)
         assert np.abs(want).max() < 0.5 and err <= bound
     print("worst difference / bound:", worst)
+
+
+# ---------------------------------------------------------------------------------------------- the turned inputs and the replay
+def _restated(P):
+    est = np.asarray(P["Scw"], np.float64)
+    e, J0, J1 = R.jacobians(P, est, np.arange(len(P["v0"])))
+    return est, np.stack([J0, J1], axis=1), e
+
+
+@pytest.mark.parametrize("name", list(K.cases()))
+def test_replay_agrees_with_the_restatement_and_notices_a_wrong_block_on_turned_inputs(name):
+    """K.replay on the restatement's own J and e against R.linearise (numpy's sums): the same products in another order, so an entry
+    of n products differs by at most 4 n 2^-53 sum |products| (nothing where no edge adds).  Then the two ways of getting the block
+    below the diagonal wrong: with the two forms exchanged, and with J1^T J0 formed as J0^T J1, the replay gives another H."""
+    P = K.cases()[name]
+    est, J, e = _restated(P)
+    H, b, nH, aH, nb, ab = K.replay(P, J, e, stats=True)
+    Hr, br, _ = R.linearise(P, est, np.arange(len(P["v0"])), np.float64)
+    keep = np.flatnonzero(np.repeat(np.arange(len(est)) != P["fixed"], 7))
+    dH, db = np.abs(H - Hr[np.ix_(keep, keep)]), np.abs(b - br[keep])
+    bH, bb = 4 * nH * 2.0 ** -53 * aH, 4 * nb * 2.0 ** -53 * ab
+    print(name, "edges", len(P["v0"]), "free pairs (J0^T J1, J1^T J0)", K.free_pairs(P),
+          "largest |H - ref| / bound %.3g, |b - ref| / bound %.3g" % (K.worst(dH, bH), K.worst(db, bb)))
+    assert (dH <= bH).all() and (db <= bb).all()
+    assert (nH > 0).tobytes() == K.pattern(P).tobytes() and np.array_equal(H, H.T)
+    if name == "n2_single_edge":
+        assert K.free_pairs(P) == (0, 0)
+        return
+    assert min(K.free_pairs(P)) >= 1
+    for mutant in ("exchanged", "kind3"):
+        assert K.replay(P, J, e, mutant=mutant)[0].tobytes() != H.tobytes(), mutant
+
+
+def test_generator_never_forms_the_block_of_a_lower_first_vertex():
+    """the hole the turned inputs close: on every problem of the generator no edge between free vertices has vertex 0 at the lower
+    hessian index, so a replay that forms J1^T J0 wrongly is IDENTICAL to the right one there"""
+    total = 0
+    for P in R.generator_case(SEED)["problems"]:
+        if not len(P["v0"]):
+            continue
+        est, J, e = _restated(P)
+        assert K.free_pairs(P)[1] == 0
+        total += K.free_pairs(P)[0]
+        H, b = K.replay(P, J, e)
+        Hm, bm = K.replay(P, J, e, mutant="kind3")
+        assert H.tobytes() == Hm.tobytes() and b.tobytes() == bm.tobytes()
+        assert P["fixed"] == min(1, len(est) - 1)   # ... and the fixed vertex is always this one
+    assert total > 1000
+    assert sum(K.free_pairs(P)[1] for P in K.cases().values()) > 500
+
+
+@pytest.mark.parametrize("name", list(K.cases()))
+def test_central_differences_of_turned_edges_agree_with_the_closed_form(name):
+    """the bound of test_central_difference_jacobian_agrees_with_the_closed_form, 100 M DBL_EPSILON / delta, on every edge of the
+    turned inputs, both sides; with fix_scale column 6 is exactly 0 and the other six are compared"""
+    P = K.cases()[name]
+    est, J, e = _restated(P)
+    closed, bound, emax = K.closed_form(P, est)
+    assert emax < 0.5
+    cols = 6 if P["fix_scale"] else 7
+    ratio = (np.abs(J - closed)[..., :cols].max(axis=(1, 2, 3)) / bound).max()
+    print(name, "largest |e| %.3f" % emax, "largest |J - closed| / bound %.3g" % ratio)
+    assert ratio <= 1
+    if P["fix_scale"]:
+        assert (J[..., 6] == 0).all()
+
+
+def test_host_tap_agrees_with_the_reference_on_turned_inputs(pkg):
+    c = K.optimised()
+    assert max(c["resolution"]) < 1e-4
+    got = pkg.capi.debug_essential_graph_host(c["problems"])
+    for k, (g, w, P, r) in enumerate(zip(got, c["want"], c["problems"], c["resolution"])):
+        ok, msg = R.same(g, w, P, r)
+        print(c["names"][k], "resolution %.1e" % r, msg, "iterations", g["iterations"], w["iterations"], "trials", g["trials"], w["trials"])
+        assert ok, (k, msg)
+        assert w["status"] == R.EG_OK and w["chi2_final"] < w["chi2_initial"]
+
+
+def test_a_measurement_that_is_not_a_number_leaves_the_estimates_as_they_were(pkg):
+    """a NaN in one Sji: chi2 is NaN, every solve fails (x keeps its zeros, tempChi = DBL_MAX), rho is NaN -- neither > 0 nor < 0 --
+    so every iteration is one rejected trial and nothing ends the call before its 20 iterations"""
+    P = K.with_nan(K.cases()["n17_fix0_fixed16"])
+    with np.errstate(all="ignore"):
+        want = R.optimize(P)
+    got = pkg.capi.debug_essential_graph_host([P])[0]
+    for name, res in (("restatement", want), ("host tap", got)):
+        assert (res["status"], res["iterations"], res["trials"], res["rejected"]) == (R.EG_NO_STEP, 20, 20, 20), name
+        assert np.asarray(res["Scw"]).tobytes() == np.asarray(P["Scw"], np.float64).tobytes(), name

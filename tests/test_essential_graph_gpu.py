@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import essential_graph_cases as K  # noqa: E402
 import essential_graph_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -125,3 +126,46 @@ def test_a_refused_call_leaves_the_sentinel_and_the_handle_works_afterwards(pkg,
         for k in range(3):
             assert all((a.view(np.uint8) == SENTINEL).all() for a in outs[k].values()) and Rc[k].status == 0x5A5A5A5A and Rc[k].iterations == 0x5A5A5A5A
     assert raw(L.optimize_essential_graph([P[4]])[0]) == raw(batch[4])   # the handle is as good as before
+
+
+# ---------------------------------------------------------------------------------------------- inputs the generator does not produce
+@pytest.fixture(scope="module")
+def turned(world):
+    """tests/essential_graph_cases.py: edges in both orientations between free vertices, a free pair named twice, the fixed vertex
+    first, last and in the middle -> the cases, the restatement's results, the batch of the five"""
+    c, L, batch = world
+    t = K.optimised()
+    return t, L.optimize_essential_graph(t["problems"])
+
+
+def test_turned_inputs_equal_the_reference_and_the_host_tap(pkg, world, turned):
+    t, together = turned
+    taps = pkg.capi.debug_essential_graph_host(t["problems"])
+    assert max(t["resolution"]) < 1e-4
+    for k, (g, w, tap, P, r) in enumerate(zip(together, t["want"], taps, t["problems"], t["resolution"])):
+        for other, name in ((w, "restatement"), (tap, "host tap")):
+            ok, msg = R.same(g, other, P, r)
+            print(t["names"][k], name, msg, "iterations", g["iterations"], other["iterations"], "trials", g["trials"], other["trials"])
+            assert ok, (k, name, msg)
+        assert g["l_blocks"] == tap["l_blocks"] and g["chi2_final"] < g["chi2_initial"]
+
+
+def test_each_turned_case_alone_equals_the_same_case_in_a_batch(world, turned):
+    c, L, batch = world
+    t, together = turned
+    for k, P in enumerate(t["problems"]):
+        assert raw(L.optimize_essential_graph([P])[0]) == raw(together[k]), t["names"][k]
+
+
+def test_a_measurement_that_is_not_a_number_stays_with_its_problem(world, turned):
+    """a NaN in one Sji of the problem between two good ones: no step of its own (tests/test_essential_graph_cpu.py: 20 iterations of
+    one rejected trial each, the estimates bit for bit the input's), the neighbours as they are alone, the handle as good as before"""
+    c, L, batch = world
+    t, together = turned
+    bad = K.with_nan(t["problems"][2])
+    got = L.optimize_essential_graph([t["problems"][0], bad, t["problems"][3]])
+    g = got[1]
+    assert (g["status"], g["iterations"], g["trials"], g["rejected"]) == (R.EG_NO_STEP, 20, 20, 20)
+    assert g["Scw"].tobytes() == np.asarray(bad["Scw"], np.float64).tobytes()
+    assert raw(got[0]) == raw(together[0]) and raw(got[2]) == raw(together[3])
+    assert raw(L.optimize_essential_graph([t["problems"][2]])[0]) == raw(together[2])
