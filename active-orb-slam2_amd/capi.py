@@ -117,6 +117,23 @@ def lib():
             getattr(L, nm).argtypes = [vp, vp, vp, ci]
         for nm in ("aos2_kfdb_scores", "aos2_debug_kfdb_scores_host"):
             getattr(L, nm).argtypes = [vp, vp, vp, ci, vp, C.POINTER(cf)]
+        L.aos2_vis_camera_default.argtypes = [ci, vp]
+        L.aos2_vis_create.argtypes = [ci, C.POINTER(vp)]
+        L.aos2_vis_destroy.argtypes = [vp]
+        L.aos2_vis_destroy.restype = None
+        L.aos2_vis_set_camera.argtypes = [vp, vp]
+        L.aos2_vis_set_map.argtypes = [vp, ci] + [vp] * 6
+        L.aos2_vis_map_size.argtypes = [vp]
+        L.aos2_vis_gate_tile.argtypes = [C.POINTER(ci), C.POINTER(ci)]
+        L.aos2_vis_gate_tile.restype = None
+        L.aos2_vis_last_device_ms.argtypes = [vp]
+        L.aos2_vis_last_device_ms.restype = cf
+        for nm in ("aos2_vis_count", "aos2_vis_count_poses", "aos2_debug_visibility_host", "aos2_debug_visibility_poses_host"):
+            getattr(L, nm).argtypes = [vp, ci, vp, vp, vp, vp]
+        for nm in ("aos2_vis_motion_costs", "aos2_debug_visibility_motion_costs_host"):
+            getattr(L, nm).argtypes = [vp, ci, vp, vp, ci, vp]
+        for nm in ("aos2_vis_advance", "aos2_debug_visibility_advance_host"):
+            getattr(L, nm).argtypes = [vp, ci, vp, ci, C.POINTER(C.c_int32)]
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
@@ -950,6 +967,102 @@ class KeyFrameDatabase:
         f = self.L.aos2_debug_kfdb_scores_host if host else self.L.aos2_kfdb_scores
         _check(f(self.h, C.byref(Q), _p(s), len(s), _p(out), C.byref(mn)))
         return out[: len(s)], np.float32(mn.value)
+
+
+# ---- planner visibility (include/aos2.h: aos2_vis_*, aos2_debug_visibility_*host)
+class VisCamera(C.Structure):
+    """aos2_vis_camera_t"""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "max_dist", "min_dist")] + \
+               [("feature_threshold", C.c_int32), ("T_sw", C.c_float * 16), ("T_bc", C.c_float * 16)]
+
+
+class Visibility:
+    """camera (include/camera.h:51-129) for batches of states: the planner's map resident on the device, countVisible for ns
+    states in one call, MotionCostCamera for many motions and AdvanceStepCamera for a trajectory.  host=True runs the library's
+    own serial routine (aos2_debug_visibility_*host) instead."""
+    CAMERA_MAP, CAMERA_PLAIN = 0, 1
+
+    def __init__(self, device=0):
+        self.L = lib()
+        h = C.c_void_p()
+        _check(self.L.aos2_vis_create(device, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.aos2_vis_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def camera_default(which=0):
+        cam = VisCamera()
+        _check(lib().aos2_vis_camera_default(which, C.byref(cam)))
+        return cam
+
+    @staticmethod
+    def gate_tile():
+        """(points a workgroup of the gate kernel takes, states of its tile)"""
+        p, s = C.c_int(0), C.c_int(0)
+        lib().aos2_vis_gate_tile(C.byref(p), C.byref(s))
+        return p.value, s.value
+
+    def set_camera(self, cam: VisCamera):
+        _check(self.L.aos2_vis_set_camera(self.h, C.byref(cam)))
+
+    def set_map(self, xyz, upper, lower, max_range, min_range, found_ratio):
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        rest = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in (upper, lower, max_range, min_range, found_ratio)]
+        if any(len(a) != len(xyz) for a in rest):
+            raise ValueError("the map's arrays differ in length")
+        _check(self.L.aos2_vis_set_map(self.h, len(xyz), _p(xyz), *[_p(a) for a in rest]))
+
+    def map_size(self):
+        return self.L.aos2_vis_map_size(self.h)
+
+    def last_device_ms(self):
+        return float(self.L.aos2_vis_last_device_ms(self.h))
+
+    def _count(self, f, arr, ns, want_sum, want_mask):
+        words = (self.map_size() + 63) // 64
+        count = np.zeros(ns, np.int32)
+        s = np.zeros(ns, np.float32) if want_sum else None
+        m = np.zeros((ns, words), np.uint64) if want_mask else None
+        _check(f(self.h, ns, _p(arr), _p(count), _p(s) if want_sum else None, _p(m) if want_mask else None))
+        return dict(count=count, sum=s, mask=m)
+
+    def count(self, states, sum=True, mask=True, host=False):
+        """aos2_vis_count: states [ns][3] = x, y, theta -> dict(count int32 [ns], sum float32 [ns] | None, mask uint64 [ns][words] | None)"""
+        st = np.ascontiguousarray(states, np.float32).reshape(-1, 3)
+        return self._count(self.L.aos2_debug_visibility_host if host else self.L.aos2_vis_count, st, len(st), sum, mask)
+
+    def count_poses(self, T_wb, sum=True, mask=True, host=False):
+        """aos2_vis_count_poses: T_wb [ns][4][4]"""
+        T = np.ascontiguousarray(T_wb, np.float32).reshape(-1, 16)
+        return self._count(self.L.aos2_debug_visibility_poses_host if host else self.L.aos2_vis_count_poses, T, len(T), sum, mask)
+
+    def motion_costs(self, motions, thres=-1, host=False):
+        """aos2_vis_motion_costs: motions = a list of [size][3] state arrays -> float64 [nm]"""
+        ms = [np.asarray(m, np.float32).reshape(-1, 3) for m in motions]
+        off = np.cumsum([0] + [len(m) for m in ms]).astype(np.int32)
+        st = np.ascontiguousarray(np.concatenate(ms) if ms else np.zeros((0, 3)), np.float32)
+        return self.motion_costs_raw(off, st, thres, host)
+
+    def motion_costs_raw(self, offsets, states, thres=-1, host=False):
+        off, st = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(states, np.float32)
+        cost = np.zeros(max(len(off) - 1, 0), np.float64)
+        f = self.L.aos2_debug_visibility_motion_costs_host if host else self.L.aos2_vis_motion_costs
+        _check(f(self.h, len(off) - 1, _p(off), _p(st), int(thres), _p(cost)))
+        return cost
+
+    def advance(self, states, thres=-1, host=False):
+        """aos2_vis_advance: the last index of the leading run of states with count > thres, -1 if the first one fails"""
+        st = np.ascontiguousarray(states, np.float32).reshape(-1, 3)
+        idx = C.c_int32(-2)
+        f = self.L.aos2_debug_visibility_advance_host if host else self.L.aos2_vis_advance
+        _check(f(self.h, len(st), _p(st), int(thres), C.byref(idx)))
+        return idx.value
 
 
 def ComputeStereoMatches(left: Extractor, right: Extractor, kps_l, desc_l, kps_r, desc_r, mb, mbf, image=0):

@@ -10,6 +10,7 @@
 #include "sincos_exact.h"
 #include "sim3.h"
 #include "triangulate.h"
+#include "visibility.h"
 #include "wave_ops.h"
 
 namespace aos2 {
@@ -597,6 +598,82 @@ int aos2_debug_octree_host(const int16_t *xs, const int16_t *ys, const uint8_t *
     std::vector<int32_t> perm(n), tmp(n), pairs((size_t)4 * mn);
     OctScratch S{nodes.data(), perm.data(), tmp.data(), pairs.data(), pairs.data() + 2 * mn, mn, mn};
     return distribute_octree(xs, ys, score, n, minX, maxX, minY, maxY, N, S, out_idx, cap);
+}
+
+// countVisible (src/camera.cc:135-198) for every state in turn, one point at a time: the loop the planner runs
+static void vis_count_host(const aos2_vis_t *h, int ns, const float *in, bool poses, int32_t *count, float *sum, uint64_t *mask)
+{
+    using namespace aos2;
+    aos2_vis_camera_t cam;
+    VisMapView M;
+    vis_view(h, &cam, &M);
+    const VisGates g = vis_gates(cam);
+    const size_t words = (size_t)(M.n + 63) / 64;
+    for (int s = 0; s < ns; ++s) {
+        const VisState S = poses ? vis_state_from_pose(in + 16 * (size_t)s, cam)
+                                 : vis_state_from_xyt(in[3 * (size_t)s], in[3 * (size_t)s + 1], in[3 * (size_t)s + 2], cam);
+        if (mask) std::fill(mask + s * words, mask + (s + 1) * words, (uint64_t)0);
+        float num_visible = 0;
+        for (int i = 0; i < M.n; ++i)
+            if (vis_point(g, S, M.x[i], M.y[i], M.z[i], M.upper[i], M.lower[i], M.max_range[i], M.min_range[i])) {
+                num_visible += M.ratio[i];
+                if (mask) mask[s * words + i / 64] |= (uint64_t)1 << (i % 64);
+            }
+        if (sum) sum[s] = num_visible;
+        count[s] = vis_round(num_visible);
+    }
+}
+
+int aos2_debug_visibility_host(aos2_vis_t *h, int ns, const float *states, int32_t *count, float *sum, uint64_t *mask)
+{
+    if (int st = aos2::vis_check_count(h, ns, states, count)) return st;
+    vis_count_host(h, ns, states, false, count, sum, mask);
+    return AOS2_OK;
+}
+
+int aos2_debug_visibility_poses_host(aos2_vis_t *h, int ns, const float *T_wb, int32_t *count, float *sum, uint64_t *mask)
+{
+    if (int st = aos2::vis_check_count(h, ns, T_wb, count)) return st;
+    vis_count_host(h, ns, T_wb, true, count, sum, mask);
+    return AOS2_OK;
+}
+
+int aos2_debug_visibility_motion_costs_host(aos2_vis_t *h, int nm, const int32_t *offsets, const float *states, int thres, double *cost)
+{
+    using namespace aos2;
+    if (int st = vis_check_motions(h, nm, offsets, states, cost)) return st;
+    aos2_vis_camera_t cam;
+    VisMapView M;
+    vis_view(h, &cam, &M);
+    const int thr = thres < 0 ? cam.feature_threshold : thres;
+    for (int m = 0; m < nm; ++m) {   // src/StateValidChecker.cc:531-541
+        double C = 0;
+        for (int i = offsets[m] + 1; i < offsets[m + 1] - 1; ++i) {
+            int32_t c;
+            vis_count_host(h, 1, states + 3 * (size_t)i, false, &c, nullptr, nullptr);
+            C += vis_motion_cost_term(c, thr);
+        }
+        cost[m] = C;
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *states, int thres, int32_t *index)
+{
+    using namespace aos2;
+    if (int st = vis_check_advance(h, ns, states, index)) return st;
+    aos2_vis_camera_t cam;
+    VisMapView M;
+    vis_view(h, &cam, &M);
+    const int thr = thres == -1 ? cam.feature_threshold : thres;
+    int i = 0;   // src/plan.cc:145-148
+    for (; i < ns; ++i) {
+        int32_t c;
+        vis_count_host(h, 1, states + 3 * (size_t)i, false, &c, nullptr, nullptr);
+        if (!(c > thr)) break;
+    }
+    *index = i - 1;
+    return AOS2_OK;
 }
 
 void aos2_debug_sincos_host(float angle_rad, float *s, float *c) { aos2::sincos_exact(angle_rad, s, c); }

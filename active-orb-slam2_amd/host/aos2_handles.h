@@ -96,6 +96,28 @@ inline aos2_lba_t *optimizer_handle()
     return h;
 }
 
+// The visibility handle of this thread and device (host/camera.h).  A handle holds ONE camera and ONE map on the device, and the
+// reference builds a camera object per plan (StateValidChecker's base, src/plan.cc:143): `owner` names the camera object whose
+// constants and map the handle holds now, so an object uploads them when it finds another one's there and not again after that.
+struct VisibilitySlot {
+    aos2_vis_t *h = nullptr;
+    unsigned long long owner = 0;
+};
+inline VisibilitySlot &visibility_slot()
+{
+    struct Cache {
+        std::map<int, VisibilitySlot> m;
+        ~Cache()
+        {
+            for (auto &kv : m) aos2_vis_destroy(kv.second.h);
+        }
+    };
+    thread_local Cache cache;
+    VisibilitySlot &s = cache.m[thread_device()];
+    if (!s.h && aos2_vis_create(thread_device(), &s.h) != AOS2_OK) fail("camera");
+    return s;
+}
+
 // wall-clock split of the last call of this thread through one of the classes: gather (pointer graph -> SoA), the C-ABI
 // call, scatter (indices -> pointer graph)
 struct ShimTiming {

@@ -386,6 +386,61 @@ int aos2_kfdb_scores(aos2_kfdb_t *db, const aos2_kfdb_query_t *query, const int3
 float aos2_kfdb_last_device_ms(const aos2_kfdb_t *db);   /* device time of the last detect / scores call (HIP events) */
 
 /* ------------------------------------------------------------------------------------------
+ * camera (planner visibility)  (include/camera.h:51-129, src/camera.cc)
+ * What the Active-SLAM planner asks of every robot state it tries: how many points of the whole map are predicted to be visible
+ * from it (camera::countVisible :135-198 over camera::isInFrustum :263-315).  The reference answers one state per call, serially,
+ * from StateValidChecker::isValid / checkMotion (src/StateValidChecker.cc:97-161), MotionCostCamera (:531-541),
+ * plan_slam::AdvanceStepCamera (src/plan.cc:141-151) and RRTstar::display_costs (src/myRRTstar.cc:1142-1163); here a call takes
+ * a batch of states against a map resident in HBM.  Every output equals the serial loop bit for bit, the float sum included
+ * (DESIGN.md section 2 item 16, section 5).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aos2_vis aos2_vis_t;
+
+typedef struct {
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y;   /* MinX, MaxX, MinY, MaxY: the window of :285-289 */
+    float max_dist, min_dist;           /* :293 */
+    int32_t feature_threshold;
+    float T_sw[16], T_bc[16];           /* row-major */
+} aos2_vis_camera_t;
+#define AOS2_VIS_CAMERA_MAP 0     /* camera(map_data, int) :5-70:  window 930 / 10 / 520 / 20, distances 6 / 0.5 */
+#define AOS2_VIS_CAMERA_PLAIN 1   /* camera() :105-132:            window 950 / 10 / 530 / 10, distances 6 / 0.1, threshold 20 */
+/* the constants of one of the reference's constructors (fx .. cy, T_sw and T_bc are the same in both); feature_threshold = 20
+ * (camera(map_data, int) takes it from its caller).  They are inputs of the handle, not built in. */
+int aos2_vis_camera_default(int which, aos2_vis_camera_t *cam);
+
+/* a handle starts with the AOS2_VIS_CAMERA_MAP constants and an empty map */
+int aos2_vis_create(int device, aos2_vis_t **out);
+void aos2_vis_destroy(aos2_vis_t *h);
+/* AOS2_ERR_ARG if a constant is not finite */
+int aos2_vis_set_camera(aos2_vis_t *h, const aos2_vis_camera_t *cam);
+/* The planner's map (plan_slam::UpdateMap src/plan.cc:129-139 -> camera(map_data, int) :23-44, which narrows map_data's doubles to
+ * float: the caller does the same): xyz [n][3], upper / lower [n] (the viewing-direction bounds), max_range / min_range [n],
+ * found_ratio [n].  n == 0 is legal.  The map replaces the one before and stays in HBM until the next call.  Needs no device:
+ * the copy goes up with the next count. */
+int aos2_vis_set_map(aos2_vis_t *h, int n, const float *xyz, const float *upper, const float *lower, const float *max_range,
+                     const float *min_range, const float *found_ratio);
+int aos2_vis_map_size(const aos2_vis_t *h);
+/* points a workgroup of the gate kernel takes, and states of its tile: the sizes at which the kernel changes block (for tests) */
+void aos2_vis_gate_tile(int *points, int *states);
+
+/* countVisible(float x_w, float y_w, float theta_rad_w) :135-167 for ns states [ns][3] = x, y, theta: count [ns] =
+ * int(round(num_visible)).  Optional (NULL: not wanted): sum [ns] = num_visible itself, the ratios of the passing points added in
+ * point order; mask [ns][ceil(n / 64)]: bit i % 64 of word i / 64 says that point i passed isInFrustum.  ns == 0 is AOS2_OK. */
+int aos2_vis_count(aos2_vis_t *h, int ns, const float *states, int32_t *count, float *sum, uint64_t *mask);
+/* countVisible(cv::Mat Twb) :170-198: T_wb [ns][16] row-major float */
+int aos2_vis_count_poses(aos2_vis_t *h, int ns, const float *T_wb, int32_t *count, float *sum, uint64_t *mask);
+/* StateValidChecker::MotionCostCamera (src/StateValidChecker.cc:531-541) for nm motions in one call: motion m is the states
+ * offsets[m] .. offsets[m + 1] - 1 of states [offsets[nm]][3]; cost [nm] = the terms c < thres ? 1./1e-4 : 1./c of its states
+ * 1 .. size - 2, added in index order (sizes 1 and 2 give 0).  A motion of size 0 is AOS2_ERR_ARG (the reference's Q.size()-1
+ * underflows there), as are offsets that do not start at 0 or descend.  thres < 0: the camera's feature_threshold. */
+int aos2_vis_motion_costs(aos2_vis_t *h, int nm, const int32_t *offsets, const float *states, int thres, double *cost);
+/* plan_slam::AdvanceStepCamera (src/plan.cc:141-151) over IsStateVisiblilty (src/camera.cc:242-250): *index = the last index of
+ * the leading run of states with count > thres, -1 if the first state fails (or ns == 0).  thres == -1: feature_threshold. */
+int aos2_vis_advance(aos2_vis_t *h, int ns, const float *states, int thres, int32_t *index);
+float aos2_vis_last_device_ms(const aos2_vis_t *h);   /* device time of the last call's kernels (HIP events) */
+
+/* ------------------------------------------------------------------------------------------
  * ORBmatcher  (include/ORBmatcher.h:37-102, src/ORBmatcher.cc)
  * The C++ shim snapshots the Frame / KeyFrame / MapPoint fields each method reads into the SoA
  * views below and maps the returned indices back to MapPoint*.
@@ -1307,6 +1362,14 @@ int aos2_debug_pnp_host(const aos2_pnp_problem_t *problems, aos2_pnp_result_t *r
 int aos2_debug_kfdb_host(aos2_kfdb_t *db, const aos2_kfdb_query_t *queries, aos2_kfdb_result_t *results, int nq);
 int aos2_debug_kfdb_scores_host(aos2_kfdb_t *db, const aos2_kfdb_query_t *query, const int32_t *slots, int n, float *scores,
                                 float *min_score);
+/* aos2_vis_count / _count_poses / _motion_costs / _advance on the HOST with the routines the device kernels also run
+ * (csrc/visibility.h): the reference's loop, one state and one point at a time on one core, over the handle's map and camera.
+ * The same arguments and the same checks; they need no device. */
+int aos2_debug_visibility_host(aos2_vis_t *h, int ns, const float *states, int32_t *count, float *sum, uint64_t *mask);
+int aos2_debug_visibility_poses_host(aos2_vis_t *h, int ns, const float *T_wb, int32_t *count, float *sum, uint64_t *mask);
+int aos2_debug_visibility_motion_costs_host(aos2_vis_t *h, int nm, const int32_t *offsets, const float *states, int thres,
+                                            double *cost);
+int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *states, int thres, int32_t *index);
 /* the indices that the draws `row` [min_set] select from 0..n-1 (src/PnPsolver.cc:188-201) as csrc/pnp.h forms them -> indices */
 int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices);
 /* the loop of PnPsolver::iterate (:182-239) as csrc/pnp.h replays it over tables: counts [n_iterations] (read from first_iteration),
