@@ -134,6 +134,23 @@ def lib():
             getattr(L, nm).argtypes = [vp, ci, vp, vp, ci, vp]
         for nm in ("aos2_vis_advance", "aos2_debug_visibility_advance_host"):
             getattr(L, nm).argtypes = [vp, ci, vp, ci, C.POINTER(C.c_int32)]
+        L.aos2_svc_params_default.argtypes = [vp]
+        L.aos2_svc_create.argtypes = [ci, C.POINTER(vp)]
+        L.aos2_svc_destroy.argtypes = [vp]
+        L.aos2_svc_destroy.restype = None
+        L.aos2_svc_vis.argtypes = [vp]
+        L.aos2_svc_vis.restype = vp
+        L.aos2_svc_set_params.argtypes = [vp, vp]
+        L.aos2_svc_set_obstacles.argtypes = [vp, ci, vp, C.c_double]
+        L.aos2_svc_collide_tile.argtypes = [C.POINTER(ci), C.POINTER(ci)]
+        L.aos2_svc_collide_tile.restype = None
+        L.aos2_svc_last_device_ms.argtypes = [vp]
+        L.aos2_svc_last_device_ms.restype = cf
+        for nm in ("aos2_svc_valid", "aos2_debug_svc_valid_host"):
+            getattr(L, nm).argtypes = [vp, ci, vp, vp, vp, vp]
+        for nm in ("aos2_svc_motions", "aos2_debug_svc_motions_host"):
+            getattr(L, nm).argtypes = [vp, ci, vp, vp, vp]
+        L.aos2_debug_tw_math.argtypes = [ci, ci] + [vp] * 7
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
@@ -1063,6 +1080,130 @@ class Visibility:
         f = self.L.aos2_debug_visibility_advance_host if host else self.L.aos2_vis_advance
         _check(f(self.h, len(st), _p(st), int(thres), C.byref(idx)))
         return idx.value
+
+
+# ---- planner motion checks (include/aos2.h: aos2_svc_*, aos2_debug_svc_*host, aos2_debug_tw_math)
+class SvcParams(C.Structure):
+    """aos2_svc_params_t"""
+    _fields_ = [(k, C.c_double) for k in ("turn_radius", "robot_r", "dt", "min_x", "max_x", "min_y", "max_y", "max_dist_heuristic")] + \
+               [("start", C.c_double * 3), ("heuristic", C.c_int32), ("feature_threshold", C.c_int32)]
+
+
+class _SvcMotionsOut(C.Structure):
+    """aos2_svc_motions_out_t"""
+    _fields_ = [(k, C.c_void_p) for k in ("path_valid", "type", "t", "m", "n_states", "valid", "first_invalid", "cost_length",
+                                          "cost_camera", "offsets", "states")] + \
+               [("states_capacity", C.c_int64), ("states_needed", C.c_int64)]
+
+
+class _OwnedVisibility(Visibility):
+    """the visibility handle a StateValidChecker owns: it dies with its owner"""
+
+    def __init__(self, owner, h):
+        self.L, self.h, self.owner = lib(), C.c_void_p(h), owner
+
+    def close(self):
+        self.h = None
+
+    __del__ = close
+
+
+class StateValidChecker:
+    """StateValidChecker (include/StateValidChecker.h:47-150) for batches: the obstacles and the camera's map resident on the
+    device, isValid for ns states and checkMotionTW / reconstructMotionTW / MotionCost for nm pairs of states in one call.
+    host=True runs the library's own serial routine (aos2_debug_svc_*host) instead.  `vis` is the camera base: set_camera and
+    set_map go there."""
+    MOTION_FIELDS = (("path_valid", np.uint8, 1), ("type", np.int32, 1), ("t", np.float64, 3), ("m", np.int32, 3), ("n_states", np.int32, 1),
+                     ("valid", np.uint8, 1), ("first_invalid", np.int32, 1), ("cost_length", np.float64, 1), ("cost_camera", np.float64, 1))
+
+    def __init__(self, device=0):
+        self.L = lib()
+        h = C.c_void_p()
+        _check(self.L.aos2_svc_create(device, C.byref(h)))
+        self.h = h
+        self.vis = _OwnedVisibility(self, self.L.aos2_svc_vis(h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.vis.close()
+            self.L.aos2_svc_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def params_default():
+        p = SvcParams()
+        _check(lib().aos2_svc_params_default(C.byref(p)))
+        return p
+
+    @staticmethod
+    def collide_tile():
+        """(obstacles a workgroup of the collision kernel stages at a time, states of its tile)"""
+        o, s = C.c_int(0), C.c_int(0)
+        lib().aos2_svc_collide_tile(C.byref(o), C.byref(s))
+        return o.value, s.value
+
+    def set_params(self, p: SvcParams):
+        _check(self.L.aos2_svc_set_params(self.h, C.byref(p)))
+
+    def set_obstacles(self, xy, obs_r=0.1):
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        _check(self.L.aos2_svc_set_obstacles(self.h, len(xy), _p(xy), float(obs_r)))
+
+    def last_device_ms(self):
+        return float(self.L.aos2_svc_last_device_ms(self.h))
+
+    def valid(self, states, host=False):
+        """aos2_svc_valid: states [ns][3] float64 -> dict(valid uint8 [ns], collision_free uint8 [ns], count int32 [ns])"""
+        st = np.ascontiguousarray(states, np.float64).reshape(-1, 3)
+        out = dict(valid=np.zeros(len(st), np.uint8), collision_free=np.zeros(len(st), np.uint8), count=np.zeros(len(st), np.int32))
+        f = self.L.aos2_debug_svc_valid_host if host else self.L.aos2_svc_valid
+        _check(f(self.h, len(st), _p(st), _p(out["valid"]), _p(out["collision_free"]), _p(out["count"])))
+        return out
+
+    def motions(self, q1, q2, states=True, capacity=None, host=False):
+        """aos2_svc_motions: q1, q2 [nm][3] float64 -> a dict of the per-motion arrays (MOTION_FIELDS) and, with states, offsets
+        int32 [nm + 1] and states float64 [total][3].  capacity: the rows of the states buffer (default: asked for with a first
+        call).  A buffer too small raises AosError(AOS2_ERR_CAPACITY) with .needed = the rows needed."""
+        a = np.ascontiguousarray(q1, np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(q2, np.float64).reshape(-1, 3)
+        if len(a) != len(b):
+            raise ValueError("q1 and q2 differ in length")
+        nm = len(a)
+        f = self.L.aos2_debug_svc_motions_host if host else self.L.aos2_svc_motions
+        out = {k: np.zeros((nm, w) if w > 1 else nm, dt) for k, dt, w in self.MOTION_FIELDS}
+        O = _SvcMotionsOut()
+        for k in out:
+            setattr(O, k, out[k].ctypes.data)
+        if states:
+            if capacity is None:      # the size first: a call that asks for no states reports the rows needed
+                probe = _SvcMotionsOut()
+                _check(f(self.h, nm, _p(a), _p(b), C.byref(probe)))
+                capacity = probe.states_needed
+            out["offsets"] = np.zeros(nm + 1, np.int32)
+            buf = np.zeros((max(int(capacity), 1), 3), np.float64)
+            O.offsets, O.states, O.states_capacity = out["offsets"].ctypes.data, buf.ctypes.data, int(capacity)
+        st = f(self.h, nm, _p(a), _p(b), C.byref(O))
+        if st == AOS2_ERR_CAPACITY:
+            e = AosError(st, lib().aos2_last_error().decode(errors="replace"))
+            e.needed = int(O.states_needed)
+            raise e
+        _check(st)
+        if states:
+            out["states"] = buf[: int(O.states_needed)]
+        return out
+
+
+def debug_tw_math(x, y, device=-1):
+    """aos2_debug_tw_math: tw_sin(x), tw_cos(x), tw_atan2(y, x), sqrt(x), y / x of csrc/motion_tw.h on the host (device -1) or in a
+    kernel -> dict of float64 arrays"""
+    x, y = np.ascontiguousarray(x, np.float64).reshape(-1), np.ascontiguousarray(y, np.float64).reshape(-1)
+    if len(x) != len(y):
+        raise ValueError("x and y differ in length")
+    out = {k: np.zeros(len(x), np.float64) for k in ("sin", "cos", "atan2", "sqrt", "quot")}
+    _check(lib().aos2_debug_tw_math(int(device), len(x), _p(x), _p(y), *[_p(out[k]) for k in ("sin", "cos", "atan2", "sqrt", "quot")]))
+    return out
 
 
 def ComputeStereoMatches(left: Extractor, right: Extractor, kps_l, desc_l, kps_r, desc_r, mb, mbf, image=0):

@@ -11,6 +11,7 @@
 #include "sim3.h"
 #include "triangulate.h"
 #include "visibility.h"
+#include "motion_tw.h"
 #include "wave_ops.h"
 
 namespace aos2 {
@@ -673,6 +674,99 @@ int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *state
         if (!(c > thr)) break;
     }
     *index = i - 1;
+    return AOS2_OK;
+}
+
+// check_collisions (src/collisions.cc:70-94) and countVisible of one state, then isValid (src/StateValidChecker.cc:97-119)
+static bool svc_valid_host(const aos2::SvcView &V, const double *q, uint8_t *cfree_out, int32_t *count_out)
+{
+    using namespace aos2;
+    int gate = tw_collision_gate(q, V.n_obs, V.params);
+    if (gate < 0) {
+        double best = INFINITY;
+        for (int i = 0; i < V.n_obs; ++i) {
+            const double d2 = tw_obstacle_d2(q, V.obs[2 * (size_t)i], V.obs[2 * (size_t)i + 1]);
+            best = d2 < best ? d2 : best;
+        }
+        gate = tw_collision_free(best, V.params.robot_r, V.obs_r) ? 1 : 0;
+    }
+    const float f[3] = {(float)q[0], (float)q[1], (float)q[2]};   // the narrowing of countVisible(float, float, float)
+    int32_t c;
+    vis_count_host(V.vis, 1, f, false, &c, nullptr, nullptr);
+    if (cfree_out) *cfree_out = (uint8_t)gate;
+    if (count_out) *count_out = c;
+    return tw_is_valid(q, gate != 0, c, V.thr, V.params);
+}
+
+int aos2_debug_svc_valid_host(aos2_svc_t *h, int ns, const double *states, uint8_t *valid, uint8_t *collision_free, int32_t *count)
+{
+    using namespace aos2;
+    if (int st = svc_check_valid(h, ns, states, valid)) return st;
+    SvcView V;
+    svc_view(h, &V);
+    for (int i = 0; i < ns; ++i)
+        valid[i] = svc_valid_host(V, states + 3 * (size_t)i, collision_free ? collision_free + i : nullptr, count ? count + i : nullptr) ? 1 : 0;
+    return AOS2_OK;
+}
+
+int aos2_debug_svc_motions_host(aos2_svc_t *h, int nm, const double *q1, const double *q2, aos2_svc_motions_out_t *out)
+{
+    using namespace aos2;
+    if (int st = svc_check_motions(h, nm, q1, q2, out)) return st;
+    SvcView V;
+    svc_view(h, &V);
+    out->states_needed = 0;
+    std::vector<TwPlan> plans(nm);
+    long long total = 0;
+    for (int m = 0; m < nm; ++m) {
+        tw_shortest_path(q1 + 3 * (size_t)m, q2 + 3 * (size_t)m, V.params.turn_radius, V.params.dt, plans[m]);
+        if (plans[m].too_long) {
+            set_error("motion checks: a segment of motion %d has more than %d states", m, AOS2_SVC_MAX_SEGMENT_STATES);
+            return AOS2_ERR_ARG;
+        }
+        total += plans[m].n_states;
+    }
+    out->states_needed = total;
+    if (total > 0x7fffffffll / 3) {
+        set_error("motion checks: the motions have %lld states together, more than a call takes", total);
+        return AOS2_ERR_ARG;
+    }
+    if (out->states && out->states_capacity < total) {
+        set_error("motion checks: the states need %lld rows, the buffer has %lld", total, (long long)out->states_capacity);
+        return AOS2_ERR_CAPACITY;
+    }
+    int32_t off = 0;
+    std::vector<double> Q;
+    for (int m = 0; m < nm; ++m) {
+        const TwPlan &P = plans[m];
+        const int n = P.n_states;
+        Q.resize(3 * (size_t)n);
+        for (int i = 0; i < n; ++i) tw_plan_state(q1 + 3 * (size_t)m, P, i, &Q[3 * (size_t)i]);
+        int first = -1;
+        double len = 0, camc = 0;
+        for (int i = 1; i < n; ++i) {
+            int32_t c;
+            const bool ok = svc_valid_host(V, &Q[3 * (size_t)i], nullptr, &c);
+            if (first < 0 && !ok) first = i;
+            len += tw_length_term(&Q[3 * (size_t)(i - 1)], &Q[3 * (size_t)i]);
+            if (i < n - 1) camc += vis_motion_cost_term(c, V.thr);
+        }
+        if (out->path_valid) out->path_valid[m] = (uint8_t)P.valid;
+        if (out->type) out->type[m] = P.type;
+        for (int k = 0; k < 3; ++k) {
+            if (out->t) out->t[3 * (size_t)m + k] = P.t[k];
+            if (out->m) out->m[3 * (size_t)m + k] = P.m[k];
+        }
+        if (out->n_states) out->n_states[m] = n;
+        if (out->valid) out->valid[m] = P.valid && first < 0 ? 1 : 0;
+        if (out->first_invalid) out->first_invalid[m] = first;
+        if (out->cost_length) out->cost_length[m] = len;
+        if (out->cost_camera) out->cost_camera[m] = camc;
+        if (out->offsets) out->offsets[m] = off;
+        if (out->states) std::copy(Q.begin(), Q.end(), out->states + 3 * (size_t)off);
+        off += n;
+    }
+    if (out->offsets) out->offsets[nm] = off;
     return AOS2_OK;
 }
 

@@ -147,5 +147,11 @@ int vis_check_motions(const aos2_vis_t *h, int nm, const int32_t *offsets, const
 int vis_check_advance(const aos2_vis_t *h, int ns, const float *states, const int32_t *index);
 // the interior states (i = 1 .. size-2) of every motion, packed, with their offsets [nm + 1]
 void vis_interior(int nm, const int32_t *offsets, const float *states, std::vector<float> &packed, std::vector<int32_t> &packed_off);
+#if defined(__HIPCC__)
+// For the library's other device paths (csrc/motion_tw.hip): countVisible of ns float states [ns][3] that are ON THE DEVICE, enqueued
+// on the caller's stream s (the map goes up on s too if it changed) with no wait.  *count: the handle's device array of the ns
+// counts, good until the handle's next call.  ns >= 1.  The caller's stream is the only one that may touch the handle meanwhile.
+int vis_counts_on_device(aos2_vis_t *h, int ns, const float *d_states, hipStream_t s, const int32_t **count);
+#endif
 
 }  // namespace aos2

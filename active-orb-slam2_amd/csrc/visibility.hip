@@ -237,26 +237,31 @@ int init_device(aos2_vis *h)
     return AOS2_OK;
 }
 
-// The counts of ns states into d_sum / d_count, between the handle's two events (the caller records the second one, after the
-// kernels it adds).  `in`: [ns][3] states or, with poses, [ns][16] matrices, host memory that outlives the stream's next wait.
-int launch_counts(aos2_vis *h, int ns, const float *in, bool poses)
+// the handle's map into HBM on stream s, if it changed since the last upload
+int upload_map(aos2_vis *h, hipStream_t s)
+{
+    if (!h->map_dirty) return AOS2_OK;
+    if (int st = h->d_map.alloc(h->map.size())) return st;
+    if (!h->map.empty()) AOS2_HIP_CHECK(hipMemcpyAsync(h->d_map.p, h->map.data(), h->map.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    h->map_dirty = false;
+    return AOS2_OK;
+}
+
+// what the three kernels write for ns states
+int alloc_counts(aos2_vis *h, int ns)
 {
     int st;
-    if ((st = init_device(h))) return st;
-    hipStream_t s = h->stream;
-    const int n = h->n, words = (n + 63) / 64;
-    if (h->map_dirty) {
-        if ((st = h->d_map.alloc(h->map.size()))) return st;
-        if (!h->map.empty()) AOS2_HIP_CHECK(hipMemcpyAsync(h->d_map.p, h->map.data(), h->map.size() * sizeof(float), hipMemcpyHostToDevice, s));
-        h->map_dirty = false;
-    }
-    const size_t per = poses ? 16 : 3;
-    if ((st = h->d_in.alloc(per * ns)) || (st = h->d_states.alloc(ns)) || (st = h->d_mask.alloc((size_t)ns * words)) ||
-        (st = h->d_sum.alloc(ns)) || (st = h->d_count.alloc(ns)))
+    const int words = (h->n + 63) / 64;
+    if ((st = h->d_states.alloc(ns)) || (st = h->d_mask.alloc((size_t)ns * words)) || (st = h->d_sum.alloc(ns)) || (st = h->d_count.alloc(ns)))
         return st;
-    AOS2_HIP_CHECK(hipMemcpyAsync(h->d_in.p, in, per * ns * sizeof(float), hipMemcpyHostToDevice, s));
-    AOS2_HIP_CHECK(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(k_vis_setup, dim3((ns + kNT - 1) / kNT), dim3(kNT), 0, s, h->cam, h->d_in.p, ns, poses ? 1 : 0, h->d_states.p);
+    return AOS2_OK;
+}
+
+// the three kernels over ns states that are on the device already: `in` [ns][3] states or, with poses, [ns][16] matrices
+int run_counts(aos2_vis *h, int ns, const float *in, bool poses, hipStream_t s)
+{
+    const int n = h->n, words = (n + 63) / 64;
+    hipLaunchKernelGGL(k_vis_setup, dim3((ns + kNT - 1) / kNT), dim3(kNT), 0, s, h->cam, in, ns, poses ? 1 : 0, h->d_states.p);
     AOS2_HIP_CHECK(hipGetLastError());
     if (n > 0) {
         hipLaunchKernelGGL(k_vis_gate, dim3((ns + kStateTile - 1) / kStateTile, (n + kPointsPerWG - 1) / kPointsPerWG), dim3(kNT), 0, s,
@@ -267,6 +272,21 @@ int launch_counts(aos2_vis *h, int ns, const float *in, bool poses)
                        ns, h->d_sum.p, h->d_count.p);
     AOS2_HIP_CHECK(hipGetLastError());
     return AOS2_OK;
+}
+
+// The counts of ns states into d_sum / d_count, between the handle's two events (the caller records the second one, after the
+// kernels it adds).  `in`: [ns][3] states or, with poses, [ns][16] matrices, host memory that outlives the stream's next wait.
+int launch_counts(aos2_vis *h, int ns, const float *in, bool poses)
+{
+    int st;
+    if ((st = init_device(h))) return st;
+    hipStream_t s = h->stream;
+    if ((st = upload_map(h, s))) return st;
+    const size_t per = poses ? 16 : 3;
+    if ((st = h->d_in.alloc(per * ns)) || (st = alloc_counts(h, ns))) return st;
+    AOS2_HIP_CHECK(hipMemcpyAsync(h->d_in.p, in, per * ns * sizeof(float), hipMemcpyHostToDevice, s));
+    AOS2_HIP_CHECK(hipEventRecord(h->ev[0], s));
+    return run_counts(h, ns, h->d_in.p, poses, s);
 }
 
 int finish(aos2_vis *h)
@@ -291,6 +311,18 @@ int count(aos2_vis *h, int ns, const float *in, bool poses, int32_t *cnt, float 
 }
 
 }  // namespace
+
+namespace aos2 {
+
+int vis_counts_on_device(aos2_vis_t *h, int ns, const float *d_states, hipStream_t s, const int32_t **count)
+{
+    int st;
+    if ((st = init_device(h)) || (st = upload_map(h, s)) || (st = alloc_counts(h, ns)) || (st = run_counts(h, ns, d_states, false, s))) return st;
+    *count = h->d_count.p;
+    return AOS2_OK;
+}
+
+}  // namespace aos2
 
 extern "C" {
 

@@ -117,6 +117,17 @@ public:
 
     int feature_threshold;
 
+protected:
+    // this object's constants and map onto another visibility handle: the one the checker derived from this class owns
+    // (host/StateValidChecker.h, aos2_svc_vis)
+    void LoadInto(aos2_vis_t *h) const
+    {
+        aos2::check(aos2_vis_set_camera(h, &mCam), "camera");
+        aos2::check(aos2_vis_set_map(h, (int)mUpper.size(), mXyz.data(), mUpper.data(), mLower.data(), mMaxRange.data(), mMinRange.data(),
+                                     mFoundRatio.data()),
+                    "camera");
+    }
+
 private:
     static std::vector<float> Narrow(const std::vector<std::vector<double> > &Q)
     {

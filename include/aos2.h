@@ -441,6 +441,73 @@ int aos2_vis_advance(aos2_vis_t *h, int ns, const float *states, int thres, int3
 float aos2_vis_last_device_ms(const aos2_vis_t *h);   /* device time of the last call's kernels (HIP events) */
 
 /* ------------------------------------------------------------------------------------------
+ * StateValidChecker (planner motion checks)  (include/StateValidChecker.h:47-150, src/StateValidChecker.cc, src/collisions.cc)
+ * What RRT* asks for every neighbour of a new node (src/myRRTstar.cc:302-464): the two-wheel shortest path between two states
+ * (GetShortestPath :313-367), its states in steps of dt (myprop :296-311), isValid of each (:97-119 = check_collisions
+ * src/collisions.cc:70-94, then camera::IsStateVisiblilty) and the two motion costs (:522-578).  The reference does this for one
+ * pair of states per call, serially; here a call takes a batch of (q1, q2) pairs.  All of it is double arithmetic with sin, cos and
+ * atan2 as fixed operation sequences (csrc/motion_tw.h), so the device, the host taps and the tests' restatement agree bit for
+ * bit.
+ * A state is x, y, theta.  A component that is not finite, or |theta| > 1e4, is AOS2_ERR_ARG (csrc/motion_tw.h says why).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aos2_svc aos2_svc_t;
+
+typedef struct {
+    double turn_radius, robot_r, dt;       /* TURN_RADIUS 0.25, ROBOT_RADIUS 0.4, DT 0.3  include/StateValidChecker.h:28-30 */
+    double min_x, max_x, min_y, max_y;     /* MIN_X -1.15, MAX_X 6.5, MIN_Y -5, MAX_Y 5   include/collisions.h:30-33 */
+    double max_dist_heuristic;             /* MAX_DIST_HEURISTIC 2  include/StateValidChecker.h:31 */
+    double start[3];                       /* StartState (setStartState :76-80); read only with `heuristic` */
+    int32_t heuristic;                     /* heuristicValidityCheck, 0 as every constructor of the reference leaves it */
+    int32_t feature_threshold;             /* -1: the feature_threshold of the handle's camera */
+} aos2_svc_params_t;
+#define AOS2_SVC_MAX_SEGMENT_STATES (1 << 20)   /* states one of a path's three segments may have; more is AOS2_ERR_ARG */
+
+int aos2_svc_params_default(aos2_svc_params_t *p);
+/* a handle starts with the default parameters, no obstacles, and a visibility handle with the AOS2_VIS_CAMERA_MAP constants and an
+ * empty map */
+int aos2_svc_create(int device, aos2_svc_t **out);
+void aos2_svc_destroy(aos2_svc_t *h);
+/* the camera base of the class: the handle's own visibility handle (it dies with the handle).  Camera and map are set on it with
+ * aos2_vis_set_camera / aos2_vis_set_map. */
+aos2_vis_t *aos2_svc_vis(aos2_svc_t *h);
+/* AOS2_ERR_ARG if a value is not finite, or turn_radius or dt is not positive */
+int aos2_svc_set_params(aos2_svc_t *h, const aos2_svc_params_t *p);
+/* collisionDetection(ppMatrix FloorMap) src/collisions.cc:23-37: xy [n][2]; obs_r is the class's 0.1 (include/collisions.h:61)
+ * unless the caller loaded a file (load_obstacles :39-64 takes the last row's r).  n == 0 is legal and makes check_collisions true
+ * for every state (:73).  The obstacles replace the ones before and stay in HBM until the next call.  Needs no device. */
+int aos2_svc_set_obstacles(aos2_svc_t *h, int n, const double *xy, double obs_r);
+/* obstacles a workgroup of the collision kernel stages at a time, and states of its tile (for tests) */
+void aos2_svc_collide_tile(int *obstacles, int *states);
+
+/* StateValidChecker::isValid(Vector) :97-119 for ns states [ns][3] (Planning.cc:190, checkMotion's interpolated states :121-161).
+ * valid [ns]; optional: collision_free [ns] = check_collisions(q, robot_r), count [ns] = countVisible of the state narrowed to
+ * float, for every state whether or not isValid reaches it. */
+int aos2_svc_valid(aos2_svc_t *h, int ns, const double *states, uint8_t *valid, uint8_t *collision_free, int32_t *count);
+
+typedef struct {
+    /* per motion, [nm] unless said otherwise; NULL: not wanted */
+    uint8_t *path_valid;     /* GetShortestPath(q1, q2).valid :313-367 */
+    int32_t *type;           /* the winning candidate in the order of the loops :337-339, (s1, s2, dir) = (-1,-1,-1) is 0, (-1,-1,1) is 1,
+                                .. (1,1,1) is 7; -1 without a path */
+    double *t;               /* [nm][3] vwt.t; zeros without a path */
+    int32_t *m;              /* [nm][3] 1 + ceil(t[i] / dt) :259; zeros without a path */
+    int32_t *n_states;       /* Q.size() of reconstructMotionTW :273-294 (1 without a path: MotionCost's Q = {q1} :561-562) */
+    uint8_t *valid;          /* checkMotionTW :244-271 */
+    int32_t *first_invalid;  /* the index into Q of the state at which checkMotionTW returns false, -1 if none does */
+    double *cost_length;     /* MotionCost(s1, s2, 1) :543-578 */
+    double *cost_camera;     /* MotionCost(s1, s2, 2) */
+    /* reconstructMotionTW of every motion: motion k is the states offsets[k] .. offsets[k + 1] - 1 */
+    int32_t *offsets;        /* [nm + 1] */
+    double *states;          /* [states_capacity][3] */
+    int64_t states_capacity; /* in: rows `states` holds */
+    int64_t states_needed;   /* out: the rows all motions have together, also when the call fails with AOS2_ERR_CAPACITY */
+} aos2_svc_motions_out_t;
+/* q1, q2 [nm][3].  With `states` set and states_capacity below the total: AOS2_ERR_CAPACITY, states_needed says how many rows are
+ * needed and no output is written.  nm == 0 is AOS2_OK. */
+int aos2_svc_motions(aos2_svc_t *h, int nm, const double *q1, const double *q2, aos2_svc_motions_out_t *out);
+float aos2_svc_last_device_ms(const aos2_svc_t *h);   /* device time of the last call (HIP events; aos2_svc_motions: its one host wait included) */
+
+/* ------------------------------------------------------------------------------------------
  * ORBmatcher  (include/ORBmatcher.h:37-102, src/ORBmatcher.cc)
  * The C++ shim snapshots the Frame / KeyFrame / MapPoint fields each method reads into the SoA
  * views below and maps the returned indices back to MapPoint*.
@@ -1370,6 +1437,16 @@ int aos2_debug_visibility_poses_host(aos2_vis_t *h, int ns, const float *T_wb, i
 int aos2_debug_visibility_motion_costs_host(aos2_vis_t *h, int nm, const int32_t *offsets, const float *states, int thres,
                                             double *cost);
 int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *states, int thres, int32_t *index);
+/* aos2_svc_valid / aos2_svc_motions on the HOST with the routines the device kernels also run (csrc/motion_tw.h): the reference's
+ * loops, one motion, one state and one obstacle at a time on one core.  The same arguments and the same checks, made before a
+ * device is looked for; they need none. */
+int aos2_debug_svc_valid_host(aos2_svc_t *h, int ns, const double *states, uint8_t *valid, uint8_t *collision_free, int32_t *count);
+int aos2_debug_svc_motions_host(aos2_svc_t *h, int nm, const double *q1, const double *q2, aos2_svc_motions_out_t *out);
+/* the math of csrc/motion_tw.h on arrays of n doubles: sin = tw_sin(x), cos = tw_cos(x), atan2 = tw_atan2(y, x), sqrt = sqrt(x),
+ * quot = y / x; on the host (device == -1) or in a kernel of one lane per element.  It tells whether a difference between the two
+ * sides comes from the math or from the logic.  Any x and y (the domain check of the states does not apply). */
+int aos2_debug_tw_math(int device, int n, const double *x, const double *y, double *sin, double *cos, double *atan2, double *sqrt,
+                       double *quot);
 /* the indices that the draws `row` [min_set] select from 0..n-1 (src/PnPsolver.cc:188-201) as csrc/pnp.h forms them -> indices */
 int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices);
 /* the loop of PnPsolver::iterate (:182-239) as csrc/pnp.h replays it over tables: counts [n_iterations] (read from first_iteration),
