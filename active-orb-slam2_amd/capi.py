@@ -151,6 +151,18 @@ def lib():
         for nm in ("aos2_svc_motions", "aos2_debug_svc_motions_host"):
             getattr(L, nm).argtypes = [vp, ci, vp, vp, vp]
         L.aos2_debug_tw_math.argtypes = [ci, ci] + [vp] * 7
+        L.aos2_local_map_create.argtypes = [ci, C.POINTER(vp)]
+        L.aos2_local_map_destroy.argtypes = [vp]
+        L.aos2_local_map_destroy.restype = None
+        L.aos2_local_map_set.argtypes = [vp, vp]
+        L.aos2_local_map_get.argtypes = [vp, vp]
+        L.aos2_local_map_debug_limits.argtypes = [vp, C.c_int64, ci]
+        L.aos2_local_map_last_groups.argtypes = [vp]
+        L.aos2_frames_update_local_map.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp]
+        L.aos2_frames_track_local_map_stats.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.aos2_debug_local_map_host.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
+        L.aos2_local_map_update.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
+        L.aos2_debug_local_map_stats_host.argtypes = [vp, ci, ci, vp, vp, vp, ci, ci, vp, vp]
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
@@ -1193,6 +1205,134 @@ class StateValidChecker:
         if states:
             out["states"] = buf[: int(O.states_needed)]
         return out
+
+
+# ---- Tracking::UpdateLocalMap for frame batches (include/aos2.h: aos2_local_map_*, aos2_frames_update_local_map)
+_LM_I32 = ("point_nobs", "obs_off", "obs_kf", "kf_mp_off", "kf_mp", "kf_best", "kf_child_off", "kf_child", "kf_parent")
+_LM_U8 = ("point_bad", "kf_bad")
+
+
+class _LocalMapGraph(C.Structure):
+    """aos2_local_map_graph_t"""
+    _fields_ = [("n_points", C.c_int32), ("point_bad", C.c_void_p), ("point_nobs", C.c_void_p), ("obs_off", C.c_void_p),
+                ("obs_kf", C.c_void_p), ("n_keyframes", C.c_int32), ("kf_bad", C.c_void_p), ("kf_mp_off", C.c_void_p),
+                ("kf_mp", C.c_void_p), ("kf_best", C.c_void_p), ("kf_child_off", C.c_void_p), ("kf_child", C.c_void_p),
+                ("kf_parent", C.c_void_p)]
+
+
+def _local_map_graph(g, keep):
+    """a graph dict (the fields of aos2_local_map_graph_t; an array may be None = NULL) -> the struct; `keep` holds the arrays"""
+    s = _LocalMapGraph()
+    s.n_points, s.n_keyframes = int(g["n_points"]), int(g["n_keyframes"])
+    for k in _LM_I32 + _LM_U8:
+        a = g.get(k)
+        if a is None:
+            setattr(s, k, None)
+            continue
+        a = np.ascontiguousarray(a, np.uint8 if k in _LM_U8 else np.int32).reshape(-1)
+        keep.append(a)
+        setattr(s, k, a.ctypes.data if a.size else keep[0].ctypes.data)   # (an empty array is not NULL)
+    return s
+
+
+class LocalMap:
+    """The covisibility graph resident on the device and Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) for the frames of a
+    capi.Frames batch.  A graph is a dict with the fields of aos2_local_map_graph_t (numpy arrays, CSR offsets)."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        h = C.c_void_p()
+        _check(self.L.aos2_local_map_create(device, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.aos2_local_map_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set(self, graph, ok=(AOS2_OK,)):
+        """aos2_local_map_set; `ok`: the return values that do not raise (a machine without a device keeps a checked graph and
+        returns AOS2_ERR_NO_DEVICE)"""
+        keep = [np.zeros(1, np.int32)]
+        s = _local_map_graph(graph, keep)
+        return _check(self.L.aos2_local_map_set(self.h, C.byref(s)), ok)
+
+    def graph(self):
+        """the handle's snapshot as a graph dict (copies)"""
+        s = _LocalMapGraph()
+        _check(self.L.aos2_local_map_get(self.h, C.byref(s)))
+        npnt, nk = s.n_points, s.n_keyframes
+        g = dict(n_points=npnt, n_keyframes=nk)
+
+        def arr(p, n, dt):
+            if not n:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8 if dt == np.uint8 else C.c_int32)), (n,)).astype(dt, copy=True)
+
+        for k, n in (("obs_off", npnt + 1), ("kf_mp_off", nk + 1), ("kf_child_off", nk + 1), ("point_nobs", npnt), ("kf_parent", nk),
+                     ("kf_best", nk * 10)):
+            g[k] = arr(getattr(s, k), n, np.int32)
+        g["point_bad"], g["kf_bad"] = arr(s.point_bad, npnt, np.uint8), arr(s.kf_bad, nk, np.uint8)
+        for k, off in (("obs_kf", "obs_off"), ("kf_mp", "kf_mp_off"), ("kf_child", "kf_child_off")):
+            g[k] = arr(getattr(s, k), int(g[off][-1]), np.int32)
+        return g
+
+    def update(self, frames, d_local, local_cap, d_n_local, d_local_kfs, kf_cap, d_n_local_kfs, d_ref_kf):
+        """aos2_frames_update_local_map: device addresses (ints); enqueued on the batch's stream"""
+        _check(self.L.aos2_frames_update_local_map(frames.h, self.h, d_local, int(local_cap), d_n_local, d_local_kfs, int(kf_cap),
+                                                   d_n_local_kfs, d_ref_kf))
+
+    def stats(self, frames, d_stats, d_found_inc=0, stereo=False, only_tracking=False):
+        """aos2_frames_track_local_map_stats: d_stats int32 [batch][3], d_found_inc int32 [n_points] or 0"""
+        _check(self.L.aos2_frames_track_local_map_stats(frames.h, self.h, int(bool(stereo)), int(bool(only_tracking)), d_stats,
+                                                        d_found_inc or None))
+
+    def debug_limits(self, scratch_bytes=0, lds_keyframes=-1):
+        _check(self.L.aos2_local_map_debug_limits(self.h, int(scratch_bytes), int(lds_keyframes)))
+
+    def last_groups(self):
+        return self.L.aos2_local_map_last_groups(self.h)
+
+    def update_host(self, n, mp, local_cap, kf_cap, local_kfs=None, n_local_kfs=None, ref_kf=None):
+        """aos2_local_map_update: the device kernels on host arrays, arguments and result as host()"""
+        return self._on_host_arrays(self.L.aos2_local_map_update, self.h, n, mp, local_cap, kf_cap, local_kfs, n_local_kfs, ref_kf)
+
+    @staticmethod
+    def host(graph, n, mp, local_cap, kf_cap, local_kfs=None, n_local_kfs=None, ref_kf=None):
+        """aos2_debug_local_map_host: n int32 [B], mp int32 [B][cap]; the previous lists default to empty and ref_kf to -1 ->
+        dict(mp, local, n_local, local_kfs, n_local_kfs, ref_kf), new arrays"""
+        keep = [np.zeros(1, np.int32)]
+        s = _local_map_graph(graph, keep)
+        return LocalMap._on_host_arrays(lib().aos2_debug_local_map_host, C.byref(s), n, mp, local_cap, kf_cap, local_kfs, n_local_kfs, ref_kf)
+
+    @staticmethod
+    def _on_host_arrays(fn, first, n, mp, local_cap, kf_cap, local_kfs, n_local_kfs, ref_kf):
+        mp = np.array(mp, np.int32, ndmin=2)
+        B, cap = mp.shape
+        n = np.ascontiguousarray(n, np.int32).reshape(B)
+        lk = np.full((B, kf_cap), -1, np.int32) if local_kfs is None else np.array(local_kfs, np.int32).reshape(B, kf_cap)
+        nlk = np.zeros(B, np.int32) if n_local_kfs is None else np.array(n_local_kfs, np.int32).reshape(B)
+        ref = np.full(B, -1, np.int32) if ref_kf is None else np.array(ref_kf, np.int32).reshape(B)
+        local, n_local = np.full((B, local_cap), -7, np.int32), np.full(B, -7, np.int32)
+        _check(fn(first, B, cap, _p(n), _p(mp), _p(local), int(local_cap), _p(n_local), _p(lk), int(kf_cap), _p(nlk), _p(ref)))
+        return dict(mp=mp, local=local, n_local=n_local, local_kfs=lk, n_local_kfs=nlk, ref_kf=ref)
+
+    @staticmethod
+    def stats_host(graph, n, mp, outlier, stereo=False, only_tracking=False, found_inc=True):
+        """aos2_debug_local_map_stats_host -> dict(stats int32 [B][3], mp, found_inc int32 [n_points] | None)"""
+        mp = np.array(mp, np.int32, ndmin=2)
+        B, cap = mp.shape
+        n = np.ascontiguousarray(n, np.int32).reshape(B)
+        outlier = np.ascontiguousarray(outlier, np.uint8).reshape(B, cap)
+        stats = np.zeros((B, 3), np.int32)
+        inc = np.zeros(max(int(graph["n_points"]), 1), np.int32) if found_inc else None
+        keep = [np.zeros(1, np.int32)]
+        s = _local_map_graph(graph, keep)
+        _check(lib().aos2_debug_local_map_stats_host(C.byref(s), B, cap, _p(n), _p(mp), _p(outlier), int(bool(stereo)),
+                                                     int(bool(only_tracking)), _p(stats), _p(inc) if found_inc else None))
+        return dict(stats=stats, mp=mp, found_inc=None if inc is None else inc[:int(graph["n_points"])])
 
 
 def debug_tw_math(x, y, device=-1):

@@ -1,6 +1,8 @@
 // Test taps: host/device execution of shared primitives so parity tests can pin them in isolation.
 #include <algorithm>
 #include <cmath>
+#include <map>
+#include <set>
 #include <vector>
 
 #include "aos2_common.h"
@@ -11,6 +13,7 @@
 #include "sim3.h"
 #include "triangulate.h"
 #include "visibility.h"
+#include "local_map.h"
 #include "motion_tw.h"
 #include "wave_ops.h"
 
@@ -674,6 +677,156 @@ int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *state
         if (!(c > thr)) break;
     }
     *index = i - 1;
+    return AOS2_OK;
+}
+
+// Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) of one frame, written the way the reference is: a std::map of votes, a
+// std::set of children, the list a std::vector that grows while it is walked, marks per keyframe and per point
+// (mnTrackReferenceForFrame).  A keyframe row stands for the KeyFrame*, so the containers iterate in ascending row.
+// Returns whether there were votes (:1433).
+static bool local_map_frame_host(const aos2_local_map_graph_t &g, int N, int32_t *mp, std::vector<int32_t> &vpLocalKeyFrames,
+                                 std::vector<int32_t> &vpLocalMapPoints, int32_t &refKF)
+{
+    // UpdateLocalKeyFrames :1411-1519
+    std::map<int32_t, int> keyframeCounter;
+    for (int i = 0; i < N; i++) {
+        if (mp[i] >= 0 && mp[i] < g.n_points) {
+            const int32_t pMP = mp[i];
+            if (!g.point_bad[pMP]) {
+                for (int e = g.obs_off[pMP]; e < g.obs_off[pMP + 1]; e++) keyframeCounter[g.obs_kf[e]]++;
+            } else {
+                mp[i] = -1;
+            }
+        }
+    }
+    if (!keyframeCounter.empty()) {
+        int max = 0;
+        int32_t pKFmax = -1;
+        vpLocalKeyFrames.clear();
+        vpLocalKeyFrames.reserve(3 * keyframeCounter.size());
+        std::vector<uint8_t> inList(g.n_keyframes, 0);
+        for (std::map<int32_t, int>::const_iterator it = keyframeCounter.begin(), itEnd = keyframeCounter.end(); it != itEnd; it++) {
+            const int32_t pKF = it->first;
+            if (g.kf_bad[pKF]) continue;
+            if (it->second > max) {
+                max = it->second;
+                pKFmax = pKF;
+            }
+            vpLocalKeyFrames.push_back(pKF);
+            inList[pKF] = 1;
+        }
+        const size_t nFirst = vpLocalKeyFrames.size();
+        for (size_t itKF = 0; itKF < nFirst; itKF++) {
+            if (vpLocalKeyFrames.size() > AOS2_LOCAL_MAP_MAX_KFS) break;
+            const int32_t pKF = vpLocalKeyFrames[itKF];
+            for (int k = 0; k < AOS2_LOCAL_MAP_NEIGHBOURS; k++) {
+                const int32_t pNeighKF = g.kf_best[(size_t)pKF * AOS2_LOCAL_MAP_NEIGHBOURS + k];
+                if (pNeighKF < 0) continue;   // (the padding of a shorter list)
+                if (!g.kf_bad[pNeighKF]) {
+                    if (!inList[pNeighKF]) {
+                        vpLocalKeyFrames.push_back(pNeighKF);
+                        inList[pNeighKF] = 1;
+                        break;
+                    }
+                }
+            }
+            const std::set<int32_t> spChilds(g.kf_child + g.kf_child_off[pKF], g.kf_child + g.kf_child_off[pKF + 1]);
+            for (std::set<int32_t>::const_iterator sit = spChilds.begin(), send = spChilds.end(); sit != send; sit++) {
+                const int32_t pChildKF = *sit;
+                if (!g.kf_bad[pChildKF]) {
+                    if (!inList[pChildKF]) {
+                        vpLocalKeyFrames.push_back(pChildKF);
+                        inList[pChildKF] = 1;
+                        break;
+                    }
+                }
+            }
+            const int32_t pParent = g.kf_parent[pKF];
+            if (pParent >= 0) {
+                if (!inList[pParent]) {
+                    vpLocalKeyFrames.push_back(pParent);
+                    inList[pParent] = 1;
+                    break;
+                }
+            }
+        }
+        if (pKFmax >= 0) refKF = pKFmax;
+    }
+    // UpdateLocalPoints :1385-1408
+    vpLocalMapPoints.clear();
+    std::vector<uint8_t> listed(g.n_points, 0);
+    for (size_t itKF = 0; itKF < vpLocalKeyFrames.size(); itKF++) {
+        const int32_t pKF = vpLocalKeyFrames[itKF];
+        if (pKF < 0 || pKF >= g.n_keyframes) continue;   // (a caller's previous list, no votes)
+        for (int e = g.kf_mp_off[pKF]; e < g.kf_mp_off[pKF + 1]; e++) {
+            const int32_t pMP = g.kf_mp[e];
+            if (pMP < 0) continue;
+            if (listed[pMP]) continue;
+            if (!g.point_bad[pMP]) {
+                vpLocalMapPoints.push_back(pMP);
+                listed[pMP] = 1;
+            }
+        }
+    }
+    return !keyframeCounter.empty();
+}
+
+int aos2_debug_local_map_host(const aos2_local_map_graph_t *g, int batch, int cap, const int32_t *n, int32_t *mp, int32_t *local,
+                              int local_cap, int32_t *n_local, int32_t *local_kfs, int kf_cap, int32_t *n_local_kfs, int32_t *ref_kf)
+{
+    if (int st = aos2::local_map_check(g, nullptr)) return st;
+    if (batch < 0 || cap <= 0 || local_cap <= 0 || kf_cap <= 0 ||
+        (batch > 0 && (!n || !mp || !local || !n_local || !local_kfs || !n_local_kfs || !ref_kf))) {
+        aos2::set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    std::vector<int32_t> kfs, pts;
+    for (int b = 0; b < batch; ++b) {
+        int32_t *lk = local_kfs + (size_t)b * kf_cap, *lp = local + (size_t)b * local_cap;
+        const int n_in = std::max(0, std::min(n_local_kfs[b], kf_cap));
+        kfs.assign(lk, lk + n_in);
+        const int N = std::max(0, std::min(n[b], cap));
+        const bool voted = local_map_frame_host(*g, N, mp + (size_t)b * cap, kfs, pts, ref_kf[b]);
+        if (voted) {   // (no votes: the caller's rows stand as they are, whatever lies behind its count)
+            for (int j = 0; j < kf_cap; ++j) lk[j] = j < (int)kfs.size() ? kfs[j] : -1;
+            n_local_kfs[b] = (int32_t)kfs.size();
+        }
+        for (int j = 0; j < local_cap; ++j) lp[j] = j < (int)pts.size() ? pts[j] : -1;
+        n_local[b] = (int32_t)pts.size();
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, int cap, const int32_t *n, int32_t *mp,
+                                    const uint8_t *outlier, int stereo, int only_tracking, int32_t *stats, int32_t *found_inc)
+{
+    if (int st = aos2::local_map_check(g, nullptr)) return st;
+    if (batch < 0 || cap <= 0 || (batch > 0 && (!n || !mp || !outlier || !stats))) {
+        aos2::set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    for (int b = 0; b < batch; ++b) {   // src/Tracking.cc:1040-1071
+        int mnMatchesInliers = 0, nObsvMappoints = 0, totalObservation = 0;
+        const int N = std::max(0, std::min(n[b], cap));
+        for (int i = 0; i < N; i++) {
+            int32_t &pMP = mp[(size_t)b * cap + i];
+            if (pMP >= 0 && pMP < g->n_points) {
+                nObsvMappoints++;
+                if (!outlier[(size_t)b * cap + i]) {
+                    if (found_inc) found_inc[pMP]++;
+                    if (!only_tracking) {
+                        if (g->point_nobs[pMP] > 0) mnMatchesInliers++;
+                        totalObservation += g->point_nobs[pMP];
+                    } else
+                        mnMatchesInliers++;
+                } else if (stereo)
+                    pMP = -1;
+            }
+        }
+        stats[3 * (size_t)b] = nObsvMappoints;
+        stats[3 * (size_t)b + 1] = mnMatchesInliers;
+        stats[3 * (size_t)b + 2] = totalObservation;
+    }
     return AOS2_OK;
 }
 

@@ -1,0 +1,147 @@
+// Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) at the reference's call site, the first line of Tracking::TrackLocalMap (:1034):
+//
+//     // once per map change (a keyframe inserted, points culled), under mpMap->mMutexMapUpdate like Tracking's own reads:
+//     aos2::LocalMapSnapshot snapshot(mpMap, mpMap->GetAllMapPoints());
+//     ...
+//     // per frame, instead of UpdateLocalMap():
+//     aos2::UpdateLocalMap(mCurrentFrame, snapshot, mvpLocalKeyFrames, mvpLocalMapPoints, mpReferenceKF);
+//     mCurrentFrame.mpReferenceKF = mpReferenceKF;                      // :1517
+//     mpMap->SetReferenceMapPoints(mvpLocalMapPoints);                  // :1378 (visualisation; the reference sets the previous list)
+//
+// The snapshot walks the pointer graph ONCE into the arrays of aos2_local_map_graph_t and uploads them (aos2_local_map_set); a frame
+// then costs one C-ABI call (aos2_local_map_update: the votes, the keyframe list, the ordered point list, all on the GPU) and the
+// walk back from rows to pointers.  Keyframe rows are ascending mnId -- the order that stands for the reference's pointer-ordered
+// containers -- and point rows are the caller's table.  A map point outside the table is NULL to the
+// snapshot, a keyframe added after the snapshot does not exist for it: re-take the snapshot when the map changes (adding one
+// keyframe without re-sending the graph is out of scope).  Include AFTER the headers that declare Map, KeyFrame, MapPoint and Frame
+// (the reference's, or tests/cpp/refstub/local_map_stub.h); nothing of the reference's data model changes.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <map>
+#include <set>
+#include <unordered_map>
+#include <vector>
+
+#include "aos2_handles.h"
+
+namespace aos2 {
+
+class LocalMapSnapshot {
+public:
+    LocalMapSnapshot(ORB_SLAM2::Map *pMap, const std::vector<ORB_SLAM2::MapPoint *> &vpTable) : mvpPoints(vpTable)
+    {
+        mvpKeyFrames = pMap->GetAllKeyFrames();
+        std::sort(mvpKeyFrames.begin(), mvpKeyFrames.end(),
+                  [](ORB_SLAM2::KeyFrame *a, ORB_SLAM2::KeyFrame *b) { return a->mnId < b->mnId; });
+        for (size_t k = 0; k < mvpKeyFrames.size(); ++k) mKeyFrameRow[mvpKeyFrames[k]] = (int32_t)k;
+        for (size_t p = 0; p < mvpPoints.size(); ++p)
+            if (mvpPoints[p]) mPointRow[mvpPoints[p]] = (int32_t)p;
+        const size_t np = mvpPoints.size(), nk = mvpKeyFrames.size();
+        std::vector<uint8_t> point_bad(np, 1), kf_bad(nk);   // (an empty slot of the table is a bad point: never listed, never votes)
+        std::vector<int32_t> point_nobs(np, 0), obs_off(1, 0), obs_kf, kf_mp_off(1, 0), kf_mp, kf_best(nk * AOS2_LOCAL_MAP_NEIGHBOURS, -1),
+            kf_child_off(1, 0), kf_child, kf_parent(nk, -1);
+        for (size_t p = 0; p < np; ++p) {
+            if (ORB_SLAM2::MapPoint *pMP = mvpPoints[p]) {
+                point_bad[p] = pMP->isBad() ? 1 : 0;
+                point_nobs[p] = pMP->Observations();
+                std::set<int32_t> rows;   // (a keyframe once, in ascending row)
+                const std::map<ORB_SLAM2::KeyFrame *, size_t> observations = pMP->GetObservations();
+                for (const auto &ob : observations) {
+                    const int32_t r = KeyFrameRow(ob.first);
+                    if (r >= 0) rows.insert(r);
+                }
+                obs_kf.insert(obs_kf.end(), rows.begin(), rows.end());
+            }
+            obs_off.push_back((int32_t)obs_kf.size());
+        }
+        for (size_t k = 0; k < nk; ++k) {
+            ORB_SLAM2::KeyFrame *pKF = mvpKeyFrames[k];
+            kf_bad[k] = pKF->isBad() ? 1 : 0;
+            const std::vector<ORB_SLAM2::MapPoint *> vpMPs = pKF->GetMapPointMatches();
+            for (ORB_SLAM2::MapPoint *pMP : vpMPs) kf_mp.push_back(PointRow(pMP));
+            kf_mp_off.push_back((int32_t)kf_mp.size());
+            const std::vector<ORB_SLAM2::KeyFrame *> vNeighs = pKF->GetBestCovisibilityKeyFrames(AOS2_LOCAL_MAP_NEIGHBOURS);
+            size_t j = 0;
+            for (ORB_SLAM2::KeyFrame *pN : vNeighs) {
+                const int32_t r = KeyFrameRow(pN);
+                if (r >= 0 && j < (size_t)AOS2_LOCAL_MAP_NEIGHBOURS) kf_best[k * AOS2_LOCAL_MAP_NEIGHBOURS + j++] = r;
+            }
+            const std::set<ORB_SLAM2::KeyFrame *> spChilds = pKF->GetChilds();
+            for (ORB_SLAM2::KeyFrame *pC : spChilds) {
+                const int32_t r = KeyFrameRow(pC);
+                if (r >= 0) kf_child.push_back(r);
+            }
+            kf_child_off.push_back((int32_t)kf_child.size());
+            kf_parent[k] = KeyFrameRow(pKF->GetParent());
+        }
+        aos2_local_map_graph_t g;
+        g.n_points = (int32_t)np; g.point_bad = point_bad.data(); g.point_nobs = point_nobs.data();
+        g.obs_off = obs_off.data(); g.obs_kf = obs_kf.data();
+        g.n_keyframes = (int32_t)nk; g.kf_bad = kf_bad.data(); g.kf_mp_off = kf_mp_off.data(); g.kf_mp = kf_mp.data();
+        g.kf_best = kf_best.data(); g.kf_child_off = kf_child_off.data(); g.kf_child = kf_child.data(); g.kf_parent = kf_parent.data();
+        check(aos2_local_map_create(thread_device(), &mHandle), "LocalMapSnapshot");
+        check(aos2_local_map_set(mHandle, &g), "LocalMapSnapshot");
+    }
+    ~LocalMapSnapshot() { aos2_local_map_destroy(mHandle); }
+    LocalMapSnapshot(const LocalMapSnapshot &) = delete;
+    LocalMapSnapshot &operator=(const LocalMapSnapshot &) = delete;
+
+    int32_t KeyFrameRow(ORB_SLAM2::KeyFrame *pKF) const
+    {
+        const auto it = mKeyFrameRow.find(pKF);
+        return it == mKeyFrameRow.end() ? -1 : it->second;
+    }
+    int32_t PointRow(ORB_SLAM2::MapPoint *pMP) const
+    {
+        const auto it = mPointRow.find(pMP);
+        return it == mPointRow.end() ? -1 : it->second;
+    }
+    const std::vector<ORB_SLAM2::KeyFrame *> &KeyFrames() const { return mvpKeyFrames; }
+    const std::vector<ORB_SLAM2::MapPoint *> &Points() const { return mvpPoints; }
+    aos2_local_map_t *Handle() const { return mHandle; }
+
+private:
+    std::vector<ORB_SLAM2::KeyFrame *> mvpKeyFrames;
+    std::vector<ORB_SLAM2::MapPoint *> mvpPoints;
+    std::unordered_map<ORB_SLAM2::KeyFrame *, int32_t> mKeyFrameRow;
+    std::unordered_map<ORB_SLAM2::MapPoint *, int32_t> mPointRow;
+    aos2_local_map_t *mHandle = nullptr;
+};
+
+// UpdateLocalKeyFrames + UpdateLocalPoints of one frame.  F.mvpMapPoints: a feature whose point isBad() loses it (:1428).
+// vpLocalKeyFrames / pReferenceKF: in / out, untouched when no feature votes (:1433); vpLocalMapPoints: out.
+inline void UpdateLocalMap(ORB_SLAM2::Frame &F, const LocalMapSnapshot &S, std::vector<ORB_SLAM2::KeyFrame *> &vpLocalKeyFrames,
+                           std::vector<ORB_SLAM2::MapPoint *> &vpLocalMapPoints, ORB_SLAM2::KeyFrame *&pReferenceKF)
+{
+    ShimClock clk;
+    const int N = F.N;
+    const int cap = std::max(N, 1);
+    std::vector<int32_t> mp(cap, -1);
+    for (int i = 0; i < N; ++i) mp[i] = S.PointRow(F.mvpMapPoints[i]);
+    const std::vector<int32_t> held = mp;
+    const int kf_cap = (int)std::max<size_t>(std::max(S.KeyFrames().size(), vpLocalKeyFrames.size()), 1);
+    const int local_cap = (int)std::max<size_t>(S.Points().size(), 1);
+    std::vector<int32_t> kfs(kf_cap, -1), local(local_cap, -1);
+    for (size_t j = 0; j < vpLocalKeyFrames.size(); ++j) kfs[j] = S.KeyFrameRow(vpLocalKeyFrames[j]);
+    const std::vector<int32_t> kfs_in = kfs;
+    int32_t n = N, n_local = 0, n_kfs = (int32_t)vpLocalKeyFrames.size(), ref = S.KeyFrameRow(pReferenceKF);
+    last_shim_timing().gather_us = clk.lap();
+    check(aos2_local_map_update(S.Handle(), 1, cap, &n, mp.data(), local.data(), local_cap, &n_local, kfs.data(), kf_cap, &n_kfs, &ref),
+          "UpdateLocalMap");
+    last_shim_timing().call_us = clk.lap();
+    for (int i = 0; i < N; ++i)
+        if (held[i] >= 0 && mp[i] < 0) F.mvpMapPoints[i] = static_cast<ORB_SLAM2::MapPoint *>(NULL);
+    // (no votes: the call leaves the rows as they were passed, and the caller's list -- with any keyframe the snapshot does not know --
+    // stands; a list the votes rebuilt has no -1 below its count, so equal rows mean an equal list)
+    if (!(kfs == kfs_in && n_kfs == (int32_t)vpLocalKeyFrames.size())) {
+        vpLocalKeyFrames.clear();
+        for (int j = 0; j < n_kfs; ++j) vpLocalKeyFrames.push_back(S.KeyFrames()[kfs[j]]);
+    }
+    if (ref >= 0) pReferenceKF = S.KeyFrames()[ref];
+    vpLocalMapPoints.clear();
+    for (int j = 0; j < n_local; ++j) vpLocalMapPoints.push_back(S.Points()[local[j]]);
+    last_shim_timing().scatter_us = clk.lap();
+}
+
+}  // namespace aos2

@@ -1153,7 +1153,8 @@ float aos2_optimize_essential_graph_last_device_ms(const aos2_lba_t *s);
  *   ORBextractor::operator() -> Frame::Frame -> SearchByProjection(Current, Last) -> PoseOptimization
  *   -> SearchLocalPoints (isInFrustum + SearchByProjection(F, vpMapPoints)) -> PoseOptimization
  * with the Frame members and the MapPoint table kept in HBM between the calls, so that no
- * keypoint, descriptor, match or pose crosses PCIe inside the chain.  A batch is B independent Frames (replaying
+ * keypoint, descriptor, match or pose crosses PCIe inside the chain (the list SearchLocalPoints searches included:
+ * aos2_frames_update_local_map, "Tracking::UpdateLocalMap" below, forms it on the device).  A batch is B independent Frames (replaying
  * or relocalising many frames, several cameras, or B (LastFrame, CurrentFrame) pairs); every call is enqueued on the
  * batch's stream and returns without waiting; aos2_frames_wait() waits and reports errors.
  * ------------------------------------------------------------------------------------------ */
@@ -1352,6 +1353,98 @@ int aos2_triangulate_matches(aos2_matcher_t *m, const aos2_triang_geom_t *g, int
                              const aos2_triang_obs_t *obs2, float *x3D, uint8_t *status);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) and the tail of Tracking::TrackLocalMap (:1040-1071) for frame batches
+ * (csrc/local_map.hip): the first line of TrackLocalMap decides what SearchLocalPoints searches, from the mvpMapPoints that
+ * SearchByProjection(Cur, Last), PoseOptimization and the outlier discard have just left on the device.  A handle keeps a
+ * snapshot of the parts of Map that UpdateLocalMap reads -- the covisibility graph -- in HBM; the call writes mvpLocalMapPoints
+ * of every frame straight into the d_local that aos2_frames_search_local_points reads, with no host wait in between.
+ * Integer graph work, no floating point: the results are a function of the frame and the graph alone.
+ *
+ * Conventions: the reference walks map<KeyFrame*, int>, map<KeyFrame*, size_t> and set<KeyFrame*>
+ * in pointer order, an accident of the allocator; here ASCENDING KEYFRAME ROW stands for it (the vote map, the observations and
+ * the children).  Everything else is followed literally.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aos2_local_map aos2_local_map_t;
+#define AOS2_LOCAL_MAP_NEIGHBOURS 10   /* GetBestCovisibilityKeyFrames(10) :1470 */
+#define AOS2_LOCAL_MAP_MAX_KFS 80      /* mvpLocalKeyFrames.size() > 80 :1465 */
+/* Host arrays; point rows are the rows of the caller's aos2_map_points_dev_t table, keyframe rows are the caller's (the host
+ * class uses ascending mnId).  Offsets are CSR: off[0] = 0, off[i + 1] - off[i] entries of row i. */
+typedef struct {
+    int32_t n_points;
+    const uint8_t *point_bad;      /* [n_points]      MapPoint::isBad() */
+    const int32_t *point_nobs;     /* [n_points]      MapPoint::Observations() = nObs: a stereo observation counts twice, so this
+                                                      is not the length of the list below */
+    const int32_t *obs_off;        /* [n_points + 1]  MapPoint::GetObservations(): the keyframe rows of each point, each keyframe */
+    const int32_t *obs_kf;         /*                 at most once per point (a map has one entry per key) */
+    int32_t n_keyframes;
+    const uint8_t *kf_bad;         /* [n_keyframes]      KeyFrame::isBad() */
+    const int32_t *kf_mp_off;      /* [n_keyframes + 1]  KeyFrame::GetMapPointMatches(): one entry per feature, in feature order, */
+    const int32_t *kf_mp;          /*                    -1 = NULL */
+    const int32_t *kf_best;        /* [n_keyframes][10]  GetBestCovisibilityKeyFrames(10), in its order, padded with -1 */
+    const int32_t *kf_child_off;   /* [n_keyframes + 1]  KeyFrame::GetChilds() (any order: walked in ascending row) */
+    const int32_t *kf_child;
+    const int32_t *kf_parent;      /* [n_keyframes]      KeyFrame::GetParent(), -1 = none */
+} aos2_local_map_graph_t;
+
+int aos2_local_map_create(int device, aos2_local_map_t **out);
+void aos2_local_map_destroy(aos2_local_map_t *m);
+/* Replaces the handle's snapshot (Map::GetAllKeyFrames / GetAllMapPoints with the members above, as Tracking reads them under
+ * mMutexMapUpdate) and uploads it; returns when the upload is complete.  The graph is checked BEFORE a device is looked for:
+ * AOS2_ERR_ARG, with the handle's previous graph left in place, for a negative count, an array that is NULL with a non-zero
+ * count, offsets that do not start at 0 or that decrease, a row out of range (other than the -1 the members allow) and a
+ * keyframe listed twice among one point's observations.  An empty map (0 keyframes, 0 points) is valid.  A graph that passed the
+ * check is the handle's from then on, also when the upload fails (AOS2_ERR_NO_DEVICE, AOS2_ERR_HIP): the next
+ * aos2_frames_update_local_map uploads it.  The whole graph is sent every time: adding one keyframe without re-sending the
+ * rest (an incremental update) is out of scope. */
+int aos2_local_map_set(aos2_local_map_t *m, const aos2_local_map_graph_t *g);
+/* the handle's snapshot: its sizes and, in *g (may be NULL), its arrays (the handle's own copies, valid until the next set) */
+int aos2_local_map_get(const aos2_local_map_t *m, aos2_local_map_graph_t *g);
+
+/* void Tracking::UpdateLocalMap() = UpdateLocalKeyFrames() (:1411-1519) + UpdateLocalPoints() (:1385-1408) for every frame of
+ * the batch, enqueued on the batch's stream, no host wait.  The frames' mvpMapPoints are rows of the graph's point table.
+ * Device arrays: d_local [batch][local_cap] = mvpLocalMapPoints, d_n_local [batch]; d_local_kfs [batch][kf_cap] =
+ * mvpLocalKeyFrames, d_n_local_kfs [batch], d_ref_kf [batch] = mpReferenceKF -- these three are IN / OUT.
+ *   :1415-1431  a feature whose point isBad() loses it (the batch's mvpMapPoints[i] = -1: a write to the batch); every other
+ *               matched feature votes once for each keyframe of its point's observations
+ *   :1433       no votes: the function returns, and UpdateLocalPoints still runs over the PREVIOUS mvpLocalKeyFrames: the three
+ *               in / out arrays of that frame are left exactly as passed and the points are gathered from its first
+ *               min(n, kf_cap) rows (rows outside the graph are skipped).  A caller without a previous list passes n = 0.
+ *   :1443-1458  the keyframes with votes in ascending row, bad ones skipped; mpReferenceKF = the first of them with strictly
+ *               more votes than every one before it.  All of them bad: the list is empty, d_ref_kf unchanged.
+ *   :1462-1512  for the keyframes of that first pass only, and only while the list holds at most 80: the first of the 10 best
+ *               covisibles that is not bad and not in the list; the first child, in ascending row, that is not bad and not in
+ *               the list; the parent if it is not in the list -- NOT tested for isBad, and adding it ends the whole loop.
+ *   :1385-1408  the local keyframes in list order, their matches in feature order: NULL and bad points skipped, a point kept at
+ *               its first occurrence only.  (A point the frame holds is listed: SearchLocalPoints skips it.)
+ * d_n_local and d_n_local_kfs are the true counts; rows from the count to the capacity are -1 (d_local goes into
+ * aos2_frames_search_local_points with n_local = local_cap as it is).  A count above its capacity: the first `cap` rows are
+ * written, nothing behind the array is touched, and the points still come from the whole keyframe list (kept in the handle's
+ * scratch).  A feature whose row is outside the table (>= n_points) is left alone and does not vote.
+ * Scratch is bounded: 4 (n_points + 2 n_keyframes) bytes per frame, the frames of a batch run in
+ * groups that fit 256 MiB, one after the other on the stream; a graph of which ONE frame does not fit is refused with
+ * AOS2_ERR_ARG before anything is enqueued.  Concurrent calls with one handle share that scratch: one stream at a time. */
+int aos2_frames_update_local_map(aos2_frames_t *f, const aos2_local_map_t *m, int32_t *d_local, int local_cap, int32_t *d_n_local,
+                                 int32_t *d_local_kfs, int kf_cap, int32_t *d_n_local_kfs, int32_t *d_ref_kf);
+/* Host-pointer form (the route of host/LocalMap.h, for a tracker whose Frames live on the host): n [batch] = Frame::N, mp
+ * [batch][cap] = mvpMapPoints as rows (in / out), the five arrays as above, all HOST memory; copied to the device, the same
+ * kernels on the handle's own stream, copied back; returns when the results are complete. */
+int aos2_local_map_update(aos2_local_map_t *m, int batch, int cap, const int32_t *n, int32_t *mp, int32_t *local, int local_cap,
+                          int32_t *n_local, int32_t *local_kfs, int kf_cap, int32_t *n_local_kfs, int32_t *ref_kf);
+/* The tail of bool Tracking::TrackLocalMap() (:1040-1071) for every frame, after the second PoseOptimization:
+ * d_stats [batch][3] = nObsvMappoints, mnMatchesInliers, totalObservation (Observations() = the graph's point_nobs; with
+ * only_tracking = mbOnlyTracking every inlier counts and totalObservation stays 0, :1053-1061); with stereo (mSensor ==
+ * System::STEREO) a feature flagged as outlier loses its point (:1063-1064: a write to the batch; mvbOutlier stays).
+ * d_found_inc [n_points] or NULL: MapPoint::IncreaseFound() as integer atomic adds ON TOP of what the array holds (the caller
+ * zeroes it).  IncreaseVisible and the mnLastFrameSeen bookkeeping of SearchLocalPoints (:1305-1345) stay with the caller. */
+int aos2_frames_track_local_map_stats(aos2_frames_t *f, const aos2_local_map_t *m, int stereo, int only_tracking, int32_t *d_stats,
+                                      int32_t *d_found_inc);
+/* test hooks: the scratch bound in bytes (<= 0: the default, 256 MiB) and the largest n_keyframes whose vote counters live in
+ * LDS (< 0: the default, 8192; 0: always global memory), so that both sides of either switch are reached with small graphs */
+int aos2_local_map_debug_limits(aos2_local_map_t *m, int64_t scratch_bytes, int lds_keyframes);
+/* groups the last aos2_frames_update_local_map call ran its batch in */
+int aos2_local_map_last_groups(const aos2_local_map_t *m);
+
+/* ------------------------------------------------------------------------------------------
  * Replay of a fixed call sequence (csrc/replay.hip).  No single reference function: the per-frame body of Tracking::Track on its
  * usual path -- Frame::Frame (src/Frame.cc:116-172), TrackWithMotionModel (src/Tracking.cc:860-1039: SearchByProjection,
  * PoseOptimization, the outlier discard), TrackLocalMap (:1041-1100: SearchLocalPoints, PoseOptimization) -- is the same ~20
@@ -1442,6 +1535,14 @@ int aos2_debug_visibility_advance_host(aos2_vis_t *h, int ns, const float *state
  * device is looked for; they need none. */
 int aos2_debug_svc_valid_host(aos2_svc_t *h, int ns, const double *states, uint8_t *valid, uint8_t *collision_free, int32_t *count);
 int aos2_debug_svc_motions_host(aos2_svc_t *h, int nm, const double *q1, const double *q2, aos2_svc_motions_out_t *out);
+/* aos2_frames_update_local_map / aos2_frames_track_local_map_stats on the HOST, on host arrays: serial, with std::map / std::set
+ * keyed by keyframe row the way the reference is written with pointers -- the one-core baseline.  n [batch] = Frame::N, mp
+ * [batch][cap] = mvpMapPoints (in / out), outlier [batch][cap]; the other arrays as the device calls take them.  The graph is
+ * checked as aos2_local_map_set checks it; no device is needed. */
+int aos2_debug_local_map_host(const aos2_local_map_graph_t *g, int batch, int cap, const int32_t *n, int32_t *mp, int32_t *local,
+                              int local_cap, int32_t *n_local, int32_t *local_kfs, int kf_cap, int32_t *n_local_kfs, int32_t *ref_kf);
+int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, int cap, const int32_t *n, int32_t *mp,
+                                    const uint8_t *outlier, int stereo, int only_tracking, int32_t *stats, int32_t *found_inc);
 /* the math of csrc/motion_tw.h on arrays of n doubles: sin = tw_sin(x), cos = tw_cos(x), atan2 = tw_atan2(y, x), sqrt = sqrt(x),
  * quot = y / x; on the host (device == -1) or in a kernel of one lane per element.  It tells whether a difference between the two
  * sides comes from the math or from the logic.  Any x and y (the domain check of the states does not apply). */
