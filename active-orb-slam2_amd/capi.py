@@ -188,6 +188,8 @@ def lib():
         L.aos2_debug_initializer_inv33.argtypes = [vp, vp, C.POINTER(C.c_double)]
         L.aos2_initializer_initialize.argtypes = [vp, vp, vp, ci]
         L.aos2_debug_sim3_opt_host.argtypes = [vp, vp, ci]
+        L.aos2_debug_sim3_opt_steps_host.argtypes = [vp, ci]
+        L.aos2_debug_sim3_opt_steps_device.argtypes = [vp, vp, ci]
         L.aos2_optimize_sim3.argtypes = [vp, vp, vp, ci]
         L.aos2_optimize_sim3_last_device_ms.argtypes = [vp]
         L.aos2_optimize_sim3_last_device_ms.restype = cf
@@ -1777,6 +1779,60 @@ def debug_sim3_opt_host(problems):
     return _sim3_opt_results(R, outs)
 
 
+SIM3_OPT_LINEARISE, SIM3_OPT_TRIAL, SIM3_OPT_REJECT = 1, 2, 4
+SIM3_OPT_STEPS_TAIL = 16   # elements the wrappers put behind act / chi / outlier
+
+
+class _Sim3OptSteps(C.Structure):
+    _fields_ = [("problem", _Sim3OptProblem), ("S_lin", C.c_double * 8), ("S_trial", C.c_double * 8)] + \
+               [(k, C.c_void_p) for k in ("act_in", "chi_in", "outlier_in")] + [(k, C.c_int32) for k in ("tail", "remove", "mask", "pad")] + \
+               [(k, C.c_void_p) for k in ("Hb", "pert", "chi_lin", "trial_sum", "chi_trial", "flagged", "chi", "act", "outlier")]
+
+
+def _sim3_opt_steps_args(items, sentinel=0x5A, tail_byte=0xA5):
+    """items: dicts with problem (as _sim3_opt_args takes it), S_lin / S_trial = (q, t, s), act_in [2n], chi_in [2n], outlier_in [n],
+    remove, mask.  Every output buffer is filled with the byte `sentinel`; the SIM3_OPT_STEPS_TAIL elements behind the three planted
+    arrays hold the byte `tail_byte` -> (the C items, what has to stay alive, the output arrays per item)"""
+    I, keep, outs, tail = (_Sim3OptSteps * max(1, len(items)))(), [], [], SIM3_OPT_STEPS_TAIL
+    for i, it in enumerate(items):
+        P, _, arrays, _ = _sim3_opt_args([it["problem"]])
+        n = P[0].n
+        I[i].problem = P[0]
+        for name in ("S_lin", "S_trial"):
+            q, t, s = it[name]
+            setattr(I[i], name, (C.c_double * 8)(*([float(v) for v in q] + [float(v) for v in t] + [float(s)])))
+        planted = {}
+        for name, count, dtype in (("act_in", 2 * n, np.uint8), ("chi_in", 2 * n, np.float64), ("outlier_in", n, np.uint8)):
+            a = np.ascontiguousarray(it[name], dtype)
+            if a.shape != (count,):
+                raise ValueError("item %d: %s [%d]" % (i, name, count))
+            full = np.empty(count + tail, dtype)
+            full.view(np.uint8)[:] = tail_byte
+            full[:count] = a
+            planted[name] = full
+            setattr(I[i], name, full.ctypes.data)
+        I[i].tail, I[i].remove, I[i].mask = tail, int(bool(it["remove"])), int(it["mask"])
+        out = {}
+        for name, count, dtype in (("Hb", 36, np.float64), ("pert", 28 * 8, np.float64), ("chi_lin", 2 * n, np.float64), ("trial_sum", 1, np.float64),
+                                   ("chi_trial", 2 * n, np.float64), ("flagged", 1, np.int32), ("chi", 2 * n + tail, np.float64),
+                                   ("act", 2 * n + tail, np.uint8), ("outlier", n + tail, np.uint8)):
+            a = np.empty(count, dtype)
+            a.view(np.uint8)[:] = sentinel
+            out[name] = a
+            setattr(I[i], name, a.ctypes.data)
+        out["pert"] = out["pert"].reshape(28, 8)
+        keep += [arrays, planted]
+        outs.append(out)
+    return I, keep, outs
+
+
+def debug_sim3_opt_steps_host(items, sentinel=0x5A):
+    """aos2_debug_sim3_opt_steps_host: linearise / trial / reject of the host tap's edges alone -> the output arrays per item"""
+    I, keep, outs = _sim3_opt_steps_args(items, sentinel)
+    _check(lib().aos2_debug_sim3_opt_steps_host(I, len(items)))
+    return outs
+
+
 # ---- Optimizer::OptimizeEssentialGraph (include/aos2.h: aos2_optimize_essential_graph, aos2_debug_essential_graph_host)
 AOS2_EG_OK, AOS2_EG_NO_STEP, AOS2_ERR_EG_MEMORY = 0, 1, -6
 
@@ -2679,6 +2735,13 @@ class LocalBA:
         self.sim3_opt_last = (R, outs)
         _check(self.L.aos2_optimize_sim3(self.h, P, R, len(problems)))
         return _sim3_opt_results(R, outs)
+
+    def debug_sim3_opt_steps(self, items, sentinel=0x5A):
+        """aos2_debug_sim3_opt_steps_device: linearise / trial / reject of the device's edges alone; items and result as
+        debug_sim3_opt_steps_host"""
+        I, keep, outs = _sim3_opt_steps_args(items, sentinel)
+        _check(self.L.aos2_debug_sim3_opt_steps_device(self.h, I, len(items)))
+        return outs
 
     def sim3_opt_last_device_ms(self):
         return float(self.L.aos2_optimize_sim3_last_device_ms(self.h))

@@ -174,16 +174,64 @@ __global__ __launch_bounds__(kSoThreads) void sim3_opt_kernel(const SoProbDev *_
     }
 }
 
+// The three members of SoDevEdges alone, on per-edge state the caller planted (aos2_debug_sim3_opt_steps_device): sim3_opt_kernel's
+// launch shape and LDS objects, no fill of act / chi / outlier, the steps of `mask` in the order linearise, trial, reject.  What a
+// step leaves is copied out by the threads that hold it: the sums by thread 0, pert by threads 0..27, chi by each edge's owner.
+struct SoStepDev {
+    SoProbDev P;   // chi / act / outlier: planted; res and S_in are not used
+    Sim3d S_lin, S_trial;
+    double *Hb, *pert, *chi_lin, *trial_sum, *chi_trial;
+    int32_t *flagged;
+    int32_t mask, remove;
+};
+
+__global__ __launch_bounds__(kSoThreads) void sim3_opt_steps_kernel(const SoStepDev *__restrict__ items)
+{
+    __shared__ double part[kSoRows * kSoSum];
+    __shared__ double fin[kSoSum];
+    __shared__ Sim3d pert[28];
+    __shared__ int cnt;
+    const SoStepDev I = items[blockIdx.x];
+    const int tid = threadIdx.x, n2 = 2 * I.P.A.n;
+    SoDevEdges edges{I.P, part, fin, pert, &cnt};
+    if (I.mask & AOS2_SIM3_OPT_STEP_LINEARISE) {
+        double Hb[kSoSum];
+        edges.linearise(I.S_lin, I.P.fix_scale != 0, I.P.delta, Hb);
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < kSoSum; ++k) I.Hb[k] = Hb[k];
+        }
+        if (tid < 28) {
+            const Sim3d T = pert[tid];
+            double *dst = I.pert + 8 * tid;
+            for (int k = 0; k < 4; ++k) dst[k] = T.q[k];
+            for (int k = 0; k < 3; ++k) dst[4 + k] = T.t[k];
+            dst[7] = T.s;
+        }
+        for (int e = tid; e < n2; e += kSoThreads) I.chi_lin[e] = I.P.chi[e];
+    }
+    if (I.mask & AOS2_SIM3_OPT_STEP_TRIAL) {
+        const double sum = edges.trial(I.S_trial, I.P.delta);
+        if (tid == 0) *I.trial_sum = sum;
+        for (int e = tid; e < n2; e += kSoThreads) I.chi_trial[e] = I.P.chi[e];
+    }
+    if (I.mask & AOS2_SIM3_OPT_STEP_REJECT) {
+        const int flagged = edges.reject(I.P.th2, I.remove != 0);
+        if (tid == 0) *I.flagged = flagged;
+    }
+}
+
 // the same edges on the host, one after the other in index order
 struct SoHostEdges {
     SoArrays A;
     std::vector<double> chi;
     std::vector<uint8_t> act;
     uint8_t *outlier;
+    Sim3d pert[28];   // of the last linearisation
 
     void linearise(const Sim3d &S, bool fix_scale, double delta, double (&Hb)[kSoSum])
     {
-        Sim3d pert[28], T0[2];
+        Sim3d T0[2];
         for (int k = 0; k < 14; ++k) so_perturbed(S, k, fix_scale, pert[2 * k], pert[2 * k + 1]);
         T0[0] = S;
         so_inverse(S, T0[1]);
@@ -222,24 +270,27 @@ struct SoHostEdges {
     }
 };
 
+static int so_check_problem(const aos2_sim3_opt_problem_t &P, const uint8_t *outlier, int i)
+{
+    if (P.n < 0 || !(P.th2 > 0) || (P.n > 0 && (!P.X1c || !P.X2c || !P.obs1 || !P.obs2 || !P.inv_sigma2_1 || !P.inv_sigma2_2 || !outlier))) {
+        set_error("problem %d: bad argument (n >= 0, th2 > 0, the per-correspondence arrays)", i);
+        return AOS2_ERR_ARG;
+    }
+    if (P.n > kSoMaxN) {
+        set_error("problem %d: more than %d correspondences", i, kSoMaxN);
+        return AOS2_ERR_CAPACITY;
+    }
+    return AOS2_OK;
+}
+
 static int so_check(const aos2_sim3_opt_problem_t *p, const aos2_sim3_opt_result_t *r, int n_problems)
 {
     if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!p || !r))) {
         set_error("bad argument (0..64 problems and their results)");
         return AOS2_ERR_ARG;
     }
-    for (int i = 0; i < n_problems; ++i) {
-        const aos2_sim3_opt_problem_t &P = p[i];
-        if (P.n < 0 || !(P.th2 > 0) ||
-            (P.n > 0 && (!P.X1c || !P.X2c || !P.obs1 || !P.obs2 || !P.inv_sigma2_1 || !P.inv_sigma2_2 || !r[i].outlier))) {
-            set_error("problem %d: bad argument (n >= 0, th2 > 0, the per-correspondence arrays)", i);
-            return AOS2_ERR_ARG;
-        }
-        if (P.n > kSoMaxN) {
-            set_error("problem %d: more than %d correspondences", i, kSoMaxN);
-            return AOS2_ERR_CAPACITY;
-        }
-    }
+    for (int i = 0; i < n_problems; ++i)
+        if (int st = so_check_problem(p[i], r[i].outlier, i)) return st;
     return AOS2_OK;
 }
 
@@ -284,6 +335,31 @@ static void so_result_set(const aos2_sim3_opt_problem_t &P, const Sim3d &S, int 
 
 // deltaHuber (:1096): a float
 static double so_delta(float th2) { return (double)sqrtf(th2); }
+
+static int so_steps_check(const aos2_sim3_opt_steps_t *it, int n_items)
+{
+    if (n_items < 0 || n_items > 64 || (n_items > 0 && !it)) {
+        set_error("bad argument (0..64 items)");
+        return AOS2_ERR_ARG;
+    }
+    for (int i = 0; i < n_items; ++i) {
+        const aos2_sim3_opt_steps_t &I = it[i];
+        if (int st = so_check_problem(I.problem, I.outlier, i)) return st;
+        if (I.problem.n < 1 || I.tail < 0 || I.tail > 4096 || (I.mask & ~7) || !I.act_in || !I.chi_in || !I.outlier_in || !I.Hb || !I.pert || !I.chi_lin ||
+            !I.trial_sum || !I.chi_trial || !I.flagged || !I.chi || !I.act) {
+            set_error("item %d: bad argument (n >= 1, 0 <= tail <= 4096, mask of 3 bits, every buffer)", i);
+            return AOS2_ERR_ARG;
+        }
+    }
+    return AOS2_OK;
+}
+
+static void so_sim3_of(const double *v, Sim3d &S)
+{
+    memcpy(S.q, v, sizeof S.q);
+    memcpy(S.t, v + 4, sizeof S.t);
+    S.s = v[7];
+}
 
 }  // namespace aos2
 
@@ -403,6 +479,130 @@ int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_res
         SoOutcome o;
         so_procedure(E, S_in, P.n, (double)P.th2, so_delta(P.th2), P.fix_scale != 0, o);
         so_result_set(P, o.S, o.wrote, o.n_bad, o.n_inliers, o.iterations, o.trials, r[i]);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_sim3_opt_steps_host(const aos2_sim3_opt_steps_t *items, int n_items)
+{
+    if (int st = so_steps_check(items, n_items)) return st;
+    for (int i = 0; i < n_items; ++i) {
+        const aos2_sim3_opt_steps_t &I = items[i];
+        const aos2_sim3_opt_problem_t &P = I.problem;
+        const size_t n2 = 2 * (size_t)P.n, tail = (size_t)I.tail;
+        SoHostEdges E;
+        Sim3d S_lin, S_trial;
+        so_input(P, E.A, S_lin);
+        so_sim3_of(I.S_lin, S_lin);
+        so_sim3_of(I.S_trial, S_trial);
+        E.chi.assign(I.chi_in, I.chi_in + n2 + tail);
+        E.act.assign(I.act_in, I.act_in + n2 + tail);
+        memmove(I.outlier, I.outlier_in, (size_t)P.n + tail);
+        E.outlier = I.outlier;
+        const double delta = so_delta(P.th2);
+        if (I.mask & AOS2_SIM3_OPT_STEP_LINEARISE) {
+            double Hb[kSoSum];
+            E.linearise(S_lin, P.fix_scale != 0, delta, Hb);
+            memcpy(I.Hb, Hb, sizeof Hb);
+            for (int k = 0; k < 28; ++k) {
+                memcpy(I.pert + 8 * k, E.pert[k].q, 4 * sizeof(double));
+                memcpy(I.pert + 8 * k + 4, E.pert[k].t, 3 * sizeof(double));
+                I.pert[8 * k + 7] = E.pert[k].s;
+            }
+            memcpy(I.chi_lin, E.chi.data(), n2 * sizeof(double));
+        }
+        if (I.mask & AOS2_SIM3_OPT_STEP_TRIAL) {
+            *I.trial_sum = E.trial(S_trial, delta);
+            memcpy(I.chi_trial, E.chi.data(), n2 * sizeof(double));
+        }
+        if (I.mask & AOS2_SIM3_OPT_STEP_REJECT) *I.flagged = E.reject((double)P.th2, I.remove != 0);
+        memcpy(I.chi, E.chi.data(), (n2 + tail) * sizeof(double));
+        memcpy(I.act, E.act.data(), n2 + tail);
+    }
+    return AOS2_OK;
+}
+
+int aos2_debug_sim3_opt_steps_device(aos2_lba_t *s, const aos2_sim3_opt_steps_t *items, int n_items)
+{
+    if (!s) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    int st = so_steps_check(items, n_items);
+    if (st || n_items == 0) return st;
+    if ((st = lba_handle_init(s))) return st;
+    // One image of the arena goes up and the whole of it comes back: the outputs start as what the caller's buffers hold, so what no
+    // thread writes returns as it was passed in.
+    HostArena H;
+    struct Off { size_t x1, x2, o1, o2, w1, w2, chi, act, out, Hb, pert, chi_lin, sum, chi_trial, flagged; };
+    std::vector<Off> offs((size_t)n_items);
+    for (int i = 0; i < n_items; ++i) {
+        const aos2_sim3_opt_steps_t &I = items[i];
+        const aos2_sim3_opt_problem_t &P = I.problem;
+        const size_t n = (size_t)P.n, tail = (size_t)I.tail;
+        Off &o = offs[i];
+        o.x1 = H.push(P.X1c, 12 * n);
+        o.x2 = H.push(P.X2c, 12 * n);
+        o.o1 = H.push(P.obs1, 8 * n);
+        o.o2 = H.push(P.obs2, 8 * n);
+        o.w1 = H.push(P.inv_sigma2_1, 4 * n);
+        o.w2 = H.push(P.inv_sigma2_2, 4 * n);
+        o.chi = H.push(I.chi_in, 8 * (2 * n + tail));
+        o.act = H.push(I.act_in, 2 * n + tail);
+        o.out = H.push(I.outlier_in, n + tail);
+        o.Hb = H.push(I.Hb, 8 * kSoSum);
+        o.pert = H.push(I.pert, 8 * 8 * 28);
+        o.chi_lin = H.push(I.chi_lin, 16 * n);
+        o.sum = H.push(I.trial_sum, 8);
+        o.chi_trial = H.push(I.chi_trial, 16 * n);
+        o.flagged = H.push(I.flagged, 4);
+    }
+    const size_t o_items = H.push(nullptr, sizeof(SoStepDev) * (size_t)n_items);
+    H.own.resize(H.size);
+    if ((st = s->arena.alloc(H.size + 256))) return st;
+    uint8_t *base = s->arena.p;
+    SoStepDev *dev = (SoStepDev *)(H.own.data() + o_items);
+    for (int i = 0; i < n_items; ++i) {
+        const aos2_sim3_opt_steps_t &I = items[i];
+        const Off &o = offs[i];
+        SoStepDev D{};
+        so_input(I.problem, D.P.A, D.P.S_in);
+        D.P.A.X1c = (const float *)(base + o.x1); D.P.A.X2c = (const float *)(base + o.x2);
+        D.P.A.obs1 = (const float *)(base + o.o1); D.P.A.obs2 = (const float *)(base + o.o2);
+        D.P.A.w1 = (const float *)(base + o.w1); D.P.A.w2 = (const float *)(base + o.w2);
+        D.P.chi = (double *)(base + o.chi); D.P.act = base + o.act; D.P.outlier = base + o.out;
+        D.P.res = nullptr;
+        D.P.th2 = (double)I.problem.th2;
+        D.P.delta = so_delta(I.problem.th2);
+        D.P.fix_scale = I.problem.fix_scale != 0;
+        so_sim3_of(I.S_lin, D.S_lin);
+        so_sim3_of(I.S_trial, D.S_trial);
+        D.Hb = (double *)(base + o.Hb); D.pert = (double *)(base + o.pert); D.chi_lin = (double *)(base + o.chi_lin);
+        D.trial_sum = (double *)(base + o.sum); D.chi_trial = (double *)(base + o.chi_trial); D.flagged = (int32_t *)(base + o.flagged);
+        D.mask = I.mask;
+        D.remove = I.remove != 0;
+        memcpy(dev + i, &D, sizeof D);
+    }
+    hipStream_t q = s->stream;
+    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.own.data(), H.size, hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(sim3_opt_steps_kernel, dim3(n_items), dim3(kSoThreads), 0, q, (const SoStepDev *)(base + o_items));
+    AOS2_HIP_CHECK(hipMemcpyAsync(H.own.data(), base, H.size, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    for (int i = 0; i < n_items; ++i) {
+        const aos2_sim3_opt_steps_t &I = items[i];
+        const size_t n = (size_t)I.problem.n, tail = (size_t)I.tail;
+        const Off &o = offs[i];
+        const uint8_t *back = H.own.data();
+        memcpy(I.chi, back + o.chi, 8 * (2 * n + tail));
+        memcpy(I.act, back + o.act, 2 * n + tail);
+        memcpy(I.outlier, back + o.out, n + tail);
+        memcpy(I.Hb, back + o.Hb, 8 * kSoSum);
+        memcpy(I.pert, back + o.pert, 8 * 8 * 28);
+        memcpy(I.chi_lin, back + o.chi_lin, 16 * n);
+        memcpy(I.trial_sum, back + o.sum, 8);
+        memcpy(I.chi_trial, back + o.chi_trial, 16 * n);
+        memcpy(I.flagged, back + o.flagged, 4);
     }
     return AOS2_OK;
 }

@@ -1568,6 +1568,36 @@ int aos2_debug_initializer_rng(int n, uint32_t *out);
 int aos2_debug_initializer_inv33(const float *S, float *inv, double *det);
 /* aos2_optimize_sim3 on the HOST: the same header (csrc/sim3_opt.h) run serially, edges summed in index order; needs no device */
 int aos2_debug_sim3_opt_host(const aos2_sim3_opt_problem_t *p, aos2_sim3_opt_result_t *r, int n_problems);
+/* The three steps of csrc/sim3_opt.hip's edge backends alone -- linearise at S_lin, trial at S_trial, reject, in that order, those
+ * that `mask` names -- on per-edge state the caller plants: the device form runs SoDevEdges' members in a kernel of sim3_opt_kernel's
+ * launch shape and LDS objects (one workgroup per item), the host form SoHostEdges'.  The problem's q12 / t12 / s12 are not read
+ * (S_lin and S_trial are given); Huber's delta is formed from th2 as the full call forms it.  act_in / chi_in [2 n + tail] and
+ * outlier_in [n + tail] replace the full call's all-ones / zero fill: the `tail` elements behind each array travel with it through the
+ * backend's memory and come back behind act / chi / outlier, where a write past the end shows.  A step that is not in `mask` leaves
+ * its outputs as the caller passed them.  n_items <= 64, n >= 1; otherwise the argument checks of aos2_optimize_sim3, and a NULL
+ * buffer is AOS2_ERR_ARG: reported before anything runs, nothing is written. */
+#define AOS2_SIM3_OPT_STEP_LINEARISE 1
+#define AOS2_SIM3_OPT_STEP_TRIAL 2
+#define AOS2_SIM3_OPT_STEP_REJECT 4
+typedef struct {
+    aos2_sim3_opt_problem_t problem;
+    double S_lin[8], S_trial[8];        /* q (x, y, z, w), t, s */
+    const uint8_t *act_in;              /* [2 n + tail]: the edge is in the graph */
+    const double *chi_in;               /* [2 n + tail]: the chi2 the edge holds */
+    const uint8_t *outlier_in;          /* [n + tail] */
+    int32_t tail, remove, mask, pad;
+    double *Hb;                         /* linearise: [36] */
+    double *pert;                       /* linearise: [28][8], transform k forward at 2 k, inverse at 2 k + 1 */
+    double *chi_lin;                    /* linearise: [2 n], chi after it */
+    double *trial_sum;                  /* trial: [1] */
+    double *chi_trial;                  /* trial: [2 n], chi after it */
+    int32_t *flagged;                   /* reject: [1] */
+    double *chi;                        /* always: [2 n + tail], chi after the last step */
+    uint8_t *act;                       /* always: [2 n + tail] */
+    uint8_t *outlier;                   /* always: [n + tail] */
+} aos2_sim3_opt_steps_t;
+int aos2_debug_sim3_opt_steps_device(aos2_lba_t *s, const aos2_sim3_opt_steps_t *items, int n_items);
+int aos2_debug_sim3_opt_steps_host(const aos2_sim3_opt_steps_t *items, int n_items);
 /* aos2_optimize_essential_graph on the HOST: the same header (csrc/essential_graph.h) run serially with a skyline LDL^T of the scalar
  * system; n_vertices <= 512 (else AOS2_ERR_CAPACITY); needs no device.  l_blocks is what the device's symbolic phase gives. */
 int aos2_debug_essential_graph_host(const aos2_essential_graph_problem_t *p, aos2_essential_graph_result_t *r, int n_problems);

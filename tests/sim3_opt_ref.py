@@ -195,8 +195,9 @@ class Graph:
             J12[:, :, d], J21[:, :, d] = scalar * (p12 - m12), scalar * (p21 - m21)
         return J12, J21
 
-    def linearise(self, S, fix_scale):
-        """computeActiveErrors + activeRobustChi2 + buildSystem -> H [7][7], b [7], chi"""
+    def edge_terms(self, S, fix_scale):
+        """computeActiveErrors + what constructQuadraticForm adds per edge -> [2n][36]: H (upper triangle row by row), b, rho[0];
+        row 2c = e12 of correspondence c, row 2c + 1 = its e21 (the chi2 of the active correspondences are stored)"""
         e12, e21 = self.residuals(S)
         J12, J21 = self.jacobians(S, fix_scale)
         c12, r12, w12 = self._robust(e12, self.w1)
@@ -209,8 +210,12 @@ class Graph:
             b = np.einsum("nir,ni->nr", J, -(w[:, None] * e) * rho1[:, None])
             return np.concatenate([H, b, rho0[:, None]], axis=1)
 
-        t = np.stack([terms(J12, e12, self.w1, r12, w12), terms(J21, e21, self.w2, r21, w21)], axis=1).reshape(2 * self.n, 36)
-        tot = self._total(t)
+        return np.stack([terms(J12, e12, self.w1, r12, w12), terms(J21, e21, self.w2, r21, w21)], axis=1).reshape(2 * self.n, 36)
+
+    def linearise(self, S, fix_scale):
+        """computeActiveErrors + activeRobustChi2 + buildSystem -> H [7][7], b [7], chi"""
+        iu = np.triu_indices(7)
+        tot = self._total(self.edge_terms(S, fix_scale))
         H = np.zeros((7, 7), self.dtype)
         H[iu] = tot[:28]
         H = H + np.triu(H, 1).T
@@ -222,6 +227,27 @@ class Graph:
         if remove:
             self.active = self.active & ~bad
         return bad, float(margin)
+
+
+def closed_form_jacobians(G, S):
+    """d e12 / d u and d e21 / d u at u = 0 for exp(u) S: exp(u) Y = Y + omega x Y + upsilon + sigma Y + O(u^2), and
+    (exp(u) S)^-1 = S^-1 exp(-u)"""
+    q, t, s = S
+    Rm = rot_of(q / np.linalg.norm(q))
+
+    def dproj(K, p):
+        z = p[:, 2]
+        o = np.zeros_like(z)
+        return -np.stack([np.stack([K[0] / z, o, -K[0] * p[:, 0] / (z * z)], axis=1), np.stack([o, K[1] / z, -K[1] * p[:, 1] / (z * z)], axis=1)], axis=1)
+
+    def dexp(Y):   # [n][3][7]
+        return np.concatenate([np.stack([-skew(y) for y in Y]), np.broadcast_to(np.eye(3), (len(Y), 3, 3)), Y[:, :, None]], axis=2)
+
+    p = s * G.X2 @ Rm.T + t
+    J12 = dproj(G.K1, p) @ dexp(p)
+    qv = (G.X1 - t) @ Rm / s
+    J21 = dproj(G.K2, qv) @ (-(1.0 / s) * Rm.T @ dexp(G.X1))
+    return J12, J21
 
 
 def cholesky_solve(H, b):

@@ -40,25 +40,7 @@ def test_noise_free_problems_give_the_planted_sim3_back(pkg, fix_scale):
             assert dR <= 1e-6 and ds <= 1e-6 and dt <= 1e-5
 
 
-def closed_form_jacobians(G, S):
-    """d e12 / d u and d e21 / d u at u = 0 for exp(u) S: exp(u) Y = Y + omega x Y + upsilon + sigma Y + O(u^2), and
-    (exp(u) S)^-1 = S^-1 exp(-u)"""
-    q, t, s = S
-    Rm = R.rot_of(q / np.linalg.norm(q))
-
-    def dproj(K, p):
-        z = p[:, 2]
-        o = np.zeros_like(z)
-        return -np.stack([np.stack([K[0] / z, o, -K[0] * p[:, 0] / (z * z)], axis=1), np.stack([o, K[1] / z, -K[1] * p[:, 1] / (z * z)], axis=1)], axis=1)
-
-    def dexp(Y):   # [n][3][7]
-        return np.concatenate([np.stack([-R.skew(y) for y in Y]), np.broadcast_to(np.eye(3), (len(Y), 3, 3)), Y[:, :, None]], axis=2)
-
-    p = s * G.X2 @ Rm.T + t
-    J12 = dproj(G.K1, p) @ dexp(p)
-    qv = (G.X1 - t) @ Rm / s
-    J21 = dproj(G.K2, qv) @ (-(1.0 / s) * Rm.T @ dexp(G.X1))
-    return J12, J21
+closed_form_jacobians = R.closed_form_jacobians   # (shared with the step tests)
 
 
 def test_central_difference_jacobian_agrees_with_the_closed_form():
