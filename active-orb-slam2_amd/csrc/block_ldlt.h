@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "lba_math.h"
 #include "wave_ops.h"
 
 namespace aos2 {
@@ -204,6 +205,89 @@ inline bool block_symbolic(int nf, const std::vector<int32_t> &hi, const std::ve
         Y.upd_ptr[(size_t)k + 1] = (int32_t)Y.upd_dst.size();
     }
     return true;
+}
+
+// The slots of a system as a dense (B nf) x (B nf) row-major matrix, both triangles.  A slot below the diagonal goes to its place
+// and, transposed, to the mirrored one.  A diagonal slot is copied as it is stored; with diag_lower it is given by its lower
+// triangle, which is mirrored.
+template <int B>
+inline void block_dense(const BlockSymbolic &Y, const double *slots, bool diag_lower, double *out)
+{
+    const size_t nf = (size_t)Y.nf, n = B * nf;
+    std::fill(out, out + n * n, 0.0);
+    for (size_t sl = 0; sl < nf + Y.l_blocks(); ++sl) {
+        const bool diag = sl < nf;
+        size_t row = sl, col = sl;
+        if (!diag) {
+            const int p = (int)(sl - nf);
+            row = (size_t)Y.rowidx[(size_t)p];
+            col = (size_t)(std::upper_bound(Y.colptr.begin(), Y.colptr.end(), p) - Y.colptr.begin()) - 1;
+        }
+        for (size_t a = 0; a < B; ++a)
+            for (size_t c = 0; c < (diag && diag_lower ? a + 1 : B); ++c) {
+                const double v = slots[sl * B * B + a * B + c];
+                out[(B * row + a) * n + B * col + c] = v;
+                if (!diag || diag_lower) out[(B * col + c) * n + B * row + a] = v;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- the solve tap (host)
+// block_factor_solve<B> alone on a system given by its diagonal blocks and the triplets of blocks below the diagonal (repeated
+// triplets add up), through the real symbolic phase: aos2_debug_essential_graph_solve_device, aos2_debug_global_ba_solve_device.
+// kKernel is the entry's one-workgroup kernel around block_factor_solve<B>.
+template <int B, void (*kKernel)(BlockSystem, double, int32_t *)>
+int block_solve_tap(aos2_lba *s, int max_blocks, int err_memory, size_t max_bytes, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols,
+                    const double *val, const double *diag, const double *b, double lambda, double *x, int32_t *ok, int32_t *l_blocks)
+{
+    constexpr size_t BB = B * B;
+    bool good = s && n_blocks >= 1 && n_blocks <= max_blocks && n_off >= 0 && diag && b && x && ok && l_blocks && (n_off == 0 || (rows && cols && val));
+    for (int i = 0; good && i < n_off; ++i) good = cols[i] >= 0 && rows[i] > cols[i] && rows[i] < n_blocks;
+    if (!good) {
+        set_error("bad argument (1..%d blocks, triplets of the lower triangle, the arrays)", max_blocks);
+        return AOS2_ERR_ARG;
+    }
+    BlockSymbolic Y;
+    if (!block_symbolic(n_blocks, std::vector<int32_t>(rows, rows + n_off), std::vector<int32_t>(cols, cols + n_off), BB, max_bytes, Y)) {
+        set_error("the factor does not fit");
+        return err_memory;
+    }
+    const size_t n_slots = (size_t)n_blocks + Y.l_blocks(), nx = B * (size_t)n_blocks;
+    std::vector<double> Hv(n_slots * BB, 0.0);
+    memcpy(Hv.data(), diag, sizeof(double) * BB * (size_t)n_blocks);
+    for (int i = 0; i < n_off; ++i) {
+        double *dst = Hv.data() + (size_t)Y.slot(rows[i], cols[i]) * BB;
+        for (size_t k = 0; k < BB; ++k) dst[k] += val[(size_t)i * BB + k];
+    }
+    int st = lba_handle_init(s);
+    if (st) return st;
+    HostArena H;
+    BlockSystem S;
+    int32_t *d_ok = nullptr;
+    S.nf = n_blocks;
+    S.n_slots = (int32_t)n_slots;
+    H.in(S.colptr, Y.colptr);
+    H.in(S.rowidx, Y.rowidx);
+    H.in(S.upd_ptr, Y.upd_ptr);
+    H.in(S.upd_dst, Y.upd_dst);
+    H.in(S.H, Hv);
+    H.in(S.b, b, nx);
+    H.in(S.x, (const double *)x, nx);
+    const size_t in_bytes = H.host_size;
+    H.room(d_ok, 1);
+    H.room(S.L, Hv.size());
+    H.room(S.y, nx);
+    if ((st = s->arena.alloc(H.size + 256))) return st;
+    H.bind(s->arena.p);
+    hipStream_t q = s->stream;
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p, H.data(), in_bytes, hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(kKernel, dim3(1), dim3(kBlockLdltThreads), 0, q, S, lambda, d_ok);
+    AOS2_HIP_CHECK(hipMemcpyAsync(x, S.x, sizeof(double) * nx, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(ok, d_ok, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipStreamSynchronize(q));
+    AOS2_HIP_CHECK(hipGetLastError());
+    *l_blocks = (int32_t)Y.l_blocks();
+    return AOS2_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- the host taps' solver

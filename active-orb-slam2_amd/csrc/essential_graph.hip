@@ -39,29 +39,6 @@ struct EgDev {
     float *Tiw, *Xw_out;
 };
 
-// Workgroup sum of N doubles per thread, the result in every thread.  Row sums by DPP (lane 0 of a row of 16 is the one that is kept),
-// then every thread adds the 16 row partials in row order: the order depends on nothing but the thread number.  The second barrier
-// lets `part` be written again.
-template <int N>
-__device__ __forceinline__ void eg_block_sum(double (&v)[N], double *part)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = row_sum_f64(v[i]);
-    if ((tid & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) part[(tid >> 4) * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = part[i];
-        for (int r = 1; r < kEgRows; ++r) s += part[r * N + i];
-        v[i] = s;
-    }
-    __syncthreads();
-}
-
 // the transforms of a linearisation that belong to a vertex: grid over (vertex, 15): the 14 perturbed estimates with their inverses,
 // and the inverse of the estimate
 __global__ __launch_bounds__(kEgThreads) void k_eg_perturb(const EgDev *__restrict__ probs)
@@ -141,7 +118,7 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_begin(const EgDev *__restrict
     if (!P.ctl->running) return;
     double chi[1] = {0};
     for (int e = threadIdx.x; e < P.ne; e += kEgThreads) chi[0] += eg_chi2(P.E + (size_t)e * 7);
-    eg_block_sum(chi, part);
+    block_sum_f64(chi, part);
     if (threadIdx.x == 0) eg_iteration_begin(*P.ctl, chi[0]);
 }
 
@@ -192,7 +169,7 @@ __device__ __forceinline__ void eg_trial(const EgDev &P, double *tap)
         eg_residual(P.C[e], P.est_try[P.v0[e]], inv, er);
         sum[0] += eg_chi2(er);
     }
-    eg_block_sum(sum, part);
+    block_sum_f64(sum, part);
     if (kTap && tid == 0) {
         tap[0] = sum[0];
         tap[1] = sum[1];
@@ -362,111 +339,90 @@ static int eg_host_phase(const aos2_essential_graph_problem_t *p, int n, std::ve
     return AOS2_OK;
 }
 
+static const Sim3d *eg_sim3(const double *p) { return reinterpret_cast<const Sim3d *>(p); }
+
 // The layout of a call: what the host stages (a prefix of the arena: per problem the graph and its lists, the EgDev table, the
 // control words, the estimates), what comes back (neighbours, read together: the control words first, read once per iteration, then
-// per problem Scw, Tiw, Xw) and the scratch.  The call and the taps share it.
+// per problem Scw, Tiw, Xw) and the scratch.  Every array is registered with the field of the table that points at it (regions.h),
+// so the object stays where it is between plan() and bind().  The call and the taps share it.
 struct EgLayout {
-    struct Off { size_t v0, v1, C, S_in, est, est_try, pert, J, E, hidx, free_v, slot_ptr, slot_list, b_ptr, b_list, colptr, rowidx, upd_ptr, upd_dst, Hv, b, L, y, x, Xw_in, ref, Tiw, Xw_out; };
     HostArena H;
-    std::vector<Off> offs;
-    size_t o_probs = 0, o_ctl = 0, in_bytes = 0, res_bytes = 0;
+    std::vector<EgDev> dev;          // the table as bind() completes it
+    const EgDev *dprobs = nullptr;   // ... and where the kernels find it
+    EgControl *ctl = nullptr;        // [n]: the start of what comes back
+    size_t o_probs = 0, in_bytes = 0, res_bytes = 0;
     long long max_v = 1, max_e = 1, max_asm = 1, max_fin = 1;   // the largest grids of the batch: vertices, edges, entries of H and b, finish items
 
     void plan(const aos2_essential_graph_problem_t *p, int n, const std::vector<EgHostGraph> &G)
     {
-        auto push_v = [this](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
-        offs.assign((size_t)n, Off());
+        dev.resize((size_t)n);
+        memset((void *)dev.data(), 0, sizeof(EgDev) * (size_t)n);
         std::vector<EgControl> ctl0((size_t)n);
         for (int i = 0; i < n; ++i) {
             const aos2_essential_graph_problem_t &P = p[i];
             const EgHostGraph &g = G[(size_t)i];
-            Off &o = offs[(size_t)i];
+            EgDev &D = dev[(size_t)i];
             const size_t nv = (size_t)P.n_vertices, ne = (size_t)P.n_edges, np = (size_t)P.n_points;
-            o.v0 = H.push(P.v0, 4 * ne);
-            o.v1 = H.push(P.v1, 4 * ne);
-            o.C = H.push(P.Sji, 64 * ne);
-            o.S_in = H.push(P.Scw, 64 * nv);
-            o.est_try = H.push(P.Scw, 64 * nv);
-            o.hidx = push_v(g.hidx);
-            o.free_v = push_v(g.free_v);
-            o.slot_ptr = push_v(g.slot_ptr);
-            o.slot_list = push_v(g.slot_list);
-            o.b_ptr = push_v(g.b_ptr);
-            o.b_list = push_v(g.b_list);
-            o.colptr = push_v(g.Y.colptr);
-            o.rowidx = push_v(g.Y.rowidx);
-            o.upd_ptr = push_v(g.Y.upd_ptr);
-            o.upd_dst = push_v(g.Y.upd_dst);
-            o.Xw_in = H.push(P.Xw, 12 * np);
-            o.ref = H.push(P.ref, 4 * np);
+            D.nv = P.n_vertices; D.ne = P.n_edges; D.np = P.n_points; D.fixed = P.fixed; D.fix_scale = P.fix_scale != 0;
+            D.sys.nf = g.nf; D.sys.n_slots = g.nf + (int32_t)g.Y.l_blocks();
+            H.in(D.v0, P.v0, ne);
+            H.in(D.v1, P.v1, ne);
+            H.in(D.C, eg_sim3(P.Sji), ne);
+            H.in(D.S_in, eg_sim3(P.Scw), nv);
+            H.in(D.est_try, eg_sim3(P.Scw), nv);
+            H.in(D.hidx, g.hidx);
+            H.in(D.free_v, g.free_v);
+            H.in(D.slot_ptr, g.slot_ptr);
+            H.in(D.slot_list, g.slot_list);
+            H.in(D.b_ptr, g.b_ptr);
+            H.in(D.b_list, g.b_list);
+            H.in(D.sys.colptr, g.Y.colptr);
+            H.in(D.sys.rowidx, g.Y.rowidx);
+            H.in(D.sys.upd_ptr, g.Y.upd_ptr);
+            H.in(D.sys.upd_dst, g.Y.upd_dst);
+            H.in(D.Xw_in, P.Xw, 3 * np);
+            H.in(D.ref, P.ref, np);
             eg_control_init(ctl0[(size_t)i], P.iterations, g.runs);
             max_v = std::max<long long>(max_v, P.n_vertices);
             max_e = std::max<long long>(max_e, P.n_edges);
             max_asm = std::max<long long>(max_asm, ((long long)g.nf + (long long)g.Y.l_blocks()) * 49 + 7LL * g.nf);
             max_fin = std::max<long long>(max_fin, std::max(P.n_vertices, P.n_points));
         }
-        std::vector<EgDev> zero((size_t)n);
-        memset((void *)zero.data(), 0, sizeof(EgDev) * (size_t)n);
-        o_probs = H.push(zero.data(), sizeof(EgDev) * (size_t)n);
+        o_probs = H.in(dprobs, dev.data(), (size_t)n);   // (bind() writes the table there)
         // The estimates and the control words are staged (inputs), the rest is scratch.
-        o_ctl = H.push(ctl0.data(), sizeof(EgControl) * (size_t)n);
-        for (int i = 0; i < n; ++i) offs[(size_t)i].est = H.push(p[i].Scw, 64 * (size_t)p[i].n_vertices);
+        const size_t o_ctl = H.in(ctl, ctl0.data(), (size_t)n);
+        for (int i = 0; i < n; ++i) H.at(dev[(size_t)i].ctl, o_ctl + sizeof(EgControl) * (size_t)i);
+        for (int i = 0; i < n; ++i) H.in(dev[(size_t)i].est, eg_sim3(p[i].Scw), (size_t)p[i].n_vertices);
         in_bytes = H.host_size;
         for (int i = 0; i < n; ++i) {
-            offs[(size_t)i].Tiw = H.push(nullptr, 64 * (size_t)p[i].n_vertices);
-            offs[(size_t)i].Xw_out = H.push(nullptr, 12 * (size_t)p[i].n_points);
+            H.room(dev[(size_t)i].Tiw, 16 * (size_t)p[i].n_vertices);
+            H.room(dev[(size_t)i].Xw_out, 3 * (size_t)p[i].n_points);
         }
         res_bytes = H.size - o_ctl;
         for (int i = 0; i < n; ++i) {
-            const EgHostGraph &g = G[(size_t)i];
-            Off &o = offs[(size_t)i];
-            const size_t nv = (size_t)p[i].n_vertices, ne = (size_t)p[i].n_edges, n_slots = (size_t)g.nf + g.Y.l_blocks(), nx = 7 * (size_t)g.nf;
-            o.pert = H.push(nullptr, sizeof(Sim3d) * kEgPert * nv);
-            o.J = H.push(nullptr, 98 * 8 * ne);
-            o.E = H.push(nullptr, 56 * ne);
-            o.Hv = H.push(nullptr, 392 * n_slots);
-            o.L = H.push(nullptr, 392 * n_slots);
-            o.b = H.push(nullptr, 8 * nx);
-            o.y = H.push(nullptr, 8 * nx);
-            o.x = H.push(nullptr, 8 * nx);
+            EgDev &D = dev[(size_t)i];
+            const size_t nv = (size_t)D.nv, ne = (size_t)D.ne, n_slots = (size_t)D.sys.n_slots, nx = 7 * (size_t)D.sys.nf;
+            H.room(D.pert, kEgPert * nv);
+            H.room(D.J, 98 * ne);
+            H.room(D.E, 7 * ne);
+            H.room(D.sys.H, 49 * n_slots);
+            H.room(D.sys.L, 49 * n_slots);
+            H.room(D.sys.b, nx);
+            H.room(D.sys.y, nx);
+            H.room(D.sys.x, nx);
         }
     }
 
-    // the EgDev table for the arena at `base`, written into the staged prefix -> where the kernels find it
-    const EgDev *bind(const aos2_essential_graph_problem_t *p, int n, const std::vector<EgHostGraph> &G, uint8_t *base)
+    // points the table at the arena at `base` and writes it into the staged prefix -> where the kernels find it
+    const EgDev *bind(uint8_t *base)
     {
-        std::vector<EgDev> dev((size_t)n);
-        memset((void *)dev.data(), 0, sizeof(EgDev) * (size_t)n);
-        for (int i = 0; i < n; ++i) {
-            const aos2_essential_graph_problem_t &P = p[i];
-            const EgHostGraph &g = G[(size_t)i];
-            const Off &o = offs[(size_t)i];
-            EgDev &D = dev[(size_t)i];
-            D.nv = P.n_vertices; D.ne = P.n_edges; D.np = P.n_points; D.fixed = P.fixed; D.fix_scale = P.fix_scale != 0;
-            D.v0 = (const int32_t *)(base + o.v0); D.v1 = (const int32_t *)(base + o.v1);
-            D.C = (const Sim3d *)(base + o.C); D.S_in = (const Sim3d *)(base + o.S_in);
-            D.est = (Sim3d *)(base + o.est); D.est_try = (Sim3d *)(base + o.est_try); D.pert = (Sim3d *)(base + o.pert);
-            D.J = (double *)(base + o.J); D.E = (double *)(base + o.E);
-            D.hidx = (const int32_t *)(base + o.hidx); D.free_v = (const int32_t *)(base + o.free_v);
-            D.slot_ptr = (const int32_t *)(base + o.slot_ptr); D.slot_list = (const int32_t *)(base + o.slot_list);
-            D.b_ptr = (const int32_t *)(base + o.b_ptr); D.b_list = (const int32_t *)(base + o.b_list);
-            D.sys.nf = g.nf; D.sys.n_slots = g.nf + (int32_t)g.Y.l_blocks();
-            D.sys.colptr = (const int32_t *)(base + o.colptr); D.sys.rowidx = (const int32_t *)(base + o.rowidx);
-            D.sys.upd_ptr = (const int32_t *)(base + o.upd_ptr); D.sys.upd_dst = (const int32_t *)(base + o.upd_dst);
-            D.sys.H = (const double *)(base + o.Hv); D.sys.b = (const double *)(base + o.b);
-            D.sys.L = (double *)(base + o.L); D.sys.y = (double *)(base + o.y); D.sys.x = (double *)(base + o.x);
-            D.ctl = (EgControl *)(base + o_ctl) + i;
-            D.Xw_in = (const float *)(base + o.Xw_in); D.ref = (const int32_t *)(base + o.ref);
-            D.Tiw = (float *)(base + o.Tiw); D.Xw_out = (float *)(base + o.Xw_out);
-        }
-        memcpy(H.own.data() + o_probs, dev.data(), sizeof(EgDev) * (size_t)n);
-        return (const EgDev *)(base + o_probs);
+        H.bind(base);
+        memcpy(H.own.data() + o_probs, dev.data(), sizeof(EgDev) * dev.size());
+        return dprobs;
     }
 };
 
 // ---------------------------------------------------------------------------------------------- the host tap
-static const Sim3d *eg_sim3(const double *p) { return reinterpret_cast<const Sim3d *>(p); }
-
 static void eg_host_one(const aos2_essential_graph_problem_t &P, EgHostGraph &G, aos2_essential_graph_result_t &R)
 {
     const int nv = P.n_vertices, ne = P.n_edges;
@@ -549,9 +505,7 @@ static inline int eg_blocks(long long items) { return (int)std::max<long long>(1
 struct EgTap {
     std::vector<EgHostGraph> G;
     EgLayout Lay;
-    uint8_t *base = nullptr;
-    const EgDev *dprobs = nullptr;
-    size_t o_sums = 0;   // the two doubles of k_eg_trial_tap
+    double *sums = nullptr;   // the two doubles of k_eg_trial_tap
 };
 
 static int eg_tap_linearise(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, EgTap &T)
@@ -575,20 +529,19 @@ static int eg_tap_linearise(aos2_lba_t *s, const aos2_essential_graph_problem_t 
         return AOS2_ERR_ARG;
     }
     T.Lay.plan(p, 1, T.G);
-    T.o_sums = T.Lay.H.push(nullptr, 16);
+    T.Lay.H.room(T.sums, 2);
     if ((st = lba_handle_init(s))) return st;
     if ((st = s->arena.alloc(T.Lay.H.size + 256))) return st;
-    T.base = s->arena.p;
-    T.dprobs = T.Lay.bind(p, 1, T.G, T.base);
-    const EgLayout::Off &o = T.Lay.offs[0];
+    const EgDev *dprobs = T.Lay.bind(s->arena.p);
+    const EgDev &D = T.Lay.dev[0];
     hipStream_t q = s->stream;
-    AOS2_HIP_CHECK(hipMemcpyAsync(T.base, T.Lay.H.data(), T.Lay.in_bytes, hipMemcpyHostToDevice, q));
-    AOS2_HIP_CHECK(hipMemsetAsync(T.base + o.x, 0, 56 * (size_t)T.G[0].nf, q));
-    AOS2_HIP_CHECK(hipMemsetAsync(T.base + o.J, 0x5A, 98 * 8 * (size_t)p->n_edges, q));
-    hipLaunchKernelGGL(k_eg_perturb, dim3(eg_blocks(T.Lay.max_v * 15), 1), dim3(kEgThreads), 0, q, T.dprobs);
-    hipLaunchKernelGGL(k_eg_linearise, dim3(eg_blocks(T.Lay.max_e * 16), 1), dim3(kEgThreads), 0, q, T.dprobs);
-    hipLaunchKernelGGL(k_eg_assemble, dim3(eg_blocks(T.Lay.max_asm), 1), dim3(kEgThreads), 0, q, T.dprobs);
-    hipLaunchKernelGGL(k_eg_begin, dim3(1), dim3(kEgThreads), 0, q, T.dprobs);
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p, T.Lay.H.data(), T.Lay.in_bytes, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipMemsetAsync(D.sys.x, 0, bytes_of(D.sys.x, 7 * (size_t)D.sys.nf), q));
+    AOS2_HIP_CHECK(hipMemsetAsync(D.J, 0x5A, bytes_of(D.J, 98 * (size_t)D.ne), q));
+    hipLaunchKernelGGL(k_eg_perturb, dim3(eg_blocks(T.Lay.max_v * 15), 1), dim3(kEgThreads), 0, q, dprobs);
+    hipLaunchKernelGGL(k_eg_linearise, dim3(eg_blocks(T.Lay.max_e * 16), 1), dim3(kEgThreads), 0, q, dprobs);
+    hipLaunchKernelGGL(k_eg_assemble, dim3(eg_blocks(T.Lay.max_asm), 1), dim3(kEgThreads), 0, q, dprobs);
+    hipLaunchKernelGGL(k_eg_begin, dim3(1), dim3(kEgThreads), 0, q, dprobs);
     return AOS2_OK;
 }
 
@@ -622,9 +575,9 @@ int aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_prob
     if ((st = s->arena.alloc(Lay.H.size + 256))) return st;
     if ((st = s->h_stage.alloc(Lay.res_bytes + 64))) return st;
     uint8_t *base = s->arena.p;
-    const EgDev *dprobs = Lay.bind(p, n, G, base);
-    const std::vector<EgLayout::Off> &offs = Lay.offs;
-    const size_t o_ctl = Lay.o_ctl, res_bytes = Lay.res_bytes;
+    const EgDev *dprobs = Lay.bind(base);
+    const std::vector<EgDev> &dev = Lay.dev;
+    const size_t res_bytes = Lay.res_bytes;
     const long long max_v = Lay.max_v, max_e = Lay.max_e, max_asm = Lay.max_asm, max_fin = Lay.max_fin;
     bool any = false;
     for (int i = 0; i < n; ++i) any = any || G[(size_t)i].runs;
@@ -633,70 +586,56 @@ int aos2_optimize_essential_graph(aos2_lba_t *s, const aos2_essential_graph_prob
     AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
     // x starts at zero: a first solve that fails applies the solver's vector as it stands
     for (int i = 0; i < n; ++i)
-        if (G[(size_t)i].nf > 0) AOS2_HIP_CHECK(hipMemsetAsync(base + offs[(size_t)i].x, 0, 56 * (size_t)G[(size_t)i].nf, q));
+        if (G[(size_t)i].nf > 0) AOS2_HIP_CHECK(hipMemsetAsync(dev[(size_t)i].sys.x, 0, bytes_of(dev[(size_t)i].sys.x, 7 * (size_t)G[(size_t)i].nf), q));
     EgControl *hctl = (EgControl *)s->h_stage.p;
     int max_it = 0;
     for (int i = 0; i < n; ++i)
         if (G[(size_t)i].runs) max_it = std::max(max_it, (int)p[i].iterations);
     // profiling (aos2_debug_essential_graph_profile): an event pair around every launch, summed per family after the call
-    std::vector<hipEvent_t> marks;
-    std::vector<int> mark_family;
-    auto family = [&](int f, bool begin) {
-        if (!s->eg_profile) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, q);
-        marks.push_back(e);
-        if (begin) mark_family.push_back(f);
-    };
+    LaunchProfiler prof{s->eg_profile, q};
     for (int it = 0; any && it < max_it; ++it) {
-        family(0, true);
+        prof.mark(0, true);
         hipLaunchKernelGGL(k_eg_perturb, dim3(eg_blocks(max_v * 15), n), dim3(kEgThreads), 0, q, dprobs);
         hipLaunchKernelGGL(k_eg_linearise, dim3(eg_blocks(max_e * 16), n), dim3(kEgThreads), 0, q, dprobs);
-        family(0, false);
-        family(1, true);
+        prof.mark(0, false);
+        prof.mark(1, true);
         hipLaunchKernelGGL(k_eg_assemble, dim3(eg_blocks(max_asm), n), dim3(kEgThreads), 0, q, dprobs);
-        family(1, false);
-        family(3, true);
+        prof.mark(1, false);
+        prof.mark(3, true);
         hipLaunchKernelGGL(k_eg_begin, dim3(n), dim3(kEgThreads), 0, q, dprobs);
-        family(3, false);
+        prof.mark(3, false);
         for (int t = 0; t < 10; ++t) {
-            family(2, true);
+            prof.mark(2, true);
             hipLaunchKernelGGL(k_eg_factor_solve, dim3(n), dim3(kEgThreads), 0, q, dprobs);
-            family(2, false);
-            family(3, true);
+            prof.mark(2, false);
+            prof.mark(3, true);
             hipLaunchKernelGGL(k_eg_trial, dim3(n), dim3(kEgThreads), 0, q, dprobs);
-            family(3, false);
+            prof.mark(3, false);
         }
-        AOS2_HIP_CHECK(hipMemcpyAsync(hctl, base + o_ctl, sizeof(EgControl) * (size_t)n, hipMemcpyDeviceToHost, q));
+        AOS2_HIP_CHECK(hipMemcpyAsync(hctl, Lay.ctl, sizeof(EgControl) * (size_t)n, hipMemcpyDeviceToHost, q));
         AOS2_HIP_CHECK(hipStreamSynchronize(q));
         AOS2_HIP_CHECK(hipGetLastError());
         any = false;
         for (int i = 0; i < n; ++i) any = any || hctl[i].running;
     }
-    family(4, true);
+    prof.mark(4, true);
     hipLaunchKernelGGL(k_eg_finish, dim3(eg_blocks(max_fin), n), dim3(kEgThreads), 0, q, dprobs);
-    family(4, false);
+    prof.mark(4, false);
     AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, base + o_ctl, res_bytes, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, Lay.ctl, res_bytes, hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
     (void)hipEventElapsedTime(&s->last_essential_graph_ms, s->ev[0], s->ev[1]);
-    for (float &f : s->eg_family_ms) f = 0;
-    for (size_t k = 0; k < mark_family.size(); ++k) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, marks[2 * k], marks[2 * k + 1]) == hipSuccess) s->eg_family_ms[mark_family[k]] += ms;
-    }
-    for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+    prof.sum(s->eg_family_ms, 5);
     const uint8_t *res = s->h_stage.p;
     for (int i = 0; i < n; ++i) {
-        const EgLayout::Off &o = offs[(size_t)i];
+        const EgDev &D = dev[(size_t)i];
         EgControl c;
-        memcpy(&c, res + sizeof(EgControl) * (size_t)i, sizeof c);
+        memcpy(&c, span_copy(res, Lay.ctl, D.ctl), sizeof c);
         eg_result_control(c, G[(size_t)i].runs, (int)G[(size_t)i].Y.l_blocks(), r[i]);
-        memcpy(r[i].Scw, res + (o.est - o_ctl), 64 * (size_t)p[i].n_vertices);
-        memcpy(r[i].Tiw, res + (o.Tiw - o_ctl), 64 * (size_t)p[i].n_vertices);
-        if (p[i].n_points > 0) memcpy(r[i].Xw, res + (o.Xw_out - o_ctl), 12 * (size_t)p[i].n_points);
+        memcpy(r[i].Scw, span_copy(res, Lay.ctl, D.est), bytes_of(D.est, (size_t)D.nv));
+        memcpy(r[i].Tiw, span_copy(res, Lay.ctl, D.Tiw), bytes_of(D.Tiw, 16 * (size_t)D.nv));
+        if (D.np > 0) memcpy(r[i].Xw, span_copy(res, Lay.ctl, D.Xw_out), bytes_of(D.Xw_out, 3 * (size_t)D.np));
     }
     return AOS2_OK;
 }
@@ -705,13 +644,7 @@ float aos2_optimize_essential_graph_last_device_ms(const aos2_lba_t *s) { return
 
 int aos2_debug_essential_graph_profile(aos2_lba_t *s, int on, float *family_ms)
 {
-    if (!s) {
-        set_error("bad argument");
-        return AOS2_ERR_ARG;
-    }
-    s->eg_profile = on != 0;
-    if (family_ms) memcpy(family_ms, s->eg_family_ms, sizeof s->eg_family_ms);
-    return AOS2_OK;
+    return LaunchProfiler::entry(s, &aos2_lba::eg_profile, &aos2_lba::eg_family_ms, on, family_ms);
 }
 
 int aos2_debug_essential_graph_host(const aos2_essential_graph_problem_t *p, aos2_essential_graph_result_t *r, int n_problems)
@@ -752,50 +685,8 @@ int aos2_debug_essential_graph_arith_host(int what, const double *in, int n, dou
 int aos2_debug_essential_graph_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols, const double *val,
                                             const double *diag, const double *b, double lambda, double *x, int32_t *ok, int32_t *l_blocks)
 {
-    bool good = s && n_blocks >= 1 && n_blocks < kEgMaxVertices && n_off >= 0 && diag && b && x && ok && l_blocks && (n_off == 0 || (rows && cols && val));
-    for (int i = 0; good && i < n_off; ++i) good = cols[i] >= 0 && rows[i] > cols[i] && rows[i] < n_blocks;
-    if (!good) {
-        set_error("bad argument (1..%d blocks, triplets of the lower triangle, the arrays)", kEgMaxVertices - 1);
-        return AOS2_ERR_ARG;
-    }
-    EgSymbolic Y;
-    if (!eg_symbolic(n_blocks, std::vector<int32_t>(rows, rows + n_off), std::vector<int32_t>(cols, cols + n_off), kEgArenaMax, Y)) {
-        set_error("the factor does not fit");
-        return AOS2_ERR_EG_MEMORY;
-    }
-    const size_t n_slots = (size_t)n_blocks + Y.l_blocks(), nx = 7 * (size_t)n_blocks;
-    std::vector<double> Hv(n_slots * 49, 0.0);
-    memcpy(Hv.data(), diag, 392 * (size_t)n_blocks);
-    for (int i = 0; i < n_off; ++i) {
-        double *dst = Hv.data() + (size_t)Y.slot(rows[i], cols[i]) * 49;
-        for (int k = 0; k < 49; ++k) dst[k] += val[(size_t)i * 49 + k];
-    }
-    int st = lba_handle_init(s);
-    if (st) return st;
-    HostArena H;
-    auto push_v = [&H](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
-    const size_t o_colptr = push_v(Y.colptr), o_rowidx = push_v(Y.rowidx), o_upd_ptr = push_v(Y.upd_ptr), o_upd_dst = push_v(Y.upd_dst);
-    const size_t o_H = H.push(Hv.data(), 8 * Hv.size()), o_b = H.push(b, 8 * nx), o_x = H.push(x, 8 * nx);
-    const size_t in_bytes = H.host_size;
-    const size_t o_ok = H.push(nullptr, 4), o_L = H.push(nullptr, 8 * Hv.size()), o_y = H.push(nullptr, 8 * nx);
-    if ((st = s->arena.alloc(H.size + 256))) return st;
-    uint8_t *base = s->arena.p;
-    EgSystem S;
-    S.nf = n_blocks;
-    S.n_slots = (int32_t)n_slots;
-    S.colptr = (const int32_t *)(base + o_colptr); S.rowidx = (const int32_t *)(base + o_rowidx);
-    S.upd_ptr = (const int32_t *)(base + o_upd_ptr); S.upd_dst = (const int32_t *)(base + o_upd_dst);
-    S.H = (const double *)(base + o_H); S.b = (const double *)(base + o_b);
-    S.L = (double *)(base + o_L); S.y = (double *)(base + o_y); S.x = (double *)(base + o_x);
-    hipStream_t q = s->stream;
-    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
-    hipLaunchKernelGGL(k_eg_factor_solve_tap, dim3(1), dim3(kEgThreads), 0, q, S, lambda, (int32_t *)(base + o_ok));
-    AOS2_HIP_CHECK(hipMemcpyAsync(x, base + o_x, 8 * nx, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(ok, base + o_ok, 4, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipStreamSynchronize(q));
-    AOS2_HIP_CHECK(hipGetLastError());
-    *l_blocks = (int32_t)Y.l_blocks();
-    return AOS2_OK;
+    return block_solve_tap<7, k_eg_factor_solve_tap>(s, kEgMaxVertices - 1, AOS2_ERR_EG_MEMORY, kEgArenaMax, n_blocks, n_off, rows, cols, val, diag, b,
+                                                     lambda, x, ok, l_blocks);
 }
 
 int aos2_debug_essential_graph_linearised_device(aos2_lba_t *s, const aos2_essential_graph_problem_t *p, double *J, double *E, double *H, double *b,
@@ -809,34 +700,19 @@ int aos2_debug_essential_graph_linearised_device(aos2_lba_t *s, const aos2_essen
     int st = eg_tap_linearise(s, p, T);
     if (st) return st;
     const EgHostGraph &G = T.G[0];
-    const EgLayout::Off &o = T.Lay.offs[0];
-    const size_t ne = (size_t)p->n_edges, nf = (size_t)G.nf, n_slots = nf + G.Y.l_blocks(), n7 = 7 * nf;
-    std::vector<double> Hv(n_slots * 49);
+    const EgDev &D = T.Lay.dev[0];
+    const size_t ne = (size_t)D.ne, n7 = 7 * (size_t)D.sys.nf;
+    std::vector<double> Hv((size_t)D.sys.n_slots * 49);
     EgControl c;
     hipStream_t q = s->stream;
-    AOS2_HIP_CHECK(hipMemcpyAsync(J, T.base + o.J, 98 * 8 * ne, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(E, T.base + o.E, 56 * ne, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(Hv.data(), T.base + o.Hv, 8 * Hv.size(), hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(b, T.base + o.b, 8 * n7, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(J, D.J, bytes_of(D.J, 98 * ne), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(E, D.E, bytes_of(D.E, 7 * ne), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(Hv.data(), D.sys.H, bytes_of(D.sys.H, Hv.size()), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(b, D.sys.b, bytes_of(D.sys.b, n7), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, D.ctl, sizeof c, hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
-    // dense: a diagonal slot as it is stored, a slot below the diagonal and its transpose
-    std::fill(H, H + n7 * n7, 0.0);
-    for (size_t sl = 0; sl < n_slots; ++sl) {
-        size_t row = sl, col = sl;
-        if (sl >= nf) {
-            const int pp = (int)(sl - nf);
-            row = (size_t)G.Y.rowidx[(size_t)pp];
-            col = (size_t)(std::upper_bound(G.Y.colptr.begin(), G.Y.colptr.end(), pp) - G.Y.colptr.begin()) - 1;
-        }
-        for (size_t a = 0; a < 7; ++a)
-            for (size_t cc = 0; cc < 7; ++cc) {
-                const double v = Hv[sl * 49 + a * 7 + cc];
-                H[(7 * row + a) * n7 + 7 * col + cc] = v;
-                if (sl >= nf) H[(7 * col + cc) * n7 + 7 * row + a] = v;
-            }
-    }
+    block_dense<7>(G.Y, Hv.data(), false, H);   // a diagonal slot as it is stored
     chi2[0] = c.lm.currentChi;
     chi2[1] = c.chi2_initial;
     *l_blocks = (int32_t)G.Y.l_blocks();
@@ -853,11 +729,11 @@ int aos2_debug_essential_graph_trial_device(aos2_lba_t *s, const aos2_essential_
     EgTap T;
     int st = eg_tap_linearise(s, p, T);
     if (st) return st;
-    const EgLayout::Off &o = T.Lay.offs[0];
-    const size_t nv = (size_t)p->n_vertices, n7 = 7 * (size_t)T.G[0].nf;
+    const EgDev &D = T.Lay.dev[0];
+    const size_t nv = (size_t)D.nv, n7 = 7 * (size_t)D.sys.nf;
     hipStream_t q = s->stream;
     EgControl c;
-    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, D.ctl, sizeof c, hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     c.running = c.open = 1;
     c.lm.lambda = seed_d[0];
@@ -866,13 +742,13 @@ int aos2_debug_essential_graph_trial_device(aos2_lba_t *s, const aos2_essential_
     c.solved = seed_i[0];
     c.iterations = seed_i[1];
     c.qmax = seed_i[2];
-    AOS2_HIP_CHECK(hipMemcpyAsync(T.base + T.Lay.o_ctl, &c, sizeof c, hipMemcpyHostToDevice, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(T.base + o.x, x, 8 * n7, hipMemcpyHostToDevice, q));
-    hipLaunchKernelGGL(k_eg_trial_tap, dim3(1), dim3(kEgThreads), 0, q, T.dprobs, (double *)(T.base + T.o_sums));
-    AOS2_HIP_CHECK(hipMemcpyAsync(est_try, T.base + o.est_try, 64 * nv, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(est, T.base + o.est, 64 * nv, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(sums, T.base + T.o_sums, 16, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(&c, T.base + T.Lay.o_ctl, sizeof c, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(D.ctl, &c, sizeof c, hipMemcpyHostToDevice, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(D.sys.x, x, bytes_of(D.sys.x, n7), hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(k_eg_trial_tap, dim3(1), dim3(kEgThreads), 0, q, T.Lay.dprobs, T.sums);
+    AOS2_HIP_CHECK(hipMemcpyAsync(est_try, D.est_try, bytes_of(D.est_try, nv), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(est, D.est, bytes_of(D.est, nv), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(sums, T.sums, bytes_of(T.sums, 2), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(&c, D.ctl, sizeof c, hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
     const double cd[6] = {c.lm.lambda, c.lm.ni, c.lm.currentChi, c.lm.iniChi, c.rho, c.chi2_initial};

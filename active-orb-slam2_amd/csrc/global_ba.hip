@@ -204,23 +204,19 @@ __host__ __device__ inline void gba_item_finish(const GbaDev &P, int i, int cur)
 }
 
 // ---------------------------------------------------------------------------------------------- the kernels
-// Workgroup sum (kMax: maximum) of one double per thread, the result in every thread.  Row results by DPP, then every thread
-// combines the 16 row partials in row order: the order depends on nothing but the thread number.
-template <bool kMax>
-__device__ __forceinline__ double gba_block_reduce(double v, double *part)
+// Workgroup maximum of one double per thread, the result in every thread: the shape of block_sum_f64 (wave_ops.h), which takes
+// the sums.  Row results by DPP, then every thread combines the 16 row partials in row order.
+__device__ __forceinline__ double gba_block_max(double v, double *part)
 {
     const int tid = threadIdx.x;
-    if (kMax) {
-        v = fmax(v, dpp_f64<0xB1>(v));
-        v = fmax(v, dpp_f64<0x4E>(v));
-        v = fmax(v, dpp_f64<0x141>(v));
-        v = fmax(v, dpp_f64<0x140>(v));
-    } else
-        v = row_sum_f64(v);
+    v = fmax(v, dpp_f64<0xB1>(v));
+    v = fmax(v, dpp_f64<0x4E>(v));
+    v = fmax(v, dpp_f64<0x141>(v));
+    v = fmax(v, dpp_f64<0x140>(v));
     if ((tid & 15) == 0) part[tid >> 4] = v;
     __syncthreads();
     double s = part[0];
-    for (int r = 1; r < kGbaRows; ++r) s = kMax ? fmax(s, part[r]) : s + part[r];
+    for (int r = 1; r < kGbaRows; ++r) s = fmax(s, part[r]);
     __syncthreads();
     return s;
 }
@@ -242,7 +238,7 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_linearise(const GbaDev *__r
     if (!P.ctl->running) return;
     const int e = blockIdx.x * kGbaThreads + threadIdx.x;
     const double chi = e < P.n_edges ? gba_item_linearise(P, e, P.ctl->cur) : 0.0;
-    const double s = gba_block_reduce<false>(chi, part);
+    const double s = block_sum_f64(chi, part);
     if (threadIdx.x == 0) P.part_chi[blockIdx.x] = s;
 }
 
@@ -263,10 +259,10 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_begin(const GbaDev *__restr
     if (!ctl->running) return;
     double chi = 0, mx = 0;
     for (int i = threadIdx.x; i < P.n_eblk; i += kGbaThreads) chi += P.part_chi[i];
-    chi = gba_block_reduce<false>(chi, part);
+    chi = block_sum_f64(chi, part);
     if (ctl->iterations == 0) {
         for (int i = threadIdx.x; i < 6 * P.np + 3 * P.nl; i += kGbaThreads) mx = fmax(gba_diag_abs(P, i), mx);
-        mx = gba_block_reduce<true>(mx, part);
+        mx = gba_block_max(mx, part);
     }
     if (threadIdx.x == 0) gba_iteration_begin(*ctl, chi, mx, gba_flag(P));
 }
@@ -311,7 +307,7 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_trial_edges(const GbaDev *_
     if (!P.ctl->running || !P.ctl->open) return;
     const int e = blockIdx.x * kGbaThreads + threadIdx.x;
     const double chi = e < P.n_edges ? gba_item_trial_edge(P, e, P.ctl->cur) : 0.0;
-    const double s = gba_block_reduce<false>(chi, part);
+    const double s = block_sum_f64(chi, part);
     if (threadIdx.x == 0) P.part_chi[blockIdx.x] = s;
 }
 
@@ -326,8 +322,8 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_decide(const GbaDev *__rest
     double chi = 0, scale = 0;
     for (int i = threadIdx.x; i < P.n_eblk; i += kGbaThreads) chi += P.part_chi[i];
     for (int i = threadIdx.x; i < 6 * P.np + 3 * P.nl; i += kGbaThreads) scale += gba_scale_term(P, i, lambda);
-    chi = gba_block_reduce<false>(chi, part);
-    scale = gba_block_reduce<false>(scale, part);
+    chi = block_sum_f64(chi, part);
+    scale = block_sum_f64(scale, part);
     if (threadIdx.x == 0) gba_trial_decide(*ctl, chi, scale, gba_flag(P));
 }
 
@@ -470,84 +466,76 @@ static bool gba_symbolic(const aos2_lba_problem_t &P, size_t max_bytes, GbaHost 
     return true;
 }
 
+static inline int gba_blocks(long long items) { return (int)std::max<long long>(1, (items + kGbaThreads - 1) / kGbaThreads); }
+
 // The layout of a call: what the host stages (a prefix), the control words and the results (neighbours, read back together), the
-// scratch.  `base` is device memory for the kernels and host memory for the tap.
+// scratch, and the grids of the launches.  Every array is registered with the field of D that points at it (regions.h), so the
+// object stays where it is between plan() and bind().  `base` is device memory for the kernels and host memory for the tap.
 struct GbaLayout {
     HostArena H;
-    size_t o_dev = 0, o_ctl = 0, o_Tcw = 0, o_xyz = 0, in_bytes = 0, res_bytes = 0;
-    size_t e_pose, e_point, e_obs, e_w, e_stereo, in_Tcw, in_xyz, hpose, hpoint, pose_hidx, point_hidx, pe_ptr, pe_list, le_ptr, le_list, pl_ptr,
-        pl_list, term_ptr, term_a, term_b, co_ptr, co_list, colptr, rowidx, upd_ptr, upd_dst;
-    size_t pose[2], point[2], lin, Hpp, bp, Hll, bl, Dinv, db, xl, part_chi, Hs, bs, L, y, x;
-    int n_eblk = 1;
+    GbaDev D;                    // as bind() completes it
+    const GbaDev *dP = nullptr;  // ... and where the kernels find it
+    size_t o_dev = 0, o_ctl = 0, in_bytes = 0, res_bytes = 0;
+    int g_prep = 1, g_sums = 1, g_land = 1, g_asm = 1, g_upd = 1, g_fin = 1, n_eblk = 1;   // workgroups of the launches
 
     void plan(const aos2_lba_problem_t &P, const aos2_gba_options_t &O, const GbaHost &G, int stop_at_poll)
     {
-        auto push_v = [this](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
         const size_t ne = (size_t)P.n_edges, npo = (size_t)P.n_poses, npt = (size_t)P.n_points, np = (size_t)G.np, nl = (size_t)G.nl;
         const size_t n_slots = np + G.Y.l_blocks();
-        n_eblk = (int)std::max<size_t>(1, (ne + kGbaThreads - 1) / kGbaThreads);
-        e_pose = H.push(P.edge_pose, 4 * ne);
-        e_point = H.push(P.edge_point, 4 * ne);
-        e_obs = H.push(P.edge_obs, 12 * ne);
-        e_w = H.push(P.edge_inv_sigma2, 4 * ne);
-        e_stereo = H.push(P.edge_stereo, ne);
-        in_Tcw = H.push(P.pose_Tcw, 64 * npo);
-        in_xyz = H.push(P.point_xyz, 12 * npt);
-        hpose = push_v(G.hpose); hpoint = push_v(G.hpoint); pose_hidx = push_v(G.pose_hidx); point_hidx = push_v(G.point_hidx);
-        pe_ptr = push_v(G.pe_ptr); pe_list = push_v(G.pe_list); le_ptr = push_v(G.le_ptr); le_list = push_v(G.le_list);
-        pl_ptr = push_v(G.pl_ptr); pl_list = push_v(G.pl_list);
-        term_ptr = push_v(G.term_ptr); term_a = push_v(G.term_a); term_b = push_v(G.term_b);
-        co_ptr = push_v(G.co_ptr); co_list = push_v(G.co_list);
-        colptr = push_v(G.Y.colptr); rowidx = push_v(G.Y.rowidx); upd_ptr = push_v(G.Y.upd_ptr); upd_dst = push_v(G.Y.upd_dst);
-        GbaDev zero;
-        memset((void *)&zero, 0, sizeof zero);
-        o_dev = H.push(&zero, sizeof zero);
-        GbaControl c;
-        gba_control_init(c, O.iterations, G.runs, stop_at_poll);
-        o_ctl = H.push(&c, sizeof c);
-        in_bytes = H.host_size;
-        o_Tcw = H.push(nullptr, 64 * npo);
-        o_xyz = H.push(nullptr, 12 * npt);
-        res_bytes = H.size - o_ctl;
-        for (int k = 0; k < 2; ++k) {
-            pose[k] = H.push(nullptr, 56 * npo);
-            point[k] = H.push(nullptr, 24 * npt);
-        }
-        lin = H.push(nullptr, 8 * kGbaLin * ne);
-        Hpp = H.push(nullptr, 288 * np); bp = H.push(nullptr, 48 * np);
-        Hll = H.push(nullptr, 72 * nl); bl = H.push(nullptr, 24 * nl);
-        Dinv = H.push(nullptr, 72 * nl); db = H.push(nullptr, 24 * nl); xl = H.push(nullptr, 24 * nl);
-        part_chi = H.push(nullptr, 8 * (size_t)n_eblk);
-        Hs = H.push(nullptr, 288 * n_slots); L = H.push(nullptr, 288 * n_slots);
-        bs = H.push(nullptr, 48 * np); y = H.push(nullptr, 48 * np); x = H.push(nullptr, 48 * np);
-    }
-
-    void bind(const aos2_lba_problem_t &P, const aos2_gba_options_t &O, const GbaHost &G, uint8_t *base, const int32_t *abort_word, GbaDev &D) const
-    {
-        auto I = [base](size_t o) { return (const int32_t *)(base + o); };
-        auto F = [base](size_t o) { return (double *)(base + o); };
+        n_eblk = gba_blocks((long long)ne);
+        g_prep = gba_blocks(std::max<long long>(std::max(P.n_poses, P.n_points), std::max(6LL * G.np, 3LL * G.nl)));
+        g_sums = gba_blocks(42LL * G.np + 12LL * G.nl);
+        g_land = gba_blocks(G.nl);
+        g_asm = gba_blocks(36LL * (long long)n_slots + 6LL * G.np);
+        g_upd = gba_blocks(std::max(G.np, G.nl));
+        g_fin = gba_blocks(std::max(P.n_poses, P.n_points));
+        memset((void *)&D, 0, sizeof D);
         D.n_poses = P.n_poses; D.n_points = P.n_points; D.n_edges = P.n_edges; D.np = G.np; D.nl = G.nl; D.robust = O.robust != 0;
-        D.n_eblk = n_eblk; D.pad = 0;
+        D.n_eblk = n_eblk;
         // KeyFrame::fx .. mbf are float members copied into the edges' double fields (:113-116, :142-146)
         D.cam.fx = (double)P.fx; D.cam.fy = (double)P.fy; D.cam.cx = (double)P.cx; D.cam.cy = (double)P.cy; D.cam.bf = (double)P.bf; D.cam.bf_f = P.bf;
         D.delta_mono = (double)O.huber_mono; D.delta_stereo = (double)O.huber_stereo;
-        D.e_pose = I(e_pose); D.e_point = I(e_point); D.e_obs = (const float *)(base + e_obs); D.e_w = (const float *)(base + e_w);
-        D.e_stereo = base + e_stereo; D.in_Tcw = (const float *)(base + in_Tcw); D.in_xyz = (const float *)(base + in_xyz);
+        D.sys.nf = G.np; D.sys.n_slots = (int32_t)n_slots;
+        H.in(D.e_pose, P.edge_pose, ne);
+        H.in(D.e_point, P.edge_point, ne);
+        H.in(D.e_obs, P.edge_obs, 3 * ne);
+        H.in(D.e_w, P.edge_inv_sigma2, ne);
+        H.in(D.e_stereo, P.edge_stereo, ne);
+        H.in(D.in_Tcw, P.pose_Tcw, 16 * npo);
+        H.in(D.in_xyz, P.point_xyz, 3 * npt);
+        H.in(D.hpose, G.hpose); H.in(D.hpoint, G.hpoint); H.in(D.pose_hidx, G.pose_hidx); H.in(D.point_hidx, G.point_hidx);
+        H.in(D.pe_ptr, G.pe_ptr); H.in(D.pe_list, G.pe_list); H.in(D.le_ptr, G.le_ptr); H.in(D.le_list, G.le_list);
+        H.in(D.pl_ptr, G.pl_ptr); H.in(D.pl_list, G.pl_list);
+        H.in(D.term_ptr, G.term_ptr); H.in(D.term_a, G.term_a); H.in(D.term_b, G.term_b);
+        H.in(D.co_ptr, G.co_ptr); H.in(D.co_list, G.co_list);
+        H.in(D.sys.colptr, G.Y.colptr); H.in(D.sys.rowidx, G.Y.rowidx); H.in(D.sys.upd_ptr, G.Y.upd_ptr); H.in(D.sys.upd_dst, G.Y.upd_dst);
+        o_dev = H.in(dP, &D, 1);   // (bind() writes D there)
+        GbaControl c;
+        gba_control_init(c, O.iterations, G.runs, stop_at_poll);
+        o_ctl = H.in(D.ctl, &c, 1);
+        in_bytes = H.host_size;
+        H.room(D.out_Tcw, 16 * npo);
+        H.room(D.out_xyz, 3 * npt);
+        res_bytes = H.size - o_ctl;
         for (int k = 0; k < 2; ++k) {
-            D.pose[k] = F(pose[k]);
-            D.point[k] = F(point[k]);
+            H.room(D.pose[k], 7 * npo);
+            H.room(D.point[k], 3 * npt);
         }
-        D.lin = F(lin);
-        D.hpose = I(hpose); D.hpoint = I(hpoint); D.pose_hidx = I(pose_hidx); D.point_hidx = I(point_hidx);
-        D.pe_ptr = I(pe_ptr); D.pe_list = I(pe_list); D.le_ptr = I(le_ptr); D.le_list = I(le_list); D.pl_ptr = I(pl_ptr); D.pl_list = I(pl_list);
-        D.term_ptr = I(term_ptr); D.term_a = I(term_a); D.term_b = I(term_b); D.co_ptr = I(co_ptr); D.co_list = I(co_list);
-        D.Hpp = F(Hpp); D.bp = F(bp); D.Hll = F(Hll); D.bl = F(bl); D.Dinv = F(Dinv); D.db = F(db); D.xl = F(xl); D.part_chi = F(part_chi);
-        D.sys.nf = G.np; D.sys.n_slots = G.np + (int32_t)G.Y.l_blocks();
-        D.sys.colptr = I(colptr); D.sys.rowidx = I(rowidx); D.sys.upd_ptr = I(upd_ptr); D.sys.upd_dst = I(upd_dst);
-        D.sys.H = F(Hs); D.sys.b = F(bs); D.sys.L = F(L); D.sys.y = F(y); D.sys.x = F(x);
-        D.ctl = (GbaControl *)(base + o_ctl);
+        H.room(D.lin, kGbaLin * ne);
+        H.room(D.Hpp, 36 * np); H.room(D.bp, 6 * np);
+        H.room(D.Hll, 9 * nl); H.room(D.bl, 3 * nl);
+        H.room(D.Dinv, 9 * nl); H.room(D.db, 3 * nl); H.room(D.xl, 3 * nl);
+        H.room(D.part_chi, (size_t)n_eblk);
+        H.room(D.sys.H, 36 * n_slots); H.room(D.sys.L, 36 * n_slots);
+        H.room(D.sys.b, 6 * np); H.room(D.sys.y, 6 * np); H.room(D.sys.x, 6 * np);
+    }
+
+    // points D at the arena at `base` and writes it into the staged prefix
+    void bind(uint8_t *base, const int32_t *abort_word)
+    {
+        H.bind(base);
         D.abort_word = abort_word;
-        D.out_Tcw = (float *)(base + o_Tcw); D.out_xyz = (float *)(base + o_xyz);
+        memcpy(H.own.data() + o_dev, &D, sizeof D);
     }
 };
 
@@ -572,8 +560,9 @@ static void gba_result(const GbaControl &c, const GbaHost &G, const aos2_lba_pro
     R.l_blocks = (int32_t)G.Y.l_blocks();
     R.ms_device = ms;
     R.status = AOS2_OK;
-    if (P.n_poses > 0) memcpy(R.pose_Tcw, res + (Lay.o_Tcw - Lay.o_ctl), 64 * (size_t)P.n_poses);
-    if (P.n_points > 0) memcpy(R.point_xyz, res + (Lay.o_xyz - Lay.o_ctl), 12 * (size_t)P.n_points);
+    const GbaDev &D = Lay.D;
+    if (P.n_poses > 0) memcpy(R.pose_Tcw, span_copy(res, D.ctl, D.out_Tcw), bytes_of(D.out_Tcw, 16 * (size_t)P.n_poses));
+    if (P.n_points > 0) memcpy(R.point_xyz, span_copy(res, D.ctl, D.out_xyz), bytes_of(D.out_xyz, 3 * (size_t)P.n_points));
     for (int i = 0; i < P.n_points; ++i) R.point_included[i] = G.point_hidx[(size_t)i] >= 0;
 }
 
@@ -656,8 +645,6 @@ static void gba_host_run(const aos2_lba_problem_t &P, const GbaHost &G, const Gb
     for (int i = 0; i < std::max(P.n_poses, P.n_points); ++i) gba_item_finish(D, i, ctl.cur);
 }
 
-static inline int gba_blocks(long long items) { return (int)std::max<long long>(1, (items + kGbaThreads - 1) / kGbaThreads); }
-
 }  // namespace aos2
 
 using namespace aos2;
@@ -688,80 +675,60 @@ int aos2_global_bundle_adjustment(aos2_lba_t *s, const aos2_lba_problem_t *p, co
     int32_t *d_abort = nullptr;
     AOS2_HIP_CHECK(hipHostGetDevicePointer((void **)&d_abort, s->h_abort.p, 0));
     __atomic_store_n(&s->h_abort.p[0], gba_stop_requested(*p) ? 1 : 0, __ATOMIC_RELAXED);
-    uint8_t *base = s->arena.p;
-    GbaDev D;
-    memset((void *)&D, 0, sizeof D);
-    Lay.bind(*p, *o, G, base, d_abort, D);
-    memcpy(Lay.H.own.data() + Lay.o_dev, &D, sizeof D);
+    Lay.bind(s->arena.p, d_abort);
     hipStream_t q = s->stream;
-    const GbaDev *dP = (const GbaDev *)(base + Lay.o_dev);
-    AOS2_HIP_CHECK(hipMemcpyAsync(base, Lay.H.data(), Lay.in_bytes, hipMemcpyHostToDevice, q));
+    const GbaDev *dP = Lay.dP;
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p, Lay.H.data(), Lay.in_bytes, hipMemcpyHostToDevice, q));
     AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
     // profiling (aos2_debug_global_ba_profile): an event pair around every family of launches, summed after the call
-    std::vector<hipEvent_t> marks;
-    std::vector<int> mark_family;
-    auto family = [&](int f, bool begin) {
-        if (!s->gba_profile) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, q);
-        marks.push_back(e);
-        if (begin) mark_family.push_back(f);
-    };
-    const long long n_prep = std::max<long long>(std::max(p->n_poses, p->n_points), std::max(6LL * G.np, 3LL * G.nl));
-    const long long n_asm = 36LL * D.sys.n_slots + 6LL * G.np, n_sums = 42LL * G.np + 12LL * G.nl;
+    LaunchProfiler prof{s->gba_profile, q};
     const dim3 T(kGbaThreads);
-    family(5, true);
-    hipLaunchKernelGGL(k_gba_prepare, dim3(gba_blocks(n_prep)), T, 0, q, dP);
-    family(5, false);
+    prof.mark(5, true);
+    hipLaunchKernelGGL(k_gba_prepare, dim3(Lay.g_prep), T, 0, q, dP);
+    prof.mark(5, false);
     GbaControl *hctl = (GbaControl *)s->h_stage.p;
     bool any = G.runs;
     for (int it = 0; any && it < o->iterations; ++it) {
-        family(0, true);
+        prof.mark(0, true);
         hipLaunchKernelGGL(k_gba_linearise, dim3(Lay.n_eblk), T, 0, q, dP);
-        hipLaunchKernelGGL(k_gba_sums, dim3(gba_blocks(n_sums)), T, 0, q, dP);
-        family(0, false);
-        family(4, true);
+        hipLaunchKernelGGL(k_gba_sums, dim3(Lay.g_sums), T, 0, q, dP);
+        prof.mark(0, false);
+        prof.mark(4, true);
         hipLaunchKernelGGL(k_gba_begin, dim3(1), T, 0, q, dP);
-        family(4, false);
+        prof.mark(4, false);
         for (int t = 0; t < 10; ++t) {
-            family(1, true);
-            hipLaunchKernelGGL(k_gba_landmarks, dim3(gba_blocks(G.nl)), T, 0, q, dP);
-            family(1, false);
-            family(2, true);
-            hipLaunchKernelGGL(k_gba_assemble, dim3(gba_blocks(n_asm)), T, 0, q, dP);
-            family(2, false);
-            family(3, true);
+            prof.mark(1, true);
+            hipLaunchKernelGGL(k_gba_landmarks, dim3(Lay.g_land), T, 0, q, dP);
+            prof.mark(1, false);
+            prof.mark(2, true);
+            hipLaunchKernelGGL(k_gba_assemble, dim3(Lay.g_asm), T, 0, q, dP);
+            prof.mark(2, false);
+            prof.mark(3, true);
             hipLaunchKernelGGL(k_gba_factor_solve, dim3(1), T, 0, q, dP);
-            family(3, false);
-            family(1, true);
-            hipLaunchKernelGGL(k_gba_update, dim3(gba_blocks(std::max(G.np, G.nl))), T, 0, q, dP);
-            family(1, false);
-            family(4, true);
+            prof.mark(3, false);
+            prof.mark(1, true);
+            hipLaunchKernelGGL(k_gba_update, dim3(Lay.g_upd), T, 0, q, dP);
+            prof.mark(1, false);
+            prof.mark(4, true);
             hipLaunchKernelGGL(k_gba_trial_edges, dim3(Lay.n_eblk), T, 0, q, dP);
             hipLaunchKernelGGL(k_gba_decide, dim3(1), T, 0, q, dP);
-            family(4, false);
+            prof.mark(4, false);
         }
-        AOS2_HIP_CHECK(hipMemcpyAsync(hctl, base + Lay.o_ctl, sizeof(GbaControl), hipMemcpyDeviceToHost, q));
+        AOS2_HIP_CHECK(hipMemcpyAsync(hctl, Lay.D.ctl, sizeof(GbaControl), hipMemcpyDeviceToHost, q));
         AOS2_HIP_CHECK(hipStreamSynchronize(q));
         AOS2_HIP_CHECK(hipGetLastError());
         any = hctl->running != 0;
         if (gba_stop_requested(*p)) __atomic_store_n(&s->h_abort.p[0], 1, __ATOMIC_RELAXED);
     }
-    family(5, true);
-    hipLaunchKernelGGL(k_gba_finish, dim3(gba_blocks(std::max(p->n_poses, p->n_points))), T, 0, q, dP);
-    family(5, false);
+    prof.mark(5, true);
+    hipLaunchKernelGGL(k_gba_finish, dim3(Lay.g_fin), T, 0, q, dP);
+    prof.mark(5, false);
     AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, base + Lay.o_ctl, Lay.res_bytes, hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, Lay.D.ctl, Lay.res_bytes, hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
     (void)hipEventElapsedTime(&s->last_gba_ms, s->ev[0], s->ev[1]);
-    for (float &f : s->gba_family_ms) f = 0;
-    for (size_t k = 0; k < mark_family.size(); ++k) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, marks[2 * k], marks[2 * k + 1]) == hipSuccess) s->gba_family_ms[mark_family[k]] += ms;
-    }
-    for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+    prof.sum(s->gba_family_ms, kGbaFamilies);
     GbaControl c;
     memcpy(&c, s->h_stage.p, sizeof c);
     gba_result(c, G, *p, s->h_stage.p, Lay, s->last_gba_ms, *r);
@@ -770,14 +737,8 @@ int aos2_global_bundle_adjustment(aos2_lba_t *s, const aos2_lba_problem_t *p, co
 
 int aos2_debug_global_ba_profile(aos2_lba_t *s, int on, float *family_ms)
 {
-    if (!s) {
-        set_error("bad argument");
-        return AOS2_ERR_ARG;
-    }
-    static_assert(sizeof s->gba_family_ms == sizeof(float) * kGbaFamilies, "the families of include/aos2.h");
-    s->gba_profile = on != 0;
-    if (family_ms) memcpy(family_ms, s->gba_family_ms, sizeof s->gba_family_ms);
-    return AOS2_OK;
+    static_assert(sizeof(aos2_lba::gba_family_ms) == sizeof(float) * kGbaFamilies, "the families of include/aos2.h");
+    return LaunchProfiler::entry(s, &aos2_lba::gba_profile, &aos2_lba::gba_family_ms, on, family_ms);
 }
 
 int aos2_debug_global_ba_host(const aos2_lba_problem_t *p, const aos2_gba_options_t *o, aos2_gba_result_t *r, int stop_at_poll)
@@ -794,11 +755,9 @@ int aos2_debug_global_ba_host(const aos2_lba_problem_t *p, const aos2_gba_option
     Lay.plan(*p, *o, G, stop_at_poll);
     std::vector<uint8_t> mem(Lay.H.size + 256, 0);
     memcpy(mem.data(), Lay.H.data(), Lay.in_bytes);
-    GbaDev D;
-    memset((void *)&D, 0, sizeof D);
-    Lay.bind(*p, *o, G, mem.data(), nullptr, D);
-    gba_host_run(*p, G, D);
-    gba_result(*D.ctl, G, *p, mem.data() + Lay.o_ctl, Lay, 0.f, *r);
+    Lay.bind(mem.data(), nullptr);
+    gba_host_run(*p, G, Lay.D);
+    gba_result(*Lay.D.ctl, G, *p, (const uint8_t *)Lay.D.ctl, Lay, 0.f, *r);
     return AOS2_OK;
 }
 
@@ -827,11 +786,7 @@ int aos2_debug_global_ba_reduced_device(aos2_lba_t *s, const aos2_lba_problem_t 
     Lay.plan(*p, *o, G, 0);
     if ((st = lba_handle_init(s))) return st;
     if ((st = s->arena.alloc(Lay.H.size + 256))) return st;
-    uint8_t *base = s->arena.p;
-    GbaDev D;
-    memset((void *)&D, 0, sizeof D);
-    Lay.bind(*p, *o, G, base, nullptr, D);
-    memcpy(Lay.H.own.data() + Lay.o_dev, &D, sizeof D);
+    Lay.bind(s->arena.p, nullptr);
     // the control words of an open first trial at the given lambda
     GbaControl c;
     gba_control_init(c, 1, true, 0);
@@ -839,37 +794,21 @@ int aos2_debug_global_ba_reduced_device(aos2_lba_t *s, const aos2_lba_problem_t 
     c.lm.lambda = lambda;
     memcpy(Lay.H.own.data() + Lay.o_ctl, &c, sizeof c);
     hipStream_t q = s->stream;
-    const GbaDev *dP = (const GbaDev *)(base + Lay.o_dev);
+    const GbaDev &D = Lay.D;
     const dim3 T(kGbaThreads);
-    const size_t n_slots = (size_t)D.sys.n_slots, n6 = 6 * (size_t)G.np;
-    std::vector<double> Hs(n_slots * 36), b(n6);
-    AOS2_HIP_CHECK(hipMemcpyAsync(base, Lay.H.data(), Lay.in_bytes, hipMemcpyHostToDevice, q));
-    hipLaunchKernelGGL(k_gba_prepare, dim3(gba_blocks(std::max<long long>(std::max(p->n_poses, p->n_points), std::max(6LL * G.np, 3LL * G.nl)))), T, 0, q, dP);
-    hipLaunchKernelGGL(k_gba_linearise, dim3(Lay.n_eblk), T, 0, q, dP);
-    hipLaunchKernelGGL(k_gba_sums, dim3(gba_blocks(42LL * G.np + 12LL * G.nl)), T, 0, q, dP);
-    hipLaunchKernelGGL(k_gba_landmarks, dim3(gba_blocks(G.nl)), T, 0, q, dP);
-    hipLaunchKernelGGL(k_gba_assemble, dim3(gba_blocks(36LL * D.sys.n_slots + 6LL * G.np)), T, 0, q, dP);
-    AOS2_HIP_CHECK(hipMemcpyAsync(Hs.data(), base + Lay.Hs, 8 * Hs.size(), hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(b.data(), base + Lay.bs, 8 * n6, hipMemcpyDeviceToHost, q));
+    const size_t n6 = 6 * (size_t)G.np;
+    std::vector<double> Hs((size_t)D.sys.n_slots * 36);
+    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p, Lay.H.data(), Lay.in_bytes, hipMemcpyHostToDevice, q));
+    hipLaunchKernelGGL(k_gba_prepare, dim3(Lay.g_prep), T, 0, q, Lay.dP);
+    hipLaunchKernelGGL(k_gba_linearise, dim3(Lay.n_eblk), T, 0, q, Lay.dP);
+    hipLaunchKernelGGL(k_gba_sums, dim3(Lay.g_sums), T, 0, q, Lay.dP);
+    hipLaunchKernelGGL(k_gba_landmarks, dim3(Lay.g_land), T, 0, q, Lay.dP);
+    hipLaunchKernelGGL(k_gba_assemble, dim3(Lay.g_asm), T, 0, q, Lay.dP);
+    AOS2_HIP_CHECK(hipMemcpyAsync(Hs.data(), D.sys.H, bytes_of(D.sys.H, Hs.size()), hipMemcpyDeviceToHost, q));
+    AOS2_HIP_CHECK(hipMemcpyAsync(bs, D.sys.b, bytes_of(D.sys.b, n6), hipMemcpyDeviceToHost, q));
     AOS2_HIP_CHECK(hipStreamSynchronize(q));
     AOS2_HIP_CHECK(hipGetLastError());
-    // dense, both triangles; a diagonal block is given by its lower triangle
-    std::fill(S, S + n6 * n6, 0.0);
-    for (size_t sl = 0; sl < n_slots; ++sl) {
-        size_t row = sl, col = sl;
-        if (sl >= (size_t)G.np) {
-            const int pp = (int)(sl - (size_t)G.np);
-            row = (size_t)G.Y.rowidx[(size_t)pp];
-            col = (size_t)(std::upper_bound(G.Y.colptr.begin(), G.Y.colptr.end(), pp) - G.Y.colptr.begin()) - 1;
-        }
-        for (size_t a = 0; a < 6; ++a)
-            for (size_t cc = 0; cc < (sl < (size_t)G.np ? a + 1 : 6); ++cc) {
-                const double v = Hs[sl * 36 + a * 6 + cc];
-                S[(6 * row + a) * n6 + 6 * col + cc] = v;
-                S[(6 * col + cc) * n6 + 6 * row + a] = v;
-            }
-    }
-    memcpy(bs, b.data(), 8 * n6);
+    block_dense<6>(G.Y, Hs.data(), true, S);   // a diagonal block is given by its lower triangle
     *h_blocks = G.h_blocks;
     return AOS2_OK;
 }
@@ -877,50 +816,8 @@ int aos2_debug_global_ba_reduced_device(aos2_lba_t *s, const aos2_lba_problem_t 
 int aos2_debug_global_ba_solve_device(aos2_lba_t *s, int n_blocks, int n_off, const int32_t *rows, const int32_t *cols, const double *val,
                                       const double *diag, const double *b, double lambda, double *x, int32_t *ok, int32_t *l_blocks)
 {
-    bool good = s && n_blocks >= 1 && n_blocks <= 8192 && n_off >= 0 && diag && b && x && ok && l_blocks && (n_off == 0 || (rows && cols && val));
-    for (int i = 0; good && i < n_off; ++i) good = cols[i] >= 0 && rows[i] > cols[i] && rows[i] < n_blocks;
-    if (!good) {
-        set_error("bad argument (1..8192 blocks, triplets of the lower triangle, the arrays)");
-        return AOS2_ERR_ARG;
-    }
-    BlockSymbolic Y;
-    if (!block_symbolic(n_blocks, std::vector<int32_t>(rows, rows + n_off), std::vector<int32_t>(cols, cols + n_off), 36, kGbaArenaMax, Y)) {
-        set_error("the factor does not fit");
-        return AOS2_ERR_GBA_MEMORY;
-    }
-    const size_t n_slots = (size_t)n_blocks + Y.l_blocks(), nx = 6 * (size_t)n_blocks;
-    std::vector<double> Hv(n_slots * 36, 0.0);
-    memcpy(Hv.data(), diag, 288 * (size_t)n_blocks);
-    for (int i = 0; i < n_off; ++i) {
-        double *dst = Hv.data() + (size_t)Y.slot(rows[i], cols[i]) * 36;
-        for (int k = 0; k < 36; ++k) dst[k] += val[(size_t)i * 36 + k];
-    }
-    int st = lba_handle_init(s);
-    if (st) return st;
-    HostArena H;
-    auto push_v = [&H](const std::vector<int32_t> &v) { return H.push(v.empty() ? nullptr : v.data(), v.size() * 4); };
-    const size_t o_colptr = push_v(Y.colptr), o_rowidx = push_v(Y.rowidx), o_upd_ptr = push_v(Y.upd_ptr), o_upd_dst = push_v(Y.upd_dst);
-    const size_t o_H = H.push(Hv.data(), 8 * Hv.size()), o_b = H.push(b, 8 * nx), o_x = H.push(x, 8 * nx);
-    const size_t in_bytes = H.host_size;
-    const size_t o_ok = H.push(nullptr, 4), o_L = H.push(nullptr, 8 * Hv.size()), o_y = H.push(nullptr, 8 * nx);
-    if ((st = s->arena.alloc(H.size + 256))) return st;
-    uint8_t *base = s->arena.p;
-    BlockSystem S;
-    S.nf = n_blocks;
-    S.n_slots = (int32_t)n_slots;
-    S.colptr = (const int32_t *)(base + o_colptr); S.rowidx = (const int32_t *)(base + o_rowidx);
-    S.upd_ptr = (const int32_t *)(base + o_upd_ptr); S.upd_dst = (const int32_t *)(base + o_upd_dst);
-    S.H = (const double *)(base + o_H); S.b = (const double *)(base + o_b);
-    S.L = (double *)(base + o_L); S.y = (double *)(base + o_y); S.x = (double *)(base + o_x);
-    hipStream_t q = s->stream;
-    AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
-    hipLaunchKernelGGL(k_gba_factor_solve_tap, dim3(1), dim3(kGbaThreads), 0, q, S, lambda, (int32_t *)(base + o_ok));
-    AOS2_HIP_CHECK(hipMemcpyAsync(x, base + o_x, 8 * nx, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(ok, base + o_ok, 4, hipMemcpyDeviceToHost, q));
-    AOS2_HIP_CHECK(hipStreamSynchronize(q));
-    AOS2_HIP_CHECK(hipGetLastError());
-    *l_blocks = (int32_t)Y.l_blocks();
-    return AOS2_OK;
+    return block_solve_tap<6, k_gba_factor_solve_tap>(s, 8192, AOS2_ERR_GBA_MEMORY, kGbaArenaMax, n_blocks, n_off, rows, cols, val, diag, b, lambda, x, ok,
+                                                      l_blocks);
 }
 
 }  // extern "C"

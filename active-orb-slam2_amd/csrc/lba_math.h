@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "aos2_common.h"
+#include "regions.h"
 
 namespace aos2 {
 
@@ -328,38 +329,6 @@ __host__ __device__ inline void pose_to_Tcw(const double qt[7], float *T)
     T[15] = 1.f;
 }
 
-// staged inputs of a call: a prefix of the device arena assembled in page-locked host memory
-struct HostArena {
-    uint8_t *host = nullptr;
-    size_t host_cap = 0, host_size = 0;
-    std::vector<uint8_t> own;
-    size_t size = 0;            // total arena size including device-only scratch
-    const uint8_t *data() const { return host ? host : own.data(); }
-    size_t push(const void *src, size_t bytes)
-    {
-        const size_t off = (size + 255) & ~(size_t)255;
-        size = off + bytes;
-        if (src && bytes) {  // inputs are pushed before any scratch, so the staged part stays a prefix
-            if (!host) {
-                own.resize(size);
-                memcpy(own.data() + off, src, bytes);
-            } else if (size <= host_cap)
-                memcpy(host + off, src, bytes);
-            host_size = size;
-        }
-        return off;
-    }
-    // input produced in place (conversions): returns where to write it
-    template <class T>
-    T *push_fill(size_t count, size_t &off)
-    {
-        off = (size + 255) & ~(size_t)255;
-        size = off + count * sizeof(T);
-        host_size = size;
-        return size <= host_cap ? reinterpret_cast<T *>(host + off) : nullptr;
-    }
-};
-
 }  // namespace aos2
 
 // Handle shared by aos2_lba_solve* (lba.hip) and aos2_pose_optimization (pose_opt.hip): device, stream, arenas.
@@ -391,9 +360,52 @@ struct aos2_lba {
     int host_threads = 0;               // LocalBA: worker threads of the per-window host work (0 = default, aos2_lba_set_host_threads)
     int last_trial_slots = 0, last_host_rounds = 0;   // the device program of the last solve (aos2_lba_last_program)
     long long last_window_slots = 0;                  // ... and its trial slots summed over the windows each round covered
+    std::vector<aos2::Region> so_fields;              // OptimizeSim3: the field list of the last call, kept for its capacity
 };
 
 namespace aos2 {
 // binds the device, creates the stream / events on first use (lba.hip)
 int lba_handle_init(aos2_lba *s);
+
+// Device time per family of launches (aos2_debug_essential_graph_profile, aos2_debug_global_ba_profile): an event pair around
+// every family of a call, summed per family after it.  With `on` false nothing is recorded.
+struct LaunchProfiler {
+    bool on;
+    hipStream_t q;
+    std::vector<hipEvent_t> marks;
+    std::vector<int> family;   // of every pair
+    void mark(int f, bool begin)
+    {
+        if (!on) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, q);
+        marks.push_back(e);
+        if (begin) family.push_back(f);
+    }
+    // after the stream was synchronised: ms[f] = the time of family f's pairs; the events go
+    void sum(float *ms, int n)
+    {
+        for (int f = 0; f < n; ++f) ms[f] = 0;
+        for (size_t k = 0; k < family.size(); ++k) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, marks[2 * k], marks[2 * k + 1]) == hipSuccess) ms[family[k]] += t;
+        }
+        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+        marks.clear();
+        family.clear();
+    }
+    // an aos2_debug_*_profile entry: the switch of the next calls, the sums of the last one
+    template <int N>
+    static int entry(aos2_lba *s, bool aos2_lba::*flag, float (aos2_lba::*ms)[N], int on_, float *out)
+    {
+        if (!s) {
+            set_error("bad argument");
+            return AOS2_ERR_ARG;
+        }
+        s->*flag = on_ != 0;
+        if (out) memcpy(out, s->*ms, sizeof(float) * N);
+        return AOS2_OK;
+    }
+};
 }  // namespace aos2

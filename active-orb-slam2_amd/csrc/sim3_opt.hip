@@ -361,6 +361,24 @@ static void so_sim3_of(const double *v, Sim3d &S)
     S.s = v[7];
 }
 
+// A problem's six input arrays staged, with the pointers of D.A registered for them (D stays where it is until the arena is bound),
+// and everything of D that is no pointer into the arena.
+static void so_stage(HostArena &H, const aos2_sim3_opt_problem_t &P, SoProbDev &D)
+{
+    const size_t n = (size_t)P.n;
+    so_input(P, D.A, D.S_in);
+    H.in(D.A.X1c, P.X1c, 3 * n);
+    H.in(D.A.X2c, P.X2c, 3 * n);
+    H.in(D.A.obs1, P.obs1, 2 * n);
+    H.in(D.A.obs2, P.obs2, 2 * n);
+    H.in(D.A.w1, P.inv_sigma2_1, n);
+    H.in(D.A.w2, P.inv_sigma2_2, n);
+    D.th2 = (double)P.th2;
+    D.delta = so_delta(P.th2);
+    D.fix_scale = P.fix_scale != 0;
+    D.pad = 0;
+}
+
 }  // namespace aos2
 
 using namespace aos2;
@@ -388,58 +406,38 @@ int aos2_optimize_sim3(aos2_lba_t *s, const aos2_sim3_opt_problem_t *p, aos2_sim
     // inputs and the problem descriptors go up as one copy from the handle's page-locked staging buffer, the results of all problems
     // -- outcome and outlier flags -- are neighbours in the arena and come back as one copy (as aos2_pose_optimization does it)
     HostArena H;
-    struct Off { size_t x1, x2, o1, o2, w1, w2, chi, act, out, res; };
-    std::vector<Off> offs((size_t)n_dev);
+    H.fields.swap(s->so_fields);   // (the handle keeps the list's memory between calls)
+    H.fields.clear();
+    std::vector<SoProbDev> dev((size_t)n_dev);   // the table: its pointer fields are registered with the arena, by address
     size_t in_cap = sizeof(SoProbDev) * (size_t)n_dev + 512;
     for (int d = 0; d < n_dev; ++d) in_cap += (size_t)p[src[d]].n * (12 + 12 + 8 + 8 + 4 + 4) + 6 * 256;
     if ((st = s->h_in.alloc(in_cap))) return st;
     H.host = s->h_in.p;
     H.host_cap = in_cap;
-    for (int d = 0; d < n_dev; ++d) {
-        const aos2_sim3_opt_problem_t &P = p[src[d]];
-        const size_t n = (size_t)P.n;
-        offs[d].x1 = H.push(P.X1c, 12 * n);
-        offs[d].x2 = H.push(P.X2c, 12 * n);
-        offs[d].o1 = H.push(P.obs1, 8 * n);
-        offs[d].o2 = H.push(P.obs2, 8 * n);
-        offs[d].w1 = H.push(P.inv_sigma2_1, 4 * n);
-        offs[d].w2 = H.push(P.inv_sigma2_2, 4 * n);
-    }
+    for (int d = 0; d < n_dev; ++d) so_stage(H, p[src[d]], dev[d]);
     size_t o_probs;
-    SoProbDev *dev = H.push_fill<SoProbDev>((size_t)n_dev, o_probs);   // filled below (needs the device base)
-    if (!dev || H.host_size > in_cap) {
+    SoProbDev *table = H.push_fill<SoProbDev>((size_t)n_dev, o_probs);   // filled below (needs the device base)
+    if (!table || H.host_size > in_cap) {
         set_error("internal: OptimizeSim3 input staging");
         return AOS2_ERR_ARG;
     }
     const size_t in_bytes = H.host_size;
     for (int d = 0; d < n_dev; ++d) {
         const size_t n = (size_t)p[src[d]].n;
-        offs[d].chi = H.push(nullptr, 16 * n);
-        offs[d].act = H.push(nullptr, 2 * n);
+        H.room(dev[d].chi, 2 * n);
+        H.room(dev[d].act, 2 * n);
     }
-    const size_t o_res = (H.size + 255) & ~(size_t)255;   // results of all problems from here on
+    const size_t o_res = up256(H.size);   // results of all problems from here on
     for (int d = 0; d < n_dev; ++d) {
-        offs[d].res = H.push(nullptr, sizeof(SoResDev));
-        offs[d].out = H.push(nullptr, (size_t)p[src[d]].n);
+        H.room(dev[d].res, 1);
+        H.room(dev[d].outlier, (size_t)p[src[d]].n);
     }
     const size_t res_bytes = H.size - o_res;
     if ((st = s->arena.alloc(H.size + 256))) return st;
     if ((st = s->h_stage.alloc(res_bytes + 64))) return st;
     uint8_t *base = s->arena.p;
-    for (int d = 0; d < n_dev; ++d) {
-        const aos2_sim3_opt_problem_t &P = p[src[d]];
-        SoProbDev &D = dev[d];
-        so_input(P, D.A, D.S_in);
-        D.A.X1c = (const float *)(base + offs[d].x1); D.A.X2c = (const float *)(base + offs[d].x2);
-        D.A.obs1 = (const float *)(base + offs[d].o1); D.A.obs2 = (const float *)(base + offs[d].o2);
-        D.A.w1 = (const float *)(base + offs[d].w1); D.A.w2 = (const float *)(base + offs[d].w2);
-        D.chi = (double *)(base + offs[d].chi); D.act = base + offs[d].act; D.outlier = base + offs[d].out;
-        D.res = (SoResDev *)(base + offs[d].res);
-        D.th2 = (double)P.th2;
-        D.delta = so_delta(P.th2);
-        D.fix_scale = P.fix_scale != 0;
-        D.pad = 0;
-    }
+    H.bind(base);
+    memcpy(table, dev.data(), sizeof(SoProbDev) * (size_t)n_dev);
     hipStream_t q = s->stream;
     AOS2_HIP_CHECK(hipMemcpyAsync(base, H.data(), in_bytes, hipMemcpyHostToDevice, q));
     AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
@@ -454,10 +452,11 @@ int aos2_optimize_sim3(aos2_lba_t *s, const aos2_sim3_opt_problem_t *p, aos2_sim
     for (int d = 0; d < n_dev; ++d) {
         const aos2_sim3_opt_problem_t &P = p[src[d]];
         SoResDev R;
-        memcpy(&R, res + (offs[d].res - o_res), sizeof R);
-        memcpy(r[src[d]].outlier, res + (offs[d].out - o_res), (size_t)P.n);
+        memcpy(&R, span_copy(res, base + o_res, dev[d].res), sizeof R);
+        memcpy(r[src[d]].outlier, span_copy(res, base + o_res, dev[d].outlier), (size_t)P.n);
         so_result_set(P, R.S, R.wrote, R.n_bad, R.n_inliers, R.iterations, R.trials, r[src[d]]);
     }
+    s->so_fields.swap(H.fields);
     return AOS2_OK;
 }
 
@@ -534,55 +533,32 @@ int aos2_debug_sim3_opt_steps_device(aos2_lba_t *s, const aos2_sim3_opt_steps_t 
     // One image of the arena goes up and the whole of it comes back: the outputs start as what the caller's buffers hold, so what no
     // thread writes returns as it was passed in.
     HostArena H;
-    struct Off { size_t x1, x2, o1, o2, w1, w2, chi, act, out, Hb, pert, chi_lin, sum, chi_trial, flagged; };
-    std::vector<Off> offs((size_t)n_items);
+    std::vector<SoStepDev> dev((size_t)n_items);   // the table: its pointer fields are registered with the arena, by address
     for (int i = 0; i < n_items; ++i) {
         const aos2_sim3_opt_steps_t &I = items[i];
-        const aos2_sim3_opt_problem_t &P = I.problem;
-        const size_t n = (size_t)P.n, tail = (size_t)I.tail;
-        Off &o = offs[i];
-        o.x1 = H.push(P.X1c, 12 * n);
-        o.x2 = H.push(P.X2c, 12 * n);
-        o.o1 = H.push(P.obs1, 8 * n);
-        o.o2 = H.push(P.obs2, 8 * n);
-        o.w1 = H.push(P.inv_sigma2_1, 4 * n);
-        o.w2 = H.push(P.inv_sigma2_2, 4 * n);
-        o.chi = H.push(I.chi_in, 8 * (2 * n + tail));
-        o.act = H.push(I.act_in, 2 * n + tail);
-        o.out = H.push(I.outlier_in, n + tail);
-        o.Hb = H.push(I.Hb, 8 * kSoSum);
-        o.pert = H.push(I.pert, 8 * 8 * 28);
-        o.chi_lin = H.push(I.chi_lin, 16 * n);
-        o.sum = H.push(I.trial_sum, 8);
-        o.chi_trial = H.push(I.chi_trial, 16 * n);
-        o.flagged = H.push(I.flagged, 4);
+        const size_t n = (size_t)I.problem.n, tail = (size_t)I.tail;
+        SoStepDev &D = dev[i];
+        so_stage(H, I.problem, D.P);
+        H.in(D.P.chi, I.chi_in, 2 * n + tail);
+        H.in(D.P.act, I.act_in, 2 * n + tail);
+        H.in(D.P.outlier, I.outlier_in, n + tail);
+        H.in(D.Hb, I.Hb, kSoSum);
+        H.in(D.pert, I.pert, 8 * 28);
+        H.in(D.chi_lin, I.chi_lin, 2 * n);
+        H.in(D.trial_sum, I.trial_sum, 1);
+        H.in(D.chi_trial, I.chi_trial, 2 * n);
+        H.in(D.flagged, I.flagged, 1);
+        so_sim3_of(I.S_lin, D.S_lin);
+        so_sim3_of(I.S_trial, D.S_trial);
+        D.mask = I.mask;
+        D.remove = I.remove != 0;
     }
     const size_t o_items = H.push(nullptr, sizeof(SoStepDev) * (size_t)n_items);
     H.own.resize(H.size);
     if ((st = s->arena.alloc(H.size + 256))) return st;
     uint8_t *base = s->arena.p;
-    SoStepDev *dev = (SoStepDev *)(H.own.data() + o_items);
-    for (int i = 0; i < n_items; ++i) {
-        const aos2_sim3_opt_steps_t &I = items[i];
-        const Off &o = offs[i];
-        SoStepDev D{};
-        so_input(I.problem, D.P.A, D.P.S_in);
-        D.P.A.X1c = (const float *)(base + o.x1); D.P.A.X2c = (const float *)(base + o.x2);
-        D.P.A.obs1 = (const float *)(base + o.o1); D.P.A.obs2 = (const float *)(base + o.o2);
-        D.P.A.w1 = (const float *)(base + o.w1); D.P.A.w2 = (const float *)(base + o.w2);
-        D.P.chi = (double *)(base + o.chi); D.P.act = base + o.act; D.P.outlier = base + o.out;
-        D.P.res = nullptr;
-        D.P.th2 = (double)I.problem.th2;
-        D.P.delta = so_delta(I.problem.th2);
-        D.P.fix_scale = I.problem.fix_scale != 0;
-        so_sim3_of(I.S_lin, D.S_lin);
-        so_sim3_of(I.S_trial, D.S_trial);
-        D.Hb = (double *)(base + o.Hb); D.pert = (double *)(base + o.pert); D.chi_lin = (double *)(base + o.chi_lin);
-        D.trial_sum = (double *)(base + o.sum); D.chi_trial = (double *)(base + o.chi_trial); D.flagged = (int32_t *)(base + o.flagged);
-        D.mask = I.mask;
-        D.remove = I.remove != 0;
-        memcpy(dev + i, &D, sizeof D);
-    }
+    H.bind(base);
+    memcpy(H.own.data() + o_items, dev.data(), sizeof(SoStepDev) * (size_t)n_items);
     hipStream_t q = s->stream;
     AOS2_HIP_CHECK(hipMemcpyAsync(base, H.own.data(), H.size, hipMemcpyHostToDevice, q));
     hipLaunchKernelGGL(sim3_opt_steps_kernel, dim3(n_items), dim3(kSoThreads), 0, q, (const SoStepDev *)(base + o_items));
@@ -592,17 +568,17 @@ int aos2_debug_sim3_opt_steps_device(aos2_lba_t *s, const aos2_sim3_opt_steps_t 
     for (int i = 0; i < n_items; ++i) {
         const aos2_sim3_opt_steps_t &I = items[i];
         const size_t n = (size_t)I.problem.n, tail = (size_t)I.tail;
-        const Off &o = offs[i];
+        const SoStepDev &D = dev[i];
         const uint8_t *back = H.own.data();
-        memcpy(I.chi, back + o.chi, 8 * (2 * n + tail));
-        memcpy(I.act, back + o.act, 2 * n + tail);
-        memcpy(I.outlier, back + o.out, n + tail);
-        memcpy(I.Hb, back + o.Hb, 8 * kSoSum);
-        memcpy(I.pert, back + o.pert, 8 * 8 * 28);
-        memcpy(I.chi_lin, back + o.chi_lin, 16 * n);
-        memcpy(I.trial_sum, back + o.sum, 8);
-        memcpy(I.chi_trial, back + o.chi_trial, 16 * n);
-        memcpy(I.flagged, back + o.flagged, 4);
+        memcpy(I.chi, span_copy(back, base, D.P.chi), bytes_of(D.P.chi, 2 * n + tail));
+        memcpy(I.act, span_copy(back, base, D.P.act), 2 * n + tail);
+        memcpy(I.outlier, span_copy(back, base, D.P.outlier), n + tail);
+        memcpy(I.Hb, span_copy(back, base, D.Hb), bytes_of(D.Hb, kSoSum));
+        memcpy(I.pert, span_copy(back, base, D.pert), bytes_of(D.pert, 8 * 28));
+        memcpy(I.chi_lin, span_copy(back, base, D.chi_lin), bytes_of(D.chi_lin, 2 * n));
+        memcpy(I.trial_sum, span_copy(back, base, D.trial_sum), bytes_of(D.trial_sum, 1));
+        memcpy(I.chi_trial, span_copy(back, base, D.chi_trial), bytes_of(D.chi_trial, 2 * n));
+        memcpy(I.flagged, span_copy(back, base, D.flagged), bytes_of(D.flagged, 1));
     }
     return AOS2_OK;
 }

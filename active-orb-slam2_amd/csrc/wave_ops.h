@@ -111,6 +111,37 @@ __device__ __forceinline__ double row_sum_f64(double v)
     return v;
 }
 
+// Sum of N doubles per thread over a workgroup of NT threads (all active; part: NT / 16 * N doubles of LDS), the result in every
+// thread.  Row sums by DPP (lane 0 of a row of 16 is the one that is kept), then every thread adds the row partials in row order:
+// the order depends on nothing but the thread number.  The second barrier lets `part` be written again.
+template <int N, int NT = 256>
+__device__ __forceinline__ void block_sum_f64(double (&v)[N], double *part)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = row_sum_f64(v[i]);
+    if ((tid & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) part[(tid >> 4) * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = part[i];
+        for (int r = 1; r < NT / 16; ++r) s += part[r * N + i];
+        v[i] = s;
+    }
+    __syncthreads();
+}
+// the same for one value
+template <int NT = 256>
+__device__ __forceinline__ double block_sum_f64(double v, double *part)
+{
+    double a[1] = {v};
+    block_sum_f64<1, NT>(a, part);
+    return a[0];
+}
+
 // ---- K row sums at once as a reduce-scatter: the totals of row_sum_f64 (the same operands in the same tree, so the same bits)
 // without forming every total in every lane.  The four levels pair lane ^ 1, lane ^ 2, lane ^ 4, lane ^ 8; at a level a lane keeps
 // one value of each pair of its remaining values and hands the other one to its partner, who adds it to the one it kept:

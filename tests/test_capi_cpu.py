@@ -398,14 +398,17 @@ def test_lba_window_builder_on_a_hand_made_graph(tmp_path):
 def test_region_list_offsets_and_binding(tmp_path):
     """aos2::Regions (csrc/regions.h), the typed region list of the frame batch's buffers, as a stand-alone program under the address
     and undefined-behaviour sanitizers: 256-byte offsets, disjoint regions in order of registration (one of them empty), bytes(),
-    what bind() writes into the fields, the same layout from the same calls (tests/cpp/regions_test.cpp)."""
+    what bind() writes into the fields, the same layout from the same calls.  And aos2::HostArena, the arena of the loop-closing
+    optimisers with its staged prefix: an empty region first and last, a null source among the inputs, an element 20 bytes wide, a
+    field set with at() inside an array, bind() to two bases, and a caller's buffer that the last push fills exactly or misses by a
+    byte (tests/cpp/regions_test.cpp)."""
     import subprocess
     exe = str(tmp_path / "regions_test")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            os.path.join(ROOT, "tests", "cpp", "regions_test.cpp"), "-I", os.path.join(ROOT, "active-orb-slam2_amd", "csrc"),
                            "-o", exe])
     out = subprocess.check_output([exe], text=True)
-    assert "regions_test ok: 7 regions, 1536 bytes" in out
+    assert "regions_test ok: 7 regions, 1536 bytes; host arena ok: 7 fields, 612 of 1280 bytes staged" in out
 
 
 def test_frame_members_of_a_batch_that_was_never_built(pkg):
