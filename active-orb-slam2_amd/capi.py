@@ -163,6 +163,13 @@ def lib():
         L.aos2_debug_local_map_host.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
         L.aos2_local_map_update.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
         L.aos2_debug_local_map_stats_host.argtypes = [vp, ci, ci, vp, vp, vp, ci, ci, vp, vp]
+        L.aos2_local_map_set_culling_view.argtypes = [vp, vp]
+        L.aos2_local_map_keyframe_culling.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
+        L.aos2_local_map_debug_culling_rounds.argtypes = [vp, ci]
+        L.aos2_local_map_last_culling_rounds.argtypes = [vp]
+        L.aos2_local_map_last_culling_device_ms.argtypes = [vp]
+        L.aos2_local_map_last_culling_device_ms.restype = C.c_float
+        L.aos2_debug_keyframe_culling_host.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
@@ -1237,6 +1244,44 @@ def _local_map_graph(g, keep):
     return s
 
 
+# ---- LocalMapping::KeyFrameCulling over the resident graph (include/aos2.h: aos2_local_map_set_culling_view and friends)
+KFC_KEPT, KFC_CULLED, KFC_DEFERRED, KFC_SKIPPED = range(4)
+_KFC_FIELDS = (("obs_idx", np.int32), ("kf_octave", np.int8), ("kf_depth", np.float32), ("kf_stereo", np.uint8),
+               ("kf_th_depth", np.float32), ("kf_flags", np.uint8))
+
+
+class _KfCullingView(C.Structure):
+    """aos2_kf_culling_view_t"""
+    _fields_ = [(k, C.c_void_p) for k, _ in _KFC_FIELDS]
+
+
+def _kf_culling_view(v, keep):
+    """a view dict (the fields of aos2_kf_culling_view_t; an array may be None = NULL) -> the struct; `keep` holds the arrays"""
+    s = _KfCullingView()
+    for k, dt in _KFC_FIELDS:
+        a = v.get(k)
+        if a is None:
+            setattr(s, k, None)
+            continue
+        a = np.ascontiguousarray(a, dt).reshape(-1)
+        keep.append(a)
+        setattr(s, k, a.ctypes.data if a.size else keep[0].ctypes.data)   # (an empty array is not NULL)
+    return s
+
+
+def _kf_culling_call(fn, first, monocular, cand, bad_cap):
+    """the arguments that aos2_local_map_keyframe_culling and its host tap share -> dict(status uint8 [n], n_mps, n_redundant int32
+    [n], n_bad_points int, bad_points int32 [bad_cap + 1]: one element more than the call may write, preset to -7)"""
+    cand = np.ascontiguousarray(cand, np.int32).reshape(-1)
+    n = len(cand)
+    status = np.full(max(n, 1), 255, np.uint8)
+    n_mps, n_red = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), -7, np.int32)
+    bad = np.full(int(bad_cap) + 1, -7, np.int32)
+    nb = C.c_int32(-7)
+    _check(fn(*first, int(bool(monocular)), n, _p(cand), _p(status), _p(n_mps), _p(n_red), _p(bad), int(bad_cap), C.byref(nb)))
+    return dict(status=status[:n], n_mps=n_mps[:n], n_redundant=n_red[:n], n_bad_points=int(nb.value), bad_points=bad)
+
+
 class LocalMap:
     """The covisibility graph resident on the device and Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) for the frames of a
     capi.Frames batch.  A graph is a dict with the fields of aos2_local_map_graph_t (numpy arrays, CSR offsets)."""
@@ -1296,6 +1341,38 @@ class LocalMap:
 
     def last_groups(self):
         return self.L.aos2_local_map_last_groups(self.h)
+
+    def set_culling_view(self, view, ok=(AOS2_OK,)):
+        """aos2_local_map_set_culling_view: a view is a dict with the fields of aos2_kf_culling_view_t; `ok` as in set()"""
+        keep = [np.zeros(1, np.int32)]
+        s = _kf_culling_view(view, keep)
+        return _check(self.L.aos2_local_map_set_culling_view(self.h, C.byref(s)), ok)
+
+    def keyframe_culling(self, cand, monocular=False, bad_cap=None):
+        """aos2_local_map_keyframe_culling (LocalMapping::KeyFrameCulling, src/LocalMapping.cc:636-700) on the device; bad_cap
+        defaults to the number of points of the handle's graph -> the dict of _kf_culling_call"""
+        if bad_cap is None:
+            s = _LocalMapGraph()
+            _check(self.L.aos2_local_map_get(self.h, C.byref(s)))
+            bad_cap = s.n_points
+        return _kf_culling_call(self.L.aos2_local_map_keyframe_culling, (self.h,), monocular, cand, bad_cap)
+
+    def debug_culling_rounds(self, rounds=0):
+        _check(self.L.aos2_local_map_debug_culling_rounds(self.h, int(rounds)))
+
+    def last_culling_rounds(self):
+        return self.L.aos2_local_map_last_culling_rounds(self.h)
+
+    def last_culling_device_ms(self):
+        return float(self.L.aos2_local_map_last_culling_device_ms(self.h))
+
+    @staticmethod
+    def keyframe_culling_host(graph, view, cand, monocular=False, bad_cap=None):
+        """aos2_debug_keyframe_culling_host: the same loop on one core, no device"""
+        keep = [np.zeros(1, np.int32)]
+        g, v = _local_map_graph(graph, keep), _kf_culling_view(view, keep)
+        bad_cap = int(graph["n_points"]) if bad_cap is None else bad_cap
+        return _kf_culling_call(lib().aos2_debug_keyframe_culling_host, (C.byref(g), C.byref(v)), monocular, cand, bad_cap)
 
     def update_host(self, n, mp, local_cap, kf_cap, local_kfs=None, n_local_kfs=None, ref_kf=None):
         """aos2_local_map_update: the device kernels on host arrays, arguments and result as host()"""

@@ -830,6 +830,46 @@ int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, 
     return AOS2_OK;
 }
 
+// LocalMapping::KeyFrameCulling (src/LocalMapping.cc:636-700): the loop as the reference runs it, one candidate, one feature and
+// one observation at a time, through the per-item functions of csrc/kf_culling.h; SetBadFlag's erasure takes effect at once
+int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view, int monocular, int n_cand,
+                                     const int32_t *cand, uint8_t *status, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points,
+                                     int bad_cap, int32_t *n_bad_points)
+{
+    using namespace aos2;
+    if (int st = local_map_check(g, nullptr)) return st;
+    if (int st = kf_culling_check_view(g, view)) return st;
+    if (int st = kf_culling_check_call(g->n_keyframes, n_cand, cand, status, n_mps, n_redundant, bad_points, bad_cap, n_bad_points))
+        return st;
+    const int np = g->n_points;
+    const KfcGraph G = {np, g->n_keyframes, g->point_bad, g->point_nobs, g->obs_off, g->obs_kf, g->kf_mp_off, g->kf_mp, view->obs_idx,
+                        view->kf_octave, view->kf_depth, view->kf_stereo, view->kf_th_depth, view->kf_flags};
+    std::vector<int32_t> nobs(g->point_nobs, g->point_nobs + np), stamp(np, -1);
+    std::vector<uint8_t> bad(g->point_bad, g->point_bad + np), erased(g->obs_off[np], 0);
+    const KfcOverlay X = {nobs.data(), stamp.data(), bad.data(), erased.data()};
+    std::vector<int32_t> went_bad;
+    for (int ci = 0; ci < n_cand; ci++) {
+        const int pKF = cand[ci];
+        int nMPs = 0, nRedundantObservations = 0;
+        if (!(G.kf_flags[pKF] & 1))
+            for (int f = G.kf_mp_off[pKF]; f < G.kf_mp_off[pKF + 1]; f++) {
+                const int r = kfc_feature(G, X, monocular ? 1 : 0, pKF, f);
+                nMPs += r & 1;
+                nRedundantObservations += r >> 1;
+            }
+        status[ci] = (uint8_t)kfc_status(G.kf_flags[pKF], nMPs, nRedundantObservations);
+        n_mps[ci] = nMPs;
+        n_redundant[ci] = nRedundantObservations;
+        if (status[ci] == AOS2_KFC_CULLED)
+            for (int f = G.kf_mp_off[pKF]; f < G.kf_mp_off[pKF + 1]; f++)
+                if (kfc_erase(G, X, pKF, ci, f)) went_bad.push_back(G.kf_mp[f]);
+    }
+    std::sort(went_bad.begin(), went_bad.end());
+    *n_bad_points = (int32_t)went_bad.size();
+    for (int j = 0; j < std::min<int>((int)went_bad.size(), bad_cap); ++j) bad_points[j] = went_bad[j];
+    return AOS2_OK;
+}
+
 // check_collisions (src/collisions.cc:70-94) and countVisible of one state, then isValid (src/StateValidChecker.cc:97-119)
 static bool svc_valid_host(const aos2::SvcView &V, const double *q, uint8_t *cfree_out, int32_t *count_out)
 {

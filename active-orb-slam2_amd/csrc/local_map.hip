@@ -27,14 +27,8 @@ namespace {
 
 constexpr int kNT = 256;                 // threads of k_lm_keyframes and k_lm_stats
 constexpr int kPT = 512;                 // threads of k_lm_points
-constexpr int kLdsKfs = 8192;            // keyframes whose vote counters fit the workgroup's LDS (32 KiB)
-constexpr int64_t kScratchBytes = (int64_t)256 << 20;
-
-struct LmGraphDev {
-    int n_points, n_kfs;
-    const uint8_t *point_bad, *kf_bad;
-    const int32_t *point_nobs, *obs_off, *obs_kf, *kf_mp_off, *kf_mp, *kf_best, *kf_child_off, *kf_child, *kf_parent;
-};
+constexpr int kLdsKfs = kLmLdsKfs;
+constexpr int64_t kScratchBytes = kLmScratchBytes;
 
 struct LmOut {
     int32_t *local, *n_local, *local_kfs, *n_local_kfs, *ref_kf;
@@ -337,24 +331,6 @@ int local_map_check(const aos2_local_map_graph_t *g, int *max_features)
 
 }  // namespace aos2
 
-struct aos2_local_map {
-    int device = 0;
-    // the snapshot, host side (aos2_local_map_get hands these out)
-    int n_points = 0, n_kfs = 0, max_features = 0;
-    std::vector<uint8_t> point_bad, kf_bad;
-    std::vector<int32_t> point_nobs, obs_off, obs_kf, kf_mp_off, kf_mp, kf_best, kf_child_off, kf_child, kf_parent;
-    // ... and on the device
-    bool dirty = true;
-    LmGraphDev G = {};
-    DevBuf<uint8_t> d_graph;
-    DevBuf<int32_t> d_scratch;
-    hipStream_t stream = nullptr;   // aos2_local_map_update (host arrays) runs here
-    DevBuf<uint8_t> d_io;           // ... on device copies of its arrays
-    int64_t scratch_bytes = kScratchBytes;
-    int lds_kfs = kLdsKfs;
-    int last_groups = 0;
-};
-
 namespace {
 
 // the handle's host copy as one block of 256-byte aligned regions, copied in one piece
@@ -388,6 +364,8 @@ int upload(aos2_local_map *h)
 }
 
 }  // namespace
+
+int aos2::local_map_upload(aos2_local_map *h) { return upload(h); }
 
 extern "C" {
 
@@ -461,6 +439,8 @@ int aos2_local_map_set(aos2_local_map_t *h, const aos2_local_map_graph_t *g)
     // set<KeyFrame*> spChilds: ascending row stands for the pointer order, each child once
     for (int k = 0; k < nk; ++k) std::sort(h->kf_child.begin() + h->kf_child_off[k], h->kf_child.begin() + h->kf_child_off[k + 1]);
     h->dirty = true;
+    h->has_graph = true;
+    h->kfc.drop_view();   // (its arrays no longer line up with the graph)
     return upload(h);
 }
 

@@ -27,9 +27,32 @@
 
 namespace aos2 {
 
+// the hooks of the snapshot's walk for what one more consumer reads (host/KeyFrameCulling.h: aos2::CullingView); this one gathers
+// nothing
+struct NoSnapshotView {
+    template <class KF> void KeyFrame(KF *) {}
+    void Observation(size_t) {}
+    void Set(aos2_local_map_t *) {}
+};
+
 class LocalMapSnapshot {
 public:
     LocalMapSnapshot(ORB_SLAM2::Map *pMap, const std::vector<ORB_SLAM2::MapPoint *> &vpTable) : mvpPoints(vpTable)
+    {
+        NoSnapshotView none;
+        Build(pMap, none);
+    }
+    // ... with a view gathered in the same walk, so that its arrays line up with the graph's: view.Observation(idx) for every entry
+    // of obs_kf, view.KeyFrame(pKF) for every keyframe in row order, view.Set(handle) behind aos2_local_map_set
+    template <class View>
+    LocalMapSnapshot(ORB_SLAM2::Map *pMap, const std::vector<ORB_SLAM2::MapPoint *> &vpTable, View &&view) : mvpPoints(vpTable)
+    {
+        Build(pMap, view);
+    }
+
+private:
+    template <class View>
+    void Build(ORB_SLAM2::Map *pMap, View &view)
     {
         mvpKeyFrames = pMap->GetAllKeyFrames();
         std::sort(mvpKeyFrames.begin(), mvpKeyFrames.end(),
@@ -45,13 +68,16 @@ public:
             if (ORB_SLAM2::MapPoint *pMP = mvpPoints[p]) {
                 point_bad[p] = pMP->isBad() ? 1 : 0;
                 point_nobs[p] = pMP->Observations();
-                std::set<int32_t> rows;   // (a keyframe once, in ascending row)
+                std::map<int32_t, size_t> rows;   // (a keyframe once, in ascending row, with the feature that observes the point)
                 const std::map<ORB_SLAM2::KeyFrame *, size_t> observations = pMP->GetObservations();
                 for (const auto &ob : observations) {
                     const int32_t r = KeyFrameRow(ob.first);
-                    if (r >= 0) rows.insert(r);
+                    if (r >= 0) rows.insert(std::make_pair(r, ob.second));
                 }
-                obs_kf.insert(obs_kf.end(), rows.begin(), rows.end());
+                for (const auto &row : rows) {
+                    obs_kf.push_back(row.first);
+                    view.Observation(row.second);
+                }
             }
             obs_off.push_back((int32_t)obs_kf.size());
         }
@@ -74,6 +100,7 @@ public:
             }
             kf_child_off.push_back((int32_t)kf_child.size());
             kf_parent[k] = KeyFrameRow(pKF->GetParent());
+            view.KeyFrame(pKF);
         }
         aos2_local_map_graph_t g;
         g.n_points = (int32_t)np; g.point_bad = point_bad.data(); g.point_nobs = point_nobs.data();
@@ -82,7 +109,10 @@ public:
         g.kf_best = kf_best.data(); g.kf_child_off = kf_child_off.data(); g.kf_child = kf_child.data(); g.kf_parent = kf_parent.data();
         check(aos2_local_map_create(thread_device(), &mHandle), "LocalMapSnapshot");
         check(aos2_local_map_set(mHandle, &g), "LocalMapSnapshot");
+        view.Set(mHandle);
     }
+
+public:
     ~LocalMapSnapshot() { aos2_local_map_destroy(mHandle); }
     LocalMapSnapshot(const LocalMapSnapshot &) = delete;
     LocalMapSnapshot &operator=(const LocalMapSnapshot &) = delete;

@@ -1445,6 +1445,64 @@ int aos2_local_map_debug_limits(aos2_local_map_t *m, int64_t scratch_bytes, int 
 int aos2_local_map_last_groups(const aos2_local_map_t *m);
 
 /* ------------------------------------------------------------------------------------------
+ * LocalMapping::KeyFrameCulling (src/LocalMapping.cc:636-700, called at :87) over the handle's resident graph
+ * (csrc/kf_culling.hip): for every covisible keyframe of the new keyframe, nMPs and nRedundantObservations, the cull test, and --
+ * because the loop is serial in its effects -- what KeyFrame::SetBadFlag (src/KeyFrame.cc:514-532) of every culled keyframe does
+ * to the candidates behind it: MapPoint::EraseObservation (src/MapPoint.cc:144-170) on each of its points, and the points that
+ * fall to nObs <= 2 and go bad.  Integer graph work.  The resident graph is READ, never written: the caller applies the verdicts
+ * to its own map (SetBadFlag in candidate order) and re-takes the snapshot, as after every other map change.
+ *
+ * Followed literally: the far-point gate `mvDepth[i] > mThDepth || mvDepth[i] < 0` as float compares
+ * when not monocular; Observations() > 3 on nObs (a stereo observation counts twice); the observer count over observation
+ * entries with pKFi == pKF skipped, the gate scaleLeveli <= scaleLevel + 1 and the stop at 3; the test nRedundantObservations >
+ * 0.9 * nMPs as an int against a double product; no isBad() test on the candidate.  The reference walks the observations in
+ * pointer order; the count stops at 3 whichever entries come first, so NO ordering convention is involved here.
+ * ------------------------------------------------------------------------------------------ */
+/* What the loop reads beside the graph.  The arrays are parallel to the graph's own, so their lengths are the graph's. */
+typedef struct {
+    const int32_t *obs_idx;      /* parallel to obs_kf: mit->second, the feature of that keyframe that observes the point */
+    const int8_t  *kf_octave;    /* parallel to kf_mp: mvKeysUn[i].octave */
+    const float   *kf_depth;     /* parallel to kf_mp: mvDepth[i] */
+    const uint8_t *kf_stereo;    /* parallel to kf_mp: mvuRight[i] >= 0 */
+    const float   *kf_th_depth;  /* [n_keyframes] mThDepth */
+    const uint8_t *kf_flags;     /* [n_keyframes] bit 0: mnId == 0, bit 1: mbNotErase */
+} aos2_kf_culling_view_t;
+#define AOS2_KFC_KEPT 0      /* not redundant */
+#define AOS2_KFC_CULLED 1    /* SetBadFlag erases the keyframe */
+#define AOS2_KFC_DEFERRED 2  /* SetBadFlag with mbNotErase: mbToBeErased is set, nothing is erased, later candidates see no change */
+#define AOS2_KFC_SKIPPED 3   /* mnId == 0 (:647) */
+/* Checks the view against the handle's graph, keeps a copy and uploads it; returns when the upload is complete.  AOS2_ERR_ARG
+ * BEFORE a device is looked for, with the handle's previous view left in place: no graph has been set, an array is NULL while
+ * the graph gives it a non-zero length, an obs_idx outside the feature range of its keyframe.  As with aos2_local_map_set, a view
+ * that passed is the handle's also when the upload fails (AOS2_ERR_NO_DEVICE, AOS2_ERR_HIP): the culling call uploads it.  A later
+ * aos2_local_map_set DROPS the view: its arrays no longer line up with the graph. */
+int aos2_local_map_set_culling_view(aos2_local_map_t *m, const aos2_kf_culling_view_t *view);
+/* The loop :644-699.  cand [n_cand] = the rows of mpCurrentKeyFrame->GetVectorCovisibleKeyFrames() in its order; monocular =
+ * mbMonocular.  All arrays are HOST memory; the call returns when the results are complete.  AOS2_ERR_ARG before any device work:
+ * no view, n_cand < 0, a NULL array with n_cand > 0, n_bad_points NULL, bad_cap < 0 (or > 0 with bad_points NULL), a row out of
+ * range, a row listed twice, and a map whose overlay exceeds the handle's scratch bound (13 bytes per point + 1 per observation
+ * against the 256 MiB of aos2_local_map_debug_limits).  n_cand == 0 is valid.
+ * Per candidate, in the loop's order: status [n_cand] = AOS2_KFC_*; n_mps / n_redundant [n_cand] = nMPs and
+ * nRedundantObservations as the serial loop has them when it reaches that candidate, AFTER the effects of every earlier cull (0 for
+ * a skipped candidate).  A CULLED candidate c changes the rest of the call, one effect per point however often the point sits among
+ * c's matches: for each non-NULL match, bad or not, whose observations contain c that entry is gone and nObs drops by 2 if
+ * kf_stereo at the OBSERVATION's feature of c is set, by 1 otherwise; with nObs <= 2 the point is bad from then on and every
+ * later candidate skips it; a match whose point does not list c changes nothing (and an entry of c in the observations of a point
+ * that c does not hold stays).  DEFERRED and KEPT change nothing.
+ * bad_points (may be NULL with bad_cap 0): the rows of the points that went bad DURING the call (not those the graph already
+ * marks), ascending; *n_bad_points is the true count, the first min(count, bad_cap) are written, nothing behind them.
+ * The work runs in rounds, culls + 1 of them; the outputs do not depend on how many one enqueue holds.
+ * It runs on the handle's own stream and shares the handle's scratch with aos2_local_map_update: one call at a time. */
+int aos2_local_map_keyframe_culling(aos2_local_map_t *m, int monocular, int n_cand, const int32_t *cand, uint8_t *status,
+                                    int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points, int bad_cap, int32_t *n_bad_points);
+/* test hooks: the rounds (count + apply launches) one enqueue holds (<= 0: the default, 4), and the rounds the last call needed */
+int aos2_local_map_debug_culling_rounds(aos2_local_map_t *m, int rounds);
+int aos2_local_map_last_culling_rounds(const aos2_local_map_t *m);
+/* device time of the last aos2_local_map_keyframe_culling call between two events on the handle's stream, from the upload of the
+ * candidates to the last copy back (the host's waits between enqueues included); -1 if there was none */
+float aos2_local_map_last_culling_device_ms(aos2_local_map_t *m);
+
+/* ------------------------------------------------------------------------------------------
  * Replay of a fixed call sequence (csrc/replay.hip).  No single reference function: the per-frame body of Tracking::Track on its
  * usual path -- Frame::Frame (src/Frame.cc:116-172), TrackWithMotionModel (src/Tracking.cc:860-1039: SearchByProjection,
  * PoseOptimization, the outlier discard), TrackLocalMap (:1041-1100: SearchLocalPoints, PoseOptimization) -- is the same ~20
@@ -1543,6 +1601,12 @@ int aos2_debug_local_map_host(const aos2_local_map_graph_t *g, int batch, int ca
                               int local_cap, int32_t *n_local, int32_t *local_kfs, int kf_cap, int32_t *n_local_kfs, int32_t *ref_kf);
 int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, int cap, const int32_t *n, int32_t *mp,
                                     const uint8_t *outlier, int stereo, int only_tracking, int32_t *stats, int32_t *found_inc);
+/* aos2_local_map_keyframe_culling on the HOST with the per-item functions the device kernels also run (csrc/kf_culling.h), in the
+ * loop's own order on one core -- the one-core baseline.  The graph and the view are checked as aos2_local_map_set and
+ * aos2_local_map_set_culling_view check them, the other arguments as the device call checks them; no device is needed. */
+int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view, int monocular, int n_cand,
+                                     const int32_t *cand, uint8_t *status, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points,
+                                     int bad_cap, int32_t *n_bad_points);
 /* the math of csrc/motion_tw.h on arrays of n doubles: sin = tw_sin(x), cos = tw_cos(x), atan2 = tw_atan2(y, x), sqrt = sqrt(x),
  * quot = y / x; on the host (device == -1) or in a kernel of one lane per element.  It tells whether a difference between the two
  * sides comes from the math or from the logic.  Any x and y (the domain check of the states does not apply). */
