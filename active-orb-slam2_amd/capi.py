@@ -1999,7 +1999,7 @@ def debug_sincos_device(angles, device=0):
 
 
 WAVE_OPS_I = ("dpp_u32_B1", "dpp_u32_4E", "dpp_u32_141", "dpp_u32_140", "dpp_i32_B1", "dpp_i32_4E", "dpp_i32_141", "dpp_i32_140",
-              "row_sum", "sum", "max", "row_min", "min", "incl_scan", "block_excl_scan", "block_total")
+              "row_sum", "sum", "max", "row_min", "min", "incl_scan", "block_excl_scan", "block_total", "block_sum")
 WAVE_OPS_D = ("dpp_f64_B1", "dpp_f64_4E", "dpp_f64_141", "dpp_f64_140", "row_sum_f64", "readlane_0", "readlane_63")
 
 

@@ -26,7 +26,7 @@ __global__ void sincos_kernel(const float *a, int n, float *s, float *c)
 
 // Every primitive of wave_ops.h on one int and one double per thread: a workgroup of NT threads per case, kWaveOpsI ints and
 // kWaveOpsD doubles per thread (the order below is the layout capi.py names).
-constexpr int kWaveOpsI = 16, kWaveOpsD = 7;
+constexpr int kWaveOpsI = 17, kWaveOpsD = 7;
 template <int NT>
 __global__ __launch_bounds__(NT) void wave_ops_kernel(const int32_t *vi, const double *vd, int32_t *out_i, double *out_d)
 {
@@ -53,6 +53,10 @@ __global__ __launch_bounds__(NT) void wave_ops_kernel(const int32_t *vi, const d
     int total;
     oi[14] = block_excl_scan_i32<NT>(v, wsum, total);
     oi[15] = total;
+    // block_sum_i32 twice on the same LDS words (which the scan has just read): the sum of v, then that of 2 v; their difference is
+    // the sum of v only if no wave of the second call stored before every wave of the first had read
+    const uint32_t once = (uint32_t)block_sum_i32<NT>(v, wsum), twice = (uint32_t)block_sum_i32<NT>((int)(2u * (uint32_t)v), wsum);
+    oi[16] = (int32_t)(twice - once);
     od[0] = dpp_f64<0xB1>(d);
     od[1] = dpp_f64<0x4E>(d);
     od[2] = dpp_f64<0x141>(d);
@@ -95,180 +99,6 @@ int row_sums_scatter_run(const double *v, double *out, int32_t *owner)
     return AOS2_OK;
 }
 
-int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
-                 const uint8_t *status)
-{
-    if (!g || n < 0 || (n > 0 && (!obs1 || !obs2 || !x3D || !status)) || g->n_levels < 2 || g->n_levels > 8) {
-        set_error("bad argument (geometry, per-match arrays, 2..8 pyramid levels)");
-        return AOS2_ERR_ARG;
-    }
-    for (int k = 0; k < n; ++k)
-        if (obs1[k].octave < 0 || obs1[k].octave >= g->n_levels || obs2[k].octave < 0 || obs2[k].octave >= g->n_levels) {
-            set_error("match %d: octaves (%d, %d) outside the %d pyramid levels", k, obs1[k].octave, obs2[k].octave, g->n_levels);
-            return AOS2_ERR_ARG;
-        }
-    return AOS2_OK;
-}
-
-// mRansacMaxIts (SetRansacParameters, src/Sim3Solver.cc:125-135).  A quotient that is no int (NaN when epsilon > 1, infinite when
-// probability is 1 or epsilon^3 vanishes against 1) converts the way the x86 instruction does it for the reference: INT_MIN.
-static int32_t sim3_ransac_its(int n, double probability, int min_inliers, int max_iterations)
-{
-    const float epsilon = (float)min_inliers / n;
-    int nIterations;
-    if (min_inliers == n) nIterations = 1;
-    else {
-        const double v = ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3)));
-        nIterations = (v >= -2147483648.0 && v <= 2147483647.0) ? (int)v : INT32_MIN;
-    }
-    return std::max(1, std::min(nIterations, max_iterations));
-}
-
-int sim3_check(const aos2_sim3_problem_t *problems, const aos2_sim3_result_t *results, int n_problems, int32_t *its, uint8_t *run)
-{
-    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
-        set_error("bad argument (0..64 problems and their results)");
-        return AOS2_ERR_ARG;
-    }
-    for (int p = 0; p < n_problems; ++p) {
-        const aos2_sim3_problem_t &P = problems[p];
-        if (P.n < 0 || P.max_iterations < 1 || (P.n > 0 && (!P.X3Dc1 || !P.X3Dc2 || !P.max_err1 || !P.max_err2 || !results[p].inliers))) {
-            set_error("problem %d: bad argument (n >= 0, max_iterations >= 1, the per-correspondence arrays)", p);
-            return AOS2_ERR_ARG;
-        }
-        its[p] = sim3_ransac_its(P.n, P.probability, P.min_inliers, P.max_iterations);
-        run[p] = P.n >= P.min_inliers;
-        if (!run[p]) continue;
-        if (P.n < 3 || !P.draws) {
-            set_error("problem %d: %d correspondences to draw triples from, or no draws", p, P.n);
-            return AOS2_ERR_ARG;
-        }
-        for (int k = 0; k < P.max_iterations; ++k)
-            for (int i = 0; i < 3; ++i) {
-                const int32_t r = P.draws[3 * (size_t)k + i];
-                if (r < 0 || r > P.n - 1 - i) {
-                    set_error("problem %d: draw %d of iteration %d is %d, outside [0, %d]", p, i, k, r, P.n - 1 - i);
-                    return AOS2_ERR_ARG;
-                }
-            }
-    }
-    return AOS2_OK;
-}
-
-void sim3_result_clear(const aos2_sim3_problem_t &P, int32_t its, aos2_sim3_result_t &R)
-{
-    uint8_t *inl = R.inliers;
-    int32_t *counts = R.counts;
-    R = aos2_sim3_result_t{};
-    R.inliers = inl;
-    R.counts = counts;
-    R.ransac_max_its = its;
-    R.first_success = R.best_iteration = -1;
-    if (P.n > 0) memset(inl, 0, (size_t)P.n);
-    if (counts) std::fill(counts, counts + P.max_iterations, -1);
-}
-
-// a double on its way into an int the way the x86 conversion does it for the reference: INT_MIN where it does not fit
-static int32_t x86_int(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN; }
-
-int pnp_check(const aos2_pnp_problem_t *problems, const aos2_pnp_result_t *results, int n_problems, uint8_t *run)
-{
-    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
-        set_error("bad argument (0..64 problems and their results)");
-        return AOS2_ERR_ARG;
-    }
-    for (int p = 0; p < n_problems; ++p) {
-        const aos2_pnp_problem_t &P = problems[p];
-        if (P.n < 0 || P.min_set < 4 || P.min_set > 16 || P.first_iteration < 0 || P.first_iteration > P.n_iterations || P.best_inliers_in < 0 ||
-            (P.n > 0 && (!P.P3Dw || !P.P2D || !P.max_err || !results[p].inliers || !results[p].best)) ||
-            (P.best_inliers_in > 0 && (!P.best_in || P.n == 0))) {
-            set_error("problem %d: bad argument (n >= 0, 4 <= min_set <= 16, 0 <= first_iteration <= n_iterations, the per-correspondence "
-                      "arrays, best_in with best_inliers_in > 0)", p);
-            return AOS2_ERR_ARG;
-        }
-        run[p] = P.n >= P.min_inliers && P.first_iteration < P.n_iterations;
-        if (!run[p]) continue;
-        if (P.n < P.min_set || !P.draws) {
-            set_error("problem %d: %d correspondences to draw sets of %d from, or no draws", p, P.n, P.min_set);
-            return AOS2_ERR_ARG;
-        }
-        for (int k = P.first_iteration; k < P.n_iterations; ++k)
-            for (int i = 0; i < P.min_set; ++i) {
-                const int32_t r = P.draws[(size_t)P.min_set * k + i];
-                if (r < 0 || r > P.n - 1 - i) {
-                    set_error("problem %d: draw %d of iteration %d is %d, outside [0, %d]", p, i, k, r, P.n - 1 - i);
-                    return AOS2_ERR_ARG;
-                }
-            }
-    }
-    return AOS2_OK;
-}
-
-void pnp_result_clear(const aos2_pnp_problem_t &P, aos2_pnp_result_t &R)
-{
-    uint8_t *inl = R.inliers, *best = R.best;
-    int32_t *counts = R.counts;
-    R = aos2_pnp_result_t{};
-    R.inliers = inl;
-    R.best = best;
-    R.counts = counts;
-    R.returned_at = R.best_iteration = -1;
-    R.best_inliers = P.best_inliers_in;
-    if (P.n > 0) {
-        memset(inl, 0, (size_t)P.n);
-        if (P.best_inliers_in > 0) memmove(best, P.best_in, (size_t)P.n);
-        else memset(best, 0, (size_t)P.n);
-    }
-    if (counts) std::fill(counts, counts + P.n_iterations, -1);
-}
-
-int initializer_check(const aos2_initializer_problem_t *problems, const aos2_initializer_result_t *results, int n_problems)
-{
-    if (n_problems < 0 || n_problems > 64 || (n_problems > 0 && (!problems || !results))) {
-        set_error("bad argument (0..64 problems and their results)");
-        return AOS2_ERR_ARG;
-    }
-    for (int p = 0; p < n_problems; ++p) {
-        const aos2_initializer_problem_t &P = problems[p];
-        const aos2_initializer_result_t &R = results[p];
-        if (P.n_keys1 < 1 || P.n_keys2 < 1 || !P.keys1 || !P.keys2 || P.n_matches < 8 || !P.matches || P.iterations < 1 || !P.sets ||
-            !(P.sigma > 0) || !R.inliers_h || !R.inliers_f || !R.P3D || !R.triangulated) {
-            set_error("problem %d: bad argument (the keys of both frames, n_matches >= 8, iterations >= 1 with their sets, sigma > 0, the four "
-                      "result arrays)", p);
-            return AOS2_ERR_ARG;
-        }
-        for (int i = 0; i < P.n_matches; ++i) {
-            const int32_t a = P.matches[2 * i], b = P.matches[2 * i + 1];
-            if (a < 0 || a >= P.n_keys1 || b < 0 || b >= P.n_keys2) {
-                set_error("problem %d: match %d is (%d, %d), outside the frames' %d and %d keys", p, i, a, b, P.n_keys1, P.n_keys2);
-                return AOS2_ERR_ARG;
-            }
-        }
-        for (size_t k = 0; k < (size_t)P.iterations * 8; ++k)
-            if (P.sets[k] < 0 || P.sets[k] >= P.n_matches) {
-                set_error("problem %d: entry %d of set %d is %d, outside [0, %d)", p, (int)(k % 8), (int)(k / 8), P.sets[k], P.n_matches);
-                return AOS2_ERR_ARG;
-            }
-    }
-    return AOS2_OK;
-}
-
-void initializer_result_clear(const aos2_initializer_problem_t &P, aos2_initializer_result_t &R)
-{
-    uint8_t *ih = R.inliers_h, *jf = R.inliers_f, *tri = R.triangulated;
-    float *p3d = R.P3D;
-    R = aos2_initializer_result_t{};
-    R.inliers_h = ih;
-    R.inliers_f = jf;
-    R.P3D = p3d;
-    R.triangulated = tri;
-    R.best_iteration_h = R.best_iteration_f = -1;
-    memset(ih, 0, (size_t)P.n_matches);
-    memset(jf, 0, (size_t)P.n_matches);
-    memset(p3d, 0, 12 * (size_t)P.n_keys1);
-    memset(tri, 0, (size_t)P.n_keys1);
-}
-
 // FindHomography / FindFundamental (:124-223) of one problem, serially: score, matrix (18 floats for H: H21 | H12), flags -> iteration
 static int initializer_find_host(bool is_h, const aos2_initializer_problem_t &P, const InitPts &pts, float *score, float *model, uint8_t *flags)
 {
@@ -301,27 +131,6 @@ static int initializer_find_host(bool is_h, const aos2_initializer_problem_t &P,
 }  // namespace aos2
 
 extern "C" {
-
-int aos2_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
-                               int32_t *ransac_min_inliers, float *ransac_epsilon, int32_t *ransac_max_its)
-{
-    using namespace aos2;
-    if (n < 0 || !ransac_min_inliers || !ransac_epsilon || !ransac_max_its) {
-        set_error("bad argument (n >= 0, the three outputs)");
-        return AOS2_ERR_ARG;
-    }
-    int nMinInliers = x86_int((double)((float)n * epsilon));   // int = N * mRansacEpsilon, a float product (:134)
-    if (nMinInliers < min_inliers) nMinInliers = min_inliers;
-    if (nMinInliers < min_set) nMinInliers = min_set;
-    if (epsilon < (float)nMinInliers / n) epsilon = (float)nMinInliers / n;
-    int nIterations;
-    if (nMinInliers == n) nIterations = 1;
-    else nIterations = x86_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
-    *ransac_min_inliers = nMinInliers;
-    *ransac_epsilon = epsilon;
-    *ransac_max_its = std::max(1, std::min(nIterations, max_iterations));
-    return AOS2_OK;
-}
 
 int aos2_debug_pnp_set(int n, const int32_t *row, int min_set, int32_t *indices)
 {

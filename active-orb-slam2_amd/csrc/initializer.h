@@ -1,5 +1,5 @@
 // Initializer (src/Initializer.cc): Normalize, ComputeH21 / ComputeF21, CheckHomography / CheckFundamental, the model pick,
-// ReconstructF + DecomposeE, ReconstructH and CheckRT, ONE routine each for the device kernels (csrc/initializer_ransac.inc) and the
+// ReconstructF + DecomposeE, ReconstructH and CheckRT, ONE routine each for the device kernels (csrc/initializer_ransac.hip) and the
 // host tap (aos2_debug_initializer_host).  The translation units are built with -ffp-contract=off, so both run the same operation
 // sequence.  The OpenCV routines it stands for are DESIGN.md section 2 item 12 (parity unpinned): the float one-sided Jacobi of item
 // 8 at 16x9, 8x9 and 3x3 with the left factor's tail loop (normalisation, and the completion row of the wide case), the 3x3
@@ -632,7 +632,7 @@ __host__ __device__ inline int init_decide_h(const int32_t *nGood, const float *
     return -1;
 }
 
-// the argument checks of both entry points (csrc/debug_taps.hip) and the cleared result
+// the argument checks of both entry points (csrc/initializer_ransac.hip) and the cleared result
 int initializer_check(const aos2_initializer_problem_t *problems, const aos2_initializer_result_t *results, int n_problems);
 void initializer_result_clear(const aos2_initializer_problem_t &P, aos2_initializer_result_t &R);
 

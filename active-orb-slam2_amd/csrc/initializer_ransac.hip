@@ -1,13 +1,60 @@
 // Initializer::Initialize (src/Initializer.cc) for a batch of monocular sequences on the device (include/aos2.h:
-// aos2_initializer_initialize), part of matcher.hip's translation unit: the call sits behind SearchForInitialization of
-// Tracking::MonocularInitialization and uses the same handle.  The arithmetic is csrc/initializer.h, shared with the host tap.  The
-// minimal sets are an input, so every (problem, iteration, H or F) is one entry of a flat list.  Seven kernels follow each other on
-// the handle's stream with one upload in front and one fetch behind: prepare (Normalize), models, scores, pick (+ the winner's
-// flags), hypotheses, CheckRT, decide (+ the scatter of the chosen reconstruction).  None needs an atomic, a spin or another
-// workgroup's result of the same launch, and the host does not wait between them.
+// aos2_initializer_initialize): the call sits behind SearchForInitialization of Tracking::MonocularInitialization and uses the
+// matcher's handle.  The arithmetic is csrc/initializer.h, shared with the host tap.  The minimal sets are an input, so every
+// (problem, iteration, H or F) is one entry of a flat list.  Seven kernels follow each other on the handle's stream with one upload
+// in front and one fetch behind: prepare (Normalize), models, scores, pick (+ the winner's flags), hypotheses, CheckRT, decide (+ the
+// scatter of the chosen reconstruction).  None needs an atomic, a spin or another workgroup's result of the same launch, and the
+// host does not wait between them.
+#include "matcher_handle.h"
 #include "initializer.h"
+#include "solver_batch.h"
+#include "wave_ops.h"
 
 namespace aos2 {
+
+int initializer_check(const aos2_initializer_problem_t *problems, const aos2_initializer_result_t *results, int n_problems)
+{
+    if (int st = solver_check_batch(problems, results, n_problems)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_initializer_problem_t &P = problems[p];
+        const aos2_initializer_result_t &R = results[p];
+        if (P.n_keys1 < 1 || P.n_keys2 < 1 || !P.keys1 || !P.keys2 || P.n_matches < 8 || !P.matches || P.iterations < 1 || !P.sets ||
+            !(P.sigma > 0) || !R.inliers_h || !R.inliers_f || !R.P3D || !R.triangulated) {
+            set_error("problem %d: bad argument (the keys of both frames, n_matches >= 8, iterations >= 1 with their sets, sigma > 0, the four "
+                      "result arrays)", p);
+            return AOS2_ERR_ARG;
+        }
+        for (int i = 0; i < P.n_matches; ++i) {
+            const int32_t a = P.matches[2 * i], b = P.matches[2 * i + 1];
+            if (a < 0 || a >= P.n_keys1 || b < 0 || b >= P.n_keys2) {
+                set_error("problem %d: match %d is (%d, %d), outside the frames' %d and %d keys", p, i, a, b, P.n_keys1, P.n_keys2);
+                return AOS2_ERR_ARG;
+            }
+        }
+        for (size_t k = 0; k < (size_t)P.iterations * 8; ++k)
+            if (P.sets[k] < 0 || P.sets[k] >= P.n_matches) {
+                set_error("problem %d: entry %d of set %d is %d, outside [0, %d)", p, (int)(k % 8), (int)(k / 8), P.sets[k], P.n_matches);
+                return AOS2_ERR_ARG;
+            }
+    }
+    return AOS2_OK;
+}
+
+void initializer_result_clear(const aos2_initializer_problem_t &P, aos2_initializer_result_t &R)
+{
+    uint8_t *ih = R.inliers_h, *jf = R.inliers_f, *tri = R.triangulated;
+    float *p3d = R.P3D;
+    R = aos2_initializer_result_t{};
+    R.inliers_h = ih;
+    R.inliers_f = jf;
+    R.P3D = p3d;
+    R.triangulated = tri;
+    R.best_iteration_h = R.best_iteration_f = -1;
+    memset(ih, 0, (size_t)P.n_matches);
+    memset(jf, 0, (size_t)P.n_matches);
+    memset(p3d, 0, 12 * (size_t)P.n_keys1);
+    memset(tri, 0, (size_t)P.n_keys1);
+}
 
 // one problem; the pointers are regions of the handle's arena.  Entry k of the flat list of a problem: k < its is the homography of
 // iteration k, k >= its the fundamental matrix of iteration k - its.
@@ -141,9 +188,8 @@ __global__ __launch_bounds__(256) void init_pick_kernel(const InitProbDev *__res
         if (i < P.n_matches) P.inl[(size_t)model * P.n_matches + i] = in;
         count += __popcll(__ballot(in));
     }
-    if ((tid & 63) == 0) s_wave[tid >> 6] = count;
-    __syncthreads();
-    if (tid == 0) R.n_inl[model] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    const int n_inl = block_sum_waves_i32<256>(count, s_wave);
+    if (tid == 0) R.n_inl[model] = n_inl;
 }
 
 // one lane per problem: RH and the branch of :112-118, the 3x3 decompositions, the 4 or 8 (R, t)
@@ -168,16 +214,6 @@ __global__ __launch_bounds__(64) void init_hyps_kernel(const InitProbDev *__rest
         init_hyps_f(R.F21, P.cam, ws, P.hyp, P.hyp + 72);
         R.n_hypotheses = 4;
     }
-}
-
-// the sum of v over the 256 threads of a workgroup -> every thread
-__device__ inline int init_block_sum(int v, int32_t *s_wave)
-{
-    v = wave_sum_i32(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
 // CheckRT, one workgroup per (problem, hypothesis): every inlier match in parallel, nGood an integer sum, the parallax the order
@@ -210,7 +246,7 @@ __global__ __launch_bounds__(256) void init_checkrt_kernel(const InitProbDev *__
             ++good;
         }
     }
-    const int nGood = init_block_sum(good, s_wave);   // (its barriers also publish code / cosv to the workgroup)
+    const int nGood = block_sum_i32<256>(good, s_wave);   // (its barriers also publish code / cosv to the workgroup)
     float parallax = 0;
     if (nGood > 0) {
         const int want = (nGood - 1 < 50 ? nGood - 1 : 50) + 1;   // the smallest key with at least `want` keys <= it
@@ -220,7 +256,7 @@ __global__ __launch_bounds__(256) void init_checkrt_kernel(const InitProbDev *__
             int c = 0;
             for (int i = tid; i < n; i += 256)
                 if ((code[i] & INIT_RT_GOOD) && init_float_key(cosv[i]) <= cand) ++c;
-            if (init_block_sum(c, s_wave) < want) prefix |= 1u << bit;
+            if (block_sum_i32<256>(c, s_wave) < want) prefix |= 1u << bit;
         }
         parallax = init_parallax_deg(init_key_float(prefix));
     }
@@ -289,27 +325,24 @@ int aos2_initializer_initialize(aos2_matcher_t *m, const aos2_initializer_proble
     if (st || n_problems == 0) return st;
     if ((st = matcher_init(m))) return st;
     const int n_dev = n_problems;
-    std::vector<InitProbDev> dev((size_t)n_dev);
+    SolverBatch<InitProbDev, InitResDev> B;
     std::vector<int32_t> hyp_prob, next_same, last;
     Arena A{m};
-    for (int d = 0; d < n_dev; ++d) {   // (dev is sized: its fields stay where they are)
+    for (int d = 0; d < n_dev; ++d) {
         const aos2_initializer_problem_t &P = problems[d];
         initializer_result_clear(P, results[d]);
-        InitProbDev &D = dev[(size_t)d];
+        InitProbDev &D = B.add(d);
         D.n_keys1 = P.n_keys1;
         D.n_keys2 = P.n_keys2;
         D.n_matches = P.n_matches;
         D.its = P.iterations;
-        D.hyp_off = (int32_t)hyp_prob.size();
         D.min_triangulated = P.min_triangulated;
         D.sigma = P.sigma;
         D.min_parallax = P.min_parallax;
         D.cam = InitCam{P.fx, P.fy, P.cx, P.cy};
-        if (hyp_prob.size() + 2 * (size_t)P.iterations > (size_t)INT32_MAX / 32) {
-            set_error("more than 2^26 hypotheses in one call");
-            return AOS2_ERR_CAPACITY;
-        }
-        hyp_prob.insert(hyp_prob.end(), 2 * (size_t)P.iterations, d);
+        if ((st = flat_list_append(hyp_prob, 2 * (size_t)P.iterations, d, (size_t)INT32_MAX / 32, "more than 2^26 hypotheses in one call",
+                                   D.hyp_off)))
+            return st;
         const size_t n = (size_t)P.n_matches, its = (size_t)P.iterations;
         next_same.assign(n, -1);
         last.assign((size_t)P.n_keys1, -1);
@@ -334,37 +367,26 @@ int aos2_initializer_initialize(aos2_matcher_t *m, const aos2_initializer_proble
         A.out(D.tri, (size_t)P.n_keys1);
     }
     const int total = (int)hyp_prob.size();
-    const int32_t *d_hyp;
-    const InitProbDev *d_probs;
-    InitResDev *d_res;
-    A.in(d_hyp, hyp_prob.data(), 4 * (size_t)total);
-    A.hole(d_probs, sizeof(InitProbDev) * (size_t)n_dev);
-    A.out(d_res, sizeof(InitResDev) * (size_t)n_dev);
-    if ((st = A.alloc())) return st;
-    A.fill_hole(d_probs, dev.data(), sizeof(InitProbDev) * (size_t)n_dev);
-    if ((st = A.upload())) return st;
-    if ((st = A.begin())) return st;
-    hipLaunchKernelGGL(init_prepare_kernel, dim3((4 * n_dev + 63) / 64), dim3(64), 0, m->stream, d_probs, n_dev);
-    hipLaunchKernelGGL(init_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, d_probs, d_hyp, total);
-    hipLaunchKernelGGL(init_scores_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, d_probs, d_hyp, total);
-    hipLaunchKernelGGL(init_pick_kernel, dim3(n_dev, 2), dim3(256), 0, m->stream, d_probs, d_res);
-    hipLaunchKernelGGL(init_hyps_kernel, dim3((n_dev + 63) / 64), dim3(64), 0, m->stream, d_probs, d_res, n_dev);
-    hipLaunchKernelGGL(init_checkrt_kernel, dim3(n_dev, 8), dim3(256), 0, m->stream, d_probs, d_res);
-    hipLaunchKernelGGL(init_decide_kernel, dim3(n_dev), dim3(256), 0, m->stream, d_probs, d_res);
-    std::vector<InitResDev> res((size_t)n_dev);
-    A.fetch(res.data(), d_res, sizeof(InitResDev) * (size_t)n_dev);
+    if ((st = B.begin(A, hyp_prob))) return st;
+    hipLaunchKernelGGL(init_prepare_kernel, dim3((4 * n_dev + 63) / 64), dim3(64), 0, m->stream, B.d_probs, n_dev);
+    hipLaunchKernelGGL(init_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, B.d_probs, B.d_hyp, total);
+    hipLaunchKernelGGL(init_scores_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, B.d_probs, B.d_hyp, total);
+    hipLaunchKernelGGL(init_pick_kernel, dim3(n_dev, 2), dim3(256), 0, m->stream, B.d_probs, B.d_res);
+    hipLaunchKernelGGL(init_hyps_kernel, dim3((n_dev + 63) / 64), dim3(64), 0, m->stream, B.d_probs, B.d_res, n_dev);
+    hipLaunchKernelGGL(init_checkrt_kernel, dim3(n_dev, 8), dim3(256), 0, m->stream, B.d_probs, B.d_res);
+    hipLaunchKernelGGL(init_decide_kernel, dim3(n_dev), dim3(256), 0, m->stream, B.d_probs, B.d_res);
     for (int d = 0; d < n_dev; ++d) {
         const aos2_initializer_problem_t &P = problems[d];
         aos2_initializer_result_t &R = results[d];
-        A.fetch(R.inliers_h, dev[(size_t)d].inl, (size_t)P.n_matches);
-        A.fetch(R.inliers_f, dev[(size_t)d].inl + P.n_matches, (size_t)P.n_matches);
-        A.fetch(R.P3D, dev[(size_t)d].P3D, 12 * (size_t)P.n_keys1);
-        A.fetch(R.triangulated, dev[(size_t)d].tri, (size_t)P.n_keys1);
+        A.fetch(R.inliers_h, B.dev[d].inl, (size_t)P.n_matches);
+        A.fetch(R.inliers_f, B.dev[d].inl + P.n_matches, (size_t)P.n_matches);
+        A.fetch(R.P3D, B.dev[d].P3D, 12 * (size_t)P.n_keys1);
+        A.fetch(R.triangulated, B.dev[d].tri, (size_t)P.n_keys1);
     }
-    if ((st = A.end())) return st;
+    if ((st = B.end(A))) return st;
     for (int d = 0; d < n_dev; ++d) {
         aos2_initializer_result_t &R = results[d];
-        const InitResDev &S = res[(size_t)d];
+        const InitResDev &S = B.res[d];
         R.status = S.status;
         R.initialized = S.initialized;
         R.used_homography = S.used_homography;

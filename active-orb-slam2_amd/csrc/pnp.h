@@ -1,7 +1,7 @@
 // The arithmetic of PnPsolver (src/PnPsolver.cc): the index removal of iterate (:188-201), compute_pose (:477-525, EPnP: control
 // points, barycentric coordinates, M'M, the null space, three beta approximations, Gauss-Newton, R and t), CheckInliers (:308-339)
 // and the loop of iterate (:182-239) over inlier counts and memoised Refine() results.  ONE routine set for the device kernels
-// (csrc/pnp_ransac.inc) and the host tap (aos2_debug_pnp_host): the translation units are built with -ffp-contract=off, so both run
+// (csrc/pnp_ransac.hip) and the host tap (aos2_debug_pnp_host): the translation units are built with -ffp-contract=off, so both run
 // the same operation sequence.  Everything is double in index order; there is no libm call but sqrt.  The OpenCV routines the
 // reference calls (cvSVD, cvSolve / cvInvert with CV_SVD, cvMulTransposed) are restated as DESIGN.md section 2 item 11.
 //
@@ -684,7 +684,7 @@ struct PnpScan {
     }
 };
 
-// validates a batch; run[p] = 0 where nothing is launched (n < min_inliers, :173-177, or no iteration asked for).  csrc/debug_taps.hip.
+// validates a batch; run[p] = 0 where nothing is launched (n < min_inliers, :173-177, or no iteration asked for).  csrc/pnp_ransac.hip.
 int pnp_check(const aos2_pnp_problem_t *problems, const aos2_pnp_result_t *results, int n_problems, uint8_t *run);
 // the results of a problem before anything ran: nothing returned, the carried-in best stands
 void pnp_result_clear(const aos2_pnp_problem_t &P, aos2_pnp_result_t &R);

@@ -1,13 +1,60 @@
 // The RANSAC of PnPsolver (src/PnPsolver.cc) for a batch of relocalisation candidates on the device (include/aos2.h:
-// aos2_pnp_ransac), part of matcher.hip's translation unit: the call sits between SearchByBoW(KF, F) and PoseOptimization of
-// Tracking::Relocalization and uses the same handle.  The arithmetic is csrc/pnp.h, shared with the host tap.  The minimal sets are
-// an input, so every hypothesis of every problem is independent, and Refine() is a function of the best set alone: a hypothesis is
-// one entry of a flat list (problem, iteration), every iteration (and the carried-in best) owns a Refine() slot that works only when
-// the loop would reach it with a new best.  Five kernels follow each other on the handle's stream with one upload in front and one
-// fetch behind; none needs an atomic, a spin or another workgroup's result of the same launch.
+// aos2_pnp_ransac): the call sits between SearchByBoW(KF, F) and PoseOptimization of Tracking::Relocalization and uses the matcher's
+// handle.  The arithmetic is csrc/pnp.h, shared with the host tap.  The minimal sets are an input, so every hypothesis of every
+// problem is independent, and Refine() is a function of the best set alone: a hypothesis is one entry of a flat list (problem,
+// iteration), every iteration (and the carried-in best) owns a Refine() slot that works only when the loop would reach it with a new
+// best.  Five kernels follow each other on the handle's stream with one upload in front and one fetch behind; none needs an atomic, a
+// spin or another workgroup's result of the same launch.
+#include <algorithm>
+#include <cmath>
+
+#include "matcher_handle.h"
 #include "pnp.h"
+#include "solver_batch.h"
+#include "wave_ops.h"
 
 namespace aos2 {
+
+int pnp_check(const aos2_pnp_problem_t *problems, const aos2_pnp_result_t *results, int n_problems, uint8_t *run)
+{
+    if (int st = solver_check_batch(problems, results, n_problems)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_pnp_problem_t &P = problems[p];
+        if (P.n < 0 || P.min_set < 4 || P.min_set > 16 || P.first_iteration < 0 || P.first_iteration > P.n_iterations || P.best_inliers_in < 0 ||
+            (P.n > 0 && (!P.P3Dw || !P.P2D || !P.max_err || !results[p].inliers || !results[p].best)) ||
+            (P.best_inliers_in > 0 && (!P.best_in || P.n == 0))) {
+            set_error("problem %d: bad argument (n >= 0, 4 <= min_set <= 16, 0 <= first_iteration <= n_iterations, the per-correspondence "
+                      "arrays, best_in with best_inliers_in > 0)", p);
+            return AOS2_ERR_ARG;
+        }
+        run[p] = P.n >= P.min_inliers && P.first_iteration < P.n_iterations;
+        if (!run[p]) continue;
+        if (P.n < P.min_set || !P.draws) {
+            set_error("problem %d: %d correspondences to draw sets of %d from, or no draws", p, P.n, P.min_set);
+            return AOS2_ERR_ARG;
+        }
+        if (int st = solver_check_draws(p, P.draws, P.n, P.min_set, P.first_iteration, P.n_iterations)) return st;
+    }
+    return AOS2_OK;
+}
+
+void pnp_result_clear(const aos2_pnp_problem_t &P, aos2_pnp_result_t &R)
+{
+    uint8_t *inl = R.inliers, *best = R.best;
+    int32_t *counts = R.counts;
+    R = aos2_pnp_result_t{};
+    R.inliers = inl;
+    R.best = best;
+    R.counts = counts;
+    R.returned_at = R.best_iteration = -1;
+    R.best_inliers = P.best_inliers_in;
+    if (P.n > 0) {
+        memset(inl, 0, (size_t)P.n);
+        if (P.best_inliers_in > 0) memmove(best, P.best_in, (size_t)P.n);
+        else memset(best, 0, (size_t)P.n);
+    }
+    if (counts) std::fill(counts, counts + P.n_iterations, -1);
+}
 
 // one problem with something to run; the pointers are regions of the handle's arena.  Iterations are local here: 0 .. its-1 stand for
 // first .. n_iterations-1 of the solver; slot k < its is the Refine() of the set of local iteration k, slot its that of the carried set
@@ -103,10 +150,7 @@ __device__ inline int pnp_block_count(const double *Rt, const PnpCam &K, const P
         if (flags && i < n) flags[i] = in;
         count += __popcll(__ballot(in));
     }
-    __syncthreads();
-    if ((tid & 63) == 0) s_wave[tid >> 6] = count;
-    __syncthreads();
-    return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    return block_sum_waves_i32<256>(count, s_wave);
 }
 
 // Refine() (:260-305), one workgroup per slot; it leaves at once unless the slot is marked.  The set is the hypothesis' flags,
@@ -193,6 +237,27 @@ __global__ __launch_bounds__(256) void pnp_resolve_kernel(const PnpProbDev *__re
 
 extern "C" {
 
+int aos2_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                               int32_t *ransac_min_inliers, float *ransac_epsilon, int32_t *ransac_max_its)
+{
+    using namespace aos2;
+    if (n < 0 || !ransac_min_inliers || !ransac_epsilon || !ransac_max_its) {
+        set_error("bad argument (n >= 0, the three outputs)");
+        return AOS2_ERR_ARG;
+    }
+    int nMinInliers = x86_int((double)((float)n * epsilon));   // int = N * mRansacEpsilon, a float product (:134)
+    if (nMinInliers < min_inliers) nMinInliers = min_inliers;
+    if (nMinInliers < min_set) nMinInliers = min_set;
+    if (epsilon < (float)nMinInliers / n) epsilon = (float)nMinInliers / n;
+    int nIterations;
+    if (nMinInliers == n) nIterations = 1;
+    else nIterations = x86_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
+    *ransac_min_inliers = nMinInliers;
+    *ransac_epsilon = epsilon;
+    *ransac_max_its = std::max(1, std::min(nIterations, max_iterations));
+    return AOS2_OK;
+}
+
 int aos2_pnp_ransac(aos2_matcher_t *m, const aos2_pnp_problem_t *problems, aos2_pnp_result_t *results, int n_problems)
 {
     using namespace aos2;
@@ -205,85 +270,71 @@ int aos2_pnp_ransac(aos2_matcher_t *m, const aos2_pnp_problem_t *problems, aos2_
     if (st || n_problems == 0) return st;
     if ((st = matcher_init(m))) return st;
     // the problems with something to run, the flat list of their hypotheses and that of their Refine() slots
-    std::vector<PnpProbDev> dev;
-    std::vector<int> src;
+    SolverBatch<PnpProbDev, PnpResDev> B;
     std::vector<int32_t> hyp_prob, slot_prob;
-    dev.reserve((size_t)n_problems);
     for (int p = 0; p < n_problems; ++p) {
         pnp_result_clear(problems[p], results[p]);
         if (!run[p]) continue;
         const aos2_pnp_problem_t &P = problems[p];
-        PnpProbDev D = {};
+        const size_t its = (size_t)(P.n_iterations - P.first_iteration), limit = (size_t)INT32_MAX / 16;
+        const char *what = "more than 2^27 hypotheses in one call";
+        int32_t hyp_off, slot_off;
+        if ((st = flat_list_append(slot_prob, its + 1, B.n, limit, what, slot_off))) return st;
+        if ((st = flat_list_append(hyp_prob, its, B.n, limit, what, hyp_off))) return st;
+        PnpProbDev &D = B.add(p);
         D.n = P.n;
-        D.its = P.n_iterations - P.first_iteration;
+        D.its = (int32_t)its;
         D.first = P.first_iteration;
-        D.hyp_off = (int32_t)hyp_prob.size();
-        D.slot_off = (int32_t)slot_prob.size();
+        D.hyp_off = hyp_off;
+        D.slot_off = slot_off;
         D.min_inliers = P.min_inliers;
         D.min_set = P.min_set;
         D.best_inliers_in = P.best_inliers_in;
         D.K = PnpCam{P.fx, P.fy, P.cx, P.cy};
-        if (slot_prob.size() + (size_t)D.its + 1 > (size_t)INT32_MAX / 16) {
-            set_error("more than 2^27 hypotheses in one call");
-            return AOS2_ERR_CAPACITY;
-        }
-        hyp_prob.insert(hyp_prob.end(), (size_t)D.its, (int32_t)dev.size());
-        slot_prob.insert(slot_prob.end(), (size_t)D.its + 1, (int32_t)dev.size());
-        dev.push_back(D);
-        src.push_back(p);
     }
-    const int n_dev = (int)dev.size(), total = (int)hyp_prob.size(), slots = (int)slot_prob.size();
+    const int n_dev = B.n, total = (int)hyp_prob.size(), slots = (int)slot_prob.size();
     if (n_dev == 0) return AOS2_OK;
     Arena A{m};
-    for (int d = 0; d < n_dev; ++d) {   // (dev is sized: its fields stay where they are)
-        const aos2_pnp_problem_t &P = problems[src[d]];
-        const size_t n = (size_t)P.n, its = (size_t)dev[d].its;
-        A.in(dev[d].P3D, P.P3Dw, 12 * n);
-        A.in(dev[d].P2D, P.P2D, 8 * n);
-        A.in(dev[d].max_err, P.max_err, 4 * n);
-        A.in(dev[d].draws, P.draws + (size_t)P.min_set * P.first_iteration, 4 * (size_t)P.min_set * its);
-        A.in(dev[d].best_in, P.best_inliers_in > 0 ? P.best_in : (const uint8_t *)nullptr, n);   // (no source: zeros)
-        A.scratch(dev[d].slot_flags, its * n);
-        A.out(dev[d].counts, 4 * its);
-        A.out(dev[d].inliers, n);
-        A.out(dev[d].best, n);
+    for (int d = 0; d < n_dev; ++d) {
+        const aos2_pnp_problem_t &P = problems[B.src[d]];
+        PnpProbDev &D = B.dev[d];
+        const size_t n = (size_t)P.n, its = (size_t)D.its;
+        A.in(D.P3D, P.P3Dw, 12 * n);
+        A.in(D.P2D, P.P2D, 8 * n);
+        A.in(D.max_err, P.max_err, 4 * n);
+        A.in(D.draws, P.draws + (size_t)P.min_set * P.first_iteration, 4 * (size_t)P.min_set * its);
+        A.in(D.best_in, P.best_inliers_in > 0 ? P.best_in : (const uint8_t *)nullptr, n);   // (no source: zeros)
+        A.scratch(D.slot_flags, its * n);
+        A.out(D.counts, 4 * its);
+        A.out(D.inliers, n);
+        A.out(D.best, n);
     }
-    const int32_t *d_hyp, *d_slot;
-    const PnpProbDev *d_probs;
+    const int32_t *d_slot;
     double *d_models, *d_ref_models;
     int32_t *d_ref_counts;
     uint8_t *d_work;
-    PnpResDev *d_res;
-    A.in(d_hyp, hyp_prob.data(), 4 * (size_t)total);
     A.in(d_slot, slot_prob.data(), 4 * (size_t)slots);
-    A.hole(d_probs, sizeof(PnpProbDev) * (size_t)n_dev);
     A.scratch(d_models, 96 * (size_t)total);
     A.scratch(d_ref_models, 96 * (size_t)slots);
     A.scratch(d_ref_counts, 4 * (size_t)slots);
     A.scratch(d_work, (size_t)slots);
-    A.out(d_res, sizeof(PnpResDev) * (size_t)n_dev);
-    if ((st = A.alloc())) return st;
-    A.fill_hole(d_probs, dev.data(), sizeof(PnpProbDev) * (size_t)n_dev);
-    if ((st = A.upload())) return st;
-    if ((st = A.begin())) return st;
-    hipLaunchKernelGGL(pnp_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, d_probs, d_hyp, total, d_models);
-    hipLaunchKernelGGL(pnp_counts_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, d_probs, d_hyp, total, d_models);
-    hipLaunchKernelGGL(pnp_mark_kernel, dim3(1), dim3(64), 0, m->stream, d_probs, n_dev, d_work);
-    hipLaunchKernelGGL(pnp_refine_kernel, dim3(slots), dim3(256), 0, m->stream, d_probs, d_slot, d_work, d_models, d_ref_models, d_ref_counts);
-    hipLaunchKernelGGL(pnp_resolve_kernel, dim3(n_dev), dim3(256), 0, m->stream, d_probs, d_models, d_ref_models, d_ref_counts, d_res);
-    std::vector<PnpResDev> res((size_t)n_dev);
-    A.fetch(res.data(), d_res, sizeof(PnpResDev) * (size_t)n_dev);
+    if ((st = B.begin(A, hyp_prob))) return st;
+    hipLaunchKernelGGL(pnp_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, B.d_probs, B.d_hyp, total, d_models);
+    hipLaunchKernelGGL(pnp_counts_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, B.d_probs, B.d_hyp, total, d_models);
+    hipLaunchKernelGGL(pnp_mark_kernel, dim3(1), dim3(64), 0, m->stream, B.d_probs, n_dev, d_work);
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3(slots), dim3(256), 0, m->stream, B.d_probs, d_slot, d_work, d_models, d_ref_models, d_ref_counts);
+    hipLaunchKernelGGL(pnp_resolve_kernel, dim3(n_dev), dim3(256), 0, m->stream, B.d_probs, d_models, d_ref_models, d_ref_counts, B.d_res);
     for (int d = 0; d < n_dev; ++d) {
-        const aos2_pnp_problem_t &P = problems[src[d]];
-        aos2_pnp_result_t &R = results[src[d]];
-        if (R.counts) A.fetch(R.counts + P.first_iteration, dev[d].counts, 4 * (size_t)dev[d].its);
-        A.fetch(R.inliers, dev[d].inliers, (size_t)dev[d].n);
-        A.fetch(R.best, dev[d].best, (size_t)dev[d].n);
+        const aos2_pnp_problem_t &P = problems[B.src[d]];
+        aos2_pnp_result_t &R = results[B.src[d]];
+        if (R.counts) A.fetch(R.counts + P.first_iteration, B.dev[d].counts, 4 * (size_t)B.dev[d].its);
+        A.fetch(R.inliers, B.dev[d].inliers, (size_t)B.dev[d].n);
+        A.fetch(R.best, B.dev[d].best, (size_t)B.dev[d].n);
     }
-    if ((st = A.end())) return st;
+    if ((st = B.end(A))) return st;
     for (int d = 0; d < n_dev; ++d) {
-        aos2_pnp_result_t &R = results[src[d]];
-        const PnpResDev &S = res[d];
+        aos2_pnp_result_t &R = results[B.src[d]];
+        const PnpResDev &S = B.res[d];
         R.returned_at = S.returned_at;
         R.best_iteration = S.best_iteration;
         R.best_inliers = S.best_inliers;

@@ -1,6 +1,6 @@
 // The arithmetic of Sim3Solver (src/Sim3Solver.cc): ComputeCentroid (:215-224), ComputeSim3 (:226-337, Horn's closed form with
 // cv::eigen of the 4x4 and cv::Rodrigues), Project (:382-403), FromCameraToImage (:405-423) and the inlier test of :350-356.  ONE
-// routine for the device kernels (csrc/sim3_ransac.inc) and the host tap (aos2_debug_sim3_host): the translation units are built
+// routine for the device kernels (csrc/sim3_ransac.hip) and the host tap (aos2_debug_sim3_host): the translation units are built
 // with -ffp-contract=off, so both run the same operation sequence.  The OpenCV conventions it restates are DESIGN.md section 2
 // item 9:
 //   cv::reduce(SUM): float sums in column order; C / P.cols, vec = 2*ang*vec/norm(vec), (1.0/s)*R.t(): a scale by the double factor
@@ -19,7 +19,7 @@
 namespace aos2 {
 
 // validates a batch and computes mRansacMaxIts of each problem (SetRansacParameters, :125-135) -> its[n_problems]; run[p] = 0 where
-// n < min_inliers (:146-150).  csrc/debug_taps.hip.
+// n < min_inliers (:146-150).  csrc/sim3_ransac.hip.
 int sim3_check(const aos2_sim3_problem_t *problems, const aos2_sim3_result_t *results, int n_problems, int32_t *its, uint8_t *run);
 // the results of a problem nothing ran for
 void sim3_result_clear(const aos2_sim3_problem_t &P, int32_t its, aos2_sim3_result_t &R);

@@ -1,11 +1,60 @@
-// The RANSAC of Sim3Solver (src/Sim3Solver.cc) for a batch of loop candidates on the device (include/aos2.h: aos2_sim3_ransac), part
-// of matcher.hip's translation unit: the call sits between SearchByBoW(KF, KF) and SearchBySim3 of LoopClosing::ComputeSim3 and uses
-// the same handle.  The arithmetic is csrc/sim3.h, shared with the host tap.  The random triples are an input, so every hypothesis of
-// every problem is independent: a hypothesis is one entry of a flat list (problem, iteration), three kernels follow each other on the
-// handle's stream with one upload in front and one fetch behind.
+// The RANSAC of Sim3Solver (src/Sim3Solver.cc) for a batch of loop candidates on the device (include/aos2.h: aos2_sim3_ransac): the
+// call sits between SearchByBoW(KF, KF) and SearchBySim3 of LoopClosing::ComputeSim3 and uses the matcher's handle.  The arithmetic
+// is csrc/sim3.h, shared with the host tap.  The random triples are an input, so every hypothesis of every problem is independent: a
+// hypothesis is one entry of a flat list (problem, iteration), three kernels follow each other on the handle's stream with one upload
+// in front and one fetch behind.
+#include <algorithm>
+#include <cmath>
+
+#include "matcher_handle.h"
 #include "sim3.h"
+#include "solver_batch.h"
+#include "wave_ops.h"
 
 namespace aos2 {
+
+// mRansacMaxIts (SetRansacParameters, src/Sim3Solver.cc:125-135).  A quotient that is no int (NaN when epsilon > 1, infinite when
+// probability is 1 or epsilon^3 vanishes against 1) converts the way the x86 instruction does it for the reference: INT_MIN.
+static int32_t sim3_ransac_its(int n, double probability, int min_inliers, int max_iterations)
+{
+    const float epsilon = (float)min_inliers / n;
+    const int nIterations = min_inliers == n ? 1 : x86_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
+    return std::max(1, std::min(nIterations, max_iterations));
+}
+
+int sim3_check(const aos2_sim3_problem_t *problems, const aos2_sim3_result_t *results, int n_problems, int32_t *its, uint8_t *run)
+{
+    if (int st = solver_check_batch(problems, results, n_problems)) return st;
+    for (int p = 0; p < n_problems; ++p) {
+        const aos2_sim3_problem_t &P = problems[p];
+        if (P.n < 0 || P.max_iterations < 1 || (P.n > 0 && (!P.X3Dc1 || !P.X3Dc2 || !P.max_err1 || !P.max_err2 || !results[p].inliers))) {
+            set_error("problem %d: bad argument (n >= 0, max_iterations >= 1, the per-correspondence arrays)", p);
+            return AOS2_ERR_ARG;
+        }
+        its[p] = sim3_ransac_its(P.n, P.probability, P.min_inliers, P.max_iterations);
+        run[p] = P.n >= P.min_inliers;
+        if (!run[p]) continue;
+        if (P.n < 3 || !P.draws) {
+            set_error("problem %d: %d correspondences to draw triples from, or no draws", p, P.n);
+            return AOS2_ERR_ARG;
+        }
+        if (int st = solver_check_draws(p, P.draws, P.n, 3, 0, P.max_iterations)) return st;
+    }
+    return AOS2_OK;
+}
+
+void sim3_result_clear(const aos2_sim3_problem_t &P, int32_t its, aos2_sim3_result_t &R)
+{
+    uint8_t *inl = R.inliers;
+    int32_t *counts = R.counts;
+    R = aos2_sim3_result_t{};
+    R.inliers = inl;
+    R.counts = counts;
+    R.ransac_max_its = its;
+    R.first_success = R.best_iteration = -1;
+    if (P.n > 0) memset(inl, 0, (size_t)P.n);
+    if (counts) std::fill(counts, counts + P.max_iterations, -1);
+}
 
 // one problem with something to run; the pointers are regions of the handle's arena
 struct Sim3ProbDev {
@@ -135,70 +184,53 @@ int aos2_sim3_ransac(aos2_matcher_t *m, const aos2_sim3_problem_t *problems, aos
     if (st || n_problems == 0) return st;
     if ((st = matcher_init(m))) return st;
     // the problems with something to run, and the flat list of their hypotheses
-    std::vector<Sim3ProbDev> dev;
-    std::vector<int> src;
+    SolverBatch<Sim3ProbDev, Sim3ResDev> B;
     std::vector<int32_t> hyp_prob;
-    dev.reserve((size_t)n_problems);
     for (int p = 0; p < n_problems; ++p) {
         sim3_result_clear(problems[p], its[p], results[p]);
         if (!run[p]) continue;
         const aos2_sim3_problem_t &P = problems[p];
-        Sim3ProbDev D = {};
+        int32_t hyp_off;
+        if ((st = flat_list_append(hyp_prob, (size_t)its[p], B.n, INT32_MAX, "more than 2^31 hypotheses in one call", hyp_off))) return st;
+        Sim3ProbDev &D = B.add(p);
         D.n = P.n;
         D.its = its[p];
-        D.hyp_off = (int32_t)hyp_prob.size();
+        D.hyp_off = hyp_off;
         D.fix_scale = P.fix_scale;
         D.min_inliers = P.min_inliers;
         D.K1 = Sim3Cam{P.fx1, P.fy1, P.cx1, P.cy1};
         D.K2 = Sim3Cam{P.fx2, P.fy2, P.cx2, P.cy2};
-        if (hyp_prob.size() + (size_t)its[p] > (size_t)INT32_MAX) {
-            set_error("more than 2^31 hypotheses in one call");
-            return AOS2_ERR_CAPACITY;
-        }
-        hyp_prob.insert(hyp_prob.end(), (size_t)its[p], (int32_t)dev.size());
-        dev.push_back(D);
-        src.push_back(p);
     }
-    const int n_dev = (int)dev.size(), total = (int)hyp_prob.size();
+    const int n_dev = B.n, total = (int)hyp_prob.size();
     if (n_dev == 0) return AOS2_OK;
     Arena A{m};
-    for (int d = 0; d < n_dev; ++d) {   // (dev is sized: its fields stay where they are)
-        const aos2_sim3_problem_t &P = problems[src[d]];
+    for (int d = 0; d < n_dev; ++d) {
+        const aos2_sim3_problem_t &P = problems[B.src[d]];
+        Sim3ProbDev &D = B.dev[d];
         const size_t n = (size_t)P.n;
-        A.in(dev[d].X1, P.X3Dc1, 12 * n);
-        A.in(dev[d].X2, P.X3Dc2, 12 * n);
-        A.in(dev[d].e1, P.max_err1, 4 * n);
-        A.in(dev[d].e2, P.max_err2, 4 * n);
-        A.in(dev[d].draws, P.draws, 12 * (size_t)dev[d].its);
-        A.out(dev[d].counts, 4 * (size_t)dev[d].its);
-        A.out(dev[d].inliers, n);
+        A.in(D.X1, P.X3Dc1, 12 * n);
+        A.in(D.X2, P.X3Dc2, 12 * n);
+        A.in(D.e1, P.max_err1, 4 * n);
+        A.in(D.e2, P.max_err2, 4 * n);
+        A.in(D.draws, P.draws, 12 * (size_t)D.its);
+        A.out(D.counts, 4 * (size_t)D.its);
+        A.out(D.inliers, n);
     }
-    const int32_t *d_hyp;
-    const Sim3ProbDev *d_probs;
     float *d_models;
-    Sim3ResDev *d_res;
-    A.in(d_hyp, hyp_prob.data(), 4 * (size_t)total);
-    A.hole(d_probs, sizeof(Sim3ProbDev) * (size_t)n_dev);
     A.scratch(d_models, 96 * (size_t)total);
-    A.out(d_res, sizeof(Sim3ResDev) * (size_t)n_dev);
-    if ((st = A.alloc())) return st;
-    A.fill_hole(d_probs, dev.data(), sizeof(Sim3ProbDev) * (size_t)n_dev);
-    if ((st = A.upload())) return st;
-    if ((st = A.begin())) return st;
-    hipLaunchKernelGGL(sim3_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, d_probs, d_hyp, total, d_models);
-    hipLaunchKernelGGL(sim3_inliers_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, d_probs, d_hyp, total, d_models);
-    hipLaunchKernelGGL(sim3_resolve_kernel, dim3(n_dev), dim3(256), 0, m->stream, d_probs, d_res);
-    std::vector<Sim3ResDev> res((size_t)n_dev);
-    A.fetch(res.data(), d_res, sizeof(Sim3ResDev) * (size_t)n_dev);
+    if ((st = B.begin(A, hyp_prob))) return st;
+    hipLaunchKernelGGL(sim3_models_kernel, dim3((total + 63) / 64), dim3(64), 0, m->stream, B.d_probs, B.d_hyp, total, d_models);
+    hipLaunchKernelGGL(sim3_inliers_kernel, dim3((total + 3) / 4), dim3(256), 0, m->stream, B.d_probs, B.d_hyp, total, d_models);
+    hipLaunchKernelGGL(sim3_resolve_kernel, dim3(n_dev), dim3(256), 0, m->stream, B.d_probs, B.d_res);
     for (int d = 0; d < n_dev; ++d) {
-        aos2_sim3_result_t &R = results[src[d]];
-        if (R.counts) A.fetch(R.counts, dev[d].counts, 4 * (size_t)dev[d].its);
-        A.fetch(R.inliers, dev[d].inliers, (size_t)dev[d].n);
+        aos2_sim3_result_t &R = results[B.src[d]];
+        if (R.counts) A.fetch(R.counts, B.dev[d].counts, 4 * (size_t)B.dev[d].its);
+        A.fetch(R.inliers, B.dev[d].inliers, (size_t)B.dev[d].n);
     }
-    if ((st = A.end())) return st;
+    if ((st = B.end(A))) return st;
     for (int d = 0; d < n_dev; ++d) {
-        aos2_sim3_result_t &R = results[src[d]];
-        const Sim3ResDev &S = res[d];
+        aos2_sim3_result_t &R = results[B.src[d]];
+        const Sim3ResDev &S = B.res[d];
         R.first_success = S.first_success;
         R.best_iteration = S.best_iteration;
         R.best_inliers = S.best_inliers;

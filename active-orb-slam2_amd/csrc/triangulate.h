@@ -31,7 +31,7 @@ struct TriObs {
     int32_t octave;
 };
 
-// the argument checks of the host-pointer form and the host tap (csrc/debug_taps.hip): everything the routine indexes with
+// the argument checks of the host-pointer form and the host tap (csrc/matcher.hip): everything the routine indexes with
 int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
                  const uint8_t *status);
 

@@ -258,4 +258,26 @@ __device__ __forceinline__ int block_excl_scan_i32(int v, int32_t *wsum, int &to
     return excl;
 }
 
+// Sum of one int per WAVE (wave_value: wave-uniform) over a workgroup of NT threads (all active; part: NT / 64 ints of LDS), the
+// result in every thread.  Two barriers inside: one in front of the stores, so `part` may have been read until the call (by the
+// previous call with the same part included), one behind them.
+template <int NT>
+__device__ __forceinline__ int block_sum_waves_i32(int wave_value, int32_t *part)
+{
+    static_assert(NT % 64 == 0, "whole waves");
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = wave_value;
+    __syncthreads();
+    int s = part[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w) s += part[w];
+    return s;
+}
+// Sum of one int per thread over a workgroup of NT threads: the same, with the same two barriers, on the waves' sums.
+template <int NT>
+__device__ __forceinline__ int block_sum_i32(int v, int32_t *part)
+{
+    return block_sum_waves_i32<NT>(wave_sum_i32(v), part);
+}
+
 }  // namespace aos2

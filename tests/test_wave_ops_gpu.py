@@ -135,3 +135,16 @@ def test_block_excl_scan(runs, nt):
     assert (got["block_excl_scan"][:n] == incl - v).all()
     assert (got["block_total"][:n] == incl[:, -1:]).all()   # in every thread
     assert got["block_excl_scan"][2 + 8 * (nt // 64), nt - 1] == 0 and got["block_total"][2 + 8 * (nt // 64), 0] == 5   # only the last thread
+
+
+@pytest.mark.parametrize("nt", NTS)
+def test_block_sum(runs, nt):
+    """block_sum_i32 twice in one kernel on the same LDS words: the tap returns sum(2 v) - sum(v), which is numpy's sum in
+    every thread only if both calls are right -- the second one's stores wait behind the call's leading barrier for every
+    wave's reads of the first"""
+    r = runs[nt]
+    n, got = r["n_int"], r["got"]
+    want = np.sum(r["v"][:n], axis=1, dtype=np.int64)
+    assert 2 * want.max() < 2 ** 31
+    assert (got["block_sum"][:n] == want[:, None]).all()   # in every thread
+    assert got["block_sum"][2 + 8 * (nt // 64), 0] == 5      # only the last thread
