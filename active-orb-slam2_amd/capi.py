@@ -170,6 +170,13 @@ def lib():
         L.aos2_local_map_last_culling_device_ms.argtypes = [vp]
         L.aos2_local_map_last_culling_device_ms.restype = C.c_float
         L.aos2_debug_keyframe_culling_host.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
+        L.aos2_local_map_get_culling_view.argtypes = [vp, vp, vp]
+        L.aos2_local_map_apply.argtypes = [vp, vp]
+        L.aos2_debug_local_map_apply_host.argtypes = [vp, vp]
+        L.aos2_local_map_last_apply.argtypes = [vp, vp, vp, vp]
+        L.aos2_local_map_last_apply_bytes.argtypes = [vp]
+        L.aos2_local_map_last_apply_bytes.restype = C.c_int64
+        L.aos2_local_map_debug_apply_tile.argtypes = [vp, ci]
         L.aos2_debug_octree_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         L.aos2_debug_sincos_host.argtypes = [cf, C.POINTER(cf), C.POINTER(cf)]
         L.aos2_debug_extractor_plan.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
@@ -1269,6 +1276,43 @@ def _kf_culling_view(v, keep):
     return s
 
 
+_LMD_I32 = ("point_row", "point_nobs", "obs_off", "obs_kf", "kf_mp_row", "kf_mp_off", "kf_mp", "kf_link_row", "kf_best", "kf_child_off",
+            "kf_child", "kf_parent")
+_LMD_U8 = ("point_bad", "kf_bad")
+
+
+class _LocalMapDelta(C.Structure):
+    """aos2_local_map_delta_t"""
+    _fields_ = [("n_points", C.c_int32), ("n_keyframes", C.c_int32),
+                ("n_point_rows", C.c_int32), ("point_row", C.c_void_p), ("point_bad", C.c_void_p), ("point_nobs", C.c_void_p),
+                ("obs_off", C.c_void_p), ("obs_kf", C.c_void_p),
+                ("n_kf_mp_rows", C.c_int32), ("kf_mp_row", C.c_void_p), ("kf_mp_off", C.c_void_p), ("kf_mp", C.c_void_p),
+                ("n_kf_link_rows", C.c_int32), ("kf_link_row", C.c_void_p), ("kf_bad", C.c_void_p), ("kf_best", C.c_void_p),
+                ("kf_child_off", C.c_void_p), ("kf_child", C.c_void_p), ("kf_parent", C.c_void_p), ("view", C.c_void_p)]
+
+
+def _local_map_delta(d, keep):
+    """a delta dict (the fields of aos2_local_map_delta_t; an array may be None = NULL, `view` a view dict or None; the three row
+    counts default to the lengths of their row lists) -> the struct; `keep` holds the arrays and the view struct"""
+    s = _LocalMapDelta()
+    s.n_points, s.n_keyframes = int(d["n_points"]), int(d["n_keyframes"])
+    for k in _LMD_I32 + _LMD_U8:
+        a = d.get(k)
+        if a is None:
+            setattr(s, k, None)
+            continue
+        a = np.ascontiguousarray(a, np.uint8 if k in _LMD_U8 else np.int32).reshape(-1)
+        keep.append(a)
+        setattr(s, k, a.ctypes.data if a.size else keep[0].ctypes.data)   # (an empty array is not NULL)
+    for n, rows in (("n_point_rows", "point_row"), ("n_kf_mp_rows", "kf_mp_row"), ("n_kf_link_rows", "kf_link_row")):
+        setattr(s, n, int(d[n]) if n in d else (0 if d.get(rows) is None else len(d[rows])))
+    if d.get("view") is not None:
+        v = _kf_culling_view(d["view"], keep)
+        keep.append(v)
+        s.view = C.addressof(v)
+    return s
+
+
 def _kf_culling_call(fn, first, monocular, cand, bad_cap):
     """the arguments that aos2_local_map_keyframe_culling and its host tap share -> dict(status uint8 [n], n_mps, n_redundant int32
     [n], n_bad_points int, bad_points int32 [bad_cap + 1]: one element more than the call may write, preset to -7)"""
@@ -1325,6 +1369,47 @@ class LocalMap:
         for k, off in (("obs_kf", "obs_off"), ("kf_mp", "kf_mp_off"), ("kf_child", "kf_child_off")):
             g[k] = arr(getattr(s, k), int(g[off][-1]), np.int32)
         return g
+
+    def view(self):
+        """the handle's culling view as a view dict (copies, parallel to graph()), None if it holds none"""
+        s, v = _LocalMapGraph(), _KfCullingView()
+        _check(self.L.aos2_local_map_get(self.h, C.byref(s)))
+        has = C.c_int32(0)
+        _check(self.L.aos2_local_map_get_culling_view(self.h, C.byref(v), C.byref(has)))
+        if not has.value:
+            return None
+        nk = s.n_keyframes
+        n_obs = int(np.ctypeslib.as_array(C.cast(s.obs_off, C.POINTER(C.c_int32)), (s.n_points + 1,))[-1])
+        n_mp = int(np.ctypeslib.as_array(C.cast(s.kf_mp_off, C.POINTER(C.c_int32)), (nk + 1,))[-1])
+        lens = dict(obs_idx=n_obs, kf_octave=n_mp, kf_depth=n_mp, kf_stereo=n_mp, kf_th_depth=nk, kf_flags=nk)
+        out = {}
+        for k, dt in _KFC_FIELDS:
+            n, nbytes = lens[k], lens[k] * np.dtype(dt).itemsize
+            out[k] = np.frombuffer(C.string_at(getattr(v, k), nbytes), dt).copy() if n else np.zeros(0, dt)
+        return out
+
+    def apply(self, delta, ok=(AOS2_OK,)):
+        """aos2_local_map_apply: a delta is a dict with the fields of aos2_local_map_delta_t (`view`: a view dict or None); `ok` as in
+        set()"""
+        keep = [np.zeros(1, np.int32)]
+        s = _local_map_delta(delta, keep)
+        return _check(self.L.aos2_local_map_apply(self.h, C.byref(s)), ok)
+
+    def apply_host(self, delta, ok=(AOS2_OK,)):
+        """aos2_debug_local_map_apply_host: the rebuild forced onto the host, the device copy marked dirty"""
+        keep = [np.zeros(1, np.int32)]
+        s = _local_map_delta(delta, keep)
+        return _check(self.L.aos2_debug_local_map_apply_host(self.h, C.byref(s)), ok)
+
+    def last_apply(self):
+        """aos2_local_map_last_apply -> dict(path 0 host / 1 device, reallocated, device_ms, bytes uploaded)"""
+        path, re, ms = C.c_int32(-1), C.c_int32(0), C.c_float(-1)
+        _check(self.L.aos2_local_map_last_apply(self.h, C.byref(path), C.byref(re), C.byref(ms)))
+        return dict(path=path.value, reallocated=re.value, device_ms=float(ms.value),
+                    bytes=int(self.L.aos2_local_map_last_apply_bytes(self.h)))
+
+    def debug_apply_tile(self, rows=0):
+        _check(self.L.aos2_local_map_debug_apply_tile(self.h, int(rows)))
 
     def update(self, frames, d_local, local_cap, d_n_local, d_local_kfs, kf_cap, d_n_local_kfs, d_ref_kf):
         """aos2_frames_update_local_map: device addresses (ints); enqueued on the batch's stream"""

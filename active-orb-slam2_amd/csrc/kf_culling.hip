@@ -127,6 +127,7 @@ int upload_view(aos2_local_map *h)
 {
     KfcState &K = h->kfc;
     if (!K.dirty) return AOS2_OK;
+    if (int st = local_map_refresh_host(h)) return st;   // (the host copy is what goes up)
     KfcGraph V = {};
     Regions<6> R;
     R.add(V.obs_idx, K.obs_idx.size()); R.add(V.kf_octave, K.kf_octave.size()); R.add(V.kf_depth, K.kf_depth.size());
@@ -215,9 +216,9 @@ int aos2_local_map_set_culling_view(aos2_local_map_t *h, const aos2_kf_culling_v
         return AOS2_ERR_ARG;
     }
     aos2_local_map_graph_t g;
-    aos2_local_map_get(h, &g);
+    if (int st = aos2_local_map_get(h, &g)) return st;   // (after a rebuild on the device: the download of the host copy)
     if (int st = kf_culling_check_view(&g, view)) return st;
-    const size_t n_obs = h->obs_kf.size(), n_mp = h->kf_mp.size(), nk = (size_t)h->n_kfs;
+    const size_t n_obs = (size_t)h->n_obs, n_mp = (size_t)h->n_mp, nk = (size_t)h->n_kfs;
     KfcState &K = h->kfc;
     auto take = [](auto &v, const auto *p, size_t n) {
         if (n) v.assign(p, p + n);
@@ -260,7 +261,7 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
     }
     int st;
     if ((st = kf_culling_check_call(h->n_kfs, n_cand, cand, status, n_mps, n_redundant, bad_points, bad_cap, n_bad_points))) return st;
-    const size_t np = (size_t)h->n_points, n_obs = h->obs_kf.size(), nc = (size_t)n_cand;
+    const size_t np = (size_t)h->n_points, n_obs = (size_t)h->n_obs, nc = (size_t)n_cand;
     // the overlay and the call's block, in the handle's scratch
     KfcOverlay X;
     KfcCall C = {};
@@ -332,6 +333,23 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
     *n_bad_points = nb;
     AOS2_HIP_CHECK(hipEventRecord(K.ev1, q));
     K.timed = true;
+    return AOS2_OK;
+}
+
+int aos2_local_map_get_culling_view(const aos2_local_map_t *ch, aos2_kf_culling_view_t *view, int32_t *has_view)
+{
+    if (!ch || !view) {
+        set_error("bad argument");
+        return AOS2_ERR_ARG;
+    }
+    aos2_local_map *h = const_cast<aos2_local_map *>(ch);
+    *view = aos2_kf_culling_view_t{};
+    if (has_view) *has_view = h->kfc.has_view ? 1 : 0;
+    if (!h->kfc.has_view) return AOS2_OK;
+    if (int st = local_map_refresh_host(h)) return st;
+    const KfcState &K = h->kfc;
+    view->obs_idx = K.obs_idx.data(); view->kf_octave = K.kf_octave.data(); view->kf_depth = K.kf_depth.data();
+    view->kf_stereo = K.kf_stereo.data(); view->kf_th_depth = K.kf_th_depth.data(); view->kf_flags = K.kf_flags.data();
     return AOS2_OK;
 }
 

@@ -73,11 +73,37 @@ struct aos2_local_map {
     int last_groups = 0;
     bool has_graph = false;   // aos2_local_map_set has been called
     aos2::KfcState kfc;
+    // aos2_local_map_apply (csrc/local_map_apply.hip).  Always current on the host, each kept in O(delta): the counts above and
+    // max_features, the entries of the three CSR arrays, and the length of every row (row_feat is Frame::N of each keyframe, the
+    // bound of obs_idx).  The vectors above and the view's are the MIRROR: after a rebuild on the device they are stale until
+    // local_map_refresh_host downloads the block.
+    int64_t n_obs = 0, n_mp = 0, n_child = 0;
+    std::vector<int32_t> row_obs, row_feat, row_child;
+    bool host_stale = false;
+    aos2::DevBuf<uint8_t> d_spare;          // the block the next rebuild writes; d_graph holds G (and V after a rebuild)
+    size_t block_bytes = 0;                 // of the rebuilt block in d_graph, the span one download copies
+    aos2::DevBuf<uint8_t> d_delta;
+    aos2::PinnedBuf<uint8_t> delta_stage;
+    int apply_tile = 0;                     // rows one workgroup scans, 0 = the default
+    int last_apply_path = -1, last_apply_realloc = 0;
+    hipEvent_t ap_ev0 = nullptr, ap_ev1 = nullptr;
+    bool apply_timed = false;
+    int64_t last_apply_bytes = 0;           // uploaded by the last device rebuild
 };
 
 namespace aos2 {
 
 // the handle's graph on the device if it is not there yet (csrc/local_map.hip)
 int local_map_upload(aos2_local_map *h);
+
+// csrc/local_map_apply.hip
+// The checks of aos2_local_map_apply against the handle's counts, O(delta): AOS2_OK or AOS2_ERR_ARG with the error text set.
+int local_map_apply_check(const aos2_local_map *h, const aos2_local_map_delta_t *d);
+// The rebuild written serially on the handle's host vectors (the mirror must be current); the delta has passed the check.
+void local_map_apply_host(aos2_local_map *h, const aos2_local_map_delta_t *d);
+// the row lengths and entry counts from the host vectors (after aos2_local_map_set)
+void local_map_recount(aos2_local_map *h);
+// the mirror from the device block if it is stale; AOS2_OK or AOS2_ERR_HIP
+int local_map_refresh_host(aos2_local_map *h);
 
 }  // namespace aos2

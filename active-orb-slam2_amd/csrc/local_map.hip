@@ -337,6 +337,7 @@ namespace {
 int upload(aos2_local_map *h)
 {
     if (!h->dirty) return AOS2_OK;
+    if (int st = local_map_refresh_host(h)) return st;   // (the host copy is what goes up)
     LmGraphDev G = {};
     G.n_points = h->n_points;
     G.n_kfs = h->n_kfs;
@@ -387,12 +388,17 @@ int aos2_local_map_create(int device, aos2_local_map_t **out)
 void aos2_local_map_destroy(aos2_local_map_t *h)
 {
     if (!h) return;
-    if (h->d_graph.p || h->d_scratch.p || h->stream) {
+    if (h->d_graph.p || h->d_scratch.p || h->stream || h->d_spare.p || h->delta_stage.p) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
         h->d_graph.release();
         h->d_scratch.release();
         h->d_io.release();
+        h->d_spare.release();
+        h->d_delta.release();
+        h->delta_stage.release();
+        if (h->ap_ev0) (void)hipEventDestroy(h->ap_ev0);
+        if (h->ap_ev1) (void)hipEventDestroy(h->ap_ev1);
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;
@@ -440,17 +446,21 @@ int aos2_local_map_set(aos2_local_map_t *h, const aos2_local_map_graph_t *g)
     for (int k = 0; k < nk; ++k) std::sort(h->kf_child.begin() + h->kf_child_off[k], h->kf_child.begin() + h->kf_child_off[k + 1]);
     h->dirty = true;
     h->has_graph = true;
+    h->host_stale = false;   // (the mirror is the graph again)
+    local_map_recount(h);
     h->kfc.drop_view();   // (its arrays no longer line up with the graph)
     return upload(h);
 }
 
-int aos2_local_map_get(const aos2_local_map_t *h, aos2_local_map_graph_t *g)
+int aos2_local_map_get(const aos2_local_map_t *ch, aos2_local_map_graph_t *g)
 {
-    if (!h) {
+    if (!ch) {
         set_error("bad argument");
         return AOS2_ERR_ARG;
     }
+    aos2_local_map *h = const_cast<aos2_local_map *>(ch);   // (the graph is not changed: the host mirror of it may be refreshed)
     if (g) {
+        if (int st = local_map_refresh_host(h)) return st;
         g->n_points = h->n_points;
         g->n_keyframes = h->n_kfs;
         g->point_bad = h->point_bad.data(); g->point_nobs = h->point_nobs.data();

@@ -10,7 +10,8 @@
 // -- after the erasures of every keyframe culled before it -- and pKF->SetBadFlag() is then called in candidate order for the
 // redundant ones (with mbNotErase set it only marks mbToBeErased, as in the reference): the erasure from the observations, the
 // points that go bad, the covisibility graph and the spanning tree are updated by the reference's own code, unchanged.  The
-// snapshot is NOT updated: re-take it after the call, as after every other map change.  A keyframe of
+// snapshot is NOT updated: name the keyframes that went bad (and what their erasure touched) in the LocalMapSnapshot::Apply that ends
+// the pass, as after every other map change (host/LocalMap.h).  A keyframe of
 // GetVectorCovisibleKeyFrames() that the snapshot does not know (added after it was taken) is left out of the call, like
 // aos2::UpdateLocalMap leaves one out.  Include AFTER the headers that declare Map, KeyFrame and MapPoint (the reference's, or
 // tests/cpp/refstub/kf_culling_stub.h).
@@ -42,8 +43,19 @@ struct KeyFrameEraseFlags : KF {
 // aos2_kf_culling_view_t gathered by LocalMapSnapshot's walk
 class CullingView {
 public:
+    static constexpr bool kGathers = true;
     template <class KF>
     void KeyFrame(KF *pKF)
+    {
+        DeltaMatches(pKF);
+        DeltaLinks(pKF);
+    }
+    void Observation(size_t idx) { obs_idx.push_back((int32_t)idx); }
+    // the hooks of LocalMapSnapshot::Apply: the same gathers for the rows of a delta -- what is parallel to a match row, and the two
+    // scalars of a link row -- and the delta pointed at them
+    void DeltaObservation(size_t idx) { Observation(idx); }
+    template <class KF>
+    void DeltaMatches(KF *pKF)
     {
         const size_t n = pKF->GetMapPointMatches().size();
         for (size_t i = 0; i < n; ++i) {
@@ -51,10 +63,19 @@ public:
             kf_depth.push_back(pKF->mvDepth[i]);
             kf_stereo.push_back(pKF->mvuRight[i] >= 0 ? 1 : 0);
         }
+    }
+    template <class KF>
+    void DeltaLinks(KF *pKF)
+    {
         kf_th_depth.push_back(pKF->mThDepth);
         kf_flags.push_back((uint8_t)((pKF->mnId == 0 ? 1 : 0) | (KeyFrameEraseFlags<KF>::NotErase(pKF) ? 2 : 0)));
     }
-    void Observation(size_t idx) { obs_idx.push_back((int32_t)idx); }
+    void PointDelta(aos2_local_map_delta_t &d)
+    {
+        mView.obs_idx = obs_idx.data(); mView.kf_octave = kf_octave.data(); mView.kf_depth = kf_depth.data();
+        mView.kf_stereo = kf_stereo.data(); mView.kf_th_depth = kf_th_depth.data(); mView.kf_flags = kf_flags.data();
+        d.view = &mView;
+    }
     void Set(aos2_local_map_t *h)
     {
         aos2_kf_culling_view_t v;
@@ -68,6 +89,7 @@ private:
     std::vector<int8_t> kf_octave;
     std::vector<float> kf_depth, kf_th_depth;
     std::vector<uint8_t> kf_stereo, kf_flags;
+    aos2_kf_culling_view_t mView = {};
 };
 
 // The loop :644-699.  vStatus (may be NULL): AOS2_KFC_* of every keyframe of GetVectorCovisibleKeyFrames(), in its order

@@ -1394,10 +1394,11 @@ void aos2_local_map_destroy(aos2_local_map_t *m);
  * count, offsets that do not start at 0 or that decrease, a row out of range (other than the -1 the members allow) and a
  * keyframe listed twice among one point's observations.  An empty map (0 keyframes, 0 points) is valid.  A graph that passed the
  * check is the handle's from then on, also when the upload fails (AOS2_ERR_NO_DEVICE, AOS2_ERR_HIP): the next
- * aos2_frames_update_local_map uploads it.  The whole graph is sent every time: adding one keyframe without re-sending the
- * rest (an incremental update) is out of scope. */
+ * aos2_frames_update_local_map uploads it.  The whole graph is sent every time; aos2_local_map_apply (below) changes a resident
+ * graph by one keyframe's worth of rows without re-sending the rest. */
 int aos2_local_map_set(aos2_local_map_t *m, const aos2_local_map_graph_t *g);
-/* the handle's snapshot: its sizes and, in *g (may be NULL), its arrays (the handle's own copies, valid until the next set) */
+/* the handle's snapshot: its sizes and, in *g (may be NULL), its arrays (the handle's own copies, valid until the next set or
+ * apply; behind an aos2_local_map_apply that ran on the device the first call downloads them, AOS2_ERR_HIP if that fails) */
 int aos2_local_map_get(const aos2_local_map_t *m, aos2_local_map_graph_t *g);
 
 /* void Tracking::UpdateLocalMap() = UpdateLocalKeyFrames() (:1411-1519) + UpdateLocalPoints() (:1385-1408) for every frame of
@@ -1450,7 +1451,7 @@ int aos2_local_map_last_groups(const aos2_local_map_t *m);
  * because the loop is serial in its effects -- what KeyFrame::SetBadFlag (src/KeyFrame.cc:514-532) of every culled keyframe does
  * to the candidates behind it: MapPoint::EraseObservation (src/MapPoint.cc:144-170) on each of its points, and the points that
  * fall to nObs <= 2 and go bad.  Integer graph work.  The resident graph is READ, never written: the caller applies the verdicts
- * to its own map (SetBadFlag in candidate order) and re-takes the snapshot, as after every other map change.
+ * to its own map (SetBadFlag in candidate order) and sends the result as a delta (aos2_local_map_apply), as after every other map change.
  *
  * Followed literally: the far-point gate `mvDepth[i] > mThDepth || mvDepth[i] < 0` as float compares
  * when not monocular; Observations() > 3 on nObs (a stereo observation counts twice); the observer count over observation
@@ -1501,6 +1502,67 @@ int aos2_local_map_last_culling_rounds(const aos2_local_map_t *m);
 /* device time of the last aos2_local_map_keyframe_culling call between two events on the handle's stream, from the upload of the
  * candidates to the last copy back (the host's waits between enqueues included); -1 if there was none */
 float aos2_local_map_last_culling_device_ms(aos2_local_map_t *m);
+/* the handle's view in *view (the handle's own copies, parallel to the arrays of aos2_local_map_get and valid as long as they are);
+ * *has_view (may be NULL) = whether the handle holds one, every pointer NULL if not */
+int aos2_local_map_get_culling_view(const aos2_local_map_t *m, aos2_kf_culling_view_t *view, int32_t *has_view);
+
+/* ------------------------------------------------------------------------------------------
+ * One keyframe's changes applied to the resident graph (csrc/local_map_apply.hip): what one pass of
+ * LocalMapping::Run (src/LocalMapping.cc:49-107) does to the map -- a keyframe inserted, points created, culled and fused,
+ * covisibility lists and the spanning tree re-linked, keyframes culled -- touches a few hundred rows of 10^5.  The delta names
+ * those rows and carries their new content; the new arrays are built ON THE DEVICE from the resident graph and the delta, and
+ * the culling view moves with the graph.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    /* counts AFTER the delta; rows only ever get appended */
+    int32_t n_points, n_keyframes;
+    /* point rows replaced wholesale (strictly ascending): isBad, nObs, the observation list */
+    int32_t n_point_rows;   const int32_t *point_row;
+    const uint8_t *point_bad;  const int32_t *point_nobs;           /* [n_point_rows] */
+    const int32_t *obs_off, *obs_kf;                                /* CSR over the n_point_rows rows */
+    /* keyframe MATCH rows replaced wholesale (strictly ascending): GetMapPointMatches() */
+    int32_t n_kf_mp_rows;   const int32_t *kf_mp_row;
+    const int32_t *kf_mp_off, *kf_mp;                               /* CSR over the n_kf_mp_rows rows */
+    /* keyframe LINK rows replaced wholesale (strictly ascending): isBad, the 10 best covisibles, children, parent */
+    int32_t n_kf_link_rows; const int32_t *kf_link_row;
+    const uint8_t *kf_bad;  const int32_t *kf_best /* [rows][10] */, *kf_child_off, *kf_child, *kf_parent;
+    /* NULL if and only if the handle holds no culling view.  Parallel to the delta's arrays: obs_idx to obs_kf;
+     * kf_octave / kf_depth / kf_stereo to kf_mp; kf_th_depth / kf_flags [n_kf_link_rows] */
+    const aos2_kf_culling_view_t *view;
+} aos2_local_map_delta_t;
+/* The graph after the call is the graph before it with every named row replaced by the delta's content and the tables extended
+ * to the new counts.  An appended point row that the delta does not name is an empty slot (bad = 1, nObs = 0, no observations);
+ * an appended keyframe row must be named in BOTH keyframe row sets.  Child lists are stored in ascending row, as
+ * aos2_local_map_set stores them.  An empty delta is valid and changes nothing; a handle without a set holds the empty map (and
+ * no view), and a delta may be applied to it.  The culling view is NOT dropped: it moves with the graph.
+ * Checked BEFORE a device is looked for, in O(delta) against counts the handle keeps on the host -- AOS2_ERR_ARG with the graph
+ * and the view left exactly as they were for: a NULL handle or delta; a count below the current one; a row list that is not
+ * strictly ascending or holds a row outside the new count; an appended keyframe missing from either keyframe set; a NULL array
+ * with a non-zero length (an offsets array of a row set without rows may be NULL); offsets that do not start at 0 or that
+ * decrease; a value outside the new counts (other than the -1 that kf_mp, kf_best and kf_parent allow); a keyframe listed twice
+ * among one point's observations; a match row of an EXISTING keyframe whose length differs from the one it has (a keyframe's N
+ * never changes: that keeps the obs_idx of untouched points in range); `view` given without a resident view, or missing with
+ * one; an obs_idx outside the feature count its keyframe has after the delta; more than 2^31 - 1 entries in an array.
+ * Where the work runs: with the graph (and the view, if there is one) resident, only the delta is uploaded and the new arrays
+ * are built by kernels on the handle's stream into the second of two device blocks; on an allocation or HIP failure
+ * (AOS2_ERR_HIP) the previous block stays current and the graph is unchanged.  The handle's host copy then goes stale and is
+ * refreshed by ONE download when something next reads it (aos2_local_map_get, aos2_local_map_get_culling_view, the check of
+ * aos2_local_map_set_culling_view, a re-upload).  With the graph not resident (no device, or never uploaded) the same rebuild
+ * runs serially on the host copy and the return value follows aos2_local_map_set: AOS2_OK or AOS2_ERR_NO_DEVICE, and a delta
+ * that passed the check is the handle's either way.
+ * Ordering: as aos2_local_map_set.  The call synchronises the device before it builds the new block, and returns when the new
+ * graph is complete: work enqueued before the call sees the old graph, work enqueued after it the new one.  Removing that wait
+ * (an event per consumer stream) is out of scope. */
+int aos2_local_map_apply(aos2_local_map_t *m, const aos2_local_map_delta_t *d);
+/* the last aos2_local_map_apply that passed its checks: *path = 0 host, 1 device (-1: none yet); *reallocated = the device block
+ * it wrote had to be allocated or grown (blocks grow with a quarter of slack); *device_ms = between two events on the handle's
+ * stream, from the delta's upload to the last kernel (-1 on the host path).  Any of the three may be NULL. */
+int aos2_local_map_last_apply(const aos2_local_map_t *m, int32_t *path, int32_t *reallocated, float *device_ms);
+/* bytes the last device rebuild uploaded (0 on the host path) */
+int64_t aos2_local_map_last_apply_bytes(const aos2_local_map_t *m);
+/* test hook: the rows one workgroup scans in the rebuild (<= 0: the default, 1024), so that the seams of the multi-workgroup scan
+ * and the loop over the workgroups' totals are reached with graphs of a few hundred rows */
+int aos2_local_map_debug_apply_tile(aos2_local_map_t *m, int rows);
 
 /* ------------------------------------------------------------------------------------------
  * Replay of a fixed call sequence (csrc/replay.hip).  No single reference function: the per-frame body of Tracking::Track on its
@@ -1607,6 +1669,10 @@ int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, 
 int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view, int monocular, int n_cand,
                                      const int32_t *cand, uint8_t *status, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points,
                                      int bad_cap, int32_t *n_bad_points);
+/* aos2_local_map_apply with the rebuild forced onto the HOST, also where the graph is resident: the same checks, the serial
+ * restatement on the handle's host copy (refreshed first if it is stale), and the device copy of graph and view marked dirty, so
+ * that the next consumer re-uploads everything.  The tap the device rebuild is compared with.  Returns as aos2_local_map_set. */
+int aos2_debug_local_map_apply_host(aos2_local_map_t *m, const aos2_local_map_delta_t *d);
 /* the math of csrc/motion_tw.h on arrays of n doubles: sin = tw_sin(x), cos = tw_cos(x), atan2 = tw_atan2(y, x), sqrt = sqrt(x),
  * quot = y / x; on the host (device == -1) or in a kernel of one lane per element.  It tells whether a difference between the two
  * sides comes from the math or from the logic.  Any x and y (the domain check of the states does not apply). */
