@@ -2137,7 +2137,7 @@ POSE_PASS_FORMS = ((4, 256, 1024), (8, 256, 2048), (9, 128, 1152), (0, 256, None
 
 
 def debug_pose_pass_device(cases, mode, device=0):
-    """test tap: pose_optimization_body of csrc/pose_opt.hip, one workgroup per case in the instantiation POSE_PASS_FORMS[case["form"]].
+    """test tap: pose_optimization_body of csrc/pose_opt.h, one workgroup per case in the instantiation POSE_PASS_FORMS[case["form"]].
     cases: synth_pose_problem()-style dicts (n, Xw, obs, stereo, inv_sigma2, fx .. bf) with form, pose (7 doubles qx qy qz qw tx ty tz) and,
     optional, it (0), level1 (zeros), robust (ones), outlier (zeros), chi2 (zeros), [n] each.  mode 1: one edge pass -> sums (28: H upper
     triangle, b, robust chi2), chi2 [n]; mode 2: the reclassification of round it -> outlier, level1, robust, chi2, n_bad; mode 0: the

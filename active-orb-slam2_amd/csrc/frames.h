@@ -3,10 +3,14 @@
 //   ORBextractor::operator() -> Frame::Frame (stereo from RGB-D, grid) -> SearchByProjection(Current, Last)
 //   -> PoseOptimization -> SearchLocalPoints (isInFrustum + SearchByProjection(F, vpMapPoints)) -> PoseOptimization
 // so that no keypoint, descriptor, match or pose crosses PCIe between them.  Internal to the library; the public
-// entry points are the aos2_frames_* functions of include/aos2.h.
+// entry points are the aos2_frames_* functions of include/aos2.h.  Their translation units: frames.hip (lifetime, build,
+// the two searches of the chain), frames_keyframe.hip (SearchForTriangulation, Fuse, CreateNewMapPoints), frames_pose.hip
+// (PoseOptimization), local_map.hip (UpdateLocalMap).  This header is what they share: the batch and its handle, frame_of
+// (one frame as search_device.h's routines take it) and, at the end, the host steps more than one of them runs.
 #pragma once
 #include "aos2_common.h"
 #include "regions.h"
+#include "search_device.h"
 
 namespace aos2 {
 
@@ -33,6 +37,28 @@ struct FramesDev {
     float dist[5];                 // mDistCoef: k1 k2 p1 p2 k3 (all 0: mvKeysUn = mvKeys)
     int has_dist;                  // mDistCoef.at<float>(0) != 0 (the reference's test, src/Frame.cc:435)
 };
+
+// frame b of a batch as the searches see one frame (search_device.h)
+__device__ __forceinline__ FrameDev frame_of(const FramesDev &S, int b)
+{
+    FrameDev F;
+    const size_t o = (size_t)b * S.cap;
+    F.n_f = S.n[b];
+    F.n_levels = S.n_levels;
+    F.desc_f = S.desc + o * 32;
+    F.kp_x = S.kp_x + o;
+    F.kp_y = S.kp_y + o;
+    F.kp_angle = S.kp_angle + o;
+    F.u_right = S.u_right + o;
+    F.scale_factors = S.scale_factors;
+    F.kp_octave = S.kp_octave + o;
+    F.min_x = S.min_x; F.min_y = S.min_y; F.max_x = S.max_x; F.max_y = S.max_y;
+    F.grid_w_inv = S.grid_w_inv; F.grid_h_inv = S.grid_h_inv;
+    F.grid_off = S.grid_off + (size_t)b * (kFrGridCells + 1);
+    F.grid_idx = S.grid_idx + o;
+    F.f_mp_state = S.mp_state + o;
+    return F;
+}
 
 // the members of MapPoint the per-frame path reads (include/MapPoint.h): GetWorldPos, GetDescriptor, Observations() > 0,
 // GetNormal, mfMinDistance / mfMaxDistance (raw)
@@ -114,3 +140,60 @@ struct aos2_frames {
     bool kf_async = false;              // aos2_frames_set_async_keyframe_calls: the keyframe entry points return after enqueueing
     float dist[5] = {0, 0, 0, 0, 0};   // mDistCoef for the next aos2_frames_build (aos2_frames_set_distortion)
 };
+
+namespace aos2 {
+
+// binds the batch's device and, on the first call, creates its stream and member arrays (csrc/frames.hip)
+int frames_init(aos2_frames *f);
+
+// `s` waits for everything enqueued on the producer batch's stream so far: the kernels the caller puts on `s` read members
+// (mvpMapPoints, mvbOutlier, mTcw, keys) that the work on the producer's own stream may still be writing -- in a tracking loop
+// the previous CurrentFrame batch becomes LastFrame while its PoseOptimization is in flight.  The entry points take the
+// producer as a read-only batch; the event it lends to the ordering is the handle's bookkeeping, none of its members: hence
+// the const_cast, here and nowhere else.
+inline int order_behind(hipStream_t s, const aos2_frames *producer)
+{
+    aos2_frames *p = const_cast<aos2_frames *>(producer);
+    if (!p->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&p->order_ev, hipEventDisableTiming));
+    AOS2_HIP_CHECK(hipEventRecord(p->order_ev, p->stream));
+    AOS2_HIP_CHECK(hipStreamWaitEvent(s, p->order_ev, 0));
+    return AOS2_OK;
+}
+
+// A keyframe call stages its host arrays through its slot of the batch: kf_stage_begin, the host fill, (order_behind,)
+// kf_stage_upload, the kernels, kf_call_end.
+//
+// the slot's last upload is over (asynchronous calls), both buffers hold `count` elements -> the page-locked one, to be filled
+template <class T>
+inline int kf_stage_begin(KfStage &k, size_t count, T *&host)
+{
+    if (k.uploaded) AOS2_HIP_CHECK(hipEventSynchronize(k.uploaded));
+    k.bytes = sizeof(T) * count;
+    if (int st = k.host.alloc(k.bytes)) return st;
+    if (int st = k.dev.alloc(k.bytes)) return st;
+    host = reinterpret_cast<T *>(k.host.p);
+    return AOS2_OK;
+}
+
+// the filled buffer goes to the device on the batch's stream -> its device copy; an asynchronous call marks the upload's end
+template <class T>
+inline int kf_stage_upload(aos2_frames *f, KfStage &k, const T *&dev)
+{
+    AOS2_HIP_CHECK(hipMemcpyAsync(k.dev.p, k.host.p, k.bytes, hipMemcpyHostToDevice, f->stream));
+    if (f->kf_async) {
+        if (!k.uploaded) AOS2_HIP_CHECK(hipEventCreateWithFlags(&k.uploaded, hipEventDisableTiming));
+        AOS2_HIP_CHECK(hipEventRecord(k.uploaded, f->stream));
+    }
+    dev = reinterpret_cast<const T *>(k.dev.p);
+    return AOS2_OK;
+}
+
+// the kernels are enqueued: a synchronous call waits for them, an asynchronous one leaves that to aos2_frames_wait
+inline int kf_call_end(aos2_frames *f)
+{
+    AOS2_HIP_CHECK(hipGetLastError());
+    if (!f->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(f->stream));
+    return AOS2_OK;
+}
+
+}  // namespace aos2

@@ -1,34 +1,18 @@
-// Device-resident frame batches (include/aos2.h: aos2_frames_*), part of matcher.hip's translation unit because the
-// searches reuse its device routines.  A batch holds B Frames whose members stay in HBM between the calls of the
-// per-frame tracking chain; every call is enqueued on the batch's own stream and returns without waiting.
+// Device-resident frame batches (include/aos2.h: aos2_frames_*): lifetime, Frame::Frame, and the two searches of the per-frame
+// tracking chain.  A batch holds B Frames whose members stay in HBM between the calls of the chain; every call is enqueued on the
+// batch's own stream and returns without waiting.  The searches are built from the device routines of search_device.h, which the
+// matcher's kernels share.  The keyframe work on resident batches is frames_keyframe.hip, PoseOptimization frames_pose.hip, the
+// local map local_map.hip.
 //
 // Reference: Frame::Frame (src/Frame.cc:116-170), Tracking::TrackWithMotionModel (src/Tracking.cc:963-1027),
 // Tracking::SearchLocalPoints (:1302-1352), ORBmatcher::SearchByProjection (src/ORBmatcher.cc:45-129, 1328-1470),
 // Frame::isInFrustum (src/Frame.cc:298-354).
+#include <algorithm>
+
 #include "frames.h"
+#include "search_device.h"
 
 namespace aos2 {
-
-__device__ __forceinline__ FrameDev frame_of(const FramesDev &S, int b)
-{
-    FrameDev F;
-    const size_t o = (size_t)b * S.cap;
-    F.n_f = S.n[b];
-    F.n_levels = S.n_levels;
-    F.desc_f = S.desc + o * 32;
-    F.kp_x = S.kp_x + o;
-    F.kp_y = S.kp_y + o;
-    F.kp_angle = S.kp_angle + o;
-    F.u_right = S.u_right + o;
-    F.scale_factors = S.scale_factors;
-    F.kp_octave = S.kp_octave + o;
-    F.min_x = S.min_x; F.min_y = S.min_y; F.max_x = S.max_x; F.max_y = S.max_y;
-    F.grid_w_inv = S.grid_w_inv; F.grid_h_inv = S.grid_h_inv;
-    F.grid_off = S.grid_off + (size_t)b * (kFrGridCells + 1);
-    F.grid_idx = S.grid_idx + o;
-    F.f_mp_state = S.mp_state + o;
-    return F;
-}
 
 // Frame::Frame after ExtractORB (:126-150): N, UndistortKeyPoints with zero distortion (mvKeysUn = mvKeys :436-442),
 // ComputeStereoFromRGBD (:672-693), mvpMapPoints = NULL, mvbOutlier = false
@@ -69,29 +53,10 @@ __global__ __launch_bounds__(256) void frames_build_kernel(FramesDev S, const fl
                      S.grid_off + (size_t)b * (kFrGridCells + 1), S.grid_idx + ob);
 }
 
-// exclusive scan of the window populations of one frame's queries -> entry offsets inside the frame's share of the pool;
-// a frame whose windows hold more than its share gets no entries and raises the sticky flag
 __global__ __launch_bounds__(256) void frames_scan_slots_kernel(QuerySlot *__restrict__ slots, const int32_t *__restrict__ nq_of,
                                                                 int nq_cap, int share, int32_t *__restrict__ overflow)
 {
-    __shared__ int32_t wsum[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    QuerySlot *sl = slots + (size_t)b * nq_cap;
-    const int nq = nq_of ? min(nq_of[b], nq_cap) : nq_cap;
-    int carry = 0;   // entries of the chunks before this one (uniform)
-    for (int q0 = 0; q0 < nq; q0 += 256) {
-        const int q = q0 + tid;
-        const int v = q < nq ? max(sl[q].cnt, 0) : 0;
-        int total;
-        const int excl = carry + block_excl_scan_i32<256>(v, wsum, total);
-        if (q < nq) sl[q].ent_off = (int)((size_t)b * share) + excl;
-        carry += total;
-        __syncthreads();   // wsum is read before the next chunk writes it
-    }
-    if (carry > share) {
-        for (int q = tid; q < nq; q += 256) sl[q].cnt = 0;
-        if (tid == 0) overflow_note(overflow, carry);   // (the word is in host memory)
-    }
+    scan_slots_body(slots, nq_of, nq_cap, share, overflow);
 }
 
 // ---- SearchByProjection(CurrentFrame, LastFrame, th, bMono) for the pairs (cur b, last b)
@@ -370,7 +335,7 @@ __global__ void frames_set_state_kernel(FramesDev S, MapPointsDev M)
     S.mp_state[o] = (i < S.n[b] && row >= 0) ? (M.has_obs[row] ? 2 : 1) : 0;
 }
 
-static int frames_init(aos2_frames *f)
+int frames_init(aos2_frames *f)
 {
     int st = bind_device(f->device);
     if (st) return st;
@@ -469,57 +434,9 @@ static FrameMember frame_member(const FramesDev &D, int what)
     }
 }
 
-// `s` waits for everything enqueued on the producer batch's stream so far: the kernels the caller puts on `s` read members
-// (mvpMapPoints, mvbOutlier, mTcw, keys) that the work on the producer's own stream may still be writing -- in a tracking loop
-// the previous CurrentFrame batch becomes LastFrame while its PoseOptimization is in flight.  The entry points take the
-// producer as a read-only batch; the event it lends to the ordering is the handle's bookkeeping, none of its members: hence
-// the const_cast, here and nowhere else.
-static int order_behind(hipStream_t s, const aos2_frames *producer)
-{
-    aos2_frames *p = const_cast<aos2_frames *>(producer);
-    if (!p->order_ev) AOS2_HIP_CHECK(hipEventCreateWithFlags(&p->order_ev, hipEventDisableTiming));
-    AOS2_HIP_CHECK(hipEventRecord(p->order_ev, p->stream));
-    AOS2_HIP_CHECK(hipStreamWaitEvent(s, p->order_ev, 0));
-    return AOS2_OK;
-}
-
-// A keyframe call stages its host arrays through its slot of the batch: kf_stage_begin, the host fill, (order_behind,)
-// kf_stage_upload, the kernels, kf_call_end.
-//
-// the slot's last upload is over (asynchronous calls), both buffers hold `count` elements -> the page-locked one, to be filled
-template <class T>
-static int kf_stage_begin(KfStage &k, size_t count, T *&host)
-{
-    if (k.uploaded) AOS2_HIP_CHECK(hipEventSynchronize(k.uploaded));
-    k.bytes = sizeof(T) * count;
-    if (int st = k.host.alloc(k.bytes)) return st;
-    if (int st = k.dev.alloc(k.bytes)) return st;
-    host = reinterpret_cast<T *>(k.host.p);
-    return AOS2_OK;
-}
-
-// the filled buffer goes to the device on the batch's stream -> its device copy; an asynchronous call marks the upload's end
-template <class T>
-static int kf_stage_upload(aos2_frames *f, KfStage &k, const T *&dev)
-{
-    AOS2_HIP_CHECK(hipMemcpyAsync(k.dev.p, k.host.p, k.bytes, hipMemcpyHostToDevice, f->stream));
-    if (f->kf_async) {
-        if (!k.uploaded) AOS2_HIP_CHECK(hipEventCreateWithFlags(&k.uploaded, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventRecord(k.uploaded, f->stream));
-    }
-    dev = reinterpret_cast<const T *>(k.dev.p);
-    return AOS2_OK;
-}
-
-// the kernels are enqueued: a synchronous call waits for them, an asynchronous one leaves that to aos2_frames_wait
-static int kf_call_end(aos2_frames *f)
-{
-    AOS2_HIP_CHECK(hipGetLastError());
-    if (!f->kf_async) AOS2_HIP_CHECK(hipStreamSynchronize(f->stream));
-    return AOS2_OK;
-}
-
 }  // namespace aos2
+
+using namespace aos2;
 
 extern "C" {
 
@@ -769,271 +686,6 @@ int aos2_frames_search_by_projection_last(aos2_frames_t *cur, const aos2_frames_
         hipLaunchKernelGGL(frames_last_resolve_kernel<512>, dim3(B), dim3(512), (size_t)C.cap * 8 + 16, q, C, Lf, M, check_orientation ? 1 : 0,
                            X.slots, X.pool, X.match_f, X.bin_f, X.nmatches, X.choice, d_nmatches);
     AOS2_HIP_CHECK(hipGetLastError());
-    return AOS2_OK;
-}
-
-}  // extern "C"
-
-namespace aos2 {
-
-// ---------------------------------------------------------------------------------------------------------------
-// Keyframe work on device-resident batches (LocalMapping::CreateNewMapPoints / SearchInNeighbors, src/LocalMapping.cc:272, 493):
-// a keyframe is a frame of a built batch -- KeyFrame::KeyFrame copies exactly these Frame members (src/KeyFrame.cc:37-62).
-// ---------------------------------------------------------------------------------------------------------------
-struct FrTriPair {
-    int32_t kf1, kf2;
-    float F12[9], ex, ey;
-};
-
-// SearchForTriangulation (src/ORBmatcher.cc:657-823) for pairs (frame kf1 of A, frame kf2 of B): one wave per KF1 feature.
-// vbMatched2 is never set by the reference, so the KF1 features are independent (triang_match_kernel above): a feature
-// without a map point looks its vocabulary node (node_of, the FeatureVector key of the feature) up in KF2's FeatureVector
-// (binary search over <= a few hundred ascending node ids) and takes the best candidate of that bucket.  The reference walks
-// KF1's FeatureVector (:688-700), which holds a feature only if its word has a non-zero weight (DBoW2 transform): the feature
-// has to be in its node's bucket of KF1's FeatureVector too.
-struct FrFvDev {
-    const int32_t *node, *off, *idx, *n;
-};
-
-// position of `node` in the ascending id list of a FeatureVector, -1 if absent (one thread: ~7 dependent loads of a hot list)
-__device__ __forceinline__ int fv_find_node(const int32_t *ids, int nn, int node)
-{
-    int lo = 0, hi = nn;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ids[mid] < node) lo = mid + 1; else hi = mid;
-    }
-    return (lo < nn && ids[lo] == node) ? lo : -1;
-}
-
-// SearchForTriangulation's matching loop (src/ORBmatcher.cc:690-773) for a list of keyframe pairs: one THREAD per feature of
-// KF1 (round 3: one wave per feature -- 655 k one-wave workgroups per 640 pairs whose lanes mostly idled: a vocabulary node at
-// levelsup 4 holds ~10 features of a keyframe).  The thread walks the bucket of KF2 in its order and keeps the LAST smallest
-// distance (`dist > bestDist` continues, :734: a tie replaces).  vbMatched2 is never set by the reference, so the features
-// are independent.
-__global__ __launch_bounds__(256) void frames_triang_match_kernel(FramesDev A, FramesDev B, const FrTriPair *__restrict__ pairs,
-                                                                 const uint32_t *__restrict__ node_of1, FrFvDev fv1, const int32_t *__restrict__ fv_node2,
-                                                                 const int32_t *__restrict__ fv_off2, const int32_t *__restrict__ fv_idx2,
-                                                                 const int32_t *__restrict__ n_fv2, int only_stereo, int32_t *__restrict__ match12)
-{
-    const FrTriPair &P = pairs[blockIdx.y];
-    const int i1 = blockIdx.x * 256 + threadIdx.x;
-    if (i1 >= A.cap) return;
-    const size_t o1 = (size_t)P.kf1 * A.cap, o2 = (size_t)P.kf2 * B.cap;
-    int32_t *out = match12 + (size_t)blockIdx.y * A.cap;
-    int best = -1;   // vMatches12(pKF1->N, -1) :681
-    do {
-        if (i1 >= A.n[P.kf1]) break;
-        if (A.mp[o1 + i1] >= 0) break;                                // pKF1->GetMapPoint(idx1) :700-703
-        const bool bStereo1 = A.u_right[o1 + i1] >= 0;
-        if (only_stereo && !bStereo1) break;                          // :705-709
-        // the bucket of KF2 with this feature's node id
-        const int node = (int)node_of1[o1 + i1];
-        const int lo = fv_find_node(fv_node2 + o2, n_fv2[P.kf2], node);
-        if (lo < 0) break;
-        {
-            const int l1 = fv_find_node(fv1.node + o1, fv1.n[P.kf1], node);
-            if (l1 < 0) break;
-            const int32_t *off1 = fv1.off + (size_t)P.kf1 * (A.cap + 1);
-            const int beg = off1[l1], cnt = off1[l1 + 1] - beg;
-            const int32_t *b1 = fv1.idx + o1 + beg;
-            bool mine = false;
-            for (int j = 0; j < cnt && !mine; ++j) mine = b1[j] == i1;
-            if (!mine) break;
-        }
-        const int32_t *off2 = fv_off2 + (size_t)P.kf2 * (B.cap + 1);
-        const int f_beg = off2[lo], f_cnt = off2[lo + 1] - f_beg;
-        const int32_t *bucket = fv_idx2 + o2 + f_beg;
-        const Desc d1 = load_desc(A.desc + (o1 + i1) * 32);
-        const float kx = A.kp_x[o1 + i1], ky = A.kp_y[o1 + i1];
-        const EpiLine line = epi_line(P.F12, kx, ky);
-        int bestDist = TH_LOW;
-        for (int j = 0; j < f_cnt; ++j) {
-            const int idx2 = bucket[j];
-            if (B.mp[o2 + idx2] >= 0) continue;                       // :723
-            const bool bStereo2 = B.u_right[o2 + idx2] >= 0;
-            if (only_stereo && !bStereo2) continue;
-            const int dist = hamming(d1, load_desc(B.desc + (o2 + idx2) * 32));
-            if (dist > TH_LOW || dist > bestDist) continue;           // :734
-            const float sf = B.scale_factors[B.kp_octave[o2 + idx2]];
-            // mvLevelSigma2[i] = mvScaleFactor[i] * mvScaleFactor[i] (ORBextractor.cc:420)
-            if (!epi_admits(line, B.kp_x[o2 + idx2], B.kp_y[o2 + idx2], !bStereo1 && !bStereo2, P.ex, P.ey, sf, __fmul_rn(sf, sf)))
-                continue;
-            best = idx2;
-            bestDist = dist;
-        }
-    } while (false);
-    out[i1] = best;
-}
-
-// rotation consistency (:776-808) + count, one wave per pair
-__global__ __launch_bounds__(64) void frames_triang_finish_kernel(FramesDev A, FramesDev B, const FrTriPair *__restrict__ pairs, int check_ori,
-                                                                  int32_t *__restrict__ match12, int32_t *__restrict__ nmatches)
-{
-    const FrTriPair &P = pairs[blockIdx.x];
-    triang_finish_body(A.n[P.kf1], A.kp_angle + (size_t)P.kf1 * A.cap, B.kp_angle + (size_t)P.kf2 * B.cap,
-                       match12 + (size_t)blockIdx.x * A.cap, nmatches + blockIdx.x, check_ori);
-}
-
-__device__ const uint8_t k_valid_one = 1;
-
-// the search part of Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-975) for problems (target keyframe = a frame of the
-// batch, candidate map points = rows of the table, -1 = the loop head rejected it).  One THREAD per candidate: the window of a
-// fused point holds a handful of features (radius th x scale: 3-4 grid columns of a sparse grid), so a wave per candidate
-// (round 3's form: 2 M one-wave workgroups per step, 1.66 ms) left ~60 lanes idle in the window loop and repeated the setup
-// in every lane.  The thread visits the window in GetFeaturesInArea's order (columns, cells of a column, the features of a
-// cell in their CSR order) and keeps the FIRST smallest distance -- `if (dist < bestDist)` of :937-941.
-__global__ __launch_bounds__(256) void frames_fuse_kernel(FramesDev S, MapPointsDev M, const int32_t *__restrict__ target,
-                                                         const int32_t *__restrict__ rows, int n_pts, float th,
-                                                         int32_t *__restrict__ best_idx, int32_t *__restrict__ best_dist)
-{
-    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, b = target[p];
-    if (i >= n_pts) return;
-    const size_t o = (size_t)p * n_pts + i;
-    const int row = rows[o];
-    int bi = -1, bd = 256;
-    if (row >= 0) {
-        const FrameDev F = frame_of(S, b);
-        const float *T = S.Tcw + (size_t)b * 16;
-        ProjGenDev P;
-        P.n_pts = 1; P.mode = 0;
-        P.valid = &k_valid_one;
-        P.desc = M.desc + (size_t)row * 32;
-        P.pos = M.pos + 3 * (size_t)row; P.max_dist = M.max_dist + row; P.min_dist = M.min_dist + row; P.normal = M.normal + 3 * (size_t)row;
-        P.q_angle = nullptr;
-        P.inv_level_sigma2 = S.inv_level_sigma2;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) P.R[3 * r + c] = T[4 * r + c];
-            P.t[r] = T[4 * r + 3];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {   // Ow = -Rcw.t() * tcw (KeyFrame::SetPose, src/KeyFrame.cc:64-82; cv::gemm: double accumulation)
-            const double sacc = __dadd_rn(__dadd_rn(__dmul_rn((double)T[k], (double)T[3]), __dmul_rn((double)T[4 + k], (double)T[7])),
-                                          __dmul_rn((double)T[8 + k], (double)T[11]));
-            P.Ow[k] = (float)__dmul_rn(sacc, -1.0);
-        }
-        P.fx = S.fx; P.fy = S.fy; P.cx = S.cx; P.cy = S.cy; P.bf = S.mbf; P.log_scale_factor = S.log_scale_factor; P.th = th;
-        const ProjSetup Q = proj_gen_setup(F, P, 0);
-        if (Q.ok) {
-            const Window w = window_cells(F, Q.u, Q.v, Q.radius);
-            if (w.ok) {
-                const Desc dq = load_desc(P.desc);
-                int best = 256, arg = -1;
-                for (int ix = w.x0; ix <= w.x1; ++ix) {
-                    const int j0 = F.grid_off[ix * GRID_ROWS + w.y0], j1 = F.grid_off[ix * GRID_ROWS + w.y1 + 1];   // (a column's cells are neighbours in the CSR)
-                    for (int j = j0; j < j1; ++j) {
-                        const int idx = F.grid_idx[j];
-                        const float kx = F.kp_x[idx], ky = F.kp_y[idx];
-                        const int oct = F.kp_octave[idx];
-                        const float kr = F.u_right[idx];
-                        if (!(fabsf(__fsub_rn(kx, Q.u)) < Q.radius && fabsf(__fsub_rn(ky, Q.v)) < Q.radius)) continue;
-                        if (oct < Q.level - 1 || oct > Q.level) continue;
-                        // reprojection error gates of Fuse (:911-935)
-                        const float ex = __fsub_rn(Q.u, kx), ey = __fsub_rn(Q.v, ky);
-                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        double lim = 5.99;
-                        if (kr >= 0) {
-                            const float er = __fsub_rn(Q.ur, kr);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            lim = 7.8;
-                        }
-                        if ((double)__fmul_rn(e2, P.inv_level_sigma2[oct]) > lim) continue;
-                        const int dist = hamming(dq, load_desc(F.desc_f + (size_t)idx * 32));
-                        if (dist < best) {
-                            best = dist;
-                            arg = idx;
-                        }
-                    }
-                }
-                if (arg >= 0 && best <= TH_LOW) {
-                    bi = arg;
-                    bd = best;
-                }
-            }
-        }
-    }
-    best_idx[o] = bi;
-    best_dist[o] = bd;
-}
-
-}  // namespace aos2
-
-extern "C" {
-
-int aos2_frames_search_for_triangulation(aos2_frames_t *a, aos2_frames_t *b, const aos2_frames_triang_t *q, int only_stereo,
-                                         int check_orientation, int32_t *d_match12, int32_t *d_nmatches)
-{
-    using namespace aos2;
-    if (!a || !b || !q || q->n_pairs <= 0 || !q->kf1 || !q->kf2 || !q->F12 || !q->epipole || !q->d_node_of1 || !q->d_fv_node1 || !q->d_fv_off1 ||
-        !q->d_fv_idx1 || !q->d_n_fv1 || !q->d_fv_node2 ||
-        !q->d_fv_off2 || !q->d_fv_idx2 || !q->d_n_fv2 || !d_match12 || !d_nmatches || !a->dev_ready || !b->dev_ready || !a->D.n || !b->D.n) {
-        set_error("bad argument (both keyframe batches built)");
-        return AOS2_ERR_ARG;
-    }
-    int st = bind_device(a->device);
-    if (st) return st;
-    const int n = q->n_pairs;
-    for (int p = 0; p < n; ++p)
-        if (q->kf1[p] < 0 || q->kf1[p] >= a->D.batch || q->kf2[p] < 0 || q->kf2[p] >= b->D.batch) {
-            set_error("pair %d names keyframes (%d, %d) outside the batches", p, q->kf1[p], q->kf2[p]);
-            return AOS2_ERR_ARG;
-        }
-    // the pair records
-    KfStage &stage = a->kf[kKfTriang];
-    FrTriPair *h;
-    if ((st = kf_stage_begin(stage, (size_t)n, h))) return st;
-    for (int p = 0; p < n; ++p) {
-        h[p].kf1 = q->kf1[p]; h[p].kf2 = q->kf2[p];
-        memcpy(h[p].F12, q->F12 + 9 * (size_t)p, 36);
-        h[p].ex = q->epipole[2 * p]; h[p].ey = q->epipole[2 * p + 1];
-    }
-    hipStream_t s = a->stream;
-    if (b != a && (st = order_behind(s, b))) return st;
-    const FrTriPair *dp;
-    if ((st = kf_stage_upload(a, stage, dp))) return st;
-    hipLaunchKernelGGL(frames_triang_match_kernel, dim3((a->D.cap + 255) / 256, n), dim3(256), 0, s, a->D, b->D, dp, q->d_node_of1,
-                       FrFvDev{q->d_fv_node1, q->d_fv_off1, q->d_fv_idx1, q->d_n_fv1}, q->d_fv_node2, q->d_fv_off2,
-                       q->d_fv_idx2, q->d_n_fv2, only_stereo ? 1 : 0, d_match12);
-    hipLaunchKernelGGL(frames_triang_finish_kernel, dim3(n), dim3(64), 0, s, a->D, b->D, dp, check_orientation ? 1 : 0, d_match12, d_nmatches);
-    return kf_call_end(a);
-}
-
-int aos2_frames_fuse(aos2_frames_t *kfs, const aos2_map_points_dev_t *mps, int n_problems, int n_pts, const int32_t *target,
-                     const int32_t *d_rows, float th, int32_t *d_best_idx, int32_t *d_best_dist)
-{
-    using namespace aos2;
-    if (!kfs || !mps || n_problems <= 0 || n_pts <= 0 || !target || !d_rows || !d_best_idx || !d_best_dist || !kfs->dev_ready || !kfs->D.n ||
-        !mps->normal || !mps->min_dist || !mps->max_dist) {
-        set_error("bad argument (keyframe batch built; map points with normals and distance ranges)");
-        return AOS2_ERR_ARG;
-    }
-    int st = bind_device(kfs->device);
-    if (st) return st;
-    for (int p = 0; p < n_problems; ++p)
-        if (target[p] < 0 || target[p] >= kfs->D.batch) {
-            set_error("problem %d names keyframe %d outside the batch", p, target[p]);
-            return AOS2_ERR_ARG;
-        }
-    KfStage &stage = kfs->kf[kKfFuse];
-    int32_t *h;
-    if ((st = kf_stage_begin(stage, (size_t)n_problems, h))) return st;
-    memcpy(h, target, 4 * (size_t)n_problems);
-    const int32_t *d_target;
-    if ((st = kf_stage_upload(kfs, stage, d_target))) return st;
-    hipLaunchKernelGGL(frames_fuse_kernel, dim3((n_pts + 255) / 256, n_problems), dim3(256), 0, kfs->stream, kfs->D, map_points_dev(mps),
-                       d_target, d_rows, n_pts, th, d_best_idx, d_best_dist);
-    return kf_call_end(kfs);
-}
-
-int aos2_frames_set_async_keyframe_calls(aos2_frames_t *f, int on)
-{
-    if (!f) {
-        set_error("bad argument");
-        return AOS2_ERR_ARG;
-    }
-    f->kf_async = on != 0;
     return AOS2_OK;
 }
 

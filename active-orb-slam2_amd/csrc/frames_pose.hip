@@ -1,7 +1,8 @@
-// Optimizer::PoseOptimization over a device-resident frame batch (include/aos2.h: aos2_frames_pose_optimization), part of
-// pose_opt.hip's translation unit.  The gather is the edge-building loop of src/Optimizer.cc:260-350 on the device:
+// Optimizer::PoseOptimization over a device-resident frame batch (include/aos2.h: aos2_frames_pose_optimization) around
+// pose_optimization_body of pose_opt.h.  The gather is the edge-building loop of src/Optimizer.cc:260-350 on the device:
 // the features that hold a map point, in feature order; mono edge when mvuRight < 0, stereo edge otherwise.
 #include "frames.h"
+#include "pose_opt.h"
 
 namespace aos2 {
 

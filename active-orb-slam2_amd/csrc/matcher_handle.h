@@ -1,6 +1,7 @@
 // The matcher handle (aos2_matcher_t of include/aos2.h) and the arena every call on it lays its memory out in.  Host only.
 // csrc/matcher.hip owns the handle (create / destroy, matcher_init); the geometric solvers that run on it (sim3_ransac.hip,
-// pnp_ransac.hip, initializer_ransac.hip) are translation units of their own and need no more of the matcher than this.
+// pnp_ransac.hip, initializer_ransac.hip) and triangulate.hip are translation units of their own and need no more of the
+// matcher than this.  (The matcher's DEVICE layer is search_device.h; no unit that includes this header alone sees it.)
 #pragma once
 #include <algorithm>
 #include <type_traits>

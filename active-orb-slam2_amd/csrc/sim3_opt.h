@@ -222,7 +222,7 @@ __host__ __device__ inline void so_edge_linearise(const Sim3d &T0, const Sim3d *
 
 // (H + lambda I) x = b for the 7x7 system, Hb = 28 (upper triangle row by row) + 7 (b): LinearSolverDense's Cholesky in the
 // square-root-free form L D L^T (the pivots are the squares of Cholesky's diagonal: the same positivity test), right-looking,
-// in registers, shaped like solve6 of pose_opt.hip.  false = "not positive definite"; x keeps its values then.
+// in registers, shaped like solve6 of pose_opt.h.  false = "not positive definite"; x keeps its values then.
 __host__ __device__ inline bool so_solve7(const double *Hb, double lambda, double (&x)[7])
 {
     double a[7][7], rd[7];

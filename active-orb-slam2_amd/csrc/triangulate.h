@@ -1,7 +1,8 @@
 // The per-match body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:295-436): parallax test, linear triangulation
 // (cv::SVD of a 4x4), the KeyFrame::UnprojectStereo fallbacks (src/KeyFrame.cc:676-692) and the depth / reprojection / scale
-// gates that decide whether a MapPoint is born.  ONE routine for the device kernels (csrc/frames_triangulate.inc) and the host
-// tap (aos2_debug_triangulate_host): the translation units are built with -ffp-contract=off, so both run the same operation
+// gates that decide whether a MapPoint is born.  ONE routine for the device kernels (csrc/frames_keyframe.hip on resident keyframe
+// batches, csrc/triangulate.hip on the matcher's handle; tri_block below is the workgroup form both run) and the host tap
+// (aos2_debug_triangulate_host): the translation units are built with -ffp-contract=off, so all run the same operation
 // sequence.  The OpenCV conventions it restates are DESIGN.md section 2.7:
 //   cv::Mat products, Mat::dot, cv::norm: products and sums in double in index order, an addend widened to double, one rounding;
 //   A.row(k) = xn * Tcw.row(2) - Tcw.row(r): float multiply, float subtract;
@@ -31,7 +32,7 @@ struct TriObs {
     int32_t octave;
 };
 
-// the argument checks of the host-pointer form and the host tap (csrc/matcher.hip): everything the routine indexes with
+// the argument checks of the host-pointer form and the host tap (csrc/triangulate.hip): everything the routine indexes with
 int triang_check(const aos2_triang_geom_t *g, int n, const aos2_triang_obs_t *obs1, const aos2_triang_obs_t *obs2, const float *x3D,
                  const uint8_t *status);
 
@@ -291,6 +292,68 @@ __host__ __device__ inline int triangulate_pair(const TriKf &K1, const TriKf &K2
         if (!tri_dehomogenize(v, x3D)) return AOS2_TRI_W_ZERO;
     } else {
         tri_unproject(branch == TRI_BRANCH_STEREO1 ? K1 : K2, branch == TRI_BRANCH_STEREO1 ? o1 : o2, x3D);
+    }
+    return tri_gates(K1, K2, o1, o2, x3D);
+}
+
+// ---- device only: the workgroup form the kernels of triangulate.hip and frames_keyframe.hip run
+
+// number of set bits of a ballot below this lane (v_mbcnt_lo + v_mbcnt_hi)
+__device__ __forceinline__ int tri_lanes_below(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// One matched pair per thread of a 256-thread workgroup whose threads share (K1, K2); every thread of the workgroup calls it.
+// The cheap part (rays, parallax, the choice of branch) runs where the match is.  Typically under a tenth of a keyframe's features
+// are matched, and the Jacobi SVD is a few thousand f64 instructions: under the divergent `if` most lanes of all four waves would
+// idle through it.  So the items that need it are compacted per workgroup (ballot + mbcnt, their xn in LDS), the first `total`
+// threads run the SVD on dense lanes -- the sweep loop of a wave ends when none of its lanes rotated; a sweep on a converged lane
+// changes nothing, so a lane's result does not depend on its neighbours -- and every item picks its vt.row(3) up again.
+__device__ __forceinline__ int tri_block(bool matched, const TriKf &K1, const TriKf &K2, const TriObs &o1, const TriObs &o2, float x3D[3])
+{
+    __shared__ float s_v[4][256];
+    __shared__ int s_wcnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float xn[4] = {0.f, 0.f, 0.f, 0.f};
+    int branch = TRI_BRANCH_NONE;
+    if (matched) branch = tri_front(K1, K2, o1, o2, xn);
+    const bool need = branch == TRI_BRANCH_SVD;
+    const unsigned long long bal = __ballot(need);
+    if (lane == 0) s_wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = s_wcnt[w];
+        if (w < wave) base += c;
+        total += c;
+    }
+    const int slot = base + tri_lanes_below(bal);   // < 256: at most one item per thread
+    if (need) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_v[k][slot] = xn[k];
+    }
+    __syncthreads();
+    if (tid < total) {
+        float in[4], v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[k] = s_v[k][tid];
+        tri_svd_null(K1, K2, in, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_v[k][tid] = v[k];
+    }
+    __syncthreads();
+    x3D[0] = x3D[1] = x3D[2] = 0.0f;
+    if (!matched) return AOS2_TRI_NO_MATCH;
+    if (branch == TRI_BRANCH_NONE) return AOS2_TRI_LOW_PARALLAX;
+    if (need) {
+        const float v[4] = {s_v[0][slot], s_v[1][slot], s_v[2][slot], s_v[3][slot]};
+        if (!tri_dehomogenize(v, x3D)) return AOS2_TRI_W_ZERO;
+    } else if (branch == TRI_BRANCH_STEREO1) {
+        tri_unproject(K1, o1, x3D);
+    } else {
+        tri_unproject(K2, o2, x3D);
     }
     return tri_gates(K1, K2, o1, o2, x3D);
 }

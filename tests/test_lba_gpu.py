@@ -105,7 +105,7 @@ def test_pose_optimization_vs_oracle(pkg, oracle, gpu, cfg):
 
 
 def test_pose_optimization_slot_count_boundaries(pkg, oracle, gpu):
-    """The edge passes run a wave's edges K at a time, K = the slots the WAVE uses (pose_opt.hip): correspondence counts around every
+    """The edge passes run a wave's edges K at a time, K = the slots the WAVE uses (pose_opt.h): correspondence counts around every
     change of a wave's slot count -- 64 w and 256 j + 64 w (+- 1) for the 256-thread kernel that keeps <= 4 edges per thread in
     registers, and beyond 1024 the kernel that leaves them in memory -- one call with all of them (problems of different sizes share a launch),
     with mono-only, stereo-only and mixed edges and enough outliers for edges to leave at every round."""
@@ -152,7 +152,7 @@ def test_pose_optimization_three_to_seven_correspondences(pkg, oracle, gpu):
 
 
 def test_pose_solver_building_blocks(pkg, oracle, gpu):
-    """pose_opt.hip's serial path uses its own exp-map update (polynomial small-angle form, a general form beyond
+    """pose_opt.h's serial path uses its own exp-map update (polynomial small-angle form, a general form beyond
     |omega|^2 = 0.6, the reference's first-order form below 1e-5 rad) and a square-root-free 6x6 solve: every branch against
     the oracle's se3quat restatement / numpy, to 1e-12 (they differ by rounding only)."""
     rng = np.random.default_rng(7)

@@ -1,4 +1,4 @@
-"""The edge pass and the outlier pass of pose_optimization_body (csrc/pose_opt.hip) alone, in every instantiation -- <4,256>, <8,256>, <9,128>
+"""The edge pass and the outlier pass of pose_optimization_body (csrc/pose_opt.h) alone, in every instantiation -- <4,256>, <8,256>, <9,128>
 and <0,256>: the K = 1..4 straight-line block, the K = 2 chunks with an odd tail, the one-by-one loop over global memory -- through the tap
 aos2_debug_pose_pass_device, which runs the shipped body itself, against tests/pose_pass_ref.py: the g2o operation in long double with a
 scale M per quantity.  The condition on the 21 + 6 + 1 sums and on the stored per-edge chi2:

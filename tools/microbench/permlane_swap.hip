@@ -1,4 +1,4 @@
-// semantics check of gfx950's v_permlane32_swap / v_permlane16_swap as pose_opt.hip's swap_add uses them:
+// semantics check of gfx950's v_permlane32_swap / v_permlane16_swap as pose_opt.h's swap_add uses them:
 // prints PASS when, for a = lane and b = 100 + lane,
 //   permlane32_swap: lanes < 32 get (a_own, a_of_lane+32), lanes >= 32 get (b_of_lane-32, b_own)
 //   permlane16_swap: even 16-lane rows get (a_own, a_of_lane+16), odd rows get (b_of_lane-16, b_own)
