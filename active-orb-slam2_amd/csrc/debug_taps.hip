@@ -651,8 +651,7 @@ int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2
     if (int st = kf_culling_check_call(g->n_keyframes, n_cand, cand, status, n_mps, n_redundant, bad_points, bad_cap, n_bad_points))
         return st;
     const int np = g->n_points;
-    const KfcGraph G = {np, g->n_keyframes, g->point_bad, g->point_nobs, g->obs_off, g->obs_kf, g->kf_mp_off, g->kf_mp, view->obs_idx,
-                        view->kf_octave, view->kf_depth, view->kf_stereo, view->kf_th_depth, view->kf_flags};
+    const LmGraph G = {{np, g->n_keyframes}, lm_from_public(*g, view)};
     std::vector<int32_t> nobs(g->point_nobs, g->point_nobs + np), stamp(np, -1);
     std::vector<uint8_t> bad(g->point_bad, g->point_bad + np), erased(g->obs_off[np], 0);
     const KfcOverlay X = {nobs.data(), stamp.data(), bad.data(), erased.data()};

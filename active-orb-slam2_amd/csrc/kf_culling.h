@@ -1,9 +1,11 @@
 // LocalMapping::KeyFrameCulling (src/LocalMapping.cc:636-700) over the resident graph of aos2_local_map_*: what csrc/kf_culling.hip
 // shares with the host tap aos2_debug_keyframe_culling_host (csrc/debug_taps.hip) -- the argument checks and the three per-item
 // functions (a feature's part in nMPs / nRedundantObservations, a candidate's verdict, a culled keyframe's erasure at one of its
-// features).  The kernels call them with a lane per item, the tap in the loop's own order on one core.  Internal to the library.
+// features).  The kernels call them with a lane per item, the tap in the loop's own order on one core.  They read the graph and
+// the view through LmGraph (csrc/local_map_arrays.h), device or host addresses.  Internal to the library.
 #pragma once
 #include "aos2_common.h"
+#include "local_map_arrays.h"
 
 #if defined(__HIPCC__)
 #define AOS2_KFC_HD __host__ __device__ __forceinline__
@@ -12,19 +14,6 @@
 #endif
 
 namespace aos2 {
-
-// the parts of the graph and of the view that the loop reads (device or host addresses)
-struct KfcGraph {
-    int n_points, n_kfs;
-    const uint8_t *point_bad;
-    const int32_t *point_nobs, *obs_off, *obs_kf, *kf_mp_off, *kf_mp;
-    const int32_t *obs_idx;
-    const int8_t *kf_octave;
-    const float *kf_depth;
-    const uint8_t *kf_stereo;
-    const float *kf_th_depth;
-    const uint8_t *kf_flags;
-};
 
 // What the culls of one call have changed so far.  The graph itself is never written: nobs and bad start as copies of point_nobs
 // and point_bad, erased marks the observation entries that EraseObservation removed, stamp holds the last candidate whose erasure
@@ -61,7 +50,7 @@ AOS2_KFC_HD int kfc_sub(int32_t *p, int v)   // the value before
 
 // :655-695 for the feature at entry f of kf_mp, a feature of keyframe kf: bit 0 = it counts in nMPs, bit 1 = in
 // nRedundantObservations
-AOS2_KFC_HD int kfc_feature(const KfcGraph &G, const KfcOverlay &X, int monocular, int kf, int f)
+AOS2_KFC_HD int kfc_feature(const LmGraph &G, const KfcOverlay &X, int monocular, int kf, int f)
 {
     const int pMP = G.kf_mp[f];
     if (pMP < 0) return 0;      // :658
@@ -100,7 +89,7 @@ AOS2_KFC_HD int kfc_status(int flags, int nMPs, int nRedundantObservations)
 
 // KeyFrame::SetBadFlag (src/KeyFrame.cc:530-532) of candidate ci = keyframe kf, at entry f of kf_mp:
 // mvpMapPoints[i]->EraseObservation(this) (src/MapPoint.cc:144-170).  Returns whether the point went bad here.
-AOS2_KFC_HD bool kfc_erase(const KfcGraph &G, const KfcOverlay &X, int kf, int ci, int f)
+AOS2_KFC_HD bool kfc_erase(const LmGraph &G, const KfcOverlay &X, int kf, int ci, int f)
 {
     const int pMP = G.kf_mp[f];
     if (pMP < 0) return false;

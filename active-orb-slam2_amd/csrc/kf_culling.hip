@@ -42,7 +42,7 @@ struct KfcCall {
     int32_t *bad_rows;        // [n_points] in the order they went bad
 };
 
-__global__ __launch_bounds__(kIT) void k_kfc_init(KfcGraph G, KfcOverlay X, KfcCall C, int n_obs)
+__global__ __launch_bounds__(kIT) void k_kfc_init(LmGraph G, KfcOverlay X, KfcCall C, int n_obs)
 {
     const int stride = gridDim.x * kIT, t0 = blockIdx.x * kIT + threadIdx.x;
     for (int p = t0; p < G.n_points; p += stride) {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kIT) void k_kfc_init(KfcGraph G, KfcOverlay X, KfcC
     if (t0 < kCtlInts) C.ctl[t0] = 0;
 }
 
-__global__ __launch_bounds__(kCT) void k_kfc_count(KfcGraph G, KfcOverlay X, KfcCall C)
+__global__ __launch_bounds__(kCT) void k_kfc_count(LmGraph G, KfcOverlay X, KfcCall C)
 {
     __shared__ int s_sum[2];
     const int ci = blockIdx.x, tid = threadIdx.x;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kCT) void k_kfc_count(KfcGraph G, KfcOverlay X, Kfc
     }
 }
 
-__global__ __launch_bounds__(kAT) void k_kfc_apply(KfcGraph G, KfcOverlay X, KfcCall C)
+__global__ __launch_bounds__(kAT) void k_kfc_apply(LmGraph G, KfcOverlay X, KfcCall C)
 {
     __shared__ int s_culled, s_next;
     const int tid = threadIdx.x;
@@ -120,35 +120,6 @@ __global__ __launch_bounds__(kAT) void k_kfc_apply(KfcGraph G, KfcOverlay X, Kfc
     }
 }
 
-bool null_with_length(const void *p, int64_t n) { return n > 0 && !p; }
-
-// the handle's view on the device if it is not there yet
-int upload_view(aos2_local_map *h)
-{
-    KfcState &K = h->kfc;
-    if (!K.dirty) return AOS2_OK;
-    if (int st = local_map_refresh_host(h)) return st;   // (the host copy is what goes up)
-    KfcGraph V = {};
-    Regions<6> R;
-    R.add(V.obs_idx, K.obs_idx.size()); R.add(V.kf_octave, K.kf_octave.size()); R.add(V.kf_depth, K.kf_depth.size());
-    R.add(V.kf_stereo, K.kf_stereo.size()); R.add(V.kf_th_depth, K.kf_th_depth.size()); R.add(V.kf_flags, K.kf_flags.size());
-    std::vector<uint8_t> stage(R.bytes() + 256);
-    R.bind(stage.data());
-    auto put = [](const void *dst, const auto &v) {
-        if (!v.empty()) memcpy(const_cast<void *>(dst), v.data(), v.size() * sizeof(v[0]));
-    };
-    put(V.obs_idx, K.obs_idx); put(V.kf_octave, K.kf_octave); put(V.kf_depth, K.kf_depth); put(V.kf_stereo, K.kf_stereo);
-    put(V.kf_th_depth, K.kf_th_depth); put(V.kf_flags, K.kf_flags);
-    if (int st = bind_device(h->device)) return st;
-    AOS2_HIP_CHECK(hipDeviceSynchronize());   // (a call that still reads the previous view)
-    if (int st = K.d_view.alloc(stage.size())) return st;
-    AOS2_HIP_CHECK(hipMemcpy(K.d_view.p, stage.data(), R.bytes(), hipMemcpyHostToDevice));
-    R.bind(K.d_view.p);
-    K.V = V;
-    K.dirty = false;
-    return AOS2_OK;
-}
-
 }  // namespace
 
 namespace aos2 {
@@ -159,22 +130,13 @@ int kf_culling_check_view(const aos2_local_map_graph_t *g, const aos2_kf_culling
         set_error("bad argument");
         return AOS2_ERR_ARG;
     }
-    const int np = g->n_points, nk = g->n_keyframes;
-    const int n_obs = g->obs_off[np], n_mp = g->kf_mp_off[nk];
-    if (null_with_length(v->obs_idx, n_obs) || null_with_length(v->kf_octave, n_mp) || null_with_length(v->kf_depth, n_mp) ||
-        null_with_length(v->kf_stereo, n_mp) || null_with_length(v->kf_th_depth, nk) || null_with_length(v->kf_flags, nk)) {
-        set_error("keyframe culling: an array of the view is NULL");
+    const size_t np = (size_t)g->n_points, nk = (size_t)g->n_keyframes;
+    const LmArrays<LmPtr> A = lm_from_public(*g, v);
+    if (lm_null_with_length(A, LmCounts{np, nk, nk, (size_t)A.obs_off[np], (size_t)A.kf_mp_off[nk], 0}, kLmView))
+        return lm_fail("keyframe culling", "an array of the view is NULL");
+    if (lm_bad_obs_idx("keyframe culling", (int)np, nullptr, A.obs_off, A.obs_kf, A.obs_idx,
+                       [&](int kf) { return A.kf_mp_off[kf + 1] - A.kf_mp_off[kf]; }))
         return AOS2_ERR_ARG;
-    }
-    for (int p = 0; p < np; ++p)
-        for (int e = g->obs_off[p]; e < g->obs_off[p + 1]; ++e) {
-            const int kf = g->obs_kf[e], nf = g->kf_mp_off[kf + 1] - g->kf_mp_off[kf];
-            if (v->obs_idx[e] < 0 || v->obs_idx[e] >= nf) {
-                set_error("keyframe culling: obs_idx[%d] = %d of point %d is outside the %d features of keyframe %d", e, v->obs_idx[e], p,
-                          nf, kf);
-                return AOS2_ERR_ARG;
-            }
-        }
     return AOS2_OK;
 }
 
@@ -182,20 +144,14 @@ int kf_culling_check_call(int n_keyframes, int n_cand, const int32_t *cand, cons
                           const int32_t *n_redundant, const int32_t *bad_points, int bad_cap, const int32_t *n_bad_points)
 {
     if (n_cand < 0 || bad_cap < 0 || !n_bad_points || (bad_cap > 0 && !bad_points) ||
-        (n_cand > 0 && (!cand || !status || !n_mps || !n_redundant))) {
-        set_error("keyframe culling: bad argument (%d candidates, room for %d bad points)", n_cand, bad_cap);
-        return AOS2_ERR_ARG;
-    }
+        (n_cand > 0 && (!cand || !status || !n_mps || !n_redundant)))
+        return lm_fail("keyframe culling", "bad argument (%d candidates, room for %d bad points)", n_cand, bad_cap);
     std::vector<uint8_t> listed(n_keyframes, 0);
     for (int i = 0; i < n_cand; ++i) {
-        if (cand[i] < 0 || cand[i] >= n_keyframes) {
-            set_error("keyframe culling: cand[%d] = %d is outside [0, %d)", i, cand[i], n_keyframes);
-            return AOS2_ERR_ARG;
-        }
-        if (listed[cand[i]]) {
-            set_error("keyframe culling: keyframe %d is listed twice", cand[i]);
-            return AOS2_ERR_ARG;
-        }
+        if (cand[i] < 0 || cand[i] >= n_keyframes)
+            return lm_fail("keyframe culling", "cand[%d] = %d is outside [0, %d)", i, cand[i], n_keyframes);
+        if (listed[cand[i]])
+            return lm_fail("keyframe culling", "keyframe %d is listed twice", cand[i]);
         listed[cand[i]] = 1;
     }
     return AOS2_OK;
@@ -211,28 +167,16 @@ int aos2_local_map_set_culling_view(aos2_local_map_t *h, const aos2_kf_culling_v
         set_error("bad argument");
         return AOS2_ERR_ARG;
     }
-    if (!h->has_graph) {
-        set_error("keyframe culling: aos2_local_map_set comes first");
-        return AOS2_ERR_ARG;
-    }
+    if (!h->has_graph)
+        return lm_fail("keyframe culling", "aos2_local_map_set comes first");
     aos2_local_map_graph_t g;
     if (int st = aos2_local_map_get(h, &g)) return st;   // (after a rebuild on the device: the download of the host copy)
     if (int st = kf_culling_check_view(&g, view)) return st;
-    const size_t n_obs = (size_t)h->n_obs, n_mp = (size_t)h->n_mp, nk = (size_t)h->n_kfs;
     KfcState &K = h->kfc;
-    auto take = [](auto &v, const auto *p, size_t n) {
-        if (n) v.assign(p, p + n);
-        else v.clear();
-    };
-    take(K.obs_idx, view->obs_idx, n_obs);
-    take(K.kf_octave, view->kf_octave, n_mp);
-    take(K.kf_depth, view->kf_depth, n_mp);
-    take(K.kf_stereo, view->kf_stereo, n_mp);
-    take(K.kf_th_depth, view->kf_th_depth, nk);
-    take(K.kf_flags, view->kf_flags, nk);
+    lm_take(h->M, lm_from_public(g, view), h->counts(), kLmView);
     K.has_view = true;
     K.dirty = true;
-    return upload_view(h);
+    return local_map_upload(h, kLmView);
 }
 
 int aos2_local_map_debug_culling_rounds(aos2_local_map_t *h, int rounds)
@@ -255,10 +199,8 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
         return AOS2_ERR_ARG;
     }
     KfcState &K = h->kfc;
-    if (!K.has_view) {
-        set_error("keyframe culling: aos2_local_map_set_culling_view comes first (aos2_local_map_set drops the view)");
-        return AOS2_ERR_ARG;
-    }
+    if (!K.has_view)
+        return lm_fail("keyframe culling", "aos2_local_map_set_culling_view comes first (aos2_local_map_set drops the view)");
     int st;
     if ((st = kf_culling_check_call(h->n_kfs, n_cand, cand, status, n_mps, n_redundant, bad_points, bad_cap, n_bad_points))) return st;
     const size_t np = (size_t)h->n_points, n_obs = (size_t)h->n_obs, nc = (size_t)n_cand;
@@ -271,18 +213,15 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
     const size_t out0 = R.add(C.ctl, kCtlInts);
     R.add(C.n_mps, nc); R.add(C.n_red, nc); R.add(C.status, nc);
     const size_t out_bytes = R.bytes() - out0;
-    if ((int64_t)R.bytes() > h->scratch_bytes) {
-        set_error("keyframe culling: %zu points and %zu observations need %zu bytes of scratch, the bound is %lld", np, n_obs, R.bytes(),
-                  (long long)h->scratch_bytes);
-        return AOS2_ERR_ARG;
-    }
+    if ((int64_t)R.bytes() > h->scratch_bytes)
+        return lm_fail("keyframe culling", "%zu points and %zu observations need %zu bytes of scratch, the bound is %lld", np, n_obs,
+                       R.bytes(), (long long)h->scratch_bytes);
     K.last_rounds = 0;
-    K.timed = false;
+    K.timer.timed = false;
     *n_bad_points = 0;
     if (n_cand == 0) return AOS2_OK;
     if ((st = bind_device(h->device))) return st;
-    if ((st = local_map_upload(h))) return st;
-    if ((st = upload_view(h))) return st;
+    if ((st = local_map_upload(h, kLmGraph)) || (st = local_map_upload(h, kLmView))) return st;
     if (!h->stream && (st = stream_create(&h->stream, false))) return st;
     if ((st = h->d_scratch.alloc((R.bytes() + 256) / 4))) return st;
     R.bind(reinterpret_cast<uint8_t *>(h->d_scratch.p));
@@ -290,18 +229,11 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
     const size_t io_out = up256(nc * 4), io_bad = io_out + up256(out_bytes);
     if ((st = K.io.alloc(io_bad + np * 4 + 256))) return st;
     memcpy(K.io.p, cand, nc * 4);
-    KfcGraph G = K.V;
-    G.n_points = h->n_points; G.n_kfs = h->n_kfs;
-    G.point_bad = h->G.point_bad; G.point_nobs = h->G.point_nobs; G.obs_off = h->G.obs_off; G.obs_kf = h->G.obs_kf;
-    G.kf_mp_off = h->G.kf_mp_off; G.kf_mp = h->G.kf_mp;
+    const LmGraph &G = h->G;
     C.n_cand = n_cand;
     C.monocular = monocular ? 1 : 0;
     hipStream_t q = h->stream;
-    if (!K.ev0) {
-        AOS2_HIP_CHECK(hipEventCreate(&K.ev0));
-        AOS2_HIP_CHECK(hipEventCreate(&K.ev1));
-    }
-    AOS2_HIP_CHECK(hipEventRecord(K.ev0, q));
+    if ((st = K.timer.begin(q))) return st;
     AOS2_HIP_CHECK(hipMemcpyAsync(const_cast<int32_t *>(C.cand), K.io.p, nc * 4, hipMemcpyHostToDevice, q));
     const int init_blocks = (int)std::min<size_t>(1024, (std::max(np, n_obs) + kIT - 1) / kIT + 1);
     hipLaunchKernelGGL(k_kfc_init, dim3(init_blocks), dim3(kIT), 0, q, G, X, C, (int)n_obs);
@@ -331,9 +263,7 @@ int aos2_local_map_keyframe_culling(aos2_local_map_t *h, int monocular, int n_ca
         if (bad_cap > 0) memcpy(bad_points, rows, (size_t)std::min(nb, bad_cap) * 4);
     }
     *n_bad_points = nb;
-    AOS2_HIP_CHECK(hipEventRecord(K.ev1, q));
-    K.timed = true;
-    return AOS2_OK;
+    return K.timer.end(q, false);
 }
 
 int aos2_local_map_get_culling_view(const aos2_local_map_t *ch, aos2_kf_culling_view_t *view, int32_t *has_view)
@@ -347,18 +277,13 @@ int aos2_local_map_get_culling_view(const aos2_local_map_t *ch, aos2_kf_culling_
     if (has_view) *has_view = h->kfc.has_view ? 1 : 0;
     if (!h->kfc.has_view) return AOS2_OK;
     if (int st = local_map_refresh_host(h)) return st;
-    const KfcState &K = h->kfc;
-    view->obs_idx = K.obs_idx.data(); view->kf_octave = K.kf_octave.data(); view->kf_depth = K.kf_depth.data();
-    view->kf_stereo = K.kf_stereo.data(); view->kf_th_depth = K.kf_th_depth.data(); view->kf_flags = K.kf_flags.data();
+    lm_to_public(lm_data(h->M), nullptr, view);
     return AOS2_OK;
 }
 
 float aos2_local_map_last_culling_device_ms(aos2_local_map_t *h)
 {
-    float ms = 0.f;
-    if (!h || !h->kfc.timed || hipEventSynchronize(h->kfc.ev1) != hipSuccess || hipEventElapsedTime(&ms, h->kfc.ev0, h->kfc.ev1) != hipSuccess)
-        return -1.f;
-    return ms;
+    return h ? h->kfc.timer.ms() : -1.f;
 }
 
 }  // extern "C"

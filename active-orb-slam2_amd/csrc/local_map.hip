@@ -71,7 +71,7 @@ __device__ __forceinline__ void lm_append(unsigned long long m, int cand, int32_
 
 // Tracking::UpdateLocalKeyFrames (:1411-1519) for frame b0 + blockIdx.x.  The global counters are zero at entry.
 template <bool kLds>
-__global__ __launch_bounds__(kNT) void k_lm_keyframes(FramesDev S, LmGraphDev G, LmOut O, LmScratch X, int b0)
+__global__ __launch_bounds__(kNT) void k_lm_keyframes(FramesDev S, LmGraph G, LmOut O, LmScratch X, int b0)
 {
     __shared__ int32_t s_cnt[kLds ? kLdsKfs : 1];
     __shared__ int32_t s_wsum[kNT / 64];
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kNT) void k_lm_keyframes(FramesDev S, LmGraphDev G,
 }
 
 // Tracking::UpdateLocalPoints (:1385-1408) for frame b0 + blockIdx.x.  The position table holds 0xffffffff ("no candidate yet") at entry.
-__global__ __launch_bounds__(kPT) void k_lm_points(LmGraphDev G, LmOut O, LmScratch X, int b0)
+__global__ __launch_bounds__(kPT) void k_lm_points(LmGraph G, LmOut O, LmScratch X, int b0)
 {
     __shared__ int32_t s_wsum[kPT / 64];
     const int g = blockIdx.x, b = b0 + g, tid = threadIdx.x;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kPT) void k_lm_points(LmGraphDev G, LmOut O, LmScra
 }
 
 // :1040-1071 for frame blockIdx.x
-__global__ __launch_bounds__(kNT) void k_lm_stats(FramesDev S, LmGraphDev G, int stereo, int only_tracking, int32_t *__restrict__ stats,
+__global__ __launch_bounds__(kNT) void k_lm_stats(FramesDev S, LmGraph G, int stereo, int only_tracking, int32_t *__restrict__ stats,
                                                   int32_t *__restrict__ found_inc)
 {
     __shared__ int s_sum[3];
@@ -259,114 +259,111 @@ __global__ __launch_bounds__(kNT) void k_lm_stats(FramesDev S, LmGraphDev G, int
     if (tid < 3) stats[3 * (size_t)b + tid] = s_sum[tid];
 }
 
-bool bad_off(const int32_t *off, int n, const char *what)
-{
-    if (off[0] != 0) {
-        set_error("local map: %s starts at %d", what, off[0]);
-        return true;
-    }
-    for (int i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) {
-            set_error("local map: %s decreases at row %d", what, i);
-            return true;
-        }
-    return false;
-}
-
-bool bad_rows(const int32_t *rows, int n, int lo, int hi, const char *what)
-{
-    for (int i = 0; i < n; ++i)
-        if (rows[i] < lo || rows[i] >= hi) {
-            set_error("local map: %s[%d] = %d is outside [%d, %d)", what, i, rows[i], lo, hi);
-            return true;
-        }
-    return false;
-}
-
 }  // namespace
 
 namespace aos2 {
 
+int lm_fail(const char *prefix, const char *fmt, ...)
+{
+    char msg[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    set_error("%s: %s", prefix, msg);
+    return AOS2_ERR_ARG;
+}
+
+bool lm_bad_offsets(const char *prefix, const int32_t *off, int n, const char *what)
+{
+    if (!off) return lm_fail(prefix, "%s is NULL", what);
+    if (off[0] != 0) return lm_fail(prefix, "%s starts at %d", what, off[0]);
+    for (int i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return lm_fail(prefix, "%s decreases at row %d", what, i);
+    return false;
+}
+
+bool lm_bad_values(const char *prefix, const int32_t *v, int64_t n, int lo, int hi, const char *what)
+{
+    if (n > 0 && !v) return lm_fail(prefix, "%s is NULL", what);
+    for (int64_t i = 0; i < n; ++i)
+        if (v[i] < lo || v[i] >= hi) return lm_fail(prefix, "%s[%lld] = %d is outside [%d, %d)", what, (long long)i, v[i], lo, hi);
+    return false;
+}
+
+bool lm_listed_twice(const char *prefix, int n_rows, const int32_t *row_name, const int32_t *obs_off, const int32_t *obs_kf, int nk)
+{
+    std::vector<int32_t> seen(nk, -1);   // the row that listed a keyframe last
+    for (int i = 0; i < n_rows; ++i)
+        for (int e = obs_off[i]; e < obs_off[i + 1]; ++e) {
+            if (seen[obs_kf[e]] == i) return lm_fail(prefix, "point %d lists keyframe %d twice", row_name ? row_name[i] : i, obs_kf[e]);
+            seen[obs_kf[e]] = i;
+        }
+    return false;
+}
+
 int local_map_check(const aos2_local_map_graph_t *g, int *max_features)
 {
+    static const char *const pre = "local map";
     if (!g) {
         set_error("bad argument");
         return AOS2_ERR_ARG;
     }
     const int np = g->n_points, nk = g->n_keyframes;
-    if (np < 0 || nk < 0) {
-        set_error("local map: negative count (%d points, %d keyframes)", np, nk);
+    if (np < 0 || nk < 0) return lm_fail(pre, "negative count (%d points, %d keyframes)", np, nk);
+    const LmArrays<LmPtr> A = lm_from_public(*g, nullptr);
+    LmCounts c = {(size_t)np, (size_t)nk, (size_t)nk, 0, 0, 0};   // the rows and offsets; the offsets then give the entries
+    if (lm_null_with_length(A, c, kLmGraph)) return lm_fail(pre, "an array is NULL");
+    if (lm_bad_offsets(pre, A.obs_off, np, "obs_off") || lm_bad_offsets(pre, A.kf_mp_off, nk, "kf_mp_off") ||
+        lm_bad_offsets(pre, A.kf_child_off, nk, "kf_child_off"))
         return AOS2_ERR_ARG;
-    }
-    if (!g->obs_off || !g->kf_mp_off || !g->kf_child_off || (np > 0 && (!g->point_bad || !g->point_nobs)) ||
-        (nk > 0 && (!g->kf_bad || !g->kf_best || !g->kf_parent))) {
-        set_error("local map: an array is NULL");
+    c.obs = A.obs_off[np]; c.mp = A.kf_mp_off[nk]; c.child = A.kf_child_off[nk];
+    if (lm_null_with_length(A, c, kLmGraph)) return lm_fail(pre, "an array is NULL");
+    if (lm_bad_values(pre, A.obs_kf, c.obs, 0, nk, "obs_kf") || lm_bad_values(pre, A.kf_mp, c.mp, -1, np, "kf_mp") ||
+        lm_bad_values(pre, A.kf_best, (int64_t)nk * kLmNeighbours, -1, nk, "kf_best") ||
+        lm_bad_values(pre, A.kf_child, c.child, 0, nk, "kf_child") || lm_bad_values(pre, A.kf_parent, nk, -1, nk, "kf_parent"))
         return AOS2_ERR_ARG;
-    }
-    if (bad_off(g->obs_off, np, "obs_off") || bad_off(g->kf_mp_off, nk, "kf_mp_off") || bad_off(g->kf_child_off, nk, "kf_child_off"))
-        return AOS2_ERR_ARG;
-    const int n_obs = g->obs_off[np], n_mp = g->kf_mp_off[nk], n_child = g->kf_child_off[nk];
-    if ((n_obs > 0 && !g->obs_kf) || (n_mp > 0 && !g->kf_mp) || (n_child > 0 && !g->kf_child)) {
-        set_error("local map: an array is NULL");
-        return AOS2_ERR_ARG;
-    }
-    if (bad_rows(g->obs_kf, n_obs, 0, nk, "obs_kf") || bad_rows(g->kf_mp, n_mp, -1, np, "kf_mp") ||
-        bad_rows(g->kf_best, nk * kLmNeighbours, -1, nk, "kf_best") || bad_rows(g->kf_child, n_child, 0, nk, "kf_child") ||
-        bad_rows(g->kf_parent, nk, -1, nk, "kf_parent"))
-        return AOS2_ERR_ARG;
-    std::vector<int32_t> seen(nk, -1);   // the point that listed a keyframe last
-    for (int p = 0; p < np; ++p)
-        for (int e = g->obs_off[p]; e < g->obs_off[p + 1]; ++e) {
-            if (seen[g->obs_kf[e]] == p) {
-                set_error("local map: point %d lists keyframe %d twice", p, g->obs_kf[e]);
-                return AOS2_ERR_ARG;
-            }
-            seen[g->obs_kf[e]] = p;
-        }
+    if (lm_listed_twice(pre, np, nullptr, A.obs_off, A.obs_kf, nk)) return AOS2_ERR_ARG;
     int mf = 0;
-    for (int k = 0; k < nk; ++k) mf = std::max(mf, g->kf_mp_off[k + 1] - g->kf_mp_off[k]);
+    for (int k = 0; k < nk; ++k) mf = std::max(mf, A.kf_mp_off[k + 1] - A.kf_mp_off[k]);
     if (max_features) *max_features = mf;
     return AOS2_OK;
 }
 
 }  // namespace aos2
 
-namespace {
+namespace aos2 {
 
-// the handle's host copy as one block of 256-byte aligned regions, copied in one piece
-int upload(aos2_local_map *h)
+int local_map_upload(aos2_local_map *h, int part)
 {
-    if (!h->dirty) return AOS2_OK;
-    if (int st = local_map_refresh_host(h)) return st;   // (the host copy is what goes up)
-    LmGraphDev G = {};
+    KfcState &K = h->kfc;
+    bool &dirty = part == kLmGraph ? h->dirty : K.dirty;
+    DevBuf<uint8_t> &buf = part == kLmGraph ? h->d_graph : K.d_view;
+    if (!dirty) return AOS2_OK;
+    if (int st = local_map_refresh_host(h)) return st;   // (the mirror is what goes up)
+    // the other part's pointers stay -- unless that part is the view and is not on the device: NULL until its own upload, and
+    // it lies in no block
+    if (!K.has_view || K.dirty) K.in_graph_block = false;
+    LmGraph G = K.has_view && (part == kLmView || !K.dirty) ? h->G : LmGraph{};
     G.n_points = h->n_points;
     G.n_kfs = h->n_kfs;
     Regions<11> R;
-    R.add(G.point_bad, h->point_bad.size()); R.add(G.kf_bad, h->kf_bad.size()); R.add(G.point_nobs, h->point_nobs.size());
-    R.add(G.obs_off, h->obs_off.size()); R.add(G.obs_kf, h->obs_kf.size()); R.add(G.kf_mp_off, h->kf_mp_off.size());
-    R.add(G.kf_mp, h->kf_mp.size()); R.add(G.kf_best, h->kf_best.size()); R.add(G.kf_child_off, h->kf_child_off.size());
-    R.add(G.kf_child, h->kf_child.size()); R.add(G.kf_parent, h->kf_parent.size());
+    lm_layout(R, G, h->counts(), part);
     std::vector<uint8_t> stage(R.bytes() + 256);
     R.bind(stage.data());
-    auto put = [](const void *dst, const auto &v) {
-        if (!v.empty()) memcpy(const_cast<void *>(dst), v.data(), v.size() * sizeof(v[0]));
-    };
-    put(G.point_bad, h->point_bad); put(G.kf_bad, h->kf_bad); put(G.point_nobs, h->point_nobs); put(G.obs_off, h->obs_off);
-    put(G.obs_kf, h->obs_kf); put(G.kf_mp_off, h->kf_mp_off); put(G.kf_mp, h->kf_mp); put(G.kf_best, h->kf_best);
-    put(G.kf_child_off, h->kf_child_off); put(G.kf_child, h->kf_child); put(G.kf_parent, h->kf_parent);
+    lm_copy(G, lm_data(h->M), h->counts(), part);
     if (int st = bind_device(h->device)) return st;
-    AOS2_HIP_CHECK(hipDeviceSynchronize());   // (a call that still reads the previous graph)
-    if (int st = h->d_graph.alloc(stage.size())) return st;
-    AOS2_HIP_CHECK(hipMemcpy(h->d_graph.p, stage.data(), R.bytes(), hipMemcpyHostToDevice));
-    R.bind(h->d_graph.p);
+    AOS2_HIP_CHECK(hipDeviceSynchronize());   // (a call that still reads the previous block)
+    if (int st = buf.alloc(stage.size())) return st;
+    AOS2_HIP_CHECK(hipMemcpy(buf.p, stage.data(), R.bytes(), hipMemcpyHostToDevice));
+    R.bind(buf.p);
     h->G = G;
-    h->dirty = false;
+    if (part == kLmView) K.in_graph_block = false;
+    dirty = false;
     return AOS2_OK;
 }
 
-}  // namespace
-
-int aos2::local_map_upload(aos2_local_map *h) { return upload(h); }
+}  // namespace aos2
 
 extern "C" {
 
@@ -378,9 +375,9 @@ int aos2_local_map_create(int device, aos2_local_map_t **out)
     }
     aos2_local_map *h = new aos2_local_map();
     h->device = device;
-    h->obs_off.assign(1, 0);
-    h->kf_mp_off.assign(1, 0);
-    h->kf_child_off.assign(1, 0);
+    h->M.obs_off.assign(1, 0);
+    h->M.kf_mp_off.assign(1, 0);
+    h->M.kf_child_off.assign(1, 0);
     *out = h;
     return AOS2_OK;
 }
@@ -397,8 +394,8 @@ void aos2_local_map_destroy(aos2_local_map_t *h)
         h->d_spare.release();
         h->d_delta.release();
         h->delta_stage.release();
-        if (h->ap_ev0) (void)hipEventDestroy(h->ap_ev0);
-        if (h->ap_ev1) (void)hipEventDestroy(h->ap_ev1);
+        h->apply_timer.release();
+        h->kfc.timer.release();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;
@@ -413,43 +410,21 @@ int aos2_local_map_set(aos2_local_map_t *h, const aos2_local_map_graph_t *g)
     int mf = 0;
     if (int st = local_map_check(g, &mf)) return st;
     const int np = g->n_points, nk = g->n_keyframes;
-    auto take = [](auto &v, const auto *p, size_t n) { v.assign(p, p + n); };
     h->n_points = np;
     h->n_kfs = nk;
     h->max_features = mf;
-    if (np) {
-        take(h->point_bad, g->point_bad, np);
-        take(h->point_nobs, g->point_nobs, np);
-    } else {
-        h->point_bad.clear();
-        h->point_nobs.clear();
-    }
-    take(h->obs_off, g->obs_off, (size_t)np + 1);
-    if (h->obs_off[np]) take(h->obs_kf, g->obs_kf, h->obs_off[np]);
-    else h->obs_kf.clear();
-    if (nk) {
-        take(h->kf_bad, g->kf_bad, nk);
-        take(h->kf_best, g->kf_best, (size_t)nk * kLmNeighbours);
-        take(h->kf_parent, g->kf_parent, nk);
-    } else {
-        h->kf_bad.clear();
-        h->kf_best.clear();
-        h->kf_parent.clear();
-    }
-    take(h->kf_mp_off, g->kf_mp_off, (size_t)nk + 1);
-    if (h->kf_mp_off[nk]) take(h->kf_mp, g->kf_mp, h->kf_mp_off[nk]);
-    else h->kf_mp.clear();
-    take(h->kf_child_off, g->kf_child_off, (size_t)nk + 1);
-    if (h->kf_child_off[nk]) take(h->kf_child, g->kf_child, h->kf_child_off[nk]);
-    else h->kf_child.clear();
+    h->n_obs = g->obs_off[np]; h->n_mp = g->kf_mp_off[nk]; h->n_child = g->kf_child_off[nk];
+    LmArrays<LmVec> &M = h->M;
+    lm_take(M, lm_from_public(*g, nullptr), h->counts(), kLmGraph);
     // set<KeyFrame*> spChilds: ascending row stands for the pointer order, each child once
-    for (int k = 0; k < nk; ++k) std::sort(h->kf_child.begin() + h->kf_child_off[k], h->kf_child.begin() + h->kf_child_off[k + 1]);
+    for (int k = 0; k < nk; ++k) std::sort(M.kf_child.begin() + M.kf_child_off[k], M.kf_child.begin() + M.kf_child_off[k + 1]);
     h->dirty = true;
     h->has_graph = true;
     h->host_stale = false;   // (the mirror is the graph again)
     local_map_recount(h);
-    h->kfc.drop_view();   // (its arrays no longer line up with the graph)
-    return upload(h);
+    h->kfc.has_view = false;   // (its arrays no longer line up with the graph)
+    h->kfc.dirty = true;
+    return local_map_upload(h, kLmGraph);
 }
 
 int aos2_local_map_get(const aos2_local_map_t *ch, aos2_local_map_graph_t *g)
@@ -463,11 +438,7 @@ int aos2_local_map_get(const aos2_local_map_t *ch, aos2_local_map_graph_t *g)
         if (int st = local_map_refresh_host(h)) return st;
         g->n_points = h->n_points;
         g->n_keyframes = h->n_kfs;
-        g->point_bad = h->point_bad.data(); g->point_nobs = h->point_nobs.data();
-        g->obs_off = h->obs_off.data(); g->obs_kf = h->obs_kf.data();
-        g->kf_bad = h->kf_bad.data(); g->kf_mp_off = h->kf_mp_off.data(); g->kf_mp = h->kf_mp.data();
-        g->kf_best = h->kf_best.data(); g->kf_child_off = h->kf_child_off.data(); g->kf_child = h->kf_child.data();
-        g->kf_parent = h->kf_parent.data();
+        lm_to_public(lm_data(h->M), g, nullptr);
     }
     return AOS2_OK;
 }
@@ -492,18 +463,14 @@ static int enqueue_update(aos2_local_map *h, const FramesDev &S, const LmOut &O,
     // the bound: one frame's tables, and 32-bit candidate positions
     const int64_t np = h->n_points, nk = h->n_kfs;
     const int64_t per_frame = 4 * (np + 2 * nk) + 4;
-    if (per_frame > h->scratch_bytes) {
-        set_error("local map: %lld points and %lld keyframes need %lld bytes of scratch per frame, the bound is %lld", (long long)np,
-                  (long long)nk, (long long)per_frame, (long long)h->scratch_bytes);
-        return AOS2_ERR_ARG;
-    }
-    if (std::max<int64_t>(nk, O.kf_cap) * h->max_features >= ((int64_t)1 << 31) - 1) {
-        set_error("local map: %lld keyframes of up to %d features exceed the 32-bit candidate positions",
-                  (long long)std::max<int64_t>(nk, O.kf_cap), h->max_features);
-        return AOS2_ERR_ARG;
-    }
+    if (per_frame > h->scratch_bytes)
+        return lm_fail("local map", "%lld points and %lld keyframes need %lld bytes of scratch per frame, the bound is %lld",
+                       (long long)np, (long long)nk, (long long)per_frame, (long long)h->scratch_bytes);
+    if (std::max<int64_t>(nk, O.kf_cap) * h->max_features >= ((int64_t)1 << 31) - 1)
+        return lm_fail("local map", "%lld keyframes of up to %d features exceed the 32-bit candidate positions",
+                       (long long)std::max<int64_t>(nk, O.kf_cap), h->max_features);
     int st;
-    if ((st = upload(h))) return st;
+    if ((st = local_map_upload(h, kLmGraph))) return st;
     const int B = S.batch;
     const int group = (int)std::min<int64_t>(B, h->scratch_bytes / per_frame);
     LmScratch X;
@@ -535,10 +502,8 @@ int aos2_frames_update_local_map(aos2_frames_t *f, const aos2_local_map_t *cm, i
         set_error("bad argument (aos2_frames_build comes first; five device arrays of positive capacity)");
         return AOS2_ERR_ARG;
     }
-    if (f->device != h->device) {
-        set_error("local map: the batch is on device %d, the graph on device %d", f->device, h->device);
-        return AOS2_ERR_ARG;
-    }
+    if (f->device != h->device)
+        return lm_fail("local map", "the batch is on device %d, the graph on device %d", f->device, h->device);
     if (int st = bind_device(f->device)) return st;
     const LmOut O = {d_local, d_n_local, d_local_kfs, d_n_local_kfs, d_ref_kf, local_cap, kf_cap};
     return enqueue_update(h, f->D, O, f->stream);
@@ -596,7 +561,7 @@ int aos2_frames_track_local_map_stats(aos2_frames_t *f, const aos2_local_map_t *
     }
     int st = bind_device(f->device);
     if (st) return st;
-    if ((st = upload(h))) return st;
+    if ((st = local_map_upload(h, kLmGraph))) return st;
     hipLaunchKernelGGL(k_lm_stats, dim3(f->D.batch), dim3(kNT), 0, f->stream, f->D, h->G, stereo ? 1 : 0, only_tracking ? 1 : 0, d_stats,
                        d_found_inc);
     AOS2_HIP_CHECK(hipGetLastError());

@@ -411,6 +411,22 @@ def test_region_list_offsets_and_binding(tmp_path):
     assert "regions_test ok: 7 regions, 1536 bytes; host arena ok: 7 fields, 612 of 1280 bytes staged" in out
 
 
+def test_local_map_array_list_layouts_and_round_trip(tmp_path):
+    """The one list of the resident local map's arrays (csrc/local_map_arrays.h), as a stand-alone program under the address and
+    undefined-behaviour sanitizers: lm_each visits 11 arrays without the view and 17 with it, each once; the graph block of a planted
+    graph (3 points, one of them unobserved, 2 keyframes) is 2568 bytes, 4098 with the view, every array on the 256-byte boundary it
+    has always had, and the empty map's block 768; the mirror survives a block of exactly that size and back, zero-length arrays
+    included; a delta's block follows the order of aos2_local_map_apply's upload; an appended row reads 1, 0, 1, -1, -1, 0.f, 0
+    (tests/cpp/local_map_arrays_test.cpp)."""
+    import subprocess
+    exe = str(tmp_path / "local_map_arrays_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "local_map_arrays_test.cpp"), "-I", os.path.join(ROOT, "active-orb-slam2_amd", "csrc"),
+                           "-o", exe])
+    out = subprocess.check_output([exe], text=True)
+    assert "local_map_arrays_test ok: 11 + 6 arrays; graph block 2568 / 4098 bytes, empty map 768; delta block 3332 / 4865 bytes" in out
+
+
 def test_frame_members_of_a_batch_that_was_never_built(pkg):
     """aos2_frames_get / aos2_frames_device_ptr on a batch without a build: whatever the id -- the gettable 0-8, the device-pointer-only
     9 and 10, ids the header does not define -- the one answers with an argument error and the other with NULL, and no device is looked

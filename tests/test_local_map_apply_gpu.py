@@ -131,6 +131,42 @@ def test_planted_delta_on_the_device(rig, c):
     lm.close()
 
 
+def delta_block_bytes(d):
+    """the block a device rebuild uploads: every array at the next 256-byte boundary -- per row set its row
+    list and then its arrays, the graph's part first, the view's behind it"""
+    npr, nmr, nlr = len(d["point_row"]), len(d["kf_mp_row"]), len(d["kf_link_row"])
+    n_obs, n_mp, n_child = (int(d[k][-1]) if len(d[k]) else 0 for k in ("obs_off", "kf_mp_off", "kf_child_off"))
+    sizes = [4 * npr, npr, 4 * npr, 4 * (npr + 1), 4 * n_obs,                        # point_row, point_bad, point_nobs, obs_off, obs_kf
+             4 * nmr, 4 * (nmr + 1), 4 * n_mp,                                       # kf_mp_row, kf_mp_off, kf_mp
+             4 * nlr, nlr, 40 * nlr, 4 * (nlr + 1), 4 * n_child, 4 * nlr]            # kf_link_row, kf_bad, kf_best, kf_child_off, kf_child, kf_parent
+    if d.get("view") is not None:
+        sizes += [4 * n_obs, n_mp, 4 * n_mp, n_mp, 4 * nlr, nlr]                     # obs_idx, kf_octave, kf_depth, kf_stereo, kf_th_depth, kf_flags
+    size = 0
+    for b in sizes:
+        size = ((size + 255) & ~255) + b
+    return size
+
+
+def test_uploaded_bytes_are_the_delta_block(rig):
+    """aos2_local_map_last_apply_bytes pins the layout of the delta through the real call: the planted delta that appends a keyframe
+    (all three row sets, with the view), then an empty delta -- zero rows, so three offsets arrays of one entry each"""
+    c = next(c for c in PLANTED if c["name"] == "append_keyframe")
+    d = c["delta"]
+    assert c["v"] is not None and d["view"] is not None and min(len(d[k]) for k in ("point_row", "kf_mp_row", "kf_link_row")) > 0
+    g, v = cases.want(c)
+    lm = rig.resident(c["g"], c["v"])
+    lm.apply(d)
+    la = lm.last_apply()
+    assert la["path"] == 1 and la["bytes"] == delta_block_bytes(d)
+    empty = cases.delta_between(cases.to_model(g, v), cases.to_model(g, v))
+    assert len(empty["point_row"]) == len(empty["kf_mp_row"]) == len(empty["kf_link_row"]) == 0 and empty["view"] is not None
+    lm.apply(empty)
+    la = lm.last_apply()
+    assert la["path"] == 1 and la["bytes"] == delta_block_bytes(empty) == 768   # (obs_off at 0, kf_mp_off at 256, kf_child_off at 512)
+    check(lm, g, v, "empty delta")
+    lm.close()
+
+
 @pytest.mark.parametrize("seed,peek", [(SEQUENCE_SEEDS[0], True), (SEQUENCE_SEEDS[1], False), (SEQUENCE_SEEDS[2], False)])
 def test_sequence_equals_a_fresh_upload(rig, seed, peek):
     """after every delta of a sequence the applied handle and a NEW handle set to the reference's graph give the same bytes through
