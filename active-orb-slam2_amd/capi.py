@@ -266,6 +266,7 @@ def lib():
             L.aos2_lba_last_program.argtypes = [vp, vp, vp]
             L.aos2_lba_debug_host_phase.argtypes = [vp, ci, ci, vp, vp]
             L.aos2_debug_lba_assemble_device.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+            L.aos2_debug_lba_trial_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, vp]
             if hasattr(L, "aos2_pose_optimization"):
                 L.aos2_pose_optimization.argtypes = [vp, vp, vp, ci]
                 L.aos2_pose_optimization_last_device_ms.argtypes = [vp]
@@ -2600,6 +2601,36 @@ class _LbaSystem(C.Structure):
                 ("b_p", C.c_void_p), ("Hll", C.c_void_p), ("b_l", C.c_void_p), ("Hs", C.c_void_p), ("bs", C.c_void_p)]
 
 
+class _LbaLmState(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lam", "ni", "currentChi", "iniChi", "final_chi2", "final_lambda")] + \
+               [(k, C.c_int32) for k in ("phase", "run", "lin", "initp", "xmark", "it", "qmax", "nBad")] + \
+               [("iters_done", C.c_int32 * 2), ("trials", C.c_int32 * 2)] + \
+               [(k, C.c_int32) for k in ("polls", "stop_poll", "n_active", "solver_failed", "err_at", "ntr")] + \
+               [(k, C.c_double * 48) for k in ("tr_rho", "tr_temp", "tr_cur", "tr_lambda")]
+
+
+# arrays of a snapshot of aos2_debug_lba_trial_device: name -> (dtype, size from n_poses, n_points, n_edges)
+_LBA_SNAP_ARRAYS = (("est", np.float64, lambda q, m, E: 7 * q + 3 * m), ("bk", np.float64, lambda q, m, E: 7 * q + 3 * m),
+                    ("x", np.float64, lambda q, m, E: 6 * q + 3 * m), ("b", np.float64, lambda q, m, E: 6 * q + 3 * m),
+                    ("Hll", np.float64, lambda q, m, E: 9 * m), ("Rl", np.float64, lambda q, m, E: 9 * q),
+                    ("tmp", np.float64, lambda q, m, E: 6 * q), ("part", np.float64, lambda q, m, E: 2 * m),
+                    ("e_level1", np.uint8, lambda q, m, E: E), ("e_robust", np.uint8, lambda q, m, E: E),
+                    ("err", np.float64, lambda q, m, E: 3 * E), ("lrec", np.float64, lambda q, m, E: 4 * E),
+                    ("erec_flags", np.uint32, lambda q, m, E: E), ("out_Tcw", np.float32, lambda q, m, E: 16 * q),
+                    ("out_xyz", np.float32, lambda q, m, E: 3 * m), ("out_chi2", np.float64, lambda q, m, E: E),
+                    ("out_outlier", np.uint8, lambda q, m, E: E))
+
+
+class _LbaTrialSnap(C.Structure):
+    _fields_ = [("taken", C.c_int32), ("pad_", C.c_int32), ("st", _LbaLmState), ("scal3", C.c_double)] + \
+               [(k, C.c_void_p) for k, _, _ in _LBA_SNAP_ARRAYS]
+
+
+class _LbaTrial(C.Structure):
+    _fields_ = [("np", C.c_int32), ("nl", C.c_int32), ("n_pl", C.c_int32), ("n_part", C.c_int32), ("hpose", C.c_void_p), ("hpoint", C.c_void_p),
+                ("pt_off", C.c_void_p), ("pt_k", C.c_void_p), ("pl_pos", C.c_void_p), ("snap", _LbaTrialSnap * 5)]
+
+
 class _PoseProblem(C.Structure):
     _fields_ = [("n", C.c_int32), ("Xw", C.c_void_p), ("obs", C.c_void_p), ("stereo", C.c_void_p),
                 ("inv_sigma2", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
@@ -2798,6 +2829,59 @@ class LocalBA:
                             e_level1=b["e_level1"], e_robust=b["e_robust"], Hpp_init=b["Hpp_init"][:36 * q].reshape(q, 6, 6),
                             b_init=b["b_init"][:6 * q], b_p=b["b_p"][:6 * q], Hll=b["Hll"][:9 * m].reshape(m, 3, 3), b_l=b["b_l"][:3 * m],
                             Hs=b["Hs"][:npad * npad].reshape(npad, npad), bs=b["bs"][:6 * q]))
+        return out
+
+    def debug_trial(self, probs, layout="slots", trials_before=0, lam=None, force_solver_failed=None, tail=0, iters=(5, 10)):
+        """test tap aos2_debug_lba_trial_device: the landmark half of a trial, the LM decision, the outlier pass and the final check,
+        read between the shipped launches -> one dict per window: np, nl, n_pl, n_part, hpose, hpoint, pt_off, pt_k, pl_pos and the
+        snapshots "A" .. "E" (None where `tail` did not reach): dicts of the arrays of aos2_lba_trial_snap_t, pose [n_poses, 7], point
+        [n_points, 3] and their backups bk_pose, bk_point, scal3, and st = the LmState scalars (traces cut to ntr)"""
+        n = len(probs)
+        keep = []
+        S, R, O = (_LbaProblem * n)(), (_LbaResult * n)(), (_LbaTrial * n)()
+        bufs = []
+        for i in range(n):
+            self._fill(S[i], R[i], probs[i], None, iters, keep)
+            q, m, E = S[i].n_poses, S[i].n_points, S[i].n_edges
+            b = dict(hpose=np.zeros(q, np.int32), hpoint=np.zeros(m, np.int32), pt_off=np.zeros(m + 1, np.int32), pt_k=np.zeros(E, np.int32),
+                     pl_pos=np.zeros(E, np.int32))
+            for k, a in b.items():
+                setattr(O[i], k, a.ctypes.data)
+            b["snap"] = []
+            for j in range(5):
+                sb = {k: np.zeros(size(q, m, E), dt) for k, dt, size in _LBA_SNAP_ARRAYS}
+                for k, a in sb.items():
+                    setattr(O[i].snap[j], k, a.ctypes.data)
+                b["snap"].append(sb)
+            bufs.append(b)
+        lam_a = None if lam is None else np.ascontiguousarray(lam, np.float64)
+        fail_a = None if force_solver_failed is None else np.ascontiguousarray(force_solver_failed, np.uint8)
+        assert (lam_a is None or lam_a.shape == (n,)) and (fail_a is None or fail_a.shape == (n,))
+        _check(self.L.aos2_debug_lba_trial_device(self.h, C.byref(S), n, self.LAYOUTS.get(layout, layout), int(trials_before),
+                                                  None if lam_a is None else _p(lam_a), None if fail_a is None else _p(fail_a), int(tail),
+                                                  C.byref(O)))
+        out = []
+        for i, (o, b) in enumerate(zip(O, bufs)):
+            q, m, npl = o.np, o.nl, o.n_pl
+            NP, NL = S[i].n_poses, S[i].n_points
+            w = dict(np=q, nl=m, n_pl=npl, n_part=o.n_part, hpose=b["hpose"][:q], hpoint=b["hpoint"][:m], pt_off=b["pt_off"][:m + 1],
+                     pt_k=b["pt_k"], pl_pos=b["pl_pos"])
+            for j, name in enumerate("ABCDE"):
+                sn, sb = o.snap[j], b["snap"][j]
+                if not sn.taken:
+                    w[name] = None
+                    continue
+                st = {k: getattr(sn.st, k) for k, _ in _LbaLmState._fields_ if not k.startswith("tr_") and k not in ("iters_done", "trials")}
+                st["iters_done"], st["trials"] = tuple(sn.st.iters_done), tuple(sn.st.trials)
+                for k in ("tr_rho", "tr_temp", "tr_cur", "tr_lambda"):
+                    st[k] = np.array(getattr(sn.st, k)[:sn.st.ntr], np.float64)
+                d = dict(sb, st=st, scal3=sn.scal3, pose=sb["est"][:7 * NP].reshape(NP, 7), point=sb["est"][7 * NP:].reshape(NL, 3),
+                         bk_pose=sb["bk"][:7 * NP].reshape(NP, 7), bk_point=sb["bk"][7 * NP:].reshape(NL, 3))
+                d.update(x=sb["x"][:6 * q + 3 * m], b=sb["b"][:6 * q + 3 * m], Hll=sb["Hll"][:9 * m].reshape(m, 3, 3), Rl=sb["Rl"][:9 * q].reshape(q, 3, 3),
+                         tmp=sb["tmp"][:6 * q], part=sb["part"][:2 * m], lrec=sb["lrec"][:4 * npl].reshape(npl, 4), err=sb["err"].reshape(-1, 3),
+                         out_Tcw=sb["out_Tcw"].reshape(NP, 16), out_xyz=sb["out_xyz"].reshape(NL, 3))
+                w[name] = d
+            out.append(w)
         return out
 
     def set_host_threads(self, n):

@@ -2539,8 +2539,8 @@ static void enqueue_schur(const Prog &P)
 {
     if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
 }
-// one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of both kinds)
-static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
+// the pose half of a Levenberg-Marquardt trial: the Schur complement and the reduced system's solve with the pose update
+static void enqueue_reduced(LaunchCtx &C, const Prog &P, bool first_group)
 {
     const GroupDims &D = P.D;
     enqueue_schur(P);
@@ -2560,12 +2560,21 @@ static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
         (void)hipEventRecord(P.join, P.q2);
         (void)hipStreamWaitEvent(P.q, P.join, 0);
     }
+}
+// one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of both kinds)
+static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
+{
+    enqueue_reduced(C, P, first_group);
     enqueue_points(C, P, 1);   // + the LM decision in its last workgroup
     enqueue_lin(C, P, 0);
 }
 static void enqueue_transition(const Prog &P)
 {
     hipLaunchKernelGGL(k_transition, dim3(blocks(P.D.mx_E, 256), P.nw), dim3(256), 0, P.q, P.blk);
+}
+static void enqueue_final(const Prog &P)
+{
+    hipLaunchKernelGGL(k_final, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk);
 }
 
 // ---- the steps of aos2_lba_solve_batch
@@ -2808,10 +2817,7 @@ struct Batch {
 static int finish(aos2_lba *s, const Prog *progs, int n_progs, const Batch &Bt)
 {
     hipStream_t q = s->stream;
-    for (int g = 0; g < n_progs; ++g) {
-        const Prog &P = progs[g];
-        hipLaunchKernelGGL(k_final, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk);
-    }
+    for (int g = 0; g < n_progs; ++g) enqueue_final(progs[g]);
     if (n_progs == 2) {
         AOS2_HIP_CHECK(hipEventRecord(s->ev_done_b, s->stream_b));
         AOS2_HIP_CHECK(hipStreamWaitEvent(q, s->ev_done_b, 0));
@@ -3315,6 +3321,143 @@ int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *prob
         memcpy(o.b_l, h + l.b + 8 * 6 * np, 8 * 3 * nl);
         memcpy(o.Hs, h + l.Hs, 8 * npad * npad);
         memcpy(o.bs, h + l.bs, 8 * 6 * np);
+    }
+    return AOS2_OK;
+}
+
+// Test tap: the landmark half of a trial and the LM decision, the outlier pass and the final check, read between the shipped launches.
+// Host phase and helpers as the assembly tap; a snapshot is a synchronisation and a copy of the arena (the windows are small).
+int aos2_debug_lba_trial_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int trials_before, const double *lambda,
+                                const uint8_t *force_solver_failed, int tail, aos2_lba_trial_t *out)
+{
+    if (!s || !problems || !out || n_problems < 1 || (layout != 0 && layout != 1) || trials_before < 0 || tail < 0 || tail > 2) {
+        set_error("aos2_debug_lba_trial_device: bad argument (layout 0 = slots, 1 = walk; trials_before >= 0; tail 0, 1 or 2)");
+        return AOS2_ERR_ARG;
+    }
+    for (int w = 0; w < n_problems; ++w) {
+        const aos2_lba_problem_t *p = problems + w;
+        const aos2_lba_trial_t *o = out + w;
+        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id || !p->point_xyz || !p->point_id ||
+            !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo || !p->edge_inv_sigma2 || p->iters_first < 1 || !o->hpose || !o->hpoint ||
+            !o->pt_off || !o->pt_k || !o->pl_pos) {
+            set_error("aos2_debug_lba_trial_device: bad problem or output %d", w);
+            return AOS2_ERR_ARG;
+        }
+    }
+    int st;
+    {   // what the host phase refuses, before a device is looked for
+        std::vector<Pass> probe(n_problems);
+        WindowPool serial;
+        if ((st = build_structures(serial, problems, nullptr, n_problems, probe))) return st;
+        for (int w = 0; w < n_problems; ++w)
+            if (probe[w].np < 1) {
+                set_error("aos2_debug_lba_trial_device: problem %d has no free keyframe with an edge", w);
+                return AOS2_ERR_ARG;
+            }
+    }
+    if ((st = lba_handle_init(s))) return st;
+    const int nw = n_problems;
+    std::vector<int> act(nw);
+    std::iota(act.begin(), act.end(), 0);
+    const int goff[3] = {0, nw, nw};
+    const bool walk = layout == 1;
+    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
+    Uploaded U;
+    if ((st = build_and_upload(s, problems, act, goff, 1, lay, true, U))) return st;
+    const std::vector<Pass> &passes = *U.passes;
+    const ArenaPlan &A = U.A;
+    uint8_t *base = s->arena.p;
+    std::vector<uint8_t> host(A.bytes);
+    for (int i = 0; i < nw; ++i) {
+        const Pass &S = passes[i];
+        aos2_lba_trial_t &o = out[i];
+        o.np = S.np; o.nl = S.nl; o.n_pl = (int32_t)S.pl_k.size(); o.n_part = A.L[i].n_part;
+        memcpy(o.hpose, S.hpose.data(), 4 * (size_t)S.np);
+        memcpy(o.hpoint, S.hpoint.data(), 4 * (size_t)S.nl);
+        memcpy(o.pt_off, S.pt_off.data(), 4 * S.pt_off.size());
+        memcpy(o.pt_k, S.pt_k.data(), 4 * S.pt_k.size());
+        memcpy(o.pl_pos, S.pl_pos.data(), 4 * S.pl_pos.size());
+        for (auto &sn : o.snap) sn.taken = 0;
+    }
+    hipStream_t q = s->stream;
+    auto snapshot = [&](int k) -> int {
+        AOS2_HIP_CHECK(hipGetLastError());
+        AOS2_HIP_CHECK(hipStreamSynchronize(q));
+        AOS2_HIP_CHECK(hipMemcpy(host.data(), base, A.bytes, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nw; ++i) {
+            const aos2_lba_problem_t &p = problems[i];
+            const Pass &S = passes[i];
+            const WinLayout &l = A.L[i];
+            aos2_lba_trial_snap_t &o = out[i].snap[k];
+            const uint8_t *h = host.data();
+            const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges, np = S.np, nl = S.nl, est = 8 * (7 * NP + 3 * NL);
+            auto put = [&](void *dst, size_t off, size_t bytes) {
+                if (dst && bytes) memcpy(dst, h + off, bytes);
+            };
+            o.taken = 1;
+            const LmState *ls = (const LmState *)(h + l.st);
+            aos2_lba_lm_state_t &t = o.st;
+            t.lambda = ls->lambda; t.ni = ls->ni; t.currentChi = ls->currentChi; t.iniChi = ls->iniChi;
+            t.final_chi2 = ls->final_chi2; t.final_lambda = ls->final_lambda;
+            t.phase = ls->phase; t.run = ls->run; t.lin = ls->lin; t.initp = ls->initp; t.xmark = ls->xmark;
+            t.it = ls->it; t.qmax = ls->qmax; t.nBad = ls->nBad;
+            for (int j = 0; j < 2; ++j) {
+                t.iters_done[j] = ls->iters_done[j];
+                t.trials[j] = ls->trials[j];
+            }
+            t.polls = ls->polls; t.stop_poll = ls->stop_poll; t.n_active = ls->n_active; t.solver_failed = ls->solver_failed;
+            t.err_at = ls->err_at; t.ntr = ls->ntr;
+            memcpy(t.tr_rho, ls->tr_rho, sizeof t.tr_rho); memcpy(t.tr_temp, ls->tr_temp, sizeof t.tr_temp);
+            memcpy(t.tr_cur, ls->tr_cur, sizeof t.tr_cur); memcpy(t.tr_lambda, ls->tr_lambda, sizeof t.tr_lambda);
+            o.scal3 = ((const double *)(h + l.scal))[3];
+            put(o.est, l.est, est); put(o.bk, l.bk, est);
+            put(o.x, l.x, 8 * (6 * np + 3 * nl)); put(o.b, l.b, 8 * (6 * np + 3 * nl));
+            put(o.Hll, l.Hll, 72 * nl); put(o.Rl, l.Rl, 72 * np); put(o.tmp, l.tmp, 48 * np); put(o.part, l.part, 16 * nl);
+            put(o.e_level1, l.level1, E); put(o.e_robust, l.robust, E);
+            put(o.err, l.err, 24 * E); put(o.lrec, l.lrec, 32 * S.pl_k.size());
+            if (o.erec_flags)
+                for (size_t a = 0; a < E; ++a) o.erec_flags[a] = ((const EdgeRec *)(h + l.erec))[a].flags;
+            put(o.out_Tcw, l.out_Tcw, 64 * NP); put(o.out_xyz, l.out_xyz, 12 * NL);
+            put(o.out_chi2, l.out_chi2, 8 * E); put(o.out_outlier, l.out_outlier, E);
+        }
+        return AOS2_OK;
+    };
+    const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
+    LaunchCtx C{s, walk, false};
+    const Prog P = make_prog(dw, dw, nw, U.TL[0], U.dt[0], U.gd[0], group_streams(s, 0));
+    static const double zero = 0.0;
+    enqueue_prepare(C, P);
+    enqueue_init(C, P);
+    for (int i = 0; i < nw; ++i)
+        if (lambda && lambda[i] > 0) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].st + offsetof(LmState, lambda), lambda + i, 8, hipMemcpyHostToDevice, q));
+    // The second optimisation starts where the solve's programs start it: behind iters_first trials when every step was accepted
+    // (enqueue_program), behind whichever later trial ends the first optimisation otherwise (continuation_round) -- both launches are
+    // gated by the state (xmark, initp), so they are enqueued before every trial from there on
+    auto between = [&](int t) {
+        if (t < U.max_i1) return;
+        enqueue_transition(P);
+        enqueue_init(C, P);
+    };
+    for (int t = 0; t < trials_before; ++t) {
+        between(t);
+        enqueue_trial(C, P, true);
+    }
+    between(trials_before);
+    enqueue_reduced(C, P, true);
+    for (int i = 0; i < nw; ++i)
+        if (force_solver_failed && force_solver_failed[i]) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].scal + 24, &zero, 8, hipMemcpyHostToDevice, q));
+    if ((st = snapshot(0))) return st;
+    enqueue_points(C, P, 1);
+    if ((st = snapshot(1))) return st;
+    enqueue_lin(C, P, 0);
+    if ((st = snapshot(2))) return st;
+    if (tail >= 1) {
+        enqueue_transition(P);
+        if ((st = snapshot(3))) return st;
+    }
+    if (tail == 2) {
+        enqueue_final(P);
+        if ((st = snapshot(4))) return st;
     }
     return AOS2_OK;
 }

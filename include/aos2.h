@@ -1856,6 +1856,57 @@ typedef struct {
 int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int stage,
                                    const double *lambda, aos2_lba_system_t *out);
 
+/* The landmark half of a LocalBA trial and the Levenberg-Marquardt decision, read between the shipped launches (csrc/lba.hip: k_points /
+ * k_points_walk with solve = 1 and lm_decide in its last workgroup, k_lin with init = 0, k_transition, k_final).  Host phase, helpers,
+ * layout and lambda as in aos2_debug_lba_assemble_device; all windows as one group; aos2_lba_debug_stop_at_poll applies.  Sequence:
+ *   k_prepare, the start of the first optimisation, [lambda], trials_before whole trials as the solve enqueues them (k_transition and
+ *   the start of the second optimisation before every trial from the iters_first-th on: both are gated by the state),
+ *   k_schur + the reduced solve of the trial under test, [scal[3] = 0.0 where force_solver_failed[w]]   -> snapshot 0 (A)
+ *   the landmark kernel, solve = 1                                                                      -> snapshot 1 (B)
+ *   k_lin, init = 0                                                                                     -> snapshot 2 (C)
+ *   tail >= 1: k_transition                                                                             -> snapshot 3 (D)
+ *   tail == 2: k_final                                                                                  -> snapshot 4 (E)
+ * tail: the k_transition of tail >= 1 does something only where the trial under test ended the first optimisation (xmark); with
+ * trials_before >= iters_first the outlier pass has already run in front of a trial and snapshot 3 equals snapshot 2.
+ * A snapshot is a stream synchronisation and a copy of the arena; every array of a snapshot whose pointer is not NULL is filled with what
+ * the arena holds at that moment (a region no kernel has written yet -- the landmark part of x before the first trial's landmark kernel,
+ * the outputs before k_final -- holds what an earlier call left there).
+ * force_solver_failed: NULL or one byte per window.  The caller sizes the arrays by the problem (np <= n_poses, nl <= n_points, free-
+ * keyframe edges <= n_edges).
+ * AOS2_ERR_ARG (before a device is looked for): a NULL, n_problems < 1, another layout or tail, trials_before < 0, iters_first < 1,
+ * a window the host phase of the solve refuses, a window without a free keyframe. */
+typedef struct {
+    double lambda, ni, currentChi, iniChi, final_chi2, final_lambda;
+    int32_t phase, run, lin, initp, xmark, it, qmax, nBad;
+    int32_t iters_done[2], trials[2];
+    int32_t polls, stop_poll, n_active, solver_failed, err_at, ntr;
+    double tr_rho[48], tr_temp[48], tr_cur[48], tr_lambda[48];
+} aos2_lba_lm_state_t;
+typedef struct {
+    int32_t taken;                    /* out: the snapshot was made (tail) */
+    int32_t pad_;
+    aos2_lba_lm_state_t st;           /* out: LmState */
+    double scal3;                     /* out: scal[3], 1.0 = the reduced solve succeeded */
+    double *est, *bk;                 /* [7 n_poses + 3 n_points]: pose | point, and the push() backup */
+    double *x, *b;                    /* [6 np + 3 nl]: pose part, landmark part */
+    double *Hll, *Rl, *tmp, *part;    /* [9 nl], [9 np], [6 np], [2 nl] */
+    uint8_t *e_level1, *e_robust;     /* [n_edges] */
+    double *err, *lrec;               /* [3 n_edges]; [4 n_pl] by position in the landmarks' free-keyframe edge lists */
+    uint32_t *erec_flags;             /* [n_edges] by position in the landmarks' edge lists: 1 stereo | 2 robust | 4 level1 */
+    float *out_Tcw, *out_xyz;         /* [16 n_poses], [3 n_points] */
+    double *out_chi2;                 /* [n_edges] */
+    uint8_t *out_outlier;             /* [n_edges] */
+} aos2_lba_trial_snap_t;
+typedef struct {
+    int32_t np, nl, n_pl, n_part;     /* out: free keyframes, landmarks with an edge, free-keyframe edges, workgroups of the landmark kernel */
+    int32_t *hpose, *hpoint;          /* [np] / [nl] */
+    int32_t *pt_off, *pt_k;           /* [nl + 1], [n_edges]: the landmarks' edge lists (insertion order) */
+    int32_t *pl_pos;                  /* [n_edges]: edge -> position of its linearisation record (-1: fixed keyframe) */
+    aos2_lba_trial_snap_t snap[5];
+} aos2_lba_trial_t;
+int aos2_debug_lba_trial_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int trials_before,
+                                const double *lambda, const uint8_t *force_solver_failed, int tail, aos2_lba_trial_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -541,6 +541,55 @@ def test_assembly_tap_refuses_on_the_host(pkg):
         assert e.value.code == capi.AOS2_ERR_NO_DEVICE
 
 
+def test_trial_tap_refuses_on_the_host(pkg):
+    """aos2_debug_lba_trial_device checks its arguments before it looks for a device: a NULL (the handle, the problems, the outputs, every
+    index array of a window, inputs of the problem), no problems, another layout or tail, a negative trials_before, iterations < 1, a
+    window the host phase refuses or one without a free keyframe."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lba_system_ref as S
+    capi = pkg.capi
+    ba = capi.LocalBA()
+    win = S.make_window(1, 2, 2, S.sees_counts(3))
+
+    def refused(w, text=None, **kw):
+        with pytest.raises(capi.AosError) as e:
+            ba.debug_trial([win, w], **kw)
+        assert e.value.code == capi.AOS2_ERR_ARG, (kw, str(e.value))
+        assert text is None or text in str(e.value), str(e.value)
+
+    for kw in (dict(layout=2), dict(layout=-1), dict(tail=3), dict(tail=-1), dict(trials_before=-1), dict(iters=(0, 10))):
+        refused(win, **kw)
+    ep = win["edge_pose"].copy()
+    ep[3] = win["n_poses"]
+    refused(dict(win, edge_pose=ep), "out of range")
+    refused(dict(win, pose_fixed=np.ones(win["n_poses"], np.uint8)), "no free keyframe")
+    f = capi.lib().aos2_debug_lba_trial_device
+    S_, R_, O_ = (capi._LbaProblem * 1)(), (capi._LbaResult * 1)(), (capi._LbaTrial * 1)()
+    keep = []
+    ba._fill(S_[0], R_[0], win, None, (5, 10), keep)
+    bufs = {k: np.zeros(4096, np.int32) for k in ("hpose", "hpoint", "pt_off", "pt_k", "pl_pos")}
+    for k, a in bufs.items():
+        setattr(O_[0], k, a.ctypes.data)
+    assert f(None, C.byref(S_), 1, 0, 0, None, None, 0, C.byref(O_)) == capi.AOS2_ERR_ARG
+    assert f(ba.h, None, 1, 0, 0, None, None, 0, C.byref(O_)) == capi.AOS2_ERR_ARG
+    assert f(ba.h, C.byref(S_), 1, 0, 0, None, None, 0, None) == capi.AOS2_ERR_ARG
+    assert f(ba.h, C.byref(S_), 0, 0, 0, None, None, 0, C.byref(O_)) == capi.AOS2_ERR_ARG
+    for k in bufs:
+        setattr(O_[0], k, None)
+        assert f(ba.h, C.byref(S_), 1, 0, 0, None, None, 0, C.byref(O_)) == capi.AOS2_ERR_ARG, k
+        setattr(O_[0], k, bufs[k].ctypes.data)
+    for k in ("pose_Tcw", "edge_obs", "point_id"):
+        old = getattr(S_[0], k)
+        setattr(S_[0], k, None)
+        assert f(ba.h, C.byref(S_), 1, 0, 0, None, None, 0, C.byref(O_)) == capi.AOS2_ERR_ARG, k
+        setattr(S_[0], k, old)
+    if pkg.device_count() == 0:   # good arguments get as far as the device (no snapshot array is required)
+        with pytest.raises(capi.AosError) as e:
+            ba.debug_trial([win], tail=2)
+        assert e.value.code == capi.AOS2_ERR_NO_DEVICE
+
+
 def test_pose_pass_tap_refuses_on_the_host(pkg):
     """aos2_debug_pose_pass_device checks its arguments before it looks for a device: a NULL (the case list, every array of a case), no
     cases, an unknown form or mode, n above the form's limit (1024, 2048, 1152; none for the form that leaves the edges in memory) or
