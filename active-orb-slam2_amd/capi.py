@@ -171,6 +171,11 @@ def lib():
         L.aos2_local_map_last_culling_device_ms.restype = C.c_float
         L.aos2_debug_keyframe_culling_host.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
         L.aos2_local_map_get_culling_view.argtypes = [vp, vp, vp]
+        L.aos2_local_map_update_connections.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci]
+        L.aos2_debug_update_connections_host.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci]
+        L.aos2_local_map_last_connections_device_ms.argtypes = [vp]
+        L.aos2_local_map_last_connections_device_ms.restype = C.c_float
+        L.aos2_local_map_debug_connections_sort.argtypes = [vp, ci]
         L.aos2_local_map_apply.argtypes = [vp, vp]
         L.aos2_debug_local_map_apply_host.argtypes = [vp, vp]
         L.aos2_local_map_last_apply.argtypes = [vp, vp, vp, vp]
@@ -1327,6 +1332,41 @@ def _kf_culling_call(fn, first, monocular, cand, bad_cap):
     return dict(status=status[:n], n_mps=n_mps[:n], n_redundant=n_red[:n], n_bad_points=int(nb.value), bad_points=bad)
 
 
+CONNECTIONS_TH = 15
+
+
+def _update_connections_call(fn, first, th, kf, mp, conn_cap, ordered_cap, mp_cap=None):
+    """the arguments that aos2_local_map_update_connections and its host tap share.  kf: the rows; mp: None (the resident matches)
+    or one sequence of point rows per keyframe -> dict(n_conn, n_ordered int32 [n], conn_kf, conn_w int32 [n][conn_cap], ordered_kf,
+    ordered_w int32 [n][ordered_cap], guard: the word behind each of the six arrays, preset to -7).  A capacity of 0 passes NULL."""
+    kf = np.ascontiguousarray(kf, np.int32).reshape(-1)
+    n = len(kf)
+    n_mp = mp2 = None
+    if mp is not None:
+        if len(mp) != n:
+            raise ValueError("one list of matches per keyframe")
+        n_mp = np.array([len(x) for x in mp] + [0], np.int32)
+        mp_cap = max(1, int(n_mp.max())) if mp_cap is None else int(mp_cap)
+        mp2 = np.full((max(n, 1), mp_cap), -1, np.int32)
+        for k, x in enumerate(mp):
+            mp2[k, :min(len(x), mp_cap)] = np.asarray(x, np.int32)[:mp_cap]
+    else:
+        mp_cap = 0
+    conn_cap, ordered_cap = int(conn_cap), int(ordered_cap)
+    flat = {k: np.full(n * c + 1, -7, np.int32) for k, c in (("n_conn", 1), ("n_ordered", 1), ("conn_kf", conn_cap), ("conn_w", conn_cap),
+                                                             ("ordered_kf", ordered_cap), ("ordered_w", ordered_cap))}
+
+    def arg(k, c):
+        return _p(flat[k]) if c > 0 else None
+    _check(fn(*first, int(th), n, _p(kf), None if mp is None else _p(n_mp), None if mp is None else _p(mp2), mp_cap,
+              _p(flat["n_conn"]), arg("conn_kf", conn_cap), arg("conn_w", conn_cap), conn_cap,
+              _p(flat["n_ordered"]), arg("ordered_kf", ordered_cap), arg("ordered_w", ordered_cap), ordered_cap))
+    out = dict(n_conn=flat["n_conn"][:n], n_ordered=flat["n_ordered"][:n], guard={k: int(a[-1]) for k, a in flat.items()})
+    for k, c in (("conn_kf", conn_cap), ("conn_w", conn_cap), ("ordered_kf", ordered_cap), ("ordered_w", ordered_cap)):
+        out[k] = flat[k][:n * c].reshape(n, c)
+    return out
+
+
 class LocalMap:
     """The covisibility graph resident on the device and Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) for the frames of a
     capi.Frames batch.  A graph is a dict with the fields of aos2_local_map_graph_t (numpy arrays, CSR offsets)."""
@@ -1459,6 +1499,24 @@ class LocalMap:
         g, v = _local_map_graph(graph, keep), _kf_culling_view(view, keep)
         bad_cap = int(graph["n_points"]) if bad_cap is None else bad_cap
         return _kf_culling_call(lib().aos2_debug_keyframe_culling_host, (C.byref(g), C.byref(v)), monocular, cand, bad_cap)
+
+    def update_connections(self, kf, mp=None, th=CONNECTIONS_TH, conn_cap=256, ordered_cap=256, mp_cap=None):
+        """aos2_local_map_update_connections (KeyFrame::UpdateConnections, src/KeyFrame.cc:350-440) on the device -> the dict of
+        _update_connections_call"""
+        return _update_connections_call(self.L.aos2_local_map_update_connections, (self.h,), th, kf, mp, conn_cap, ordered_cap, mp_cap)
+
+    @staticmethod
+    def update_connections_host(graph, kf, mp=None, th=CONNECTIONS_TH, conn_cap=256, ordered_cap=256, mp_cap=None):
+        """aos2_debug_update_connections_host: the same function on one core, no device"""
+        keep = [np.zeros(1, np.int32)]
+        g = _local_map_graph(graph, keep)
+        return _update_connections_call(lib().aos2_debug_update_connections_host, (C.byref(g),), th, kf, mp, conn_cap, ordered_cap, mp_cap)
+
+    def debug_connections_sort(self, lds_entries=0):
+        _check(self.L.aos2_local_map_debug_connections_sort(self.h, int(lds_entries)))
+
+    def last_connections_device_ms(self):
+        return float(self.L.aos2_local_map_last_connections_device_ms(self.h))
 
     def update_host(self, n, mp, local_cap, kf_cap, local_kfs=None, n_local_kfs=None, ref_kf=None):
         """aos2_local_map_update: the device kernels on host arrays, arguments and result as host()"""

@@ -13,6 +13,7 @@
 #include "sim3.h"
 #include "triangulate.h"
 #include "visibility.h"
+#include "connections.h"
 #include "local_map.h"
 #include "motion_tw.h"
 #include "wave_ops.h"
@@ -675,6 +676,22 @@ int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2
     std::sort(went_bad.begin(), went_bad.end());
     *n_bad_points = (int32_t)went_bad.size();
     for (int j = 0; j < std::min<int>((int)went_bad.size(), bad_cap); ++j) bad_points[j] = went_bad[j];
+    return AOS2_OK;
+}
+
+// KeyFrame::UpdateConnections (src/KeyFrame.cc:350-440): the serial loop of csrc/connections.h over a host graph, with the checks
+// of the device call
+int aos2_debug_update_connections_host(const aos2_local_map_graph_t *g, int th, int n, const int32_t *kf, const int32_t *n_mp,
+                                       const int32_t *mp, int mp_cap, int32_t *n_conn, int32_t *conn_kf, int32_t *conn_w, int conn_cap,
+                                       int32_t *n_ordered, int32_t *ordered_kf, int32_t *ordered_w, int ordered_cap)
+{
+    using namespace aos2;
+    if (int st = local_map_check(g, nullptr)) return st;
+    const ConnArgs A = {th, n, kf, n_mp, mp, mp_cap, n_conn, conn_kf, conn_w, conn_cap, n_ordered, ordered_kf, ordered_w, ordered_cap};
+    char why[200];
+    if (conn_check(A, g->n_keyframes, why, sizeof why)) return lm_fail("update connections", "%s", why);
+    const LmGraph G = {{g->n_points, g->n_keyframes}, lm_from_public(*g, nullptr)};
+    conn_host_run(G, A);
     return AOS2_OK;
 }
 

@@ -118,6 +118,20 @@ struct KfcState {
     }
 };
 
+// what is specific to aos2_local_map_update_connections (csrc/connections.hip): the device block of one call's arguments and
+// results, its page-locked staging, the sort switch
+struct ConnState {
+    DevBuf<uint8_t> d_io;
+    PinnedBuf<uint8_t> io;
+    int lds_entries = 0;   // ordered lists up to this length are sorted in LDS, 0 = the default
+    EventTimer timer;      // around the last call's device work
+    ~ConnState()
+    {
+        d_io.release();
+        io.release();
+    }
+};
+
 }  // namespace aos2
 
 struct aos2_local_map {
@@ -137,6 +151,7 @@ struct aos2_local_map {
     int last_groups = 0;
     bool has_graph = false;   // aos2_local_map_set has been called
     aos2::KfcState kfc;
+    aos2::ConnState conn;
     // aos2_local_map_apply (csrc/local_map_apply.hip).  Always current on the host, each kept in O(delta): the counts above and
     // max_features, the entries of the three CSR arrays, and the length of every row (row_feat is Frame::N of each keyframe, the
     // bound of obs_idx).  M is the MIRROR: after a rebuild on the device it is stale until local_map_refresh_host downloads the

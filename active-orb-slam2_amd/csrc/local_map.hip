@@ -18,6 +18,7 @@
 
 #include "aos2_common.h"
 #include "frames.h"
+#include "lm_counters.h"
 #include "local_map.h"
 #include "wave_ops.h"
 
@@ -41,20 +42,6 @@ struct LmScratch {
     int32_t *cnt, *klist, *nk;
     uint32_t *minpos;
 };
-
-// counters and marks: LDS, or global memory through the L2 (they are written by atomics and read back in the same launch)
-template <bool kLds>
-__device__ __forceinline__ int lm_load(const int32_t *p)
-{
-    if constexpr (kLds) return *p;
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool kLds>
-__device__ __forceinline__ void lm_store(int32_t *p, int v)
-{
-    if constexpr (kLds) *p = v;
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // one wave, all lanes: the first lane of `m` names the keyframe that joins the list
 template <bool kLds>
@@ -396,6 +383,7 @@ void aos2_local_map_destroy(aos2_local_map_t *h)
         h->delta_stage.release();
         h->apply_timer.release();
         h->kfc.timer.release();
+        h->conn.timer.release();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;

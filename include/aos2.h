@@ -1442,7 +1442,7 @@ int aos2_frames_track_local_map_stats(aos2_frames_t *f, const aos2_local_map_t *
 /* test hooks: the scratch bound in bytes (<= 0: the default, 256 MiB) and the largest n_keyframes whose vote counters live in
  * LDS (< 0: the default, 8192; 0: always global memory), so that both sides of either switch are reached with small graphs */
 int aos2_local_map_debug_limits(aos2_local_map_t *m, int64_t scratch_bytes, int lds_keyframes);
-/* groups the last aos2_frames_update_local_map call ran its batch in */
+/* groups the last aos2_frames_update_local_map or aos2_local_map_update_connections call ran its batch in */
 int aos2_local_map_last_groups(const aos2_local_map_t *m);
 
 /* ------------------------------------------------------------------------------------------
@@ -1505,6 +1505,55 @@ float aos2_local_map_last_culling_device_ms(aos2_local_map_t *m);
 /* the handle's view in *view (the handle's own copies, parallel to the arrays of aos2_local_map_get and valid as long as they are);
  * *has_view (may be NULL) = whether the handle holds one, every pointer NULL if not */
 int aos2_local_map_get_culling_view(const aos2_local_map_t *m, aos2_kf_culling_view_t *view, int32_t *has_view);
+
+/* ------------------------------------------------------------------------------------------
+ * KeyFrame::UpdateConnections (src/KeyFrame.cc:350-440; called at LocalMapping.cc:168 and :537, Tracking.cc:775-776,
+ * LoopClosing.cc:434, :517, :556) over the handle's resident graph (csrc/connections.hip): the counting stage and the ordering,
+ * for a batch of keyframes in one call.  Every keyframe of the batch is independent: the counting stage reads points and
+ * observations, never connection weights, so the sequential loops of CorrectLoop are exact as one batch.  Integer graph work.
+ * The resident graph is READ, never written: the caller applies the verdicts to its own pointer graph (AddConnection on the
+ * neighbours, the three members, the first-connection parent: host/UpdateConnections.h) and sends the new link rows with its
+ * next aos2_local_map_apply.
+ *
+ * Followed literally, per keyframe k:
+ *   :363-381  every entry of the matches in feature order; a NULL (-1) entry and a point with isBad() are skipped; every
+ *             observation of the point whose keyframe is not k counts once for that keyframe.  No isBad() test on the observer or
+ *             on k; a point that sits at two features counts twice.
+ *   :384      no counter: the keyframe's members stay as they are.  n_conn = 0, n_ordered = 0.
+ *   :389-413  every counter >= th is listed (th: the reference's literal 15, AOS2_CONNECTIONS_TH); if none is, the single pKFmax =
+ *             the first strict maximum in the map's iteration order = the LOWEST row among the keyframes of maximal weight
+ *             (ascending row stands for pointer order).
+ *   :415-422  the list sorted on (weight, KeyFrame*) ascending and reversed: DESCENDING weight, and among equal weights
+ *             DESCENDING row -- not the order of the line above.
+ *   :428-430  mConnectedKeyFrameWeights = every keyframe with a count > 0, below the threshold or not.
+ * ------------------------------------------------------------------------------------------ */
+#define AOS2_CONNECTIONS_TH 15
+/* kf [n] = the keyframe rows.  All arrays are HOST memory; the call runs on the handle's own stream, shares the handle's scratch
+ * with aos2_local_map_update and aos2_local_map_keyframe_culling (one call at a time) and returns when the results are complete.
+ * Matches: with n_mp, mp and mp_cap NULL / NULL / 0 they are the resident kf_mp row of kf[k], which must be a row of the graph.
+ * With mp [n][mp_cap] and n_mp [n] given they are mp[k][0 .. n_mp[k]), 0 <= n_mp[k] <= mp_cap; kf[k] then only names the observer
+ * to skip and may be -1, a keyframe the graph does not know yet: nothing is skipped (the form for LocalMapping.cc:168).  An entry
+ * >= n_points is a point the table does not know and is skipped, as aos2_frames_update_local_map skips one.  A row may be listed
+ * twice in a batch; n == 0 is valid.
+ * Outputs: n_conn [n] / n_ordered [n] = the true counts; conn_kf / conn_w [n][conn_cap] = KFcounter in ascending row; ordered_kf /
+ * ordered_w [n][ordered_cap] = mvpOrderedConnectedKeyFrames / mvOrderedWeights.  The first min(count, cap) entries of a row are
+ * written, entries from the count to the capacity are -1 (keyframe) and 0 (weight), nothing behind an array is touched.  A
+ * capacity of 0 with NULL arrays is valid: the counts are still returned.
+ * AOS2_ERR_ARG before a device is looked for: no graph set; th < 1; a negative count or capacity; a NULL array with a non-zero
+ * length; mp without n_mp or the reverse; a row out of range; an n_mp[k] outside [0, mp_cap]; a match entry < -1; a scratch need of
+ * ONE keyframe (12 n_keyframes + 16 bytes: DESIGN.md section 5.16) above the bound of aos2_local_map_debug_limits.  A batch runs
+ * in groups that fit that bound (aos2_local_map_last_groups counts them); the outputs do not depend on the grouping, on where the
+ * counters live or on where the list is sorted.  After an aos2_local_map_apply that ran on the device the call reads the new block.
+ * Without a device: AOS2_ERR_NO_DEVICE. */
+int aos2_local_map_update_connections(aos2_local_map_t *m, int th, int n, const int32_t *kf, const int32_t *n_mp, const int32_t *mp,
+                                      int mp_cap, int32_t *n_conn, int32_t *conn_kf, int32_t *conn_w, int conn_cap, int32_t *n_ordered,
+                                      int32_t *ordered_kf, int32_t *ordered_w, int ordered_cap);
+/* device time of the last aos2_local_map_update_connections call between two events on the handle's stream, from the upload of
+ * the arguments to the copy back; -1 if there was none */
+float aos2_local_map_last_connections_device_ms(aos2_local_map_t *m);
+/* test hook: the longest ordered list that is sorted in LDS (<= 0: the default, 2048, which is also the most), so that the form
+ * in global scratch is reached with small graphs */
+int aos2_local_map_debug_connections_sort(aos2_local_map_t *m, int lds_entries);
 
 /* ------------------------------------------------------------------------------------------
  * One keyframe's changes applied to the resident graph (csrc/local_map_apply.hip): what one pass of
@@ -1669,6 +1718,12 @@ int aos2_debug_local_map_stats_host(const aos2_local_map_graph_t *g, int batch, 
 int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view, int monocular, int n_cand,
                                      const int32_t *cand, uint8_t *status, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points,
                                      int bad_cap, int32_t *n_bad_points);
+/* aos2_local_map_update_connections on the HOST: the per-item functions the device kernel also runs (csrc/connections.h), in the
+ * function's own order on one core -- the one-core baseline and the tap the device is compared with.  The graph is checked as
+ * aos2_local_map_set checks it, the other arguments as the device call checks them (the scratch bound aside); no device is needed. */
+int aos2_debug_update_connections_host(const aos2_local_map_graph_t *g, int th, int n, const int32_t *kf, const int32_t *n_mp,
+                                       const int32_t *mp, int mp_cap, int32_t *n_conn, int32_t *conn_kf, int32_t *conn_w, int conn_cap,
+                                       int32_t *n_ordered, int32_t *ordered_kf, int32_t *ordered_w, int ordered_cap);
 /* aos2_local_map_apply with the rebuild forced onto the HOST, also where the graph is resident: the same checks, the serial
  * restatement on the handle's host copy (refreshed first if it is stale), and the device copy of graph and view marked dirty, so
  * that the next consumer re-uploads everything.  The tap the device rebuild is compared with.  Returns as aos2_local_map_set. */
