@@ -22,136 +22,15 @@
 // is left alone like g2o leaves the _error of an inactive edge -- so every sum it took part in receives +0.0, which
 // is the same as leaving it out; vertices that lose all their edges keep a lambda-only diagonal block, decoupled from
 // the rest, and receive a zero update (g2o drops them from the index mapping instead: same result for the others).
-#include <dlfcn.h>
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-#include <numeric>
-#include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
-
-#include "lba_math.h"
+//
+// This unit holds every kernel and the helpers that launch them (lba_launch.h).  What host and device share -- the window
+// descriptor LbaWin, LmState, EdgeRec, SchurTask and the constants the layout depends on -- is lba_window.h; the host plan that
+// fills them is lba_plan.h; the handle, the steps of a solve and the C API are lba_solve.hip; the test taps are lba_taps.hip.
+#include "lba_launch.h"
 #include "ldlt_reg.h"
 #include "wave_ops.h"
 
 namespace aos2 {
-
-struct Cam {
-    double fx, fy, cx, cy, bf;
-    float bf_f;  // cam_project takes bf as `const float&` (types_six_dof_expmap.cpp:150)
-    double delta_mono, delta_stereo;  // Huber deltas (float sqrt -> double, Optimizer.cc:570-571)
-};
-
-// Levenberg-Marquardt / SparseOptimizer::optimize state of one window (levenberg.cpp:61-164, sparse_optimizer.cpp:354-419)
-struct LmState {
-    double lambda, ni, currentChi, iniChi;
-    double final_chi2, final_lambda;
-    int32_t phase;      // 0: first optimize() running, 1: first finished, 2: second running, 3: finished
-    int32_t run;        // the trial kernels execute
-    int32_t lin;        // the system is (re)linearised at the current estimates (after an accepted step)
-    int32_t initp;      // start of an optimize() call: residuals, system, lambda init pending
-    int32_t xmark;      // transition: the outlier pass runs
-    int32_t it, qmax, nBad;
-    int32_t iters_max[2], iters_done[2], trials[2];
-    int32_t polls;      // evaluations of terminate() so far (the host's entry check is the first)
-    int32_t stop_poll;  // the poll at which the stop flag was first seen set (0 = never)
-    int32_t stop_at_poll;  // test hook: the flag counts as set from this poll on (0 = off)
-    int32_t n_active;   // level-0 edges of the second optimisation
-    int32_t solver_failed;  // trials whose reduced system hit a zero pivot
-    int32_t blocks_done;    // workgroups of the current k_points launch that delivered their partial sums
-    int32_t ntr;            // trials recorded below (AOS2_LBA_TRACE=1 prints them)
-    // Where the edges' _error of the LAST residual evaluation can be re-formed from (the trials do not store 24 bytes per edge;
-    // the two passes that read _error -- the outlier pass and the final check -- re-form it): 0 = nowhere, the stored values
-    // stand (no evaluation since they were written); 1 = the current estimates (evaluation at the start of an optimisation, or
-    // an accepted trial); 2 = the backup, which after a rejected trial holds the trial's estimates (pop() swaps).
-    int32_t err_at;
-    int32_t pad_;
-    double tr_rho[48], tr_temp[48], tr_cur[48], tr_lambda[48];
-};
-
-// The kernel that factorises a window's reduced system: k_ldlt_reg (the matrix in registers, up to 40 free keyframes) or
-// k_ldlt_dev (in place in device memory, any size)
-enum LdltForm : int { kLdltDev = 0, kLdltReg = 2 };
-
-// What the one-thread-per-landmark kernels need of an edge before they can go to its keyframe, packed and kept in the order of the
-// landmarks' edge lists (position a of LbaWin::pt_k: a landmark's records are neighbours): two 16-byte loads in place of the
-// index pt_k[a] and, behind it, eight scattered loads of the per-edge arrays.  Copies: the per-edge arrays stay what every other
-// kernel reads.  k_prepare builds the records, k_transition keeps the flags in step with e_robust / e_level1.
-struct EdgeRec {
-    float obs[3], w;   // in_obs, in_w of the edge
-    int32_t pose;      // e_pose
-    int32_t pl_pos;    // pl_pos
-    uint32_t flags;    // kEdgeStereo | kEdgeRobust | kEdgeLevel1
-    uint32_t pad_;
-};
-static_assert(sizeof(EdgeRec) == 32, "an edge record is two 16-byte loads");
-constexpr uint32_t kEdgeStereo = 1, kEdgeRobust = 2, kEdgeLevel1 = 4;
-
-// device-side view of one window
-struct LbaWin {
-    int n_poses, n_points, n_edges, np, nl, n_items;
-    int iters1, iters2;              // optimize(5), optimize(10) (Optimizer.cc:661, 708)
-    // raw float32 inputs as the reference holds them (staged), converted by k_prepare (Converter.cc:37-47, 83-90)
-    const float *in_Tcw, *in_xyz, *in_obs, *in_w;   // (observations and information weights stay float32: the kernels widen them on
-                                                     // load -- exact -- instead of reading converted double copies, 16 bytes per edge and use)
-    double *pose, *point;            // estimates, contiguous [7 n_poses | 3 n_points]
-    double *bk;                      // SparseOptimizer::push backup of the same span
-    int est_n;
-    const int32_t *e_pose, *e_point;
-    const uint8_t *e_stereo;
-    uint8_t *e_robust, *e_level1;
-    double *err;                     // n_edges x 3, last computed _error
-    Cam cam;
-    const int32_t *pl_pos;           // edge -> its position in the landmark's free-keyframe edge list (-1: fixed keyframe)
-    const int32_t *hpose, *hpoint;   // hidx -> pose / point index
-    const int32_t *pt_off, *pt_k;    // edges by point (insertion order)
-    const int32_t *ps_off, *ps_k;    // edges by free pose
-    const int32_t *pl_off, *pl_ph;   // free-pose edges by point, ascending pose hidx: the pose hidx of each position
-    // Schur complement by items: item = (landmark, free-pose edges ka <= kb of it), ranked by (pose, pose) block in
-    // upper-triangular order, landmark order inside a block (build_schur_items)
-    const int32_t *it_ka, *it_kb, *it_l, *blk_off;
-    // k_schur's packed units (build_schur_units): rows of <= 16 items of ONE off-diagonal block, 16 rows per workgroup
-    const int32_t *sr_o0, *sr_info, *sr_ij;   // per row: first item; items | row-in-block << 8 | rows-of-block << 16; i1 | i2 << 16
-    int n_srows;
-    // Linearisation record of a free-keyframe edge, DENSE by its position in the pl list (a landmark's records are
-    // neighbours): {a = x / z, b = y / z, iz = 1 / z of the camera-frame point, robustified information w} -- 32 bytes in
-    // place of the edge's 144-byte Hpl block J_pose^T (w Omega) J_point, which factors as -E^T C R (EdgeLin below; R: the
-    // keyframe's rotation at the linearisation point, Rl) and is applied in that form.  w < 0 marks a stereo edge (|w| is
-    // the weight); a masked edge holds zeros: every product it takes part in is +-0.
-    double *lrec;
-    double *lomr;                    // 3 per free-keyframe edge (position like lrec): omr = -rho' Omega e of the linearisation (k_schur forms b_p from it)
-    double *Rl;                      // 9 per free keyframe (hidx): rotation the system was linearised at (k_lin)
-    double *Hpp, *Hll, *b, *x, *Hs, *bs;
-    double *tmp;                     // scale terms of the poses (6 np)
-    double *scal;                    // [3] solve ok
-    double *part;                    // per-landmark sums of k_points: chi2 terms [0, nl), scale terms [nl, 2 nl)
-    int n_part;                      // workgroups of a k_points launch for this window
-    EdgeRec *erec;                   // per position of pt_k: the edge's record (the walk layout's kernels)
-    int npad;                        // 6 np rounded up to a multiple of 16
-    LdltForm ldlt_form;
-    int hs_ld;                       // leading dimension of Hs: always npad now (both forms take the padded matrix)
-    LmState *st;
-    const int32_t *abort_word;       // mapped host memory: the forwarded pbStopFlag
-    float *out_Tcw, *out_xyz;        // Converter::toCvMat / toCvMat(Vector3d) write-back (Optimizer.cc:763-778)
-    double *out_chi2;
-    uint8_t *out_outlier;
-};
-
-// (the kernels' code depends on the members' offsets: a change here is a change of every kernel, to be measured as one)
-static_assert(sizeof(LbaWin) == 520 && offsetof(LbaWin, st) == 472, "LbaWin's layout is fixed");
-
-// One workgroup's share of a launch: (window, what).  The host lays the work of ALL windows of a call out as task lists (one per
-// kernel family) instead of grids padded to the largest window -- the windows of a batch differ (10-40 keyframes, 2-6 k points),
-// and a workgroup that only finds out it has nothing to do still holds a slot for two dependent loads.
-struct SchurTask {
-    int32_t w;      // window (-1: padding)
-    int32_t code;   // k_schur: kind << 28 | argument; k_lin: kind << 28 | block; k_points: block
-};
 
 // an edge record as its two 16-byte halves: {obs[3], w} and {pose, pl_pos, flags, -}
 typedef float flt4_t __attribute__((ext_vector_type(4)));
@@ -600,7 +479,7 @@ __device__ __forceinline__ void lrec_backsub(const Cam &cam, const dbl4_t rec, c
 // thread adds the per-edge terms in edge order, so the sums are the ones a thread walking the edges one after the other
 // would form (the order g2o adds them in), while the chain of dependent gathers per thread is one edge long instead of
 // the whole observation list (a single window has only ~2000 landmarks: the walk was pure latency).
-constexpr int kLmBlock = 32, kLmSlots = 8;
+// (kLmBlock = 32, kLmSlots = 8: lba_window.h)
 // edges of a landmark fetched together by the one-thread-per-landmark kernels (measured on 32 windows of 24 k edges, 6
 // observations per landmark: k_points_walk 43.4 us with 4 / 4, 38.6 with 6 / 6; the linearisation spills beyond 4)
 constexpr int kWalkChunk = 4;     // free-keyframe edges (back-substitution)
@@ -720,10 +599,8 @@ __global__ __launch_bounds__(256) void k_points(const LbaWin *__restrict__ wins,
 // that every edge of the workgroup's landmarks gathers from.  The last level of the walks' dependent gathers then reads LDS.
 // A window whose state is larger than kWalkLdsBytes reads device memory as before (a choice per workgroup; both from one body).
 // 16 KB per workgroup: with 12 waves per compute unit (three per SIMD) that is 3 workgroups of k_lin / 6 of k_points_walk, 48 / 96 of
-// the unit's 160 KB -- the registers bound the residency, not the LDS.
-constexpr int kWalkLdsBytes = 16 * 1024;
+// the unit's 160 KB -- the registers bound the residency, not the LDS.  (kWalkLdsBytes, walk_lds_bytes: lba_window.h)
 extern __shared__ double walk_sm[];   // the dynamic LDS of k_points_walk and k_lin<true>
-__host__ __device__ constexpr int walk_lds_bytes(int n_poses, int np) { return 8 * (7 * n_poses + 15 * np); }
 __device__ __forceinline__ void walk_stage(const LbaWin &W, double *sm, bool with_x)
 {
     const int n7 = 7 * W.n_poses, n6 = 6 * W.np, n9 = 9 * W.np;
@@ -1158,8 +1035,8 @@ constexpr int kSchurThreads = 256;
 //         few dozen, often fewer than 16 -- one wave per block left 40-85 % of the lanes idle and a window of 40 free keyframes
 //         cost 235 workgroups.  Row sums by DPP, then a block's rows are added in row order: for a block of up to 64 items
 //         exactly the sums (and bits) of the one-wave-per-block form.
-constexpr int kSchurDiag = 0, kSchurBig = 1, kSchurPack = 2;
-// (SchurTask.code = kind << 28 | argument -- DIAG: i; BIG: block rank; PACK: first row; w = -1: padding of the XCD interleave)
+// (kSchurDiag = 0, kSchurBig = 1, kSchurPack = 2: lba_window.h;
+// SchurTask.code = kind << 28 | argument -- DIAG: i; BIG: block rank; PACK: first row; w = -1: padding of the XCD interleave)
 // one item: (Hll + lambda I)^-1 of the landmark, and B_a D^-1 B_b^T in factored form.  With B = -E^T C R (lrec_form)
 //     B_a D^-1 B_b^T = E_a^T Q E_b,   Q = C_a (R_a D^-1 R_b^T) C_b   (3 x 3),
 // and the products with E = [ [a b 1]x | -iz I ] are cross products: the two 144-byte blocks are neither stored nor fetched --
@@ -1395,8 +1272,7 @@ constexpr int kTileBatch = 4;
 // doubles of dynamic LDS ldlt_body needs (W, the four vectors, T_k^T of two panels, the staged diagonal block, 16 of slack) ...
 __host__ __device__ constexpr size_t ldlt_dev_lds_doubles(int npad) { return (size_t)npad * 17 + 4 * (size_t)npad + 3 * 16 * 17 + 16; }
 // ... and the largest window that fits a CU's 160 KB with the kernel's static LDS: npad = 928, 154 free keyframes.  A larger window is
-// refused on the host (build_structures) before anything is enqueued.
-constexpr int kLdMaxNpad = 928, kLdMaxNp = kLdMaxNpad / 6;
+// refused on the host (build_structures) before anything is enqueued.  (kLdMaxNpad, kLdMaxNp: lba_window.h)
 constexpr size_t kLdMaxDynLds = ldlt_dev_lds_doubles(kLdMaxNpad) * sizeof(double);   // 162 560 B
 static_assert(kLdMaxDynLds + 64 <= 160 * 1024 && ldlt_dev_lds_doubles(kLdMaxNpad + 16) * sizeof(double) + 64 > 160 * 1024,
               "k_ldlt_dev: kLdMaxNpad is the largest padded size whose dynamic + static LDS fits a CU's 160 KB");
@@ -1845,9 +1721,11 @@ __global__ __launch_bounds__(256) void k_final(const LbaWin *__restrict__ wins)
 }
 
 // ---------------------------------------------------------------------------------------------------------- host
+static_assert(kLrMaxNpad == 16 * kLrMaxNb, "lba_window.h restates the register form's size limit (ldlt_reg.h)");
+
 // The reduced-system kernels take their LDS dynamically (the panel and the vectors of the largest window of a launch): each
 // kernel's cap is declared once per device binding, and every launch goes through enqueue_ldlt, which sizes it
-static int ldlt_declare_lds()
+int ldlt_declare_lds()
 {
     AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_dev, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdMaxDynLds));
     AOS2_HIP_CHECK(hipFuncSetAttribute((const void *)k_ldlt_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLrMaxDynLds));
@@ -1855,673 +1733,28 @@ static int ldlt_declare_lds()
 }
 // Both forms over the descriptors blk[0 .. nw): a window returns early from the kernel that is not its form.  mx_npad_reg /
 // mx_npad_dev: the largest padded size among the windows of that form, 0 = none (the kernel is not launched)
-static void enqueue_ldlt(const LbaWin *blk, int nw, int mx_npad_reg, int mx_npad_dev, hipStream_t q_reg, hipStream_t q_dev)
+void enqueue_ldlt(const LbaWin *blk, int nw, int mx_npad_reg, int mx_npad_dev, hipStream_t q_reg, hipStream_t q_dev)
 {
     if (mx_npad_reg > 0)
         hipLaunchKernelGGL(k_ldlt_reg, dim3(nw), dim3(kLrThreads), ldlt_reg_lds_doubles(mx_npad_reg) * sizeof(double), q_reg, blk);
     if (mx_npad_dev > 0) hipLaunchKernelGGL(k_ldlt_dev, dim3(nw), dim3(512), ldlt_dev_lds_doubles(mx_npad_dev) * sizeof(double), q_dev, blk);
 }
 
-int lba_handle_init(aos2_lba *s)
-{
-    int st = bind_device(s->device);
-    if (st) return st;
-    if (s->dev_ready) return AOS2_OK;
-    // The optimiser's kernels are few workgroups on a latency-bound chain; the tracking kernels that share the device in a
-    // running system (extraction, searches) are wide and throughput-bound.  On a high-priority stream the optimiser's
-    // workgroups are dispatched ahead of the waiting ones of those kernels.
-    if ((st = stream_create(&s->stream, true))) return st;
-    for (auto &e : s->ev) AOS2_HIP_CHECK(hipEventCreate(&e));
-    {
-        if ((st = stream_create(&s->stream2, true))) return st;
-        AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        AOS2_HIP_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-    }
-    if ((st = ldlt_declare_lds())) return st;
-    s->dev_ready = true;
-    return AOS2_OK;
-}
-
-// The second window group's streams and events, created when a call first runs two groups: a handle that never does keeps two
-// streams.  (The runtime maps the streams of a priority class onto GPU_MAX_HW_QUEUES = 4 hardware queues by creation order and
-// serialises those that share one: two handles solving side by side, each with four streams, had their main streams on the same
-// queue in some processes and not in others -- 50 k against 60 k frames/s of the composite from run to run.)
-static int lba_group_streams(aos2_lba *s)
-{
-    if (s->stream_b) return AOS2_OK;
-    if (int st_ = stream_create(&s->stream_b, true)) return st_;
-    if (int st_ = stream_create(&s->stream2_b, true)) return st_;
-    for (hipEvent_t *ev : {&s->ev_fork_b, &s->ev_join_b, &s->ev_up, &s->ev_stag, &s->ev_done_b}) AOS2_HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return AOS2_OK;
-}
-
-static bool stop_requested(const aos2_lba_problem_t *p) { return p->stop_flag && *p->stop_flag != 0; }
-
-// index mapping and edge lists of a window: initializeOptimization(level 0) + buildIndexMapping + the symbolic part of
-// buildStructure for ALL edges (the second optimisation masks edges instead of rebuilding)
-struct Pass {
-    std::vector<int32_t> k_ph, k_lh, hpose, hpoint, pt_off, pt_k, ps_off, ps_k, pl_off, pl_k;
-    std::vector<int32_t> pl_pos, pl_ph;   // edge -> position in pl_k (-1: fixed keyframe); position -> pose hidx
-    std::vector<int32_t> it_ka, it_kb, it_l, blk_off;   // Schur items (k_schur_items / k_schur_blocks)
-    std::vector<int32_t> sr_o0, sr_info, sr_ij, units;    // k_schur's row table and unit codes (build_schur_units)
-    int np = 0, nl = 0;
-};
-// worker threads of a handle for the per-window host work of a batch (structure build, staging): created once -- 32
-// std::thread per phase cost ~1 ms per call
-struct WindowPool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv_go, cv_done;
-    std::function<void(int)> fn;
-    int n_items = 0, generation = 0, running = 0;
-    std::atomic<int> next{0};
-    bool quit = false;
-    void start(int n)
-    {
-        int born;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            born = generation;   // a thread added later starts with the jobs after its creation, not with a finished one
-        }
-        active = n;
-        for (int t = (int)th.size(); t < n; ++t)
-            th.emplace_back([this, born, idx = t] {
-                int seen = born;
-                for (;;) {
-                    {
-                        std::unique_lock<std::mutex> lk(m);
-                        cv_go.wait(lk, [&] { return quit || generation != seen; });
-                        if (quit) return;
-                        seen = generation;
-                    }
-                    if (idx < active)
-                        for (int i; (i = next.fetch_add(1)) < n_items;) fn(i);
-                    std::lock_guard<std::mutex> lk(m);
-                    if (--running == 0) cv_done.notify_one();
-                }
-            });
-    }
-    int active = 0;   // workers that take items of the current job (a lowered host_threads setting: the others just check in)
-    void run(int n, std::function<void(int)> f)
-    {
-        if (n <= 1 || th.empty()) {
-            for (int i = 0; i < n; ++i) f(i);
-            return;
-        }
-        std::unique_lock<std::mutex> lk(m);
-        fn = std::move(f);
-        n_items = n;
-        next = 0;
-        running = (int)th.size();
-        ++generation;
-        cv_go.notify_all();
-        cv_done.wait(lk, [&] { return running == 0; });
-    }
-    ~WindowPool()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            quit = true;
-        }
-        cv_go.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-struct LbaCache {
-    std::vector<Pass> passes;
-    WindowPool pool;
-};
-
-// worker threads of a batch's per-window host work (structure build, staging): the handle's setting, else
-// AOS2_LBA_HOST_THREADS, else the host's cores shared among the ranks of the node (LOCAL_WORLD_SIZE / WORLD_SIZE as the
-// launcher exports them: 8 ranks x 2 handles x 32 threads would be 512 threads on 256 cores), at most 32, at most one per window
-static int lba_host_threads(const aos2_lba *s, int nw)
-{
-    int n = s->host_threads;
-    if (n <= 0)
-        if (const char *e = getenv("AOS2_LBA_HOST_THREADS")) n = atoi(e);
-    if (n <= 0) {
-        int ranks = 1;
-        const char *e = getenv("LOCAL_WORLD_SIZE");
-        if (!e) e = getenv("WORLD_SIZE");
-        if (e && atoi(e) > 1) ranks = atoi(e);
-        n = std::min(32, std::max(1, (int)std::thread::hardware_concurrency() / ranks));
-    }
-    return std::max(1, std::min(n, nw));
-}
-
-static bool build_pass(const aos2_lba_problem_t *p, Pass &S)
-{
-    // (the vectors keep their storage from call to call: a 24 k-edge window holds ~1.5 MB of index lists, and fresh
-    // allocations of that size are mmap / page faults / munmap every time -- 2 ms per 32-window call, half of it at scope exit)
-    S.hpose.clear(); S.hpoint.clear(); S.it_ka.clear(); S.it_kb.clear(); S.it_l.clear(); S.blk_off.clear();
-    S.np = S.nl = 0;
-    const int E = p->n_edges;
-    std::vector<uint8_t> pose_act(p->n_poses, 0), point_act(p->n_points, 0);
-    for (int e = 0; e < E; ++e) {
-        pose_act[p->edge_pose[e]] = 1;
-        point_act[p->edge_point[e]] = 1;
-    }
-    std::vector<int32_t> pose_h(p->n_poses, -1), point_h(p->n_points, -1);
-    for (int i = 0; i < p->n_poses; ++i)
-        if (pose_act[i] && !p->pose_fixed[i]) S.hpose.push_back(i);
-    auto by_pose_id = [&](int a, int b) { return p->pose_id[a] < p->pose_id[b]; };
-    if (!std::is_sorted(S.hpose.begin(), S.hpose.end(), by_pose_id)) std::stable_sort(S.hpose.begin(), S.hpose.end(), by_pose_id);
-    for (int i = 0; i < p->n_points; ++i)
-        if (point_act[i]) S.hpoint.push_back(i);
-    auto by_point_id = [&](int a, int b) { return p->point_id[a] < p->point_id[b]; };
-    if (!std::is_sorted(S.hpoint.begin(), S.hpoint.end(), by_point_id)) std::stable_sort(S.hpoint.begin(), S.hpoint.end(), by_point_id);
-    S.np = (int)S.hpose.size();
-    S.nl = (int)S.hpoint.size();
-    for (int i = 0; i < S.np; ++i) pose_h[S.hpose[i]] = i;
-    for (int i = 0; i < S.nl; ++i) point_h[S.hpoint[i]] = i;
-    S.k_ph.resize(E);
-    S.k_lh.resize(E);
-    S.pt_off.assign(S.nl + 1, 0);
-    S.ps_off.assign(S.np + 1, 0);
-    S.pl_off.assign(S.nl + 1, 0);
-    for (int k = 0; k < E; ++k) {
-        S.k_ph[k] = pose_h[p->edge_pose[k]];
-        S.k_lh[k] = point_h[p->edge_point[k]];
-        S.pt_off[S.k_lh[k] + 1]++;
-        if (S.k_ph[k] >= 0) {
-            S.ps_off[S.k_ph[k] + 1]++;
-            S.pl_off[S.k_lh[k] + 1]++;
-        }
-    }
-    for (int i = 0; i < S.nl; ++i) {
-        S.pt_off[i + 1] += S.pt_off[i];
-        S.pl_off[i + 1] += S.pl_off[i];
-    }
-    for (int i = 0; i < S.np; ++i) S.ps_off[i + 1] += S.ps_off[i];
-    S.pt_k.resize(S.pt_off[S.nl]);
-    S.ps_k.resize(S.ps_off[S.np]);
-    S.pl_k.resize(S.pl_off[S.nl]);
-    std::vector<int> f1(S.nl, 0), f2(S.np, 0), f3(S.nl, 0);
-    for (int k = 0; k < E; ++k) {
-        const int l = S.k_lh[k], ph = S.k_ph[k];
-        S.pt_k[S.pt_off[l] + f1[l]++] = k;
-        if (ph >= 0) {
-            S.ps_k[S.ps_off[ph] + f2[ph]++] = k;
-            S.pl_k[S.pl_off[l] + f3[l]++] = k;
-        }
-    }
-    // per landmark: ascending pose index, ties in edge order (a stable insertion sort: the runs are a handful of
-    // edges long, and std::stable_sort would allocate a buffer for each of the thousands of runs)
-    for (int l = 0; l < S.nl; ++l) {
-        int32_t *q = S.pl_k.data() + S.pl_off[l];
-        const int m = S.pl_off[l + 1] - S.pl_off[l];
-        for (int i = 1; i < m; ++i) {
-            const int32_t v = q[i], key = S.k_ph[v];
-            int j = i - 1;
-            for (; j >= 0 && S.k_ph[q[j]] > key; --j) q[j + 1] = q[j];
-            q[j + 1] = v;
-        }
-        for (int i = 1; i < m; ++i)
-            if (S.k_ph[q[i]] == S.k_ph[q[i - 1]]) return false;   // two edges between one keyframe and one landmark
-    }
-    S.pl_pos.assign(E, -1);
-    S.pl_ph.resize(S.pl_k.size());
-    for (size_t a = 0; a < S.pl_k.size(); ++a) {
-        S.pl_pos[S.pl_k[a]] = (int32_t)a;
-        S.pl_ph[a] = S.k_ph[S.pl_k[a]];
-    }
-    return true;
-}
-
-// items ranked by (pose, pose) block -- upper block triangle, row-major -- and by landmark inside a block (counting
-// sort; this order is the summation order of k_schur_blocks)
-static void build_schur_items(Pass &S)
-{
-    size_t n = 0;
-    for (int l = 0; l < S.nl; ++l) {
-        const size_t m = (size_t)(S.pl_off[l + 1] - S.pl_off[l]);
-        n += m * (m + 1) / 2;
-    }
-    const int np = S.np;
-    const size_t nblk = (size_t)np * (np + 1) / 2;
-    S.it_ka.resize(n); S.it_kb.resize(n); S.it_l.resize(n);
-    S.blk_off.assign(nblk + 1, 0);
-    // block of (i1 <= i2) = row_base[i1] + i2 (pl_k is sorted by pose, so a <= b gives i1 <= i2)
-    std::vector<int32_t> row_base(np > 0 ? np : 1);
-    const std::vector<int32_t> &ph = S.pl_ph;
-    for (int i = 0; i < np; ++i) row_base[i] = i * np - i * (i - 1) / 2 - i;
-    for (int l = 0; l < S.nl; ++l) {
-        const int32_t *q = ph.data() + S.pl_off[l];
-        const int m = S.pl_off[l + 1] - S.pl_off[l];
-        for (int a = 0; a < m; ++a) {
-            int32_t *cnt = S.blk_off.data() + row_base[q[a]] + 1;
-            for (int b = a; b < m; ++b) cnt[q[b]]++;
-        }
-    }
-    for (size_t i = 0; i < nblk; ++i) S.blk_off[i + 1] += S.blk_off[i];
-    std::vector<int32_t> fill(S.blk_off.begin(), S.blk_off.end() - 1);
-    for (int l = 0; l < S.nl; ++l) {
-        const int c0 = S.pl_off[l], m = S.pl_off[l + 1] - c0;
-        const int32_t *q = ph.data() + c0;
-        for (int a = 0; a < m; ++a) {   // (items name the two edges by their positions in the pl list = the indices of the dense Hpl array)
-            int32_t *f = fill.data() + row_base[q[a]];
-            const int32_t ka = c0 + a;
-            for (int b = a; b < m; ++b) {
-                const int slot = f[q[b]]++;
-                S.it_ka[slot] = ka;
-                S.it_kb[slot] = c0 + b;
-                S.it_l[slot] = l;
-            }
-        }
-    }
-}
-
-// k_schur's units of a window (see the kernel): DIAG units first (the long ones must not be dispatched last), then the BIG
-// off-diagonal blocks, then the PACK units -- off-diagonal blocks in rank order, ceil(n / 16) rows each (an empty block keeps one
-// row: its zeros are written like any other sum), a block never split across two units.
-static void build_schur_units(Pass &S)
-{
-    S.sr_o0.clear(); S.sr_info.clear(); S.sr_ij.clear(); S.units.clear();
-    const int np = S.np;
-    for (int i = 0; i < np; ++i) S.units.push_back((kSchurDiag << 28) | i);
-    std::vector<int32_t> pack_first;
-    int in_unit = 0;
-    for (int i1 = 0, blk = 0; i1 < np; ++i1)
-        for (int i2 = i1; i2 < np; ++i2, ++blk) {
-            if (i2 == i1) continue;
-            const int o0 = S.blk_off[blk], n = S.blk_off[blk + 1] - o0;
-            if (n > 256) {
-                S.units.push_back((kSchurBig << 28) | blk);
-                continue;
-            }
-            const int nrows = std::max(1, (n + 15) / 16);
-            if (in_unit + nrows > 16) {   // pad the unit: a block's rows stay together
-                for (; in_unit < 16; ++in_unit) {
-                    S.sr_o0.push_back(0); S.sr_info.push_back(0); S.sr_ij.push_back(0);
-                }
-                in_unit = 0;
-            }
-            if (in_unit == 0) pack_first.push_back((int32_t)S.sr_o0.size());
-            for (int r = 0; r < nrows; ++r) {
-                S.sr_o0.push_back(o0 + 16 * r);
-                S.sr_info.push_back(std::max(0, std::min(16, n - 16 * r)) | (r << 8) | (nrows << 16));
-                S.sr_ij.push_back(i1 | (i2 << 16));
-            }
-            in_unit = (in_unit + nrows) % 16;
-        }
-    for (int32_t f : pack_first) S.units.push_back((kSchurPack << 28) | f);
-}
-
-// byte offsets of one window's regions in the arena
-struct WinLayout {
-    // staged (uploaded)
-    size_t in_Tcw, in_xyz, in_obs, in_w, e_pose, e_point, e_stereo, pl_pos, hpose, hpoint, pt_off, pt_k, ps_off, ps_k,
-        pl_off, pl_k, it_ka, it_kb, it_l, blk_off, sr_o0, sr_info, sr_ij;
-    // device only
-    size_t est, bk, robust, level1, err, lrec, lomr, Rl, Hpp, Hll, b, x, Hs, bs, tmp, scal, part, erec;
-    // results (downloaded)
-    size_t out_Tcw, out_xyz, out_outlier, out_chi2, st;
-    int n_part, npad;
-    LdltForm ldlt_form;
-    size_t n_items;
-};
-
-// ROCTx ranges around the host-side phases of a solve (AOS2_ROCTX=1; rocprofv3 --marker-trace shows them next to the
-// kernels).  The library is looked up at run time: no link dependency.  g2o's statistics buckets
-// (Thirdparty/g2o/g2o/core/batch_stats.h, filled in block_solver.hpp:441-453 and sparse_optimizer.cpp:376-414) map to
-// the kernels of the device program: timeResiduals -> k_points, timeLinearize + timeQuadraticForm -> k_lin,
-// timeSchurComplement -> k_schur, timeLinearSolver -> k_ldlt_reg / k_ldlt_dev, timeUpdate -> the pose
-// update inside the LDL^T kernel and the landmark update inside k_points.
-struct RoctxRange {
-    typedef int (*push_t)(const char *);
-    typedef int (*pop_t)();
-    static void resolve(push_t &push, pop_t &pop)
-    {
-        static push_t s_push = nullptr;
-        static pop_t s_pop = nullptr;
-        static bool tried = false;
-        if (!tried) {
-            tried = true;
-            const char *v = getenv("AOS2_ROCTX");
-            if (v && atoi(v) != 0) {
-                void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
-                if (!h) h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-                if (h) {
-                    s_push = (push_t)dlsym(h, "roctxRangePushA");
-                    s_pop = (pop_t)dlsym(h, "roctxRangePop");
-                }
-            }
-        }
-        push = s_push;
-        pop = s_pop;
-    }
-    pop_t pop_ = nullptr;
-    explicit RoctxRange(const char *name)
-    {
-        push_t push;
-        resolve(push, pop_);
-        if (push && pop_) push(name); else pop_ = nullptr;
-    }
-    ~RoctxRange()
-    {
-        if (pop_) pop_();
-    }
-};
-
-struct Bump {
-    size_t size = 0;
-    size_t take(size_t bytes, size_t align = 256)
-    {
-        const size_t off = (size + align - 1) & ~(align - 1);
-        size = off + bytes;
-        return off;
-    }
-};
-
-// ---- the per-window host work: index structures, arena regions, staging
-
-// The index structures of n windows -- window i is problems[ids ? ids[i] : i] -- into passes[0 .. n), a pool thread per window,
-// after the range check of the edges' vertex indices
-static int build_structures(WindowPool &pool, const aos2_lba_problem_t *problems, const int *ids, int n, std::vector<Pass> &passes)
-{
-    std::vector<uint8_t> pass_ok(n, 1);
-    std::vector<int> bad_edge(n, -1);
-    pool.run(n, [&](int i) {
-        const aos2_lba_problem_t *p = problems + (ids ? ids[i] : i);
-        for (int e = 0; e < p->n_edges; ++e)
-            if (p->edge_pose[e] < 0 || p->edge_pose[e] >= p->n_poses || p->edge_point[e] < 0 || p->edge_point[e] >= p->n_points) {
-                bad_edge[i] = e;
-                return;
-            }
-        pass_ok[i] = build_pass(p, passes[i]) ? 1 : 0;
-        if (pass_ok[i] && passes[i].np > 0) {
-            build_schur_items(passes[i]);
-            build_schur_units(passes[i]);
-        } else
-            passes[i].units.clear();
-    });
-    for (int i = 0; i < n; ++i)
-        if (bad_edge[i] >= 0) {
-            set_error("problem %d: edge %d references a vertex out of range", ids ? ids[i] : i, bad_edge[i]);
-            return AOS2_ERR_ARG;
-        }
-    for (int i = 0; i < n; ++i)
-        if (!pass_ok[i]) {   // (cannot come from the reference: KeyFrame observations are a map MapPoint -> index)
-            set_error("problem %d: two edges connect the same keyframe and map point", ids ? ids[i] : i);
-            return AOS2_ERR_ARG;
-        }
-    for (int i = 0; i < n; ++i)
-        if (passes[i].np > kLdMaxNp) {   // (k_ldlt_dev's panel and vectors would not fit a CU's LDS: kLdMaxDynLds)
-            set_error("problem %d: %d free keyframes, the reduced-system solve takes at most %d", ids ? ids[i] : i, passes[i].np, kLdMaxNp);
-            return AOS2_ERR_ARG;
-        }
-    return AOS2_OK;
-}
-
-// The landmark kernels' layout of a call (see aos2_lba_solve_batch) and the block sizes that follow from it
-struct LmLayout {
-    bool walk;
-    int lm_per_block, lin_block;
-    int points_blocks(const Pass &S) const { return std::max(1, (S.nl + lm_per_block - 1) / lm_per_block); }   // workgroups of a k_points launch
-    int lin_blocks(const Pass &S) const { return (S.nl + lin_block - 1) / lin_block; }                         // landmark workgroups of a k_lin launch
-};
-
-// The staged regions of a window, in arena order: fn(its WinLayout member, the host array it is filled from, the array's bytes,
-// bytes of tail).  A region is array + tail long.  The layout and the staging copy both go through this one list.
-template <class Layout, class Fn>
-static inline void for_each_staged(const aos2_lba_problem_t &p, const Pass &S, Layout &l, Fn &&fn)
-{
-    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
-    fn(l.in_Tcw, p.pose_Tcw, 64 * NP, 0); fn(l.in_xyz, p.point_xyz, 12 * NL, 0); fn(l.in_obs, p.edge_obs, 12 * E, 0); fn(l.in_w, p.edge_inv_sigma2, 4 * E, 0);
-    fn(l.e_pose, p.edge_pose, 4 * E, 0); fn(l.e_point, p.edge_point, 4 * E, 0); fn(l.e_stereo, p.edge_stereo, E, 0);
-    auto list = [&](auto &off, const std::vector<int32_t> &v, size_t tail) { fn(off, v.data(), 4 * v.size(), tail); };
-    list(l.pl_pos, S.pl_pos, 0);   // (one per edge)
-    list(l.hpose, S.hpose, 4); list(l.hpoint, S.hpoint, 4);
-    list(l.pt_off, S.pt_off, 0); list(l.pt_k, S.pt_k, 4);   // (the offset lists hold nl + 1 or np + 1 entries: never empty)
-    list(l.ps_off, S.ps_off, 0); list(l.ps_k, S.ps_k, 4);
-    list(l.pl_off, S.pl_off, 0); list(l.pl_k, S.pl_ph, 4);
-    list(l.it_ka, S.it_ka, 4); list(l.it_kb, S.it_kb, 4); list(l.it_l, S.it_l, 4);
-    list(l.blk_off, S.blk_off, 4);
-    list(l.sr_o0, S.sr_o0, 4); list(l.sr_info, S.sr_info, 4); list(l.sr_ij, S.sr_ij, 4);
-}
-
-static void layout_staged(const aos2_lba_problem_t &p, const Pass &S, Bump &B, WinLayout &l)
-{
-    for_each_staged(p, S, l, [&](size_t &off, const void *, size_t bytes, size_t tail) { off = B.take(bytes + tail); });
-    l.n_items = S.it_ka.size();
-}
-
-// the window's staged regions into the staging buffer `dst` (which mirrors the arena)
-static void stage_window(uint8_t *dst, const WinLayout &l, const aos2_lba_problem_t &p, const Pass &S)
-{
-    for_each_staged(p, S, l, [&](size_t off, const void *src, size_t bytes, size_t) {
-        if (bytes) memcpy(dst + off, src, bytes);
-    });
-}
-
-// the device-only regions, and which reduced-system kernel the window takes
-static void layout_scratch(const aos2_lba_problem_t &p, const Pass &S, const LmLayout &lay, Bump &B, WinLayout &l)
-{
-    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
-    const size_t n6 = 6 * (size_t)S.np, dim = n6 + 3 * (size_t)S.nl;
-    l.est = B.take(8 * (7 * NP + 3 * NL)); l.bk = B.take(8 * (7 * NP + 3 * NL));
-    l.robust = B.take(E); l.level1 = B.take(E);
-    l.err = B.take(24 * E);
-    l.lrec = B.take(32 * (S.pl_k.size() + 1)); l.lomr = B.take(24 * (S.pl_k.size() + 1)); l.Rl = B.take(72 * (size_t)S.np + 8);
-    l.Hpp = B.take(288 * (size_t)S.np + 8); l.Hll = B.take(72 * (size_t)S.nl + 8);
-    l.b = B.take(8 * dim + 8); l.x = B.take(8 * dim + 8);
-    l.npad = (int)((n6 + 15) & ~(size_t)15);
-    // the register-resident form serves every window of up to 40 free keyframes
-    l.ldlt_form = l.npad <= 16 * kLrMaxNb ? kLdltReg : kLdltDev;
-    // (both forms take the reduced system padded: k_schur writes it with leading dimension npad, k_ldlt_dev factorises it in place)
-    l.Hs = B.take(8 * (size_t)l.npad * l.npad + 8); l.bs = B.take(8 * n6 + 8);
-    l.tmp = B.take(8 * n6 + 8);
-    l.n_part = lay.points_blocks(S);
-    l.scal = B.take(64); l.part = B.take(16 * (size_t)std::max(S.nl, 1) + 8);
-    l.erec = B.take(sizeof(EdgeRec) * (E + 1));
-}
-
-// the regions that come back in one copy: the window's state, then its results
-static void layout_results(const aos2_lba_problem_t &p, bool want_chi2, Bump &B, WinLayout &l)
-{
-    const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges;
-    l.st = B.take(sizeof(LmState), 64);
-    l.out_Tcw = B.take(64 * NP, 64); l.out_xyz = B.take(12 * NL, 64); l.out_outlier = B.take(E, 64);
-    l.out_chi2 = want_chi2 ? B.take(8 * E, 64) : 0;
-}
-
-// the device-side view of a window whose regions lie at `base` + l
-static void describe_window(LbaWin &W, uint8_t *base, const aos2_lba_problem_t &p, const Pass &S, const WinLayout &l, const int32_t *abort_word, bool want_chi2)
-{
-    memset(&W, 0, sizeof(W));
-    W.n_poses = p.n_poses; W.n_points = p.n_points; W.n_edges = p.n_edges;
-    W.np = S.np; W.nl = S.nl; W.n_items = (int)l.n_items;
-    W.iters1 = p.iters_first; W.iters2 = p.iters_second;
-    W.in_Tcw = (const float *)(base + l.in_Tcw); W.in_xyz = (const float *)(base + l.in_xyz);
-    W.in_obs = (const float *)(base + l.in_obs); W.in_w = (const float *)(base + l.in_w);
-    W.pose = (double *)(base + l.est); W.point = W.pose + 7 * (size_t)p.n_poses;
-    W.bk = (double *)(base + l.bk);
-    W.est_n = 7 * p.n_poses + 3 * p.n_points;
-    W.e_pose = (const int32_t *)(base + l.e_pose); W.e_point = (const int32_t *)(base + l.e_point);
-    W.e_stereo = base + l.e_stereo; W.e_robust = base + l.robust; W.e_level1 = base + l.level1;
-    W.err = (double *)(base + l.err);
-    W.cam.fx = (double)p.fx; W.cam.fy = (double)p.fy; W.cam.cx = (double)p.cx; W.cam.cy = (double)p.cy;
-    W.cam.bf = (double)p.bf; W.cam.bf_f = p.bf;
-    W.cam.delta_mono = (double)(float)std::sqrt(5.991);
-    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
-    W.pl_pos = (const int32_t *)(base + l.pl_pos);
-    W.hpose = (const int32_t *)(base + l.hpose); W.hpoint = (const int32_t *)(base + l.hpoint);
-    W.pt_off = (const int32_t *)(base + l.pt_off); W.pt_k = (const int32_t *)(base + l.pt_k);
-    W.ps_off = (const int32_t *)(base + l.ps_off); W.ps_k = (const int32_t *)(base + l.ps_k);
-    W.pl_off = (const int32_t *)(base + l.pl_off); W.pl_ph = (const int32_t *)(base + l.pl_k);
-    W.it_ka = (const int32_t *)(base + l.it_ka); W.it_kb = (const int32_t *)(base + l.it_kb);
-    W.it_l = (const int32_t *)(base + l.it_l); W.blk_off = (const int32_t *)(base + l.blk_off);
-    W.sr_o0 = (const int32_t *)(base + l.sr_o0); W.sr_info = (const int32_t *)(base + l.sr_info); W.sr_ij = (const int32_t *)(base + l.sr_ij);
-    W.n_srows = (int)S.sr_o0.size();
-    W.lrec = (double *)(base + l.lrec); W.lomr = (double *)(base + l.lomr); W.Rl = (double *)(base + l.Rl); W.Hpp = (double *)(base + l.Hpp);
-    W.Hll = (double *)(base + l.Hll); W.b = (double *)(base + l.b); W.x = (double *)(base + l.x);
-    W.Hs = (double *)(base + l.Hs); W.bs = (double *)(base + l.bs);
-    W.tmp = (double *)(base + l.tmp); W.scal = (double *)(base + l.scal); W.part = (double *)(base + l.part);
-    W.n_part = l.n_part;
-    W.erec = (EdgeRec *)(base + l.erec); W.npad = l.npad; W.ldlt_form = l.ldlt_form;
-    W.hs_ld = l.npad;
-    W.st = (LmState *)(base + l.st);
-    W.abort_word = abort_word;
-    W.out_Tcw = (float *)(base + l.out_Tcw); W.out_xyz = (float *)(base + l.out_xyz);
-    W.out_outlier = base + l.out_outlier;
-    W.out_chi2 = want_chi2 ? (double *)(base + l.out_chi2) : nullptr;
-}
-
-// ---- what a launch sequence runs on
-
-// the largest dimensions of a set of windows, and which reduced-system kernels it needs
-struct GroupDims {
-    bool any_glob = false, any_reg = false;
-    int mx_E = 0, mx_pts = 0, mx_npad_glob = 0, mx_npad_reg = 0;
-    int walk_lds = 0;   // dynamic LDS of the walks: the largest keyframe state among the windows that stage it (walk_lds_bytes)
-    void add(const aos2_lba_problem_t &p, const Pass &S, const WinLayout &l)
-    {
-        if (S.np > 0) {
-            if (l.ldlt_form == kLdltReg) {
-                any_reg = true;
-                mx_npad_reg = std::max(mx_npad_reg, l.npad);
-            } else {
-                any_glob = true;
-                mx_npad_glob = std::max(mx_npad_glob, l.npad);
-            }
-        }
-        mx_E = std::max(mx_E, p.n_edges);
-        mx_pts = std::max(mx_pts, std::max(p.n_points, p.n_poses));
-        if (walk_lds_bytes(p.n_poses, S.np) <= kWalkLdsBytes) walk_lds = std::max(walk_lds, walk_lds_bytes(p.n_poses, S.np));
-    }
-};
-
-struct TaskLists {
-    std::vector<SchurTask> schur, pts, lin;
-    size_t size() const { return schur.size() + pts.size() + lin.size(); }
-};
-
-// The task lists of a set of windows `ids` (indices into passes), addressed by their position in `ids` (by_position: a compacted
-// descriptor array) or by ids[position].
-// k_schur's list: the units of all windows, window w on XCD w' (workgroups go round-robin to the 8 XCDs in linear-id order,
-// each with an L2 of its own -- 4 MB, about one window's working set: the Hpl blocks a window's items share are then served by
-// one L2), the windows dealt to the XCDs largest first (every XCD gets about the same number of units), two windows of an XCD
-// at a time, unit by unit -- their DIAG units first.  Padding entries (w = -1) keep the 8 queues in step.
-// The landmark kernels' lists: block b of every window before block b + 1 of any (the windows advance side by side); k_lin: every
-// landmark block first (the long dependent chains of the launch), then one task per free keyframe
-static void build_tasks(const std::vector<Pass> &passes, const std::vector<int> &ids, bool by_position, const LmLayout &lay, TaskLists &T, bool one_queue = false)
-{
-    auto wmap = [&](int k) { return by_position ? k : ids[k]; };
-    std::vector<SchurTask> &tasks = T.schur;
-    const int nwg = (int)ids.size();
-    std::vector<int> order(nwg);
-    std::iota(order.begin(), order.end(), 0);
-    // (dealt by unit count.  By estimated cost instead -- a DIAG / BIG unit = 2 + ceil(items / 256) workgroup rounds, a PACK unit one --
-    // the mixed 64-window batch took 4.15 / 4.17 / 4.14 ms against 4.14 / 4.13 / 4.12: the XCD queues are not what k_schur's tail waits for)
-    auto weight = [&](int k) { return passes[ids[k]].units.size(); };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return weight(a) > weight(b); });
-    const int NX = nwg >= 8 && !one_queue ? 8 : 1;
-    std::vector<std::vector<int>> xw(NX);
-    std::vector<size_t> load(NX, 0);
-    for (int k : order) {
-        const int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        xw[x].push_back(k);
-        load[x] += weight(k);
-    }
-    std::vector<std::vector<SchurTask>> qx(NX);
-    for (int x = 0; x < NX; ++x)
-        for (size_t k = 0; k < xw[x].size(); k += 2) {
-            const int a = xw[x][k], b = k + 1 < xw[x].size() ? xw[x][k + 1] : -1;
-            const std::vector<int32_t> &ua = passes[ids[a]].units;
-            static const std::vector<int32_t> none;
-            const std::vector<int32_t> &ub = b >= 0 ? passes[ids[b]].units : none;
-            for (size_t u = 0; u < std::max(ua.size(), ub.size()); ++u) {
-                if (u < ua.size()) qx[x].push_back(SchurTask{wmap(a), ua[u]});
-                if (u < ub.size()) qx[x].push_back(SchurTask{wmap(b), ub[u]});
-            }
-        }
-    size_t mxq = 0;
-    for (auto &q_ : qx) mxq = std::max(mxq, q_.size());
-    tasks.assign(mxq * NX, SchurTask{-1, 0});
-    for (int x = 0; x < NX; ++x)
-        for (size_t k = 0; k < qx[x].size(); ++k) tasks[k * NX + x] = qx[x][k];
-    int mx_pb = 0, mx_lb = 0, mx_k = 0;
-    std::vector<int> npb(nwg), nlb(nwg);
-    for (int k = 0; k < nwg; ++k) {
-        const Pass &S = passes[ids[k]];
-        npb[k] = lay.points_blocks(S);   // = WinLayout::n_part
-        nlb[k] = lay.lin_blocks(S);
-        mx_pb = std::max(mx_pb, npb[k]); mx_lb = std::max(mx_lb, nlb[k]); mx_k = std::max(mx_k, S.np);
-    }
-    T.pts.clear();
-    T.lin.clear();
-    for (int b = 0; b < mx_pb; ++b)
-        for (int k = 0; k < nwg; ++k)
-            if (b < npb[k]) T.pts.push_back(SchurTask{wmap(k), b});
-    for (int b = 0; b < mx_lb; ++b)
-        for (int k = 0; k < nwg; ++k)
-            if (b < nlb[k]) T.lin.push_back(SchurTask{wmap(k), b});
-    for (int kf = 0; kf < mx_k; ++kf)
-        for (int k = 0; k < nwg; ++k)
-            if (kf < passes[ids[k]].np) T.lin.push_back(SchurTask{wmap(k), (1 << 28) | kf});
-}
-
-// the device addresses of a TaskLists
-struct DevTasks {
-    const SchurTask *schur, *pts, *lin;
-};
-// Writes the three lists of T behind each other at byte offset `o` of the staging buffer `host`, which mirrors the device memory
-// at `dev`; `o` moves on to the end of what was written
-static DevTasks put_tasks(const TaskLists &T, uint8_t *host, const uint8_t *dev, size_t &o)
-{
-    DevTasks d;
-    const std::vector<SchurTask> *lists[3] = {&T.schur, &T.pts, &T.lin};
-    const SchurTask **where[3] = {&d.schur, &d.pts, &d.lin};
-    for (int k = 0; k < 3; ++k) {
-        *where[k] = (const SchurTask *)(dev + o);
-        if (!lists[k]->empty()) memcpy(host + o, lists[k]->data(), sizeof(SchurTask) * lists[k]->size());
-        o += sizeof(SchurTask) * lists[k]->size();
-    }
-    return d;
-}
-
-// the streams a launch sequence is enqueued on: its own, and the one the second reduced-system kernel runs on, forked and joined
-struct StreamSet {
-    hipStream_t q, q2;
-    hipEvent_t fork, join;
-};
-static StreamSet group_streams(const aos2_lba *s, int g)
-{
-    return g == 0 ? StreamSet{s->stream, s->stream2, s->ev_fork, s->ev_join} : StreamSet{s->stream_b, s->stream2_b, s->ev_fork_b, s->ev_join_b};
-}
-
-// What a launch sequence runs on: the descriptor array its task lists index (`wins`), the first descriptor and the number of
-// windows of the kernels that take one workgroup row per window (`blk`, nw), the lists, the largest dimensions, the streams
-struct Prog : StreamSet {
-    const LbaWin *wins, *blk;
-    int nw;
-    const SchurTask *schur, *pts, *lin;
-    size_t n_schur, n_pts, n_lin;
-    GroupDims D;
-};
-static Prog make_prog(const LbaWin *wins, const LbaWin *blk, int nw, const TaskLists &T, const DevTasks &d, const GroupDims &D, const StreamSet &Q)
-{
-    return Prog{Q, wins, blk, nw, d.schur, d.pts, d.lin, T.schur.size(), T.pts.size(), T.lin.size(), D};
-}
-
-// ---- enqueueing.  What the launches of a call share besides their Prog:
-struct LaunchCtx {
-    aos2_lba *s;
-    bool walk;              // the landmark kernels' layout (LmLayout::walk)
-    bool stagger_pending;   // two groups: the second group's stream has not been released yet (enqueue_trial)
-};
-
+// ---- enqueueing (csrc/lba_launch.h declares these: the solve and the taps call them, no kernel is launched from another unit)
 static unsigned blocks(size_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
-static void enqueue_points(const LaunchCtx &C, const Prog &P, int solve)
+void enqueue_prepare(const LaunchCtx &C, const Prog &P)
+{
+    hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, C.s->debug_stop_at_poll);
+}
+void enqueue_points(const LaunchCtx &C, const Prog &P, int solve)
 {
     if (C.walk)
         hipLaunchKernelGGL(k_points_walk, dim3((unsigned)P.n_pts), dim3(128), (size_t)P.D.walk_lds, P.q, P.wins, P.pts, solve);
     else
         hipLaunchKernelGGL(k_points, dim3((unsigned)P.n_pts), dim3(256), 0, P.q, P.wins, P.pts, solve);
 }
-static void enqueue_lin(const LaunchCtx &C, const Prog &P, int init)
+void enqueue_lin(const LaunchCtx &C, const Prog &P, int init)
 {
     if (!P.n_lin) return;
     if (C.walk)
@@ -2529,18 +1762,18 @@ static void enqueue_lin(const LaunchCtx &C, const Prog &P, int init)
     else
         hipLaunchKernelGGL(k_lin<false>, dim3((unsigned)P.n_lin), dim3(256), 0, P.q, P.wins, P.lin, init);
 }
-static void enqueue_init(const LaunchCtx &C, const Prog &P)
+void enqueue_init(const LaunchCtx &C, const Prog &P)
 {
     enqueue_points(C, P, 0);
     enqueue_lin(C, P, 1);
     hipLaunchKernelGGL(k_lm_init, dim3(P.nw), dim3(1024), 0, P.q, P.blk);
 }
-static void enqueue_schur(const Prog &P)
+void enqueue_schur(const Prog &P)
 {
     if (P.n_schur) hipLaunchKernelGGL(k_schur, dim3((unsigned)P.n_schur), dim3(kSchurThreads), 0, P.q, P.wins, P.schur);
 }
 // the pose half of a Levenberg-Marquardt trial: the Schur complement and the reduced system's solve with the pose update
-static void enqueue_reduced(LaunchCtx &C, const Prog &P, bool first_group)
+void enqueue_reduced(LaunchCtx &C, const Prog &P, bool first_group)
 {
     const GroupDims &D = P.D;
     enqueue_schur(P);
@@ -2562,154 +1795,24 @@ static void enqueue_reduced(LaunchCtx &C, const Prog &P, bool first_group)
     }
 }
 // one Levenberg-Marquardt trial: 4 launches (5 with reduced systems of both kinds)
-static void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
+void enqueue_trial(LaunchCtx &C, const Prog &P, bool first_group)
 {
     enqueue_reduced(C, P, first_group);
     enqueue_points(C, P, 1);   // + the LM decision in its last workgroup
     enqueue_lin(C, P, 0);
 }
-static void enqueue_transition(const Prog &P)
+void enqueue_transition(const Prog &P)
 {
     hipLaunchKernelGGL(k_transition, dim3(blocks(P.D.mx_E, 256), P.nw), dim3(256), 0, P.q, P.blk);
 }
-static void enqueue_final(const Prog &P)
+void enqueue_final(const Prog &P)
 {
     hipLaunchKernelGGL(k_final, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk);
 }
 
-// ---- the steps of aos2_lba_solve_batch
-
-// Validates the call and settles the windows whose stop flag is set on entry (Optimizer.cc:656-658: return before optimising when
-// the flag is already set; nothing is written back); `act` lists the others
-static int settle_entry(const aos2_lba *s, const aos2_lba_problem_t *problems, aos2_lba_result_t *results, int n_problems, std::vector<int> &act, bool &want_chi2)
-{
-    want_chi2 = false;
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        aos2_lba_result_t *r = results + w;
-        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id ||
-            !p->point_xyz || !p->point_id || !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo ||
-            !p->edge_inv_sigma2 || !r->pose_Tcw || !r->point_xyz) {
-            set_error("bad LocalBA problem %d", w);
-            return AOS2_ERR_ARG;
-        }
-        want_chi2 |= r->edge_chi2 != nullptr;   // (the edges' vertex indices are checked with the structure build, a thread per window)
-    }
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        aos2_lba_result_t *r = results + w;
-        r->iters_done_first = r->iters_done_second = 0;
-        r->trials_first = r->trials_second = 0;
-        r->final_chi2 = r->final_lambda = 0;
-        r->ms_device = 0;
-        r->polls = 1;
-        r->stop_poll = 0;
-        r->status = AOS2_OK;
-        if (stop_requested(p) || s->debug_stop_at_poll == 1) {
-            memcpy(r->pose_Tcw, p->pose_Tcw, sizeof(float) * 16 * p->n_poses);
-            memcpy(r->point_xyz, p->point_xyz, sizeof(float) * 3 * p->n_points);
-            if (r->edge_outlier) memset(r->edge_outlier, 0, p->n_edges);
-            r->status = AOS2_ERR_STOPPED;
-            r->stop_poll = 1;
-        } else
-            act.push_back(w);
-    }
-    return AOS2_OK;
-}
-
-// Window groups.  A trial is three wide launches (Schur, back-substitution, linearisation: every window's landmarks) and one
-// narrow one (the reduced systems: ONE workgroup per window, the longest launch of the mixed batch, during which most of the device
-// idles).  A batch of many windows runs as TWO groups with the same program each, on their own streams, the second started
-// behind the first group's first Schur launch: one group's reduced systems are factorised while the other group's landmark
-// kernels fill the device.  Windows are dealt to the groups by size (edges), largest first, so both get the same mix; the
-// windows of a group are neighbours in the descriptor array.  (aos2_lba_set_window_groups overrides.)
-// Returns the number of groups; group g is act[goff[g] .. goff[g + 1]), `act` reordered accordingly.
-static int deal_groups(const aos2_lba *s, const aos2_lba_problem_t *problems, std::vector<int> &act, int (&goff)[3])
-{
-    const int nw = (int)act.size();
-    int G = s->window_groups ? s->window_groups : nw >= 16 ? 2 : 1;
-    if (G > nw) G = 1;
-    goff[0] = 0;
-    goff[1] = goff[2] = nw;
-    if (G == 2) {
-        std::vector<int> order(act);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return problems[a].n_edges > problems[b].n_edges; });
-        std::vector<int> g0, g1;
-        for (size_t k = 0; k < order.size(); ++k) (((k & 3) == 0 || (k & 3) == 3) ? g0 : g1).push_back(order[k]);   // a b b a | a b b a ...
-        act = g0;
-        act.insert(act.end(), g1.begin(), g1.end());
-        goff[1] = (int)g0.size();
-    }
-    return G;
-}
-
-// The arena of a call: [staged regions of all windows | task lists of the groups | descriptors] (the part that is uploaded)
-// [continuation region][device-only regions of all windows][states and results of all windows] (the part that comes back)
-struct ArenaPlan {
-    std::vector<WinLayout> L;
-    size_t o_tasks, o_wins, staged_bytes, o_cont, cont_bytes, o_res, res_bytes, bytes;
-};
-static void plan_arena(const aos2_lba_problem_t *problems, const std::vector<int> &act, const std::vector<Pass> &passes, const LmLayout &lay, size_t n_all_tasks,
-                       bool want_chi2, ArenaPlan &A)
-{
-    const int nw = (int)act.size();
-    A.L.resize(nw);
-    Bump B;
-    for (int i = 0; i < nw; ++i) layout_staged(problems[act[i]], passes[i], B, A.L[i]);
-    A.o_tasks = B.take(sizeof(SchurTask) * n_all_tasks + 8);
-    A.o_wins = B.take(sizeof(LbaWin) * (size_t)nw);
-    A.staged_bytes = B.size;
-    // (a continuation round runs on the windows that are not finished, compacted: their descriptors and task lists go here)
-    // Sized for ANY subset of the windows, not for the first round's lists: a subset is dealt to the 8 queues anew (largest first; with
-    // queues of about equal length the padded list holds about sum + 8 x max units -- a first round of fewer than 8 windows per group
-    // is not padded at all, and the dealing is not monotone on subsets); the landmark / linearisation lists of a subset are parts of
-    // the full ones.  A subset whose padded list is longer still falls back to one unpadded queue (continuation_round), which always fits.
-    size_t cont_tasks = 0, cont_max_units = 0;
-    for (int i = 0; i < nw; ++i) {
-        const Pass &S = passes[i];
-        cont_max_units = std::max(cont_max_units, S.units.size());
-        cont_tasks += S.units.size() + (size_t)lay.points_blocks(S) + (size_t)lay.lin_blocks(S) + (size_t)S.np;
-    }
-    cont_tasks += 8 * cont_max_units;
-    A.cont_bytes = sizeof(LbaWin) * (size_t)nw + sizeof(SchurTask) * std::max(cont_tasks, n_all_tasks) + 64;
-    A.o_cont = B.take(A.cont_bytes);
-    for (int i = 0; i < nw; ++i) layout_scratch(problems[act[i]], passes[i], lay, B, A.L[i]);
-    A.o_res = B.take(0);
-    for (int i = 0; i < nw; ++i) layout_results(problems[act[i]], want_chi2, B, A.L[i]);
-    A.res_bytes = B.size - A.o_res;
-    A.bytes = B.size;
-}
-
-// Staging, a pool thread per window.  A window's staged region goes to the device as soon as it is assembled: its upload overlaps
-// the staging of the other windows (one copy of everything after the staging cost 0.4 ms more per 32-window call)
-static int stage_and_upload(aos2_lba *s, WindowPool &pool, const aos2_lba_problem_t *problems, const std::vector<int> &act, const std::vector<Pass> &passes,
-                            const ArenaPlan &A)
-{
-    const int nw = (int)act.size();
-    uint8_t *base = s->arena.p, *hin = s->h_in.p;
-    std::vector<uint8_t> up_fail(nw, 0);
-    pool.run(nw, [&](int i) {
-        stage_window(hin, A.L[i], problems[act[i]], passes[i]);
-        const size_t r0 = A.L[i].in_Tcw, r1 = i + 1 < nw ? A.L[i + 1].in_Tcw : A.o_tasks;
-        if (hipSetDevice(s->device) != hipSuccess || hipMemcpyAsync(base + r0, hin + r0, r1 - r0, hipMemcpyHostToDevice, s->stream) != hipSuccess)
-            up_fail[i] = 1;
-    });
-    for (int i = 0; i < nw; ++i)
-        if (up_fail[i]) {
-            set_error("LocalBA: upload of window %d failed", act[i]);
-            return AOS2_ERR_HIP;
-        }
-    return AOS2_OK;
-}
-
-static void enqueue_prepare(const LaunchCtx &C, const Prog &P)
-{
-    hipLaunchKernelGGL(k_prepare, dim3(blocks(std::max(P.D.mx_E, P.D.mx_pts), 256), P.nw), dim3(256), 0, P.q, P.blk, C.s->debug_stop_at_poll);
-}
-
 // The whole procedure of a group's windows: optimisation k gets slots[k] trials and runs if any window of the call asks for
 // iterations (iters[k] > 0)
-static void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const int (&iters)[2], const int (&slots)[2])
+void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const int (&iters)[2], const int (&slots)[2])
 {
     enqueue_prepare(C, P);
     for (int k = 0; k < 2; ++k) {
@@ -2721,745 +1824,4 @@ static void enqueue_program(LaunchCtx &C, const Prog &P, bool first_group, const
     }
 }
 
-// The host phase of a call up to the upload (aos2_lba_solve_batch and the assembly tap share it): the index structures of the windows
-// `act` (a pool thread per window), the task lists of the G groups, the arena, staging + upload, the descriptors
-struct Uploaded {
-    std::vector<Pass> *passes = nullptr;   // the handle's (LbaCache)
-    TaskLists TL[2];
-    ArenaPlan A;
-    LbaWin *hw = nullptr;                  // the host's copy of the descriptors
-    GroupDims gd[2];
-    DevTasks dt[2];
-    int max_i1 = 0, max_i2 = 0;
-    bool any_flag = false;
-};
-static int build_and_upload(aos2_lba *s, const aos2_lba_problem_t *problems, const std::vector<int> &act, const int (&goff)[3], int G, const LmLayout &lay,
-                            bool want_chi2, Uploaded &U)
-{
-    const int nw = (int)act.size();
-    int st;
-    // ---- per-window structure (host; windows in parallel when there are several), the groups' task lists
-    auto rg = std::make_unique<RoctxRange>("LocalBA::buildStructure (index mapping, edge lists, Schur items)");
-    if (!s->lba_cache) s->lba_cache = new LbaCache();
-    std::vector<Pass> &passes = static_cast<LbaCache *>(s->lba_cache)->passes;
-    U.passes = &passes;
-    if ((int)passes.size() < nw) passes.resize(nw);
-    WindowPool &pool = static_cast<LbaCache *>(s->lba_cache)->pool;
-    if (nw > 1) pool.start(lba_host_threads(s, nw));
-    if ((st = build_structures(pool, problems, act.data(), nw, passes))) return st;
-    rg = std::make_unique<RoctxRange>("LocalBA::stage + upload");
-    TaskLists(&TL)[2] = U.TL;
-    size_t n_all_tasks = 0;
-    for (int g = 0; g < G; ++g) {
-        std::vector<int> ids(goff[g + 1] - goff[g]);
-        std::iota(ids.begin(), ids.end(), goff[g]);
-        build_tasks(passes, ids, false, lay, TL[g]);   // (the groups' kernels index the whole descriptor array)
-        n_all_tasks += TL[g].size();
-    }
-
-    // ---- arena: layout, allocation, staging + upload (parallel), descriptors
-    ArenaPlan &A = U.A;
-    plan_arena(problems, act, passes, lay, n_all_tasks, want_chi2, A);
-    if ((st = s->arena.alloc(A.bytes + 256))) return st;
-    if ((st = s->h_in.alloc(A.o_cont + A.cont_bytes + 256))) return st;
-    if ((st = s->h_stage.alloc(A.res_bytes + 256))) return st;
-    if ((st = s->h_abort.alloc((size_t)nw + 1))) return st;
-    uint8_t *base = s->arena.p, *hin = s->h_in.p;
-    int32_t *d_abort = nullptr;
-    AOS2_HIP_CHECK(hipHostGetDevicePointer((void **)&d_abort, s->h_abort.p, 0));
-    bool &any_flag = U.any_flag;
-    any_flag = false;
-    for (int i = 0; i < nw; ++i) {
-        s->h_abort.p[i] = 0;
-        any_flag |= problems[act[i]].stop_flag != nullptr;
-    }
-    if ((st = stage_and_upload(s, pool, problems, act, passes, A))) return st;
-    LbaWin *hw = U.hw = reinterpret_cast<LbaWin *>(hin + A.o_wins);
-    GroupDims(&gd)[2] = U.gd;
-    int &max_i1 = U.max_i1, &max_i2 = U.max_i2;
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t &p = problems[act[i]];
-        describe_window(hw[i], base, p, passes[i], A.L[i], d_abort + i, want_chi2);
-        gd[i >= goff[1] ? 1 : 0].add(p, passes[i], A.L[i]);
-        max_i1 = std::max(max_i1, p.iters_first);
-        max_i2 = std::max(max_i2, p.iters_second);
-    }
-    hipStream_t q = s->stream;
-    // the task lists of the groups, one after the other: [schur | points | lin] per group
-    DevTasks(&dt)[2] = U.dt;
-    {
-        size_t o = A.o_tasks;
-        for (int g = 0; g < G; ++g) dt[g] = put_tasks(TL[g], hin, base, o);
-    }
-    AOS2_HIP_CHECK(hipMemcpyAsync(base + A.o_tasks, hin + A.o_tasks, A.staged_bytes - A.o_tasks, hipMemcpyHostToDevice, q));   // the task lists, the descriptors
-    AOS2_HIP_CHECK(hipEventRecord(s->ev[0], q));
-    if (G == 2) {   // the second group's stream starts behind the upload
-        AOS2_HIP_CHECK(hipEventRecord(s->ev_up, q));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(s->stream_b, s->ev_up, 0));
-    }
-    return AOS2_OK;
-}
-
-// what the steps after the upload work on
-struct Batch {
-    const aos2_lba_problem_t *problems;
-    const std::vector<int> &act;        // the windows that run, in descriptor order
-    const std::vector<Pass> &passes;    // their structures ...
-    const ArenaPlan &A;                 // ... and regions
-    LmLayout lay;
-    const LbaWin *hw;                   // the host's copy of their descriptors
-    bool any_flag;                      // a window has a stop flag: forwarded to the abort words while the device runs
-    const LmState *state_of(const aos2_lba *s, int i) const { return reinterpret_cast<const LmState *>(s->h_stage.p + (A.L[i].st - A.o_res)); }
-};
-
-// Ends the programs with the final check; the results (and states) come back as one copy; the host forwards pbStopFlag into the
-// mapped abort words meanwhile
-static int finish(aos2_lba *s, const Prog *progs, int n_progs, const Batch &Bt)
-{
-    hipStream_t q = s->stream;
-    for (int g = 0; g < n_progs; ++g) enqueue_final(progs[g]);
-    if (n_progs == 2) {
-        AOS2_HIP_CHECK(hipEventRecord(s->ev_done_b, s->stream_b));
-        AOS2_HIP_CHECK(hipStreamWaitEvent(q, s->ev_done_b, 0));
-    }
-    AOS2_HIP_CHECK(hipEventRecord(s->ev[1], q));
-    AOS2_HIP_CHECK(hipMemcpyAsync(s->h_stage.p, s->arena.p + Bt.A.o_res, Bt.A.res_bytes, hipMemcpyDeviceToHost, q));
-    if (Bt.any_flag) {
-        AOS2_HIP_CHECK(hipEventRecord(s->ev[2], q));
-        while (hipEventQuery(s->ev[2]) == hipErrorNotReady)
-            for (size_t i = 0; i < Bt.act.size(); ++i)
-                if (stop_requested(Bt.problems + Bt.act[i])) __atomic_store_n(&s->h_abort.p[i], 1, __ATOMIC_RELAXED);
-    }
-    AOS2_HIP_CHECK(hipStreamSynchronize(q));
-    AOS2_HIP_CHECK(hipGetLastError());
-    return AOS2_OK;
-}
-
-// One continuation round: the windows that are not finished when a program has run (steps rejected by the gain ratio) get another,
-// sized for what they still need at most if no further step is rejected, compacted: their descriptors and task lists, which address
-// them by position, go to the continuation region.  *done: there was no such window.
-static int continuation_round(LaunchCtx &C, const Batch &Bt, int max_i2, int round, bool *done)
-{
-    aos2_lba *s = C.s;
-    const ArenaPlan &A = Bt.A;
-    std::vector<int> todo;
-    int need1 = 0, need2 = 0;
-    bool before_second = false;
-    for (int i = 0; i < (int)Bt.act.size(); ++i) {
-        const LmState *ls = Bt.state_of(s, i);
-        if (ls->phase == 3) continue;
-        todo.push_back(i);
-        if (ls->phase == 0) need1 = std::max(need1, std::max(1, ls->iters_max[0] - ls->it));
-        if (ls->phase <= 1) before_second = true;
-        if (ls->phase == 2) need2 = std::max(need2, std::max(1, ls->iters_max[1] - ls->it));
-    }
-    *done = todo.empty();
-    if (*done) return AOS2_OK;
-    if (round > 64) {   // 2 x 10 iterations x 10 trials at most: cannot happen
-        set_error("internal: LocalBA program did not finish");
-        return AOS2_ERR_ARG;
-    }
-    if (before_second) need2 = std::max(need2, max_i2);
-    TaskLists TC;
-    build_tasks(Bt.passes, todo, true, Bt.lay, TC);
-    static const bool force_one_queue = getenv("AOS2_LBA_CONT_ONE_QUEUE") != nullptr;   // (test hook: the fallback below on every continuation)
-    // (the dealing is not monotone on subsets: should one pad past the bound, one unpadded queue always fits -- its length is the subset's sum)
-    if (force_one_queue || sizeof(LbaWin) * todo.size() + sizeof(SchurTask) * TC.size() > A.cont_bytes) build_tasks(Bt.passes, todo, true, Bt.lay, TC, true);
-    if (sizeof(LbaWin) * todo.size() + sizeof(SchurTask) * TC.size() > A.cont_bytes) {
-        set_error("internal: continuation region");
-        return AOS2_ERR_ARG;
-    }
-    uint8_t *hc = s->h_in.p + A.o_cont;
-    const uint8_t *dc = s->arena.p + A.o_cont;
-    GroupDims D;
-    for (size_t k = 0; k < todo.size(); ++k) {
-        const int i = todo[k];
-        reinterpret_cast<LbaWin *>(hc)[k] = Bt.hw[i];
-        D.add(Bt.problems[Bt.act[i]], Bt.passes[i], A.L[i]);
-    }
-    size_t o = sizeof(LbaWin) * todo.size();
-    const DevTasks dt = put_tasks(TC, hc, dc, o);
-    AOS2_HIP_CHECK(hipMemcpyAsync(s->arena.p + A.o_cont, hc, o, hipMemcpyHostToDevice, s->stream));
-    const Prog PC = make_prog((const LbaWin *)dc, (const LbaWin *)dc, (int)todo.size(), TC, dt, D, group_streams(s, 0));
-    for (int t = 0; t < need1; ++t) enqueue_trial(C, PC, false);
-    if (before_second) {
-        enqueue_transition(PC);
-        enqueue_init(C, PC);
-    }
-    for (int t = 0; t < need2; ++t) enqueue_trial(C, PC, false);
-    s->last_trial_slots += need1 + need2;
-    s->last_window_slots += (long long)(need1 + need2) * (long long)todo.size();
-    s->last_host_rounds++;
-    return finish(s, &PC, 1, Bt);
-}
-
-static void write_back(const aos2_lba *s, const Batch &Bt, aos2_lba_result_t *results)
-{
-    const ArenaPlan &A = Bt.A;
-    const int nw = (int)Bt.act.size();
-    if (getenv("AOS2_LBA_TRACE"))
-        for (int i = 0; i < nw; ++i) {
-            const LmState *ls = Bt.state_of(s, i);
-            for (int t = 0; t < ls->ntr; ++t)
-                fprintf(stderr, "[lba] win %d trial %2d lambda %.6e chi %.9e -> %.9e rho %.6e\n", i, t, ls->tr_lambda[t], ls->tr_cur[t], ls->tr_temp[t], ls->tr_rho[t]);
-        }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t *p = Bt.problems + Bt.act[i];
-        aos2_lba_result_t *r = results + Bt.act[i];
-        const WinLayout &l = A.L[i];
-        const uint8_t *hb = s->h_stage.p;
-        const LmState *ls = Bt.state_of(s, i);
-        memcpy(r->pose_Tcw, hb + (l.out_Tcw - A.o_res), 64 * (size_t)p->n_poses);
-        memcpy(r->point_xyz, hb + (l.out_xyz - A.o_res), 12 * (size_t)p->n_points);
-        if (r->edge_outlier) memcpy(r->edge_outlier, hb + (l.out_outlier - A.o_res), (size_t)p->n_edges);
-        if (r->edge_chi2) memcpy(r->edge_chi2, hb + (l.out_chi2 - A.o_res), 8 * (size_t)p->n_edges);
-        r->iters_done_first = ls->iters_done[0];
-        r->iters_done_second = ls->iters_done[1];
-        r->trials_first = ls->trials[0];
-        r->trials_second = ls->trials[1];
-        r->final_chi2 = ls->final_chi2;
-        r->final_lambda = ls->final_lambda;
-        r->polls = ls->polls;
-        r->stop_poll = ls->stop_poll;
-        r->ms_device = ms;
-    }
-}
-
 }  // namespace aos2
-
-using namespace aos2;
-
-extern "C" {
-
-int aos2_lba_create(int device, aos2_lba_t **out)
-{
-    if (!out) return AOS2_ERR_ARG;
-    aos2_lba *s = new aos2_lba();
-    s->device = device;
-    *out = s;
-    return AOS2_OK;
-}
-
-void aos2_lba_destroy(aos2_lba_t *s)
-{
-    if (!s) return;
-    delete static_cast<LbaCache *>(s->lba_cache);
-    if (s->dev_ready) {
-        (void)hipSetDevice(s->device);
-        (void)hipStreamSynchronize(s->stream);
-        s->arena.release();
-        s->h_stage.release();
-        s->h_in.release();
-        s->h_abort.release();
-        for (auto &e : s->ev) (void)hipEventDestroy(e);
-        (void)hipEventDestroy(s->ev_fork);
-        (void)hipEventDestroy(s->ev_join);
-        if (s->stream_b) {
-            for (hipEvent_t e : {s->ev_fork_b, s->ev_join_b, s->ev_up, s->ev_stag, s->ev_done_b}) (void)hipEventDestroy(e);
-            (void)hipStreamSynchronize(s->stream_b);
-            (void)hipStreamDestroy(s->stream2_b);
-            (void)hipStreamDestroy(s->stream_b);
-        }
-        (void)hipStreamDestroy(s->stream2);
-        (void)hipStreamDestroy(s->stream);
-    }
-    delete s;
-}
-
-int aos2_lba_set_host_threads(aos2_lba_t *s, int n)
-{
-    if (!s || n < 0) {
-        set_error("aos2_lba_set_host_threads: bad argument");
-        return AOS2_ERR_ARG;
-    }
-    s->host_threads = n;
-    return AOS2_OK;
-}
-
-int aos2_lba_set_window_groups(aos2_lba_t *s, int n)
-{
-    if (!s || n < 0 || n > 2) {
-        set_error("aos2_lba_set_window_groups: 0 (default), 1 or 2");
-        return AOS2_ERR_ARG;
-    }
-    s->window_groups = n;
-    return AOS2_OK;
-}
-
-int aos2_lba_last_program(const aos2_lba_t *s, int32_t *trial_slots, int32_t *host_rounds)
-{
-    if (!s) {
-        set_error("aos2_lba_last_program: no handle");
-        return AOS2_ERR_ARG;
-    }
-    if (trial_slots) *trial_slots = s->last_trial_slots;
-    if (host_rounds) *host_rounds = s->last_host_rounds;
-    return AOS2_OK;
-}
-
-// The host part of aos2_lba_solve_batch without a device: the per-window index structures (build_pass, Schur items and units)
-// and the staging copies (into pageable memory here), on `threads` worker threads.  For measuring / testing how the host phases of
-// several ranks share a node's cores (tests/test_sharding_cpu.py); returns the wall time of the two phases.
-int aos2_lba_debug_host_phase(const aos2_lba_problem_t *problems, int n_problems, int threads, double *build_ms, double *stage_ms)
-{
-    if (!problems || n_problems <= 0 || threads <= 0) {
-        set_error("aos2_lba_debug_host_phase: bad argument");
-        return AOS2_ERR_ARG;
-    }
-    std::vector<Pass> passes(n_problems);
-    WindowPool pool;
-    if (n_problems > 1 && threads > 1) pool.start(std::min(threads, n_problems));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = build_structures(pool, problems, nullptr, n_problems, passes)) return st;
-    const auto t1 = std::chrono::steady_clock::now();
-    std::vector<std::vector<uint8_t>> stage(n_problems);
-    pool.run(n_problems, [&](int i) {
-        WinLayout l{};
-        Bump B;
-        layout_staged(problems[i], passes[i], B, l);
-        stage[i].resize(B.size);
-        stage_window(stage[i].data(), l, problems[i], passes[i]);
-    });
-    const auto t2 = std::chrono::steady_clock::now();
-    if (build_ms) *build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (stage_ms) *stage_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return AOS2_OK;
-}
-
-int aos2_lba_last_window_slots(const aos2_lba_t *s, int64_t *window_slots)
-{
-    if (!s || !window_slots) {
-        set_error("aos2_lba_last_window_slots: bad argument");
-        return AOS2_ERR_ARG;
-    }
-    *window_slots = s->last_window_slots;
-    return AOS2_OK;
-}
-
-int aos2_lba_debug_stop_at_poll(aos2_lba_t *s, int poll)
-{
-    if (!s || poll < 0) return AOS2_ERR_ARG;
-    s->debug_stop_at_poll = poll;
-    return AOS2_OK;
-}
-
-int aos2_lba_solve_batch(aos2_lba_t *s, const aos2_lba_problem_t *problems, aos2_lba_result_t *results, int n_problems)
-{
-    if (!s || !problems || !results || n_problems <= 0) {
-        set_error("bad LocalBA batch");
-        return AOS2_ERR_ARG;
-    }
-    // ---- the windows that run, dealt to one or two groups
-    std::vector<int> act;
-    bool want_chi2;
-    int st = settle_entry(s, problems, results, n_problems, act, want_chi2);
-    if (st) return st;
-    const int nw = (int)act.size();
-    if (nw == 0) return AOS2_OK;
-    if ((st = lba_handle_init(s))) return st;
-    int goff[3];
-    const int G = deal_groups(s, problems, act, goff);
-    if (G == 2 && (st = lba_group_streams(s))) return st;
-    // layout of the landmark kernels: kLmSlots threads per landmark while the landmarks of the call cannot fill the device
-    // (one or a few windows: latency), one thread per landmark beyond (throughput); same results either way.
-    // AOS2_LBA_LAYOUT=slots|walk forces one (tests).
-    size_t total_points = 0;
-    for (int i = 0; i < nw; ++i) total_points += (size_t)problems[act[i]].n_points;
-    bool walk = total_points > 16000;
-    if (const char *e = getenv("AOS2_LBA_LAYOUT")) walk = !strcmp(e, "walk");
-    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
-
-    // ---- per-window structure, task lists, arena, staging + upload, descriptors
-    Uploaded U;
-    if ((st = build_and_upload(s, problems, act, goff, G, lay, want_chi2, U))) return st;
-    const std::vector<Pass> &passes = *U.passes;
-    const ArenaPlan &A = U.A;
-    const int max_i1 = U.max_i1, max_i2 = U.max_i2;
-    uint8_t *base = s->arena.p;
-
-    // ---- the program
-    auto rg = std::make_unique<RoctxRange>("LocalBA::optimize(5) + outlier pass + optimize(10) + inlier check (one device program)");
-    // As many trials as iterations per optimisation -- what every window needs whose steps are all accepted.  A window
-    // with rejected steps is not finished when the program ends: it leaves with the others' results and gets a continuation round
-    // sized for what it still needs, together with the (few) windows like it, compacted (continuation_round).  Rounds 2-4 enqueued one spare
-    // trial per optimisation for EVERY window instead (AOS2_LBA_SPARE_SLOTS=1): 13 % of the launches of a batch whose windows need none.
-    const int spare = getenv("AOS2_LBA_SPARE_SLOTS") ? atoi(getenv("AOS2_LBA_SPARE_SLOTS")) : 0;
-    const int iters[2] = {max_i1, max_i2}, slots[2] = {max_i1 > 0 ? max_i1 + spare : 0, max_i2 > 0 ? max_i2 + spare : 0};
-    s->last_trial_slots = slots[0] + slots[1];
-    s->last_window_slots = (long long)(slots[0] + slots[1]) * nw;
-    s->last_host_rounds = 1;
-    const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
-    LaunchCtx C{s, walk, G == 2};
-    Prog PG[2];
-    for (int g = 0; g < G; ++g) {
-        PG[g] = make_prog(dw, dw + goff[g], goff[g + 1] - goff[g], U.TL[g], U.dt[g], U.gd[g], group_streams(s, g));
-        enqueue_program(C, PG[g], g == 0, iters, slots);
-    }
-    const Batch Bt{problems, act, passes, A, lay, U.hw, U.any_flag};
-    if ((st = finish(s, PG, G, Bt))) return st;
-
-    // ---- continuation rounds, write-back
-    for (int round = 0;; ++round) {
-        bool done;
-        if ((st = continuation_round(C, Bt, max_i2, round, &done))) return st;
-        if (done) break;
-    }
-    rg = std::make_unique<RoctxRange>("LocalBA::write-back");
-    write_back(s, Bt, results);
-    return AOS2_OK;
-}
-
-int aos2_lba_solve(aos2_lba_t *s, const aos2_lba_problem_t *p, aos2_lba_result_t *r)
-{
-    if (!s || !p || !r) {
-        set_error("bad LocalBA problem");
-        return AOS2_ERR_ARG;
-    }
-    const int st = aos2_lba_solve_batch(s, p, r, 1);
-    return st ? st : r->status;
-}
-
-// Test tap: k_ldlt_reg / k_ldlt_dev alone.  One hand-made window descriptor and state per case -- only the members the two kernels read --
-// over a padded matrix filled like k_schur and k_prepare leave it; launched through enqueue_ldlt like a trial's.
-int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const int32_t *form, const double *H, const double *bs, const double *b_pose,
-                                        const double *lambda, const double *T, double *x, double *T_out, double *T_backup, double *scale_terms,
-                                        uint8_t *ok, int device)
-{
-    if (n_cases < 1 || !np || !form || !H || !bs || !b_pose || !lambda || !T || !x || !T_out || !T_backup || !scale_terms || !ok) {
-        set_error("aos2_debug_lba_reduced_solve_device: bad argument");
-        return AOS2_ERR_ARG;
-    }
-    for (int c = 0; c < n_cases; ++c) {
-        if (form[c] != kLdltDev && form[c] != kLdltReg) {
-            set_error("aos2_debug_lba_reduced_solve_device: case %d: form %d (0 = k_ldlt_dev, 2 = k_ldlt_reg)", c, form[c]);
-            return AOS2_ERR_ARG;
-        }
-        if (np[c] < 1 || np[c] > (form[c] == kLdltReg ? 16 * kLrMaxNb / 6 : kLdMaxNp)) {
-            set_error("aos2_debug_lba_reduced_solve_device: case %d: %d free keyframes, form %d takes 1..%d", c, np[c], form[c],
-                      form[c] == kLdltReg ? 16 * kLrMaxNb / 6 : kLdMaxNp);
-            return AOS2_ERR_ARG;
-        }
-    }
-    int st = bind_device(device);
-    if (st) return st;
-    if ((st = ldlt_declare_lds())) return st;
-    // regions of a case in one buffer (offsets in bytes)
-    struct CaseLayout {
-        size_t Hs, bs, b, x, tmp, scal, pose, bk, hpose, st;
-        int n, npad;
-    };
-    std::vector<CaseLayout> L(n_cases);
-    Bump B;
-    const size_t o_wins = B.take(sizeof(LbaWin) * (size_t)n_cases);
-    int mx_npad[2] = {0, 0};   // register form, device-memory form
-    for (int c = 0; c < n_cases; ++c) {
-        CaseLayout &l = L[c];
-        l.n = 6 * np[c];
-        l.npad = (l.n + 15) & ~15;
-        int &mx = mx_npad[form[c] == kLdltReg ? 0 : 1];
-        mx = std::max(mx, l.npad);
-        const size_t n8 = 8 * (size_t)l.n, p56 = 56 * (size_t)np[c];
-        l.Hs = B.take(8 * (size_t)l.npad * l.npad); l.bs = B.take(n8); l.b = B.take(n8); l.x = B.take(n8); l.tmp = B.take(n8);
-        l.scal = B.take(64); l.pose = B.take(p56); l.bk = B.take(p56); l.hpose = B.take(4 * (size_t)np[c]); l.st = B.take(sizeof(LmState));
-    }
-    std::vector<uint8_t> host(B.size, 0);
-    DevBuf<uint8_t> dev;
-    if ((st = dev.alloc(B.size))) return st;
-    size_t oH = 0, ov = 0, oT = 0;   // the case's place in the caller's arrays (doubles)
-    for (int c = 0; c < n_cases; ++c) {
-        const CaseLayout &l = L[c];
-        const int n = l.n, npad = l.npad;
-        double *Hs = (double *)(host.data() + l.Hs);
-        for (int r = 0; r < npad; ++r)
-            for (int q = 0; q < npad; ++q) Hs[(size_t)r * npad + q] = r < n && q < n ? H[oH + (size_t)r * n + q] : r == q ? 1.0 : 0.0;
-        memcpy(host.data() + l.bs, bs + ov, 8 * (size_t)n);
-        memcpy(host.data() + l.b, b_pose + ov, 8 * (size_t)n);
-        memcpy(host.data() + l.x, x + ov, 8 * (size_t)n);
-        memcpy(host.data() + l.tmp, scale_terms + ov, 8 * (size_t)n);
-        ((double *)(host.data() + l.scal))[3] = -1.0;   // (neither kernel ran: ok = 255)
-        memcpy(host.data() + l.pose, T + oT, 56 * (size_t)np[c]);
-        memset(host.data() + l.bk, 0xFF, 56 * (size_t)np[c]);   // (NaNs: the backup is the kernel's)
-        for (int i = 0; i < np[c]; ++i) ((int32_t *)(host.data() + l.hpose))[i] = i;
-        LmState *S = (LmState *)(host.data() + l.st);
-        S->run = 1;
-        S->lambda = lambda[c];
-        LbaWin &W = ((LbaWin *)(host.data() + o_wins))[c];
-        W.np = np[c]; W.npad = npad; W.hs_ld = npad; W.ldlt_form = (LdltForm)form[c];
-        W.Hs = (double *)(dev.p + l.Hs); W.bs = (double *)(dev.p + l.bs); W.b = (double *)(dev.p + l.b); W.x = (double *)(dev.p + l.x);
-        W.tmp = (double *)(dev.p + l.tmp); W.scal = (double *)(dev.p + l.scal);
-        W.pose = (double *)(dev.p + l.pose); W.bk = (double *)(dev.p + l.bk); W.n_poses = np[c];
-        W.hpose = (const int32_t *)(dev.p + l.hpose);
-        W.st = (LmState *)(dev.p + l.st);
-        oH += (size_t)n * n; ov += n; oT += 7 * (size_t)np[c];
-    }
-    st = [&]() -> int {
-        AOS2_HIP_CHECK(hipMemcpy(dev.p, host.data(), B.size, hipMemcpyHostToDevice));
-        enqueue_ldlt((const LbaWin *)(dev.p + o_wins), n_cases, mx_npad[0], mx_npad[1], 0, 0);
-        AOS2_HIP_CHECK(hipGetLastError());
-        AOS2_HIP_CHECK(hipDeviceSynchronize());
-        AOS2_HIP_CHECK(hipMemcpy(host.data(), dev.p, B.size, hipMemcpyDeviceToHost));
-        return AOS2_OK;
-    }();
-    dev.release();
-    if (st) return st;
-    ov = oT = 0;
-    for (int c = 0; c < n_cases; ++c) {
-        const CaseLayout &l = L[c];
-        memcpy(x + ov, host.data() + l.x, 8 * (size_t)l.n);
-        memcpy(scale_terms + ov, host.data() + l.tmp, 8 * (size_t)l.n);
-        memcpy(T_out + oT, host.data() + l.pose, 56 * (size_t)np[c]);
-        memcpy(T_backup + oT, host.data() + l.bk, 56 * (size_t)np[c]);
-        const double s3 = ((const double *)(host.data() + l.scal))[3];
-        ok[c] = s3 == 1.0 ? 1 : s3 == 0.0 ? 0 : 255;
-        ov += l.n; oT += 7 * (size_t)np[c];
-    }
-    return AOS2_OK;
-}
-
-// Test tap: the system a Levenberg-Marquardt trial solves, as the shipped kernels assemble it.  The host phase is aos2_lba_solve_batch's
-// (build_and_upload), the launches go through its helpers; one group, the landmark layout as the caller says.
-int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int stage, const double *lambda,
-                                   aos2_lba_system_t *out)
-{
-    if (!s || !problems || !out || n_problems < 1 || (layout != 0 && layout != 1) || (stage != 0 && stage != 1)) {
-        set_error("aos2_debug_lba_assemble_device: bad argument (layout 0 = slots, 1 = walk; stage 0 or 1)");
-        return AOS2_ERR_ARG;
-    }
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        const aos2_lba_system_t *o = out + w;
-        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id || !p->point_xyz || !p->point_id ||
-            !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo || !p->edge_inv_sigma2 || p->iters_first < 1 ||
-            (stage == 1 && p->iters_second < 1) || !o->hpose || !o->hpoint || !o->pose || !o->point || !o->e_level1 || !o->e_robust || !o->Hpp_init ||
-            !o->b_init || !o->b_p || !o->Hll || !o->b_l || !o->Hs || !o->bs || !o->blk_off || !o->units) {
-            set_error("aos2_debug_lba_assemble_device: bad problem or output %d", w);
-            return AOS2_ERR_ARG;
-        }
-    }
-    int st;
-    {   // what the host phase refuses, before a device is looked for
-        std::vector<Pass> probe(n_problems);
-        WindowPool serial;
-        if ((st = build_structures(serial, problems, nullptr, n_problems, probe))) return st;
-        for (int w = 0; w < n_problems; ++w)
-            if (probe[w].np < 1) {
-                set_error("aos2_debug_lba_assemble_device: problem %d has no free keyframe with an edge", w);
-                return AOS2_ERR_ARG;
-            }
-    }
-    if ((st = lba_handle_init(s))) return st;
-    const int nw = n_problems;
-    std::vector<int> act(nw);
-    std::iota(act.begin(), act.end(), 0);
-    const int goff[3] = {0, nw, nw};
-    const bool walk = layout == 1;
-    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
-    Uploaded U;
-    if ((st = build_and_upload(s, problems, act, goff, 1, lay, false, U))) return st;
-    const std::vector<Pass> &passes = *U.passes;
-    const ArenaPlan &A = U.A;
-    uint8_t *base = s->arena.p;
-    // Hpp and the pose part of b as the first linearisation left them, copied aside between k_lm_init and k_schur
-    std::vector<size_t> o_snap(nw);
-    Bump SB;
-    for (int i = 0; i < nw; ++i) o_snap[i] = SB.take(8 * 42 * (size_t)passes[i].np);
-    DevBuf<uint8_t> snap;
-    if ((st = snap.alloc(SB.size))) return st;
-    std::vector<uint8_t> host(A.bytes), hsnap(SB.size);
-    st = [&]() -> int {
-        const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
-        LaunchCtx C{s, walk, false};
-        const Prog P = make_prog(dw, dw, nw, U.TL[0], U.dt[0], U.gd[0], group_streams(s, 0));
-        enqueue_prepare(C, P);
-        if (stage == 1) {
-            enqueue_init(C, P);
-            for (int t = 0; t < U.max_i1; ++t) enqueue_trial(C, P, true);
-            enqueue_transition(P);
-        }
-        enqueue_init(C, P);
-        for (int i = 0; i < nw; ++i) {
-            const size_t n36 = 8 * 36 * (size_t)passes[i].np, n6 = 8 * 6 * (size_t)passes[i].np;
-            if (lambda && lambda[i] > 0) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].st + offsetof(LmState, lambda), lambda + i, 8, hipMemcpyHostToDevice, P.q));
-            AOS2_HIP_CHECK(hipMemcpyAsync(snap.p + o_snap[i], base + A.L[i].Hpp, n36, hipMemcpyDeviceToDevice, P.q));
-            AOS2_HIP_CHECK(hipMemcpyAsync(snap.p + o_snap[i] + n36, base + A.L[i].b, n6, hipMemcpyDeviceToDevice, P.q));
-        }
-        enqueue_schur(P);
-        AOS2_HIP_CHECK(hipGetLastError());
-        AOS2_HIP_CHECK(hipStreamSynchronize(P.q));
-        AOS2_HIP_CHECK(hipMemcpy(host.data(), base, A.bytes, hipMemcpyDeviceToHost));
-        AOS2_HIP_CHECK(hipMemcpy(hsnap.data(), snap.p, SB.size, hipMemcpyDeviceToHost));
-        return AOS2_OK;
-    }();
-    snap.release();
-    if (st) return st;
-    for (int i = 0; i < nw; ++i) {
-        const aos2_lba_problem_t &p = problems[i];
-        const Pass &S = passes[i];
-        const WinLayout &l = A.L[i];
-        aos2_lba_system_t &o = out[i];
-        const uint8_t *h = host.data();
-        const LmState *ls = (const LmState *)(h + l.st);
-        const size_t np = S.np, nl = S.nl, npad = l.npad;
-        o.np = S.np; o.nl = S.nl; o.npad = l.npad;
-        o.phase = ls->phase; o.trials_first = ls->trials[0]; o.iters_done_first = ls->iters_done[0];
-        o.lambda = ls->lambda; o.current_chi = ls->currentChi;
-        memcpy(o.hpose, S.hpose.data(), 4 * np);
-        memcpy(o.hpoint, S.hpoint.data(), 4 * nl);
-        memcpy(o.blk_off, S.blk_off.data(), 4 * (np * (np + 1) / 2 + 1));
-        o.n_units = (int32_t)S.units.size();
-        memcpy(o.units, S.units.data(), 4 * S.units.size());
-        memcpy(o.pose, h + l.est, 8 * 7 * (size_t)p.n_poses);
-        memcpy(o.point, h + l.est + 8 * 7 * (size_t)p.n_poses, 8 * 3 * (size_t)p.n_points);
-        memcpy(o.e_level1, h + l.level1, (size_t)p.n_edges);
-        memcpy(o.e_robust, h + l.robust, (size_t)p.n_edges);
-        memcpy(o.Hpp_init, hsnap.data() + o_snap[i], 8 * 36 * np);
-        memcpy(o.b_init, hsnap.data() + o_snap[i] + 8 * 36 * np, 8 * 6 * np);
-        memcpy(o.b_p, h + l.b, 8 * 6 * np);
-        memcpy(o.Hll, h + l.Hll, 8 * 9 * nl);
-        memcpy(o.b_l, h + l.b + 8 * 6 * np, 8 * 3 * nl);
-        memcpy(o.Hs, h + l.Hs, 8 * npad * npad);
-        memcpy(o.bs, h + l.bs, 8 * 6 * np);
-    }
-    return AOS2_OK;
-}
-
-// Test tap: the landmark half of a trial and the LM decision, the outlier pass and the final check, read between the shipped launches.
-// Host phase and helpers as the assembly tap; a snapshot is a synchronisation and a copy of the arena (the windows are small).
-int aos2_debug_lba_trial_device(aos2_lba_t *s, const aos2_lba_problem_t *problems, int n_problems, int layout, int trials_before, const double *lambda,
-                                const uint8_t *force_solver_failed, int tail, aos2_lba_trial_t *out)
-{
-    if (!s || !problems || !out || n_problems < 1 || (layout != 0 && layout != 1) || trials_before < 0 || tail < 0 || tail > 2) {
-        set_error("aos2_debug_lba_trial_device: bad argument (layout 0 = slots, 1 = walk; trials_before >= 0; tail 0, 1 or 2)");
-        return AOS2_ERR_ARG;
-    }
-    for (int w = 0; w < n_problems; ++w) {
-        const aos2_lba_problem_t *p = problems + w;
-        const aos2_lba_trial_t *o = out + w;
-        if (p->n_poses <= 0 || p->n_points <= 0 || p->n_edges <= 0 || !p->pose_Tcw || !p->pose_fixed || !p->pose_id || !p->point_xyz || !p->point_id ||
-            !p->edge_pose || !p->edge_point || !p->edge_obs || !p->edge_stereo || !p->edge_inv_sigma2 || p->iters_first < 1 || !o->hpose || !o->hpoint ||
-            !o->pt_off || !o->pt_k || !o->pl_pos) {
-            set_error("aos2_debug_lba_trial_device: bad problem or output %d", w);
-            return AOS2_ERR_ARG;
-        }
-    }
-    int st;
-    {   // what the host phase refuses, before a device is looked for
-        std::vector<Pass> probe(n_problems);
-        WindowPool serial;
-        if ((st = build_structures(serial, problems, nullptr, n_problems, probe))) return st;
-        for (int w = 0; w < n_problems; ++w)
-            if (probe[w].np < 1) {
-                set_error("aos2_debug_lba_trial_device: problem %d has no free keyframe with an edge", w);
-                return AOS2_ERR_ARG;
-            }
-    }
-    if ((st = lba_handle_init(s))) return st;
-    const int nw = n_problems;
-    std::vector<int> act(nw);
-    std::iota(act.begin(), act.end(), 0);
-    const int goff[3] = {0, nw, nw};
-    const bool walk = layout == 1;
-    const LmLayout lay{walk, walk ? 128 : kLmBlock, walk ? 256 : kLmBlock};
-    Uploaded U;
-    if ((st = build_and_upload(s, problems, act, goff, 1, lay, true, U))) return st;
-    const std::vector<Pass> &passes = *U.passes;
-    const ArenaPlan &A = U.A;
-    uint8_t *base = s->arena.p;
-    std::vector<uint8_t> host(A.bytes);
-    for (int i = 0; i < nw; ++i) {
-        const Pass &S = passes[i];
-        aos2_lba_trial_t &o = out[i];
-        o.np = S.np; o.nl = S.nl; o.n_pl = (int32_t)S.pl_k.size(); o.n_part = A.L[i].n_part;
-        memcpy(o.hpose, S.hpose.data(), 4 * (size_t)S.np);
-        memcpy(o.hpoint, S.hpoint.data(), 4 * (size_t)S.nl);
-        memcpy(o.pt_off, S.pt_off.data(), 4 * S.pt_off.size());
-        memcpy(o.pt_k, S.pt_k.data(), 4 * S.pt_k.size());
-        memcpy(o.pl_pos, S.pl_pos.data(), 4 * S.pl_pos.size());
-        for (auto &sn : o.snap) sn.taken = 0;
-    }
-    hipStream_t q = s->stream;
-    auto snapshot = [&](int k) -> int {
-        AOS2_HIP_CHECK(hipGetLastError());
-        AOS2_HIP_CHECK(hipStreamSynchronize(q));
-        AOS2_HIP_CHECK(hipMemcpy(host.data(), base, A.bytes, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nw; ++i) {
-            const aos2_lba_problem_t &p = problems[i];
-            const Pass &S = passes[i];
-            const WinLayout &l = A.L[i];
-            aos2_lba_trial_snap_t &o = out[i].snap[k];
-            const uint8_t *h = host.data();
-            const size_t NP = p.n_poses, NL = p.n_points, E = p.n_edges, np = S.np, nl = S.nl, est = 8 * (7 * NP + 3 * NL);
-            auto put = [&](void *dst, size_t off, size_t bytes) {
-                if (dst && bytes) memcpy(dst, h + off, bytes);
-            };
-            o.taken = 1;
-            const LmState *ls = (const LmState *)(h + l.st);
-            aos2_lba_lm_state_t &t = o.st;
-            t.lambda = ls->lambda; t.ni = ls->ni; t.currentChi = ls->currentChi; t.iniChi = ls->iniChi;
-            t.final_chi2 = ls->final_chi2; t.final_lambda = ls->final_lambda;
-            t.phase = ls->phase; t.run = ls->run; t.lin = ls->lin; t.initp = ls->initp; t.xmark = ls->xmark;
-            t.it = ls->it; t.qmax = ls->qmax; t.nBad = ls->nBad;
-            for (int j = 0; j < 2; ++j) {
-                t.iters_done[j] = ls->iters_done[j];
-                t.trials[j] = ls->trials[j];
-            }
-            t.polls = ls->polls; t.stop_poll = ls->stop_poll; t.n_active = ls->n_active; t.solver_failed = ls->solver_failed;
-            t.err_at = ls->err_at; t.ntr = ls->ntr;
-            memcpy(t.tr_rho, ls->tr_rho, sizeof t.tr_rho); memcpy(t.tr_temp, ls->tr_temp, sizeof t.tr_temp);
-            memcpy(t.tr_cur, ls->tr_cur, sizeof t.tr_cur); memcpy(t.tr_lambda, ls->tr_lambda, sizeof t.tr_lambda);
-            o.scal3 = ((const double *)(h + l.scal))[3];
-            put(o.est, l.est, est); put(o.bk, l.bk, est);
-            put(o.x, l.x, 8 * (6 * np + 3 * nl)); put(o.b, l.b, 8 * (6 * np + 3 * nl));
-            put(o.Hll, l.Hll, 72 * nl); put(o.Rl, l.Rl, 72 * np); put(o.tmp, l.tmp, 48 * np); put(o.part, l.part, 16 * nl);
-            put(o.e_level1, l.level1, E); put(o.e_robust, l.robust, E);
-            put(o.err, l.err, 24 * E); put(o.lrec, l.lrec, 32 * S.pl_k.size());
-            if (o.erec_flags)
-                for (size_t a = 0; a < E; ++a) o.erec_flags[a] = ((const EdgeRec *)(h + l.erec))[a].flags;
-            put(o.out_Tcw, l.out_Tcw, 64 * NP); put(o.out_xyz, l.out_xyz, 12 * NL);
-            put(o.out_chi2, l.out_chi2, 8 * E); put(o.out_outlier, l.out_outlier, E);
-        }
-        return AOS2_OK;
-    };
-    const LbaWin *dw = (const LbaWin *)(base + A.o_wins);
-    LaunchCtx C{s, walk, false};
-    const Prog P = make_prog(dw, dw, nw, U.TL[0], U.dt[0], U.gd[0], group_streams(s, 0));
-    static const double zero = 0.0;
-    enqueue_prepare(C, P);
-    enqueue_init(C, P);
-    for (int i = 0; i < nw; ++i)
-        if (lambda && lambda[i] > 0) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].st + offsetof(LmState, lambda), lambda + i, 8, hipMemcpyHostToDevice, q));
-    // The second optimisation starts where the solve's programs start it: behind iters_first trials when every step was accepted
-    // (enqueue_program), behind whichever later trial ends the first optimisation otherwise (continuation_round) -- both launches are
-    // gated by the state (xmark, initp), so they are enqueued before every trial from there on
-    auto between = [&](int t) {
-        if (t < U.max_i1) return;
-        enqueue_transition(P);
-        enqueue_init(C, P);
-    };
-    for (int t = 0; t < trials_before; ++t) {
-        between(t);
-        enqueue_trial(C, P, true);
-    }
-    between(trials_before);
-    enqueue_reduced(C, P, true);
-    for (int i = 0; i < nw; ++i)
-        if (force_solver_failed && force_solver_failed[i]) AOS2_HIP_CHECK(hipMemcpyAsync(base + A.L[i].scal + 24, &zero, 8, hipMemcpyHostToDevice, q));
-    if ((st = snapshot(0))) return st;
-    enqueue_points(C, P, 1);
-    if ((st = snapshot(1))) return st;
-    enqueue_lin(C, P, 0);
-    if ((st = snapshot(2))) return st;
-    if (tail >= 1) {
-        enqueue_transition(P);
-        if ((st = snapshot(3))) return st;
-    }
-    if (tail == 2) {
-        enqueue_final(P);
-        if ((st = snapshot(4))) return st;
-    }
-    return AOS2_OK;
-}
-
-}  // extern "C"

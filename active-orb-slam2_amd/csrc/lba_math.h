@@ -1,4 +1,4 @@
-// Shared pieces of the two Optimizer translation units (lba.hip: LocalBundleAdjustment, pose_opt.hip:
+// Shared pieces of the Optimizer translation units (lba.hip / lba_solve.hip: LocalBundleAdjustment, pose_opt.hip:
 // PoseOptimization): SE3 / quaternion arithmetic exactly as g2o + Eigen perform it (se3quat.h, Eigen Quaternion),
 // the Huber kernel, the float32 <-> SE3Quat converters of src/Converter.cc, and the handle both entry points share.
 #pragma once
@@ -331,7 +331,7 @@ __host__ __device__ inline void pose_to_Tcw(const double qt[7], float *T)
 
 }  // namespace aos2
 
-// Handle shared by aos2_lba_solve* (lba.hip) and aos2_pose_optimization (pose_opt.hip): device, stream, arenas.
+// Handle shared by aos2_lba_solve* (lba_solve.hip) and aos2_pose_optimization (pose_opt.hip): device, stream, arenas.
 struct aos2_lba {
     int device;
     bool dev_ready = false;
@@ -339,7 +339,7 @@ struct aos2_lba {
     hipEvent_t ev[3] = {};   // [0], [1]: device time of a call; [2]: spare
     hipStream_t stream2 = nullptr;      // LocalBA: the register form of the reduced-system kernel runs here beside the device-memory form
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // LocalBA: a batch of many windows runs as TWO groups whose programs are staggered on their own streams (lba.hip, solve_batch)
+    // LocalBA: a batch of many windows runs as TWO groups whose programs are staggered on their own streams (lba_solve.hip, solve_batch)
     hipStream_t stream_b = nullptr, stream2_b = nullptr;
     hipEvent_t ev_fork_b = nullptr, ev_join_b = nullptr, ev_up = nullptr, ev_stag = nullptr, ev_done_b = nullptr;
     int window_groups = 0;              // LocalBA: 0 = default (two groups for batches of >= 16 windows), 1 / 2 (aos2_lba_set_window_groups)
@@ -356,7 +356,7 @@ struct aos2_lba {
     bool gba_profile = false;           // ... with events around every family of launches (aos2_debug_global_ba_profile)
     float gba_family_ms[6] = {};
     int debug_stop_at_poll = 0;         // test hook: treat pbStopFlag as set from this poll on (0 = off)
-    void *lba_cache = nullptr;          // LocalBA: host-side structure buffers kept between calls (lba.hip: LbaCache)
+    void *lba_cache = nullptr;          // LocalBA: host-side structure buffers kept between calls (lba_solve.h: LbaCache)
     int host_threads = 0;               // LocalBA: worker threads of the per-window host work (0 = default, aos2_lba_set_host_threads)
     int last_trial_slots = 0, last_host_rounds = 0;   // the device program of the last solve (aos2_lba_last_program)
     long long last_window_slots = 0;                  // ... and its trial slots summed over the windows each round covered
@@ -364,7 +364,7 @@ struct aos2_lba {
 };
 
 namespace aos2 {
-// binds the device, creates the stream / events on first use (lba.hip)
+// binds the device, creates the stream / events on first use (lba_solve.hip)
 int lba_handle_init(aos2_lba *s);
 
 // Device time per family of launches (aos2_debug_essential_graph_profile, aos2_debug_global_ba_profile): an event pair around

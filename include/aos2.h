@@ -1869,7 +1869,7 @@ typedef struct {
     int32_t n_bad, n_inliers;         /* out */
 } aos2_pose_pass_case_t;
 int aos2_debug_pose_pass_device(aos2_pose_pass_case_t *cases, int n_cases, int mode, int device);
-/* The two kernels that solve LocalBA's reduced camera system (csrc/lba.hip: k_ldlt_reg, k_ldlt_dev), alone, with their epilogue: n_cases
+/* The two kernels that solve LocalBA's reduced camera system (csrc/lba.hip: k_ldlt_reg, k_ldlt_dev; this tap and the two below: csrc/lba_taps.hip), alone, with their epilogue: n_cases
  * independent systems H x = bs in ONE launch of each kernel, sized and launched like a Levenberg-Marquardt trial's.  Case c: np[c] free
  * keyframes, n = 6 np[c]; form[c] = 2: k_ldlt_reg (np <= 40), 0: k_ldlt_dev (np <= 154); H: n x n, both triangles (the tap pads it the
  * way the Schur kernel leaves it); the cases' H, bs, b_pose (n each), T (7 per pose: qx qy qz qw tx ty tz) back to back; lambda[c].
@@ -1881,7 +1881,8 @@ int aos2_debug_lba_reduced_solve_device(int n_cases, const int32_t *np, const in
                                         double *T_backup, double *scale_terms, uint8_t *ok, int device);
 
 /* The reduced camera system of a LocalBA trial as the shipped kernels assemble it (csrc/lba.hip: k_lin, k_lm_init, k_schur), read before
- * anything solves it.  The host phase is aos2_lba_solve_batch's, the kernels are enqueued through its helpers, all windows as one group.
+ * anything solves it.  The host phase is aos2_lba_solve_batch's (csrc/lba_solve.h: build_and_upload), the kernels are enqueued through its
+ * helpers (csrc/lba_launch.h), all windows as one group.
  * layout: 0 = slots (k_lin<false> + k_points), 1 = walk (k_lin<true> + k_points_walk) -- as given, whatever the batch size or AOS2_LBA_LAYOUT.
  * stage 0: k_prepare, the start of the first optimisation (residual pass, k_lin with init = 1, k_lm_init), one k_schur.
  * stage 1: the program of aos2_lba_solve_batch for iters_first trials of the first optimisation, k_transition, the start of the second
@@ -1913,7 +1914,7 @@ int aos2_debug_lba_assemble_device(aos2_lba_t *s, const aos2_lba_problem_t *prob
 
 /* The landmark half of a LocalBA trial and the Levenberg-Marquardt decision, read between the shipped launches (csrc/lba.hip: k_points /
  * k_points_walk with solve = 1 and lm_decide in its last workgroup, k_lin with init = 0, k_transition, k_final).  Host phase, helpers,
- * layout and lambda as in aos2_debug_lba_assemble_device; all windows as one group; aos2_lba_debug_stop_at_poll applies.  Sequence:
+ * layout and lambda as in aos2_debug_lba_assemble_device (the two share their preamble, tap_setup of csrc/lba_taps.hip); all windows as one group; aos2_lba_debug_stop_at_poll applies.  Sequence:
  *   k_prepare, the start of the first optimisation, [lambda], trials_before whole trials as the solve enqueues them (k_transition and
  *   the start of the second optimisation before every trial from the iters_first-th on: both are gated by the state),
  *   k_schur + the reduced solve of the trial under test, [scal[3] = 0.0 where force_solver_failed[w]]   -> snapshot 0 (A)

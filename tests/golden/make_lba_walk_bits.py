@@ -25,7 +25,7 @@ DEGREES = (1, 4, 5, 6, 7, 8, 9, 12, 13)
 FREE_DEGREES = (0, 1, 4, 5, 8, 9)
 # The big window: the keyframe state a landmark workgroup of the walks stages in LDS is the window's poses (7 doubles each) and, in a
 # trial, the update x (6 doubles) and the linearisation's rotation (9 doubles) of every free keyframe: 56 n_poses + 120 n_free bytes
-# (walk_lds_bytes, lba.hip).  With 2 free keyframes that exceeds the 16 KB budget from (16384 - 240) / 56 = 288.3, i.e. 289 keyframes,
+# (walk_lds_bytes, lba_window.h).  With 2 free keyframes that exceeds the 16 KB budget from (16384 - 240) / 56 = 288.3, i.e. 289 keyframes,
 # on: such a window reads device memory, beside the small windows of the same launch that read LDS.
 BIG_FIXED = 300
 _cache = {}

@@ -229,7 +229,7 @@ LAMBDA_POW_BOUND = 10 * 2.0 ** -53
 def decide(state, tempChi, scale, ok, flag_seen, iters_max=(5, 10), stop_at_poll=0):
     """The end of one pass of the do-while of OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:123-149), what
     follows it when the loop ends (:151-163), the loop condition of SparseOptimizer::optimize (sparse_optimizer.cpp:376) and, when the
-    first optimize() returns, Optimizer.cc:663-667 -- on the state record the device keeps (LmState of lba.hip: the members of the g2o
+    first optimize() returns, Optimizer.cc:663-667 -- on the state record the device keeps (LmState of lba_window.h: the members of the g2o
     objects plus where the program stands).  state: the record before (snapshot A); tempChi = activeRobustChi2() at the trial's
     estimates; scale = computeScale() (the 1e-3 is added here); ok = the linear solve succeeded; flag_seen = *pbStopFlag.
     -> the record after (plus `pow_used`, see below), and `restored` (pop() ran).  The traces get one more entry (the device records rho = -1 for a failed solve,

@@ -70,7 +70,7 @@ def test_the_windows_are_what_they_are_meant_to_be(wins, want):
     assert any(lt[i + 1] > lt[i] for i in range(len(lt) - 1) if i + 1 != n1)
     r = want["rejected_repeated"]
     assert r["trials"] > sum(r["iters"])
-    # 5: more keyframes than the 16 KB LDS copy of a window's keyframe state holds (walk_lds_bytes, lba.hip): the device-memory path
+    # 5: more keyframes than the 16 KB LDS copy of a window's keyframe state holds (walk_lds_bytes, lba_window.h): the device-memory path
     w = wins["big"]
     n_free = int((np.asarray(w["pose_fixed"]) == 0).sum())
     assert n_free == 2 and 56 * w["n_poses"] + 120 * n_free > 16 * 1024 and w["n_edges"] < 3000

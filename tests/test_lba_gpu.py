@@ -603,7 +603,7 @@ def test_lba_continuation_lists_larger_than_the_first_rounds(pkg, gpu, groups):
     """with two window groups and 8-15 windows a group has fewer than 8 windows, so the first round's Schur list is NOT
     padded to 8 queues -- the continuation round on >= 8 unfinished windows is (NX = 8, each queue as long as the longest: one
     40-keyframe window among 10-keyframe ones), i.e. LONGER than anything the first round built.  The continuation region is sized
-    for any subset (lba.hip "Sized for ANY subset"): the batch solves, every window gives the bits it gives alone.  (Seeds whose
+    for any subset (lba_plan.h "Sized for ANY subset"): the batch solves, every window gives the bits it gives alone.  (Seeds whose
     oracle runs reject steps: more trials than iterations.)"""
     S = pkg.synth
     small = lambda seed, pert: S.perturb_lba_problem(S.synth_lba_problem(seed, n_local=10, n_fixed=4, n_points=260, obs_per_point=4, stereo_frac=0.3), seed, *pert)  # noqa: E731

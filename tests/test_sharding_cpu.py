@@ -116,7 +116,7 @@ def _host_phase_worker(rank, threads, barrier, q):
 
 def test_lba_host_phase_of_eight_ranks_shares_the_cores(pkg):
     """8 ranks' LocalBA handles build their windows' index structures at the same time.  Every rank caps its
-    worker pool at cores / ranks (lba.hip: lba_host_threads; bench.py passes cores / (ranks x handles)), so 8 processes running the
+    worker pool at cores / ranks (lba_solve.hip: lba_host_threads; bench.py passes cores / (ranks x handles)), so 8 processes running the
     host part of a batch concurrently must not take much longer than one process alone with the same number of threads (an
     oversubscribed node -- 8 x 2 x 32 threads on the cores of one rank -- would)."""
     ranks, n_win = 8, 6
