@@ -58,11 +58,8 @@ def _native_unfilter():
     if os.environ.get("AOS2_PNG_PYTHON") == "1":
         return None
     try:
-        import ctypes as C
         from . import capi
-        fn = capi.lib().aos2_png_unfilter
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        return fn
+        return capi.lib().aos2_png_unfilter
     except Exception:   # no library / an older one: the pure-Python path below
         return None
 

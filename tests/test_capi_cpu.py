@@ -135,7 +135,6 @@ def test_bad_arguments_and_missing_device(pkg):
         ex(np.zeros((480, 640), np.float32))
     # aos2_device_local_cpus: argument checks need no device; without one the call says so and bind_to_device_node changes nothing
     L = capi.lib()
-    L.aos2_device_local_cpus.argtypes = [capi.C.c_int, capi.C.c_char_p, capi.C.c_int]
     assert L.aos2_device_local_cpus(0, None, 16) == capi.AOS2_ERR_ARG
     if pkg.device_count() == 0:
         import os

@@ -225,7 +225,7 @@ def test_argument_errors_are_refused_with_no_byte_written(pkg):
         with pytest.raises(pkg.AosError) as e:
             capi.debug_initializer_host([good, bad, good], sentinel=0x5A)
         assert e.value.code == capi.AOS2_ERR_ARG
-        Rc, outs, before = capi.init_last
+        Rc, outs, before = capi.debug_initializer_host.last
         for k in range(3):
             assert bytes(Rc[k]) == before[k]
             assert all((a.view(np.uint8) == 0x5A).all() for a in outs[k])
