@@ -19,7 +19,7 @@ from .extractor import *  # noqa: F401,F403
 from .frames import *  # noqa: F401,F403
 from .kfdb import *  # noqa: F401,F403
 from .local_map import *  # noqa: F401,F403
-from .local_map import _local_map_delta, _local_map_graph  # noqa: F401
+from .local_map import _kf_culling_view, _local_map_delta, _local_map_graph, _normal_depth_args  # noqa: F401
 from .matcher import *  # noqa: F401,F403
 from .optimisers import *  # noqa: F401,F403
 from .optimisers import _GBA_SENTINEL_INT, _essential_graph_args, _sim3_opt_args, _sim3_opt_steps_args  # noqa: F401

@@ -25,6 +25,8 @@ AOS2_INIT_OK, AOS2_INIT_NO_MODEL = _mirror("AOS2_INIT_", ("OK", "NO_MODEL"))
 AOS2_EG_OK, AOS2_EG_NO_STEP, AOS2_ERR_EG_MEMORY = _mirror("AOS2_", ("EG_OK", "EG_NO_STEP", "ERR_EG_MEMORY"), (0, 1, -6))
 KFC_KEPT, KFC_CULLED, KFC_DEFERRED, KFC_SKIPPED = _mirror("AOS2_KFC_", ("KEPT", "CULLED", "DEFERRED", "SKIPPED"))
 (CONNECTIONS_TH,) = _mirror("AOS2_", ("CONNECTIONS_TH",), (15,))
+ND_UPDATED, ND_BAD, ND_NO_OBS, ND_UNKNOWN, ND_REF_UNUSABLE = _mirror("AOS2_ND_", ("UPDATED", "BAD", "NO_OBS", "UNKNOWN", "REF_UNUSABLE"))
+ND_ROWS_PLANNING, ND_ROWS_TRACKING = _mirror("AOS2_ND_ROWS_", ("PLANNING", "TRACKING"))
 TRI_NO_MATCH, TRI_ACCEPTED, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_DEPTH1, TRI_DEPTH2, TRI_REPROJ1, TRI_REPROJ2, TRI_ZERO_DIST, TRI_SCALE, \
     TRI_SUPERSEDED = _mirror("AOS2_TRI_", ("NO_MATCH", "ACCEPTED", "LOW_PARALLAX", "W_ZERO", "DEPTH1", "DEPTH2", "REPROJ1", "REPROJ2",
                                            "ZERO_DIST", "SCALE", "SUPERSEDED"))
@@ -255,6 +257,19 @@ _LocalMapDelta = _struct("aos2_local_map_delta_t",
     ("n_kf_link_rows", C.c_int32), ("kf_link_row", C.c_void_p), ("kf_bad", C.c_void_p), ("kf_best", C.c_void_p),
     ("kf_child_off", C.c_void_p), ("kf_child", C.c_void_p), ("kf_parent", C.c_void_p), ("view", C.c_void_p)])
 
+# the arrays of an aos2_normal_depth_t: field -> (dtype, elements per listed point; None: per observation slot)
+_ND_INPUTS = (("point", np.int32), ("xyz", np.float32), ("ref_kf", np.int32), ("kf_center", np.float32), ("scale", np.float32),
+              ("term_off", np.int32))
+_ND_OUTPUTS = (("status", np.uint8, 1), ("normal", np.float32, 3), ("min_dist", np.float32, 1), ("max_dist", np.float32, 1),
+               ("theta_mean", np.float32, 1), ("theta_std", np.float32, 1), ("n_terms", np.int32, 1), ("upper", np.float32, 1),
+               ("lower", np.float32, 1), ("max_range", np.float32, 1), ("min_range", np.float32, 1), ("term_unit", np.float32, None),
+               ("term_theta", np.float32, None))
+
+_NormalDepth = _struct("aos2_normal_depth_t",
+    [("n", C.c_int32), ("point", C.c_void_p), ("xyz", C.c_void_p), ("ref_kf", C.c_void_p), ("kf_center", C.c_void_p),
+    ("n_levels", C.c_int32), ("scale", C.c_void_p), ("rows_form", C.c_int32), ("term_off", C.c_void_p)] +
+    [(k, C.c_void_p) for k, _, _ in _ND_OUTPUTS])
+
 _Sim3OptSteps = _struct("aos2_sim3_opt_steps_t",
     [("problem", _Sim3OptProblem), ("S_lin", C.c_double * 8), ("S_trial", C.c_double * 8)] +
     [(k, C.c_void_p) for k in ("act_in", "chi_in", "outlier_in")] + [(k, C.c_int32) for k in ("tail", "remove", "mask", "pad")] +
@@ -442,7 +457,7 @@ PROTOTYPES = {
     "aos2_lba_solve": (ci, [vp, vp, vp]),
     **_same((ci, [vp, ci]), "aos2_lba_debug_stop_at_poll", "aos2_lba_set_host_threads", "aos2_lba_set_window_groups",
             "aos2_debug_sim3_opt_steps_host", "aos2_local_map_debug_culling_rounds", "aos2_local_map_debug_connections_sort",
-            "aos2_local_map_debug_apply_tile", "aos2_frames_set_async_keyframe_calls"),
+            "aos2_local_map_debug_normal_depth", "aos2_local_map_debug_apply_tile", "aos2_frames_set_async_keyframe_calls"),
     "aos2_lba_last_program": (ci, [vp, vp, vp]),
     "aos2_lba_last_window_slots": (ci, [vp, C.POINTER(i64)]),
     "aos2_lba_debug_host_phase": (ci, [vp, ci, ci, vp, vp]),
@@ -490,7 +505,10 @@ PROTOTYPES = {
     "aos2_local_map_keyframe_culling": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
     "aos2_debug_keyframe_culling_host": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
     "aos2_local_map_get_culling_view": (ci, [vp, vp, vp]),
-    **_same((cf, [vp]), "aos2_local_map_last_culling_device_ms", "aos2_local_map_last_connections_device_ms"),
+    **_same((cf, [vp]), "aos2_local_map_last_culling_device_ms", "aos2_local_map_last_connections_device_ms",
+            "aos2_local_map_last_normal_depth_device_ms"),
+    "aos2_local_map_update_normal_depth": (ci, [vp, vp]),
+    "aos2_debug_update_normal_depth_host": (ci, [vp, vp, vp]),
     **_same((ci, [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci]), "aos2_local_map_update_connections",
             "aos2_debug_update_connections_host"),
     "aos2_local_map_last_apply": (ci, [vp, vp, vp, vp]),

@@ -1,12 +1,13 @@
-"""The resident covisibility graph: Tracking::UpdateLocalMap, KeyFrameCulling, UpdateConnections and the application of one
-keyframe's changes (include/aos2.h: aos2_local_map_*, aos2_frames_update_local_map and their host taps)."""
+"""The resident covisibility graph: Tracking::UpdateLocalMap, KeyFrameCulling, UpdateConnections, UpdateNormalAndDepth and the
+application of one keyframe's changes (include/aos2.h: aos2_local_map_*, aos2_frames_update_local_map and their host taps)."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AOS2_OK, CONNECTIONS_TH, _KFC_FIELDS, _KfCullingView, _LocalMapDelta, _LocalMapGraph
+from ._abi import (AOS2_OK, CONNECTIONS_TH, ND_ROWS_PLANNING, _KFC_FIELDS, _ND_INPUTS, _ND_OUTPUTS, _KfCullingView, _LocalMapDelta,
+                   _LocalMapGraph, _NormalDepth)
 from ._core import _Handle, _check, _p, lib
 
 
@@ -98,6 +99,44 @@ def _update_connections_call(fn, first, th, kf, mp, conn_cap, ordered_cap, mp_ca
     out = dict(n_conn=flat["n_conn"][:n], n_ordered=flat["n_ordered"][:n], guard={k: int(a[-1]) for k, a in flat.items()})
     for k, c in (("conn_kf", conn_cap), ("conn_w", conn_cap), ("ordered_kf", ordered_cap), ("ordered_w", ordered_cap)):
         out[k] = flat[k][:n * c].reshape(n, c)
+    return out
+
+
+def _normal_depth_args(point, xyz, ref_kf, kf_center, scale, rows_form=ND_ROWS_PLANNING, term_off=None, want=None, n=None, n_levels=None,
+                       null=()):
+    """an aos2_normal_depth_t, which aos2_local_map_update_normal_depth and its host tap share -> (the struct, what keeps its input
+    arrays alive, the output arrays by name, each with one guard element behind it).  point int32 [n], xyz float32 [n][3], ref_kf int32
+    [n], kf_center float32 [n_keyframes][3], scale float32 [n_levels], term_off int32 [n + 1] or None.  want: the outputs that are
+    asked for (default: all of them, the per-observation ones only with term_off); the others go in as NULL.  n / n_levels override
+    the counts and `null` names input fields that go in as NULL whatever was passed (what the argument checks are tried with).
+    The outputs are [n] or [n][3] or per observation slot, PRESET to a sentinel -- status 255, n_terms -7, the floats -7.0 -- so that
+    what the call leaves untouched shows; the call's dict holds them without their guard elements, which are in `guard`."""
+    ins = dict(point=point, xyz=xyz, ref_kf=ref_kf, kf_center=kf_center, scale=scale, term_off=term_off)
+    s, keep = _NormalDepth(), [np.zeros(1, np.int32)]
+    for k, dt in _ND_INPUTS:
+        ins[k] = None if ins[k] is None else np.ascontiguousarray(ins[k], dt).reshape(-1)
+    count = (0 if ins["point"] is None else len(ins["point"])) if n is None else int(n)
+    s.n, s.rows_form = count, int(rows_form)
+    s.n_levels = (0 if ins["scale"] is None else len(ins["scale"])) if n_levels is None else int(n_levels)
+    _set_arrays(s, {k: None if k in null else a for k, a in ins.items()}, _ND_INPUTS, keep)
+    slots = int(ins["term_off"][-1]) if ins["term_off"] is not None and len(ins["term_off"]) else 0
+    want = [k for k, _, per in _ND_OUTPUTS if per is not None or term_off is not None] if want is None else list(want)
+    flat = {}
+    for k, dt, per in _ND_OUTPUTS:
+        if k in want:
+            size = max(count, 0) * per if per is not None else max(slots, 0) * (3 if k == "term_unit" else 1)
+            flat[k] = np.full(size + 1, 255 if dt == np.uint8 else -7, dt)
+            setattr(s, k, flat[k].ctypes.data)
+    return s, keep, flat
+
+
+def _update_normal_depth_call(fn, first, *args, **kw):
+    """one call with the arguments of _normal_depth_args -> its dict of outputs"""
+    s, keep, flat = _normal_depth_args(*args, **kw)
+    _check(fn(*first, C.byref(s)))
+    out = dict(guard={k: a[-1] for k, a in flat.items()})
+    for k, a in flat.items():
+        out[k] = a[:-1].reshape(-1, 3) if k in ("normal", "term_unit") else a[:-1]
     return out
 
 
@@ -243,6 +282,25 @@ class LocalMap(_Handle):
 
     def last_connections_device_ms(self):
         return float(self.L.aos2_local_map_last_connections_device_ms(self.h))
+
+    def update_normal_depth(self, point, xyz, ref_kf, kf_center, scale, **kw):
+        """aos2_local_map_update_normal_depth (MapPoint::UpdateNormalAndDepth, src/MapPoint.cc:363-413) on the device; the keywords
+        and the result are those of _update_normal_depth_call"""
+        return _update_normal_depth_call(self.L.aos2_local_map_update_normal_depth, (self.h,), point, xyz, ref_kf, kf_center, scale, **kw)
+
+    @staticmethod
+    def update_normal_depth_host(graph, view, point, xyz, ref_kf, kf_center, scale, **kw):
+        """aos2_debug_update_normal_depth_host: the same function on one core, no device"""
+        keep = [np.zeros(1, np.int32)]
+        g, v = _local_map_graph(graph, keep), _kf_culling_view(view, keep)
+        return _update_normal_depth_call(lib().aos2_debug_update_normal_depth_host, (C.byref(g), C.byref(v)), point, xyz, ref_kf,
+                                         kf_center, scale, **kw)
+
+    def debug_normal_depth(self, lds_terms=-1):
+        _check(self.L.aos2_local_map_debug_normal_depth(self.h, int(lds_terms)))
+
+    def last_normal_depth_device_ms(self):
+        return float(self.L.aos2_local_map_last_normal_depth_device_ms(self.h))
 
     def update_host(self, n, mp, local_cap, kf_cap, local_kfs=None, n_local_kfs=None, ref_kf=None):
         """aos2_local_map_update: the device kernels on host arrays, arguments and result as host()"""

@@ -16,6 +16,7 @@
 #include "connections.h"
 #include "local_map.h"
 #include "motion_tw.h"
+#include "normal_depth.h"
 #include "wave_ops.h"
 
 namespace aos2 {
@@ -692,6 +693,22 @@ int aos2_debug_update_connections_host(const aos2_local_map_graph_t *g, int th, 
     if (conn_check(A, g->n_keyframes, why, sizeof why)) return lm_fail("update connections", "%s", why);
     const LmGraph G = {{g->n_points, g->n_keyframes}, lm_from_public(*g, nullptr)};
     conn_host_run(G, A);
+    return AOS2_OK;
+}
+
+// MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:363-413): the serial loop of csrc/normal_depth.h over a host graph and view, with
+// the checks of the device call
+int aos2_debug_update_normal_depth_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view,
+                                        const aos2_normal_depth_t *a)
+{
+    using namespace aos2;
+    if (int st = local_map_check(g, nullptr)) return st;
+    if (int st = kf_culling_check_view(g, view)) return st;
+    if (!a) return lm_fail("update normal and depth", "the arguments are NULL");
+    char why[200];
+    if (nd_check(*a, g->n_keyframes, why, sizeof why)) return lm_fail("update normal and depth", "%s", why);
+    const LmGraph G = {{g->n_points, g->n_keyframes}, lm_from_public(*g, view)};
+    nd_host_run(G, *a);
     return AOS2_OK;
 }
 

@@ -1,8 +1,8 @@
 // Tracking::UpdateLocalMap (src/Tracking.cc:1375-1519) for frame batches: what csrc/local_map.hip shares with the host tap
 // aos2_debug_local_map_host (csrc/debug_taps.hip), and the handle itself, which csrc/kf_culling.hip extends with the view and the
-// scratch of LocalMapping::KeyFrameCulling and csrc/local_map_apply.hip rebuilds.  The resident arrays are those of
-// csrc/local_map_arrays.h.  Internal to the library; the public entry points are aos2_local_map_* and
-// aos2_frames_update_local_map / aos2_frames_track_local_map_stats of include/aos2.h.
+// scratch of LocalMapping::KeyFrameCulling, csrc/connections.hip and csrc/normal_depth.hip with the state of their calls, and
+// csrc/local_map_apply.hip rebuilds.  The resident arrays are those of csrc/local_map_arrays.h.  Internal to the library; the
+// public entry points are aos2_local_map_* and aos2_frames_update_local_map / aos2_frames_track_local_map_stats of include/aos2.h.
 #pragma once
 #include <vector>
 
@@ -132,6 +132,20 @@ struct ConnState {
     }
 };
 
+// what is specific to aos2_local_map_update_normal_depth (csrc/normal_depth.hip): the device block of one call's arguments and
+// results, its page-locked staging, the switch between the two places where the thetas wait
+struct NdState {
+    DevBuf<uint8_t> d_io;
+    PinnedBuf<uint8_t> io;
+    int lds_terms = -1;   // observation lists up to this length keep their thetas in LDS, < 0 = the default
+    EventTimer timer;     // around the last call's device work
+    ~NdState()
+    {
+        d_io.release();
+        io.release();
+    }
+};
+
 }  // namespace aos2
 
 struct aos2_local_map {
@@ -152,6 +166,7 @@ struct aos2_local_map {
     bool has_graph = false;   // aos2_local_map_set has been called
     aos2::KfcState kfc;
     aos2::ConnState conn;
+    aos2::NdState nd;
     // aos2_local_map_apply (csrc/local_map_apply.hip).  Always current on the host, each kept in O(delta): the counts above and
     // max_features, the entries of the three CSR arrays, and the length of every row (row_feat is Frame::N of each keyframe, the
     // bound of obs_idx).  M is the MIRROR: after a rebuild on the device it is stale until local_map_refresh_host downloads the

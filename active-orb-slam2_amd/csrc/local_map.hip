@@ -384,6 +384,7 @@ void aos2_local_map_destroy(aos2_local_map_t *h)
         h->apply_timer.release();
         h->kfc.timer.release();
         h->conn.timer.release();
+        h->nd.timer.release();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;

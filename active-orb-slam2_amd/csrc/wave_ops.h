@@ -225,6 +225,52 @@ __device__ __forceinline__ void row_scatter_store(const double (&v)[N], double *
     }
 }
 
+// ---- groups of 8 lanes (group g = lanes 8 g .. 8 g + 7, half a row; li = lane & 7)
+// v of the lane in front (lane - 1): row_shr:1.  Lane 0 of a row has no source and gets 0; li == 0 never uses what it gets.
+__device__ __forceinline__ float group8_prev(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));
+}
+__device__ __forceinline__ double group8_prev(double v) { return dpp_f64<0x111>(v); }
+// v of lane 7 of the group in every lane of the group: quad_perm [3,3,3,3] puts lane 3 / lane 7 into every lane of its quad, then
+// row_shl:4 into banks 0 and 2 hands the upper quad's value to the lower one
+__device__ __forceinline__ int group8_last_i32(int v)
+{
+    const int q = __builtin_amdgcn_update_dpp(0, v, 0xFF, 0xf, 0xf, true);
+    return __builtin_amdgcn_update_dpp(q, q, 0x104, 0xf, 0x5, false);
+}
+__device__ __forceinline__ float group8_last(float v) { return __int_as_float(group8_last_i32(__float_as_int(v))); }
+__device__ __forceinline__ double group8_last(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = group8_last_i32((int)b), hi = group8_last_i32((int)(b >> 32));
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// The ORDERED sum of a group: ((carry + v of lane 0) + v of lane 1) + ... over the first min(cnt, 8) lanes of the group, one add
+// after the other in lane order -- no tree, so the bits are those of a serial loop over the lanes.  carry and cnt are the same in
+// every lane of a group; the result is too.  The partial sum walks up the group: at step k lane k takes it from lane k - 1 and adds
+// its own value (or hands it on unchanged behind the count).  T = float or double.
+template <class T>
+__device__ __forceinline__ T group8_sum_ordered(T carry, T v, int cnt)
+{
+    const int li = threadIdx.x & 7;
+    T s = (li == 0 && cnt > 0) ? carry + v : carry;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        const T t = group8_prev(s);
+        s = li == k ? (k < cnt ? t + v : t) : s;
+    }
+    return group8_last(s);
+}
+// every lane: the max over its group of 8
+__device__ __forceinline__ int group8_max_i32(int v)
+{
+    v = max(v, dpp_i32<0xB1>(v));
+    v = max(v, dpp_i32<0x4E>(v));
+    v = max(v, dpp_i32<0x141>(v));
+    return v;
+}
+
 __device__ __forceinline__ int wave_incl_scan_i32(int v)  // inclusive prefix sum over the lanes
 {
     int x = v;

@@ -1442,7 +1442,8 @@ int aos2_frames_track_local_map_stats(aos2_frames_t *f, const aos2_local_map_t *
 /* test hooks: the scratch bound in bytes (<= 0: the default, 256 MiB) and the largest n_keyframes whose vote counters live in
  * LDS (< 0: the default, 8192; 0: always global memory), so that both sides of either switch are reached with small graphs */
 int aos2_local_map_debug_limits(aos2_local_map_t *m, int64_t scratch_bytes, int lds_keyframes);
-/* groups the last aos2_frames_update_local_map or aos2_local_map_update_connections call ran its batch in */
+/* groups the last aos2_frames_update_local_map, aos2_local_map_update_connections or aos2_local_map_update_normal_depth call ran
+ * its batch in */
 int aos2_local_map_last_groups(const aos2_local_map_t *m);
 
 /* ------------------------------------------------------------------------------------------
@@ -1554,6 +1555,73 @@ float aos2_local_map_last_connections_device_ms(aos2_local_map_t *m);
 /* test hook: the longest ordered list that is sorted in LDS (<= 0: the default, 2048, which is also the most), so that the form
  * in global scratch is reached with small graphs */
 int aos2_local_map_debug_connections_sort(aos2_local_map_t *m, int lds_entries);
+
+/* ------------------------------------------------------------------------------------------
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:363-413 with compute_std_pts :27-37; called at LocalMapping.cc:156, :448, :531,
+ * Tracking.cc:628, :764, :1298, Optimizer.cc:227, :777, :1043, LoopClosing.cc:502) for a batch of points over the handle's resident
+ * observation lists (csrc/normal_depth.hip): mNormalVector, mfMinDistance, mfMaxDistance, theta_mean and theta_std, the
+ * per-observation mNormalVectors / theta_sVector, and the planner's map rows that Planning.cc:86-96 and Tracking.cc:1088-1112 derive
+ * from them.  The observers and their feature indices are the resident obs_kf rows and the culling view's obs_idx / kf_octave;
+ * the geometry (point positions, camera centres, the scale table) comes in with the call.  The resident graph is READ, never written.
+ *
+ * Conventions (parity unpinned: the cv::Mat expressions are restated as OpenCV 3.2's plain path):
+ * the observers are taken in the STORED order of the point's observation row (the host class stores ascending keyframe row, which
+ * stands for pointer order as in items 18 and 20); every sum is folded in that order, one add after the other.  Per observation k:
+ * d = P - O_k in float; nrm = sqrt(((double)d0 d0 + (double)d1 d1) + (double)d2 d2) in double (cv::norm); u = d * (float)(1.0 / nrm);
+ * normal += u in float from 0; theta = (float)atan2((double)d0, (double)d2).  Behind the loop, n = the length of the list:
+ * mNormalVector = normal * (float)(1.0 / (double)n); dist = (float)nrm over P - O_ref; level = kf_octave of feature
+ * observations[pRefKF] of the reference keyframe (feature 0 if it does not observe the point: what map::operator[] yields);
+ * mfMaxDistance = dist * scale[level]; mfMinDistance = mfMaxDistance / scale[n_levels - 1]; compute_std_pts literally: a double
+ * accumulator over the float thetas rounded to float, mean = sum / (float)n, a double accumulator over the FLOAT products
+ * (theta - mean)^2 rounded to float, std = sqrtf(sq / (float)n).  A point on a camera centre gives NaN where the reference does.
+ * ------------------------------------------------------------------------------------------ */
+#define AOS2_ND_UPDATED 0        /* the members were written */
+#define AOS2_ND_BAD 1            /* isBad(): the return at :371 */
+#define AOS2_ND_NO_OBS 2         /* no observation: the return at :378 */
+#define AOS2_ND_UNKNOWN 3        /* a point row >= n_points: a point the table does not know */
+#define AOS2_ND_REF_UNUSABLE 4   /* the reference keyframe has no feature, or the octave is outside [0, n_levels): the reference
+                                    reads out of bounds there */
+#define AOS2_ND_ROWS_PLANNING 0  /* Planning.cc:86-93: theta_interval is a float member, floor 30.0 / 57.3 */
+#define AOS2_ND_ROWS_TRACKING 1  /* Tracking.cc:1103-1110: theta_interval is a double local, floor 10.0 / 57.3 */
+/* One call's arguments, all HOST memory. */
+typedef struct {
+    int32_t n;
+    const int32_t *point;      /* [n]     the point rows; a row may repeat, a row >= n_points is skipped (AOS2_ND_UNKNOWN) */
+    const float *xyz;          /* [n][3]  mWorldPos of each listed point */
+    const int32_t *ref_kf;     /* [n]     the row of mpRefKF */
+    const float *kf_center;    /* [n_keyframes][3]  GetCameraCenter() of every keyframe row of the graph */
+    int32_t n_levels;
+    const float *scale;        /* [n_levels]  mvScaleFactors (one table for every keyframe) */
+    int32_t rows_form;         /* AOS2_ND_ROWS_* : the form of upper / lower */
+    const int32_t *term_off;   /* [n + 1] or NULL: where the per-observation outputs of each listed point go (CSR) */
+    /* outputs, each may be NULL = not wanted.  status is written for every listed point; every other output of a point whose
+     * status is not AOS2_ND_UPDATED is left untouched, as the reference leaves the members */
+    uint8_t *status;           /* [n]     AOS2_ND_* */
+    float *normal;             /* [n][3]  mNormalVector */
+    float *min_dist, *max_dist, *theta_mean, *theta_std;   /* [n] */
+    int32_t *n_terms;          /* [n]     the true length of the observation list */
+    float *upper, *lower;      /* [n]     theta_mean +- theta_interval in the form of rows_form */
+    float *max_range, *min_range;   /* [n]  GetMaxDistanceInvariance() = 1.2f max, GetMinDistanceInvariance() = 0.8f min */
+    /* mNormalVectors [term_off[n]][3] and theta_sVector [term_off[n]] in list order: written only for the points where
+     * term_off[i + 1] - term_off[i] equals the list length */
+    float *term_unit, *term_theta;
+} aos2_normal_depth_t;
+/* Runs on the handle's own stream, shares the handle's scratch with the other aos2_local_map_* calls (one call at a time) and
+ * returns when the results are complete.  n == 0 is valid.
+ * AOS2_ERR_ARG before a device is looked for: no graph set; no culling view set; a negative count; n_levels < 1; point, xyz,
+ * ref_kf, kf_center or scale NULL with a non-zero length; a ref_kf outside [0, n_keyframes); a point row < 0; term_off that does not
+ * start at 0 or that decreases; term_unit or term_theta without term_off; an unknown rows_form; ONE observation list whose thetas
+ * need more scratch than the bound of aos2_local_map_debug_limits (4 bytes per observation of a list longer than the LDS form
+ * holds: DESIGN.md section 5.17).  A batch runs in groups that fit that bound (aos2_local_map_last_groups counts them); the outputs
+ * do not depend on the grouping or on where the thetas wait between the two passes of compute_std_pts.  After an
+ * aos2_local_map_apply that ran on the device the call reads the new block.  Without a device: AOS2_ERR_NO_DEVICE. */
+int aos2_local_map_update_normal_depth(aos2_local_map_t *m, const aos2_normal_depth_t *a);
+/* device time of the last aos2_local_map_update_normal_depth call between two events on the handle's stream, from the upload of
+ * the arguments to the copy back; -1 if there was none (a call with n == 0 included) */
+float aos2_local_map_last_normal_depth_device_ms(aos2_local_map_t *m);
+/* test hook: the longest observation list whose thetas wait in LDS (< 0: the default, 64, which is also the most; 0: every list
+ * waits in global scratch), so that both forms and the groups are reached with small inputs */
+int aos2_local_map_debug_normal_depth(aos2_local_map_t *m, int lds_terms);
 
 /* ------------------------------------------------------------------------------------------
  * One keyframe's changes applied to the resident graph (csrc/local_map_apply.hip): what one pass of
@@ -1724,6 +1792,12 @@ int aos2_debug_keyframe_culling_host(const aos2_local_map_graph_t *g, const aos2
 int aos2_debug_update_connections_host(const aos2_local_map_graph_t *g, int th, int n, const int32_t *kf, const int32_t *n_mp,
                                        const int32_t *mp, int mp_cap, int32_t *n_conn, int32_t *conn_kf, int32_t *conn_w, int conn_cap,
                                        int32_t *n_ordered, int32_t *ordered_kf, int32_t *ordered_w, int ordered_cap);
+/* aos2_local_map_update_normal_depth on the HOST: the arithmetic the device kernel also runs (csrc/normal_depth.h), one point and
+ * one observation at a time on one core -- the one-core baseline and the tap the device is compared with.  The graph and the view
+ * are checked as aos2_local_map_set and aos2_local_map_set_culling_view check them, the other arguments as the device call checks
+ * them (the scratch bound aside); no device is needed. */
+int aos2_debug_update_normal_depth_host(const aos2_local_map_graph_t *g, const aos2_kf_culling_view_t *view,
+                                        const aos2_normal_depth_t *a);
 /* aos2_local_map_apply with the rebuild forced onto the HOST, also where the graph is resident: the same checks, the serial
  * restatement on the handle's host copy (refreshed first if it is stale), and the device copy of graph and view marked dirty, so
  * that the next consumer re-uploads everything.  The tap the device rebuild is compared with.  Returns as aos2_local_map_set. */
